@@ -14,9 +14,13 @@ samples (--scaling strong: BASELINE.json configs[3] = `--workload cfg3 --scaling
 per waypoint the moments of the whole batch (batch x 11 K doubles) are summed over ranks with ONE
 RCCL all-reduce.
 
-Timing: after the warm-up the K-step pass is repeated -- at least 10 times and for about a second
-of GPU time, each repeat bracketed by barrier + synchronize on both sides and taken as the MAX over ranks --
-and `ms_per_step` / `value` are the MEDIAN repeat's; min / max / repeats travel in `timing`.
+Timing: after the warm-up ONE pass of exactly K steps, bracketed by barrier + synchronize on both sides and
+taken as the MAX over ranks, gives `ms_per_step` / `value`.  With --full the K-step pass is
+repeated -- at least 10 times and for about a second of GPU time -- and `ms_per_step` / `value` are the MEDIAN
+repeat's; min / max / repeats travel in `timing`.  --full also adds what takes calls or runs of its own: the
+roofline, one run per call, the CPU baseline and, for N > 1, the strong-scaling record.
+
+--dump-outputs DIR writes what the last call of the (first) timed pass returned as DIR/<name>.npy.
 
 Prints ONE JSON line on rank 0 (fields: DESIGN.md section 7).
 """
@@ -155,6 +159,47 @@ def cpu_baseline(plan, env, K, W, path, budget_evals, budget_s=None):
         except (OSError, ValueError):
             out["host_cores"]["cgroup_cpu_limit"] = None
     return out
+
+
+DUMP_LIMIT_BYTES = 64 << 20     # --dump-outputs writes at most this much
+
+
+def last_outputs(ctx, path, K, prob):
+    """What the last timed call handed its caller, copied to the host (--dump-outputs), float64: the probability it
+    returned and, where that call was one context's (one GPU, or a connected context's whole call), its batch -- per
+    run the probability (GMM) or the collided count (MC), and for the GMM path every run's per-waypoint probabilities
+    and moments (W x K x 11).  Runs past the size limit are left out, the last ones first."""
+    import numpy as np
+    out = {"probability": np.array([prob], dtype=np.float64)}
+    if ctx is None:                                    # the per-waypoint sharded forms: the returned probability only
+        return out
+    if path != "gmm":
+        out["hit_counts"] = np.array(ctx.mc_batch_counts(), dtype=np.float64)
+        return out
+    runs = ctx.batch_probabilities()
+    out["batch_probabilities"] = np.asarray(runs, dtype=np.float64)
+    W = ctx.path_length()
+    per_run = 8 * W * (1 + K * 11)
+    keep = max(1, min(len(runs), (DUMP_LIMIT_BYTES - 8 * (len(runs) + 1)) // per_run))
+    wp, mom = [], []
+    for r in range(keep):
+        if len(runs) > 1:                              # (one run: the getters already show it)
+            ctx.select_batch_run(r)
+        wp.append(ctx.waypoint_probabilities())
+        mom.append([ctx.moments(w, K) for w in range(W)])
+    if len(runs) > 1:
+        ctx.select_batch_run(0)
+    out["waypoint_probabilities"] = np.asarray(wp, dtype=np.float64)          # [run][waypoint]
+    out["moments"] = np.asarray(mom, dtype=np.float64)                        # [run][waypoint][component][11]
+    return out
+
+
+def write_outputs(directory, outputs):
+    import numpy as np
+    d = Path(directory)
+    d.mkdir(parents=True, exist_ok=True)
+    for name, a in outputs.items():
+        np.save(d / (name + ".npy"), np.ascontiguousarray(a, dtype=np.float64))
 
 
 class BoardProbe:
@@ -372,6 +417,14 @@ def main():
                     help="N > 1: skip the short strong-scaling pass (cfg3 split over the ranks = BASELINE configs[3] at N = 8) "
                          "that the default weak line carries as `strong`")
     ap.add_argument("--cpu-evals", type=float, default=6.0e7, help="upper bound of the CPU baseline's sample (evaluations)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beside the headline figure: the median of >= 10 repeats of the timed pass, the roofline "
+                         "(its own profiled calls, the no-store variant, board clock, copy / fill ceilings), one run per call, "
+                         "the CPU baseline and, for N > 1, the strong-scaling record.  Without it: ONE pass of exactly "
+                         "`--steps` timed steps and the headline line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed call returned (probabilities per run and per "
+                         "waypoint, the GMM path's moments) as DIR/<name>.npy, float64; the same arguments give the same inputs")
     args = ap.parse_args()
     if args.gpus > 1 and "RANK" not in os.environ and "WORLD_SIZE" not in os.environ:
         raise SystemExit(spawn_ranks(args.gpus))          # this process never touches the GPU: it starts the ranks and relays
@@ -447,8 +500,9 @@ def main():
             xstate["mode"], xstate["note"] = "0", "one-hop probe failed on this node: fell back to RCCL"
     os.environ["POCS_ONEHOP"] = xstate["mode"]
 
-    def measure(workload, scaling, steps, warmup, batch_arg, samples, full):
-        """One workload through the timing protocol; full = the main record (roofline extras, single call, board)."""
+    def measure(workload, scaling, steps, warmup, batch_arg, samples, full, plain_repeats=1):
+        """One workload through the timing protocol; full = the main record of a --full run (the median of >= 10
+        repeats, roofline extras, single call, board); otherwise `plain_repeats` passes of the timed steps."""
         W, n_local, K, path = WORKLOADS[workload]
         if samples:
             n_local = samples
@@ -498,6 +552,7 @@ def main():
             return c, None
 
         onehop, run_onehop = False, None
+        last = {"ctx": None}                              # the context of the last call (its results: --dump-outputs)
         if not sharded or whole:
             # one GPU: each distinct batch size has its own context (and its own captured hipGraph)
             made = [make(b_hi, 0x5EED0001)]
@@ -520,6 +575,7 @@ def main():
                 for b in sizes:
                     c = made[0][0] if b == b_hi else made[1][0]
                     p = c.run_gmm_estimation() if path == "gmm" else c.run_simulation()
+                    last["ctx"] = c
                     if span["on"] and b == b_hi:
                         ms, n = c.kernel_time()
                         span["ms"] += ms
@@ -577,7 +633,7 @@ def main():
                     fence()
                     for c, _ in made:
                         c.close()
-                    return measure(workload, scaling, steps, warmup, batch_arg, samples, full)
+                    return measure(workload, scaling, steps, warmup, batch_arg, samples, full, plain_repeats)
                 xmode, onehop = "0", False
                 run_steps(warm)
         else:
@@ -600,17 +656,27 @@ def main():
         if plain:
             span["ms"], span["n"] = 0.0, 0             # (the warm-up's spans are not the timed region's)
         d0, prob = timed_pass()                        # (`probability` = the last run of the FIRST repeat: reproducible)
-        repeats = int(min(200, max(10, math.ceil(TIMED_TARGET_S / max(d0, 1e-6))))) if full else 3
+        # what the first pass's last call returned, read back before any further call (--dump-outputs): the same
+        # arguments give the same number of runs before it, hence the same seeds, however many repeats follow
+        outputs = last_outputs(last["ctx"], path, K, prob) if args.dump_outputs else None
+        repeats = int(min(200, max(10, math.ceil(TIMED_TARGET_S / max(d0, 1e-6))))) if full else plain_repeats
         dts = [d0] + [timed_pass()[0] for _ in range(repeats - 1)]
         dt = statistics.median(dts)
         evals = float(N) * W * steps
         res = {"workload": workload, "W": W, "K": K, "path": path, "n_local": n_local, "N": N, "batch": batch, "chunks": chunks,
                "prob": prob, "value": evals / dt, "ms_per_step": dt / steps * 1e3, "engines": len(engines) if engines else 1,
-               "xmode": xmode, "plan": plan,
+               "xmode": xmode, "plan": plan, "outputs": outputs,
                "timing": {"repeats": repeats, "ms_per_step_median": dt / steps * 1e3, "ms_per_step_min": min(dts) / steps * 1e3,
                           "ms_per_step_max": max(dts) / steps * 1e3, "timed_region_s": sum(dts),
                           "protocol": "each repeat = `steps` steps between barrier + synchronize on both sides, MAX over ranks; "
-                                      "value and ms_per_step are the median repeat's"}}
+                                      "value and ms_per_step are the median repeat's" + ("" if full else " (--full: >= 10 repeats)")}}
+
+        if not args.full:                                  # a plain run: the headline figure and nothing else
+            if dist is not None:
+                fence()
+            for c, _ in made:
+                c.close()
+            return res
 
         # roofline of the dominant kernel: further calls with the hot kernel bracketed by hipEvents on
         # the launch stream (eager launches; not part of `value`)
@@ -739,9 +805,9 @@ def main():
                         "(pocs_get_exchange_wait); a rank that runs ahead of the others waits here",
                 "status": "measured on this run's ranks" + (" -- ALL ON ONE CARD (rehearsal): unmeasured on hardware with more than one GPU" if "POCS_FORCE_DEVICE" in os.environ or world == 1 else "")}
 
-    main_res = measure(args.workload, args.scaling, args.steps, args.warmup, args.batch, args.samples, True)
+    main_res = measure(args.workload, args.scaling, args.steps, args.warmup, args.batch, args.samples, args.full)
     strong_rec = None
-    if (world > 1 and args.scaling == "weak" and args.workload == "cfg2" and not args.no_strong_record and not args.mc_fused):
+    if (args.full and world > 1 and args.scaling == "weak" and args.workload == "cfg2" and not args.no_strong_record and not args.mc_fused):
         # north_star's >= 6 x is about BASELINE configs[3] (cfg3's 10^7 samples x 500 waypoints, K = 8, SPLIT over the
         # GPUs): the default curve above is weak scaling on cfg2, so a short pass of that workload rides along
         # (64 runs per call: a rank's launch then holds 64 x 10^7 / N evaluations -- at N = 8 what a 64-run launch of the
@@ -749,7 +815,7 @@ def main():
         # (the one-card rehearsal keeps 16: two ranks' 512-block launches do not fit ONE card side by side, and a closer
         # that waits for a rank whose launch cannot start waits for its 30 s)
         sruns = int(os.environ.get("POCS_STRONG_RUNS", "16" if "POCS_FORCE_DEVICE" in os.environ else "64"))
-        sres = measure("cfg3", "strong", sruns, sruns, sruns, args.samples, False)
+        sres = measure("cfg3", "strong", sruns, sruns, sruns, args.samples, False, plain_repeats=3)
         kus = sres["ranks_kernel_us"] or []
         strong_rec = {"workload": "cfg3 split over %d GPUs (BASELINE configs[3] at 8): %d samples per GPU per run of %d in total, W=%d, K=%d, %d runs per call"
                                   % (world, sres["n_local"], sres["N"], sres["W"], sres["K"], sres["batch"]),
@@ -762,95 +828,97 @@ def main():
 
     res = main_res
     W, K, path, n_local, N, batch, chunks = res["W"], res["K"], res["path"], res["n_local"], res["N"], res["batch"], res["chunks"]
-    board, nostore_ms, groups, avg_ms = res["board"], res["nostore_ms"], res["groups"], res["avg_ms"]
-    copy_gbps, fill_gbps = res["copy_gbps"], res["fill_gbps"]
-    kern = "k_gmm_step" if path == "gmm" else ("k_mc_fused" if args.mc_fused else "k_mc_step")
-    bpe = BYTES_PER_EVAL_GMM if path == "gmm" else BYTES_PER_EVAL_MC
-    # a call may be issued as G sub-batches whose launches run side by side (POCS_OPT_SUB_BATCHES, default 1): the events
-    # bracket sub-batch 0's launches, each of which works on batch / G runs
-    # A call of many runs goes out as G sub-batches on G streams (POCS_OPT_SUB_BATCHES; two by default where the call has
-    # the work for it): G launches of batch / G runs run SIDE BY SIDE, and the span-timed period is that of a waypoint of
-    # the whole call -- so the rate is the chip's: the bytes of all G launches over the period.  (Bracketed timing, the
-    # fallback, times sub-batch 0's launches alone: one launch's bytes over its duration.)
-    per_launch = n_local * batch // max(groups, 1)  # evaluations one launch of the hot kernel processes
-    units = n_local * batch if res.get("span_timed") else per_launch       # ... and one period
-    achieved = (bpe * units) / (avg_ms * 1e-3) / 1e9 if avg_ms > 0 else 0.0
-    # Committed counter records of this workload (separate rocprofv3 --pmc passes, gfx950 FETCH_SIZE correction applied;
-    # profiles/traffic.json with its sources): HBM bytes and vector instructions per launch.  The record nearest in launch
-    # size is scaled to THIS launch's evaluations -- an extrapolation, said so in `traffic_source`, and dropped (null)
-    # when the nearest record's launch is more than 2 x away.
-    traffic, traffic_src, valu_per_eval, valu_src = None, None, None, None
-    tj = ROOT / "profiles" / "traffic.json"
-    if tj.exists():
-        recs = [(k, v) for k, v in json.loads(tj.read_text()).items()
-                if v.get("path", "gmm" if k.startswith("cfg") and not k.startswith("cfg5") else "mc") == path and v.get("evals_per_launch")
-                and v.get("numerics", "v6") == NUMERICS
-                and (path != "gmm" or (v.get("components") or (8 if "cfg3" in k else 3)) == K)]     # another K is another kernel
-        if recs:
-            k, rec = min(recs, key=lambda kv: abs(kv[1]["evals_per_launch"] - units))
-            if 0.5 <= rec["evals_per_launch"] / units <= 2.0:
-                traffic = rec["bytes_per_launch"] / rec["evals_per_launch"] * units
-                traffic_src = "%.3f B/eval measured at %d evals per launch (%s), scaled to %d evals" % (
-                    rec["bytes_per_launch"] / rec["evals_per_launch"], rec["evals_per_launch"], rec["source"].split(":")[0], units)
-                if rec.get("valu_insts_per_launch"):
-                    valu_per_eval = rec["valu_insts_per_launch"] / (rec["evals_per_launch"] / 64.0)   # wave instructions per wave's 64 evaluations
-                    valu_src = rec["source"].split(":")[0]
-    # What the kernel is actually limited by, in numbers: vector instructions per evaluation (counter record above) x
-    # the evaluations per second inside the kernel, against the chip's wave64 issue rate -- 256 CUs x 4 SIMDs, one vector
-    # instruction per SIMD every 4 cycles -- at the shader clock read live under this load (`board`), or at the peak clock.
-    mc_state_bytes = float(batch) * float((n_local + 1) & ~1) * 28.0
-    mc_resident = path == "mc" and not args.mc_fused and mc_state_bytes <= MC_CACHE_BYTES
-    if path == "gmm":
-        clock = (board or {}).get("sclk_MHz") or 2400.0
-        issue_peak = 1024 * clock * 1e6 / 4.0
-        bound = "fp64-issue+power"
-        limiter = {"kind": "FP64 vector issue (+ per-lane LDS table reads) and the all-write sample stream, coupled through the "
-                           "board's power cap: neither alone (DESIGN.md section 5)",
-                   "kernel_us_without_sample_stores": nostore_ms * 1e3 if nostore_ms else None,
-                   "stream_alone_us_at_fill_rate": (bpe * units / (fill_gbps * 1e9) * 1e6) if (fill_gbps or 0) > 0 else None,
-                   "valu_instr_per_eval": valu_per_eval, "clock_MHz": clock,
-                   "clock_source": "amdgpu hwmon, live" if (board or {}).get("sclk_MHz") else "peak clock (no live reading)",
-                   "valu_issue_frac": (valu_per_eval * (units / 64.0) / (avg_ms * 1e-3) / issue_peak) if (valu_per_eval and avg_ms > 0) else None,
-                   "valu_source": valu_src,
-                   "power_W": (board or {}).get("power_W"), "power_cap_W": (board or {}).get("power_cap_W")}
-    elif args.mc_fused:
-        bound = "fp64-issue"
-        limiter = {"kind": "FP64 vector issue: the particle stays in registers for the whole roll-out"}
-    elif mc_resident:
-        bound = "infinity-cache"
-        limiter = {"kind": "streaming through the 256 MB Infinity Cache: the batch's particle state (%.0f MB = %d runs x %d particles x 28 B) "
-                           "stays resident between two waypoint launches BY DESIGN (bench.py sizes the batch for it, pocs_host.hip picks the "
-                           "plain-access kernel), so the bytes per second below are not HBM traffic; the HBM-streaming form of the same kernel "
-                           "(k_mc_step<NT>) is what `--batch` beyond the cache measures (profiles/r04_mc_nt_*)" % (mc_state_bytes / 1e6, batch, n_local)}
-    else:
-        bound = "hbm"
-        limiter = {"kind": "HBM streaming (particle state read and written per waypoint, non-temporal: %.0f MB of state per launch do not fit "
-                           "the 256 MB Infinity Cache; the hit counter only where a particle collides)" % (mc_state_bytes / 1e6)}
-    # `frac` is quoted against the HBM peak wherever the bytes can be HBM bytes: not for the cache-resident MC batch (null
-    # there: the guide gives no peak for the Infinity Cache) -- its achieved rate stands beside the copy ceiling instead
-    hbm_frac = None if mc_resident else achieved / HBM_PEAK_GBPS
-    roofline = {"bound": bound, "reported_against": None if mc_resident else "hbm", "limiter": limiter, "board": board,
-                "kernel": kern, "achieved": achieved, "peak": None if mc_resident else HBM_PEAK_GBPS, "unit": "GB/s",
-                "frac": hbm_frac, "traffic": traffic, "traffic_source": traffic_src,
-                "traffic_frac": (traffic / (avg_ms * 1e-3) / 1e9 / HBM_PEAK_GBPS) if (traffic and avg_ms > 0 and not mc_resident) else None,
-                "copy_GBps": copy_gbps, "frac_of_copy": achieved / copy_gbps if (copy_gbps or 0) > 0 else None,
-                "fill_GBps": fill_gbps, "frac_of_fill": achieved / fill_gbps if (fill_gbps or 0) > 0 else None,
-                "algorithmic_bytes_per_launch": bpe * per_launch, "bytes_per_eval": bpe, "evals_per_launch": per_launch,
-                "concurrent_launches": groups, "evals_per_period": units, "algorithmic_bytes_per_period": bpe * units,
-                "avg_kernel_us": avg_ms * 1e3, "duration_is": res["duration_is"], "bracketed_kernel_us": res["bracketed_ms"] * 1e3,
-                "waypoint_us": res["waypoint_us"],
-                "evals_per_s_in_kernel": units / (avg_ms * 1e-3) if avg_ms > 0 else 0.0}
-    if path == "mc" and not args.mc_fused:
-        roofline["resident"] = "infinity-cache" if mc_resident else "hbm"
-        roofline["state_bytes_per_launch"] = mc_state_bytes
-    if args.mc_fused:
-        roofline["note"] = ("fused roll-out: the particle stays in registers for all waypoints, ~0 algorithmic bytes per evaluation "
-                            "(28 B per particle per RUN) -- an FP64-issue kernel whose roofline is not HBM; read evals_per_s_in_kernel, "
-                            "not frac (SURVEY 8d: reported separately from the streaming kernel)")
-    if dist is not None:                               # every rank's kernel time, so that a scaling run explains itself
-        kus = res["ranks_kernel_us"]
-        roofline["ranks_kernel_us"] = {"min": min(kus), "max": max(kus), "all": kus}
-        roofline["skew_us"] = max(kus) - min(kus)      # slowest - fastest rank's mean launch of the hot kernel
+    roofline = None
+    if args.full:                                      # (the roofline: the --full record's own calls)
+        board, nostore_ms, groups, avg_ms = res["board"], res["nostore_ms"], res["groups"], res["avg_ms"]
+        copy_gbps, fill_gbps = res["copy_gbps"], res["fill_gbps"]
+        kern = "k_gmm_step" if path == "gmm" else ("k_mc_fused" if args.mc_fused else "k_mc_step")
+        bpe = BYTES_PER_EVAL_GMM if path == "gmm" else BYTES_PER_EVAL_MC
+        # a call may be issued as G sub-batches whose launches run side by side (POCS_OPT_SUB_BATCHES, default 1): the events
+        # bracket sub-batch 0's launches, each of which works on batch / G runs
+        # A call of many runs goes out as G sub-batches on G streams (POCS_OPT_SUB_BATCHES; two by default where the call has
+        # the work for it): G launches of batch / G runs run SIDE BY SIDE, and the span-timed period is that of a waypoint of
+        # the whole call -- so the rate is the chip's: the bytes of all G launches over the period.  (Bracketed timing, the
+        # fallback, times sub-batch 0's launches alone: one launch's bytes over its duration.)
+        per_launch = n_local * batch // max(groups, 1)  # evaluations one launch of the hot kernel processes
+        units = n_local * batch if res.get("span_timed") else per_launch       # ... and one period
+        achieved = (bpe * units) / (avg_ms * 1e-3) / 1e9 if avg_ms > 0 else 0.0
+        # Committed counter records of this workload (separate rocprofv3 --pmc passes, gfx950 FETCH_SIZE correction applied;
+        # profiles/traffic.json with its sources): HBM bytes and vector instructions per launch.  The record nearest in launch
+        # size is scaled to THIS launch's evaluations -- an extrapolation, said so in `traffic_source`, and dropped (null)
+        # when the nearest record's launch is more than 2 x away.
+        traffic, traffic_src, valu_per_eval, valu_src = None, None, None, None
+        tj = ROOT / "profiles" / "traffic.json"
+        if tj.exists():
+            recs = [(k, v) for k, v in json.loads(tj.read_text()).items()
+                    if v.get("path", "gmm" if k.startswith("cfg") and not k.startswith("cfg5") else "mc") == path and v.get("evals_per_launch")
+                    and v.get("numerics", "v6") == NUMERICS
+                    and (path != "gmm" or (v.get("components") or (8 if "cfg3" in k else 3)) == K)]     # another K is another kernel
+            if recs:
+                k, rec = min(recs, key=lambda kv: abs(kv[1]["evals_per_launch"] - units))
+                if 0.5 <= rec["evals_per_launch"] / units <= 2.0:
+                    traffic = rec["bytes_per_launch"] / rec["evals_per_launch"] * units
+                    traffic_src = "%.3f B/eval measured at %d evals per launch (%s), scaled to %d evals" % (
+                        rec["bytes_per_launch"] / rec["evals_per_launch"], rec["evals_per_launch"], rec["source"].split(":")[0], units)
+                    if rec.get("valu_insts_per_launch"):
+                        valu_per_eval = rec["valu_insts_per_launch"] / (rec["evals_per_launch"] / 64.0)   # wave instructions per wave's 64 evaluations
+                        valu_src = rec["source"].split(":")[0]
+        # What the kernel is actually limited by, in numbers: vector instructions per evaluation (counter record above) x
+        # the evaluations per second inside the kernel, against the chip's wave64 issue rate -- 256 CUs x 4 SIMDs, one vector
+        # instruction per SIMD every 4 cycles -- at the shader clock read live under this load (`board`), or at the peak clock.
+        mc_state_bytes = float(batch) * float((n_local + 1) & ~1) * 28.0
+        mc_resident = path == "mc" and not args.mc_fused and mc_state_bytes <= MC_CACHE_BYTES
+        if path == "gmm":
+            clock = (board or {}).get("sclk_MHz") or 2400.0
+            issue_peak = 1024 * clock * 1e6 / 4.0
+            bound = "fp64-issue+power"
+            limiter = {"kind": "FP64 vector issue (+ per-lane LDS table reads) and the all-write sample stream, coupled through the "
+                               "board's power cap: neither alone (DESIGN.md section 5)",
+                       "kernel_us_without_sample_stores": nostore_ms * 1e3 if nostore_ms else None,
+                       "stream_alone_us_at_fill_rate": (bpe * units / (fill_gbps * 1e9) * 1e6) if (fill_gbps or 0) > 0 else None,
+                       "valu_instr_per_eval": valu_per_eval, "clock_MHz": clock,
+                       "clock_source": "amdgpu hwmon, live" if (board or {}).get("sclk_MHz") else "peak clock (no live reading)",
+                       "valu_issue_frac": (valu_per_eval * (units / 64.0) / (avg_ms * 1e-3) / issue_peak) if (valu_per_eval and avg_ms > 0) else None,
+                       "valu_source": valu_src,
+                       "power_W": (board or {}).get("power_W"), "power_cap_W": (board or {}).get("power_cap_W")}
+        elif args.mc_fused:
+            bound = "fp64-issue"
+            limiter = {"kind": "FP64 vector issue: the particle stays in registers for the whole roll-out"}
+        elif mc_resident:
+            bound = "infinity-cache"
+            limiter = {"kind": "streaming through the 256 MB Infinity Cache: the batch's particle state (%.0f MB = %d runs x %d particles x 28 B) "
+                               "stays resident between two waypoint launches BY DESIGN (bench.py sizes the batch for it, pocs_host.hip picks the "
+                               "plain-access kernel), so the bytes per second below are not HBM traffic; the HBM-streaming form of the same kernel "
+                               "(k_mc_step<NT>) is what `--batch` beyond the cache measures (profiles/r04_mc_nt_*)" % (mc_state_bytes / 1e6, batch, n_local)}
+        else:
+            bound = "hbm"
+            limiter = {"kind": "HBM streaming (particle state read and written per waypoint, non-temporal: %.0f MB of state per launch do not fit "
+                               "the 256 MB Infinity Cache; the hit counter only where a particle collides)" % (mc_state_bytes / 1e6)}
+        # `frac` is quoted against the HBM peak wherever the bytes can be HBM bytes: not for the cache-resident MC batch (null
+        # there: the guide gives no peak for the Infinity Cache) -- its achieved rate stands beside the copy ceiling instead
+        hbm_frac = None if mc_resident else achieved / HBM_PEAK_GBPS
+        roofline = {"bound": bound, "reported_against": None if mc_resident else "hbm", "limiter": limiter, "board": board,
+                    "kernel": kern, "achieved": achieved, "peak": None if mc_resident else HBM_PEAK_GBPS, "unit": "GB/s",
+                    "frac": hbm_frac, "traffic": traffic, "traffic_source": traffic_src,
+                    "traffic_frac": (traffic / (avg_ms * 1e-3) / 1e9 / HBM_PEAK_GBPS) if (traffic and avg_ms > 0 and not mc_resident) else None,
+                    "copy_GBps": copy_gbps, "frac_of_copy": achieved / copy_gbps if (copy_gbps or 0) > 0 else None,
+                    "fill_GBps": fill_gbps, "frac_of_fill": achieved / fill_gbps if (fill_gbps or 0) > 0 else None,
+                    "algorithmic_bytes_per_launch": bpe * per_launch, "bytes_per_eval": bpe, "evals_per_launch": per_launch,
+                    "concurrent_launches": groups, "evals_per_period": units, "algorithmic_bytes_per_period": bpe * units,
+                    "avg_kernel_us": avg_ms * 1e3, "duration_is": res["duration_is"], "bracketed_kernel_us": res["bracketed_ms"] * 1e3,
+                    "waypoint_us": res["waypoint_us"],
+                    "evals_per_s_in_kernel": units / (avg_ms * 1e-3) if avg_ms > 0 else 0.0}
+        if path == "mc" and not args.mc_fused:
+            roofline["resident"] = "infinity-cache" if mc_resident else "hbm"
+            roofline["state_bytes_per_launch"] = mc_state_bytes
+        if args.mc_fused:
+            roofline["note"] = ("fused roll-out: the particle stays in registers for all waypoints, ~0 algorithmic bytes per evaluation "
+                                "(28 B per particle per RUN) -- an FP64-issue kernel whose roofline is not HBM; read evals_per_s_in_kernel, "
+                                "not frac (SURVEY 8d: reported separately from the streaming kernel)")
+        if dist is not None:                               # every rank's kernel time, so that a scaling run explains itself
+            kus = res["ranks_kernel_us"]
+            roofline["ranks_kernel_us"] = {"min": min(kus), "max": max(kus), "all": kus}
+            roofline["skew_us"] = max(kus) - min(kus)      # slowest - fastest rank's mean launch of the hot kernel
 
     t_gpu_part = time.perf_counter() - t_process
     if rank == 0:
@@ -861,7 +929,7 @@ def main():
             "scaling": args.scaling, "vs_baseline": None, "dtype": "f64", "data": "synthetic",
             "numerics": "%s (%s)" % (NUMERICS, pocs_amd.load_library().pocs_version().decode()),
             "timing": res["timing"],
-            "single_call_evals_per_s": res["single"],
+            **({"single_call_evals_per_s": res["single"]} if args.full else {}),
             "config": {"workload": "%s: %s path, %s plan (%d waypoints), %d samples per GPU per run, K=%d, pr2test2 walls, PR2 0.668 m square footprint"
                                    % (args.workload, path.upper(), "bundled trajectory.dat/odometry.dat" if W == 56 else "resampled", W, n_local, K),
                        "waypoints": W, "samples_per_gpu": n_local, "components": K, "probability": res["prob"],
@@ -876,19 +944,22 @@ def main():
                        "sanity_band": "collision model = this build's 2-D boxes, not OpenRAVE/ODE + PR2 mesh (not in the reference tree): "
                                       "200 runs at N = 10^4 give MC 0.706 / GMM 0.285 (profiles/r01_table1_like.txt) against the paper's "
                                       "0.935 / 0.64; same ordering, different level -- parity unpinned at that call site (DESIGN.md 8)"},
-            "roofline": roofline,
+            **({"roofline": roofline} if args.full else {}),
         }
         if sharded:
             out["exchange_probe"] = xstate["probe"]
-            out["exchange_wait_us"] = None
-    if sharded:                                            # (collectives: every rank takes part)
+            if args.full:
+                out["exchange_wait_us"] = None
+    if sharded and args.full:                              # (collectives: every rank takes part)
         xw = exchange_wait(res)
         if rank == 0:
             out["exchange_wait_us"] = xw
             if strong_rec is not None:
                 out["strong"] = strong_rec
     if rank == 0:
-        if world == 1 and not args.no_cpu_baseline:
+        if args.dump_outputs:
+            write_outputs(args.dump_outputs, res["outputs"])
+        if world == 1 and args.full and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(res["plan"], env, K, W, path, args.cpu_evals, budget_s=max(2.0, CPU_BUDGET_FACTOR * t_gpu_part))
         sys.stdout.flush()
         os.dup2(json_fd, 1)

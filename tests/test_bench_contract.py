@@ -4,6 +4,7 @@ import subprocess
 import sys
 from pathlib import Path
 
+import numpy as np
 import pytest
 
 ROOT = Path(__file__).resolve().parents[1]
@@ -20,7 +21,7 @@ def run_bench(*extra, env=None):
 
 
 def test_default_line_has_every_field():
-    d = run_bench()
+    d = run_bench("--full")
     for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
               "vs_baseline", "dtype", "data", "config", "roofline", "cpu_baseline"):
         assert k in d, k
@@ -53,13 +54,40 @@ def test_default_line_has_every_field():
     assert "budget" in c
 
 
+def test_plain_line_is_the_headline_and_dumps_the_last_call(tmp_path):
+    """Without --full: ONE pass of exactly --steps timed steps and the headline, nothing that takes calls of its own
+    (roofline, one run per call, CPU baseline); --dump-outputs writes what the last timed call returned, float64, and
+    the same arguments give the same arrays, bit for bit."""
+    d = run_bench("--dump-outputs", str(tmp_path / "a"))
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "steps", "warmup", "config"):
+        assert k in d, k
+    for k in ("roofline", "cpu_baseline", "single_call_evals_per_s"):
+        assert k not in d, k
+    assert d["timing"]["repeats"] == 1 and sum(d["config"]["calls"]) == 5 and d["steps"] == 5
+    assert d["value"] > 0 and abs(d["value"] - 20000 * 56 * 5 / (d["ms_per_step"] * 5e-3)) / d["value"] < 1e-9
+    got = {f.stem: np.load(f) for f in (tmp_path / "a").glob("*.npy")}
+    assert set(got) == {"probability", "batch_probabilities", "waypoint_probabilities", "moments"}
+    assert all(v.dtype == np.float64 for v in got.values())
+    assert got["probability"].tolist() == [d["config"]["probability"]]
+    assert got["batch_probabilities"].shape == (5,) and np.all((got["batch_probabilities"] > 0) & (got["batch_probabilities"] < 1))
+    assert got["waypoint_probabilities"].shape == (5, 56) and got["moments"].shape == (5, 56, 3, 11)
+    again = run_bench("--dump-outputs", str(tmp_path / "b"))
+    assert again["config"]["probability"] == d["config"]["probability"]
+    for name, a in got.items():
+        assert np.array_equal(np.load(tmp_path / "b" / (name + ".npy")), a), name
+    mc = run_bench("--workload", "mc", "--dump-outputs", str(tmp_path / "mc"))
+    hits = np.load(tmp_path / "mc" / "hit_counts.npy")
+    assert hits.dtype == np.float64 and hits.shape == (5,) and np.all(hits == np.round(hits)) and np.all(hits <= 20000)
+    assert np.load(tmp_path / "mc" / "probability.npy").tolist() == [mc["config"]["probability"]]
+
+
 def test_full_size_line_carries_the_counter_records():
     """At the workload's own size the line carries the committed PMC figures: HBM bytes per launch (close to the
     algorithmic 26 B/eval) and the vector instructions per evaluation with the issue fraction they imply."""
     recs = json.loads((ROOT / "profiles" / "traffic.json").read_text())
     if not any(v.get("numerics") == "v9" and v.get("evals_per_launch") in (10_000_000, 20_000_000) for v in recs.values()):
         pytest.skip("no counter record of the current numerics at this launch size yet")
-    out = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--steps", "20", "--warmup", "5", "--no-cpu-baseline"],
+    out = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--steps", "20", "--warmup", "5", "--no-cpu-baseline", "--full"],
                          capture_output=True, text=True, check=True, cwd=str(ROOT))
     d = json.loads(out.stdout.splitlines()[-1])
     r = d["roofline"]
@@ -84,13 +112,14 @@ def test_strong_scaling_line():
 
 
 def test_mc_workload_line():
-    d = run_bench("--workload", "mc", "--no-cpu-baseline")
+    d = run_bench("--workload", "mc", "--no-cpu-baseline", "--full")
     assert "MC" in d["metric"] and d["roofline"]["bytes_per_eval"] == 56 and "cpu_baseline" not in d
     # 64 roll-outs of 20 000 particles = 36 MB of state: resident in the Infinity Cache between launches, so the line
     # does not call its bytes per second an HBM fraction
     r = d["roofline"]
     assert r["resident"] == "infinity-cache" and r["bound"] == "infinity-cache" and r["frac"] is None and r["achieved"] > 0
-    d = run_bench("--workload", "mc", "--no-cpu-baseline", "--samples", "1200000", "--batch", "8", "--steps", "8", "--warmup", "8")
+    d = run_bench("--workload", "mc", "--no-cpu-baseline", "--samples", "1200000", "--batch", "8", "--steps", "8", "--warmup", "8",
+                  "--full")
     r = d["roofline"]                                  # 8 x 1.2e6 x 28 B = 269 MB: past the cache, the non-temporal kernel, an HBM fraction
     assert r["resident"] == "hbm" and r["bound"] == "hbm" and 0.2 < r["frac"] < 1.0
 
@@ -112,7 +141,7 @@ def test_gpus_2_started_by_hand_brings_up_its_own_ranks():
     refuses."""
     import os
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
-    d = run_bench("--gpus", "2", "--no-cpu-baseline", env=dict(env, POCS_FORCE_DEVICE="0", POCS_DIST_BACKEND="gloo",
+    d = run_bench("--gpus", "2", "--no-cpu-baseline", "--full", env=dict(env, POCS_FORCE_DEVICE="0", POCS_DIST_BACKEND="gloo",
                                                                 POCS_SKIP_SINGLE="1", POCS_NO_BOARD_PROBE="1"))
     assert d["n_gpus"] == 2 and d["config"]["total_samples_per_run"] == 40000 and "tail" in d["config"]["exchange"]
     assert "whole call" in d["config"]["exchange"]                # ... replayed from a graph by the library, as on one GPU

@@ -10,7 +10,7 @@ import pytest
 
 HERE = Path(__file__).resolve().parent
 SCENES = {"pr2test2": (7, 0), "pr2custom": (29, 25)}       # boxes, of which rotated
-REF = Path("/root/reference")
+SCENE_XML = HERE / "golden"           # the reference's two scene files, stored as fixtures
 
 
 @pytest.mark.parametrize("name", sorted(SCENES))
@@ -24,11 +24,10 @@ def test_scene_tables_are_well_formed(name, pocs, orc):
     assert orc.collides(3.9, 0.0, 0.3, env["footprint"], b)
 
 
-@pytest.mark.skipif(not REF.exists(), reason="reference tree not mounted")
 @pytest.mark.parametrize("name", sorted(SCENES))
 def test_fixture_is_what_the_loader_extracts(name, pocs):
     envxml = import_module("probability-of-collision-for-safe-planning_amd.envxml")
-    got = envxml.load_env_xml(REF / (name + ".env.xml"))
+    got = envxml.load_env_xml(SCENE_XML / (name + ".env.xml"))
     want = pocs.load_env(HERE / "golden" / (name + "_env.txt"))
     assert np.array_equal(got["boxes"], want["boxes"]) and got["footprint"] == want["footprint"]
 

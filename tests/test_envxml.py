@@ -7,7 +7,7 @@ import numpy as np
 import pytest
 
 HERE = Path(__file__).resolve().parent
-REF_XML = Path("/root/reference/pr2test2.env.xml")
+REF_XML = HERE / "golden" / "pr2test2.env.xml"        # the reference's scene file, stored as a fixture
 
 
 @pytest.fixture(scope="module")
@@ -37,7 +37,6 @@ def test_round_trip_through_text(envxml, pocs, tmp_path):
     assert np.array_equal(back["boxes"], env["boxes"]) and back["footprint"] == env["footprint"]
 
 
-@pytest.mark.skipif(not REF_XML.exists(), reason="reference tree not mounted")
 def test_reference_scene_gives_the_bundled_obstacle_table(envxml, env):
     got = envxml.load_env_xml(REF_XML)
     assert np.allclose(got["boxes"], env["boxes"])               # data/pr2test2_env.txt, transcribed by hand

@@ -19,6 +19,6 @@ fi
 args=${@:---steps 64 --warmup 64}
 line() { python -c "import json,sys; d=json.loads(sys.stdin.read()); r=d['roofline']; print('$1: value %.4g frac %.3f %.1f us' % (d['value'], r['frac'], r['avg_kernel_us']))"; }
 for i in 1 2 3; do
-  POCS_LIB=ab_build/libpocs_base.so POCS_SKIP_SINGLE=1 python bench.py $args --no-cpu-baseline 2>/dev/null | line base
-  POCS_SKIP_SINGLE=1 python bench.py $args --no-cpu-baseline 2>/dev/null | line new
+  POCS_LIB=ab_build/libpocs_base.so POCS_SKIP_SINGLE=1 python bench.py --full $args --no-cpu-baseline 2>/dev/null | line base
+  POCS_SKIP_SINGLE=1 python bench.py --full $args --no-cpu-baseline 2>/dev/null | line new
 done

@@ -5,10 +5,10 @@ out=${1:-gpurun_out/sweep.txt}; shift
 : > "$out"
 run() { echo "## $*" >> "$out"; env "$@" >> "$out" 2>> "$out.err" || echo "FAILED: $*" >> "$out"; }
 for g in 1 2; do
-  run POCS_GMM_GROUPS=$g python bench.py --steps 20 --warmup 5 --no-cpu-baseline
-  run POCS_GMM_GROUPS=$g python bench.py --steps 256 --warmup 64 --no-cpu-baseline
-  run POCS_GMM_GROUPS=$g python bench.py --batch 1 --steps 16 --warmup 4 --no-cpu-baseline
-  run POCS_GMM_GROUPS=$g python bench.py --batch 8 --steps 32 --warmup 8 --no-cpu-baseline
+  run POCS_GMM_GROUPS=$g python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline
+  run POCS_GMM_GROUPS=$g python bench.py --full --steps 256 --warmup 64 --no-cpu-baseline
+  run POCS_GMM_GROUPS=$g python bench.py --full --batch 1 --steps 16 --warmup 4 --no-cpu-baseline
+  run POCS_GMM_GROUPS=$g python bench.py --full --batch 8 --steps 32 --warmup 8 --no-cpu-baseline
 done
 python - "$out" <<'PY'
 import json, sys

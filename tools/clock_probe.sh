@@ -5,7 +5,7 @@
 lib=$1
 [ -n "$lib" ] && export POCS_LIB=$lib
 export POCS_SKIP_SINGLE=1
-python bench.py --steps ${STEPS:-32768} --warmup 64 --no-cpu-baseline > /tmp/clock_probe_bench.json 2>/dev/null &
+python bench.py --full --steps ${STEPS:-32768} --warmup 64 --no-cpu-baseline > /tmp/clock_probe_bench.json 2>/dev/null &
 pid=$!
 sleep 3
 for i in $(seq 1 40); do
