@@ -99,6 +99,10 @@ int pocs_send_command(pocs_ctx* ctx, const char* line, char* out, size_t cap);
 #define POCS_OPT_MC_NONTEMPORAL 9  /* -1 (default): k_mc_step streams past the caches when the batch's particle state (28 B per particle)
                                       exceeds the 256 MB Infinity Cache and uses plain accesses when it fits; 0 / 1 force one form.
                                       Same results either way. */
+#define POCS_OPT_PLAN_SEEDS 10     /* a call of plans (pocs_set_plans): 0 (default): plan p draws the stream of run run_index + p, as run p
+                                      of a batch does, and the run counter advances by P; 1, common random numbers: every plan draws the
+                                      stream of run run_index and the counter advances by 1 -- the difference between two plans'
+                                      probabilities, what a planner compares, then has a much smaller variance */
 int pocs_set_option(pocs_ctx* ctx, int option, long long value);
 
 /* ---- batches of independent runs (ours) --------------------------------------------------
@@ -114,6 +118,31 @@ int pocs_set_batch(pocs_ctx* ctx, int runs);
 int pocs_get_batch_probabilities(pocs_ctx* ctx, double* out, int cap);
 int pocs_select_batch_run(pocs_ctx* ctx, int run);   /* the getters below (waypoint probabilities, moments, mixture state, host chain,
                                                         samples / particles) expose run `run` of the last batch; a new launch selects run 0 */
+
+/* ---- batches of candidate plans (ours) ---------------------------------------------------
+ * A planner has many candidate plans and wants the collision probability of each.  With P plans set
+ * (1 <= P <= 256), one pocs_run_gmm_estimation / pocs_run_simulation call evaluates every plan once, in
+ * one batch, and each plan gets bit for bit what a context holding that plan alone computes for it.
+ *   W[p] >= 1 is plan p's length.  trajs: plan p's trajectory, 3 x W[p] by component (x_0..x_{W-1}
+ *   y_0.. theta_0..), as pocs_set_trajectory takes it, the plans' blocks concatenated in plan order;
+ *   odoms: its odometry, 3 x (W[p] - 1) by component as pocs_set_odometry takes it, concatenated the
+ *   same way (may be NULL if every plan has one waypoint).  P = 0 clears the plans: the context goes
+ *   back to its single plan and batch.  Bad input: POCS_E_ARG.  Setting plans drops the last results.
+ * While plans are set:
+ *   - the batch is P; pocs_get_batch_probabilities / pocs_mc_get_batch_counts return the P results in
+ *     plan order, pocs_run_* returns plan 0's;
+ *   - pocs_select_batch_run(p) selects plan p for the getters: pocs_get_path_length returns W[p], the
+ *     waypoint getters cover W[p] waypoints (a waypoint >= W[p] is POCS_E_ARG), samples and particles
+ *     are plan p's;
+ *   - seeds: POCS_OPT_PLAN_SEEDS;
+ *   - pocs_set_batch, pocs_set_path_length, pocs_set_trajectory and pocs_set_odometry return
+ *     POCS_E_ORDER (clear the plans with pocs_set_plans(ctx, 0, ...) first); a shard (pocs_set_shard
+ *     other than (-1, -1)), the step API (pocs_gmm_begin) and the in-library exchange (pocs_xchg_*)
+ *     return POCS_E_STATE: plan batches run on one GPU;
+ *   - run-ahead (POCS_OPT_RUN_AHEAD) is not applied.
+ * A launch covers only the plans still running: the slots of a batch are ordered by descending plan
+ * length, and the launch of waypoint w covers the plans longer than w. */
+int pocs_set_plans(pocs_ctx* ctx, int P, const int* W, const double* trajs, const double* odoms);
 
 /* ---- sharding over GPUs (one process per GPU; the caller owns the collective) -----------
  * A context evaluates global sample / particle indices [first, first+count) of the N configured;

@@ -14,8 +14,9 @@ from . import build as _build
 POCS_OK = 0
 E_ARG, E_ORDER, E_STATE, E_DEVICE, E_UNKNOWN_COMMAND, E_BUFFER = -1, -2, -3, -4, -5, -6
 OPT_STORE_SAMPLES, OPT_MC_FUSED, OPT_USE_GRAPH, OPT_PROFILE, OPT_RUN_AHEAD, OPT_PERSISTENT, OPT_LONE_CALL = 1, 2, 3, 4, 5, 6, 7
-OPT_SUB_BATCHES, OPT_MC_NONTEMPORAL = 8, 9
+OPT_SUB_BATCHES, OPT_MC_NONTEMPORAL, OPT_PLAN_SEEDS = 8, 9, 10
 NMOM = 11
+MAX_PLANS = 256
 
 _dp = C.POINTER(C.c_double)
 _vp = C.c_void_p
@@ -47,6 +48,7 @@ SIGNATURES = {
     "pocs_set_batch": (C.c_int, [_vp, C.c_int]),
     "pocs_get_batch_probabilities": (C.c_int, [_vp, _dp, C.c_int]),
     "pocs_select_batch_run": (C.c_int, [_vp, C.c_int]),
+    "pocs_set_plans": (C.c_int, [_vp, C.c_int, C.POINTER(C.c_int), _dp, _dp]),
     "pocs_set_shard": (C.c_int, [_vp, C.c_longlong, C.c_longlong]),
     "pocs_set_stream": (C.c_int, [_vp, _vp]),
     "pocs_gmm_begin": (C.c_int, [_vp]),
@@ -143,6 +145,30 @@ class PocsError(RuntimeError):
 
 def _arr(a):
     return np.ascontiguousarray(a, dtype=np.float64)
+
+
+def pack_plans(plans):
+    """Candidate plans ({"traj": W x 3, "odom": (W-1) x 3} each, as set_plan takes one) -> (W, trajs, odoms) as
+    pocs_set_plans takes them: W int32[P]; trajs = plan p's trajectory by component (x_0..x_{W-1}, y.., theta..),
+    the plans one after the other; odoms = its odometry by component (r1.., tr.., r2..), concatenated the same way."""
+    plans = list(plans)
+    if not 1 <= len(plans) <= MAX_PLANS:
+        raise ValueError("between 1 and %d plans, got %d" % (MAX_PLANS, len(plans)))
+    Ws, trajs, odoms = [], [], []
+    for i, pl in enumerate(plans):
+        t = np.asarray(pl["traj"], dtype=np.float64)
+        o = np.asarray(pl["odom"], dtype=np.float64)
+        if t.ndim != 2 or t.shape[1] != 3 or t.shape[0] < 1:
+            raise ValueError("plan %d: trajectory of shape %s, W x 3 with W >= 1 expected" % (i, t.shape))
+        W = t.shape[0]
+        if o.size == 0 and W == 1:
+            o = o.reshape(0, 3)
+        if o.ndim != 2 or o.shape != (W - 1, 3):
+            raise ValueError("plan %d: odometry of shape %s, (%d, 3) expected" % (i, o.shape, W - 1))
+        Ws.append(W)
+        trajs.append(t.T.ravel())
+        odoms.append(o.T.ravel())
+    return (np.array(Ws, dtype=np.int32), _arr(np.concatenate(trajs)), _arr(np.concatenate(odoms)))
 
 
 class Context:
@@ -248,6 +274,23 @@ class Context:
     def select_batch_run(self, run):
         """The getters (waypoint probabilities, moments, mixture state, samples ...) expose run `run` of the last batch."""
         self._chk(self.lib.pocs_select_batch_run(self.h, int(run)))
+
+    def set_plans(self, plans):
+        """Candidate plans (list of {"traj": W x 3, "odom": (W-1) x 3}): every run call then evaluates each of them once,
+        in one batch; the results come in plan order and select_batch_run(p) selects plan p for the getters."""
+        W, trajs, odoms = pack_plans(plans)
+        if not hasattr(self, "_single_batch"):
+            self._single_batch = getattr(self, "_batch", 1)
+        self._chk(self.lib.pocs_set_plans(self.h, len(W), W.ctypes.data_as(C.POINTER(C.c_int)), trajs.ctypes.data_as(_dp),
+                                          odoms.ctypes.data_as(_dp)))
+        self._batch = len(W)
+
+    def clear_plans(self):
+        """Back to the single plan (and batch) of set_plan / set_batch."""
+        self._chk(self.lib.pocs_set_plans(self.h, 0, None, None, None))
+        if hasattr(self, "_single_batch"):
+            self._batch = self._single_batch
+            del self._single_batch
 
     def set_shard(self, first=-1, count=-1):
         """Evaluate global indices [first, first+count); no arguments = the whole range."""

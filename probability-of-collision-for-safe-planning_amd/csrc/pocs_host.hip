@@ -85,6 +85,17 @@ struct pocs_ctx {
   int batch_R = 1;                       // runs in the last launch
   std::vector<double> batch_moments;     // [W][R][K*11] of the last GMM launch
 
+  // candidate plans (pocs_set_plans): P > 0 = every run* call evaluates P plans, one run each, in one batch.  W is
+  // then the longest plan's length (the stride of every [run][W] array) and batch = P; the single plan's length and
+  // the batch wait in single_W / single_batch for pocs_set_plans(ctx, 0, ...).
+  int nplans = 0;
+  std::vector<int> plan_W;                        // [P]
+  std::vector<size_t> plan_toff, plan_ooff;       // [P] where plan p starts in plan_traj (3 x W_p) / plan_odom (3 x (W_p - 1))
+  std::vector<double> plan_traj, plan_odom;
+  int single_W = -1, single_batch = 1;
+  long long opt_plan_seeds = 0;                   // POCS_OPT_PLAN_SEEDS
+  std::vector<int> plan_slot[2];                  // the batch slot of plan p in the last call of plans: [0] GMM, [1] MC
+
   // host image (headers | chains | initial mixtures) of the NEXT batch, computed while the GPU
   // works on the current one
   struct {
@@ -93,11 +104,13 @@ struct pocs_ctx {
     int R = 0;
     unsigned long long epoch = 0;
     std::vector<double> image, chain0, mu0, cov0;
+    std::vector<int> slot_plan;          // a call of plans: the layout the image was built for
   } ahead;
 
   // ---- device state ----
   DevBuf d_env, d_sensor, d_hdr, d_chain, d_state, d_param, d_moments, d_partial;
   DevBuf d_sx, d_sy, d_st, d_flags, d_px, d_py, d_pt, d_hits, d_total, d_ticket, d_tables;
+  DevBuf d_runplan;                      // a call of plans: [R][4] start mean and steps per run (the MC kernels)
   // one-hop exchange (pocs_xchg_*): this rank's buffer, the peers' buffers as mapped here
   void* xchg_own = nullptr;
   void* xchg_peer[POCS_XCHG_MAX_WORLD] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
@@ -245,21 +258,30 @@ double chain_normal(uint64_t seed, int step, int draw) {
   return (draw & 1) ? n1 : n0;
 }
 
-void compute_chain(pocs_ctx* c, uint64_t seed) {
-  const int W = c->W, L = c->sensor.L;
+// One plan as the host chain and the initial mixture read it: trajectory 3 x W and odometry 3 x (W-1), by component.
+struct PlanView { const double* traj; const double* odom; int W; };
+PlanView plan_view(const pocs_ctx* c, int p) {          // p < 0: the single plan (pocs_set_trajectory / pocs_set_odometry)
+  if (p < 0) return PlanView{c->traj.data(), c->odom.data(), c->W};
+  return PlanView{c->plan_traj.data() + c->plan_toff[(size_t)p], c->plan_odom.data() + c->plan_ooff[(size_t)p], c->plan_W[(size_t)p]};
+}
+
+void compute_chain(pocs_ctx* c, uint64_t seed, const PlanView& pv) {
+  const int W = pv.W, L = c->sensor.L;
+  const double* traj = pv.traj;
+  const double* odom = pv.odom;
   c->h_chain.assign((size_t)(W > 1 ? W - 1 : 1) * POCS_CHAIN_STRIDE, 0.0);
   c->h_mu.assign((size_t)(W > 1 ? W - 1 : 1) * 3, 0.0);
   c->h_cov.assign((size_t)(W > 1 ? W - 1 : 1) * 9, 0.0);
-  double mu[3] = {c->traj[0], c->traj[W], c->traj[2 * W]};
+  double mu[3] = {traj[0], traj[W], traj[2 * W]};
   double cov[9];
   memcpy(cov, c->cov0, sizeof cov);
   double real[3] = {mu[0], mu[1], mu[2]};
   const double a1 = c->alphas[0], a2 = c->alphas[1], a3 = c->alphas[2], a4 = c->alphas[3];
   for (int i = 0; i < W - 1; ++i) {
     double* rec = &c->h_chain[(size_t)i * POCS_CHAIN_STRIDE];
-    const double us[3] = {c->odom[i], c->odom[(W - 1) + i], c->odom[2 * (W - 1) + i]};
-    const double xs[3] = {c->traj[i], c->traj[W + i], c->traj[2 * W + i]};
-    const double xg[3] = {c->traj[i + 1], c->traj[W + i + 1], c->traj[2 * W + i + 1]};
+    const double us[3] = {odom[i], odom[(W - 1) + i], odom[2 * (W - 1) + i]};
+    const double xs[3] = {traj[i], traj[W + i], traj[2 * W + i]};
+    const double xg[3] = {traj[i + 1], traj[W + i + 1], traj[2 * W + i + 1]};
     // generateM_EKF on the NOMINAL control
     rec[3] = a1 * (us[0] * us[0]) + a2 * (us[1] * us[1]);
     rec[4] = a3 * (us[1] * us[1]) + a4 * (us[0] * us[0]) + a4 * (us[2] * us[2]);
@@ -307,7 +329,7 @@ void compute_chain(pocs_ctx* c, uint64_t seed) {
 int check_common(pocs_ctx* c) {
   if (!c->have_q || !c->have_landmarks) return fail(c, POCS_E_STATE, "setQ / setLandmarks missing");
   if (!c->have_cov0) return fail(c, POCS_E_STATE, "setInitialCovariance missing");
-  if (!c->have_traj || !c->have_odom) return fail(c, POCS_E_STATE, "setTrajectory / setOdometry missing");
+  if (!c->nplans && (!c->have_traj || !c->have_odom)) return fail(c, POCS_E_STATE, "setTrajectory / setOdometry missing");
   if (c->W < 1) return fail(c, POCS_E_STATE, "setPathLength missing");
   // The reference receives its collision world through the module constructor (sim(penv),
   // mcsimplugin.cpp:12 -> MCSimulator.h:139-156).  A context that was never given one would answer
@@ -346,15 +368,16 @@ int upload_static(pocs_ctx* c) {
   return POCS_OK;
 }
 
-// pinned staging layout (doubles): [0 .. 2R) run headers, then R chains, then R initial mixtures,
-// then the moments [W][R][K*11], then the MC total
-struct PinLayout { size_t chain, state0, moments, total, end; };
+// pinned staging layout (doubles): [0 .. 2R) run headers, then R chains, then R initial mixtures, (a call of plans:
+// then R rows of start mean and steps), then the moments [W][R][K*11], then the MC total
+struct PinLayout { size_t chain, state0, runplan, moments, total, end; };
 PinLayout pin_layout(const pocs_ctx* c) {
   PinLayout p;
   const size_t W = (size_t)(c->W > 0 ? c->W : 1), K = (size_t)(c->K > 0 ? c->K : 1), R = (size_t)c->batch;
   p.chain = 2 * R;
   p.state0 = p.chain + R * (W > 1 ? W - 1 : 1) * POCS_CHAIN_STRIDE;
-  p.moments = p.state0 + R * K * POCS_STATE_STRIDE;
+  p.runplan = p.state0 + R * K * POCS_STATE_STRIDE;
+  p.moments = p.runplan + (c->nplans ? 4 * R : 0);
   p.total = p.moments + W * R * K * POCS_NMOM;
   p.end = p.total + R + 2;                 // one u64 per run: MC totals
   return p;
@@ -456,6 +479,8 @@ int gmm_prepare(pocs_ctx* c) {
     return fail(c, POCS_E_BUFFER, "bound moments buffer too small");
   if (int r = ensure(c, c->d_partial, 2 * (R << geo.vs_shift) * K * POCS_NMOM * sizeof(double))) return r;   // (x 2: a lone call alternates halves)
   if (int r = ensure(c, c->d_ticket, sync_words(c) * sizeof(unsigned))) return r;
+  if (c->nplans)
+    if (int r = ensure(c, c->d_runplan, R * 4 * sizeof(double))) return r;
   if (c->opt_store) {
     const size_t n = R * (size_t)sample_stride_of(count);
     if (int r = ensure(c, c->d_sx, n * sizeof(double))) return r;
@@ -466,38 +491,93 @@ int gmm_prepare(pocs_ctx* c) {
   return ensure_pin(c);
 }
 
-// host staging -> device: run header, chain, initial mixture (initGMM, MCSimulator.h:350-352,
-// GM_Model.h:57-77: K copies of (mu0, Sigma0), weights 1/K)
+// A call of plans (pocs_set_plans): which plan each batch slot holds.  Slots in DESCENDING plan length (ties in plan
+// order), so that the runs still live at any waypoint are a prefix of every sub-batch's slot range and the launch of
+// waypoint w covers those only; with G sub-batches (gmm_groups) the plans of consecutive rank go to consecutive
+// sub-batches, the larger ones first, so that all of them stay busy to the end.  Empty without plans.
+std::vector<int> plan_layout(const pocs_ctx* c, int G) {
+  std::vector<int> slot_plan;
+  if (!c->nplans) return slot_plan;
+  const int R = c->nplans;
+  if (G < 1) G = 1;
+  if (G > R) G = R;
+  std::vector<int> rank(R);
+  for (int p = 0; p < R; ++p) rank[p] = p;
+  std::stable_sort(rank.begin(), rank.end(), [c](int x, int y) { return c->plan_W[(size_t)x] > c->plan_W[(size_t)y]; });
+  std::vector<int> lo(G), n(G), fill(G, 0), order(G);
+  for (int g = 0; g < G; ++g) {                      // sub-batch g = slots [g R / G, (g + 1) R / G), as enqueue_gmm_all cuts them
+    lo[g] = (int)((long long)g * R / G);
+    n[g] = (int)((long long)(g + 1) * R / G) - lo[g];
+    order[g] = g;
+  }
+  std::stable_sort(order.begin(), order.end(), [&n](int x, int y) { return n[x] > n[y]; });
+  slot_plan.assign(R, 0);
+  for (int i = 0; i < R; ++i) {
+    int k = i % G;
+    while (fill[order[k]] == n[order[k]]) k = (k + 1) % G;
+    const int g = order[k];
+    slot_plan[(size_t)(lo[g] + fill[g]++)] = rank[i];
+  }
+  return slot_plan;
+}
+// the plan length of every slot of such a layout
+std::vector<int> slot_lengths(const pocs_ctx* c, const std::vector<int>& slot_plan) {
+  std::vector<int> Ws(slot_plan.size());
+  for (size_t s = 0; s < slot_plan.size(); ++s) Ws[s] = c->plan_W[(size_t)slot_plan[s]];
+  return Ws;
+}
+// runs of slots [lo, hi) whose plan is longer than w: a prefix of the range (plan_layout)
+int live_runs(const std::vector<int>& Ws, int lo, int hi, int w) {
+  int n = 0;
+  while (lo + n < hi && Ws[(size_t)(lo + n)] > w) ++n;
+  return n;
+}
+// The run number whose stream plan p draws, relative to the call's first: plan p draws run p's (the default), or --
+// POCS_OPT_PLAN_SEEDS = 1, common random numbers -- every plan the call's first run's.
+uint64_t plan_run(const pocs_ctx* c, int p) { return c->opt_plan_seeds ? 0 : (uint64_t)p; }
+
 // Host image of one batch starting at run `base` (relative to c->run_index): per run the header
 // (seed), the chain record and the initial mixture (initGMM, MCSimulator.h:350-352,
 // GM_Model.h:57-77: K copies of (mu0, Sigma0), weights 1/K), laid out as the pinned staging area.
-// Leaves run 0's chain in c->h_chain / h_mu / h_cov.
-void build_run_image(pocs_ctx* c, uint64_t base, double* img) {
+// A call of plans: slot r holds plan slot_plan[r] -- its own chain, start mean and seed (plan_run) -- and a row of
+// start mean and steps.  Leaves slot 0's chain in c->h_chain / h_mu / h_cov.
+void build_run_image(pocs_ctx* c, uint64_t base, double* img, const std::vector<int>& slot_plan) {
   const PinLayout pl = pin_layout(c);
   const int W = c->W, R = c->batch;
   const size_t steps = (size_t)(W > 1 ? W - 1 : 1);
   for (int r = R - 1; r >= 0; --r) {          // run 0 last: c->h_chain / h_mu / h_cov keep ITS chain
-    const uint64_t seed = effective_seed(c, base + (uint64_t)r);
-    compute_chain(c, seed);
+    const int p = c->nplans ? slot_plan[(size_t)r] : -1;
+    const uint64_t seed = effective_seed(c, base + (p >= 0 ? plan_run(c, p) : (uint64_t)r));
+    const PlanView pv = plan_view(c, p);
+    compute_chain(c, seed, pv);
     pocs_run_header hdr; hdr.seed = seed; hdr.pad = c->xchg_calls;      // (sharded whole calls read their exchange epoch from here)
     memcpy(img + 2 * (size_t)r, &hdr, sizeof hdr);
-    memcpy(img + pl.chain + (size_t)r * steps * POCS_CHAIN_STRIDE, c->h_chain.data(), c->h_chain.size() * sizeof(double));
+    double* ch = img + pl.chain + (size_t)r * steps * POCS_CHAIN_STRIDE;
+    memcpy(ch, c->h_chain.data(), c->h_chain.size() * sizeof(double));
+    if (c->h_chain.size() < steps * POCS_CHAIN_STRIDE)                // (a shorter plan: records no kernel reads, zeroed)
+      memset(ch + c->h_chain.size(), 0, (steps * POCS_CHAIN_STRIDE - c->h_chain.size()) * sizeof(double));
     for (int k = 0; k < c->K; ++k) {
       double* s = img + pl.state0 + ((size_t)r * c->K + k) * POCS_STATE_STRIDE;
-      s[0] = c->traj[0]; s[1] = c->traj[W]; s[2] = c->traj[2 * W];
+      s[0] = pv.traj[0]; s[1] = pv.traj[pv.W]; s[2] = pv.traj[2 * pv.W];
       memcpy(s + 3, c->cov0, 9 * sizeof(double));
       s[12] = 1.0 / c->K; s[13] = 1.0; s[14] = 0.0; s[15] = 0.0;
+    }
+    if (c->nplans) {
+      double* q = img + pl.runplan + 4 * (size_t)r;
+      q[0] = pv.traj[0]; q[1] = pv.traj[pv.W]; q[2] = pv.traj[2 * pv.W]; q[3] = (double)(pv.W - 1);
     }
   }
 }
 
-// While the GPU works on the current batch: the host chains of the next one.
-void prefetch_next_batch(pocs_ctx* c) {
+// While the GPU works on the current batch: the host chains of the next one (`groups`: the next call's sub-batches,
+// which a call of plans lays its slots out by).
+void prefetch_next_batch(pocs_ctx* c, int groups) {
   const PinLayout pl = pin_layout(c);
   auto& a = c->ahead;
   std::vector<double> keep_chain = c->h_chain, keep_mu = c->h_mu, keep_cov = c->h_cov;
   a.image.resize(pl.moments);
-  build_run_image(c, 0, a.image.data());       // c->run_index already points at the next batch
+  a.slot_plan = plan_layout(c, groups);
+  build_run_image(c, 0, a.image.data(), a.slot_plan);       // c->run_index already points at the next batch
   a.chain0.swap(c->h_chain); a.mu0.swap(c->h_mu); a.cov0.swap(c->h_cov);
   c->h_chain.swap(keep_chain); c->h_mu.swap(keep_mu); c->h_cov.swap(keep_cov);
   a.seed = c->seed; a.run_index = c->run_index; a.R = c->batch; a.epoch = c->epoch;
@@ -505,34 +585,44 @@ void prefetch_next_batch(pocs_ctx* c) {
 }
 
 // Host image of this call's batch into the pinned staging area (from the look-ahead cache when it
-// matches), run counter advanced; then the uploads every path needs: headers and chains.
-int stage_and_upload_runs(pocs_ctx* c) {
+// matches), run counter advanced; then the uploads every path needs: headers and chains (and, for a call of
+// plans, the runs' start rows).  `groups`: the call's sub-batches; `kind`: 0 GMM, 1 MC (whose plan layout it records).
+int stage_and_upload_runs(pocs_ctx* c, int groups, int kind) {
   const PinLayout pl = pin_layout(c);
   double* pin = (double*)c->h_pin;
   const int W = c->W, R = c->batch;
   const size_t steps = (size_t)(W > 1 ? W - 1 : 1);
+  const std::vector<int> slot_plan = plan_layout(c, groups);
   auto& a = c->ahead;
   if (a.valid && a.seed == c->seed && a.run_index == c->run_index && a.R == R && a.epoch == c->epoch &&
-      a.image.size() == pl.moments) {
+      a.image.size() == pl.moments && a.slot_plan == slot_plan) {
     memcpy(pin, a.image.data(), pl.moments * sizeof(double));
     c->h_chain = a.chain0; c->h_mu = a.mu0; c->h_cov = a.cov0;
   } else {
-    build_run_image(c, 0, pin);
+    build_run_image(c, 0, pin, slot_plan);
   }
   a.valid = false;
   for (int r = 0; r < R; ++r) ((uint64_t*)pin)[2 * (size_t)r + 1] = c->xchg_calls;      // (the image may have been built a call ago: the headers' exchange count is this call's)
   c->batch_base = c->run_index;
   c->batch_R = R;
   c->view = 0;
-  c->run_index += (uint64_t)R;
+  c->run_index += c->nplans && c->opt_plan_seeds ? 1 : (uint64_t)R;
+  if (c->nplans) {
+    std::vector<int>& ps = c->plan_slot[kind];
+    ps.assign((size_t)R, 0);
+    for (int r = 0; r < R; ++r) ps[(size_t)slot_plan[(size_t)r]] = r;
+    HIPCHK(c, hipMemcpyAsync(c->d_runplan.p, pin + pl.runplan, (size_t)R * 4 * sizeof(double), hipMemcpyHostToDevice, c->stream));
+  }
   HIPCHK(c, hipMemcpyAsync(c->d_hdr.p, pin, (size_t)R * sizeof(pocs_run_header), hipMemcpyHostToDevice, c->stream));
   HIPCHK(c, hipMemcpyAsync(c->d_chain.p, pin + pl.chain, (size_t)R * steps * POCS_CHAIN_STRIDE * sizeof(double),
                            hipMemcpyHostToDevice, c->stream));
   return POCS_OK;
 }
 
+int gmm_groups(const pocs_ctx* c);
+
 int gmm_upload_run(pocs_ctx* c) {
-  if (int r = stage_and_upload_runs(c)) return r;
+  if (int r = stage_and_upload_runs(c, gmm_groups(c), 0)) return r;
   const PinLayout pl = pin_layout(c);
   double* pin = (double*)c->h_pin;
   const int W = c->W, R = c->batch;
@@ -599,12 +689,13 @@ void set_lone(pocs_ctx* c, pocs_gmm_launch* a, int w) {
   a->partial_prev = (double*)c->d_partial.p + (size_t)((w + 1) & 1) * half;
 }
 
+// adv_cnt >= 0 (a call of plans): only the first adv_cnt of the launch's runs go on past waypoint w
 int enqueue_step(pocs_ctx* c, long long first, long long count, int w, bool advance_in_tail, int prof_slot,
-                 hipStream_t stream = nullptr, int run_lo = 0, int run_cnt = -1, int groups = 1, bool lone = false) {
+                 hipStream_t stream = nullptr, int run_lo = 0, int run_cnt = -1, int groups = 1, bool lone = false, int adv_cnt = -1) {
   pocs_gmm_launch a;
   if (!stream) stream = c->stream;
   fill_gmm_launch(c, &a, first, count, w, run_lo, run_cnt, groups);
-  a.advance_in_tail = (advance_in_tail && w + 1 < c->W) ? 1 : 0;
+  a.advance_in_tail = (advance_in_tail && w + 1 < c->W) ? a.run_lo + (adv_cnt >= 0 ? adv_cnt : a.run_cnt) : 0;   // (the runs below it advance)
   if (lone) set_lone(c, &a, w);
   if (whole_call_exchanges(c)) {
     a.exchange_in_tail = 1;
@@ -662,10 +753,23 @@ int enqueue_gmm_all(pocs_ctx* c, long long first, long long count, bool prof) {
   if (G > 1) HIPCHK(c, hipEventRecord(c->ev_fork, c->stream));
   for (int g = 1; g < G; ++g) HIPCHK(c, hipStreamWaitEvent(c->side_stream[g - 1], c->ev_fork, 0));
   const bool lone = lone_call(c);
+  // a call of plans: the launch of waypoint w covers the runs whose plan is longer than w -- a prefix of every
+  // sub-batch's slots (plan_layout) -- and the closers of those whose plan ends at w do not advance
+  const std::vector<int> Ws = slot_lengths(c, plan_layout(c, G));
   for (int w = 0; w < W; ++w)
     for (int g = 0; g < G; ++g) {                    // sub-batch g = runs [g R / G, (g + 1) R / G); events bracket sub-batch 0's launches
       const int lo = (int)((long long)g * R / G), hi = (int)((long long)(g + 1) * R / G);
-      if (int r = enqueue_step(c, first, count, w, true, (prof && g == 0) ? w : -1, g == 0 ? c->stream : c->side_stream[g - 1], lo, hi - lo, G, lone)) return r;
+      hipStream_t st = g == 0 ? c->stream : c->side_stream[g - 1];
+      int cnt = hi - lo, adv = -1;
+      if (c->nplans) {
+        cnt = live_runs(Ws, lo, hi, w);
+        adv = live_runs(Ws, lo, hi, w + 1);
+        if (cnt == 0) {                              // this sub-batch's plans have all ended
+          if (prof && g == 0) { HIPCHK(c, hipEventRecord(c->events[2 * w], st)); HIPCHK(c, hipEventRecord(c->events[2 * w + 1], st)); }
+          continue;
+        }
+      }
+      if (int r = enqueue_step(c, first, count, w, true, (prof && g == 0) ? w : -1, st, lo, cnt, G, lone, adv)) return r;
     }
   if (lone) {                                        // the last waypoint's rows -> moments[W-1]
     pocs_gmm_launch a;
@@ -693,13 +797,16 @@ int enqueue_gmm_results(pocs_ctx* c) {
 
 // F1 (MCSimulator.h:848-856): p_w = colliding / numGMMSamples (:633-641), result = 1 - prod(1 - p_w)
 // The getters' view of the last GMM launch: per-waypoint probabilities and moments of run v.
+// (a call of plans: v is the plan, which the moments hold in its batch slot, over its own W_p waypoints)
 void gmm_select_view(pocs_ctx* c, int v) {
-  const int W = c->W, K = c->K, R = c->batch_R;
+  const bool plans = c->nplans && !c->plan_slot[0].empty();
+  const int W = plans ? c->plan_W[(size_t)v] : c->W, K = c->K, R = c->batch_R;
+  const int slot = plans ? c->plan_slot[0][(size_t)v] : v;
   c->view = v;
   c->probs.assign(W, 0.0);
   c->last_moments.assign((size_t)W * K * POCS_NMOM, 0.0);
   for (int w = 0; w < W; ++w) {
-    const double* m = &c->batch_moments[((size_t)w * R + v) * K * POCS_NMOM];
+    const double* m = &c->batch_moments[((size_t)w * R + slot) * K * POCS_NMOM];
     double coll = 0.0;
     for (int k = 0; k < K; ++k) coll += m[(size_t)k * POCS_NMOM + 1];
     c->probs[w] = coll / (1.0 * (double)c->num_gmm);
@@ -713,10 +820,12 @@ void gmm_combine(pocs_ctx* c, const double* moments, double* probability) {
   c->last_kind = 1;
   c->batch_moments.assign(moments, moments + (size_t)W * R * K * POCS_NMOM);
   c->batch_probs.assign(R, 0.0);
-  for (int r = 0; r < R; ++r) {
+  const bool plans = c->nplans && !c->plan_slot[0].empty();
+  for (int r = 0; r < R; ++r) {                        // (a call of plans: r is the plan, in its slot, over its W_p waypoints)
+    const int slot = plans ? c->plan_slot[0][(size_t)r] : r, Wr = plans ? c->plan_W[(size_t)r] : W;
     double prod = 1.0;
-    for (int w = 0; w < W; ++w) {
-      const double* m = moments + ((size_t)w * R + r) * K * POCS_NMOM;
+    for (int w = 0; w < Wr; ++w) {
+      const double* m = moments + ((size_t)w * R + slot) * K * POCS_NMOM;
       double coll = 0.0;
       for (int k = 0; k < K; ++k) coll += m[(size_t)k * POCS_NMOM + 1];
       const double p = coll / (1.0 * (double)c->num_gmm);
@@ -733,7 +842,12 @@ std::string config_key(const pocs_ctx* c, long long first, long long count, cons
   snprintf(buf, sizeof buf, "%s e%llu W%d K%d R%d g%d l%d x%d n%lld f%lld c%lld s%lld fu%lld st%p em%p", tag, c->epoch,
            c->W, c->K, c->batch, gmm_groups(c), lone_call(c) ? 1 : 0, (c->xchg_connected && c->shard_first >= 0 && !c->ext_moments) ? c->xchg_world : 0,
            c->num_gmm, first, count, c->opt_store, c->opt_fused, (void*)c->stream, (void*)c->ext_moments);
-  return buf;
+  std::string key = buf;
+  if (c->nplans) {                                   // a call of plans: one launch per waypoint and LIVE sub-batch, by the plans' lengths
+    key += " P";
+    for (int p = 0; p < c->nplans; ++p) key += (p ? "," : "") + std::to_string(c->plan_W[(size_t)p]);
+  }
+  return key;
 }
 
 int run_gmm_full(pocs_ctx* c, double* probability) {
@@ -797,7 +911,7 @@ int run_gmm_full(pocs_ctx* c, double* probability) {
   }
   if (!copies_in_graph) if (int r = enqueue_gmm_results(c)) return r;
   lap("launched");
-  prefetch_next_batch(c);          // host chains of the next batch, while the GPU works on this one
+  prefetch_next_batch(c, gmm_groups(c));          // host chains of the next batch, while the GPU works on this one
   lap("next batch prepared");
   HIPCHK(c, hipStreamSynchronize(c->stream));
   lap("synchronised");
@@ -848,8 +962,15 @@ int enqueue_mc_all(pocs_ctx* c, long long first, long long count, bool prof) {
   // 256 MB Infinity Cache between waypoint launches; past that the launches stream from HBM whatever
   // they do, and non-temporal accesses then stream faster (16 x 10^6: 148 us instead of 189 us)
   a.nontemporal = c->opt_mc_nt >= 0 ? (int)c->opt_mc_nt : (((double)R * (double)a.stride * 28.0 > 232.0e6) ? 1 : 0);
-  a.mu0[0] = c->traj[0]; a.mu0[1] = c->traj[W]; a.mu0[2] = c->traj[2 * W];
+  if (c->nplans) {
+    a.run_plan = (const double*)c->d_runplan.p;      // every run its own start mean and steps
+  } else {
+    a.mu0[0] = c->traj[0]; a.mu0[1] = c->traj[W]; a.mu0[2] = c->traj[2 * W];
+  }
   if (!pocs_chol3_lower(c->cov0, a.L0)) return fail(c, POCS_E_ARG, "initial covariance is not positive definite");
+  // a call of plans: slots in descending plan length (plan_layout, one group), so the runs that still drive a control at
+  // step s are a prefix -- the launch of step s covers those only
+  const std::vector<int> Ws = slot_lengths(c, plan_layout(c, 1));
   if (c->opt_fused) {
     a.step = W - 1;
     if (prof) HIPCHK(c, hipEventRecord(c->events[0], c->stream));
@@ -860,8 +981,14 @@ int enqueue_mc_all(pocs_ctx* c, long long first, long long count, bool prof) {
     HIPCHK(c, pocs_launch_mc_init(nblk, a, c->stream));
     for (int s = 0; s < W - 1; ++s) {
       a.step = s;
+      pocs_mc_launch as = a;
+      int nb = nblk;
+      if (c->nplans) {
+        as.nruns = live_runs(Ws, 0, R, s + 1);       // plans with a control at step s: W_p - 1 > s
+        nb = grid_for_mc(count, as.nruns);
+      }
       if (prof) HIPCHK(c, hipEventRecord(c->events[2 * s], c->stream));
-      HIPCHK(c, pocs_launch_mc_step(nblk, a, c->stream));
+      if (as.nruns > 0) HIPCHK(c, pocs_launch_mc_step(nb, as, c->stream));
       if (prof) HIPCHK(c, hipEventRecord(c->events[2 * s + 1], c->stream));
     }
   }
@@ -884,8 +1011,10 @@ int run_mc_local(pocs_ctx* c) {
   if (int r = ensure(c, c->d_pt, n * sizeof(double))) return r;
   if (int r = ensure(c, c->d_hits, n * sizeof(uint32_t))) return r;
   if (int r = ensure(c, c->d_total, R * sizeof(unsigned long long) + 16)) return r;
+  if (c->nplans)
+    if (int r = ensure(c, c->d_runplan, R * 4 * sizeof(double))) return r;
   if (int r = ensure_pin(c)) return r;
-  if (int r = stage_and_upload_runs(c)) return r;
+  if (int r = stage_and_upload_runs(c, 1, 1)) return r;
   const bool prof = c->opt_profile == 1, span = c->opt_profile == 2 && c->opt_graph;      // (as run_gmm_full)
   const size_t nprof = c->opt_fused ? 1 : (W > 1 ? W - 1 : 0);
   if (int r = prof_begin(c, nprof > 0 ? nprof : 1)) return r;
@@ -916,7 +1045,7 @@ int run_mc_local(pocs_ctx* c) {
   const PinLayout pl = pin_layout(c);
   HIPCHK(c, hipMemcpyAsync((double*)c->h_pin + pl.total, c->d_total.p, R * sizeof(unsigned long long),
                            hipMemcpyDeviceToHost, c->stream));
-  prefetch_next_batch(c);          // host chains of the next batch, while the GPU works on this one
+  prefetch_next_batch(c, 1);       // host chains of the next batch, while the GPU works on this one
   HIPCHK(c, hipStreamSynchronize(c->stream));
   if (int r = prof_collect(c, nprof)) return r;
   if (span) {                                          // the graph's span over its W - 1 hot launches (+ the init and count launches: an upper bound)
@@ -926,6 +1055,10 @@ int run_mc_local(pocs_ctx* c) {
   }
   c->mc_counts.resize(R);
   memcpy(c->mc_counts.data(), (double*)c->h_pin + pl.total, R * sizeof(unsigned long long));
+  if (c->nplans) {                                     // slot order -> the caller's plan order
+    const std::vector<unsigned long long> by_slot = c->mc_counts;
+    for (size_t p = 0; p < R; ++p) c->mc_counts[p] = by_slot[(size_t)c->plan_slot[1][p]];
+  }
   c->last_mc_count = count;
   c->last_kind = 2;
   return POCS_OK;
@@ -1024,7 +1157,7 @@ void pocs_destroy(pocs_ctx* c) {
     if (c->ev_seq[1]) hipEventDestroy(c->ev_seq[1]);
     DevBuf* all[] = {&c->d_env, &c->d_sensor, &c->d_hdr, &c->d_chain, &c->d_state, &c->d_param,
                      &c->d_moments, &c->d_partial, &c->d_sx, &c->d_sy, &c->d_st, &c->d_flags,
-                     &c->d_px, &c->d_py, &c->d_pt, &c->d_hits, &c->d_total, &c->d_ticket, &c->d_tables};
+                     &c->d_px, &c->d_py, &c->d_pt, &c->d_hits, &c->d_total, &c->d_ticket, &c->d_tables, &c->d_runplan};
     for (DevBuf* b : all) if (b->p) hipFree(b->p);
     if (c->h_pin) hipHostFree(c->h_pin);
     if (c->h_copy) hipHostFree(c->h_copy);
@@ -1116,6 +1249,7 @@ int pocs_set_initial_covariance(pocs_ctx* c, const double* m9) {
 int pocs_set_path_length(pocs_ctx* c, int W) {
   if (c) touch(c);
   if (!c) return POCS_E_ARG;
+  if (c->nplans) return fail(c, POCS_E_ORDER, "pocs_set_path_length while plans are set: clear them first with pocs_set_plans(ctx, 0, ...)");
   if (W < 1) return fail(c, POCS_E_ARG, "pathLength must be >= 1");
   if (W != c->W) { c->have_traj = false; c->have_odom = false; }
   c->W = W;
@@ -1125,6 +1259,7 @@ int pocs_set_path_length(pocs_ctx* c, int W) {
 int pocs_set_trajectory(pocs_ctx* c, const double* v, int W) {
   if (c) touch(c);
   if (!c) return POCS_E_ARG;
+  if (c->nplans) return fail(c, POCS_E_ORDER, "pocs_set_trajectory while plans are set: clear them first with pocs_set_plans(ctx, 0, ...)");
   if (c->W < 1) return fail(c, POCS_E_ORDER, "setTrajectory before setPathLength");
   if (W != c->W || !v) return fail(c, POCS_E_ARG, "setTrajectory needs 3*%d values", c->W);
   c->traj.assign(v, v + (size_t)3 * W);
@@ -1135,6 +1270,7 @@ int pocs_set_trajectory(pocs_ctx* c, const double* v, int W) {
 int pocs_set_odometry(pocs_ctx* c, const double* v, int Wm1) {
   if (c) touch(c);
   if (!c) return POCS_E_ARG;
+  if (c->nplans) return fail(c, POCS_E_ORDER, "pocs_set_odometry while plans are set: clear them first with pocs_set_plans(ctx, 0, ...)");
   if (c->W < 1) return fail(c, POCS_E_ORDER, "setOdometry before setPathLength");
   if (Wm1 != c->W - 1 || (Wm1 > 0 && !v)) return fail(c, POCS_E_ARG, "setOdometry needs 3*%d values", c->W - 1);
   c->odom.assign(v, v + (size_t)3 * Wm1);
@@ -1190,6 +1326,10 @@ int pocs_set_option(pocs_ctx* c, int option, long long value) {
       if (value < -1 || value > 1) return fail(c, POCS_E_ARG, "POCS_OPT_MC_NONTEMPORAL takes -1 (by size), 0 or 1");
       c->opt_mc_nt = value;
       break;
+    case POCS_OPT_PLAN_SEEDS:
+      if (value < 0 || value > 1) return fail(c, POCS_E_ARG, "POCS_OPT_PLAN_SEEDS takes 0 (plan p draws run p's stream) or 1 (common random numbers)");
+      c->opt_plan_seeds = value;
+      break;
     case POCS_OPT_RUN_AHEAD:
       if (value < 0 || value > 256) return fail(c, POCS_E_ARG, "run-ahead %lld outside 0..256", value);
       c->run_ahead = (int)value;                     // 0 = sized per call (ra_depth)
@@ -1202,9 +1342,61 @@ int pocs_set_option(pocs_ctx* c, int option, long long value) {
 int pocs_set_batch(pocs_ctx* c, int runs) {
   if (!c) return POCS_E_ARG;
   touch(c);
+  if (c->nplans) return fail(c, POCS_E_ORDER, "pocs_set_batch while plans are set (the batch is the plans): clear them first with pocs_set_plans(ctx, 0, ...)");
   if (runs < 1 || runs > 256) return fail(c, POCS_E_ARG, "batch %d outside 1..256", runs);
   if (c->gmm_open) return fail(c, POCS_E_ORDER, "pocs_set_batch inside a begin/end sequence");
   c->batch = runs;
+  return POCS_OK;
+}
+
+// The results of the last launch refer to the plans (or the plan) it evaluated: a new set of plans drops them.
+static void drop_results(pocs_ctx* c) {
+  c->batch_probs.clear(); c->mc_counts.clear(); c->probs.clear(); c->last_moments.clear(); c->batch_moments.clear();
+  c->h_chain.clear(); c->h_mu.clear(); c->h_cov.clear();
+  c->plan_slot[0].clear(); c->plan_slot[1].clear();
+  c->last_gmm_wp = -1; c->last_gmm_count = 0; c->last_mc_count = 0; c->last_kind = 0;
+  c->view = 0; c->batch_R = c->batch;
+}
+
+int pocs_set_plans(pocs_ctx* c, int P, const int* W, const double* trajs, const double* odoms) {
+  if (!c) return POCS_E_ARG;
+  touch(c);
+  if (c->gmm_open) return fail(c, POCS_E_ORDER, "pocs_set_plans inside a begin/end sequence");
+  if (P < 0 || P > 256) return fail(c, POCS_E_ARG, "plans: P = %d outside 0..256", P);
+  if (P == 0) {                                      // back to the single plan
+    if (c->nplans) {
+      c->W = c->single_W; c->batch = c->single_batch;
+      c->nplans = 0;
+      c->plan_W.clear(); c->plan_toff.clear(); c->plan_ooff.clear(); c->plan_traj.clear(); c->plan_odom.clear();
+      drop_results(c);
+    }
+    return POCS_OK;
+  }
+  if (!W || !trajs) return fail(c, POCS_E_ARG, "plans: null lengths or trajectories");
+  size_t nt = 0, no = 0;
+  int Wmax = 0;
+  for (int p = 0; p < P; ++p) {
+    if (W[p] < 1) return fail(c, POCS_E_ARG, "plans: plan %d has length %d (>= 1 needed)", p, W[p]);
+    nt += 3 * (size_t)W[p]; no += 3 * (size_t)(W[p] - 1);
+    Wmax = W[p] > Wmax ? W[p] : Wmax;
+  }
+  if (no > 0 && !odoms) return fail(c, POCS_E_ARG, "plans: null odometry");
+  if (c->shard_first >= 0) return fail(c, POCS_E_STATE, "plans: not with a shard (pocs_set_shard(ctx, -1, -1) first): multi-GPU plan batches are not supported");
+  if (c->xchg_connected) return fail(c, POCS_E_STATE, "plans: not on a context connected to the in-library exchange");
+  if (!c->nplans) { c->single_W = c->W; c->single_batch = c->batch; }
+  c->plan_W.assign(W, W + P);
+  c->plan_toff.assign((size_t)P, 0); c->plan_ooff.assign((size_t)P, 0);
+  for (int p = 1; p < P; ++p) {
+    c->plan_toff[(size_t)p] = c->plan_toff[(size_t)p - 1] + 3 * (size_t)W[p - 1];
+    c->plan_ooff[(size_t)p] = c->plan_ooff[(size_t)p - 1] + 3 * (size_t)(W[p - 1] - 1);
+  }
+  c->plan_traj.assign(trajs, trajs + nt);
+  if (no > 0) c->plan_odom.assign(odoms, odoms + no); else c->plan_odom.clear();
+  c->plan_odom.push_back(0.0);                       // (never read: keeps .data() of a set of one-waypoint plans non-null)
+  c->nplans = P;
+  c->W = Wmax;
+  c->batch = P;
+  drop_results(c);
   return POCS_OK;
 }
 
@@ -1233,6 +1425,7 @@ int pocs_set_shard(pocs_ctx* c, long long first, long long count) {
   if (c) touch(c);
   if (!c) return POCS_E_ARG;
   if (first == -1 && count == -1) { c->shard_first = -1; c->shard_count = -1; return POCS_OK; }   // whole range
+  if (c->nplans) return fail(c, POCS_E_STATE, "pocs_set_shard: plans are set (multi-GPU plan batches are not supported)");
   if (first < 0 || count < 0) return fail(c, POCS_E_ARG, "negative shard");
   c->shard_first = first; c->shard_count = count;
   return POCS_OK;
@@ -1269,7 +1462,7 @@ static int ra_depth(const pocs_ctx* c, int kind) {
   return (int)(want < 8 ? 8 : want > 64 ? 64 : want);
 }
 static bool ra_wanted(const pocs_ctx* c, int kind) {
-  return ra_depth(c, kind) > 1 && c->batch == 1 && c->shard_first < 0 && !c->opt_profile && !c->ext_moments && !c->gmm_open;
+  return ra_depth(c, kind) > 1 && c->batch == 1 && !c->nplans && c->shard_first < 0 && !c->opt_profile && !c->ext_moments && !c->gmm_open;
 }
 static void mc_fill_probs(pocs_ctx* c) {
   // getCollisionProportion, MCSimulator.h:324-330 (of the particles this context evaluated)
@@ -1346,6 +1539,7 @@ int pocs_mc_get_batch_counts(pocs_ctx* c, unsigned long long* out, int cap) {
 
 int pocs_gmm_begin(pocs_ctx* c) {
   if (!c) return POCS_E_ARG;
+  if (c->nplans) return fail(c, POCS_E_STATE, "pocs_gmm_begin: plans are set (the step API serves a single plan)");
   HIPCHK(c, hipSetDevice(c->device));
   ra_drop(c);
   c->ra_internal = false;
@@ -1401,6 +1595,7 @@ int pocs_xchg_create(pocs_ctx* c, int world, int rank, void* handle64) {
   if (world < 1 || world > POCS_XCHG_MAX_WORLD || rank < 0 || rank >= world)
     return fail(c, POCS_E_ARG, "exchange: world %d / rank %d outside 1..%d", world, rank, POCS_XCHG_MAX_WORLD);
   static_assert(sizeof(hipIpcMemHandle_t) == 64, "pocs.h promises a 64-byte handle");
+  if (c->nplans) return fail(c, POCS_E_STATE, "pocs_xchg_create: plans are set (multi-GPU plan batches are not supported)");
   HIPCHK(c, hipSetDevice(c->device));
   if (!c->xchg_own) {
     // FINE-GRAINED device memory: other GPUs write into it and this GPU polls it inside a running kernel.
@@ -1419,6 +1614,7 @@ int pocs_xchg_create(pocs_ctx* c, int world, int rank, void* handle64) {
 
 int pocs_xchg_connect(pocs_ctx* c, const void* handles, int world) {
   if (!c || !handles) return POCS_E_ARG;
+  if (c->nplans) return fail(c, POCS_E_STATE, "pocs_xchg_connect: plans are set (multi-GPU plan batches are not supported)");
   if (!c->xchg_own || world != c->xchg_world) return fail(c, POCS_E_ORDER, "pocs_xchg_connect before pocs_xchg_create (or another world size)");
   HIPCHK(c, hipSetDevice(c->device));
   for (int q = 0; q < world; ++q) {
@@ -1465,7 +1661,7 @@ int pocs_gmm_sample_exchange_local(pocs_ctx* c, int w) {
   if (int r = gmm_shard(c, &first, &count)) return r;
   pocs_gmm_launch a;
   fill_gmm_launch(c, &a, first, count, w);
-  a.advance_in_tail = (w + 1 < c->W) ? 1 : 0;
+  a.advance_in_tail = (w + 1 < c->W) ? a.run_lo + a.run_cnt : 0;
   a.exchange_in_tail = 1;
   for (int q = 0; q < c->xchg_world; ++q) a.xchg.buf[q] = (double*)c->xchg_peer[q];
   a.xchg.world = c->xchg_world; a.xchg.rank = c->xchg_rank;
@@ -1491,7 +1687,7 @@ int pocs_gmm_end(pocs_ctx* c, double* probability) {
                            (size_t)c->W * c->batch * c->K * POCS_NMOM * sizeof(double), hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipMemcpyAsync((double*)c->h_pin + pl.total + c->batch + 1, (unsigned*)c->d_ticket.p + POCS_SYNC_ABORT,
                            sizeof(unsigned), hipMemcpyDeviceToHost, c->stream));
-  prefetch_next_batch(c);          // host chains of the next batch, while the queued work drains
+  prefetch_next_batch(c, gmm_groups(c));          // host chains of the next batch, while the queued work drains
   HIPCHK(c, hipStreamSynchronize(c->stream));
   {
     unsigned gave_up = 0;
@@ -1504,7 +1700,20 @@ int pocs_gmm_end(pocs_ctx* c, double* probability) {
   return POCS_OK;
 }
 
-int pocs_get_path_length(const pocs_ctx* c) { return c ? c->W : POCS_E_ARG; }
+int pocs_get_path_length(const pocs_ctx* c) {
+  if (!c) return POCS_E_ARG;
+  if (c->nplans) return c->plan_W[(size_t)(c->view < c->nplans ? c->view : 0)];     // the selected plan's
+  return c->W;
+}
+
+namespace {
+// The batch slot that holds the selected run's data in the device buffers: the run itself, or -- the last launch of that
+// kind (0 GMM, 1 MC) was a call of plans -- the selected plan's slot.
+size_t view_slot(const pocs_ctx* c, int kind) {
+  const std::vector<int>& ps = c->plan_slot[kind];
+  return (c->nplans && (size_t)c->view < ps.size()) ? (size_t)ps[(size_t)c->view] : (size_t)c->view;
+}
+}  // namespace
 
 int pocs_get_waypoint_probabilities(pocs_ctx* c, double* out, int cap) {
   if (!c || !out) return POCS_E_ARG;
@@ -1527,10 +1736,11 @@ static int copy_out(pocs_ctx* c, void* dst, const void* src_dev, size_t bytes, s
 int pocs_get_gmm_state(pocs_ctx* c, int w, double* means3, double* covs9, double* weights, double* alive) {
   if (!c) return POCS_E_ARG;
   if (w < 0 || w > c->last_gmm_wp || !c->d_state.p) return fail(c, POCS_E_ARG, "no mixture for waypoint %d", w);
+  if (c->nplans && w >= pocs_get_path_length(c)) return fail(c, POCS_E_ARG, "no mixture for waypoint %d: plan %d has %d waypoints", w, c->view, pocs_get_path_length(c));
   HIPCHK(c, hipSetDevice(c->device));
   std::vector<double> s((size_t)c->K * POCS_STATE_STRIDE);
   HIPCHK(c, hipStreamSynchronize(c->stream));
-  const double* run_state = (double*)c->d_state.p + (size_t)c->view * c->W * s.size();    // [run][W][K*16]
+  const double* run_state = (double*)c->d_state.p + view_slot(c, 0) * c->W * s.size();    // [run][W][K*16]
   if (int r = copy_out(c, s.data(), run_state + (size_t)w * s.size(), s.size() * sizeof(double), 1, 0)) return r;
   for (int k = 0; k < c->K; ++k) {
     if (means3) memcpy(means3 + 3 * k, &s[(size_t)k * POCS_STATE_STRIDE], 3 * sizeof(double));
@@ -1543,10 +1753,14 @@ int pocs_get_gmm_state(pocs_ctx* c, int w, double* means3, double* covs9, double
 
 int pocs_get_host_chain(pocs_ctx* c, double* applied3, double* noisy3, double* z, double* mu3, double* cov9) {
   if (!c) return POCS_E_ARG;
-  const int steps = c->W - 1, L = c->sensor.L;
+  const int steps = pocs_get_path_length(c) - 1, L = c->sensor.L;
+  if (c->nplans) {                                   // the selected plan's chain (h_chain holds slot 0's)
+    if (c->h_chain.empty()) return fail(c, POCS_E_STATE, "no run yet");
+    compute_chain(c, seed_of_run(c, c->batch_base + plan_run(c, c->view)), plan_view(c, c->view));
+  }
   if (steps < 0 || c->h_chain.size() < (size_t)(steps > 0 ? steps : 1) * POCS_CHAIN_STRIDE)
     return fail(c, POCS_E_STATE, "no run yet");
-  if (c->view != 0) compute_chain(c, seed_of_run(c, c->batch_base + (uint64_t)c->view));   // h_chain holds run 0's
+  if (c->view != 0 && !c->nplans) compute_chain(c, seed_of_run(c, c->batch_base + (uint64_t)c->view), plan_view(c, -1));   // h_chain holds run 0's
   for (int i = 0; i < steps; ++i) {
     const double* rec = &c->h_chain[(size_t)i * POCS_CHAIN_STRIDE];
     if (applied3) memcpy(applied3 + 3 * i, rec, 3 * sizeof(double));
@@ -1590,7 +1804,7 @@ long long pocs_copy_gmm_samples(pocs_ctx* c, double* aos, int16_t* flags, long l
   if (cap < n) return fail(c, POCS_E_BUFFER, "need room for %lld samples", n);
   if (hipSetDevice(c->device) != hipSuccess || hipStreamSynchronize(c->stream) != hipSuccess)
     return fail(c, POCS_E_DEVICE, "sync failed");
-  const size_t off = (size_t)c->view * (size_t)sample_stride_of(n);          // this run's slice
+  const size_t off = view_slot(c, 0) * (size_t)sample_stride_of(n);          // this run's slice
   if (aos && copy_soa_as_aos(c, c->d_sx, c->d_sy, c->d_st, off, n, aos) < 0) return fail(c, POCS_E_DEVICE, "copy failed");
   if (flags && copy_out(c, flags, (const int16_t*)c->d_flags.p + off, (size_t)n * sizeof(int16_t), 1, 0) != POCS_OK)
     return fail(c, POCS_E_DEVICE, "copy failed");
@@ -1604,7 +1818,7 @@ long long pocs_copy_particles(pocs_ctx* c, double* aos, uint32_t* hits, long lon
   if (cap < n) return fail(c, POCS_E_BUFFER, "need room for %lld particles", n);
   if (hipSetDevice(c->device) != hipSuccess || hipStreamSynchronize(c->stream) != hipSuccess)
     return fail(c, POCS_E_DEVICE, "sync failed");
-  const size_t off = (size_t)c->view * (size_t)sample_stride_of(n);          // this run's slice
+  const size_t off = view_slot(c, 1) * (size_t)sample_stride_of(n);          // this run's slice
   if (aos && copy_soa_as_aos(c, c->d_px, c->d_py, c->d_pt, off, n, aos) < 0) return fail(c, POCS_E_DEVICE, "copy failed");
   if (hits && copy_out(c, hits, (const uint32_t*)c->d_hits.p + off, (size_t)n * sizeof(uint32_t), 1, 0) != POCS_OK)
     return fail(c, POCS_E_DEVICE, "copy failed");

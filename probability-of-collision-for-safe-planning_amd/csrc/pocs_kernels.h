@@ -77,7 +77,7 @@ struct pocs_gmm_launch {
   const pocs_run_header* hdr;    // [nruns] per-run seeds
   const pocs_env_dev* env;       // obstacle table (records only; M and the footprint travel below)
   const pocs_tables* tables;     // log / sector tables (pocs_math.h), staged to LDS
-  const double* chain;           // [nruns][W-1][POCS_CHAIN_STRIDE]
+  const double* chain;           // [nruns][W-1][POCS_CHAIN_STRIDE]  (a call of plans: W = the longest plan's length)
   const pocs_sensor* sensor;
   double* state;                 // [nruns][W][K*POCS_STATE_STRIDE]  mixture sampled at each waypoint
   double* param;                 // [nruns][W][K*POCS_PARAM_STRIDE]  its sampler parameters (incl. the cumulative component counts)
@@ -101,7 +101,9 @@ struct pocs_gmm_launch {
   int M;
   int waypoint;
   int store;
-  int advance_in_tail;           // 1: the last block also builds state/param[waypoint+1] (single GPU)
+  int advance_in_tail;           // > 0: the last block of run r < advance_in_tail also builds state/param[waypoint+1] (single GPU;
+                                 // run_lo + run_cnt, except in a call of plans: the runs whose plan ends at this waypoint are the
+                                 // tail of the launch's runs and have no waypoint + 1); 0: none
   int exchange_in_tail;          // 1: ... after exchanging the run's moments with the other ranks through `xchg` (sharded)
   int xchg_epoch_from_header;    // 1: the exchange's call number comes from hdr[run].pad (whole calls replayed from a graph), not from xchg
   int lone;                      // 1: one run per call -- no tickets, no closer: every block of waypoint w's launch adds the
@@ -129,6 +131,8 @@ struct pocs_mc_launch {               // blockIdx.y = run of the batch, like poc
   int W;
   double mu0[3];
   double L0[6];
+  const double* run_plan;              // a call of plans: [nruns][4] = start mean (3) and number of steps of each run's plan
+                                       // (k_mc_init, k_mc_fused); null: mu0 and `step` hold for every run
   int step;                            // k_mc_step: control index; k_mc_fused: number of steps
   int nruns;
   int nontemporal;                     // k_mc_step: the batch's state exceeds the Infinity Cache, stream past it

@@ -1174,6 +1174,9 @@ __global__ __launch_bounds__(TB, (LONE ? 1 : POCS_GMM_BLOCKS_PER_CU) * TB / 256)
   // (256 bytes of scratch per lane instead of 60).
   auto closer = [&](const int rb) __attribute__((always_inline)) -> bool {
     const int r = r0 + rb;
+    // (a call of plans: a run whose plan ends at w has no waypoint w + 1 -- no chain record, no state / param rows to build;
+    // those runs are the tail of the launch's, and advance_in_tail is where they begin)
+    const bool adv = r < a.advance_in_tail;
     if (tid == 0) acquire_agent();
     __syncthreads();
     // the run's rows and -- one GPU -- what the mixture advance wants besides their sums (state[w], the chain record, the
@@ -1181,11 +1184,11 @@ __global__ __launch_bounds__(TB, (LONE ? 1 : POCS_GMM_BLOCKS_PER_CU) * TB / 256)
     const adv_ptrs ap = advance_ptrs(a, K, w + 1, r, sm.adv());
     double* const l_mom = ap.l_mom;
     double advv[4];
-    advance_request<true>(ap, false, tid, TB, advv, a.advance_in_tail != 0);
+    advance_request<true>(ap, false, tid, TB, advv, adv);
     close_rows<K, TB> cr;
     cr.request(close_rows_of<K>(a, a.partial, r), 1 << a.vs_shift, tid);
     requests_issued();
-    if (a.advance_in_tail) advance_commit(ap, false, tid, TB, advv);
+    if (adv) advance_commit(ap, false, tid, TB, advv);
     gmm_close_sums<K, TB, true>(a, w, r, sm.par[rb], sm.stage(), l_mom, tid, a.partial, true, cr);
     POCS_STAMP(5);
     if (a.exchange_in_tail) {
@@ -1205,7 +1208,7 @@ __global__ __launch_bounds__(TB, (LONE ? 1 : POCS_GMM_BLOCKS_PER_CU) * TB / 256)
       if (!gmm_exchange_rows(a, a.xchg, epoch, parity, K, w, r, l_mom, l_mom, tid, TB, &sm.nkeep[0] /* free by now */)) return false;
       __syncthreads();                                 // the world's sums are in l_mom for the advance (which no longer starts with a staging barrier)
     }
-    if (a.advance_in_tail) advance_block(a, K, w + 1, r, sm.adv(), sm.spec(), true, tid, TB, true);     // (staged above; gmm_close_sums' barriers lie between)
+    if (adv) advance_block(a, K, w + 1, r, sm.adv(), sm.spec(), true, tid, TB, true);     // (staged above; gmm_close_sums' barriers lie between)
     __syncthreads();
     POCS_STAMP(6);
     POCS_STAMP_COUNT(14);
@@ -1247,6 +1250,25 @@ __device__ __forceinline__ mc_run_view mc_view(const pocs_mc_launch& a) {
   return v;
 }
 
+// Where run blockIdx.y starts and how many controls it drives (k_mc_fused): the launch's mu0 / step, or -- a call of
+// plans -- its own plan's start and length (pocs_mc_launch::run_plan).
+struct mc_run_start {
+  double mu[3];
+  int steps;
+};
+__device__ __forceinline__ mc_run_start mc_start(const pocs_mc_launch& a) {
+  mc_run_start s;
+  if (a.run_plan) {
+    const double* q = a.run_plan + 4 * (size_t)blockIdx.y;
+    s.mu[0] = q[0]; s.mu[1] = q[1]; s.mu[2] = q[2];
+    s.steps = (int)q[3];
+  } else {
+    s.mu[0] = a.mu0[0]; s.mu[1] = a.mu0[1]; s.mu[2] = a.mu0[2];
+    s.steps = a.step;
+  }
+  return s;
+}
+
 __global__ __launch_bounds__(POCS_BLOCK) void k_mc_init(pocs_mc_launch a) {
   __shared__ double s_obs[POCS_MAX_OBSTACLES * POCS_OBS_STRIDE];
   __shared__ pocs_footprint s_fp;
@@ -1257,14 +1279,15 @@ __global__ __launch_bounds__(POCS_BLOCK) void k_mc_init(pocs_mc_launch a) {
   const mc_run_view v = mc_view(a);
   const pocs_footprint fp = s_fp;
   const int M = s_M;
+  const mc_run_start st = mc_start(a);
   const long long stride = (long long)gridDim.x * POCS_BLOCK;
   for (long long i = (long long)blockIdx.x * POCS_BLOCK + threadIdx.x; i < a.count; i += stride) {
     double z[3];
     uint32_t spare;
     pocs_normal3(v.seed, (uint64_t)(a.first + i), 0u, POCS_STREAM_MCINIT, z, &spare);
-    const double x = fma(a.L0[0], z[0], a.mu0[0]);
-    const double y = fma(a.L0[2], z[1], fma(a.L0[1], z[0], a.mu0[1]));
-    const double t = fma(a.L0[5], z[2], fma(a.L0[4], z[1], fma(a.L0[3], z[0], a.mu0[2])));
+    const double x = fma(a.L0[0], z[0], st.mu[0]);
+    const double y = fma(a.L0[2], z[1], fma(a.L0[1], z[0], st.mu[1]));
+    const double t = fma(a.L0[5], z[2], fma(a.L0[4], z[1], fma(a.L0[3], z[0], st.mu[2])));
     v.x[i] = x; v.y[i] = y; v.th[i] = t;
     v.hits[i] = pocs_pose_collides(x, y, t, &fp, s_obs, M, &s_tab) ? 1u : 0u;
   }
@@ -1316,16 +1339,17 @@ __global__ __launch_bounds__(POCS_BLOCK) void k_mc_fused(pocs_mc_launch a) {
   const mc_run_view v = mc_view(a);
   const pocs_footprint fp = s_fp;
   const int M = s_M;
+  const mc_run_start st = mc_start(a);             // (its steps: uniform per block, blockIdx.y being the run)
   const long long stride = (long long)gridDim.x * POCS_BLOCK;
   for (long long i = (long long)blockIdx.x * POCS_BLOCK + threadIdx.x; i < a.count; i += stride) {
     double z[3];
     uint32_t spare;
     pocs_normal3(v.seed, (uint64_t)(a.first + i), 0u, POCS_STREAM_MCINIT, z, &spare);
-    double x = fma(a.L0[0], z[0], a.mu0[0]);
-    double y = fma(a.L0[2], z[1], fma(a.L0[1], z[0], a.mu0[1]));
-    double t = fma(a.L0[5], z[2], fma(a.L0[4], z[1], fma(a.L0[3], z[0], a.mu0[2])));
+    double x = fma(a.L0[0], z[0], st.mu[0]);
+    double y = fma(a.L0[2], z[1], fma(a.L0[1], z[0], st.mu[1]));
+    double t = fma(a.L0[5], z[2], fma(a.L0[4], z[1], fma(a.L0[3], z[0], st.mu[2])));
     unsigned h = pocs_pose_collides(x, y, t, &fp, s_obs, M, &s_tab) ? 1u : 0u;
-    for (int s = 0; s < a.step; ++s) {
+    for (int s = 0; s < st.steps; ++s) {
       const double* u = v.chain + (size_t)s * POCS_CHAIN_STRIDE + 6;   // wave-uniform
       const double u0 = u[0], u1 = u[1], u2 = u[2];
       double sn, cs;
