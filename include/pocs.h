@@ -182,7 +182,8 @@ int pocs_gmm_end(pocs_ctx* ctx, double* probability);
  * rank's moments of waypoint w into its slot of EVERY rank's buffer (one hop over xGMI), waits for the
  * world's slots in its own buffer, adds them in rank order (every rank the same bits) and builds the
  * mixture of waypoint w+1, so the sequence per waypoint is sample_local(w), exchange_local(w) -- no
- * advance_local, no all-reduce.  Setup, once: pocs_xchg_create on every rank (returns the 64-byte IPC
+ * advance_local, no all-reduce.  sample_local and step_local never exchange themselves, moments buffer bound
+ * or not: their moments stay the shard's until the caller's exchange.  Setup, once: pocs_xchg_create on every rank (returns the 64-byte IPC
  * handle of its buffer), the caller gathers the handles (any host channel), pocs_xchg_connect(handles of
  * rank 0 .. world-1, 64 bytes each).  world <= 8, batch <= 256.
  * Two rules for connected contexts: (1) LOCK STEP -- every rank calls pocs_gmm_begin the same number of times
@@ -204,7 +205,8 @@ int pocs_gmm_exchange_local(pocs_ctx* ctx, int waypoint);
  * probabilities; the getters show the whole mixture's moments and states.  The call's number -- part of every row's epoch --
  * travels in the run headers uploaded per call, so the replayed graph needs no re-capture.  Rules as below: lock step (every
  * connected rank makes the same calls in the same order), nobody leaves early; a peer that never arrives makes the call return
- * POCS_E_DEVICE after the kernel's bounded wait.
+ * POCS_E_DEVICE after the kernel's bounded wait.  Only the whole call exchanges by itself: on the same context the step API
+ * (pocs_gmm_sample_local / pocs_gmm_step_local) leaves the shard's sums for pocs_gmm_exchange_local or the caller's all-reduce.
  * The same exchange one waypoint at a time, launches issued by the caller (POCS_ONEHOP=3; round 3's default):
  * POCS_ONEHOP=1 is the two-launch form above, POCS_ONEHOP=0 one RCCL all-reduce per waypoint): the block that closes a run's
  * waypoint is also its messenger -- it sends the shard's moments, waits for the world's, adds them in rank

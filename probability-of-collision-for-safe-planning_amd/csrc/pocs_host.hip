@@ -636,6 +636,8 @@ int gmm_upload_run(pocs_ctx* c) {
 // A whole-run call of a context that is CONNECTED to its peers (pocs_xchg_connect) and holds a shard exchanges every
 // run's moments in the closing block of its launch (k_gmm_step, exchange_in_tail): the call is then the sharded
 // estimation in ONE library call -- the same graph replay, the same two sub-batches as on one GPU, no host in the loop.
+// Only the whole-run call (enqueue_gmm_all) asks enqueue_step for that exchange: the step API's sample launches
+// (pocs_gmm_sample_local / pocs_gmm_step_local) leave the shard's sums to the caller's exchange, whatever the context.
 bool whole_call_exchanges(const pocs_ctx* c) { return c->xchg_connected && c->shard_first >= 0 && !c->ext_moments; }
 
 void fill_gmm_launch(pocs_ctx* c, pocs_gmm_launch* a, long long first, long long count, int w,
@@ -689,15 +691,16 @@ void set_lone(pocs_ctx* c, pocs_gmm_launch* a, int w) {
   a->partial_prev = (double*)c->d_partial.p + (size_t)((w + 1) & 1) * half;
 }
 
-// adv_cnt >= 0 (a call of plans): only the first adv_cnt of the launch's runs go on past waypoint w
-int enqueue_step(pocs_ctx* c, long long first, long long count, int w, bool advance_in_tail, int prof_slot,
+// adv_cnt >= 0 (a call of plans): only the first adv_cnt of the launch's runs go on past waypoint w.  exchange: the closers
+// exchange the run's moments with the peers, the call's number read from the run headers (the whole-run call only, above)
+int enqueue_step(pocs_ctx* c, long long first, long long count, int w, bool advance_in_tail, bool exchange, int prof_slot,
                  hipStream_t stream = nullptr, int run_lo = 0, int run_cnt = -1, int groups = 1, bool lone = false, int adv_cnt = -1) {
   pocs_gmm_launch a;
   if (!stream) stream = c->stream;
   fill_gmm_launch(c, &a, first, count, w, run_lo, run_cnt, groups);
   a.advance_in_tail = (advance_in_tail && w + 1 < c->W) ? a.run_lo + (adv_cnt >= 0 ? adv_cnt : a.run_cnt) : 0;   // (the runs below it advance)
   if (lone) set_lone(c, &a, w);
-  if (whole_call_exchanges(c)) {
+  if (exchange) {
     a.exchange_in_tail = 1;
     a.xchg_epoch_from_header = 1;
     for (int q = 0; q < c->xchg_world; ++q) a.xchg.buf[q] = (double*)c->xchg_peer[q];
@@ -752,7 +755,7 @@ int enqueue_gmm_all(pocs_ctx* c, long long first, long long count, bool prof) {
   if (prof) HIPCHK(c, hipEventRecord(c->ev_seq[0], c->stream));
   if (G > 1) HIPCHK(c, hipEventRecord(c->ev_fork, c->stream));
   for (int g = 1; g < G; ++g) HIPCHK(c, hipStreamWaitEvent(c->side_stream[g - 1], c->ev_fork, 0));
-  const bool lone = lone_call(c);
+  const bool lone = lone_call(c), exchange = whole_call_exchanges(c);
   // a call of plans: the launch of waypoint w covers the runs whose plan is longer than w -- a prefix of every
   // sub-batch's slots (plan_layout) -- and the closers of those whose plan ends at w do not advance
   const std::vector<int> Ws = slot_lengths(c, plan_layout(c, G));
@@ -769,7 +772,7 @@ int enqueue_gmm_all(pocs_ctx* c, long long first, long long count, bool prof) {
           continue;
         }
       }
-      if (int r = enqueue_step(c, first, count, w, true, (prof && g == 0) ? w : -1, st, lo, cnt, G, lone, adv)) return r;
+      if (int r = enqueue_step(c, first, count, w, true, exchange, (prof && g == 0) ? w : -1, st, lo, cnt, G, lone, adv)) return r;
     }
   if (lone) {                                        // the last waypoint's rows -> moments[W-1]
     pocs_gmm_launch a;
@@ -1571,7 +1574,7 @@ int pocs_gmm_sample_local(pocs_ctx* c, int w) {
   if (w != c->last_gmm_adv) return fail(c, POCS_E_ORDER, "waypoint %d sampled before pocs_gmm_advance_local(%d)", w, w);
   long long first, count;
   if (int r = gmm_shard(c, &first, &count)) return r;
-  if (int r = enqueue_step(c, first, count, w, false, c->opt_profile == 1 ? w : -1)) return r;
+  if (int r = enqueue_step(c, first, count, w, false, false, c->opt_profile == 1 ? w : -1)) return r;
   c->last_gmm_wp = w;
   c->last_gmm_count = count;
   return POCS_OK;
