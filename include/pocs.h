@@ -144,6 +144,32 @@ int pocs_select_batch_run(pocs_ctx* ctx, int run);   /* the getters below (waypo
  * length, and the launch of waypoint w covers the plans longer than w. */
 int pocs_set_plans(pocs_ctx* ctx, int P, const int* W, const double* trajs, const double* odoms);
 
+/* ---- a risk bound for calls of plans (ours) ------------------------------------------------
+ * What a planner does with a plan's probability is a chance constraint: a candidate above the bound it plans under is
+ * thrown away, however far above.  A plan's probability 1 - prod_w (1 - p_w) never decreases along the plan, so with a
+ * bound in (0, 1) set, a GMM call of plans (pocs_run_gmm_estimation while plans are set) stops plan p at the FIRST waypoint
+ * s whose running probability c_s = 1 - prod_{v <= s} (1 - p_v) is >= bound -- formed exactly as the final probability is
+ * (p_v = collisions / numGMMSamples, the product in waypoint order, IEEE double) -- and evaluates nothing of it beyond:
+ *   - pocs_get_batch_probabilities()[p] (pocs_run_gmm_estimation's value for plan 0) is c_s: a lower bound of the plan's
+ *     full probability that is already >= bound.  A plan that never reaches the bound, or reaches it only at its last
+ *     waypoint, gets its full probability as without a bound;
+ *   - pocs_get_plan_evaluated: per plan, in plan order, the number of waypoints evaluated, 1 <= E[p] <= W[p]; E[p] < W[p]
+ *     means the plan was stopped.  POCS_E_BUFFER for cap < P, POCS_E_STATE when the last call was not a call of plans;
+ *     W[p] after a pocs_run_simulation call or with the bound off;
+ *   - with plan p selected, pocs_get_waypoint_probabilities writes (and returns) E[p] values, pocs_get_moments and
+ *     pocs_get_gmm_state cover waypoints 0 .. E[p] - 1 (POCS_E_ARG beyond), pocs_get_path_length stays W[p], and
+ *     pocs_copy_gmm_samples returns the samples of waypoint E[p] - 1, the last one drawn for that plan;
+ *   - everything computed before the stop is, bit for bit, what the same plan gets with the bound off; seeds and the run
+ *     counter (POCS_OPT_PLAN_SEEDS) do not depend on who stopped.
+ * bound >= 1.0 (the default is 1.0): off -- every call is what it is without this function.  bound <= 0 or NaN: POCS_E_ARG.
+ * The bound belongs to the context: it survives pocs_set_plans, and has no effect while no plans are set (pocs_set_batch,
+ * run-ahead, the step API; sharded contexts refuse plans).  pocs_run_simulation IGNORES it: the MC result is the share of
+ * particles that EVER collided, which the per-step kernels do not count between steps.
+ * The stop is decided and obeyed on the device, inside the call's one replayed graph; the host restates
+ * the rule on the moments it reads back, and a call whose two stops differ returns POCS_E_DEVICE. */
+int pocs_set_plan_risk_bound(pocs_ctx* ctx, double bound);
+int pocs_get_plan_evaluated(pocs_ctx* ctx, int* out, int cap);
+
 /* ---- sharding over GPUs (one process per GPU; the caller owns the collective) -----------
  * A context evaluates global sample / particle indices [first, first+count) of the N configured;
  * random draws are keyed by the GLOBAL index, so every sample, flag, survivor count and hit counter is the same

@@ -49,6 +49,8 @@ SIGNATURES = {
     "pocs_get_batch_probabilities": (C.c_int, [_vp, _dp, C.c_int]),
     "pocs_select_batch_run": (C.c_int, [_vp, C.c_int]),
     "pocs_set_plans": (C.c_int, [_vp, C.c_int, C.POINTER(C.c_int), _dp, _dp]),
+    "pocs_set_plan_risk_bound": (C.c_int, [_vp, C.c_double]),
+    "pocs_get_plan_evaluated": (C.c_int, [_vp, C.POINTER(C.c_int), C.c_int]),
     "pocs_set_shard": (C.c_int, [_vp, C.c_longlong, C.c_longlong]),
     "pocs_set_stream": (C.c_int, [_vp, _vp]),
     "pocs_gmm_begin": (C.c_int, [_vp]),
@@ -291,6 +293,18 @@ class Context:
         if hasattr(self, "_single_batch"):
             self._batch = self._single_batch
             del self._single_batch
+
+    def set_plan_risk_bound(self, bound):
+        """Calls of plans on the GMM path stop a plan at the first waypoint where its running probability reaches `bound`
+        (in (0, 1); >= 1.0 turns the bound off): include/pocs.h."""
+        self._chk(self.lib.pocs_set_plan_risk_bound(self.h, float(bound)))
+
+    def plan_evaluated(self):
+        """Waypoints evaluated per plan in the last call of plans (int32[P]); less than the plan's length = stopped."""
+        n = getattr(self, "_batch", 1)
+        out = np.zeros(n, dtype=np.int32)
+        got = self._chk(self.lib.pocs_get_plan_evaluated(self.h, out.ctypes.data_as(C.POINTER(C.c_int)), n))
+        return out[:got]
 
     def set_shard(self, first=-1, count=-1):
         """Evaluate global indices [first, first+count); no arguments = the whole range."""

@@ -95,6 +95,10 @@ struct pocs_ctx {
   int single_W = -1, single_batch = 1;
   long long opt_plan_seeds = 0;                   // POCS_OPT_PLAN_SEEDS
   std::vector<int> plan_slot[2];                  // the batch slot of plan p in the last call of plans: [0] GMM, [1] MC
+  // risk bound of calls of plans (pocs_set_plan_risk_bound): a plan whose running probability reaches it is not evaluated
+  // any further (k_gmm_step_risk decides and obeys on the device; gmm_combine restates the rule on the moments read back)
+  double risk_bound = 1.0;                        // >= 1: off
+  std::vector<int> plan_E;                        // [P] waypoints evaluated per plan in the last GMM call of plans (empty: there was none)
 
   // host image (headers | chains | initial mixtures) of the NEXT batch, computed while the GPU
   // works on the current one
@@ -111,6 +115,7 @@ struct pocs_ctx {
   DevBuf d_env, d_sensor, d_hdr, d_chain, d_state, d_param, d_moments, d_partial;
   DevBuf d_sx, d_sy, d_st, d_flags, d_px, d_py, d_pt, d_hits, d_total, d_ticket, d_tables;
   DevBuf d_runplan;                      // a call of plans: [R][4] start mean and steps per run (the MC kernels)
+  DevBuf d_surv;                         // a call of plans under a risk bound: [R] running survival product of every run
   // one-hop exchange (pocs_xchg_*): this rank's buffer, the peers' buffers as mapped here
   void* xchg_own = nullptr;
   void* xchg_peer[POCS_XCHG_MAX_WORLD] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
@@ -379,7 +384,7 @@ PinLayout pin_layout(const pocs_ctx* c) {
   p.runplan = p.state0 + R * K * POCS_STATE_STRIDE;
   p.moments = p.runplan + (c->nplans ? 4 * R : 0);
   p.total = p.moments + W * R * K * POCS_NMOM;
-  p.end = p.total + R + 2;                 // one u64 per run: MC totals
+  p.end = p.total + R + 2 + (R + 4) / 2 + 1;   // one u64 per run: MC totals; the call's give-up word and -- under a risk bound -- the R stop words behind it
   return p;
 }
 
@@ -448,10 +453,18 @@ int gmm_shard(pocs_ctx* c, long long* first, long long* count) {
   return POCS_OK;
 }
 
-// The synchronisation words of one call (pocs_kernels.h): [1] give-up code, [0], [2..3] pad, then the
+// A call of plans on the GMM path under a risk bound: the launches are k_gmm_step_risk (and never the lone form: a call of
+// ONE plan takes the ticket form then, which computes the same bits -- tests/test_gpu_parity.py::test_lone_call_changes_no_bit).
+// Off (the default, bound >= 1) and without plans nothing of a call changes: the same launches of the same kernels, the same
+// memset, the same copies.
+bool risk_active(const pocs_ctx* c) { return c->nplans > 0 && c->risk_bound < 1.0; }
+
+// The synchronisation words of one call (pocs_kernels.h): [1] give-up code, [0], [2..3] pad, then -- under a risk bound -- the
+// runs' stop words [R] (padded to 4: they travel back with the give-up word in one copy), then the
 // tickets [R][W], then -- sharded runs -- the closers' exchange waits [R][W]; a block of its own, a multiple of
 // 16 bytes, zeroed by ONE memset at the head of every call.
-size_t sync_ticket_offset(const pocs_ctx*) { return 4; }
+size_t sync_stop_offset(const pocs_ctx*) { return 4; }
+size_t sync_ticket_offset(const pocs_ctx* c) { return 4 + (risk_active(c) ? (((size_t)c->batch + 3) & ~(size_t)3) : 0); }
 size_t sync_xwait_offset(const pocs_ctx* c) { return sync_ticket_offset(c) + (size_t)c->batch * (size_t)(c->W > 0 ? c->W : 1); }
 size_t sync_words(const pocs_ctx* c) {
   const size_t n = sync_xwait_offset(c) + (size_t)c->batch * (size_t)(c->W > 0 ? c->W : 1);      // tickets, then the exchange waits
@@ -481,6 +494,8 @@ int gmm_prepare(pocs_ctx* c) {
   if (int r = ensure(c, c->d_ticket, sync_words(c) * sizeof(unsigned))) return r;
   if (c->nplans)
     if (int r = ensure(c, c->d_runplan, R * 4 * sizeof(double))) return r;
+  if (risk_active(c))
+    if (int r = ensure(c, c->d_surv, R * sizeof(double))) return r;
   if (c->opt_store) {
     const size_t n = R * (size_t)sample_stride_of(count);
     if (int r = ensure(c, c->d_sx, n * sizeof(double))) return r;
@@ -682,7 +697,7 @@ int enqueue_advance(pocs_ctx* c, int w) {
 // One run per call (no batch, no run-ahead) on one GPU: the launches close the previous waypoint in their heads
 // (k_gmm_step, "LONE"): 30.6 -> 27.5 us per waypoint at 10^6 samples, K = 3 (MI355X).  POCS_OPT_LONE_CALL = 0
 // keeps the ticket-and-closer form; the results are the same bits.
-bool lone_call(const pocs_ctx* c) { return c->opt_lone && c->batch == 1 && !c->ext_moments && !(c->xchg_connected && c->shard_first >= 0); }
+bool lone_call(const pocs_ctx* c) { return c->opt_lone && c->batch == 1 && !c->ext_moments && !(c->xchg_connected && c->shard_first >= 0) && !risk_active(c); }
 void set_lone(pocs_ctx* c, pocs_gmm_launch* a, int w) {
   const size_t half = ((size_t)1 << a->vs_shift) * c->K * POCS_NMOM;      // one run's rows
   a->lone = 1;
@@ -694,12 +709,19 @@ void set_lone(pocs_ctx* c, pocs_gmm_launch* a, int w) {
 // adv_cnt >= 0 (a call of plans): only the first adv_cnt of the launch's runs go on past waypoint w.  exchange: the closers
 // exchange the run's moments with the peers, the call's number read from the run headers (the whole-run call only, above)
 int enqueue_step(pocs_ctx* c, long long first, long long count, int w, bool advance_in_tail, bool exchange, int prof_slot,
-                 hipStream_t stream = nullptr, int run_lo = 0, int run_cnt = -1, int groups = 1, bool lone = false, int adv_cnt = -1) {
+                 hipStream_t stream = nullptr, int run_lo = 0, int run_cnt = -1, int groups = 1, bool lone = false, int adv_cnt = -1,
+                 bool risk = false) {
   pocs_gmm_launch a;
   if (!stream) stream = c->stream;
   fill_gmm_launch(c, &a, first, count, w, run_lo, run_cnt, groups);
   a.advance_in_tail = (advance_in_tail && w + 1 < c->W) ? a.run_lo + (adv_cnt >= 0 ? adv_cnt : a.run_cnt) : 0;   // (the runs below it advance)
   if (lone) set_lone(c, &a, w);
+  if (risk) {                                        // (the whole call of plans only: enqueue_gmm_all)
+    a.risk = 1;
+    a.stop = a.sync + sync_stop_offset(c);
+    a.surv = (double*)c->d_surv.p;
+    a.risk_bound = c->risk_bound;
+  }
   if (exchange) {
     a.exchange_in_tail = 1;
     a.xchg_epoch_from_header = 1;
@@ -755,7 +777,7 @@ int enqueue_gmm_all(pocs_ctx* c, long long first, long long count, bool prof) {
   if (prof) HIPCHK(c, hipEventRecord(c->ev_seq[0], c->stream));
   if (G > 1) HIPCHK(c, hipEventRecord(c->ev_fork, c->stream));
   for (int g = 1; g < G; ++g) HIPCHK(c, hipStreamWaitEvent(c->side_stream[g - 1], c->ev_fork, 0));
-  const bool lone = lone_call(c), exchange = whole_call_exchanges(c);
+  const bool lone = lone_call(c), exchange = whole_call_exchanges(c), risk = risk_active(c);
   // a call of plans: the launch of waypoint w covers the runs whose plan is longer than w -- a prefix of every
   // sub-batch's slots (plan_layout) -- and the closers of those whose plan ends at w do not advance
   const std::vector<int> Ws = slot_lengths(c, plan_layout(c, G));
@@ -772,7 +794,7 @@ int enqueue_gmm_all(pocs_ctx* c, long long first, long long count, bool prof) {
           continue;
         }
       }
-      if (int r = enqueue_step(c, first, count, w, true, exchange, (prof && g == 0) ? w : -1, st, lo, cnt, G, lone, adv)) return r;
+      if (int r = enqueue_step(c, first, count, w, true, exchange, (prof && g == 0) ? w : -1, st, lo, cnt, G, lone, adv, risk)) return r;
     }
   if (lone) {                                        // the last waypoint's rows -> moments[W-1]
     pocs_gmm_launch a;
@@ -792,9 +814,11 @@ int enqueue_gmm_results(pocs_ctx* c) {
   const PinLayout pl = pin_layout(c);
   HIPCHK(c, hipMemcpyAsync((double*)c->h_pin + pl.moments, moments_dev(c),
                            (size_t)W * c->batch * c->K * POCS_NMOM * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-  // the call's give-up word travels back with the results
+  // the call's give-up word travels back with the results -- and, under a risk bound, the runs' stop words [R] behind it
+  // (words 4 .. 4 + R of the block: the same copy, 3 + R words instead of one)
+  static_assert(POCS_SYNC_ABORT == 1, "the stop words follow the give-up word and two pad words");
   HIPCHK(c, hipMemcpyAsync((double*)c->h_pin + pl.total + c->batch + 1, (unsigned*)c->d_ticket.p + POCS_SYNC_ABORT,
-                           sizeof(unsigned), hipMemcpyDeviceToHost, c->stream));
+                           (risk_active(c) ? 3 + (size_t)c->batch : 1) * sizeof(unsigned), hipMemcpyDeviceToHost, c->stream));
   return POCS_OK;
 }
 
@@ -803,7 +827,8 @@ int enqueue_gmm_results(pocs_ctx* c) {
 // (a call of plans: v is the plan, which the moments hold in its batch slot, over its own W_p waypoints)
 void gmm_select_view(pocs_ctx* c, int v) {
   const bool plans = c->nplans && !c->plan_slot[0].empty();
-  const int W = plans ? c->plan_W[(size_t)v] : c->W, K = c->K, R = c->batch_R;
+  // (a plan stopped by the risk bound: its E[v] evaluated waypoints -- what lies behind them is whatever an earlier call left)
+  const int W = plans ? ((size_t)v < c->plan_E.size() ? c->plan_E[(size_t)v] : c->plan_W[(size_t)v]) : c->W, K = c->K, R = c->batch_R;
   const int slot = plans ? c->plan_slot[0][(size_t)v] : v;
   c->view = v;
   c->probs.assign(W, 0.0);
@@ -817,27 +842,43 @@ void gmm_select_view(pocs_ctx* c, int v) {
   }
 }
 
-void gmm_combine(pocs_ctx* c, const double* moments, double* probability) {
+// `stop` (a whole call of plans under a risk bound, else null): the device's stop word of every batch slot -- 0, or s + 1 for
+// a run whose closer of waypoint s found the running probability at the bound.  The rule is restated here on the moments read
+// back: plan p stops at the FIRST waypoint s with c_s = 1 - prod_{v <= s} (1 - p_v) >= bound, E[p] = s + 1 waypoints were
+// evaluated and its probability is c_s; the moments past E[p] - 1 are not read.  Device and host form c_s with the same
+// operations in the same order; if the two stops ever differ the call fails instead of reporting either.
+int gmm_combine(pocs_ctx* c, const double* moments, double* probability, const unsigned* stop = nullptr) {
   const int W = c->W, K = c->K, R = c->batch;          // moments: [W][R][K*11]
   c->batch_R = R;
   c->last_kind = 1;
   c->batch_moments.assign(moments, moments + (size_t)W * R * K * POCS_NMOM);
   c->batch_probs.assign(R, 0.0);
   const bool plans = c->nplans && !c->plan_slot[0].empty();
+  if (plans) c->plan_E = c->plan_W; else c->plan_E.clear();
   for (int r = 0; r < R; ++r) {                        // (a call of plans: r is the plan, in its slot, over its W_p waypoints)
     const int slot = plans ? c->plan_slot[0][(size_t)r] : r, Wr = plans ? c->plan_W[(size_t)r] : W;
+    const int dev = stop ? (int)stop[(size_t)slot] : 0;
+    if (dev < 0 || dev > Wr) return fail(c, POCS_E_DEVICE, "risk bound: the device stopped plan %d at waypoint %d of %d; results discarded", r, dev - 1, Wr);
+    const int Er = dev ? dev : Wr;
+    int host = 0;                                      // the host's stop word
     double prod = 1.0;
-    for (int w = 0; w < Wr; ++w) {
+    for (int w = 0; w < Er; ++w) {
       const double* m = moments + ((size_t)w * R + slot) * K * POCS_NMOM;
       double coll = 0.0;
       for (int k = 0; k < K; ++k) coll += m[(size_t)k * POCS_NMOM + 1];
       const double p = coll / (1.0 * (double)c->num_gmm);
       prod *= (1.0 - p);
+      if (stop && 1.0 - prod >= c->risk_bound) { host = w + 1; break; }
     }
+    if (host != dev)
+      return fail(c, POCS_E_DEVICE, "risk bound: plan %d stops at waypoint %d on the device and at %d on the host (-1: not at all); results discarded",
+                  r, dev - 1, host - 1);
     c->batch_probs[r] = 1.0 - prod;
+    if (plans) c->plan_E[(size_t)r] = Er;
   }
   gmm_select_view(c, 0);
   *probability = c->batch_probs[0];
+  return POCS_OK;
 }
 
 std::string config_key(const pocs_ctx* c, long long first, long long count, const char* tag) {
@@ -849,6 +890,11 @@ std::string config_key(const pocs_ctx* c, long long first, long long count, cons
   if (c->nplans) {                                   // a call of plans: one launch per waypoint and LIVE sub-batch, by the plans' lengths
     key += " P";
     for (int p = 0; p < c->nplans; ++p) key += (p ? "," : "") + std::to_string(c->plan_W[(size_t)p]);
+    if (risk_active(c)) {                            // the bound is baked into the launches (and selects their kernel)
+      char rb[48];
+      snprintf(rb, sizeof rb, " rb%a", c->risk_bound);
+      key += rb;
+    }
   }
   return key;
 }
@@ -930,7 +976,16 @@ int run_gmm_full(pocs_ctx* c, double* probability) {
     memcpy(&gave_up, (double*)c->h_pin + pin_layout(c).total + c->batch + 1, sizeof gave_up);
     if (gave_up) return fail(c, POCS_E_DEVICE, "a bounded wait expired on the device (code %u); results discarded", gave_up);
   }
-  gmm_combine(c, (double*)c->h_pin + pin_layout(c).moments, probability);
+  {
+    const PinLayout pl = pin_layout(c);
+    // (the stop words: behind the give-up word and its two pad words)
+    const unsigned* stop = risk_active(c) ? (const unsigned*)((double*)c->h_pin + pl.total + c->batch + 1) + 3 : nullptr;
+    if (int r = gmm_combine(c, (double*)c->h_pin + pl.moments, probability, stop)) {
+      c->batch_probs.clear(); c->probs.clear(); c->last_moments.clear(); c->batch_moments.clear(); c->plan_E.clear();
+      c->last_kind = 0; c->last_gmm_wp = -1;
+      return r;
+    }
+  }
   c->last_gmm_count = count;
   c->last_gmm_wp = c->W - 1;
   lap("combined");
@@ -1160,7 +1215,7 @@ void pocs_destroy(pocs_ctx* c) {
     if (c->ev_seq[1]) hipEventDestroy(c->ev_seq[1]);
     DevBuf* all[] = {&c->d_env, &c->d_sensor, &c->d_hdr, &c->d_chain, &c->d_state, &c->d_param,
                      &c->d_moments, &c->d_partial, &c->d_sx, &c->d_sy, &c->d_st, &c->d_flags,
-                     &c->d_px, &c->d_py, &c->d_pt, &c->d_hits, &c->d_total, &c->d_ticket, &c->d_tables, &c->d_runplan};
+                     &c->d_px, &c->d_py, &c->d_pt, &c->d_hits, &c->d_total, &c->d_ticket, &c->d_tables, &c->d_runplan, &c->d_surv};
     for (DevBuf* b : all) if (b->p) hipFree(b->p);
     if (c->h_pin) hipHostFree(c->h_pin);
     if (c->h_copy) hipHostFree(c->h_copy);
@@ -1356,7 +1411,7 @@ int pocs_set_batch(pocs_ctx* c, int runs) {
 static void drop_results(pocs_ctx* c) {
   c->batch_probs.clear(); c->mc_counts.clear(); c->probs.clear(); c->last_moments.clear(); c->batch_moments.clear();
   c->h_chain.clear(); c->h_mu.clear(); c->h_cov.clear();
-  c->plan_slot[0].clear(); c->plan_slot[1].clear();
+  c->plan_slot[0].clear(); c->plan_slot[1].clear(); c->plan_E.clear();
   c->last_gmm_wp = -1; c->last_gmm_count = 0; c->last_mc_count = 0; c->last_kind = 0;
   c->view = 0; c->batch_R = c->batch;
 }
@@ -1401,6 +1456,26 @@ int pocs_set_plans(pocs_ctx* c, int P, const int* W, const double* trajs, const 
   c->batch = P;
   drop_results(c);
   return POCS_OK;
+}
+
+int pocs_set_plan_risk_bound(pocs_ctx* c, double bound) {
+  if (!c) return POCS_E_ARG;
+  touch(c);                                          // (the epoch is part of the graphs' key: no graph captured for another bound is replayed)
+  if (!(bound > 0.0)) return fail(c, POCS_E_ARG, "risk bound %g: a probability in (0, 1), or >= 1 for none", bound);     // (NaN too)
+  if (c->gmm_open) return fail(c, POCS_E_ORDER, "pocs_set_plan_risk_bound inside a begin/end sequence");
+  c->risk_bound = bound < 1.0 ? bound : 1.0;
+  return POCS_OK;
+}
+
+int pocs_get_plan_evaluated(pocs_ctx* c, int* out, int cap) {
+  if (!c || !out) return POCS_E_ARG;
+  const int kind = c->last_kind;                     // 1 GMM, 2 MC -- which ignores the bound: every plan is driven to its end
+  if (!c->nplans || kind == 0 || c->plan_slot[kind - 1].empty() || (kind == 1 && c->plan_E.empty()))
+    return fail(c, POCS_E_STATE, "pocs_get_plan_evaluated: the last call was not a call of plans");
+  const std::vector<int>& E = kind == 1 ? c->plan_E : c->plan_W;
+  if ((int)E.size() > cap) return fail(c, POCS_E_BUFFER, "need %zu ints", E.size());
+  memcpy(out, E.data(), E.size() * sizeof(int));
+  return (int)E.size();
 }
 
 int pocs_get_batch_probabilities(pocs_ctx* c, double* out, int cap) {
@@ -1698,7 +1773,7 @@ int pocs_gmm_end(pocs_ctx* c, double* probability) {
     if (gave_up) { c->gmm_open = false; return fail(c, POCS_E_DEVICE, "a bounded wait expired on the device (code %u: 4 = a peer's moments never arrived); results discarded", gave_up); }
   }
   if (int r = prof_collect(c, (size_t)c->W)) return r;
-  gmm_combine(c, (double*)c->h_pin + pl.moments, probability);
+  (void)gmm_combine(c, (double*)c->h_pin + pl.moments, probability);      // (no risk bound in the step API: cannot fail)
   c->gmm_open = false;
   return POCS_OK;
 }
@@ -1740,6 +1815,8 @@ int pocs_get_gmm_state(pocs_ctx* c, int w, double* means3, double* covs9, double
   if (!c) return POCS_E_ARG;
   if (w < 0 || w > c->last_gmm_wp || !c->d_state.p) return fail(c, POCS_E_ARG, "no mixture for waypoint %d", w);
   if (c->nplans && w >= pocs_get_path_length(c)) return fail(c, POCS_E_ARG, "no mixture for waypoint %d: plan %d has %d waypoints", w, c->view, pocs_get_path_length(c));
+  if (c->nplans && (size_t)c->view < c->plan_E.size() && w >= c->plan_E[(size_t)c->view])
+    return fail(c, POCS_E_ARG, "no mixture for waypoint %d: plan %d was stopped by the risk bound after %d waypoints", w, c->view, c->plan_E[(size_t)c->view]);
   HIPCHK(c, hipSetDevice(c->device));
   std::vector<double> s((size_t)c->K * POCS_STATE_STRIDE);
   HIPCHK(c, hipStreamSynchronize(c->stream));

@@ -115,6 +115,14 @@ struct pocs_gmm_launch {
   int upb;                       // units per block (<= VS)
   int blocks;
   int run_lo, run_cnt;           // the runs of the batch this launch works on
+  // a call of plans under a risk bound (pocs_set_plan_risk_bound; behind everything else: the other launches' argument offsets stay)
+  int risk;                      // 1: the launch is k_gmm_step_risk, whose closers decide the stop of their run and whose heads obey it
+  int risk_pad;
+  unsigned* stop;                // [nruns] 0 = the run is live, w + 1 = its closer of waypoint w found the running probability at the
+                                 // bound -- no later launch works on the run; part of the call's zeroed synchronisation block
+  double* surv;                  // [nruns] the run's running survival product prod_{v <= w} (1 - p_v), kept by its closers (the closer
+                                 // of waypoint 0 starts from 1.0: never read before it is written)
+  double risk_bound;             // a run stops at the first waypoint w with 1 - surv >= risk_bound
 };
 #define POCS_SYNC_ABORT 1
 

@@ -1044,10 +1044,28 @@ __device__ __forceinline__ void gmm_close_sums(const pocs_gmm_launch& a, const i
 // otherwise wait for one of them to do it -- and keeps param[w] in LDS; block 0 writes moments[w-1], state[w],
 // param[w] out for the getters.  The tail is the rows' stores and nothing else; a one-block launch
 // (k_gmm_close) adds the last waypoint's rows.  Same functions, same order of additions: the same bits.
-template <int K, bool STORE, int TB, bool LONE>
-__global__ __launch_bounds__(TB, (LONE ? 1 : POCS_GMM_BLOCKS_PER_CU) * TB / 256) void k_gmm_step(pocs_gmm_launch a) {   // (lone: one block per CU, its LDS)
+//
+// RISK (a call of plans under a risk bound, pocs_set_plan_risk_bound; the kernel k_gmm_step_risk, never LONE): a run whose
+// running probability 1 - prod_{v <= w} (1 - p_v) has reached the bound is not worked on any further.
+//   deciding  the closer of (r, w) has the run's collision counts in LDS the moment it has added the rows: one lane forms p_w
+//             and the survival product exactly as the host's combine does (plain / and *, this file is built without
+//             contraction), keeps the product in surv[r] and, at the bound, publishes stop[r] = w + 1 and does not advance
+//             the mixture (as for a plan that ends at w);
+//   obeying   a head asks for the stop words of its (at most two) runs with its other requests -- the same round trip -- and
+//             a block whose runs have all stopped returns behind it (nothing staged, no cull, no rows, no ticket); a block
+//             that straddles a stopped and a live run narrows its range to the live run's units and takes that run's ticket
+//             only.  Which blocks meet a run (b_first, b_last) does not change: a stopped run's tickets are never drawn, so
+//             nobody closes it and nobody waits for it.
+// No fence of its own: stop[r] and surv[r] are written by a closer of waypoint w's launch and read by waypoint w + 1's launch
+// of the SAME sub-batch -- a run never changes sub-batch (plan_layout) --, i.e. behind a kernel boundary on one stream, as
+// state / param[w + 1] are; write-through stores and L1-bypassing loads like those.
+template <int K, bool STORE, int TB, bool LONE, bool RISK>
+__device__ __forceinline__ void gmm_step_block(const pocs_gmm_launch a) {      // (by value, as a kernel holds its argument)
   typedef gmm_smem<K, TB> smem_t;
+  static_assert(!(LONE && RISK), "the lone form closes in its heads: a call under a risk bound takes the ticket form");
   constexpr int SUB = smem_t::SUB, NW = smem_t::NW;
+  // (the block's LDS, declared here and not handed in by the kernel: every instantiation is inlined into exactly one kernel,
+  // and the accesses stay LDS accesses from the front end on)
   __shared__ smem_t sm;
   // (lone form: one block per CU, the whole LDS is its own) the normals of the unit's first POCS_LONE_PRE iterations
   __shared__ double s_zpre[LONE ? POCS_LONE_PRE * 6 * TB : 2];
@@ -1056,9 +1074,11 @@ __global__ __launch_bounds__(TB, (LONE ? 1 : POCS_GMM_BLOCKS_PER_CU) * TB / 256)
   const int w = a.waypoint;
   const int t_lo = a.run_lo << a.vs_shift, t_hi = (a.run_lo + a.run_cnt) << a.vs_shift;    // this launch's units
   const int bx = (int)blockIdx.x;
-  const int t0 = t_lo + bx * a.upb;
-  const int t1 = (t0 + a.upb < t_hi) ? t0 + a.upb : t_hi;
-  const int r0 = t0 >> a.vs_shift, r1 = (t1 - 1) >> a.vs_shift;       // the block's first and last run (r1 <= r0 + 1)
+  const int t0_all = t_lo + bx * a.upb;
+  const int t1_all = (t0_all + a.upb < t_hi) ? t0_all + a.upb : t_hi;
+  const int r0_all = t0_all >> a.vs_shift, r1_all = (t1_all - 1) >> a.vs_shift;       // the block's first and last run (r1 <= r0 + 1)
+  // (RISK: narrowed below to the block's live run where the other one has stopped; otherwise these ARE the block's range)
+  int t0 = t0_all, t1 = t1_all, r0 = r0_all, r1 = r1_all;
   POCS_STAMP_BEGIN();
   // The head's inputs are all REQUESTED before the first of them is waited for: the tables (24 bytes per thread), and per
   // form what follows -- one memory round trip for the lot, then the stores to LDS.
@@ -1127,12 +1147,30 @@ __global__ __launch_bounds__(TB, (LONE ? 1 : POCS_GMM_BLOCKS_PER_CU) * TB / 256)
     const int rp = tid / PS, jp = tid - rp * PS;
     const double parv = tid < (r1 - r0 + 1) * PS ? load_wt(&a.param[((size_t)(r0 + rp) * a.W + w) * PS + jp]) : 0.0;
     const unsigned long long seedv = tid <= r1 - r0 ? a.hdr[r0 + tid].seed : 0ull;
+    if constexpr (RISK) {
+      // the stop words of the block's runs, every lane the same two addresses, in flight with everything above (a stopped run's
+      // param[w] was never built: what was requested of it is dropped below, unread)
+      const unsigned s0 = __hip_atomic_load(&a.stop[r0_all], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      const unsigned s1 = __hip_atomic_load(&a.stop[r1_all], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      requests_issued();
+      const bool dead0 = __builtin_amdgcn_readfirstlane((int)s0) != 0, dead1 = __builtin_amdgcn_readfirstlane((int)s1) != 0;
+      if (dead0 && dead1) return;                      // (one run: both words are its word) nothing left to do for this block
+      int shift = 0;                                   // the live run's requests land in buffer 0
+      if (dead0) { shift = 1; r0 = r1_all; t0 = r1_all << a.vs_shift; }
+      else if (dead1) { r1 = r0_all; t1 = r1_all << a.vs_shift; }
+      commit_tables<TB>(&sm.tab, tid, tabv);
+      if (tid < a.M * POCS_OBS_STRIDE) sm.obs()[tid] = obs_elem;
+      if (tid < (r1_all - r0_all + 1) * PS && rp >= shift && rp - shift <= r1 - r0) sm.par[rp - shift][jp] = parv;
+      for (int j = tid; j < 2 * NW * K; j += TB) (&sm.xj[0][0][0])[j] = -1;
+      if (tid <= r1_all - r0_all && tid >= shift && tid - shift <= r1 - r0) sm.seed[tid - shift] = seedv;
+    } else {
     requests_issued();
     commit_tables<TB>(&sm.tab, tid, tabv);
     if (tid < a.M * POCS_OBS_STRIDE) sm.obs()[tid] = obs_elem;
     if (tid < (r1 - r0 + 1) * PS) sm.par[rp][jp] = parv;
     for (int j = tid; j < 2 * NW * K; j += TB) (&sm.xj[0][0][0])[j] = -1;
     if (tid <= r1 - r0) sm.seed[tid] = seedv;
+    }
   }
   __syncthreads();
   if (!(LONE && w > 0)) {                            // (scalar; the lone form's heads have culled already, above)
@@ -1176,7 +1214,7 @@ __global__ __launch_bounds__(TB, (LONE ? 1 : POCS_GMM_BLOCKS_PER_CU) * TB / 256)
     const int r = r0 + rb;
     // (a call of plans: a run whose plan ends at w has no waypoint w + 1 -- no chain record, no state / param rows to build;
     // those runs are the tail of the launch's, and advance_in_tail is where they begin)
-    const bool adv = r < a.advance_in_tail;
+    bool adv = r < a.advance_in_tail;
     if (tid == 0) acquire_agent();
     __syncthreads();
     // the run's rows and -- one GPU -- what the mixture advance wants besides their sums (state[w], the chain record, the
@@ -1187,10 +1225,29 @@ __global__ __launch_bounds__(TB, (LONE ? 1 : POCS_GMM_BLOCKS_PER_CU) * TB / 256)
     advance_request<true>(ap, false, tid, TB, advv, adv);
     close_rows<K, TB> cr;
     cr.request(close_rows_of<K>(a, a.partial, r), 1 << a.vs_shift, tid);
+    double survv = 1.0;                                // RISK: the run's survival product up to w - 1, requested with the rest
+    if constexpr (RISK) if (tid == 0 && w > 0) survv = load_wt(&a.surv[r]);
     requests_issued();
     if (adv) advance_commit(ap, false, tid, TB, advv);
     gmm_close_sums<K, TB, true>(a, w, r, sm.par[rb], sm.stage(), l_mom, tid, a.partial, true, cr);
     POCS_STAMP(5);
+    if constexpr (RISK) {
+      // p_w and the running probability as gmm_combine (pocs_host.hip) forms them from the same moments: the counts added in
+      // component order from 0.0, one division, one multiplication, one subtraction, IEEE double -- the host recomputes the
+      // stop from the moments it reads back and refuses the call if the two ever disagree
+      if (tid == 0) {
+        double coll = 0.0;
+        for (int k = 0; k < K; ++k) coll += l_mom[k * POCS_NMOM + 1];
+        const double p = coll / (1.0 * (double)a.n_total);
+        const double prod = survv * (1.0 - p);
+        store_wt(&a.surv[r], prod);
+        const bool stop = (1.0 - prod) >= a.risk_bound;
+        if (stop) __hip_atomic_store(&a.stop[r], (unsigned)(w + 1), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        sm.last[rb] = stop ? 2 : 1;                    // (last0 / last1 were read before the first closer)
+      }
+      __syncthreads();
+      if (sm.last[rb] == 2) adv = false;               // a stopped run builds no state / param[w + 1], draws no component counts
+    }
     if (a.exchange_in_tail) {
       // sharded: the run's closer is also its messenger -- this shard's moments go to every rank, the world's
       // come back summed in rank order, and the mixture advances here (no launch, no host, between waypoints)
@@ -1217,6 +1274,17 @@ __global__ __launch_bounds__(TB, (LONE ? 1 : POCS_GMM_BLOCKS_PER_CU) * TB / 256)
   const int last0 = __builtin_amdgcn_readfirstlane(sm.last[0]), last1 = __builtin_amdgcn_readfirstlane(sm.last[1]);
   if (last0 && !closer(0)) return;
   if (last1) (void)closer(1);
+}
+
+template <int K, bool STORE, int TB, bool LONE>
+__global__ __launch_bounds__(TB, (LONE ? 1 : POCS_GMM_BLOCKS_PER_CU) * TB / 256) void k_gmm_step(pocs_gmm_launch a) {   // (lone: one block per CU, its LDS)
+  gmm_step_block<K, STORE, TB, LONE, false>(a);
+}
+// The ticket form under a risk bound (RISK above).  A kernel of its own name: k_gmm_step is, instruction for instruction, what
+// it is without the feature.
+template <int K, bool STORE, int TB>
+__global__ __launch_bounds__(TB, POCS_GMM_BLOCKS_PER_CU * TB / 256) void k_gmm_step_risk(pocs_gmm_launch a) {
+  gmm_step_block<K, STORE, TB, false, true>(a);
 }
 
 // Lone call, behind the last waypoint's launch: its rows -> moments[W-1] (one block).
@@ -1384,7 +1452,11 @@ __global__ __launch_bounds__(POCS_BLOCK) void k_mc_count(pocs_mc_launch a) {
 template <int K>
 hipError_t launch_gmm_k(const pocs_gmm_launch& a, hipStream_t s) {
   constexpr int TB = POCS_GMM_BLOCK_OF(K);
-  if (a.lone) {
+  if (a.risk) {
+    if (a.lone || a.exchange_in_tail || !a.stop || !a.surv) return hipErrorInvalidValue;
+    if (a.store) hipLaunchKernelGGL((k_gmm_step_risk<K, true, TB>), dim3(a.blocks), dim3(TB), 0, s, a);
+    else         hipLaunchKernelGGL((k_gmm_step_risk<K, false, TB>), dim3(a.blocks), dim3(TB), 0, s, a);
+  } else if (a.lone) {
     if (a.store) hipLaunchKernelGGL((k_gmm_step<K, true, TB, true>), dim3(a.blocks), dim3(TB), 0, s, a);
     else         hipLaunchKernelGGL((k_gmm_step<K, false, TB, true>), dim3(a.blocks), dim3(TB), 0, s, a);
   } else {
