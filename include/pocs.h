@@ -103,6 +103,13 @@ int pocs_send_command(pocs_ctx* ctx, const char* line, char* out, size_t cap);
                                       of a batch does, and the run counter advances by P; 1, common random numbers: every plan draws the
                                       stream of run run_index and the counter advances by 1 -- the difference between two plans'
                                       probabilities, what a planner compares, then has a much smaller variance */
+#define POCS_OPT_MC_WAYPOINT_COUNTS 11   /* 0 (default): an MC call is what it has always been.  1: MC calls also count, per run and waypoint w, the
+                                      particles that collide at w and at no waypoint before it (pocs_mc_get_waypoint_counts), in both launch
+                                      forms (POCS_OPT_MC_FUSED 0 and 1); no other result changes */
+#define POCS_OPT_MC_RISK_BOUND 12  /* 0 (default): pocs_run_simulation ignores the risk bound.  1: an MC call of plans under a bound in (0, 1)
+                                      stops a plan at the first waypoint where its share of collided particles reaches the bound
+                                      (pocs_set_plan_risk_bound); such a call counts as under POCS_OPT_MC_WAYPOINT_COUNTS and takes the per-step
+                                      launch form whatever POCS_OPT_MC_FUSED says.  No effect without plans or with the bound off */
 int pocs_set_option(pocs_ctx* ctx, int option, long long value);
 
 /* ---- batches of independent runs (ours) --------------------------------------------------
@@ -163,10 +170,24 @@ int pocs_set_plans(pocs_ctx* ctx, int P, const int* W, const double* trajs, cons
  *     counter (POCS_OPT_PLAN_SEEDS) do not depend on who stopped.
  * bound >= 1.0 (the default is 1.0): off -- every call is what it is without this function.  bound <= 0 or NaN: POCS_E_ARG.
  * The bound belongs to the context: it survives pocs_set_plans, and has no effect while no plans are set (pocs_set_batch,
- * run-ahead, the step API; sharded contexts refuse plans).  pocs_run_simulation IGNORES it: the MC result is the share of
- * particles that EVER collided, which the per-step kernels do not count between steps.
+ * run-ahead, the step API; sharded contexts refuse plans).
  * The stop is decided and obeyed on the device, inside the call's one replayed graph; the host restates
- * the rule on the moments it reads back, and a call whose two stops differ returns POCS_E_DEVICE. */
+ * the rule on the moments it reads back, and a call whose two stops differ returns POCS_E_DEVICE.
+ * pocs_run_simulation ignores the bound BY DEFAULT.  With POCS_OPT_MC_RISK_BOUND = 1 an MC call of plans under a bound in (0, 1)
+ * stops plan p at the FIRST waypoint s with (double)C[s] / (double)N >= bound -- C[s] = F[0] + ... + F[s] the particles that
+ * have collided at waypoints 0 .. s (pocs_mc_get_waypoint_counts), N = numParticles, one IEEE division -- and moves its particles
+ * no further:
+ *   - pocs_mc_get_batch_counts()[p] is C[s], pocs_get_batch_probabilities()[p] (pocs_run_simulation's value for plan 0) is
+ *     C[s] / N, pocs_get_plan_evaluated()[p] is s + 1, pocs_mc_get_waypoint_counts covers s + 1 waypoints, and
+ *     pocs_copy_particles returns the cloud at waypoint s with its hit counters over waypoints 0 .. s.  A plan that never reaches
+ *     the bound, or only at its last waypoint, gets what it gets without the option;
+ *   - everything before the stop is bit for bit what the plan gets unstopped; seeds and the run counter do not depend on who
+ *     stopped;
+ *   - the stop is decided on the device from the counts that the earlier launches of the call's graph completed, one launch per
+ *     waypoint: the fused kernel (POCS_OPT_MC_FUSED = 1) meets no launch boundary between steps, so a call with the MC stop active
+ *     takes the per-step form whatever that option says.  The host restates the rule on the counts it reads back; a mismatch
+ *     is POCS_E_DEVICE and the results are discarded;
+ *   - stopped plans' blocks are still launched and return in their head. */
 int pocs_set_plan_risk_bound(pocs_ctx* ctx, double bound);
 int pocs_get_plan_evaluated(pocs_ctx* ctx, int* out, int cap);
 
@@ -243,6 +264,14 @@ int pocs_gmm_sample_exchange_local(pocs_ctx* ctx, int waypoint);
 /* MC: the shard's count of particles that collided at least once (device-synchronous). */
 int pocs_mc_run_local(pocs_ctx* ctx, unsigned long long* collided);            /* run 0 of the batch */
 int pocs_mc_get_batch_counts(pocs_ctx* ctx, unsigned long long* out, int cap);   /* every run of the last MC batch */
+/* MC under POCS_OPT_MC_WAYPOINT_COUNTS: the first-collision profile of the selected run (pocs_select_batch_run; plan p while plans
+ * are set; the run served last under run-ahead): out[w] = the shard's particles that collide at waypoint w and at no waypoint
+ * before it -- waypoint 0 is the initial cloud, waypoint s + 1 what control s produces.  Their sum is the run's entry of
+ * pocs_mc_get_batch_counts; out[0] + ... + out[s] over N particles is the MC counterpart of the GMM path's running probability;
+ * the shards' profiles add up to the whole run's.  Integer counts: the same whatever the launch form, the grid and the
+ * partition.  Writes and returns the number of waypoints covered (a plan's own length, or the waypoints before its stop).
+ * POCS_E_BUFFER for a short buffer; POCS_E_STATE when the last call was not an MC call or ran with the option off. */
+int pocs_mc_get_waypoint_counts(pocs_ctx* ctx, unsigned long long* out, int cap);
 
 /* ---- results of the last run, for audits and parity tests ------------------------------- */
 int pocs_get_path_length(const pocs_ctx* ctx);

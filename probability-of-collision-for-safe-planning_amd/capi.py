@@ -14,7 +14,7 @@ from . import build as _build
 POCS_OK = 0
 E_ARG, E_ORDER, E_STATE, E_DEVICE, E_UNKNOWN_COMMAND, E_BUFFER = -1, -2, -3, -4, -5, -6
 OPT_STORE_SAMPLES, OPT_MC_FUSED, OPT_USE_GRAPH, OPT_PROFILE, OPT_RUN_AHEAD, OPT_PERSISTENT, OPT_LONE_CALL = 1, 2, 3, 4, 5, 6, 7
-OPT_SUB_BATCHES, OPT_MC_NONTEMPORAL, OPT_PLAN_SEEDS = 8, 9, 10
+OPT_SUB_BATCHES, OPT_MC_NONTEMPORAL, OPT_PLAN_SEEDS, OPT_MC_WAYPOINT_COUNTS, OPT_MC_RISK_BOUND = 8, 9, 10, 11, 12
 NMOM = 11
 MAX_PLANS = 256
 
@@ -63,6 +63,7 @@ SIGNATURES = {
     "pocs_gmm_end": (C.c_int, [_vp, _dp]),
     "pocs_mc_run_local": (C.c_int, [_vp, C.POINTER(C.c_ulonglong)]),
     "pocs_mc_get_batch_counts": (C.c_int, [_vp, C.POINTER(C.c_ulonglong), C.c_int]),
+    "pocs_mc_get_waypoint_counts": (C.c_int, [_vp, C.POINTER(C.c_ulonglong), C.c_int]),
     "pocs_xchg_create": (C.c_int, [_vp, C.c_int, C.c_int, C.c_void_p]),
     "pocs_xchg_connect": (C.c_int, [_vp, C.c_void_p, C.c_int]),
     "pocs_gmm_exchange_local": (C.c_int, [_vp, C.c_int]),
@@ -352,6 +353,14 @@ class Context:
         out = (C.c_ulonglong * n)()
         got = self._chk(self.lib.pocs_mc_get_batch_counts(self.h, out, n))
         return [int(v) for v in out[:got]]
+
+    def mc_waypoint_counts(self):
+        """First collisions per waypoint of the selected run of the last MC call under OPT_MC_WAYPOINT_COUNTS (uint64 array):
+        entry w = the shard's particles that collide at waypoint w and at no waypoint before it (include/pocs.h)."""
+        W = max(self.path_length(), 1)
+        out = np.zeros(W, dtype=np.uint64)
+        got = self._chk(self.lib.pocs_mc_get_waypoint_counts(self.h, out.ctypes.data_as(C.POINTER(C.c_ulonglong)), W))
+        return out[:got]
 
     def gmm_begin(self):
         self._chk(self.lib.pocs_gmm_begin(self.h))

@@ -99,6 +99,13 @@ struct pocs_ctx {
   // any further (k_gmm_step_risk decides and obeys on the device; gmm_combine restates the rule on the moments read back)
   double risk_bound = 1.0;                        // >= 1: off
   std::vector<int> plan_E;                        // [P] waypoints evaluated per plan in the last GMM call of plans (empty: there was none)
+  // first collisions per waypoint of MC calls (POCS_OPT_MC_WAYPOINT_COUNTS) and the risk bound obeyed by them
+  // (POCS_OPT_MC_RISK_BOUND): k_mc_*_counts count, k_mc_step_counts<.., MC_STOP> decides and obeys; run_mc_local restates the
+  // rule on the counts read back
+  long long opt_mc_wp = 0, opt_mc_rb = 0;
+  std::vector<unsigned long long> mc_wp;          // [R][mc_wp_W] of the last MC call, in run / plan order (empty: the call ran without)
+  int mc_wp_W = 0;
+  std::vector<int> plan_E_mc;                     // [P] waypoints evaluated per plan in the last MC call of plans under the bound (empty: every plan to its end)
 
   // host image (headers | chains | initial mixtures) of the NEXT batch, computed while the GPU
   // works on the current one
@@ -385,6 +392,7 @@ PinLayout pin_layout(const pocs_ctx* c) {
   p.moments = p.runplan + (c->nplans ? 4 * R : 0);
   p.total = p.moments + W * R * K * POCS_NMOM;
   p.end = p.total + R + 2 + (R + 4) / 2 + 1;   // one u64 per run: MC totals; the call's give-up word and -- under a risk bound -- the R stop words behind it
+  if (c->opt_mc_wp || c->opt_mc_rb) p.end += R * W + (R + 1) / 2;   // MC calls with first collisions per waypoint: behind the totals, [R][W] u64 and the R stop words
   return p;
 }
 
@@ -1003,6 +1011,20 @@ int mc_shard(pocs_ctx* c, long long* first, long long* count) {
   return POCS_OK;
 }
 
+// An MC call of plans obeys the risk bound only when asked to (POCS_OPT_MC_RISK_BOUND; by default it ignores the bound); such a
+// call, or any MC call under POCS_OPT_MC_WAYPOINT_COUNTS, counts the first collisions per waypoint.  Both off: the launches,
+// the memset and the copies of an MC call are what they have always been.
+bool mc_stop_active(const pocs_ctx* c) { return c->opt_mc_rb && risk_active(c); }
+bool mc_counts_active(const pocs_ctx* c) { return c->opt_mc_wp || mc_stop_active(c); }
+// The fused kernel carries a particle through all its steps and meets no other block on the way: a call that stops on a count
+// takes the per-step form.
+bool mc_fused_form(const pocs_ctx* c) { return c->opt_fused && !mc_stop_active(c); }
+// d_total, u64 words: [R] collided particles per run | counts active: [R][W] first collisions | [R] u32 stop words
+size_t mc_total_words(const pocs_ctx* c) {
+  const size_t R = (size_t)c->batch, W = (size_t)c->W;
+  return mc_counts_active(c) ? R + R * W + (R + 1) / 2 : R;
+}
+
 int enqueue_mc_all(pocs_ctx* c, long long first, long long count, bool prof) {
   const int W = c->W, R = c->batch, nblk = grid_for_mc(count, R);
   pocs_mc_launch a;
@@ -1016,6 +1038,13 @@ int enqueue_mc_all(pocs_ctx* c, long long first, long long count, bool prof) {
   a.total = (unsigned long long*)c->d_total.p;
   a.first = first; a.count = count; a.stride = sample_stride_of(count);
   a.W = W; a.nruns = R;
+  if (mc_counts_active(c)) {
+    a.wp_mode = mc_stop_active(c) ? 2 : 1;
+    a.wp_counts = a.total + R;
+    a.wp_stop = (unsigned*)(a.wp_counts + (size_t)R * (size_t)W);
+    a.wp_n = c->num_particles;                       // (a context with plans holds no shard: the run's particles)
+    a.wp_bound = c->risk_bound;
+  }
   // 28 B of state per particle.  Up to 8 x 10^6 particles (224 MB) the state of a batch stays in the
   // 256 MB Infinity Cache between waypoint launches; past that the launches stream from HBM whatever
   // they do, and non-temporal accesses then stream faster (16 x 10^6: 148 us instead of 189 us)
@@ -1029,7 +1058,7 @@ int enqueue_mc_all(pocs_ctx* c, long long first, long long count, bool prof) {
   // a call of plans: slots in descending plan length (plan_layout, one group), so the runs that still drive a control at
   // step s are a prefix -- the launch of step s covers those only
   const std::vector<int> Ws = slot_lengths(c, plan_layout(c, 1));
-  if (c->opt_fused) {
+  if (mc_fused_form(c)) {
     a.step = W - 1;
     if (prof) HIPCHK(c, hipEventRecord(c->events[0], c->stream));
     HIPCHK(c, pocs_launch_mc_fused(nblk, a, c->stream));
@@ -1054,6 +1083,45 @@ int enqueue_mc_all(pocs_ctx* c, long long first, long long count, bool prof) {
   return POCS_OK;
 }
 
+// The first collisions per waypoint as the call's copy brought them back (`words`: mc_total_words, slot order) -> c->mc_wp in
+// run / plan order.  Every run's counts must add up to its collided particles (k_mc_count's own count of hits > 0).  Under an
+// MC stop the rule is restated here on the counts read back: plan p stops at the FIRST waypoint s with
+// (double)C[s] / (double)N >= bound, C[s] = F[0] + ... + F[s]; a stop at the last waypoint stops nothing.  The device's stop
+// word must say the same and nothing may have been counted behind the stop, or the call fails instead of reporting either.
+int mc_read_waypoint_counts(pocs_ctx* c, const unsigned long long* words) {
+  const size_t R = (size_t)c->batch, W = (size_t)c->W;
+  const unsigned long long* F = words + R;
+  const unsigned* stopw = (const unsigned*)(F + R * W);
+  const bool plans = c->nplans > 0, stop = mc_stop_active(c);
+  c->mc_wp.assign(R * W, 0ull);
+  c->mc_wp_W = (int)W;
+  if (stop) c->plan_E_mc = c->plan_W;
+  const double n = (double)c->num_particles;
+  for (size_t r = 0; r < R; ++r) {                     // (a call of plans: r is the plan, in its slot, over its W_p waypoints)
+    const size_t slot = plans ? (size_t)c->plan_slot[1][r] : r, Wr = plans ? (size_t)c->plan_W[r] : W;
+    const unsigned long long* f = F + slot * W;
+    unsigned long long C = 0;
+    int host = 0;                                      // the host's stop word
+    for (size_t w = 0; w < W; ++w) {
+      C += f[w];
+      if (w >= Wr && f[w]) return fail(c, POCS_E_DEVICE, "MC waypoint counts: run %zu has %llu first collisions at waypoint %zu of %zu; results discarded", r, f[w], w, Wr);
+      if (stop && !host && w + 1 < Wr && (double)C / n >= c->risk_bound) host = (int)w + 1;
+      if (host && (int)w >= host && f[w]) return fail(c, POCS_E_DEVICE, "MC risk bound: plan %zu moved behind its stop at waypoint %d; results discarded", r, host - 1);
+    }
+    if (C != c->mc_counts[r])
+      return fail(c, POCS_E_DEVICE, "MC waypoint counts: the first collisions of run %zu add up to %llu, its collided particles are %llu; results discarded", r, C, c->mc_counts[r]);
+    if (stop) {
+      const int dev = (int)stopw[slot];
+      if (dev != host)
+        return fail(c, POCS_E_DEVICE, "MC risk bound: plan %zu stops at waypoint %d on the device and at %d on the host (-1: not at all); results discarded",
+                    r, dev - 1, host - 1);
+      if (host) c->plan_E_mc[r] = host;
+    }
+    memcpy(&c->mc_wp[r * W], f, W * sizeof(unsigned long long));
+  }
+  return POCS_OK;
+}
+
 // One batch of MC roll-outs (runSimulation x batch) over this context's shard; fills c->mc_counts.
 int run_mc_local(pocs_ctx* c) {
   if (int r = check_common(c)) return r;
@@ -1068,19 +1136,22 @@ int run_mc_local(pocs_ctx* c) {
   if (int r = ensure(c, c->d_py, n * sizeof(double))) return r;
   if (int r = ensure(c, c->d_pt, n * sizeof(double))) return r;
   if (int r = ensure(c, c->d_hits, n * sizeof(uint32_t))) return r;
-  if (int r = ensure(c, c->d_total, R * sizeof(unsigned long long) + 16)) return r;
+  const size_t total_bytes = mc_total_words(c) * sizeof(unsigned long long);
+  if (int r = ensure(c, c->d_total, total_bytes + 16)) return r;
   if (c->nplans)
     if (int r = ensure(c, c->d_runplan, R * 4 * sizeof(double))) return r;
   if (int r = ensure_pin(c)) return r;
   if (int r = stage_and_upload_runs(c, 1, 1)) return r;
   const bool prof = c->opt_profile == 1, span = c->opt_profile == 2 && c->opt_graph;      // (as run_gmm_full)
-  const size_t nprof = c->opt_fused ? 1 : (W > 1 ? W - 1 : 0);
+  const size_t nprof = mc_fused_form(c) ? 1 : (W > 1 ? W - 1 : 0);
   if (int r = prof_begin(c, nprof > 0 ? nprof : 1)) return r;
   // (the counter reset ahead of the launches and the result copy behind them are plain stream operations: the
   // captured graph holds kernel nodes only, like the GMM path's)
-  HIPCHK(c, hipMemsetAsync(c->d_total.p, 0, R * sizeof(unsigned long long), c->stream));
+  HIPCHK(c, hipMemsetAsync(c->d_total.p, 0, total_bytes, c->stream));
   if (c->opt_graph && !prof) {
-    const std::string key = config_key(c, first, count, "mc") + std::to_string(c->num_particles);
+    // (the two options select the kernels; the bound an MC stop obeys is in the key already: config_key, "rb")
+    const std::string key = config_key(c, first, count, "mc") + std::to_string(c->num_particles) +
+                            (mc_stop_active(c) ? " wp2" : mc_counts_active(c) ? " wp1" : "");
     if (!c->graph_mc || key != c->graph_mc_key) {
       if (c->graph_mc) { hipGraphExecDestroy(c->graph_mc); c->graph_mc = nullptr; }
       hipGraph_t g = nullptr;
@@ -1101,8 +1172,7 @@ int run_mc_local(pocs_ctx* c) {
     if (int r = enqueue_mc_all(c, first, count, prof)) return r;
   }
   const PinLayout pl = pin_layout(c);
-  HIPCHK(c, hipMemcpyAsync((double*)c->h_pin + pl.total, c->d_total.p, R * sizeof(unsigned long long),
-                           hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipMemcpyAsync((double*)c->h_pin + pl.total, c->d_total.p, total_bytes, hipMemcpyDeviceToHost, c->stream));
   prefetch_next_batch(c, 1);       // host chains of the next batch, while the GPU works on this one
   HIPCHK(c, hipStreamSynchronize(c->stream));
   if (int r = prof_collect(c, nprof)) return r;
@@ -1119,6 +1189,14 @@ int run_mc_local(pocs_ctx* c) {
   }
   c->last_mc_count = count;
   c->last_kind = 2;
+  c->mc_wp.clear(); c->plan_E_mc.clear();
+  if (mc_counts_active(c)) {
+    if (int r = mc_read_waypoint_counts(c, (const unsigned long long*)((double*)c->h_pin + pl.total))) {
+      c->mc_counts.clear(); c->mc_wp.clear(); c->plan_E_mc.clear(); c->batch_probs.clear();
+      c->last_mc_count = 0; c->last_kind = 0;
+      return r;
+    }
+  }
   return POCS_OK;
 }
 
@@ -1388,6 +1466,14 @@ int pocs_set_option(pocs_ctx* c, int option, long long value) {
       if (value < 0 || value > 1) return fail(c, POCS_E_ARG, "POCS_OPT_PLAN_SEEDS takes 0 (plan p draws run p's stream) or 1 (common random numbers)");
       c->opt_plan_seeds = value;
       break;
+    case POCS_OPT_MC_WAYPOINT_COUNTS:
+      if (value < 0 || value > 1) return fail(c, POCS_E_ARG, "POCS_OPT_MC_WAYPOINT_COUNTS takes 0 or 1");
+      c->opt_mc_wp = value;
+      break;
+    case POCS_OPT_MC_RISK_BOUND:
+      if (value < 0 || value > 1) return fail(c, POCS_E_ARG, "POCS_OPT_MC_RISK_BOUND takes 0 (MC calls ignore the risk bound) or 1");
+      c->opt_mc_rb = value;
+      break;
     case POCS_OPT_RUN_AHEAD:
       if (value < 0 || value > 256) return fail(c, POCS_E_ARG, "run-ahead %lld outside 0..256", value);
       c->run_ahead = (int)value;                     // 0 = sized per call (ra_depth)
@@ -1412,6 +1498,7 @@ static void drop_results(pocs_ctx* c) {
   c->batch_probs.clear(); c->mc_counts.clear(); c->probs.clear(); c->last_moments.clear(); c->batch_moments.clear();
   c->h_chain.clear(); c->h_mu.clear(); c->h_cov.clear();
   c->plan_slot[0].clear(); c->plan_slot[1].clear(); c->plan_E.clear();
+  c->mc_wp.clear(); c->plan_E_mc.clear();
   c->last_gmm_wp = -1; c->last_gmm_count = 0; c->last_mc_count = 0; c->last_kind = 0;
   c->view = 0; c->batch_R = c->batch;
 }
@@ -1469,10 +1556,10 @@ int pocs_set_plan_risk_bound(pocs_ctx* c, double bound) {
 
 int pocs_get_plan_evaluated(pocs_ctx* c, int* out, int cap) {
   if (!c || !out) return POCS_E_ARG;
-  const int kind = c->last_kind;                     // 1 GMM, 2 MC -- which ignores the bound: every plan is driven to its end
+  const int kind = c->last_kind;                     // 1 GMM, 2 MC -- which by default ignores the bound: every plan is driven to its end
   if (!c->nplans || kind == 0 || c->plan_slot[kind - 1].empty() || (kind == 1 && c->plan_E.empty()))
     return fail(c, POCS_E_STATE, "pocs_get_plan_evaluated: the last call was not a call of plans");
-  const std::vector<int>& E = kind == 1 ? c->plan_E : c->plan_W;
+  const std::vector<int>& E = kind == 1 ? c->plan_E : c->plan_E_mc.empty() ? c->plan_W : c->plan_E_mc;
   if ((int)E.size() > cap) return fail(c, POCS_E_BUFFER, "need %zu ints", E.size());
   memcpy(out, E.data(), E.size() * sizeof(int));
   return (int)E.size();
@@ -1613,6 +1700,18 @@ int pocs_mc_get_batch_counts(pocs_ctx* c, unsigned long long* out, int cap) {
   if ((int)c->mc_counts.size() > cap) return fail(c, POCS_E_BUFFER, "need %zu counters", c->mc_counts.size());
   memcpy(out, c->mc_counts.data(), c->mc_counts.size() * sizeof(unsigned long long));
   return (int)c->mc_counts.size();
+}
+
+int pocs_mc_get_waypoint_counts(pocs_ctx* c, unsigned long long* out, int cap) {
+  if (!c || !out) return POCS_E_ARG;
+  const size_t W = (size_t)(c->mc_wp_W > 0 ? c->mc_wp_W : 1), r = (size_t)c->view;
+  if (c->last_kind != 2 || c->mc_wp.empty() || (r + 1) * W > c->mc_wp.size())
+    return fail(c, POCS_E_STATE, "pocs_mc_get_waypoint_counts: the last call was not an MC call under POCS_OPT_MC_WAYPOINT_COUNTS (or POCS_OPT_MC_RISK_BOUND with a bound)");
+  int n = (int)W;                                    // the selected run's waypoints; a plan's own, or those before its stop
+  if (c->nplans && r < c->plan_slot[1].size()) n = c->plan_E_mc.empty() ? c->plan_W[r] : c->plan_E_mc[r];
+  if (n > cap) return fail(c, POCS_E_BUFFER, "need %d counters", n);
+  memcpy(out, &c->mc_wp[r * W], (size_t)n * sizeof(unsigned long long));
+  return n;
 }
 
 int pocs_gmm_begin(pocs_ctx* c) {

@@ -144,6 +144,15 @@ struct pocs_mc_launch {               // blockIdx.y = run of the batch, like poc
   int step;                            // k_mc_step: control index; k_mc_fused: number of steps
   int nruns;
   int nontemporal;                     // k_mc_step: the batch's state exceeds the Infinity Cache, stream past it
+  // first collisions per waypoint (POCS_OPT_MC_WAYPOINT_COUNTS / POCS_OPT_MC_RISK_BOUND; behind everything else: the other
+  // launches' argument offsets stay)
+  int wp_mode;                         // 0: the kernels above as they are; 1: the _counts kernels also fill wp_counts; 2 (k_mc_step
+                                       // only): ... and a run whose cumulative count has reached the bound moves no further
+  unsigned long long* wp_counts;       // [nruns][W] particles of the shard whose FIRST collision is at waypoint w (0: k_mc_init,
+                                       // s + 1: control s); zeroed with `total`, one allocation
+  unsigned* wp_stop;                   // [nruns] 0 = never stopped, s + 1 = stopped at waypoint s; written once, read by the host only
+  long long wp_n;                      // mode 2: N, the particles of a run
+  double wp_bound;                     // mode 2: a run stops at the first waypoint s with (double)C[s] / (double)N >= wp_bound
 };
 
 

@@ -1337,6 +1337,65 @@ __device__ __forceinline__ mc_run_start mc_start(const pocs_mc_launch& a) {
   return s;
 }
 
+// First collisions per waypoint (POCS_OPT_MC_WAYPOINT_COUNTS, POCS_OPT_MC_RISK_BOUND).  The MC kernels have one body each,
+// instantiated by MODE: MC_PLAIN is the kernel as it has always been (k_mc_init, k_mc_step, k_mc_fused: not one instruction
+// more), MC_COUNTS also adds to wp_counts[run][w] the particles that collide at waypoint w and at no waypoint before it,
+// MC_STOP (k_mc_step only) also obeys the risk bound.  A particle's first collision is read off the hit counter the kernel
+// holds anyway (old == 0).  Integer counts added with integer atomics: exact, whatever the grid and the shard partition.
+enum { MC_PLAIN = 0, MC_COUNTS = 1, MC_STOP = 2 };
+
+// The block's first collisions of one waypoint -> wp_counts: every thread's own count, one wave sum, one atomic per block,
+// and none when the block saw no first collision.  Every thread of the block arrives (behind its particle loop).
+__device__ __forceinline__ void mc_add_first_hits(unsigned f, unsigned long long* dst) {
+  __shared__ unsigned s_f[POCS_BLOCK / 64];
+  f = wave_sum_u32(f);
+  if ((threadIdx.x & 63) == 0) s_f[threadIdx.x >> 6] = f;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    unsigned long long t = 0;
+    for (int w = 0; w < POCS_BLOCK / 64; ++w) t += s_f[w];
+    if (t) atomicAdd(dst, t);
+  }
+}
+
+// The lanes of a wave that are in the particle loop together: those with a first collision at this waypoint, counted by
+// ballot, added by the first of them.
+__device__ __forceinline__ void mc_wave_first_hits(bool first, unsigned long long* dst) {
+  const unsigned long long m = __ballot(first);
+  if (m != 0ull && (threadIdx.x & 63) == (unsigned)__builtin_ctzll(m)) atomicAdd(dst, (unsigned long long)__popcll(m));
+}
+
+// MC_STOP, the head of every block of the launch of control s: is the run stopped?  The run stops at the FIRST waypoint s
+// whose cumulative count C[s] = F[0] + ... + F[s] has (double)C[s] / (double)N >= bound.  F[0..s] were completed by the
+// EARLIER launches of the graph (control s - 1 wrote F[s]); this launch adds to F[s + 1] only, which nobody reads here: all
+// blocks of the run see the same numbers and decide alike.  A stopped run's particles stay where they are, so its later
+// launches find F[s + 1 ...] = 0, the same C and the same answer -- no block reads a word that a block of its own launch
+// writes.  Block 0 of the launch that finds the bound reached for the first time (C[s - 1] was below it) reports s + 1 in the
+// run's stop word, which only the host reads.
+__device__ __forceinline__ bool mc_run_stopped(const pocs_mc_launch& a) {
+  __shared__ unsigned long long s_c[POCS_BLOCK / 64];
+  const int r = blockIdx.y, s = a.step;
+  const unsigned long long* F = a.wp_counts + (size_t)r * (size_t)a.W;
+  unsigned long long part = 0;
+  for (int w = threadIdx.x; w <= s; w += POCS_BLOCK) part += F[w];
+  // (a wave sum of 64-bit counts out of 32-bit ones: three pieces of 22 bits, 64 of which cannot overflow)
+  const unsigned long long c = (unsigned long long)wave_sum_u32((unsigned)(part & 0x3FFFFFull)) +
+                               ((unsigned long long)wave_sum_u32((unsigned)((part >> 22) & 0x3FFFFFull)) << 22) +
+                               ((unsigned long long)wave_sum_u32((unsigned)(part >> 44)) << 44);
+  if ((threadIdx.x & 63) == 0) s_c[threadIdx.x >> 6] = c;
+  __syncthreads();
+  unsigned long long C = 0;
+  for (int w = 0; w < POCS_BLOCK / 64; ++w) C += s_c[w];
+  const double n = (double)a.wp_n;
+  const bool stopped = (double)C / n >= a.wp_bound;
+  if (stopped && blockIdx.x == 0 && threadIdx.x == 0) {
+    const unsigned long long before = C - F[s];          // C[s - 1] (0 for s = 0: waypoint 0 is always evaluated)
+    if (!((double)before / n >= a.wp_bound)) a.wp_stop[r] = (unsigned)s + 1u;
+  }
+  return stopped;
+}
+
+template <int MODE>
 __global__ __launch_bounds__(POCS_BLOCK) void k_mc_init(pocs_mc_launch a) {
   __shared__ double s_obs[POCS_MAX_OBSTACLES * POCS_OBS_STRIDE];
   __shared__ pocs_footprint s_fp;
@@ -1348,6 +1407,7 @@ __global__ __launch_bounds__(POCS_BLOCK) void k_mc_init(pocs_mc_launch a) {
   const pocs_footprint fp = s_fp;
   const int M = s_M;
   const mc_run_start st = mc_start(a);
+  unsigned first = 0;                              // (MODE != MC_PLAIN) this thread's particles that collide at waypoint 0
   const long long stride = (long long)gridDim.x * POCS_BLOCK;
   for (long long i = (long long)blockIdx.x * POCS_BLOCK + threadIdx.x; i < a.count; i += stride) {
     double z[3];
@@ -1357,20 +1417,28 @@ __global__ __launch_bounds__(POCS_BLOCK) void k_mc_init(pocs_mc_launch a) {
     const double y = fma(a.L0[2], z[1], fma(a.L0[1], z[0], st.mu[1]));
     const double t = fma(a.L0[5], z[2], fma(a.L0[4], z[1], fma(a.L0[3], z[0], st.mu[2])));
     v.x[i] = x; v.y[i] = y; v.th[i] = t;
-    v.hits[i] = pocs_pose_collides(x, y, t, &fp, s_obs, M, &s_tab) ? 1u : 0u;
+    if (MODE == MC_PLAIN) {
+      v.hits[i] = pocs_pose_collides(x, y, t, &fp, s_obs, M, &s_tab) ? 1u : 0u;
+    } else {
+      const unsigned h = pocs_pose_collides(x, y, t, &fp, s_obs, M, &s_tab) ? 1u : 0u;
+      v.hits[i] = h;
+      first += h;
+    }
   }
+  if (MODE != MC_PLAIN) mc_add_first_hits(first, a.wp_counts + (size_t)blockIdx.y * (size_t)a.W);      // waypoint 0
 }
 
 // NT: non-temporal accesses, chosen by the host when the particle state of the batch does not fit
 // the 256 MB Infinity Cache anyway (the stream then runs faster past the caches; when it does fit,
 // plain accesses keep it there between waypoint launches).  One particle per thread and iteration:
 // a two-particle version with 16-byte accesses measured 12 % slower in cache, 7 % faster out of it.
-template <bool NT>
-__global__ __launch_bounds__(POCS_BLOCK) void k_mc_step(pocs_mc_launch a) {
+template <bool NT, int MODE>
+__device__ __forceinline__ void mc_step_body(const pocs_mc_launch& a) {
   __shared__ double s_obs[POCS_MAX_OBSTACLES * POCS_OBS_STRIDE];
   __shared__ pocs_footprint s_fp;
   __shared__ int s_M;
   __shared__ pocs_tables s_tab;
+  if (MODE == MC_STOP) { if (mc_run_stopped(a)) return; }      // (the same answer in every thread of the block)
   stage_mc_head(a.env, a.tables, s_obs, &s_fp, &s_M, &s_tab);
   __syncthreads();
   const mc_run_view v = mc_view(a);
@@ -1378,6 +1446,7 @@ __global__ __launch_bounds__(POCS_BLOCK) void k_mc_step(pocs_mc_launch a) {
   const int M = s_M;
   const double* u = v.chain + (size_t)a.step * POCS_CHAIN_STRIDE + 6;
   const double u0 = u[0], u1 = u[1], u2 = u[2];
+  unsigned first = 0;                              // (MODE != MC_PLAIN) this thread's particles whose first collision is this waypoint
   const long long stride = (long long)gridDim.x * POCS_BLOCK;
   for (long long i = (long long)blockIdx.x * POCS_BLOCK + threadIdx.x; i < a.count; i += stride) {
     const double x = NT ? __builtin_nontemporal_load(v.x + i) : v.x[i];
@@ -1393,11 +1462,25 @@ __global__ __launch_bounds__(POCS_BLOCK) void k_mc_step(pocs_mc_launch a) {
     } else {
       v.x[i] = nx; v.y[i] = ny; v.th[i] = nt;
     }
-    if (pocs_pose_collides(nx, ny, nt, &fp, s_obs, M, &s_tab)) v.hits[i] += 1u;
+    if (MODE == MC_PLAIN) {
+      if (pocs_pose_collides(nx, ny, nt, &fp, s_obs, M, &s_tab)) v.hits[i] += 1u;
+    } else if (pocs_pose_collides(nx, ny, nt, &fp, s_obs, M, &s_tab)) {
+      const uint32_t old = v.hits[i];                // the counter is in hand exactly when the particle collides
+      v.hits[i] = old + 1u;
+      first += old == 0u ? 1u : 0u;
+    }
   }
+  if (MODE != MC_PLAIN) mc_add_first_hits(first, a.wp_counts + (size_t)blockIdx.y * (size_t)a.W + (size_t)a.step + 1);   // control s -> waypoint s + 1
 }
+template <bool NT>
+__global__ __launch_bounds__(POCS_BLOCK) void k_mc_step(pocs_mc_launch a) { mc_step_body<NT, MC_PLAIN>(a); }
+template <bool NT, int MODE>
+__global__ __launch_bounds__(POCS_BLOCK) void k_mc_step_counts(pocs_mc_launch a) { mc_step_body<NT, MODE>(a); }
 
-__global__ __launch_bounds__(POCS_BLOCK) void k_mc_fused(pocs_mc_launch a) {
+// MC_COUNTS: a particle has at most one first collision, so per step a wave ballots them and one lane adds the wave's count,
+// only when there is one (no block-level sum: the blocks of a fused launch never meet between steps).
+template <int MODE>
+__device__ __forceinline__ void mc_fused_body(const pocs_mc_launch& a) {
   __shared__ double s_obs[POCS_MAX_OBSTACLES * POCS_OBS_STRIDE];
   __shared__ pocs_footprint s_fp;
   __shared__ int s_M;
@@ -1408,6 +1491,7 @@ __global__ __launch_bounds__(POCS_BLOCK) void k_mc_fused(pocs_mc_launch a) {
   const pocs_footprint fp = s_fp;
   const int M = s_M;
   const mc_run_start st = mc_start(a);             // (its steps: uniform per block, blockIdx.y being the run)
+  unsigned long long* wp = MODE != MC_PLAIN ? a.wp_counts + (size_t)blockIdx.y * (size_t)a.W : nullptr;
   const long long stride = (long long)gridDim.x * POCS_BLOCK;
   for (long long i = (long long)blockIdx.x * POCS_BLOCK + threadIdx.x; i < a.count; i += stride) {
     double z[3];
@@ -1417,6 +1501,7 @@ __global__ __launch_bounds__(POCS_BLOCK) void k_mc_fused(pocs_mc_launch a) {
     double y = fma(a.L0[2], z[1], fma(a.L0[1], z[0], st.mu[1]));
     double t = fma(a.L0[5], z[2], fma(a.L0[4], z[1], fma(a.L0[3], z[0], st.mu[2])));
     unsigned h = pocs_pose_collides(x, y, t, &fp, s_obs, M, &s_tab) ? 1u : 0u;
+    if (MODE != MC_PLAIN) mc_wave_first_hits(h != 0u, wp);
     for (int s = 0; s < st.steps; ++s) {
       const double* u = v.chain + (size_t)s * POCS_CHAIN_STRIDE + 6;   // wave-uniform
       const double u0 = u[0], u1 = u[1], u2 = u[2];
@@ -1425,12 +1510,20 @@ __global__ __launch_bounds__(POCS_BLOCK) void k_mc_fused(pocs_mc_launch a) {
       x = fma(u1, cs, x);
       y = fma(u1, sn, y);
       t = pocs_wrap_angle(t + u0 + u2);
-      h += pocs_pose_collides(x, y, t, &fp, s_obs, M, &s_tab) ? 1u : 0u;
+      if (MODE == MC_PLAIN) {
+        h += pocs_pose_collides(x, y, t, &fp, s_obs, M, &s_tab) ? 1u : 0u;
+      } else {
+        const bool hit = pocs_pose_collides(x, y, t, &fp, s_obs, M, &s_tab);
+        mc_wave_first_hits(hit && h == 0u, wp + s + 1);
+        h += hit ? 1u : 0u;
+      }
     }
     v.x[i] = x; v.y[i] = y; v.th[i] = t;
     v.hits[i] = h;
   }
 }
+__global__ __launch_bounds__(POCS_BLOCK) void k_mc_fused(pocs_mc_launch a) { mc_fused_body<MC_PLAIN>(a); }
+__global__ __launch_bounds__(POCS_BLOCK) void k_mc_fused_counts(pocs_mc_launch a) { mc_fused_body<MC_COUNTS>(a); }
 
 __global__ __launch_bounds__(POCS_BLOCK) void k_mc_count(pocs_mc_launch a) {
   __shared__ unsigned s_w[POCS_BLOCK / 64];
@@ -1575,16 +1668,30 @@ hipError_t pocs_launch_gmm_advance(int K, const pocs_gmm_launch& a, hipStream_t 
   return hipGetLastError();
 }
 hipError_t pocs_launch_mc_init(int nblk, const pocs_mc_launch& a, hipStream_t s) {
-  hipLaunchKernelGGL(k_mc_init, dim3(nblk, a.nruns), dim3(POCS_BLOCK), 0, s, a);
+  if (a.wp_mode != 0 && !a.wp_counts) return hipErrorInvalidValue;
+  if (a.wp_mode) hipLaunchKernelGGL(k_mc_init<MC_COUNTS>, dim3(nblk, a.nruns), dim3(POCS_BLOCK), 0, s, a);
+  else           hipLaunchKernelGGL(k_mc_init<MC_PLAIN>, dim3(nblk, a.nruns), dim3(POCS_BLOCK), 0, s, a);
   return hipGetLastError();
 }
 hipError_t pocs_launch_mc_step(int nblk, const pocs_mc_launch& a, hipStream_t s) {
-  if (a.nontemporal) hipLaunchKernelGGL(k_mc_step<true>, dim3(nblk, a.nruns), dim3(POCS_BLOCK), 0, s, a);
-  else               hipLaunchKernelGGL(k_mc_step<false>, dim3(nblk, a.nruns), dim3(POCS_BLOCK), 0, s, a);
+  const dim3 grid(nblk, a.nruns), block(POCS_BLOCK);
+  if (a.wp_mode != 0 && !a.wp_counts) return hipErrorInvalidValue;
+  if (a.wp_mode == 2) {                               // first collisions per waypoint, and the risk bound obeyed
+    if (!a.wp_stop || a.wp_n < 1 || a.step < 0 || a.step + 1 >= a.W) return hipErrorInvalidValue;
+    if (a.nontemporal) hipLaunchKernelGGL((k_mc_step_counts<true, MC_STOP>), grid, block, 0, s, a);
+    else               hipLaunchKernelGGL((k_mc_step_counts<false, MC_STOP>), grid, block, 0, s, a);
+  } else if (a.wp_mode == 1) {                        // first collisions per waypoint
+    if (a.step < 0 || a.step + 1 >= a.W) return hipErrorInvalidValue;
+    if (a.nontemporal) hipLaunchKernelGGL((k_mc_step_counts<true, MC_COUNTS>), grid, block, 0, s, a);
+    else               hipLaunchKernelGGL((k_mc_step_counts<false, MC_COUNTS>), grid, block, 0, s, a);
+  } else if (a.nontemporal) hipLaunchKernelGGL(k_mc_step<true>, grid, block, 0, s, a);
+  else                      hipLaunchKernelGGL(k_mc_step<false>, grid, block, 0, s, a);
   return hipGetLastError();
 }
 hipError_t pocs_launch_mc_fused(int nblk, const pocs_mc_launch& a, hipStream_t s) {
-  hipLaunchKernelGGL(k_mc_fused, dim3(nblk, a.nruns), dim3(POCS_BLOCK), 0, s, a);
+  if (a.wp_mode == 2 || (a.wp_mode != 0 && !a.wp_counts)) return hipErrorInvalidValue;      // (no stop without a launch boundary per step)
+  if (a.wp_mode) hipLaunchKernelGGL(k_mc_fused_counts, dim3(nblk, a.nruns), dim3(POCS_BLOCK), 0, s, a);
+  else           hipLaunchKernelGGL(k_mc_fused, dim3(nblk, a.nruns), dim3(POCS_BLOCK), 0, s, a);
   return hipGetLastError();
 }
 hipError_t pocs_launch_mc_count(int nblk, const pocs_mc_launch& a, hipStream_t s) {
