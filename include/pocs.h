@@ -191,6 +191,57 @@ int pocs_set_plans(pocs_ctx* ctx, int P, const int* W, const double* trajs, cons
 int pocs_set_plan_risk_bound(pocs_ctx* ctx, double bound);
 int pocs_get_plan_evaluated(pocs_ctx* ctx, int* out, int cap);
 
+/* ---- a tree of candidate plans (ours) ------------------------------------------------------
+ * What a planner holds is a search tree: candidates that share long prefixes (RRT extensions, lattice expansions).  With a
+ * tree of T nodes set (1 <= T <= POCS_MAX_TREE_NODES), one pocs_run_gmm_estimation / pocs_run_simulation call evaluates every
+ * NODE once -- not every root-to-leaf path -- and returns the running probability of the path root -> n for every node n.
+ *   parent[0] == -1 and 0 <= parent[n] < n otherwise: one root, nodes in topological order.  poses: the nodes' poses, 3 x T by
+ *   component (x_0..x_{T-1} y_0.. theta_0..); odoms: the control of the edge parent[n] -> n, 3 x T by component (node 0's
+ *   entry is ignored; may be NULL for T = 1).  A path's length, depth + 1, is bounded as pocs_set_path_length bounds it.
+ *   Anything else: POCS_E_ARG.  nodes = 0 clears the tree: the context goes back to its single plan and batch.  Setting a
+ *   tree drops the last results.
+ * THE CONTRACT: for every node n, every value below is bit for bit what pocs_set_plans computes for the path root -> n alone
+ * under POCS_OPT_PLAN_SEEDS = 1, on a context with the same configuration, seed and run counter -- GMM and MC, both MC launch
+ * forms.  (The host chain is keyed by (seed, step), the mixture of a waypoint depends on the waypoints before it only, and
+ * the moment sums do not depend on the launch they travel in: a shared prefix computes the same bits for every path.)
+ * While a tree is set:
+ *   - a call draws the stream of run run_index, as POCS_OPT_PLAN_SEEDS = 1 does for plans, and the run counter advances by 1;
+ *     pocs_run_gmm_estimation / pocs_run_simulation return node 0's value;
+ *   - pocs_get_tree_probabilities: per node, in node order, the running probability 1 - prod (1 - p_v) over the path root -> n
+ *     (after an MC call: collided at or before n / numParticles); pocs_mc_get_tree_counts: after an MC call, per node, the
+ *     particles that collided at or before n on its path; POCS_E_BUFFER for cap < T, POCS_E_STATE when the last call was not
+ *     such a call;
+ *   - pocs_select_tree_node(n) makes the getters show the path root -> n as a plan of depth(n) + 1 waypoints:
+ *     pocs_get_path_length, pocs_get_waypoint_probabilities, pocs_get_moments, pocs_get_gmm_state, pocs_get_host_chain,
+ *     pocs_mc_get_waypoint_counts (always counted on a tree, POCS_OPT_MC_WAYPOINT_COUNTS or not).  pocs_copy_particles serves
+ *     the nodes of the DEEPEST level only (an MC call keeps two levels of particle state, not T clouds) and returns
+ *     POCS_E_STATE for any other node.  A new call selects node 0;
+ *   - samples are NOT stored, whatever POCS_OPT_STORE_SAMPLES says: pocs_copy_gmm_samples returns POCS_E_STATE;
+ *   - a tree and a set of plans exclude each other: pocs_set_plans while a tree is set, pocs_set_plan_tree while plans are set,
+ *     and pocs_set_batch, pocs_set_path_length, pocs_set_trajectory, pocs_set_odometry, pocs_select_batch_run return
+ *     POCS_E_ORDER; a shard, the step API (pocs_gmm_begin) and the in-library exchange (pocs_xchg_*) return POCS_E_STATE;
+ *     run-ahead is not applied; POCS_OPT_PROFILE = 1 runs the call eagerly without per-launch times.
+ * Risk bound (pocs_set_plan_risk_bound in (0, 1)): a GMM call does not evaluate the descendants of a node whose running
+ * probability has reached the bound.  The stop is decided on the device -- a node's launch reads its parent's stop word and
+ * inherits it -- and the host restates the rule on what it reads back (a mismatch: POCS_E_DEVICE).  A stopped node's entry of
+ * pocs_get_tree_probabilities is its own running probability; an unevaluated node's entry is its nearest evaluated ancestor's,
+ * and its byte of pocs_get_tree_evaluated is 0 (1 for every evaluated node; all 1 with the bound off and after an MC call).
+ * With an unevaluated node selected the getters cover the evaluated part of its path.  Everything evaluated is bit for bit
+ * what it is with the bound off.  An MC call on a tree IGNORES the bound, POCS_OPT_MC_RISK_BOUND included.
+ * Launches: the nodes are laid out level by level; per level a GMM call makes one small launch that builds the nodes'
+ * mixtures from their parents' and one sampling launch (more for a level wider than 256 nodes); an MC call makes one launch
+ * per level that moves every node's particles from its parent's cloud into its own -- this per-step form also serves
+ * POCS_OPT_MC_FUSED = 1 (same arithmetic, same bits) -- and refuses (POCS_E_ARG) a tree whose two widest consecutive
+ * levels' clouds would not fit (DESIGN.md sections 3 and 5). */
+#define POCS_MAX_TREE_NODES 4096
+int pocs_set_plan_tree(pocs_ctx* ctx, int nodes, const int* parent,
+                       const double* poses,   /* 3 x nodes by component: x_0..x_{T-1} y_0.. theta_0.. */
+                       const double* odoms);  /* 3 x nodes by component: the control of the edge parent[n] -> n (node 0's entry is ignored) */
+int pocs_get_tree_probabilities(pocs_ctx* ctx, double* out, int cap);   /* per node, node order: running probability of the path root -> n */
+int pocs_get_tree_evaluated(pocs_ctx* ctx, unsigned char* out, int cap);/* per node: 1 evaluated, 0 cut off below a stopped ancestor */
+int pocs_mc_get_tree_counts(pocs_ctx* ctx, unsigned long long* out, int cap); /* MC: per node, particles that collided at or before n on its path */
+int pocs_select_tree_node(pocs_ctx* ctx, int node);
+
 /* ---- sharding over GPUs (one process per GPU; the caller owns the collective) -----------
  * A context evaluates global sample / particle indices [first, first+count) of the N configured;
  * random draws are keyed by the GLOBAL index, so every sample, flag, survivor count and hit counter is the same

@@ -17,6 +17,7 @@ OPT_STORE_SAMPLES, OPT_MC_FUSED, OPT_USE_GRAPH, OPT_PROFILE, OPT_RUN_AHEAD, OPT_
 OPT_SUB_BATCHES, OPT_MC_NONTEMPORAL, OPT_PLAN_SEEDS, OPT_MC_WAYPOINT_COUNTS, OPT_MC_RISK_BOUND = 8, 9, 10, 11, 12
 NMOM = 11
 MAX_PLANS = 256
+MAX_TREE_NODES = 4096
 
 _dp = C.POINTER(C.c_double)
 _vp = C.c_void_p
@@ -51,6 +52,11 @@ SIGNATURES = {
     "pocs_set_plans": (C.c_int, [_vp, C.c_int, C.POINTER(C.c_int), _dp, _dp]),
     "pocs_set_plan_risk_bound": (C.c_int, [_vp, C.c_double]),
     "pocs_get_plan_evaluated": (C.c_int, [_vp, C.POINTER(C.c_int), C.c_int]),
+    "pocs_set_plan_tree": (C.c_int, [_vp, C.c_int, C.POINTER(C.c_int), _dp, _dp]),
+    "pocs_get_tree_probabilities": (C.c_int, [_vp, _dp, C.c_int]),
+    "pocs_get_tree_evaluated": (C.c_int, [_vp, C.POINTER(C.c_ubyte), C.c_int]),
+    "pocs_mc_get_tree_counts": (C.c_int, [_vp, C.POINTER(C.c_ulonglong), C.c_int]),
+    "pocs_select_tree_node": (C.c_int, [_vp, C.c_int]),
     "pocs_set_shard": (C.c_int, [_vp, C.c_longlong, C.c_longlong]),
     "pocs_set_stream": (C.c_int, [_vp, _vp]),
     "pocs_gmm_begin": (C.c_int, [_vp]),
@@ -306,6 +312,48 @@ class Context:
         out = np.zeros(n, dtype=np.int32)
         got = self._chk(self.lib.pocs_get_plan_evaluated(self.h, out.ctypes.data_as(C.POINTER(C.c_int)), n))
         return out[:got]
+
+    def set_plan_tree(self, parent, poses, odoms):
+        """A tree of candidate plans: parent int[T] (parent[0] = -1, parent[n] < n), poses T x 3, odoms T x 3 (row n = the
+        control of the edge parent[n] -> n; row 0 is ignored).  Every run call then evaluates each NODE once; the results
+        come in node order (tree_probabilities, tree_counts) and select_tree_node(n) shows the path root -> n to the getters."""
+        from .planio import check_tree
+        parent, poses, odoms = check_tree(parent, poses, odoms)
+        T = len(parent)
+        self._chk(self.lib.pocs_set_plan_tree(self.h, T, parent.ctypes.data_as(C.POINTER(C.c_int)),
+                                              _arr(poses.T).ctypes.data_as(_dp), _arr(odoms.T).ctypes.data_as(_dp)))
+        self._tree_nodes = T
+
+    def clear_plan_tree(self):
+        """Back to the single plan (and batch) of set_plan / set_batch."""
+        self._chk(self.lib.pocs_set_plan_tree(self.h, 0, None, None, None))
+        self._tree_nodes = 0
+
+    def tree_probabilities(self):
+        """Per node, in node order: the running probability of the path root -> n of the last call on the tree."""
+        T = getattr(self, "_tree_nodes", 0)
+        out = np.zeros(max(T, 1))
+        got = self._chk(self.lib.pocs_get_tree_probabilities(self.h, out.ctypes.data_as(_dp), T))
+        return out[:got]
+
+    def tree_evaluated(self):
+        """Per node: 1 evaluated, 0 cut off below a node stopped by the risk bound (uint8[T])."""
+        T = getattr(self, "_tree_nodes", 0)
+        out = np.zeros(max(T, 1), dtype=np.uint8)
+        got = self._chk(self.lib.pocs_get_tree_evaluated(self.h, out.ctypes.data_as(C.POINTER(C.c_ubyte)), T))
+        return out[:got]
+
+    def tree_counts(self):
+        """After an MC call on the tree, per node: the particles that collided at or before n on its path (uint64[T])."""
+        T = getattr(self, "_tree_nodes", 0)
+        out = np.zeros(max(T, 1), dtype=np.uint64)
+        got = self._chk(self.lib.pocs_mc_get_tree_counts(self.h, out.ctypes.data_as(C.POINTER(C.c_ulonglong)), T))
+        return out[:got]
+
+    def select_tree_node(self, n):
+        """The getters (path length, waypoint probabilities, moments, mixture state, host chain, waypoint counts) show the
+        path root -> n of the last call on the tree, as a plan of depth(n) + 1 waypoints."""
+        self._chk(self.lib.pocs_select_tree_node(self.h, int(n)))
 
     def set_shard(self, first=-1, count=-1):
         """Evaluate global indices [first, first+count); no arguments = the whole range."""

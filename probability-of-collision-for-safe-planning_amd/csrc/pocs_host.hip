@@ -107,6 +107,24 @@ struct pocs_ctx {
   int mc_wp_W = 0;
   std::vector<int> plan_E_mc;                     // [P] waypoints evaluated per plan in the last MC call of plans under the bound (empty: every plan to its end)
 
+  // a tree of candidate plans (pocs_set_plan_tree): T > 0 = every run* call evaluates the T nodes once each.  On the device a node
+  // is a SLOT: the nodes level by level (BFS), every level a contiguous range of slots, and every per-run array holds one row
+  // per slot -- while a tree is set W = 1 and batch = T (the single plan's length and batch wait in single_W / single_batch,
+  // as under pocs_set_plans; a tree and a set of plans exclude each other).
+  int tree_n = 0;
+  std::vector<int> tree_parent, tree_depth;       // [T], the caller's node order
+  std::vector<double> tree_pose, tree_odom;       // 3 x T by component: the node's pose, the control of the edge into it
+  std::vector<int> tree_slot, tree_node;          // node -> slot, slot -> node
+  std::vector<int> tree_level;                    // [D + 2]: level d = slots [tree_level[d], tree_level[d + 1])
+  std::vector<int> tree_pslot;                    // [T] the slot of every slot's parent (slot 0: 0), as uploaded to d_tparent
+  bool tree_dirty = false;
+  int tree_last = 0;                              // what the last call on the tree was: 0 none, 1 GMM, 2 MC
+  int tree_sel = 0;                               // the node the getters show (pocs_select_tree_node)
+  std::vector<double> tree_probs;                 // [T] node order: running probability of the path root -> n
+  std::vector<unsigned char> tree_eval;           // [T] 1 evaluated, 0 cut off below a stopped ancestor
+  std::vector<unsigned long long> tree_F, tree_C; // [T] MC: first collisions at the node, collided at or before it
+  size_t tree_mc_half = 0;                        // MC: elements of one level's half of the particle buffers
+
   // host image (headers | chains | initial mixtures) of the NEXT batch, computed while the GPU
   // works on the current one
   struct {
@@ -123,6 +141,7 @@ struct pocs_ctx {
   DevBuf d_sx, d_sy, d_st, d_flags, d_px, d_py, d_pt, d_hits, d_total, d_ticket, d_tables;
   DevBuf d_runplan;                      // a call of plans: [R][4] start mean and steps per run (the MC kernels)
   DevBuf d_surv;                         // a call of plans under a risk bound: [R] running survival product of every run
+  DevBuf d_tparent;                      // a tree of plans: [T] int, the slot of every slot's parent
   // one-hop exchange (pocs_xchg_*): this rank's buffer, the peers' buffers as mapped here
   void* xchg_own = nullptr;
   void* xchg_peer[POCS_XCHG_MAX_WORLD] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
@@ -277,8 +296,56 @@ PlanView plan_view(const pocs_ctx* c, int p) {          // p < 0: the single pla
   return PlanView{c->plan_traj.data() + c->plan_toff[(size_t)p], c->plan_odom.data() + c->plan_ooff[(size_t)p], c->plan_W[(size_t)p]};
 }
 
+// Step i of the chain: from waypoint xs to waypoint xg under the nominal control us, with the normals of step i.  Carries the
+// main EKF's mu / cov and the real state across the step and fills the step's record.  A plan applies it along its waypoints
+// (compute_chain), a tree of plans from every parent to each of its children (build_tree_image).
+void chain_step(const pocs_ctx* c, uint64_t seed, int i, const double us[3], const double xs[3], const double xg[3],
+                double mu[3], double cov[9], double real[3], double* rec) {
+  const int L = c->sensor.L;
+  const double a1 = c->alphas[0], a2 = c->alphas[1], a3 = c->alphas[2], a4 = c->alphas[3];
+  // generateM_EKF on the NOMINAL control
+  rec[3] = a1 * (us[0] * us[0]) + a2 * (us[1] * us[1]);
+  rec[4] = a3 * (us[1] * us[1]) + a4 * (us[0] * us[0]) + a4 * (us[2] * us[2]);
+  rec[5] = a1 * (us[2] * us[2]) + a2 * (us[1] * us[1]);
+  // generateL + applied control
+  double ureq[3], applied[3];
+  inverse_odometry(mu, xg, ureq);
+  for (int j = 0; j < 3; ++j) {
+    const double xhat = mu[j] - xs[j];
+    const double ubar = ureq[j] - us[j];
+    const double gain = ubar / (xhat != 0 ? xhat : 0.1);
+    applied[j] = us[j] + gain * xhat;
+    rec[j] = applied[j];
+  }
+  // EKFpredict on the main estimate
+  double pmu[3], pcov[9];
+  pocs_ekf_predict(mu, cov, applied, rec + 3, pmu, pcov);
+  // sampleOdometry on the APPLIED control
+  const double v0 = a1 * (applied[0] * applied[0]) + a2 * (applied[1] * applied[1]);
+  const double v1 = a3 * (applied[1] * applied[1]) +
+                    a4 * ((applied[0] * applied[0]) + (applied[2] * applied[2]));
+  const double v2 = a1 * (applied[2] * applied[2]) + a2 * (applied[1] * applied[1]);
+  double noisy[3];
+  noisy[0] = applied[0] + chain_normal(seed, i, 0) * sqrt(v0);
+  noisy[1] = applied[1] + chain_normal(seed, i, 1) * sqrt(v1);
+  noisy[2] = applied[2] + chain_normal(seed, i, 2) * sqrt(v2);
+  rec[6] = noisy[0]; rec[7] = noisy[1]; rec[8] = noisy[2];
+  double next[3];
+  pocs_motion(real, noisy, next);
+  real[0] = next[0]; real[1] = next[1]; real[2] = next[2];
+  // noisy range observations of the real state
+  for (int l = 0; l < L; ++l) {
+    const double dx = real[0] - c->sensor.lx[l], dy = real[1] - c->sensor.ly[l];
+    const double dist = sqrt(dx * dx + dy * dy);
+    rec[POCS_CHAIN_Z + l] = dist + (0.0 + chain_normal(seed, i, 3 + l) * sqrt(c->sensor.Q));
+  }
+  pocs_ekf_update(pmu, pcov, rec + POCS_CHAIN_Z, &c->sensor);
+  memcpy(mu, pmu, 3 * sizeof(double));
+  memcpy(cov, pcov, 9 * sizeof(double));
+}
+
 void compute_chain(pocs_ctx* c, uint64_t seed, const PlanView& pv) {
-  const int W = pv.W, L = c->sensor.L;
+  const int W = pv.W;
   const double* traj = pv.traj;
   const double* odom = pv.odom;
   c->h_chain.assign((size_t)(W > 1 ? W - 1 : 1) * POCS_CHAIN_STRIDE, 0.0);
@@ -288,51 +355,12 @@ void compute_chain(pocs_ctx* c, uint64_t seed, const PlanView& pv) {
   double cov[9];
   memcpy(cov, c->cov0, sizeof cov);
   double real[3] = {mu[0], mu[1], mu[2]};
-  const double a1 = c->alphas[0], a2 = c->alphas[1], a3 = c->alphas[2], a4 = c->alphas[3];
   for (int i = 0; i < W - 1; ++i) {
     double* rec = &c->h_chain[(size_t)i * POCS_CHAIN_STRIDE];
     const double us[3] = {odom[i], odom[(W - 1) + i], odom[2 * (W - 1) + i]};
     const double xs[3] = {traj[i], traj[W + i], traj[2 * W + i]};
     const double xg[3] = {traj[i + 1], traj[W + i + 1], traj[2 * W + i + 1]};
-    // generateM_EKF on the NOMINAL control
-    rec[3] = a1 * (us[0] * us[0]) + a2 * (us[1] * us[1]);
-    rec[4] = a3 * (us[1] * us[1]) + a4 * (us[0] * us[0]) + a4 * (us[2] * us[2]);
-    rec[5] = a1 * (us[2] * us[2]) + a2 * (us[1] * us[1]);
-    // generateL + applied control
-    double ureq[3], applied[3];
-    inverse_odometry(mu, xg, ureq);
-    for (int j = 0; j < 3; ++j) {
-      const double xhat = mu[j] - xs[j];
-      const double ubar = ureq[j] - us[j];
-      const double gain = ubar / (xhat != 0 ? xhat : 0.1);
-      applied[j] = us[j] + gain * xhat;
-      rec[j] = applied[j];
-    }
-    // EKFpredict on the main estimate
-    double pmu[3], pcov[9];
-    pocs_ekf_predict(mu, cov, applied, rec + 3, pmu, pcov);
-    // sampleOdometry on the APPLIED control
-    const double v0 = a1 * (applied[0] * applied[0]) + a2 * (applied[1] * applied[1]);
-    const double v1 = a3 * (applied[1] * applied[1]) +
-                      a4 * ((applied[0] * applied[0]) + (applied[2] * applied[2]));
-    const double v2 = a1 * (applied[2] * applied[2]) + a2 * (applied[1] * applied[1]);
-    double noisy[3];
-    noisy[0] = applied[0] + chain_normal(seed, i, 0) * sqrt(v0);
-    noisy[1] = applied[1] + chain_normal(seed, i, 1) * sqrt(v1);
-    noisy[2] = applied[2] + chain_normal(seed, i, 2) * sqrt(v2);
-    rec[6] = noisy[0]; rec[7] = noisy[1]; rec[8] = noisy[2];
-    double next[3];
-    pocs_motion(real, noisy, next);
-    real[0] = next[0]; real[1] = next[1]; real[2] = next[2];
-    // noisy range observations of the real state
-    for (int l = 0; l < L; ++l) {
-      const double dx = real[0] - c->sensor.lx[l], dy = real[1] - c->sensor.ly[l];
-      const double dist = sqrt(dx * dx + dy * dy);
-      rec[POCS_CHAIN_Z + l] = dist + (0.0 + chain_normal(seed, i, 3 + l) * sqrt(c->sensor.Q));
-    }
-    pocs_ekf_update(pmu, pcov, rec + POCS_CHAIN_Z, &c->sensor);
-    memcpy(mu, pmu, sizeof mu);
-    memcpy(cov, pcov, sizeof cov);
+    chain_step(c, seed, i, us, xs, xg, mu, cov, real, rec);
     memcpy(&c->h_mu[(size_t)i * 3], mu, sizeof mu);
     memcpy(&c->h_cov[(size_t)i * 9], cov, sizeof cov);
   }
@@ -341,7 +369,7 @@ void compute_chain(pocs_ctx* c, uint64_t seed, const PlanView& pv) {
 int check_common(pocs_ctx* c) {
   if (!c->have_q || !c->have_landmarks) return fail(c, POCS_E_STATE, "setQ / setLandmarks missing");
   if (!c->have_cov0) return fail(c, POCS_E_STATE, "setInitialCovariance missing");
-  if (!c->nplans && (!c->have_traj || !c->have_odom)) return fail(c, POCS_E_STATE, "setTrajectory / setOdometry missing");
+  if (!c->nplans && !c->tree_n && (!c->have_traj || !c->have_odom)) return fail(c, POCS_E_STATE, "setTrajectory / setOdometry missing");
   if (c->W < 1) return fail(c, POCS_E_STATE, "setPathLength missing");
   // The reference receives its collision world through the module constructor (sim(penv),
   // mcsimplugin.cpp:12 -> MCSimulator.h:139-156).  A context that was never given one would answer
@@ -380,6 +408,15 @@ int upload_static(pocs_ctx* c) {
   return POCS_OK;
 }
 
+int upload_tree(pocs_ctx* c) {                  // a tree of plans: the slots' parents, once per tree
+  if (!c->tree_dirty && c->d_tparent.p) return POCS_OK;
+  if (int r = ensure(c, c->d_tparent, c->tree_pslot.size() * sizeof(int))) return r;
+  HIPCHK(c, hipStreamSynchronize(c->stream));      // (nothing queued may still read the last tree's)
+  HIPCHK(c, hipMemcpy(c->d_tparent.p, c->tree_pslot.data(), c->tree_pslot.size() * sizeof(int), hipMemcpyHostToDevice));
+  c->tree_dirty = false;
+  return POCS_OK;
+}
+
 // pinned staging layout (doubles): [0 .. 2R) run headers, then R chains, then R initial mixtures, (a call of plans:
 // then R rows of start mean and steps), then the moments [W][R][K*11], then the MC total
 struct PinLayout { size_t chain, state0, runplan, moments, total, end; };
@@ -392,7 +429,8 @@ PinLayout pin_layout(const pocs_ctx* c) {
   p.moments = p.runplan + (c->nplans ? 4 * R : 0);
   p.total = p.moments + W * R * K * POCS_NMOM;
   p.end = p.total + R + 2 + (R + 4) / 2 + 1;   // one u64 per run: MC totals; the call's give-up word and -- under a risk bound -- the R stop words behind it
-  if (c->opt_mc_wp || c->opt_mc_rb) p.end += R * W + (R + 1) / 2;   // MC calls with first collisions per waypoint: behind the totals, [R][W] u64 and the R stop words
+  if (c->opt_mc_wp || c->opt_mc_rb) p.end += R * W + (R + 1) / 2;
+  if (c->tree_n) p.end += R;                          // an MC call on a tree: [T] collided at or before the node, [T] first collisions   // MC calls with first collisions per waypoint: behind the totals, [R][W] u64 and the R stop words
   return p;
 }
 
@@ -465,7 +503,7 @@ int gmm_shard(pocs_ctx* c, long long* first, long long* count) {
 // ONE plan takes the ticket form then, which computes the same bits -- tests/test_gpu_parity.py::test_lone_call_changes_no_bit).
 // Off (the default, bound >= 1) and without plans nothing of a call changes: the same launches of the same kernels, the same
 // memset, the same copies.
-bool risk_active(const pocs_ctx* c) { return c->nplans > 0 && c->risk_bound < 1.0; }
+bool risk_active(const pocs_ctx* c) { return (c->nplans > 0 || c->tree_n > 0) && c->risk_bound < 1.0; }
 
 // The synchronisation words of one call (pocs_kernels.h): [1] give-up code, [0], [2..3] pad, then -- under a risk bound -- the
 // runs' stop words [R] (padded to 4: they travel back with the give-up word in one copy), then the
@@ -498,13 +536,16 @@ int gmm_prepare(pocs_ctx* c) {
     if (int r = ensure(c, c->d_moments, W * R * K * POCS_NMOM * sizeof(double))) return r;
   if (c->ext_moments && c->ext_moments_len < (long long)(W * R * K * POCS_NMOM))
     return fail(c, POCS_E_BUFFER, "bound moments buffer too small");
-  if (int r = ensure(c, c->d_partial, 2 * (R << geo.vs_shift) * K * POCS_NMOM * sizeof(double))) return r;   // (x 2: a lone call alternates halves)
+  // (x 2: a lone call alternates halves; a tree: its launches cover at most 256 nodes and use the rows one after the other)
+  if (int r = ensure(c, c->d_partial, 2 * ((c->tree_n && R > 256 ? (size_t)256 : R) << geo.vs_shift) * K * POCS_NMOM * sizeof(double))) return r;
   if (int r = ensure(c, c->d_ticket, sync_words(c) * sizeof(unsigned))) return r;
   if (c->nplans)
     if (int r = ensure(c, c->d_runplan, R * 4 * sizeof(double))) return r;
   if (risk_active(c))
     if (int r = ensure(c, c->d_surv, R * sizeof(double))) return r;
-  if (c->opt_store) {
+  if (c->tree_n)
+    if (int r = upload_tree(c)) return r;
+  if (c->opt_store && !c->tree_n) {                   // (a call on a tree stores no samples)
     const size_t n = R * (size_t)sample_stride_of(count);
     if (int r = ensure(c, c->d_sx, n * sizeof(double))) return r;
     if (int r = ensure(c, c->d_sy, n * sizeof(double))) return r;
@@ -564,7 +605,44 @@ uint64_t plan_run(const pocs_ctx* c, int p) { return c->opt_plan_seeds ? 0 : (ui
 // GM_Model.h:57-77: K copies of (mu0, Sigma0), weights 1/K), laid out as the pinned staging area.
 // A call of plans: slot r holds plan slot_plan[r] -- its own chain, start mean and seed (plan_run) -- and a row of
 // start mean and steps.  Leaves slot 0's chain in c->h_chain / h_mu / h_cov.
+// A tree of plans: every slot's header (ONE stream: the run `base`'s, as common random numbers give every plan of a call),
+// the record of the edge into every node -- compute_chain unrolled over the tree: the main EKF's mu / cov and the real state
+// travel from parent to child, a node of depth d is reached by step d - 1 and its normals -- and the root's initial mixture.
+void build_tree_image(pocs_ctx* c, uint64_t base, double* img) {
+  const PinLayout pl = pin_layout(c);
+  const int T = c->tree_n;
+  const uint64_t seed = effective_seed(c, base);
+  std::vector<double> mu((size_t)T * 3), cov((size_t)T * 9), real((size_t)T * 3);
+  for (int n = 0; n < T; ++n) {                       // (node order is topological: a parent comes before its children)
+    const size_t slot = (size_t)c->tree_slot[(size_t)n];
+    pocs_run_header hdr; hdr.seed = seed; hdr.pad = c->xchg_calls;
+    memcpy(img + 2 * slot, &hdr, sizeof hdr);
+    double* rec = img + pl.chain + slot * POCS_CHAIN_STRIDE;
+    memset(rec, 0, POCS_CHAIN_STRIDE * sizeof(double));
+    const double xg[3] = {c->tree_pose[(size_t)n], c->tree_pose[(size_t)T + n], c->tree_pose[2 * (size_t)T + n]};
+    if (n == 0) {
+      memcpy(&mu[0], xg, sizeof xg); memcpy(&real[0], xg, sizeof xg); memcpy(&cov[0], c->cov0, 9 * sizeof(double));
+      continue;
+    }
+    const size_t p = (size_t)c->tree_parent[(size_t)n];
+    const double xs[3] = {c->tree_pose[p], c->tree_pose[(size_t)T + p], c->tree_pose[2 * (size_t)T + p]};
+    const double us[3] = {c->tree_odom[(size_t)n], c->tree_odom[(size_t)T + n], c->tree_odom[2 * (size_t)T + n]};
+    memcpy(&mu[3 * (size_t)n], &mu[3 * p], 3 * sizeof(double));
+    memcpy(&cov[9 * (size_t)n], &cov[9 * p], 9 * sizeof(double));
+    memcpy(&real[3 * (size_t)n], &real[3 * p], 3 * sizeof(double));
+    chain_step(c, seed, c->tree_depth[(size_t)n] - 1, us, xs, xg, &mu[3 * (size_t)n], &cov[9 * (size_t)n], &real[3 * (size_t)n], rec);
+  }
+  for (int k = 0; k < (c->K > 0 ? c->K : 0); ++k) {  // the root's slot is 0
+    double* s = img + pl.state0 + (size_t)k * POCS_STATE_STRIDE;
+    s[0] = c->tree_pose[0]; s[1] = c->tree_pose[(size_t)T]; s[2] = c->tree_pose[2 * (size_t)T];
+    memcpy(s + 3, c->cov0, 9 * sizeof(double));
+    s[12] = 1.0 / c->K; s[13] = 1.0; s[14] = 0.0; s[15] = 0.0;
+  }
+  c->h_chain.assign(POCS_CHAIN_STRIDE, 0.0); c->h_mu.assign(3, 0.0); c->h_cov.assign(9, 0.0);      // (the getters compute a path's chain when asked)
+}
+
 void build_run_image(pocs_ctx* c, uint64_t base, double* img, const std::vector<int>& slot_plan) {
+  if (c->tree_n) { build_tree_image(c, base, img); return; }
   const PinLayout pl = pin_layout(c);
   const int W = c->W, R = c->batch;
   const size_t steps = (size_t)(W > 1 ? W - 1 : 1);
@@ -597,6 +675,7 @@ void build_run_image(pocs_ctx* c, uint64_t base, double* img, const std::vector<
 void prefetch_next_batch(pocs_ctx* c, int groups) {
   const PinLayout pl = pin_layout(c);
   auto& a = c->ahead;
+  if (c->tree_n) { a.valid = false; return; }        // (a planner sets a new tree for its next call: nothing to look ahead to)
   std::vector<double> keep_chain = c->h_chain, keep_mu = c->h_mu, keep_cov = c->h_cov;
   a.image.resize(pl.moments);
   a.slot_plan = plan_layout(c, groups);
@@ -629,7 +708,7 @@ int stage_and_upload_runs(pocs_ctx* c, int groups, int kind) {
   c->batch_base = c->run_index;
   c->batch_R = R;
   c->view = 0;
-  c->run_index += c->nplans && c->opt_plan_seeds ? 1 : (uint64_t)R;
+  c->run_index += (c->nplans && c->opt_plan_seeds) || c->tree_n ? 1 : (uint64_t)R;      // (a tree: one stream for all its nodes)
   if (c->nplans) {
     std::vector<int>& ps = c->plan_slot[kind];
     ps.assign((size_t)R, 0);
@@ -651,7 +730,7 @@ int gmm_upload_run(pocs_ctx* c) {
   const int W = c->W, R = c->batch;
   // the initial mixture of run r goes to state[r][0]: R rows of K*16 doubles, pitch W*K*16
   const size_t row = (size_t)c->K * POCS_STATE_STRIDE * sizeof(double);
-  HIPCHK(c, hipMemcpy2DAsync(c->d_state.p, (size_t)W * row, pin + pl.state0, row, row, (size_t)R,
+  HIPCHK(c, hipMemcpy2DAsync(c->d_state.p, (size_t)W * row, pin + pl.state0, row, row, (size_t)(c->tree_n ? 1 : R),     // (a tree: the root's)
                              hipMemcpyHostToDevice, c->stream));
   return POCS_OK;
 }
@@ -705,7 +784,7 @@ int enqueue_advance(pocs_ctx* c, int w) {
 // One run per call (no batch, no run-ahead) on one GPU: the launches close the previous waypoint in their heads
 // (k_gmm_step, "LONE"): 30.6 -> 27.5 us per waypoint at 10^6 samples, K = 3 (MI355X).  POCS_OPT_LONE_CALL = 0
 // keeps the ticket-and-closer form; the results are the same bits.
-bool lone_call(const pocs_ctx* c) { return c->opt_lone && c->batch == 1 && !c->ext_moments && !(c->xchg_connected && c->shard_first >= 0) && !risk_active(c); }
+bool lone_call(const pocs_ctx* c) { return c->opt_lone && c->batch == 1 && !c->tree_n && !c->ext_moments && !(c->xchg_connected && c->shard_first >= 0) && !risk_active(c); }
 void set_lone(pocs_ctx* c, pocs_gmm_launch* a, int w) {
   const size_t half = ((size_t)1 << a->vs_shift) * c->K * POCS_NMOM;      // one run's rows
   a->lone = 1;
@@ -763,6 +842,7 @@ size_t gmm_hot_launches(const pocs_ctx* c) { return (size_t)c->W; }
 // POCS_OPT_SUB_BATCHES: 0 = this rule (default), 1, 2 (tests/test_gpu_parity.py checks the bits).
 int gmm_groups(const pocs_ctx* c) {
   if (c->ext_moments) return 1;                      // the caller's all-reduce covers the whole batch at once
+  if (c->tree_n) return 1;                           // a tree's levels depend on each other: one stream
   int g = (int)c->opt_groups;
   if (g == 0) {
     const double count = (double)(c->shard_first >= 0 ? c->shard_count : c->num_gmm);
@@ -779,7 +859,42 @@ int gmm_groups(const pocs_ctx* c) {
 // and samples back between two runs), the next replay's memset no longer cleared the tickets and its kernels
 // ran on garbage -- reproduced with round 2's library, gone with kernel-only graphs (tests/test_gpu_parity.py
 // ::test_graph_replays_survive_readbacks).
+// A call on a tree of plans: per level d an advance launch that builds the mixtures of the level's nodes from their parents'
+// rows (k_gmm_tree_advance), then the sampling launch over those nodes -- the ticket-and-closer form without an advance in its
+// tail, whose closers leave the nodes' moments (k_gmm_step_tree) -- a level wider than 256 nodes as several launches of at most
+// 256.  The launches of a level read what the launches of the level above wrote: one stream, one after the other.  A launch's
+// rows of partial sums start at the head of the row buffer whatever its first slot is (the kernels address them by slot).
+int enqueue_gmm_tree(pocs_ctx* c, long long count) {
+  const bool risk = risk_active(c);
+  const int D = (int)c->tree_level.size() - 2;
+  auto tree_launch = [&](pocs_gmm_launch* a, int d, int lo, int cnt) {
+    fill_gmm_launch(c, a, 0, count, d, lo, cnt, 1);
+    a->store = 0;
+    a->tree_parent = (const int*)c->d_tparent.p;
+    a->partial = (double*)((uintptr_t)c->d_partial.p - (uintptr_t)(((size_t)lo << a->vs_shift) * (size_t)c->K * POCS_NMOM * sizeof(double)));
+    a->partial_prev = a->partial;
+    if (risk) {
+      a->risk = 1;
+      a->stop = a->sync + sync_stop_offset(c);
+      a->surv = (double*)c->d_surv.p;
+      a->risk_bound = c->risk_bound;
+    }
+  };
+  for (int d = 0; d <= D; ++d) {
+    const int lo = c->tree_level[(size_t)d], hi = c->tree_level[(size_t)d + 1];
+    pocs_gmm_launch a;
+    tree_launch(&a, d, lo, hi - lo);
+    HIPCHK(c, pocs_launch_gmm_tree_advance(c->K, a, c->stream));
+    for (int s = lo; s < hi; s += 256) {
+      tree_launch(&a, d, s, hi - s < 256 ? hi - s : 256);
+      HIPCHK(c, pocs_launch_gmm_tree_step(c->K, a, c->stream));
+    }
+  }
+  return POCS_OK;
+}
+
 int enqueue_gmm_all(pocs_ctx* c, long long first, long long count, bool prof) {
+  if (c->tree_n) return enqueue_gmm_tree(c, count);
   const int W = c->W, R = c->batch, G = gmm_groups(c);
   if (int r = enqueue_advance(c, 0)) return r;
   if (prof) HIPCHK(c, hipEventRecord(c->ev_seq[0], c->stream));
@@ -855,7 +970,75 @@ void gmm_select_view(pocs_ctx* c, int v) {
 // back: plan p stops at the FIRST waypoint s with c_s = 1 - prod_{v <= s} (1 - p_v) >= bound, E[p] = s + 1 waypoints were
 // evaluated and its probability is c_s; the moments past E[p] - 1 are not read.  Device and host form c_s with the same
 // operations in the same order; if the two stops ever differ the call fails instead of reporting either.
+// The getters' view of a node of the last GMM call on a tree: the path root -> n as a plan of depth(n) + 1 waypoints (its
+// evaluated part, where the risk bound has cut the path off above n).
+void tree_select_gmm(pocs_ctx* c, int n) {
+  const int K = c->K;
+  std::vector<int> path;
+  for (int v = n; v >= 0; v = c->tree_parent[(size_t)v]) if (c->tree_eval[(size_t)v]) path.push_back(v);
+  std::reverse(path.begin(), path.end());
+  c->tree_sel = n;
+  c->probs.assign(path.size(), 0.0);
+  c->last_moments.assign(path.size() * (size_t)K * POCS_NMOM, 0.0);
+  for (size_t w = 0; w < path.size(); ++w) {
+    const double* m = &c->batch_moments[(size_t)c->tree_slot[(size_t)path[w]] * K * POCS_NMOM];
+    double coll = 0.0;
+    for (int k = 0; k < K; ++k) coll += m[(size_t)k * POCS_NMOM + 1];
+    c->probs[w] = coll / (1.0 * (double)c->num_gmm);
+    memcpy(&c->last_moments[w * (size_t)K * POCS_NMOM], m, (size_t)K * POCS_NMOM * sizeof(double));
+  }
+}
+
+// A call on a tree: moments [T][K*11] and -- under a risk bound -- the stop words [T], both by slot.  Every node's running
+// probability is its parent's survival product times its own (1 - p), formed as gmm_combine forms a plan's: the same operations
+// in the same order as along the path root -> n.  The bound's rule is restated on what came back: a node is evaluated unless an
+// ancestor's running probability has reached the bound; the device's word of every node must say the same (0, depth + 1 at
+// the bound, the inherited mark below it), or the call fails.
+int gmm_combine_tree(pocs_ctx* c, const double* moments, double* probability, const unsigned* stop) {
+  const int T = c->tree_n, K = c->K;
+  c->batch_R = T;
+  c->last_kind = 1;
+  c->batch_moments.assign(moments, moments + (size_t)T * K * POCS_NMOM);
+  c->plan_E.clear();
+  c->tree_probs.assign((size_t)T, 0.0);
+  c->tree_eval.assign((size_t)T, 1);
+  std::vector<double> prod((size_t)T, 1.0);
+  std::vector<unsigned char> cut((size_t)T, 0);        // the node, or an ancestor, is at the bound: nothing below is evaluated
+  for (int n = 0; n < T; ++n) {
+    const size_t slot = (size_t)c->tree_slot[(size_t)n];
+    const int p = c->tree_parent[(size_t)n], depth = c->tree_depth[(size_t)n];
+    const unsigned dev = stop ? stop[slot] : 0u;
+    if (p >= 0 && cut[(size_t)p]) {
+      if (!(dev & POCS_TREE_STOP_INHERITED))
+        return fail(c, POCS_E_DEVICE, "risk bound: node %d lies below a stopped node, the device's word for it is %u; results discarded", n, dev);
+      c->tree_eval[(size_t)n] = 0; cut[(size_t)n] = 1;
+      prod[(size_t)n] = prod[(size_t)p];
+      c->tree_probs[(size_t)n] = c->tree_probs[(size_t)p];
+      continue;
+    }
+    const double* m = moments + slot * K * POCS_NMOM;
+    double coll = 0.0;
+    for (int k = 0; k < K; ++k) coll += m[(size_t)k * POCS_NMOM + 1];
+    const double pw = coll / (1.0 * (double)c->num_gmm);
+    double pr = p >= 0 ? prod[(size_t)p] : 1.0;
+    pr *= (1.0 - pw);
+    prod[(size_t)n] = pr;
+    const unsigned host = (stop && 1.0 - pr >= c->risk_bound) ? (unsigned)depth + 1u : 0u;
+    if (host != dev)
+      return fail(c, POCS_E_DEVICE, "risk bound: node %d (depth %d): stop word %u on the device, %u on the host; results discarded", n, depth, dev, host);
+    cut[(size_t)n] = host != 0u;
+    c->tree_probs[(size_t)n] = 1.0 - pr;
+  }
+  c->batch_probs.assign(1, c->tree_probs[0]);
+  c->tree_last = 1;
+  c->view = 0;
+  tree_select_gmm(c, 0);
+  *probability = c->tree_probs[0];
+  return POCS_OK;
+}
+
 int gmm_combine(pocs_ctx* c, const double* moments, double* probability, const unsigned* stop = nullptr) {
+  if (c->tree_n) return gmm_combine_tree(c, moments, probability, stop);
   const int W = c->W, K = c->K, R = c->batch;          // moments: [W][R][K*11]
   c->batch_R = R;
   c->last_kind = 1;
@@ -895,6 +1078,13 @@ std::string config_key(const pocs_ctx* c, long long first, long long count, cons
            c->W, c->K, c->batch, gmm_groups(c), lone_call(c) ? 1 : 0, (c->xchg_connected && c->shard_first >= 0 && !c->ext_moments) ? c->xchg_world : 0,
            c->num_gmm, first, count, c->opt_store, c->opt_fused, (void*)c->stream, (void*)c->ext_moments);
   std::string key = buf;
+  if (c->tree_n) {                                   // a tree: the launches follow its shape (the levels' widths, the parents on the device)
+    unsigned long long h = 1469598103934665603ull;   // FNV-1a over the slots' parents
+    for (int v : c->tree_pslot) { h ^= (unsigned)v; h *= 1099511628211ull; }
+    char tb[96];
+    snprintf(tb, sizeof tb, " T%d D%zu h%llx rb%a", c->tree_n, c->tree_level.size() - 2, h, c->risk_bound);
+    key += tb;
+  }
   if (c->nplans) {                                   // a call of plans: one launch per waypoint and LIVE sub-batch, by the plans' lengths
     key += " P";
     for (int p = 0; p < c->nplans; ++p) key += (p ? "," : "") + std::to_string(c->plan_W[(size_t)p]);
@@ -930,7 +1120,8 @@ int run_gmm_full(pocs_ctx* c, double* probability) {
   // keeps the command processor from preparing the next launch under the running one, which adds ~9 us to what it
   // brackets); 2 = the replayed graph as it runs in production between ONE pair of events outside it: span / W is the
   // mean launch PERIOD -- duration plus the gap to the next launch --, an upper bound of the mean duration.
-  const bool prof = c->opt_profile == 1, span = c->opt_profile == 2 && c->opt_graph;
+  // (a call on a tree is not bracketed launch by launch: POCS_OPT_PROFILE = 1 runs it eagerly, untimed)
+  const bool prof = c->opt_profile == 1 && !c->tree_n, span = c->opt_profile == 2 && c->opt_graph;
   if (int r = prof_begin(c, gmm_hot_launches(c))) return r;
 #if defined(POCS_TUNING) && defined(POCS_GRAPH_WITH_COPIES)      // diagnostic build: round 2's graph shape (the memset and the two result copies as graph nodes)
   const bool copies_in_graph = c->opt_graph && !prof;
@@ -938,7 +1129,7 @@ int run_gmm_full(pocs_ctx* c, double* probability) {
   const bool copies_in_graph = false;
 #endif
   if (!copies_in_graph) if (int r = enqueue_ticket_reset(c)) return r;
-  if (c->opt_graph && !prof) {
+  if (c->opt_graph && c->opt_profile != 1) {
     const std::string key = config_key(c, first, count, "gmm");
     if (!c->graph_gmm || key != c->graph_gmm_key) {
       if (c->graph_gmm) { hipGraphExecDestroy(c->graph_gmm); c->graph_gmm = nullptr; }
@@ -972,7 +1163,7 @@ int run_gmm_full(pocs_ctx* c, double* probability) {
   lap("next batch prepared");
   HIPCHK(c, hipStreamSynchronize(c->stream));
   lap("synchronised");
-  if (int r = prof_collect(c, gmm_hot_launches(c))) return r;
+  if (prof) if (int r = prof_collect(c, gmm_hot_launches(c))) return r;
   if (prof || span) {
     float ms = 0.f;
     HIPCHK(c, hipEventElapsedTime(&ms, c->ev_seq[0], c->ev_seq[1]));
@@ -990,6 +1181,7 @@ int run_gmm_full(pocs_ctx* c, double* probability) {
     const unsigned* stop = risk_active(c) ? (const unsigned*)((double*)c->h_pin + pl.total + c->batch + 1) + 3 : nullptr;
     if (int r = gmm_combine(c, (double*)c->h_pin + pl.moments, probability, stop)) {
       c->batch_probs.clear(); c->probs.clear(); c->last_moments.clear(); c->batch_moments.clear(); c->plan_E.clear();
+      c->tree_probs.clear(); c->tree_eval.clear(); c->tree_last = 0;
       c->last_kind = 0; c->last_gmm_wp = -1;
       return r;
     }
@@ -1014,7 +1206,7 @@ int mc_shard(pocs_ctx* c, long long* first, long long* count) {
 // An MC call of plans obeys the risk bound only when asked to (POCS_OPT_MC_RISK_BOUND; by default it ignores the bound); such a
 // call, or any MC call under POCS_OPT_MC_WAYPOINT_COUNTS, counts the first collisions per waypoint.  Both off: the launches,
 // the memset and the copies of an MC call are what they have always been.
-bool mc_stop_active(const pocs_ctx* c) { return c->opt_mc_rb && risk_active(c); }
+bool mc_stop_active(const pocs_ctx* c) { return c->opt_mc_rb && risk_active(c) && !c->tree_n; }     // (an MC call on a tree ignores the bound)
 bool mc_counts_active(const pocs_ctx* c) { return c->opt_mc_wp || mc_stop_active(c); }
 // The fused kernel carries a particle through all its steps and meets no other block on the way: a call that stops on a count
 // takes the per-step form.
@@ -1122,8 +1314,134 @@ int mc_read_waypoint_counts(pocs_ctx* c, const unsigned long long* words) {
   return POCS_OK;
 }
 
+// An MC call on a tree of plans.  The root's cloud is drawn by k_mc_init; per level one k_mc_tree_step launch (several for a
+// level wider than 256 nodes) moves every node's particles from its parent's place in the previous level's half of the
+// particle buffers to its own place in this level's half -- two levels of state are live at a time -- and counts the node's
+// first collisions and its collided particles.  The fused form has no counterpart here: a node's cloud is its parent's, so
+// POCS_OPT_MC_FUSED = 1 is served by these per-step launches (the same arithmetic, the same bits).  The risk bound is ignored,
+// POCS_OPT_MC_RISK_BOUND or not.
+size_t tree_max_width(const pocs_ctx* c) {
+  size_t w = 1;
+  for (size_t d = 0; d + 1 < c->tree_level.size(); ++d) w = std::max(w, (size_t)(c->tree_level[d + 1] - c->tree_level[d]));
+  return w;
+}
+#define POCS_TREE_MC_MAX_BYTES (64ull << 30)      // both halves of the particle state of an MC call on a tree
+int enqueue_mc_tree(pocs_ctx* c, long long count) {
+  const int T = c->tree_n, D = (int)c->tree_level.size() - 2;
+  const size_t half = c->tree_mc_half;
+  pocs_mc_launch a;
+  memset(&a, 0, sizeof a);
+  a.hdr = (const pocs_run_header*)c->d_hdr.p;
+  a.env = (const pocs_env_dev*)c->d_env.p;
+  a.tables = (const pocs_tables*)c->d_tables.p;
+  a.chain = (const double*)c->d_chain.p;
+  a.total = (unsigned long long*)c->d_total.p;
+  a.wp_mode = 1;
+  a.wp_counts = a.total + T;                         // [T] first collisions, by slot (W = 1: k_mc_init's row of run 0 is the root's)
+  a.first = 0; a.count = count; a.stride = sample_stride_of(count);
+  a.W = 1;
+  a.nontemporal = c->opt_mc_nt >= 0 ? (int)c->opt_mc_nt : ((2.0 * (double)half * 28.0 > 232.0e6) ? 1 : 0);
+  a.mu0[0] = c->tree_pose[0]; a.mu0[1] = c->tree_pose[(size_t)T]; a.mu0[2] = c->tree_pose[2 * (size_t)T];
+  if (!pocs_chol3_lower(c->cov0, a.L0)) return fail(c, POCS_E_ARG, "initial covariance is not positive definite");
+  auto half_of = [&](pocs_mc_launch* l, int d) {
+    const size_t o = (size_t)(d & 1) * half;
+    l->x = (double*)c->d_px.p + o; l->y = (double*)c->d_py.p + o; l->th = (double*)c->d_pt.p + o; l->hits = (uint32_t*)c->d_hits.p + o;
+  };
+  half_of(&a, 0);
+  a.nruns = 1;
+  HIPCHK(c, pocs_launch_mc_init(grid_for_mc(count, 1), a, c->stream));
+  a.tree_parent = (const int*)c->d_tparent.p;
+  for (int d = 1; d <= D; ++d) {
+    const int lo = c->tree_level[(size_t)d], hi = c->tree_level[(size_t)d + 1];
+    pocs_mc_launch prev = a;
+    half_of(&prev, d - 1);
+    half_of(&a, d);
+    a.tree_sx = prev.x; a.tree_sy = prev.y; a.tree_sth = prev.th; a.tree_shits = prev.hits;
+    a.tree_dst_lo = lo; a.tree_src_lo = c->tree_level[(size_t)d - 1];
+    for (int s = lo; s < hi; s += 256) {
+      a.tree_lo = s;
+      a.nruns = hi - s < 256 ? hi - s : 256;
+      HIPCHK(c, pocs_launch_mc_tree_step(grid_for_mc(count, a.nruns), a, c->stream));
+    }
+  }
+  return POCS_OK;
+}
+
+int run_mc_tree(pocs_ctx* c) {
+  if (int r = check_common(c)) return r;
+  if (c->num_particles < 1) return fail(c, POCS_E_STATE, "setNumParticles missing");
+  if (int r = upload_static(c)) return r;
+  if (int r = upload_tree(c)) return r;
+  const long long count = c->num_particles;
+  const size_t T = (size_t)c->tree_n, stride = (size_t)sample_stride_of(count), half = tree_max_width(c) * stride;
+  if ((double)half * 2.0 * 28.0 > (double)POCS_TREE_MC_MAX_BYTES)
+    return fail(c, POCS_E_ARG, "MC on a tree: its widest level has %zu nodes; two levels of %lld particles each need %.1f GB of particle state, more than the %llu GB an MC call on a tree may hold",
+                tree_max_width(c), count, (double)half * 2.0 * 28.0 / 1e9, (unsigned long long)(POCS_TREE_MC_MAX_BYTES >> 30));
+  c->tree_mc_half = half;
+  if (int r = ensure(c, c->d_hdr, T * sizeof(pocs_run_header))) return r;
+  if (int r = ensure(c, c->d_chain, T * POCS_CHAIN_STRIDE * sizeof(double))) return r;
+  if (int r = ensure(c, c->d_px, 2 * half * sizeof(double))) return r;
+  if (int r = ensure(c, c->d_py, 2 * half * sizeof(double))) return r;
+  if (int r = ensure(c, c->d_pt, 2 * half * sizeof(double))) return r;
+  if (int r = ensure(c, c->d_hits, 2 * half * sizeof(uint32_t))) return r;
+  const size_t total_bytes = 2 * T * sizeof(unsigned long long);       // [T] collided at or before the node | [T] first collisions at it
+  if (int r = ensure(c, c->d_total, total_bytes + 16)) return r;
+  if (int r = ensure_pin(c)) return r;
+  if (int r = stage_and_upload_runs(c, 1, 1)) return r;
+  HIPCHK(c, hipMemsetAsync(c->d_total.p, 0, total_bytes, c->stream));
+  if (c->opt_graph && c->opt_profile != 1) {
+    const std::string key = config_key(c, 0, count, "mc-tree") + std::to_string(c->num_particles) + "h" + std::to_string(half);
+    if (!c->graph_mc || key != c->graph_mc_key) {
+      if (c->graph_mc) { hipGraphExecDestroy(c->graph_mc); c->graph_mc = nullptr; }
+      hipGraph_t g = nullptr;
+      HIPCHK(c, hipStreamBeginCapture(c->stream, hipStreamCaptureModeThreadLocal));
+      int r = enqueue_mc_tree(c, count);
+      hipError_t e = hipStreamEndCapture(c->stream, &g);
+      if (r) { if (g) hipGraphDestroy(g); return r; }
+      HIPCHK(c, e);
+      e = hipGraphInstantiate(&c->graph_mc, g, nullptr, nullptr, 0);
+      hipGraphDestroy(g);
+      HIPCHK(c, e);
+      c->graph_mc_key = key;
+    }
+    HIPCHK(c, hipGraphLaunch(c->graph_mc, c->stream));
+  } else {
+    if (int r = enqueue_mc_tree(c, count)) return r;
+  }
+  const PinLayout pl = pin_layout(c);
+  HIPCHK(c, hipMemcpyAsync((double*)c->h_pin + pl.total, c->d_total.p, total_bytes, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  c->prof_ms = 0.0; c->prof_launches = 0;
+  const unsigned long long* tot = (const unsigned long long*)((double*)c->h_pin + pl.total);
+  const unsigned long long* F = tot + T;
+  c->tree_F.assign(T, 0ull); c->tree_C.assign(T, 0ull);
+  c->tree_probs.assign(T, 0.0); c->tree_eval.assign(T, 1);
+  c->mc_wp.clear(); c->plan_E_mc.clear();
+  for (size_t n = 0; n < T; ++n) {
+    const size_t slot = (size_t)c->tree_slot[n];
+    const int p = c->tree_parent[n];
+    c->tree_F[n] = F[slot];
+    c->tree_C[n] = (p >= 0 ? c->tree_C[(size_t)p] : 0ull) + F[slot];
+    // (the kernel's own count of the node's collided particles must be its path's first collisions added up)
+    if (p >= 0 && tot[slot] != c->tree_C[n]) {
+      c->tree_F.clear(); c->tree_C.clear(); c->tree_probs.clear(); c->tree_eval.clear(); c->mc_counts.clear(); c->batch_probs.clear();
+      c->tree_last = 0; c->last_kind = 0; c->last_mc_count = 0;
+      return fail(c, POCS_E_DEVICE, "MC on a tree: node %zu has %llu collided particles, the first collisions along its path add up to %llu; results discarded",
+                  n, tot[slot], c->tree_C[n]);
+    }
+    c->tree_probs[n] = (double)c->tree_C[n] / (double)count;
+  }
+  c->mc_counts.assign(1, c->tree_C[0]);
+  c->last_mc_count = count;
+  c->last_kind = 2;
+  c->tree_last = 2;
+  c->tree_sel = 0;
+  return POCS_OK;
+}
+
 // One batch of MC roll-outs (runSimulation x batch) over this context's shard; fills c->mc_counts.
 int run_mc_local(pocs_ctx* c) {
+  if (c->tree_n) return run_mc_tree(c);
   if (int r = check_common(c)) return r;
   if (c->num_particles < 1) return fail(c, POCS_E_STATE, "setNumParticles missing");
   long long first, count;
@@ -1293,7 +1611,7 @@ void pocs_destroy(pocs_ctx* c) {
     if (c->ev_seq[1]) hipEventDestroy(c->ev_seq[1]);
     DevBuf* all[] = {&c->d_env, &c->d_sensor, &c->d_hdr, &c->d_chain, &c->d_state, &c->d_param,
                      &c->d_moments, &c->d_partial, &c->d_sx, &c->d_sy, &c->d_st, &c->d_flags,
-                     &c->d_px, &c->d_py, &c->d_pt, &c->d_hits, &c->d_total, &c->d_ticket, &c->d_tables, &c->d_runplan, &c->d_surv};
+                     &c->d_px, &c->d_py, &c->d_pt, &c->d_hits, &c->d_total, &c->d_ticket, &c->d_tables, &c->d_runplan, &c->d_surv, &c->d_tparent};
     for (DevBuf* b : all) if (b->p) hipFree(b->p);
     if (c->h_pin) hipHostFree(c->h_pin);
     if (c->h_copy) hipHostFree(c->h_copy);
@@ -1386,6 +1704,7 @@ int pocs_set_path_length(pocs_ctx* c, int W) {
   if (c) touch(c);
   if (!c) return POCS_E_ARG;
   if (c->nplans) return fail(c, POCS_E_ORDER, "pocs_set_path_length while plans are set: clear them first with pocs_set_plans(ctx, 0, ...)");
+  if (c->tree_n) return fail(c, POCS_E_ORDER, "pocs_set_path_length while a tree of plans is set: clear it first with pocs_set_plan_tree(ctx, 0, ...)");
   if (W < 1) return fail(c, POCS_E_ARG, "pathLength must be >= 1");
   if (W != c->W) { c->have_traj = false; c->have_odom = false; }
   c->W = W;
@@ -1396,6 +1715,7 @@ int pocs_set_trajectory(pocs_ctx* c, const double* v, int W) {
   if (c) touch(c);
   if (!c) return POCS_E_ARG;
   if (c->nplans) return fail(c, POCS_E_ORDER, "pocs_set_trajectory while plans are set: clear them first with pocs_set_plans(ctx, 0, ...)");
+  if (c->tree_n) return fail(c, POCS_E_ORDER, "pocs_set_trajectory while a tree of plans is set: clear it first with pocs_set_plan_tree(ctx, 0, ...)");
   if (c->W < 1) return fail(c, POCS_E_ORDER, "setTrajectory before setPathLength");
   if (W != c->W || !v) return fail(c, POCS_E_ARG, "setTrajectory needs 3*%d values", c->W);
   c->traj.assign(v, v + (size_t)3 * W);
@@ -1407,6 +1727,7 @@ int pocs_set_odometry(pocs_ctx* c, const double* v, int Wm1) {
   if (c) touch(c);
   if (!c) return POCS_E_ARG;
   if (c->nplans) return fail(c, POCS_E_ORDER, "pocs_set_odometry while plans are set: clear them first with pocs_set_plans(ctx, 0, ...)");
+  if (c->tree_n) return fail(c, POCS_E_ORDER, "pocs_set_odometry while a tree of plans is set: clear it first with pocs_set_plan_tree(ctx, 0, ...)");
   if (c->W < 1) return fail(c, POCS_E_ORDER, "setOdometry before setPathLength");
   if (Wm1 != c->W - 1 || (Wm1 > 0 && !v)) return fail(c, POCS_E_ARG, "setOdometry needs 3*%d values", c->W - 1);
   c->odom.assign(v, v + (size_t)3 * Wm1);
@@ -1487,6 +1808,7 @@ int pocs_set_batch(pocs_ctx* c, int runs) {
   if (!c) return POCS_E_ARG;
   touch(c);
   if (c->nplans) return fail(c, POCS_E_ORDER, "pocs_set_batch while plans are set (the batch is the plans): clear them first with pocs_set_plans(ctx, 0, ...)");
+  if (c->tree_n) return fail(c, POCS_E_ORDER, "pocs_set_batch while a tree of plans is set: clear it first with pocs_set_plan_tree(ctx, 0, ...)");
   if (runs < 1 || runs > 256) return fail(c, POCS_E_ARG, "batch %d outside 1..256", runs);
   if (c->gmm_open) return fail(c, POCS_E_ORDER, "pocs_set_batch inside a begin/end sequence");
   c->batch = runs;
@@ -1499,6 +1821,7 @@ static void drop_results(pocs_ctx* c) {
   c->h_chain.clear(); c->h_mu.clear(); c->h_cov.clear();
   c->plan_slot[0].clear(); c->plan_slot[1].clear(); c->plan_E.clear();
   c->mc_wp.clear(); c->plan_E_mc.clear();
+  c->tree_probs.clear(); c->tree_eval.clear(); c->tree_F.clear(); c->tree_C.clear(); c->tree_last = 0; c->tree_sel = 0;
   c->last_gmm_wp = -1; c->last_gmm_count = 0; c->last_mc_count = 0; c->last_kind = 0;
   c->view = 0; c->batch_R = c->batch;
 }
@@ -1517,6 +1840,7 @@ int pocs_set_plans(pocs_ctx* c, int P, const int* W, const double* trajs, const 
     }
     return POCS_OK;
   }
+  if (c->tree_n) return fail(c, POCS_E_ORDER, "pocs_set_plans while a tree of plans is set: clear it first with pocs_set_plan_tree(ctx, 0, ...)");
   if (!W || !trajs) return fail(c, POCS_E_ARG, "plans: null lengths or trajectories");
   size_t nt = 0, no = 0;
   int Wmax = 0;
@@ -1565,6 +1889,87 @@ int pocs_get_plan_evaluated(pocs_ctx* c, int* out, int cap) {
   return (int)E.size();
 }
 
+int pocs_set_plan_tree(pocs_ctx* c, int nodes, const int* parent, const double* poses, const double* odoms) {
+  if (!c) return POCS_E_ARG;
+  touch(c);
+  if (c->gmm_open) return fail(c, POCS_E_ORDER, "pocs_set_plan_tree inside a begin/end sequence");
+  if (nodes < 0 || nodes > POCS_MAX_TREE_NODES) return fail(c, POCS_E_ARG, "tree: %d nodes outside 0..%d", nodes, POCS_MAX_TREE_NODES);
+  if (nodes == 0) {                                  // back to the single plan
+    if (c->tree_n) {
+      c->W = c->single_W; c->batch = c->single_batch;
+      c->tree_n = 0;
+      c->tree_parent.clear(); c->tree_depth.clear(); c->tree_pose.clear(); c->tree_odom.clear();
+      c->tree_slot.clear(); c->tree_node.clear(); c->tree_level.clear(); c->tree_pslot.clear();
+      drop_results(c);
+    }
+    return POCS_OK;
+  }
+  if (c->nplans) return fail(c, POCS_E_ORDER, "pocs_set_plan_tree while plans are set: clear them first with pocs_set_plans(ctx, 0, ...)");
+  if (!parent || !poses || (nodes > 1 && !odoms)) return fail(c, POCS_E_ARG, "tree: null parents, poses or controls");
+  if (parent[0] != -1) return fail(c, POCS_E_ARG, "tree: node 0 is the root, its parent must be -1 (got %d)", parent[0]);
+  for (int n = 1; n < nodes; ++n)
+    if (parent[n] < 0 || parent[n] >= n)
+      return fail(c, POCS_E_ARG, "tree: parent[%d] = %d; one root, and every other node's parent comes before it (0 <= parent[n] < n)", n, parent[n]);
+  if (c->shard_first >= 0) return fail(c, POCS_E_STATE, "tree: not with a shard (pocs_set_shard(ctx, -1, -1) first): trees run on one GPU");
+  if (c->xchg_connected) return fail(c, POCS_E_STATE, "tree: not on a context connected to the in-library exchange");
+  const size_t T = (size_t)nodes;
+  std::vector<int> depth(T, 0);
+  int D = 0;
+  for (size_t n = 1; n < T; ++n) { depth[n] = depth[(size_t)parent[n]] + 1; D = depth[n] > D ? depth[n] : D; }
+  if (!c->tree_n) { c->single_W = c->W; c->single_batch = c->batch; }
+  c->tree_parent.assign(parent, parent + T);
+  c->tree_depth = depth;
+  c->tree_pose.assign(poses, poses + 3 * T);
+  if (odoms) c->tree_odom.assign(odoms, odoms + 3 * T); else c->tree_odom.assign(3 * T, 0.0);
+  // slots: level by level, every level a contiguous range, the nodes of a level in node order
+  c->tree_level.assign((size_t)D + 2, 0);
+  for (size_t n = 0; n < T; ++n) c->tree_level[(size_t)depth[n] + 1] += 1;
+  for (size_t d = 0; d <= (size_t)D; ++d) c->tree_level[d + 1] += c->tree_level[d];
+  std::vector<int> fill(c->tree_level.begin(), c->tree_level.end() - 1);
+  c->tree_slot.assign(T, 0); c->tree_node.assign(T, 0); c->tree_pslot.assign(T, 0);
+  for (size_t n = 0; n < T; ++n) { const int s = fill[(size_t)depth[n]]++; c->tree_slot[n] = s; c->tree_node[(size_t)s] = (int)n; }
+  for (size_t n = 1; n < T; ++n) c->tree_pslot[(size_t)c->tree_slot[n]] = c->tree_slot[(size_t)parent[n]];
+  c->tree_dirty = true;
+  c->tree_n = nodes;
+  c->W = 1;                                          // one row per node in every [run][W] array
+  c->batch = nodes;
+  drop_results(c);
+  return POCS_OK;
+}
+
+int pocs_get_tree_probabilities(pocs_ctx* c, double* out, int cap) {
+  if (!c || !out) return POCS_E_ARG;
+  if (!c->tree_n || !c->tree_last || c->tree_probs.empty()) return fail(c, POCS_E_STATE, "pocs_get_tree_probabilities: the last call was not a call on a tree of plans");
+  if ((int)c->tree_probs.size() > cap) return fail(c, POCS_E_BUFFER, "need %zu doubles", c->tree_probs.size());
+  memcpy(out, c->tree_probs.data(), c->tree_probs.size() * sizeof(double));
+  return (int)c->tree_probs.size();
+}
+
+int pocs_get_tree_evaluated(pocs_ctx* c, unsigned char* out, int cap) {
+  if (!c || !out) return POCS_E_ARG;
+  if (!c->tree_n || !c->tree_last || c->tree_eval.empty()) return fail(c, POCS_E_STATE, "pocs_get_tree_evaluated: the last call was not a call on a tree of plans");
+  if ((int)c->tree_eval.size() > cap) return fail(c, POCS_E_BUFFER, "need %zu bytes", c->tree_eval.size());
+  memcpy(out, c->tree_eval.data(), c->tree_eval.size());
+  return (int)c->tree_eval.size();
+}
+
+int pocs_mc_get_tree_counts(pocs_ctx* c, unsigned long long* out, int cap) {
+  if (!c || !out) return POCS_E_ARG;
+  if (!c->tree_n || c->tree_last != 2 || c->tree_C.empty()) return fail(c, POCS_E_STATE, "pocs_mc_get_tree_counts: the last call was not an MC call on a tree of plans");
+  if ((int)c->tree_C.size() > cap) return fail(c, POCS_E_BUFFER, "need %zu counters", c->tree_C.size());
+  memcpy(out, c->tree_C.data(), c->tree_C.size() * sizeof(unsigned long long));
+  return (int)c->tree_C.size();
+}
+
+int pocs_select_tree_node(pocs_ctx* c, int node) {
+  if (!c) return POCS_E_ARG;
+  if (!c->tree_n || !c->tree_last) return fail(c, POCS_E_STATE, "pocs_select_tree_node: the last call was not a call on a tree of plans");
+  if (node < 0 || node >= c->tree_n) return fail(c, POCS_E_ARG, "node %d outside the tree (0..%d)", node, c->tree_n - 1);
+  if (c->tree_last == 1) tree_select_gmm(c, node);
+  c->tree_sel = node;
+  return POCS_OK;
+}
+
 int pocs_get_batch_probabilities(pocs_ctx* c, double* out, int cap) {
   if (!c || !out) return POCS_E_ARG;
   if (c->ra_internal) {                       // the caller asked for one run at a time
@@ -1580,6 +1985,7 @@ int pocs_get_batch_probabilities(pocs_ctx* c, double* out, int cap) {
 int pocs_select_batch_run(pocs_ctx* c, int run) {
   if (!c) return POCS_E_ARG;
   if (c->ra_internal) return fail(c, POCS_E_ORDER, "pocs_select_batch_run: the last launch was a run-ahead batch (one run per command)");
+  if (c->tree_n) return fail(c, POCS_E_ORDER, "pocs_select_batch_run: a tree of plans is set (pocs_select_tree_node selects a node)");
   if (run < 0 || run >= c->batch_R || c->batch_probs.empty()) return fail(c, POCS_E_ARG, "run %d outside the last batch (0..%d)", run, c->batch_R - 1);
   if (c->last_kind == 1) gmm_select_view(c, run);       // per-waypoint probabilities and moments of that run
   c->view = run;
@@ -1591,6 +1997,7 @@ int pocs_set_shard(pocs_ctx* c, long long first, long long count) {
   if (!c) return POCS_E_ARG;
   if (first == -1 && count == -1) { c->shard_first = -1; c->shard_count = -1; return POCS_OK; }   // whole range
   if (c->nplans) return fail(c, POCS_E_STATE, "pocs_set_shard: plans are set (multi-GPU plan batches are not supported)");
+  if (c->tree_n) return fail(c, POCS_E_STATE, "pocs_set_shard: a tree of plans is set (trees run on one GPU)");
   if (first < 0 || count < 0) return fail(c, POCS_E_ARG, "negative shard");
   c->shard_first = first; c->shard_count = count;
   return POCS_OK;
@@ -1627,7 +2034,7 @@ static int ra_depth(const pocs_ctx* c, int kind) {
   return (int)(want < 8 ? 8 : want > 64 ? 64 : want);
 }
 static bool ra_wanted(const pocs_ctx* c, int kind) {
-  return ra_depth(c, kind) > 1 && c->batch == 1 && !c->nplans && c->shard_first < 0 && !c->opt_profile && !c->ext_moments && !c->gmm_open;
+  return ra_depth(c, kind) > 1 && c->batch == 1 && !c->nplans && !c->tree_n && c->shard_first < 0 && !c->opt_profile && !c->ext_moments && !c->gmm_open;
 }
 static void mc_fill_probs(pocs_ctx* c) {
   // getCollisionProportion, MCSimulator.h:324-330 (of the particles this context evaluated)
@@ -1705,6 +2112,13 @@ int pocs_mc_get_batch_counts(pocs_ctx* c, unsigned long long* out, int cap) {
 int pocs_mc_get_waypoint_counts(pocs_ctx* c, unsigned long long* out, int cap) {
   if (!c || !out) return POCS_E_ARG;
   const size_t W = (size_t)(c->mc_wp_W > 0 ? c->mc_wp_W : 1), r = (size_t)c->view;
+  if (c->tree_n) {                                   // the selected node's path: the first collisions at each of its nodes
+    if (c->tree_last != 2 || c->tree_F.empty()) return fail(c, POCS_E_STATE, "pocs_mc_get_waypoint_counts: the last call was not an MC call on the tree");
+    const int n = c->tree_depth[(size_t)c->tree_sel] + 1;
+    if (n > cap) return fail(c, POCS_E_BUFFER, "need %d counters", n);
+    for (int v = c->tree_sel, w = n - 1; v >= 0; v = c->tree_parent[(size_t)v], --w) out[w] = c->tree_F[(size_t)v];
+    return n;
+  }
   if (c->last_kind != 2 || c->mc_wp.empty() || (r + 1) * W > c->mc_wp.size())
     return fail(c, POCS_E_STATE, "pocs_mc_get_waypoint_counts: the last call was not an MC call under POCS_OPT_MC_WAYPOINT_COUNTS (or POCS_OPT_MC_RISK_BOUND with a bound)");
   int n = (int)W;                                    // the selected run's waypoints; a plan's own, or those before its stop
@@ -1717,6 +2131,7 @@ int pocs_mc_get_waypoint_counts(pocs_ctx* c, unsigned long long* out, int cap) {
 int pocs_gmm_begin(pocs_ctx* c) {
   if (!c) return POCS_E_ARG;
   if (c->nplans) return fail(c, POCS_E_STATE, "pocs_gmm_begin: plans are set (the step API serves a single plan)");
+  if (c->tree_n) return fail(c, POCS_E_STATE, "pocs_gmm_begin: a tree of plans is set (the step API serves a single plan)");
   HIPCHK(c, hipSetDevice(c->device));
   ra_drop(c);
   c->ra_internal = false;
@@ -1773,6 +2188,7 @@ int pocs_xchg_create(pocs_ctx* c, int world, int rank, void* handle64) {
     return fail(c, POCS_E_ARG, "exchange: world %d / rank %d outside 1..%d", world, rank, POCS_XCHG_MAX_WORLD);
   static_assert(sizeof(hipIpcMemHandle_t) == 64, "pocs.h promises a 64-byte handle");
   if (c->nplans) return fail(c, POCS_E_STATE, "pocs_xchg_create: plans are set (multi-GPU plan batches are not supported)");
+  if (c->tree_n) return fail(c, POCS_E_STATE, "pocs_xchg_create: a tree of plans is set (trees run on one GPU)");
   HIPCHK(c, hipSetDevice(c->device));
   if (!c->xchg_own) {
     // FINE-GRAINED device memory: other GPUs write into it and this GPU polls it inside a running kernel.
@@ -1792,6 +2208,7 @@ int pocs_xchg_create(pocs_ctx* c, int world, int rank, void* handle64) {
 int pocs_xchg_connect(pocs_ctx* c, const void* handles, int world) {
   if (!c || !handles) return POCS_E_ARG;
   if (c->nplans) return fail(c, POCS_E_STATE, "pocs_xchg_connect: plans are set (multi-GPU plan batches are not supported)");
+  if (c->tree_n) return fail(c, POCS_E_STATE, "pocs_xchg_connect: a tree of plans is set (trees run on one GPU)");
   if (!c->xchg_own || world != c->xchg_world) return fail(c, POCS_E_ORDER, "pocs_xchg_connect before pocs_xchg_create (or another world size)");
   HIPCHK(c, hipSetDevice(c->device));
   for (int q = 0; q < world; ++q) {
@@ -1880,6 +2297,7 @@ int pocs_gmm_end(pocs_ctx* c, double* probability) {
 int pocs_get_path_length(const pocs_ctx* c) {
   if (!c) return POCS_E_ARG;
   if (c->nplans) return c->plan_W[(size_t)(c->view < c->nplans ? c->view : 0)];     // the selected plan's
+  if (c->tree_n) return c->tree_depth[(size_t)c->tree_sel] + 1;                     // the path root -> the selected node
   return c->W;
 }
 
@@ -1912,6 +2330,25 @@ static int copy_out(pocs_ctx* c, void* dst, const void* src_dev, size_t bytes, s
 
 int pocs_get_gmm_state(pocs_ctx* c, int w, double* means3, double* covs9, double* weights, double* alive) {
   if (!c) return POCS_E_ARG;
+  if (c->tree_n) {                                   // the mixture of the selected node's ancestor of depth w
+    if (c->tree_last != 1 || !c->d_state.p) return fail(c, POCS_E_ARG, "no mixture for waypoint %d: the last call was not a GMM call on the tree", w);
+    const int depth = c->tree_depth[(size_t)c->tree_sel];
+    if (w < 0 || w > depth) return fail(c, POCS_E_ARG, "no mixture for waypoint %d: node %d has depth %d", w, c->tree_sel, depth);
+    int v = c->tree_sel;
+    for (int d = depth; d > w; --d) v = c->tree_parent[(size_t)v];
+    if (!c->tree_eval[(size_t)v]) return fail(c, POCS_E_ARG, "no mixture for waypoint %d: node %d lies below a node stopped by the risk bound", w, v);
+    HIPCHK(c, hipSetDevice(c->device));
+    std::vector<double> s((size_t)c->K * POCS_STATE_STRIDE);
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (int r = copy_out(c, s.data(), (double*)c->d_state.p + (size_t)c->tree_slot[(size_t)v] * s.size(), s.size() * sizeof(double), 1, 0)) return r;
+    for (int k = 0; k < c->K; ++k) {
+      if (means3) memcpy(means3 + 3 * k, &s[(size_t)k * POCS_STATE_STRIDE], 3 * sizeof(double));
+      if (covs9) memcpy(covs9 + 9 * k, &s[(size_t)k * POCS_STATE_STRIDE + 3], 9 * sizeof(double));
+      if (weights) weights[k] = s[(size_t)k * POCS_STATE_STRIDE + 12];
+      if (alive) alive[k] = s[(size_t)k * POCS_STATE_STRIDE + 13];
+    }
+    return c->K;
+  }
   if (w < 0 || w > c->last_gmm_wp || !c->d_state.p) return fail(c, POCS_E_ARG, "no mixture for waypoint %d", w);
   if (c->nplans && w >= pocs_get_path_length(c)) return fail(c, POCS_E_ARG, "no mixture for waypoint %d: plan %d has %d waypoints", w, c->view, pocs_get_path_length(c));
   if (c->nplans && (size_t)c->view < c->plan_E.size() && w >= c->plan_E[(size_t)c->view])
@@ -1933,13 +2370,24 @@ int pocs_get_gmm_state(pocs_ctx* c, int w, double* means3, double* covs9, double
 int pocs_get_host_chain(pocs_ctx* c, double* applied3, double* noisy3, double* z, double* mu3, double* cov9) {
   if (!c) return POCS_E_ARG;
   const int steps = pocs_get_path_length(c) - 1, L = c->sensor.L;
+  if (c->tree_n) {                                   // the chain of the path root -> the selected node, as a plan's
+    if (!c->tree_last) return fail(c, POCS_E_STATE, "no run yet");
+    const size_t W = (size_t)steps + 1, T = (size_t)c->tree_n;
+    std::vector<double> traj(3 * W), odom(3 * (W > 1 ? W - 1 : 1));
+    for (int v = c->tree_sel, w = steps; v >= 0; v = c->tree_parent[(size_t)v], --w)
+      for (size_t j = 0; j < 3; ++j) {
+        traj[j * W + (size_t)w] = c->tree_pose[j * T + (size_t)v];
+        if (w > 0) odom[j * (W - 1) + (size_t)w - 1] = c->tree_odom[j * T + (size_t)v];
+      }
+    compute_chain(c, seed_of_run(c, c->batch_base), PlanView{traj.data(), odom.data(), (int)W});
+  }
   if (c->nplans) {                                   // the selected plan's chain (h_chain holds slot 0's)
     if (c->h_chain.empty()) return fail(c, POCS_E_STATE, "no run yet");
     compute_chain(c, seed_of_run(c, c->batch_base + plan_run(c, c->view)), plan_view(c, c->view));
   }
   if (steps < 0 || c->h_chain.size() < (size_t)(steps > 0 ? steps : 1) * POCS_CHAIN_STRIDE)
     return fail(c, POCS_E_STATE, "no run yet");
-  if (c->view != 0 && !c->nplans) compute_chain(c, seed_of_run(c, c->batch_base + (uint64_t)c->view), plan_view(c, -1));   // h_chain holds run 0's
+  if (c->view != 0 && !c->nplans && !c->tree_n) compute_chain(c, seed_of_run(c, c->batch_base + (uint64_t)c->view), plan_view(c, -1));   // h_chain holds run 0's
   for (int i = 0; i < steps; ++i) {
     const double* rec = &c->h_chain[(size_t)i * POCS_CHAIN_STRIDE];
     if (applied3) memcpy(applied3 + 3 * i, rec, 3 * sizeof(double));
@@ -1979,6 +2427,7 @@ static long long copy_soa_as_aos(pocs_ctx* c, const DevBuf& bx, const DevBuf& by
 long long pocs_copy_gmm_samples(pocs_ctx* c, double* aos, int16_t* flags, long long cap) {
   if (!c) return POCS_E_ARG;
   const long long n = c->last_gmm_count;
+  if (c->tree_n) return fail(c, POCS_E_STATE, "no stored samples: a call on a tree of plans stores none");
   if (!c->opt_store || !c->d_sx.p || c->last_gmm_wp < 0) return fail(c, POCS_E_STATE, "no stored samples");
   if (cap < n) return fail(c, POCS_E_BUFFER, "need room for %lld samples", n);
   if (hipSetDevice(c->device) != hipSuccess || hipStreamSynchronize(c->stream) != hipSuccess)
@@ -1997,7 +2446,14 @@ long long pocs_copy_particles(pocs_ctx* c, double* aos, uint32_t* hits, long lon
   if (cap < n) return fail(c, POCS_E_BUFFER, "need room for %lld particles", n);
   if (hipSetDevice(c->device) != hipSuccess || hipStreamSynchronize(c->stream) != hipSuccess)
     return fail(c, POCS_E_DEVICE, "sync failed");
-  const size_t off = view_slot(c, 1) * (size_t)sample_stride_of(n);          // this run's slice
+  size_t off = view_slot(c, 1) * (size_t)sample_stride_of(n);                // this run's slice
+  if (c->tree_n) {                                   // a tree: the last two levels' clouds are still there; the deepest level's are served
+    const int D = (int)c->tree_level.size() - 2;
+    if (c->tree_last != 2) return fail(c, POCS_E_STATE, "no particles: the last call was not an MC call on the tree");
+    if (c->tree_depth[(size_t)c->tree_sel] != D)
+      return fail(c, POCS_E_STATE, "particles of node %d (depth %d) are gone: an MC call on a tree keeps the clouds of its deepest level (%d)", c->tree_sel, c->tree_depth[(size_t)c->tree_sel], D);
+    off = (size_t)(D & 1) * c->tree_mc_half + (size_t)(c->tree_slot[(size_t)c->tree_sel] - c->tree_level[(size_t)D]) * (size_t)sample_stride_of(n);
+  }
   if (aos && copy_soa_as_aos(c, c->d_px, c->d_py, c->d_pt, off, n, aos) < 0) return fail(c, POCS_E_DEVICE, "copy failed");
   if (hits && copy_out(c, hits, (const uint32_t*)c->d_hits.p + off, (size_t)n * sizeof(uint32_t), 1, 0) != POCS_OK)
     return fail(c, POCS_E_DEVICE, "copy failed");

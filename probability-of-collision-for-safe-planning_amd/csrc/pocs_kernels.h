@@ -123,7 +123,12 @@ struct pocs_gmm_launch {
   double* surv;                  // [nruns] the run's running survival product prod_{v <= w} (1 - p_v), kept by its closers (the closer
                                  // of waypoint 0 starts from 1.0: never read before it is written)
   double risk_bound;             // a run stops at the first waypoint w with 1 - surv >= risk_bound
+  // a tree of plans (pocs_set_plan_tree; behind everything else again).  Its launches work on the nodes of ONE level: a "run" is a
+  // node's slot, nruns the number of nodes, W = 1 (every [run][W] array holds one row per node), `waypoint` the level's depth.
+  const int* tree_parent;        // [nruns] the slot of every slot's parent (slot 0, the root: 0); null: not a tree launch
 };
+// a tree's stop words: 0 = live, depth + 1 = the node's own closer found the bound reached, this bit = below such a node
+#define POCS_TREE_STOP_INHERITED 0x80000000u
 #define POCS_SYNC_ABORT 1
 
 struct pocs_mc_launch {               // blockIdx.y = run of the batch, like pocs_gmm_launch
@@ -153,11 +158,20 @@ struct pocs_mc_launch {               // blockIdx.y = run of the batch, like poc
   unsigned* wp_stop;                   // [nruns] 0 = never stopped, s + 1 = stopped at waypoint s; written once, read by the host only
   long long wp_n;                      // mode 2: N, the particles of a run
   double wp_bound;                     // mode 2: a run stops at the first waypoint s with (double)C[s] / (double)N >= wp_bound
+  // a tree of plans (k_mc_tree_step; behind everything else again): the launch's nodes are slots tree_lo .. tree_lo + nruns of one
+  // level; x / y / th / hits above are that level's half of the particle buffers (node r at (r - tree_dst_lo) * stride), tree_s* the
+  // previous level's (the parent at (tree_parent[r] - tree_src_lo) * stride); chain, wp_counts and total hold one entry per slot
+  const int* tree_parent;
+  const double* tree_sx; const double* tree_sy; const double* tree_sth;
+  const uint32_t* tree_shits;
+  int tree_lo, tree_dst_lo, tree_src_lo, tree_pad;   // the launch's first slot, its level's, the previous level's
 };
 
 
 hipError_t pocs_launch_gmm_step(int K, const pocs_gmm_launch& a, hipStream_t s);              // grid = a.blocks
 hipError_t pocs_launch_gmm_advance(int K, const pocs_gmm_launch& a, hipStream_t s);
+hipError_t pocs_launch_gmm_tree_advance(int K, const pocs_gmm_launch& a, hipStream_t s);    // grid = a.run_cnt: the nodes of one level
+hipError_t pocs_launch_gmm_tree_step(int K, const pocs_gmm_launch& a, hipStream_t s);       // grid = a.blocks
 hipError_t pocs_launch_gmm_close(int K, const pocs_gmm_launch& a, hipStream_t s);             // lone call: the last waypoint's rows -> moments
 hipError_t pocs_launch_gmm_exchange(int K, const pocs_gmm_launch& a, const pocs_xchg_dev& x, hipStream_t s);   // grid = a.nruns
 hipError_t pocs_launch_copy(const void* src, void* dst, long long bytes, hipStream_t s);
@@ -167,3 +181,4 @@ hipError_t pocs_launch_mc_init(int nblk, const pocs_mc_launch& a, hipStream_t s)
 hipError_t pocs_launch_mc_step(int nblk, const pocs_mc_launch& a, hipStream_t s);
 hipError_t pocs_launch_mc_fused(int nblk, const pocs_mc_launch& a, hipStream_t s);
 hipError_t pocs_launch_mc_count(int nblk, const pocs_mc_launch& a, hipStream_t s);
+hipError_t pocs_launch_mc_tree_step(int nblk, const pocs_mc_launch& a, hipStream_t s);

@@ -260,6 +260,10 @@ struct adv_ptrs {
   const double *g_prev, *g_mom, *g_ch, *g_sen;
   int ss, ps, NC;
 };
+// TREE (a tree of plans, pocs_set_plan_tree): the rows are one per NODE -- state / param / moments [slot], chain [slot] = the
+// record of the edge into the node -- and the predecessor of slot r is its PARENT's row, not "the same run, one waypoint
+// earlier"; w is the node's depth: it keys the random draws and tells the root (w = 0) from the rest, and addresses nothing.
+template <bool TREE = false>
 __device__ __forceinline__ adv_ptrs advance_ptrs(const pocs_gmm_launch& a, int K, int w, int r, double* scratch) {
   adv_ptrs p;
   constexpr int SEN = (int)(sizeof(pocs_sensor) / sizeof(double));
@@ -270,6 +274,16 @@ __device__ __forceinline__ adv_ptrs advance_ptrs(const pocs_gmm_launch& a, int K
   p.l_sen = p.l_ch + POCS_CHAIN_STRIDE;
   p.l_next = p.l_sen + SEN;
   p.l_par = p.l_next + p.ss;
+  if (TREE) {
+    const int pr = w > 0 ? a.tree_parent[r] : r;     // (the root's initial mixture lies in its own row, as a run's in state[r][0])
+    p.g_state = a.state + (size_t)r * p.ss;
+    p.g_param = a.param + (size_t)r * p.ps;
+    p.g_prev = a.state + (size_t)pr * p.ss;
+    p.g_mom = a.moments + (size_t)pr * p.NC;
+    p.g_ch = a.chain + (size_t)r * POCS_CHAIN_STRIDE;
+    p.g_sen = reinterpret_cast<const double*>(a.sensor);
+    return p;
+  }
   // run r of the batch: state/param [r][W][..], moments [W][R][..] (one all-reduce per waypoint
   // covers every run), chain [r][W-1][..]
   p.g_state = a.state + (size_t)r * a.W * p.ss;
@@ -343,9 +357,10 @@ __device__ __forceinline__ void advance_commit(const adv_ptrs& p, const bool loa
     else if (i < n) p.l_mom[i - ss - POCS_CHAIN_STRIDE - SEN] = v[u];
   }
 }
+template <bool TREE = false>
 __device__ __forceinline__ void advance_stage(const pocs_gmm_launch& a, int K, int w, int r, double* scratch,
                                               bool mom_in_lds, int tid, int nthreads) {
-  const adv_ptrs p = advance_ptrs(a, K, w, r, scratch);
+  const adv_ptrs p = advance_ptrs<TREE>(a, K, w, r, scratch);
   const bool load_mom = w > 0 && !mom_in_lds;
   // index space: [0, ss) state | [ss, ss + CH + SEN) chain record, sensor | then (only if wanted) the moments;
   // l_mom is NOT touched when the caller has put the moments there
@@ -361,8 +376,9 @@ __device__ __forceinline__ void advance_stage(const pocs_gmm_launch& a, int K, i
 #define POCS_ADV_STAGE_MAX (POCS_MAX_GAUSSIANS * (POCS_STATE_STRIDE + POCS_NMOM) + POCS_CHAIN_STRIDE + (int)(sizeof(pocs_sensor) / sizeof(double)))
 
 // one wave, after advance_stage (+ barrier): one component per lane
+template <bool TREE = false>
 __device__ __forceinline__ void advance_components(const pocs_gmm_launch& a, int K, int w, int r, int lane, double* scratch) {
-  const adv_ptrs p = advance_ptrs(a, K, w, r, scratch);
+  const adv_ptrs p = advance_ptrs<TREE>(a, K, w, r, scratch);
   if (lane < K)
     pocs_gmm_advance_component(lane, p.l_prev, (w == 0) ? nullptr : p.l_mom, p.l_ch, p.l_ch + 3, p.l_ch + POCS_CHAIN_Z,
                                reinterpret_cast<const pocs_sensor*>(p.l_sen), p.l_next, p.l_par);
@@ -370,8 +386,9 @@ __device__ __forceinline__ void advance_components(const pocs_gmm_launch& a, int
 
 // one lane of ANOTHER wave, meanwhile: the component counts of waypoint w on the premise -- checked by
 // advance_finish -- that no Cholesky factorisation fails.  spec = K cumulative counts, K alive flags assumed.
+template <bool TREE = false>
 __device__ __forceinline__ void speculate_counts(const pocs_gmm_launch& a, int K, int w, int r, double* scratch, double* spec) {
-  const adv_ptrs p = advance_ptrs(a, K, w, r, scratch);
+  const adv_ptrs p = advance_ptrs<TREE>(a, K, w, r, scratch);
   double* st = spec + 2 * K;                                   // a K x STATE_STRIDE image: only [12], [13] matter
   for (int k = 0; k < K; ++k) {
     const double alive_prev = p.l_prev[k * POCS_STATE_STRIDE + 13];
@@ -387,9 +404,10 @@ __device__ __forceinline__ void speculate_counts(const pocs_gmm_launch& a, int K
 
 // the wave of advance_components, after it (+ barrier): weights, component counts (the speculated ones
 // if there are any and their premise held), write-through stores of state[w] / param[w].
+template <bool TREE = false>
 __device__ __forceinline__ void advance_finish(const pocs_gmm_launch& a, int K, int w, int r, int lane, double* scratch,
                                                const double* spec, const bool publish = true) {
-  const adv_ptrs p = advance_ptrs(a, K, w, r, scratch);
+  const adv_ptrs p = advance_ptrs<TREE>(a, K, w, r, scratch);
   if (lane == 0) {
     bool use_spec = spec != nullptr;
     if (use_spec) for (int k = 0; k < K; ++k) use_spec = use_spec && (p.l_next[k * POCS_STATE_STRIDE + 13] == spec[K + k]);
@@ -403,8 +421,9 @@ __device__ __forceinline__ void advance_finish(const pocs_gmm_launch& a, int K, 
   __threadfence_block();
   __builtin_amdgcn_wave_barrier();
   if (!publish) return;                              // (lone call: one block of the launch writes the records out)
-  for (int j = lane; j < p.ss; j += 64) store_wt(&p.g_state[(size_t)w * p.ss + j], p.l_next[j]);
-  for (int j = lane; j < p.ps; j += 64) store_wt(&p.g_param[(size_t)w * p.ps + j], p.l_par[j]);
+  const size_t row = TREE ? 0 : (size_t)w;           // (a tree: g_state / g_param are the node's own row)
+  for (int j = lane; j < p.ss; j += 64) store_wt(&p.g_state[row * p.ss + j], p.l_next[j]);
+  for (int j = lane; j < p.ps; j += 64) store_wt(&p.g_param[row * p.ps + j], p.l_par[j]);
   // (not drained: nothing inside this launch reads the records -- state[w] / param[w] are for the NEXT waypoint's launch, behind
   // the kernel boundary; waiting for the write-through stores here kept every closer 1.2 us longer in the launch's tail)
 }
@@ -419,23 +438,23 @@ struct advance_no_side_job { __device__ __forceinline__ void operator()() const 
 // `post_job`: run by wave 1 (64 <= tid < 128; its lane 0 has drawn the counts by then) beside advance_finish, with nothing in it
 // that the normalisation still changes -- means and Cholesky factors of param[w] are final once the components are through
 // (the lone form's heads cull the obstacle table there)
-template <typename SideJob = advance_no_side_job, typename PostJob = advance_no_side_job>
+template <bool TREE = false, typename SideJob = advance_no_side_job, typename PostJob = advance_no_side_job>
 __device__ __forceinline__ void advance_block(const pocs_gmm_launch& a, int K, int w, int r, double* adv, double* spec,
                                               bool mom_in_lds, int tid, int nthreads, const bool staged = false,
                                               const bool publish = true, SideJob side_job = SideJob(), PostJob post_job = PostJob()) {
   POCS_ADV_STAMP_BEGIN();
   if (!staged) {
-    advance_stage(a, K, w, r, adv, mom_in_lds, tid, nthreads);
+    advance_stage<TREE>(a, K, w, r, adv, mom_in_lds, tid, nthreads);
     __syncthreads();
   }
   POCS_ADV_STAMP(8);
-  if (tid < 64) advance_components(a, K, w, r, tid, adv);
-  else if (tid == 64 && w > 0) speculate_counts(a, K, w, r, adv, spec);
+  if (tid < 64) advance_components<TREE>(a, K, w, r, tid, adv);
+  else if (tid == 64 && w > 0) speculate_counts<TREE>(a, K, w, r, adv, spec);
   else if (tid >= 128) side_job();
   POCS_ADV_STAMP(9);
   __syncthreads();
   POCS_ADV_STAMP(10);
-  if (tid < 64) advance_finish(a, K, w, r, tid, adv, w > 0 ? spec : nullptr, publish);
+  if (tid < 64) advance_finish<TREE>(a, K, w, r, tid, adv, w > 0 ? spec : nullptr, publish);
   else if (tid < 128) post_job();
   POCS_ADV_STAMP(11);
 }
@@ -443,6 +462,29 @@ __global__ __launch_bounds__(128) void k_gmm_advance(pocs_gmm_launch a, int K) {
   __shared__ double s_adv[POCS_ADV_SCRATCH(POCS_MAX_GAUSSIANS)];
   __shared__ double s_spec[POCS_SPEC_SCRATCH(POCS_MAX_GAUSSIANS)];
   advance_block(a, K, a.waypoint, blockIdx.x, s_adv, s_spec, false, threadIdx.x, 128);      // one block per run
+}
+// A tree of plans, level d = a.waypoint: one block per node of the level (slots run_lo .. run_lo + run_cnt), the mixture of
+// the node from its PARENT's state and reduced moments and its own chain record -- the arithmetic of k_gmm_advance in the same
+// order.  RISK (pocs_set_plan_risk_bound): a node whose parent has stopped -- at the bound itself, or below a node that has --
+// inherits the stop (its word gets the inherited mark, no mixture is built, and the heads of the level's sampling launch
+// return on it as they do on a plan's stop); a live parent hands its running survival product down, so that the node's
+// closer starts from it exactly as a plan's closer of waypoint d starts from waypoint d - 1's.  stop / surv of the parent
+// were written by the launches of level d - 1, behind a kernel boundary on the same stream.
+template <bool RISK>
+__global__ __launch_bounds__(128) void k_gmm_tree_advance(pocs_gmm_launch a, int K) {
+  __shared__ double s_adv[POCS_ADV_SCRATCH(POCS_MAX_GAUSSIANS)];
+  __shared__ double s_spec[POCS_SPEC_SCRATCH(POCS_MAX_GAUSSIANS)];
+  const int r = a.run_lo + (int)blockIdx.x, w = a.waypoint;
+  if (RISK && w > 0) {
+    const int pr = a.tree_parent[r];
+    const unsigned sp = __hip_atomic_load(&a.stop[pr], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (__builtin_amdgcn_readfirstlane((int)sp) != 0) {
+      if (threadIdx.x == 0) __hip_atomic_store(&a.stop[r], sp | POCS_TREE_STOP_INHERITED, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      return;
+    }
+    if (threadIdx.x == 0) store_wt(&a.surv[r], load_wt(&a.surv[pr]));
+  }
+  advance_block<true>(a, K, w, r, s_adv, s_spec, false, threadIdx.x, 128);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1059,10 +1101,18 @@ __device__ __forceinline__ void gmm_close_sums(const pocs_gmm_launch& a, const i
 // No fence of its own: stop[r] and surv[r] are written by a closer of waypoint w's launch and read by waypoint w + 1's launch
 // of the SAME sub-batch -- a run never changes sub-batch (plan_layout) --, i.e. behind a kernel boundary on one stream, as
 // state / param[w + 1] are; write-through stores and L1-bypassing loads like those.
-template <int K, bool STORE, int TB, bool LONE, bool RISK>
+//
+// TREE (a tree of plans, pocs_set_plan_tree; the kernel k_gmm_step_tree, ticket form, never LONE, nothing stored): the launch's
+// "runs" are nodes of ONE level of the tree.  a.waypoint is the level's depth and keys the random draws, as a plan's waypoint
+// does; the rows a node owns -- param, ticket, moments, and under RISK its stop word and survival product -- are addressed by
+// its slot alone (the host lays them out [slot], i.e. W = 1, row 0).  The mixtures were built by k_gmm_tree_advance, which
+// under RISK has also handed the parent's stop and survival product down: the heads and closers below do what they do for
+// waypoint `depth` of a plan.
+template <int K, bool STORE, int TB, bool LONE, bool RISK, bool TREE = false>
 __device__ __forceinline__ void gmm_step_block(const pocs_gmm_launch a) {      // (by value, as a kernel holds its argument)
   typedef gmm_smem<K, TB> smem_t;
   static_assert(!(LONE && RISK), "the lone form closes in its heads: a call under a risk bound takes the ticket form");
+  static_assert(!(TREE && (LONE || STORE)), "a tree's levels take the ticket form and store no samples");
   constexpr int SUB = smem_t::SUB, NW = smem_t::NW;
   // (the block's LDS, declared here and not handed in by the kernel: every instantiation is inlined into exactly one kernel,
   // and the accesses stay LDS accesses from the front end on)
@@ -1072,6 +1122,7 @@ __device__ __forceinline__ void gmm_step_block(const pocs_gmm_launch a) {      /
   int npre = 0;
   const int tid = threadIdx.x;
   const int w = a.waypoint;
+  const int wr = TREE ? 0 : w;                       // the row of (run, waypoint) in the run's [W] arrays; a tree: one row per node
   const int t_lo = a.run_lo << a.vs_shift, t_hi = (a.run_lo + a.run_cnt) << a.vs_shift;    // this launch's units
   const int bx = (int)blockIdx.x;
   const int t0_all = t_lo + bx * a.upb;
@@ -1145,7 +1196,7 @@ __device__ __forceinline__ void gmm_step_block(const pocs_gmm_launch a) {      /
   } else {
     // param[r][w][..]: the two runs' records are a.W records apart
     const int rp = tid / PS, jp = tid - rp * PS;
-    const double parv = tid < (r1 - r0 + 1) * PS ? load_wt(&a.param[((size_t)(r0 + rp) * a.W + w) * PS + jp]) : 0.0;
+    const double parv = tid < (r1 - r0 + 1) * PS ? load_wt(&a.param[((size_t)(r0 + rp) * a.W + wr) * PS + jp]) : 0.0;
     const unsigned long long seedv = tid <= r1 - r0 ? a.hdr[r0 + tid].seed : 0ull;
     if constexpr (RISK) {
       // the stop words of the block's runs, every lane the same two addresses, in flight with everything above (a stopped run's
@@ -1200,7 +1251,7 @@ __device__ __forceinline__ void gmm_step_block(const pocs_gmm_launch a) {      /
     const int r = r0 + tid;
     const int b_first = ((r << a.vs_shift) - t_lo) / a.upb, b_last_raw = ((((r + 1) << a.vs_shift) - 1) - t_lo) / a.upb;
     const int b_last = b_last_raw < (int)gridDim.x - 1 ? b_last_raw : (int)gridDim.x - 1;
-    const unsigned t = __hip_atomic_fetch_add(&a.ticket[(size_t)r * a.W + w], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    const unsigned t = __hip_atomic_fetch_add(&a.ticket[(size_t)r * a.W + wr], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     sm.last[tid] = (t == (unsigned)(b_last - b_first)) ? 1 : 0;
   }
   if (tid == 0 && r1 == r0) sm.last[1] = 0;
@@ -1229,7 +1280,7 @@ __device__ __forceinline__ void gmm_step_block(const pocs_gmm_launch a) {      /
     if constexpr (RISK) if (tid == 0 && w > 0) survv = load_wt(&a.surv[r]);
     requests_issued();
     if (adv) advance_commit(ap, false, tid, TB, advv);
-    gmm_close_sums<K, TB, true>(a, w, r, sm.par[rb], sm.stage(), l_mom, tid, a.partial, true, cr);
+    gmm_close_sums<K, TB, true>(a, wr, r, sm.par[rb], sm.stage(), l_mom, tid, a.partial, true, cr);
     POCS_STAMP(5);
     if constexpr (RISK) {
       // p_w and the running probability as gmm_combine (pocs_host.hip) forms them from the same moments: the counts added in
@@ -1285,6 +1336,12 @@ __global__ __launch_bounds__(TB, (LONE ? 1 : POCS_GMM_BLOCKS_PER_CU) * TB / 256)
 template <int K, bool STORE, int TB>
 __global__ __launch_bounds__(TB, POCS_GMM_BLOCKS_PER_CU * TB / 256) void k_gmm_step_risk(pocs_gmm_launch a) {
   gmm_step_block<K, STORE, TB, false, true>(a);
+}
+
+// One level of a tree of plans (TREE above), with or without the risk bound.
+template <int K, int TB, bool RISK>
+__global__ __launch_bounds__(TB, POCS_GMM_BLOCKS_PER_CU * TB / 256) void k_gmm_step_tree(pocs_gmm_launch a) {
+  gmm_step_block<K, false, TB, false, RISK, true>(a);
 }
 
 // Lone call, behind the last waypoint's launch: its rows -> moments[W-1] (one block).
@@ -1525,6 +1582,57 @@ __device__ __forceinline__ void mc_fused_body(const pocs_mc_launch& a) {
 __global__ __launch_bounds__(POCS_BLOCK) void k_mc_fused(pocs_mc_launch a) { mc_fused_body<MC_PLAIN>(a); }
 __global__ __launch_bounds__(POCS_BLOCK) void k_mc_fused_counts(pocs_mc_launch a) { mc_fused_body<MC_COUNTS>(a); }
 
+// A tree of plans (pocs_set_plan_tree), one launch per level (at most 256 nodes per launch): blockIdx.y = node of the launch,
+// slot r = tree_lo + blockIdx.y.  The node's particles are its PARENT's, moved by the noisy control of the edge into the node
+// (chain[r], one record per node) -- mc_step_body's arithmetic -- read from the parent's place in the previous level's half of
+// the particle buffers and written to the node's place in this level's half: source != destination, two levels live at a
+// time.  Counted per node: the particles whose FIRST collision on the path root -> node is at the node (wp_counts[r]) and
+// those that have collided at or before it (total[r]); integer atomics, exact whatever the grid.
+template <bool NT>
+__global__ __launch_bounds__(POCS_BLOCK) void k_mc_tree_step(pocs_mc_launch a) {
+  __shared__ double s_obs[POCS_MAX_OBSTACLES * POCS_OBS_STRIDE];
+  __shared__ pocs_footprint s_fp;
+  __shared__ int s_M;
+  __shared__ pocs_tables s_tab;
+  stage_mc_head(a.env, a.tables, s_obs, &s_fp, &s_M, &s_tab);
+  __syncthreads();
+  const int r = a.tree_lo + (int)blockIdx.y, pr = a.tree_parent[r];
+  const size_t so = (size_t)(pr - a.tree_src_lo) * (size_t)a.stride, dso = (size_t)(r - a.tree_dst_lo) * (size_t)a.stride;
+  const double* sx = a.tree_sx + so; const double* sy = a.tree_sy + so; const double* st = a.tree_sth + so;
+  const uint32_t* sh = a.tree_shits + so;
+  double* dx = a.x + dso; double* dy = a.y + dso; double* dt = a.th + dso;
+  uint32_t* dh = a.hits + dso;
+  const pocs_footprint fp = s_fp;
+  const int M = s_M;
+  const double* u = a.chain + (size_t)r * POCS_CHAIN_STRIDE + 6;
+  const double u0 = u[0], u1 = u[1], u2 = u[2];
+  unsigned first = 0, coll = 0;
+  const long long stride = (long long)gridDim.x * POCS_BLOCK;
+  for (long long i = (long long)blockIdx.x * POCS_BLOCK + threadIdx.x; i < a.count; i += stride) {
+    const double x = NT ? __builtin_nontemporal_load(sx + i) : sx[i];
+    const double y = NT ? __builtin_nontemporal_load(sy + i) : sy[i];
+    const double t = NT ? __builtin_nontemporal_load(st + i) : st[i];
+    const uint32_t old = NT ? __builtin_nontemporal_load(sh + i) : sh[i];
+    double sn, cs;
+    pocs_sincos(t + u0, &sn, &cs);
+    const double nx = fma(u1, cs, x);
+    const double ny = fma(u1, sn, y);
+    const double nt = pocs_wrap_angle(t + u0 + u2);
+    const uint32_t h = old + (pocs_pose_collides(nx, ny, nt, &fp, s_obs, M, &s_tab) ? 1u : 0u);
+    if (NT) {
+      __builtin_nontemporal_store(nx, dx + i); __builtin_nontemporal_store(ny, dy + i); __builtin_nontemporal_store(nt, dt + i);
+      __builtin_nontemporal_store(h, dh + i);
+    } else {
+      dx[i] = nx; dy[i] = ny; dt[i] = nt; dh[i] = h;
+    }
+    first += (old == 0u && h != 0u) ? 1u : 0u;
+    coll += h != 0u ? 1u : 0u;
+  }
+  mc_add_first_hits(first, a.wp_counts + r);
+  __syncthreads();                                   // (mc_add_first_hits' scratch is read by thread 0 of the call above)
+  mc_add_first_hits(coll, a.total + r);
+}
+
 __global__ __launch_bounds__(POCS_BLOCK) void k_mc_count(pocs_mc_launch a) {
   __shared__ unsigned s_w[POCS_BLOCK / 64];
   const mc_run_view v = mc_view(a);
@@ -1559,6 +1667,13 @@ hipError_t launch_gmm_k(const pocs_gmm_launch& a, hipStream_t s) {
   return hipGetLastError();
 }
 template <int K>
+hipError_t launch_gmm_tree_k(const pocs_gmm_launch& a, hipStream_t s) {
+  constexpr int TB = POCS_GMM_BLOCK_OF(K);
+  if (a.risk) hipLaunchKernelGGL((k_gmm_step_tree<K, TB, true>), dim3(a.blocks), dim3(TB), 0, s, a);
+  else        hipLaunchKernelGGL((k_gmm_step_tree<K, TB, false>), dim3(a.blocks), dim3(TB), 0, s, a);
+  return hipGetLastError();
+}
+template <int K>
 hipError_t launch_gmm_close_k(const pocs_gmm_launch& a, hipStream_t s) {
   hipLaunchKernelGGL((k_gmm_close<K>), dim3(1), dim3(256), 0, s, a);
   return hipGetLastError();
@@ -1583,6 +1698,45 @@ hipError_t pocs_launch_gmm_close(int K, const pocs_gmm_launch& a, hipStream_t s)
     case 8: return launch_gmm_close_k<8>(a, s);
     default: return hipErrorInvalidValue;
   }
+}
+
+// One level of a tree of plans: the sampling launch over nodes [run_lo, run_lo + run_cnt) of depth a.waypoint.  The rows are
+// one per node: the launch must address them with W = 1 (TREE, gmm_step_block), and nothing may ask its closers for more than
+// the node's sums (no advance, no exchange, no stored samples).
+hipError_t pocs_launch_gmm_tree_step(int K, const pocs_gmm_launch& a, hipStream_t s) {
+  if (a.W != 1 || !a.tree_parent || a.lone || a.store || a.advance_in_tail || a.exchange_in_tail || a.run_cnt < 1 || a.run_cnt > 256 ||
+      a.run_lo < 0 || a.run_lo + a.run_cnt > a.nruns || (a.risk && (!a.stop || !a.surv)))
+    return hipErrorInvalidValue;
+  switch (K) {
+    case 1: return launch_gmm_tree_k<1>(a, s);
+    case 2: return launch_gmm_tree_k<2>(a, s);
+    case 3: return launch_gmm_tree_k<3>(a, s);
+    case 4: return launch_gmm_tree_k<4>(a, s);
+    case 5: return launch_gmm_tree_k<5>(a, s);
+    case 6: return launch_gmm_tree_k<6>(a, s);
+    case 7: return launch_gmm_tree_k<7>(a, s);
+    case 8: return launch_gmm_tree_k<8>(a, s);
+    default: return hipErrorInvalidValue;
+  }
+}
+// ... and the launch that builds the level's mixtures ahead of it: one block per node, grid = a.run_cnt.
+hipError_t pocs_launch_gmm_tree_advance(int K, const pocs_gmm_launch& a, hipStream_t s) {
+  if (a.W != 1 || !a.tree_parent || a.run_cnt < 1 || a.run_lo < 0 || a.run_lo + a.run_cnt > a.nruns || (a.risk && (!a.stop || !a.surv)) ||
+      K < 1 || K > POCS_MAX_GAUSSIANS)
+    return hipErrorInvalidValue;
+  if (a.risk) hipLaunchKernelGGL(k_gmm_tree_advance<true>, dim3(a.run_cnt), dim3(128), 0, s, a, K);
+  else        hipLaunchKernelGGL(k_gmm_tree_advance<false>, dim3(a.run_cnt), dim3(128), 0, s, a, K);
+  return hipGetLastError();
+}
+// One level of a tree of plans on the MC path: grid (nblk, a.nruns), a.nruns = the launch's nodes, slots tree_lo ...
+hipError_t pocs_launch_mc_tree_step(int nblk, const pocs_mc_launch& a, hipStream_t s) {
+  if (!a.tree_parent || !a.tree_sx || !a.tree_sy || !a.tree_sth || !a.tree_shits || !a.wp_counts || !a.total || a.nruns < 1 || a.nruns > 256 ||
+      a.tree_dst_lo < 1 || a.tree_lo < a.tree_dst_lo || a.tree_src_lo < 0 || a.tree_src_lo >= a.tree_dst_lo || a.tree_sx == a.x)
+    return hipErrorInvalidValue;
+  const dim3 grid(nblk, a.nruns), block(POCS_BLOCK);
+  if (a.nontemporal) hipLaunchKernelGGL(k_mc_tree_step<true>, grid, block, 0, s, a);
+  else               hipLaunchKernelGGL(k_mc_tree_step<false>, grid, block, 0, s, a);
+  return hipGetLastError();
 }
 
 hipError_t pocs_launch_gmm_step(int K, const pocs_gmm_launch& a, hipStream_t s) {

@@ -91,3 +91,73 @@ def resample_plan(plan, W):
         else:
             out[j] = t0[0]
     return dict(traj=out, odom=path_odometry(out))
+
+
+MAX_TREE_NODES = 4096
+
+
+def check_tree(parent, poses, odoms):
+    """A tree of plans as pocs_set_plan_tree takes it -> (parent int32[T], poses float64 T x 3, odoms float64 T x 3), or
+    ValueError: one root (parent[0] = -1), every other node after its parent (0 <= parent[n] < n), 1 <= T <= 4096."""
+    parent = np.ascontiguousarray(parent, dtype=np.int32)
+    poses = np.ascontiguousarray(poses, dtype=np.float64)
+    odoms = np.ascontiguousarray(odoms, dtype=np.float64)
+    T = len(parent)
+    if parent.ndim != 1 or not 1 <= T <= MAX_TREE_NODES:
+        raise ValueError("a tree has between 1 and %d nodes, got %s" % (MAX_TREE_NODES, parent.shape))
+    if poses.shape != (T, 3) or odoms.shape != (T, 3):
+        raise ValueError("poses and odoms are T x 3 with T = %d, got %s and %s" % (T, poses.shape, odoms.shape))
+    if parent[0] != -1:
+        raise ValueError("node 0 is the root: parent[0] must be -1, got %d" % parent[0])
+    for n in range(1, T):
+        if not 0 <= parent[n] < n:
+            raise ValueError("parent[%d] = %d: one root, and every other node comes after its parent" % (n, parent[n]))
+    return parent, poses, odoms
+
+
+def tree_from_plans(plans):
+    """Merges the common prefixes of plans ({"traj": W x 3, "odom": (W-1) x 3} each) that start at the same pose into a
+    tree -> (parent, poses, odoms, leaf_of_plan): node arrays as Context.set_plan_tree takes them (nodes in the order the
+    plans first reach them, so parent[n] < n) and, per plan, the node its last waypoint became.  Two plans share a node only
+    where every pose and every control up to it is equal as float64 BITS (0.0 and -0.0 differ, a NaN equals itself)."""
+    plans = list(plans)
+    if not plans:
+        raise ValueError("no plans")
+    parent, poses, odoms, leaf = [], [], [], []
+    child = {}                                   # (parent node, bits of the control and the pose) -> node
+    for i, pl in enumerate(plans):
+        t = np.ascontiguousarray(pl["traj"], dtype=np.float64)
+        o = np.ascontiguousarray(pl["odom"], dtype=np.float64).reshape(-1, 3)
+        if t.ndim != 2 or t.shape[1] != 3 or t.shape[0] < 1 or o.shape != (t.shape[0] - 1, 3):
+            raise ValueError("plan %d: trajectory %s / odometry %s, W x 3 and (W - 1) x 3 expected" % (i, t.shape, o.shape))
+        at = -1
+        for w in range(t.shape[0]):
+            key = (at, o[w - 1].tobytes() if w else b"", t[w].tobytes())
+            n = child.get(key)
+            if n is None:
+                if w == 0 and parent:
+                    raise ValueError("plan %d starts at another pose than plan 0: a tree has one root" % i)
+                n = len(parent)
+                if n >= MAX_TREE_NODES:
+                    raise ValueError("the plans make a tree of more than %d nodes" % MAX_TREE_NODES)
+                child[key] = n
+                parent.append(at)
+                poses.append(t[w].copy())
+                odoms.append(o[w - 1].copy() if w else np.zeros(3))
+            at = n
+        leaf.append(at)
+    return (np.array(parent, dtype=np.int32), np.array(poses, dtype=np.float64).reshape(-1, 3),
+            np.array(odoms, dtype=np.float64).reshape(-1, 3), np.array(leaf, dtype=np.int32))
+
+
+def tree_path(parent, poses, odoms, n):
+    """The path root -> n of a tree as a plan dict(traj: W x 3, odom: (W-1) x 3), W = depth(n) + 1."""
+    parent, poses, odoms = check_tree(parent, poses, odoms)
+    if not 0 <= n < len(parent):
+        raise ValueError("node %d outside the tree (0..%d)" % (n, len(parent) - 1))
+    path = []
+    while n >= 0:
+        path.append(n)
+        n = int(parent[n])
+    path.reverse()
+    return dict(traj=poses[path].copy(), odom=odoms[path[1:]].copy().reshape(-1, 3))
