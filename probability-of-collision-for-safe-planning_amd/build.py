@@ -7,8 +7,6 @@ from pathlib import Path
 PKG = Path(__file__).resolve().parent
 CSRC = PKG / "csrc"
 LIB = PKG / "libpocs.so"
-SOURCES = ["pocs_kernels.hip", "pocs_host.hip"]
-HEADERS = ["pocs_math.h", "pocs_model.h", "pocs_collide.h", "pocs_kernels.h", "pocs_command.hpp", "../../include/pocs.h"]
 FLAGS = ["-O3", "--offload-arch=gfx950", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off",
          "-Wall", "-Wno-unused-function", "-Wno-unused-value"]
 
@@ -20,11 +18,17 @@ def hipcc():
     return exe
 
 
+def sources():
+    """Every csrc/*.hip is a unit of the library (sorted: the command line, and so the build, is the same everywhere)."""
+    return sorted(CSRC.glob("*.hip"))
+
+
 def stale():
     if not LIB.exists():
         return True
     t = LIB.stat().st_mtime
-    return any((CSRC / f).stat().st_mtime > t for f in SOURCES + HEADERS)
+    deps = [f for f in CSRC.iterdir() if f.is_file()] + [PKG.parent / "include" / "pocs.h"]
+    return any(f.stat().st_mtime > t for f in deps)
 
 
 def build_library(force=False, verbose=False):
@@ -39,7 +43,7 @@ def build_library(force=False, verbose=False):
         if not force and not stale():                # another process built it while this one waited
             return LIB
         tmp = PKG / (".libpocs.%d.so" % os.getpid())
-        cmd = [hipcc()] + FLAGS + [str(CSRC / s) for s in SOURCES] + ["-o", str(tmp)]
+        cmd = [hipcc()] + FLAGS + [str(s) for s in sources()] + ["-o", str(tmp)]
         r = subprocess.run(cmd, capture_output=True, text=True)
         if verbose or r.returncode:
             print(" ".join(cmd))

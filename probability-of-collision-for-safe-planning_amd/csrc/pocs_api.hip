@@ -1,0 +1,711 @@
+// pocs_api.hip -- the C ABI's front (include/pocs.h): context life cycle, the typed setters and getters, the run* calls with
+// their run-ahead, and the MCModule-compatible text dispatcher (mirrors MCModule, mcsimplugin/mcsimplugin.cpp:7-232).
+// Without a HIP device pocs_create fails: there is no CPU path.
+#include <new>
+
+#include "pocs_ctx.hpp"
+#include "pocs_command.hpp"
+
+#define POCS_VERSION_STRING "pocs-mi355x 0.4 (gfx950; numerics v9: summation tree of 512-pair chunks, 256 virtual slices)"
+
+using namespace pocs_rt;
+
+// ---- text dispatcher: replies and the help text ----
+static int put(pocs_ctx* c, char* out, size_t cap, const char* text) {
+  if (!out || cap == 0) return POCS_OK;
+  const size_t n = strlen(text);
+  if (n + 1 > cap) { out[0] = 0; return fail(c, POCS_E_BUFFER, "reply needs %zu bytes", n + 1); }
+  memcpy(out, text, n + 1);
+  return POCS_OK;
+}
+
+static const char* kHelp =
+    "MyCommand        This is an example command\n"
+    "ArmaCommand      kept for compatibility (no-op)\n"
+    "setAlphas        a1 a2 a3 a4: squared odometry noise coefficients\n"
+    "setQ             q: variance of the range sensor noise\n"
+    "setNumLandmarks  n\n"
+    "setLandmarks     x_0..x_{n-1} y_0..y_{n-1}\n"
+    "setNumParticles  n: particles of the MC simulation\n"
+    "setInitialCovariance  c00 c01 c02 c10 .. c22 (row major)\n"
+    "setPathLength    W\n"
+    "setTrajectory    x_0..x_{W-1} y_0..y_{W-1} theta_0..theta_{W-1}\n"
+    "setOdometry      r1_0.. tr_0.. r2_0.. (W-1 each)\n"
+    "runSimulation    run the MC simulation, replies the collision probability\n"
+    "setNumGaussians  k: components of the mixture (1..8)\n"
+    "runGMMEstimation sampling-based GMM estimate, replies the collision probability\n"
+    "setNumGMMSamples n: samples per waypoint for the GMM estimate\n"
+    "setSeed          s: 64-bit seed of the counter-based random streams (new)\n"
+    "setFootprint     dx dy half_x half_y (new)\n"
+    "addObstacle      cx cy half_x half_y yaw_rad (new)\n"
+    "clearObstacles   (new)\n"
+    "setBatch         r: independent GMM estimations advanced in lockstep per runGMMEstimation (new)\n"
+    "setRunAhead      r: with one run per command, evaluate the next r runs in one launch and serve the following commands from it (new)\n"
+    "help             this text\n";
+
+extern "C" {
+
+const char* pocs_version(void) { return POCS_VERSION_STRING; }
+
+int pocs_create(pocs_ctx** out, int device) {
+  if (!out) return POCS_E_ARG;
+  *out = nullptr;
+  pocs_ctx* c = new (std::nothrow) pocs_ctx();
+  if (!c) return POCS_E_ARG;
+  *out = c;        // returned even on failure so the caller can read pocs_last_error
+  memset(&c->sensor, 0, sizeof c->sensor);
+  int n = 0;
+  hipError_t e = hipGetDeviceCount(&n);
+  if (e != hipSuccess || n <= 0)
+    return fail(c, POCS_E_DEVICE, "no HIP device available (%s); libpocs has no CPU path",
+                e != hipSuccess ? hipGetErrorString(e) : "device count 0");
+  if (device < 0 || device >= n) return fail(c, POCS_E_ARG, "device %d out of range (0..%d)", device, n - 1);
+  c->device = device;
+  HIPCHK(c, hipSetDevice(device));
+  HIPCHK(c, hipStreamCreateWithFlags(&c->own_stream, hipStreamNonBlocking));
+  c->stream = c->own_stream;
+  for (int g = 0; g < 3; ++g) {
+    HIPCHK(c, hipStreamCreateWithFlags(&c->side_stream[g], hipStreamNonBlocking));
+    HIPCHK(c, hipEventCreateWithFlags(&c->ev_join[g], hipEventDisableTiming));
+  }
+  HIPCHK(c, hipEventCreateWithFlags(&c->ev_fork, hipEventDisableTiming));
+  HIPCHK(c, hipEventCreate(&c->ev_seq[0]));
+  HIPCHK(c, hipEventCreate(&c->ev_seq[1]));
+  return POCS_OK;
+}
+
+#if defined(POCS_TUNING) && defined(POCS_STAMPS)
+void pocs_stamps_report();
+#endif
+void pocs_destroy(pocs_ctx* c) {
+  if (!c) return;
+#if defined(POCS_TUNING) && defined(POCS_STAMPS)
+  if (c->own_stream) { hipSetDevice(c->device); hipStreamSynchronize(c->stream); pocs_stamps_report(); }
+#endif
+  if (c->own_stream) {
+    hipSetDevice(c->device);
+    hipStreamSynchronize(c->stream);
+    drop_graphs(c);
+    for (hipEvent_t e : c->events) hipEventDestroy(e);
+    for (int g = 0; g < 3; ++g) {
+      if (c->side_stream[g]) { hipStreamSynchronize(c->side_stream[g]); hipStreamDestroy(c->side_stream[g]); }
+      if (c->ev_join[g]) hipEventDestroy(c->ev_join[g]);
+    }
+    if (c->ev_fork) hipEventDestroy(c->ev_fork);
+    if (c->ev_seq[0]) hipEventDestroy(c->ev_seq[0]);
+    if (c->ev_seq[1]) hipEventDestroy(c->ev_seq[1]);
+    DevBuf* all[] = {&c->d_env, &c->d_sensor, &c->d_hdr, &c->d_chain, &c->d_state, &c->d_param,
+                     &c->d_moments, &c->d_partial, &c->d_sx, &c->d_sy, &c->d_st, &c->d_flags,
+                     &c->d_px, &c->d_py, &c->d_pt, &c->d_hits, &c->d_total, &c->d_ticket, &c->d_tables, &c->d_runplan, &c->d_surv, &c->d_tparent};
+    for (DevBuf* b : all) if (b->p) hipFree(b->p);
+    if (c->h_pin) hipHostFree(c->h_pin);
+    if (c->h_copy) hipHostFree(c->h_copy);
+    for (int q = 0; q < POCS_XCHG_MAX_WORLD; ++q)
+      if (c->xchg_peer[q] && c->xchg_peer[q] != c->xchg_own) (void)hipIpcCloseMemHandle(c->xchg_peer[q]);
+    if (c->xchg_own) (void)hipFree(c->xchg_own);
+    hipStreamDestroy(c->own_stream);
+  }
+  delete c;
+}
+
+const char* pocs_last_error(const pocs_ctx* c) { return c ? c->err.c_str() : "null context"; }
+
+int pocs_set_footprint(pocs_ctx* c, double dx, double dy, double hx, double hy) {
+  if (c) touch(c);
+  if (!c) return POCS_E_ARG;
+  if (!(hx > 0) || !(hy > 0)) return fail(c, POCS_E_ARG, "footprint half extents must be > 0");
+  c->fp.dx = dx; c->fp.dy = dy; c->fp.hx = hx; c->fp.hy = hy;
+  c->env_dirty = true;
+  return POCS_OK;
+}
+
+int pocs_set_obstacles(pocs_ctx* c, const double* boxes, int M) {
+  if (c) touch(c);
+  if (!c) return POCS_E_ARG;
+  if (M < 0 || M > POCS_MAX_OBSTACLES || (M > 0 && !boxes))
+    return fail(c, POCS_E_ARG, "obstacle count %d outside 0..%d", M, POCS_MAX_OBSTACLES);
+  for (int m = 0; m < M; ++m)
+    if (!(boxes[5 * m + 2] > 0) || !(boxes[5 * m + 3] > 0))
+      return fail(c, POCS_E_ARG, "obstacle %d: half extents must be > 0", m);
+  c->boxes.assign(boxes, boxes + (size_t)M * 5);
+  c->have_obstacles = true;
+  c->env_dirty = true;
+  return POCS_OK;
+}
+
+int pocs_set_alphas(pocs_ctx* c, const double* a, int n) {
+  if (c) touch(c);
+  if (!c) return POCS_E_ARG;
+  if (n < 1 || n > 4 || !a) return fail(c, POCS_E_ARG, "setAlphas takes 1..4 values (got %d)", n);
+  for (int i = 0; i < n; ++i) c->alphas[i] = a[i];
+  c->have_alphas = true;
+  return POCS_OK;
+}
+
+int pocs_set_q(pocs_ctx* c, double q) {
+  if (c) touch(c);
+  if (!c) return POCS_E_ARG;
+  if (!(q >= 0)) return fail(c, POCS_E_ARG, "Q must be >= 0");
+  c->sensor.Q = q; c->have_q = true; c->sensor_dirty = true;
+  return POCS_OK;
+}
+
+int pocs_set_num_landmarks(pocs_ctx* c, int n) {
+  if (c) touch(c);
+  if (!c) return POCS_E_ARG;
+  if (n < 0 || n > POCS_MAX_LANDMARKS) return fail(c, POCS_E_ARG, "numLandmarks %d outside 0..%d", n, POCS_MAX_LANDMARKS);
+  c->num_landmarks = n; c->have_landmarks = false;
+  return POCS_OK;
+}
+
+int pocs_set_landmarks(pocs_ctx* c, const double* xy, int n) {
+  if (c) touch(c);
+  if (!c) return POCS_E_ARG;
+  if (c->num_landmarks < 0) return fail(c, POCS_E_ORDER, "setLandmarks before setNumLandmarks");
+  if (n != c->num_landmarks || (n > 0 && !xy)) return fail(c, POCS_E_ARG, "setLandmarks needs 2*%d values", c->num_landmarks);
+  c->sensor.L = n;
+  for (int i = 0; i < n; ++i) { c->sensor.lx[i] = xy[i]; c->sensor.ly[i] = xy[n + i]; }
+  c->have_landmarks = true; c->sensor_dirty = true;
+  return POCS_OK;
+}
+
+int pocs_set_num_particles(pocs_ctx* c, long long n) {
+  if (c) touch(c);
+  if (!c) return POCS_E_ARG;
+  if (n < 1) return fail(c, POCS_E_ARG, "numParticles must be >= 1");
+  c->num_particles = n;
+  return POCS_OK;
+}
+
+int pocs_set_initial_covariance(pocs_ctx* c, const double* m9) {
+  if (c) touch(c);
+  if (!c || !m9) return POCS_E_ARG;
+  memcpy(c->cov0, m9, 9 * sizeof(double));
+  c->have_cov0 = true;
+  return POCS_OK;
+}
+
+int pocs_set_path_length(pocs_ctx* c, int W) {
+  if (c) touch(c);
+  if (!c) return POCS_E_ARG;
+  if (c->plans.n) return fail(c, POCS_E_ORDER, "pocs_set_path_length while plans are set: clear them first with pocs_set_plans(ctx, 0, ...)");
+  if (c->tree.n) return fail(c, POCS_E_ORDER, "pocs_set_path_length while a tree of plans is set: clear it first with pocs_set_plan_tree(ctx, 0, ...)");
+  if (W < 1) return fail(c, POCS_E_ARG, "pathLength must be >= 1");
+  if (W != c->W) { c->have_traj = false; c->have_odom = false; }
+  c->W = W;
+  return POCS_OK;
+}
+
+int pocs_set_trajectory(pocs_ctx* c, const double* v, int W) {
+  if (c) touch(c);
+  if (!c) return POCS_E_ARG;
+  if (c->plans.n) return fail(c, POCS_E_ORDER, "pocs_set_trajectory while plans are set: clear them first with pocs_set_plans(ctx, 0, ...)");
+  if (c->tree.n) return fail(c, POCS_E_ORDER, "pocs_set_trajectory while a tree of plans is set: clear it first with pocs_set_plan_tree(ctx, 0, ...)");
+  if (c->W < 1) return fail(c, POCS_E_ORDER, "setTrajectory before setPathLength");
+  if (W != c->W || !v) return fail(c, POCS_E_ARG, "setTrajectory needs 3*%d values", c->W);
+  c->traj.assign(v, v + (size_t)3 * W);
+  c->have_traj = true;
+  return POCS_OK;
+}
+
+int pocs_set_odometry(pocs_ctx* c, const double* v, int Wm1) {
+  if (c) touch(c);
+  if (!c) return POCS_E_ARG;
+  if (c->plans.n) return fail(c, POCS_E_ORDER, "pocs_set_odometry while plans are set: clear them first with pocs_set_plans(ctx, 0, ...)");
+  if (c->tree.n) return fail(c, POCS_E_ORDER, "pocs_set_odometry while a tree of plans is set: clear it first with pocs_set_plan_tree(ctx, 0, ...)");
+  if (c->W < 1) return fail(c, POCS_E_ORDER, "setOdometry before setPathLength");
+  if (Wm1 != c->W - 1 || (Wm1 > 0 && !v)) return fail(c, POCS_E_ARG, "setOdometry needs 3*%d values", c->W - 1);
+  c->odom.assign(v, v + (size_t)3 * Wm1);
+  c->have_odom = true;
+  return POCS_OK;
+}
+
+int pocs_set_num_gaussians(pocs_ctx* c, int K) {
+  if (c) touch(c);
+  if (!c) return POCS_E_ARG;
+  if (K < 1 || K > POCS_MAX_GAUSSIANS) return fail(c, POCS_E_ARG, "numGaussians %d outside 1..%d", K, POCS_MAX_GAUSSIANS);
+  c->K = K;
+  return POCS_OK;
+}
+
+int pocs_set_num_gmm_samples(pocs_ctx* c, long long n) {
+  if (c) touch(c);
+  if (!c) return POCS_E_ARG;
+  if (n < 1) return fail(c, POCS_E_ARG, "numGMMSamples must be >= 1");
+  c->num_gmm = n;
+  return POCS_OK;
+}
+
+int pocs_set_seed(pocs_ctx* c, uint64_t seed) {
+  if (c) touch(c);
+  if (!c) return POCS_E_ARG;
+  c->seed = seed; c->run_index = 0;
+  return POCS_OK;
+}
+
+int pocs_set_option(pocs_ctx* c, int option, long long value) {
+  if (c) touch(c);
+  if (!c) return POCS_E_ARG;
+  switch (option) {
+    case POCS_OPT_STORE_SAMPLES: c->opt_store = value ? 1 : 0; break;
+    case POCS_OPT_MC_FUSED: c->opt_fused = value ? 1 : 0; break;
+    case POCS_OPT_USE_GRAPH: c->opt_graph = value ? 1 : 0; break;
+    case POCS_OPT_PROFILE:
+      if (value < 0 || value > 2) return fail(c, POCS_E_ARG, "POCS_OPT_PROFILE takes 0, 1 or 2");
+      c->opt_profile = value;
+      break;
+    case POCS_OPT_PERSISTENT:
+      // the queue-driven whole-call kernel (k_gmm_run) of round 2 was retired in round 3: slower than one launch per
+      // waypoint at every batch size measured, and not worth a second summation shape
+      if (value) return fail(c, POCS_E_ARG, "POCS_OPT_PERSISTENT: the queue-driven kernel has been retired (DESIGN.md section 5)");
+      break;
+    case POCS_OPT_LONE_CALL: c->opt_lone = value ? 1 : 0; break;
+    case POCS_OPT_SUB_BATCHES:
+      if (value < 0 || value > 2) return fail(c, POCS_E_ARG, "sub-batches %lld outside 0..2 (0 = by the call's size; three lost, four gained less than two: DESIGN.md section 5)", value);
+      c->opt_groups = value;
+      break;
+    case POCS_OPT_MC_NONTEMPORAL:
+      if (value < -1 || value > 1) return fail(c, POCS_E_ARG, "POCS_OPT_MC_NONTEMPORAL takes -1 (by size), 0 or 1");
+      c->opt_mc_nt = value;
+      break;
+    case POCS_OPT_PLAN_SEEDS:
+      if (value < 0 || value > 1) return fail(c, POCS_E_ARG, "POCS_OPT_PLAN_SEEDS takes 0 (plan p draws run p's stream) or 1 (common random numbers)");
+      c->opt_plan_seeds = value;
+      break;
+    case POCS_OPT_MC_WAYPOINT_COUNTS:
+      if (value < 0 || value > 1) return fail(c, POCS_E_ARG, "POCS_OPT_MC_WAYPOINT_COUNTS takes 0 or 1");
+      c->opt_mc_wp = value;
+      break;
+    case POCS_OPT_MC_RISK_BOUND:
+      if (value < 0 || value > 1) return fail(c, POCS_E_ARG, "POCS_OPT_MC_RISK_BOUND takes 0 (MC calls ignore the risk bound) or 1");
+      c->opt_mc_rb = value;
+      break;
+    case POCS_OPT_RUN_AHEAD:
+      if (value < 0 || value > 256) return fail(c, POCS_E_ARG, "run-ahead %lld outside 0..256", value);
+      c->run_ahead = (int)value;                     // 0 = sized per call (ra_depth)
+      break;
+    default: return fail(c, POCS_E_ARG, "unknown option %d", option);
+  }
+  return POCS_OK;
+}
+
+int pocs_set_batch(pocs_ctx* c, int runs) {
+  if (!c) return POCS_E_ARG;
+  touch(c);
+  if (c->plans.n) return fail(c, POCS_E_ORDER, "pocs_set_batch while plans are set (the batch is the plans): clear them first with pocs_set_plans(ctx, 0, ...)");
+  if (c->tree.n) return fail(c, POCS_E_ORDER, "pocs_set_batch while a tree of plans is set: clear it first with pocs_set_plan_tree(ctx, 0, ...)");
+  if (runs < 1 || runs > 256) return fail(c, POCS_E_ARG, "batch %d outside 1..256", runs);
+  if (c->gmm_open) return fail(c, POCS_E_ORDER, "pocs_set_batch inside a begin/end sequence");
+  c->batch = runs;
+  return POCS_OK;
+}
+
+// A set of plans or a tree takes the context's W and batch over (W: the stride of every [run][W] array; batch: the plans or
+// the nodes); the single plan's wait for leave_multi.  The results of the last launch refer to the plans (or the plan) it
+// evaluated: entering and leaving drop them.
+static void enter_multi(pocs_ctx* c, int W, int batch) {
+  if (!c->plans.n && !c->tree.n) { c->single_W = c->W; c->single_batch = c->batch; }
+  c->W = W; c->batch = batch;
+  reset_results(c);
+}
+static void leave_multi(pocs_ctx* c) {
+  c->W = c->single_W; c->batch = c->single_batch;
+  reset_results(c);
+}
+
+int pocs_set_plans(pocs_ctx* c, int P, const int* W, const double* trajs, const double* odoms) {
+  if (!c) return POCS_E_ARG;
+  touch(c);
+  if (c->gmm_open) return fail(c, POCS_E_ORDER, "pocs_set_plans inside a begin/end sequence");
+  if (P < 0 || P > 256) return fail(c, POCS_E_ARG, "plans: P = %d outside 0..256", P);
+  if (P == 0) {                                      // back to the single plan
+    if (c->plans.n) { c->plans = PlanSet{}; leave_multi(c); }
+    return POCS_OK;
+  }
+  if (c->tree.n) return fail(c, POCS_E_ORDER, "pocs_set_plans while a tree of plans is set: clear it first with pocs_set_plan_tree(ctx, 0, ...)");
+  if (!W || !trajs) return fail(c, POCS_E_ARG, "plans: null lengths or trajectories");
+  size_t nt = 0, no = 0;
+  int Wmax = 0;
+  for (int p = 0; p < P; ++p) {
+    if (W[p] < 1) return fail(c, POCS_E_ARG, "plans: plan %d has length %d (>= 1 needed)", p, W[p]);
+    nt += 3 * (size_t)W[p]; no += 3 * (size_t)(W[p] - 1);
+    Wmax = W[p] > Wmax ? W[p] : Wmax;
+  }
+  if (no > 0 && !odoms) return fail(c, POCS_E_ARG, "plans: null odometry");
+  if (c->shard_first >= 0) return fail(c, POCS_E_STATE, "plans: not with a shard (pocs_set_shard(ctx, -1, -1) first): multi-GPU plan batches are not supported");
+  if (c->xchg_connected) return fail(c, POCS_E_STATE, "plans: not on a context connected to the in-library exchange");
+  c->plans.W.assign(W, W + P);
+  c->plans.toff.assign((size_t)P, 0); c->plans.ooff.assign((size_t)P, 0);
+  for (int p = 1; p < P; ++p) {
+    c->plans.toff[(size_t)p] = c->plans.toff[(size_t)p - 1] + 3 * (size_t)W[p - 1];
+    c->plans.ooff[(size_t)p] = c->plans.ooff[(size_t)p - 1] + 3 * (size_t)(W[p - 1] - 1);
+  }
+  c->plans.traj.assign(trajs, trajs + nt);
+  if (no > 0) c->plans.odom.assign(odoms, odoms + no); else c->plans.odom.clear();
+  c->plans.odom.push_back(0.0);                       // (never read: keeps .data() of a set of one-waypoint plans non-null)
+  enter_multi(c, Wmax, P);
+  c->plans.n = P;
+  return POCS_OK;
+}
+
+int pocs_set_plan_risk_bound(pocs_ctx* c, double bound) {
+  if (!c) return POCS_E_ARG;
+  touch(c);                                          // (the epoch is part of the graphs' key: no graph captured for another bound is replayed)
+  if (!(bound > 0.0)) return fail(c, POCS_E_ARG, "risk bound %g: a probability in (0, 1), or >= 1 for none", bound);     // (NaN too)
+  if (c->gmm_open) return fail(c, POCS_E_ORDER, "pocs_set_plan_risk_bound inside a begin/end sequence");
+  c->risk_bound = bound < 1.0 ? bound : 1.0;
+  return POCS_OK;
+}
+
+int pocs_get_plan_evaluated(pocs_ctx* c, int* out, int cap) {
+  if (!c || !out) return POCS_E_ARG;
+  const int kind = c->res.last_kind;                     // 1 GMM, 2 MC -- which by default ignores the bound: every plan is driven to its end
+  if (!c->plans.n || kind == 0 || c->res.plan_slot[kind - 1].empty() || (kind == 1 && c->res.plan_E.empty()))
+    return fail(c, POCS_E_STATE, "pocs_get_plan_evaluated: the last call was not a call of plans");
+  const std::vector<int>& E = kind == 1 ? c->res.plan_E : c->res.plan_E_mc.empty() ? c->plans.W : c->res.plan_E_mc;
+  if ((int)E.size() > cap) return fail(c, POCS_E_BUFFER, "need %zu ints", E.size());
+  memcpy(out, E.data(), E.size() * sizeof(int));
+  return (int)E.size();
+}
+
+int pocs_set_plan_tree(pocs_ctx* c, int nodes, const int* parent, const double* poses, const double* odoms) {
+  if (!c) return POCS_E_ARG;
+  touch(c);
+  if (c->gmm_open) return fail(c, POCS_E_ORDER, "pocs_set_plan_tree inside a begin/end sequence");
+  if (nodes < 0 || nodes > POCS_MAX_TREE_NODES) return fail(c, POCS_E_ARG, "tree: %d nodes outside 0..%d", nodes, POCS_MAX_TREE_NODES);
+  if (nodes == 0) {                                  // back to the single plan
+    if (c->tree.n) { c->tree = PlanTree{}; leave_multi(c); }
+    return POCS_OK;
+  }
+  if (c->plans.n) return fail(c, POCS_E_ORDER, "pocs_set_plan_tree while plans are set: clear them first with pocs_set_plans(ctx, 0, ...)");
+  if (!parent || !poses || (nodes > 1 && !odoms)) return fail(c, POCS_E_ARG, "tree: null parents, poses or controls");
+  if (parent[0] != -1) return fail(c, POCS_E_ARG, "tree: node 0 is the root, its parent must be -1 (got %d)", parent[0]);
+  for (int n = 1; n < nodes; ++n)
+    if (parent[n] < 0 || parent[n] >= n)
+      return fail(c, POCS_E_ARG, "tree: parent[%d] = %d; one root, and every other node's parent comes before it (0 <= parent[n] < n)", n, parent[n]);
+  if (c->shard_first >= 0) return fail(c, POCS_E_STATE, "tree: not with a shard (pocs_set_shard(ctx, -1, -1) first): trees run on one GPU");
+  if (c->xchg_connected) return fail(c, POCS_E_STATE, "tree: not on a context connected to the in-library exchange");
+  const size_t T = (size_t)nodes;
+  std::vector<int> depth(T, 0);
+  int D = 0;
+  for (size_t n = 1; n < T; ++n) { depth[n] = depth[(size_t)parent[n]] + 1; D = depth[n] > D ? depth[n] : D; }
+  c->tree.parent.assign(parent, parent + T);
+  c->tree.depth = depth;
+  c->tree.pose.assign(poses, poses + 3 * T);
+  if (odoms) c->tree.odom.assign(odoms, odoms + 3 * T); else c->tree.odom.assign(3 * T, 0.0);
+  // slots: level by level, every level a contiguous range, the nodes of a level in node order
+  c->tree.level.assign((size_t)D + 2, 0);
+  for (size_t n = 0; n < T; ++n) c->tree.level[(size_t)depth[n] + 1] += 1;
+  for (size_t d = 0; d <= (size_t)D; ++d) c->tree.level[d + 1] += c->tree.level[d];
+  std::vector<int> fill(c->tree.level.begin(), c->tree.level.end() - 1);
+  c->tree.slot.assign(T, 0); c->tree.node.assign(T, 0); c->tree.pslot.assign(T, 0);
+  for (size_t n = 0; n < T; ++n) { const int s = fill[(size_t)depth[n]]++; c->tree.slot[n] = s; c->tree.node[(size_t)s] = (int)n; }
+  for (size_t n = 1; n < T; ++n) c->tree.pslot[(size_t)c->tree.slot[n]] = c->tree.slot[(size_t)parent[n]];
+  c->tree.dirty = true;
+  enter_multi(c, 1, nodes);                          // one row per node in every [run][W] array
+  c->tree.n = nodes;
+  return POCS_OK;
+}
+
+int pocs_get_tree_probabilities(pocs_ctx* c, double* out, int cap) {
+  if (!c || !out) return POCS_E_ARG;
+  if (!c->tree.n || !c->res.tree_last || c->res.tree_probs.empty()) return fail(c, POCS_E_STATE, "pocs_get_tree_probabilities: the last call was not a call on a tree of plans");
+  if ((int)c->res.tree_probs.size() > cap) return fail(c, POCS_E_BUFFER, "need %zu doubles", c->res.tree_probs.size());
+  memcpy(out, c->res.tree_probs.data(), c->res.tree_probs.size() * sizeof(double));
+  return (int)c->res.tree_probs.size();
+}
+
+int pocs_get_tree_evaluated(pocs_ctx* c, unsigned char* out, int cap) {
+  if (!c || !out) return POCS_E_ARG;
+  if (!c->tree.n || !c->res.tree_last || c->res.tree_eval.empty()) return fail(c, POCS_E_STATE, "pocs_get_tree_evaluated: the last call was not a call on a tree of plans");
+  if ((int)c->res.tree_eval.size() > cap) return fail(c, POCS_E_BUFFER, "need %zu bytes", c->res.tree_eval.size());
+  memcpy(out, c->res.tree_eval.data(), c->res.tree_eval.size());
+  return (int)c->res.tree_eval.size();
+}
+
+int pocs_mc_get_tree_counts(pocs_ctx* c, unsigned long long* out, int cap) {
+  if (!c || !out) return POCS_E_ARG;
+  if (!c->tree.n || c->res.tree_last != 2 || c->res.tree_C.empty()) return fail(c, POCS_E_STATE, "pocs_mc_get_tree_counts: the last call was not an MC call on a tree of plans");
+  if ((int)c->res.tree_C.size() > cap) return fail(c, POCS_E_BUFFER, "need %zu counters", c->res.tree_C.size());
+  memcpy(out, c->res.tree_C.data(), c->res.tree_C.size() * sizeof(unsigned long long));
+  return (int)c->res.tree_C.size();
+}
+
+int pocs_select_tree_node(pocs_ctx* c, int node) {
+  if (!c) return POCS_E_ARG;
+  if (!c->tree.n || !c->res.tree_last) return fail(c, POCS_E_STATE, "pocs_select_tree_node: the last call was not a call on a tree of plans");
+  if (node < 0 || node >= c->tree.n) return fail(c, POCS_E_ARG, "node %d outside the tree (0..%d)", node, c->tree.n - 1);
+  if (c->res.tree_last == 1) tree_select_gmm(c, node);
+  c->res.tree_sel = node;
+  return POCS_OK;
+}
+
+int pocs_get_batch_probabilities(pocs_ctx* c, double* out, int cap) {
+  if (!c || !out) return POCS_E_ARG;
+  if (c->ra_internal) {                       // the caller asked for one run at a time
+    if (cap < 1 || c->res.batch_probs.empty()) return fail(c, POCS_E_BUFFER, "need 1 double");
+    out[0] = c->res.batch_probs[(size_t)c->res.view];
+    return 1;
+  }
+  if ((int)c->res.batch_probs.size() > cap) return fail(c, POCS_E_BUFFER, "need %zu doubles", c->res.batch_probs.size());
+  memcpy(out, c->res.batch_probs.data(), c->res.batch_probs.size() * sizeof(double));
+  return (int)c->res.batch_probs.size();
+}
+
+int pocs_select_batch_run(pocs_ctx* c, int run) {
+  if (!c) return POCS_E_ARG;
+  if (c->ra_internal) return fail(c, POCS_E_ORDER, "pocs_select_batch_run: the last launch was a run-ahead batch (one run per command)");
+  if (c->tree.n) return fail(c, POCS_E_ORDER, "pocs_select_batch_run: a tree of plans is set (pocs_select_tree_node selects a node)");
+  if (run < 0 || run >= c->res.batch_R || c->res.batch_probs.empty()) return fail(c, POCS_E_ARG, "run %d outside the last batch (0..%d)", run, c->res.batch_R - 1);
+  if (c->res.last_kind == 1) gmm_select_view(c, run);       // per-waypoint probabilities and moments of that run
+  c->res.view = run;
+  return POCS_OK;
+}
+
+int pocs_set_shard(pocs_ctx* c, long long first, long long count) {
+  if (c) touch(c);
+  if (!c) return POCS_E_ARG;
+  if (first == -1 && count == -1) { c->shard_first = -1; c->shard_count = -1; return POCS_OK; }   // whole range
+  if (c->plans.n) return fail(c, POCS_E_STATE, "pocs_set_shard: plans are set (multi-GPU plan batches are not supported)");
+  if (c->tree.n) return fail(c, POCS_E_STATE, "pocs_set_shard: a tree of plans is set (trees run on one GPU)");
+  if (first < 0 || count < 0) return fail(c, POCS_E_ARG, "negative shard");
+  c->shard_first = first; c->shard_count = count;
+  return POCS_OK;
+}
+
+int pocs_set_stream(pocs_ctx* c, void* s) {
+  if (c) touch(c);
+  if (!c) return POCS_E_ARG;
+  c->stream = s ? (hipStream_t)s : c->own_stream;
+  drop_graphs(c);
+  return POCS_OK;
+}
+
+int pocs_gmm_bind_moments(pocs_ctx* c, void* dptr, long long len) {
+  if (c) touch(c);
+  if (!c) return POCS_E_ARG;
+  c->ext_moments = (double*)dptr; c->ext_moments_len = dptr ? len : 0;
+  drop_graphs(c);
+  return POCS_OK;
+}
+
+// run* with run-ahead: serve the next cached run, or evaluate the next `run_ahead` runs at once.
+static bool ra_can_serve(const pocs_ctx* c, int kind) {
+  return c->ra_have > 0 && c->ra_kind == kind && c->batch == 1 && c->res.view + 1 < c->ra_have;
+}
+// Runs evaluated per launch when run-ahead is on.  0 (automatic): enough runs to keep the chip busy for the
+// launch's fixed cost to fade -- 1.6 x 10^7 mixture samples or 8 x 10^6 particles (what stays in the
+// Infinity Cache between two waypoint launches) per launch, at least 8, at most 64: the reference's
+// own 200 runs of 10^4 samples go 64 at a time, a 10^6-sample estimation 16 at a time.
+static int ra_depth(const pocs_ctx* c, int kind) {
+  if (c->run_ahead != 0) return c->run_ahead;
+  const long long n = kind == 1 ? c->num_gmm : c->num_particles;
+  const long long want = (kind == 1 ? 16000000LL : 8000000LL) / (n > 0 ? n : 1);
+  return (int)(want < 8 ? 8 : want > 64 ? 64 : want);
+}
+static bool ra_wanted(const pocs_ctx* c, int kind) {
+  return ra_depth(c, kind) > 1 && c->batch == 1 && !c->plans.n && !c->tree.n && c->shard_first < 0 && !c->opt_profile && !c->ext_moments && !c->gmm_open;
+}
+static void mc_fill_probs(pocs_ctx* c) {
+  // getCollisionProportion, MCSimulator.h:324-330 (of the particles this context evaluated)
+  const double den = (double)(c->res.last_mc_count > 0 ? c->res.last_mc_count : 1);
+  c->res.batch_probs.assign(c->res.mc_counts.size(), 0.0);
+  for (size_t r = 0; r < c->res.mc_counts.size(); ++r) c->res.batch_probs[r] = (double)c->res.mc_counts[r] / den;
+}
+
+int pocs_run_gmm_estimation(pocs_ctx* c, double* probability) {
+  if (!c) return POCS_E_ARG;
+  if (!probability) return fail(c, POCS_E_ARG, "null output");
+  HIPCHK(c, hipSetDevice(c->device));
+  if (ra_can_serve(c, 1)) {
+    gmm_select_view(c, c->res.view + 1);
+    *probability = c->res.batch_probs[(size_t)c->res.view];
+    return POCS_OK;
+  }
+  ra_drop(c);
+  c->ra_internal = false;
+  if (!ra_wanted(c, 1)) return run_gmm_full(c, probability);
+  const int depth = ra_depth(c, 1);
+  c->batch = depth;
+  const int rc = run_gmm_full(c, probability);
+  c->batch = 1;
+  if (rc == POCS_OK) { c->ra_have = depth; c->ra_kind = 1; c->ra_internal = true; }
+  return rc;
+}
+
+int pocs_run_simulation(pocs_ctx* c, double* probability) {
+  if (!c) return POCS_E_ARG;
+  if (!probability) return fail(c, POCS_E_ARG, "null output");
+  HIPCHK(c, hipSetDevice(c->device));
+  if (ra_can_serve(c, 2)) {
+    c->res.view += 1;
+    *probability = c->res.batch_probs[(size_t)c->res.view];
+    return POCS_OK;
+  }
+  ra_drop(c);
+  c->ra_internal = false;
+  const bool ra = ra_wanted(c, 2);
+  const int depth = ra_depth(c, 2);
+  if (ra) c->batch = depth;
+  const int rc = run_mc_local(c);
+  c->batch = ra ? 1 : c->batch;
+  if (rc) return rc;
+  mc_fill_probs(c);
+  if (ra) { c->ra_have = depth; c->ra_kind = 2; c->ra_internal = true; }
+  *probability = c->res.batch_probs[0];
+  return POCS_OK;
+}
+
+int pocs_mc_run_local(pocs_ctx* c, unsigned long long* collided) {
+  if (!c) return POCS_E_ARG;
+  if (!collided) return fail(c, POCS_E_ARG, "null output");
+  HIPCHK(c, hipSetDevice(c->device));
+  ra_drop(c);
+  c->ra_internal = false;
+  if (int r = run_mc_local(c)) return r;
+  *collided = c->res.mc_counts[0];
+  return POCS_OK;
+}
+
+int pocs_mc_get_batch_counts(pocs_ctx* c, unsigned long long* out, int cap) {
+  if (!c || !out) return POCS_E_ARG;
+  if (c->ra_internal) {                       // the caller asked for one run at a time
+    if (cap < 1 || c->res.mc_counts.empty()) return fail(c, POCS_E_BUFFER, "need 1 counter");
+    out[0] = c->res.mc_counts[(size_t)c->res.view];
+    return 1;
+  }
+  if ((int)c->res.mc_counts.size() > cap) return fail(c, POCS_E_BUFFER, "need %zu counters", c->res.mc_counts.size());
+  memcpy(out, c->res.mc_counts.data(), c->res.mc_counts.size() * sizeof(unsigned long long));
+  return (int)c->res.mc_counts.size();
+}
+
+int pocs_mc_get_waypoint_counts(pocs_ctx* c, unsigned long long* out, int cap) {
+  if (!c || !out) return POCS_E_ARG;
+  const size_t W = (size_t)(c->res.mc_wp_W > 0 ? c->res.mc_wp_W : 1), r = (size_t)c->res.view;
+  if (c->tree.n) {                                   // the selected node's path: the first collisions at each of its nodes
+    if (c->res.tree_last != 2 || c->res.tree_F.empty()) return fail(c, POCS_E_STATE, "pocs_mc_get_waypoint_counts: the last call was not an MC call on the tree");
+    const int n = c->tree.depth[(size_t)c->res.tree_sel] + 1;
+    if (n > cap) return fail(c, POCS_E_BUFFER, "need %d counters", n);
+    for (int v = c->res.tree_sel, w = n - 1; v >= 0; v = c->tree.parent[(size_t)v], --w) out[w] = c->res.tree_F[(size_t)v];
+    return n;
+  }
+  if (c->res.last_kind != 2 || c->res.mc_wp.empty() || (r + 1) * W > c->res.mc_wp.size())
+    return fail(c, POCS_E_STATE, "pocs_mc_get_waypoint_counts: the last call was not an MC call under POCS_OPT_MC_WAYPOINT_COUNTS (or POCS_OPT_MC_RISK_BOUND with a bound)");
+  int n = (int)W;                                    // the selected run's waypoints; a plan's own, or those before its stop
+  if (c->plans.n && r < c->res.plan_slot[1].size()) n = c->res.plan_E_mc.empty() ? c->plans.W[r] : c->res.plan_E_mc[r];
+  if (n > cap) return fail(c, POCS_E_BUFFER, "need %d counters", n);
+  memcpy(out, &c->res.mc_wp[r * W], (size_t)n * sizeof(unsigned long long));
+  return n;
+}
+
+int pocs_xchg_create(pocs_ctx* c, int world, int rank, void* handle64) {
+  if (!c || !handle64) return POCS_E_ARG;
+  if (world < 1 || world > POCS_XCHG_MAX_WORLD || rank < 0 || rank >= world)
+    return fail(c, POCS_E_ARG, "exchange: world %d / rank %d outside 1..%d", world, rank, POCS_XCHG_MAX_WORLD);
+  static_assert(sizeof(hipIpcMemHandle_t) == 64, "pocs.h promises a 64-byte handle");
+  if (c->plans.n) return fail(c, POCS_E_STATE, "pocs_xchg_create: plans are set (multi-GPU plan batches are not supported)");
+  if (c->tree.n) return fail(c, POCS_E_STATE, "pocs_xchg_create: a tree of plans is set (trees run on one GPU)");
+  HIPCHK(c, hipSetDevice(c->device));
+  if (!c->xchg_own) {
+    // FINE-GRAINED device memory: other GPUs write into it and this GPU polls it inside a running kernel.
+    // Ordinary (coarse-grained) allocations are only coherent with other devices at kernel boundaries --
+    // a flag once cached in an XCD's L2 could be read stale for ever.
+    HIPCHK(c, hipExtMallocWithFlags(&c->xchg_own, POCS_XCHG_BYTES, hipDeviceMallocFinegrained));
+    HIPCHK(c, hipMemset(c->xchg_own, 0, POCS_XCHG_BYTES));       // epoch 0 = nothing has landed
+    HIPCHK(c, hipDeviceSynchronize());
+  }
+  c->xchg_world = world; c->xchg_rank = rank; c->xchg_connected = false;
+  hipIpcMemHandle_t h;
+  HIPCHK(c, hipIpcGetMemHandle(&h, c->xchg_own));
+  memcpy(handle64, &h, sizeof h);
+  return POCS_OK;
+}
+
+int pocs_xchg_connect(pocs_ctx* c, const void* handles, int world) {
+  if (!c || !handles) return POCS_E_ARG;
+  if (c->plans.n) return fail(c, POCS_E_STATE, "pocs_xchg_connect: plans are set (multi-GPU plan batches are not supported)");
+  if (c->tree.n) return fail(c, POCS_E_STATE, "pocs_xchg_connect: a tree of plans is set (trees run on one GPU)");
+  if (!c->xchg_own || world != c->xchg_world) return fail(c, POCS_E_ORDER, "pocs_xchg_connect before pocs_xchg_create (or another world size)");
+  HIPCHK(c, hipSetDevice(c->device));
+  for (int q = 0; q < world; ++q) {
+    if (q == c->xchg_rank) { c->xchg_peer[q] = c->xchg_own; continue; }
+    hipIpcMemHandle_t h;
+    memcpy(&h, (const char*)handles + 64 * (size_t)q, sizeof h);
+    if (c->xchg_peer[q] && c->xchg_peer[q] != c->xchg_own) { (void)hipIpcCloseMemHandle(c->xchg_peer[q]); c->xchg_peer[q] = nullptr; }
+    HIPCHK(c, hipIpcOpenMemHandle(&c->xchg_peer[q], h, hipIpcMemLazyEnablePeerAccess));
+  }
+  c->xchg_connected = true;
+  return POCS_OK;
+}
+
+int pocs_get_path_length(const pocs_ctx* c) {
+  if (!c) return POCS_E_ARG;
+  if (c->plans.n) return c->plans.W[(size_t)(c->res.view < c->plans.n ? c->res.view : 0)];     // the selected plan's
+  if (c->tree.n) return c->tree.depth[(size_t)c->res.tree_sel] + 1;                     // the path root -> the selected node
+  return c->W;
+}
+
+int pocs_get_waypoint_probabilities(pocs_ctx* c, double* out, int cap) {
+  if (!c || !out) return POCS_E_ARG;
+  if ((int)c->res.probs.size() > cap) return fail(c, POCS_E_BUFFER, "need %zu doubles", c->res.probs.size());
+  memcpy(out, c->res.probs.data(), c->res.probs.size() * sizeof(double));
+  return (int)c->res.probs.size();
+}
+
+int pocs_get_moments(pocs_ctx* c, int w, double* out, int cap) {
+  if (!c || !out) return POCS_E_ARG;
+  const int n = c->K * POCS_NMOM;
+  if (w < 0 || (size_t)(w + 1) * n > c->res.last_moments.size()) return fail(c, POCS_E_ARG, "no moments for waypoint %d", w);
+  if (cap < n) return fail(c, POCS_E_BUFFER, "need %d doubles", n);
+  memcpy(out, &c->res.last_moments[(size_t)w * n], (size_t)n * sizeof(double));
+  return n;
+}
+
+// The text channel: the grammar (names, token counts, order rules) lives in pocs_command.hpp -- host only, fuzzed
+// under sanitizers on the CPU -- and this is the dispatch of a parsed line to the typed setters above.
+int pocs_send_command(pocs_ctx* c, const char* line, char* out, size_t cap) {
+  if (!c || !line) return POCS_E_ARG;
+  if (out && cap) out[0] = 0;
+  const pocs_cmd::Shape shape = {c->num_landmarks, c->W};
+  const pocs_cmd::Parsed p = pocs_cmd::parse(line, shape);
+  if (p.err) return fail(c, p.err, "%s", p.msg.c_str());
+  const std::vector<double>& v = p.v;
+  switch (p.id) {
+    case pocs_cmd::kMyCommand: return put(c, out, cap, "output");                   // mcsimplugin.cpp:225-231
+    case pocs_cmd::kArmaCommand: return POCS_OK;                                     // :189-223 (Armadillo demo) -> no-op
+    case pocs_cmd::kHelp: return put(c, out, cap, kHelp);
+    case pocs_cmd::kSetAlphas: return pocs_set_alphas(c, v.data(), (int)v.size());   // :174-187
+    case pocs_cmd::kSetQ: return pocs_set_q(c, v[0]);
+    case pocs_cmd::kSetNumLandmarks: return pocs_set_num_landmarks(c, (int)p.n);
+    case pocs_cmd::kSetLandmarks: return pocs_set_landmarks(c, v.data(), c->num_landmarks);
+    case pocs_cmd::kSetNumParticles: return pocs_set_num_particles(c, p.n);
+    case pocs_cmd::kSetInitialCovariance: return pocs_set_initial_covariance(c, v.data());
+    case pocs_cmd::kSetPathLength: return pocs_set_path_length(c, (int)p.n);
+    case pocs_cmd::kSetTrajectory: return pocs_set_trajectory(c, v.data(), c->W);
+    case pocs_cmd::kSetOdometry: return pocs_set_odometry(c, v.data(), c->W - 1);
+    case pocs_cmd::kSetNumGaussians: return pocs_set_num_gaussians(c, (int)p.n);
+    case pocs_cmd::kSetNumGMMSamples: return pocs_set_num_gmm_samples(c, p.n);
+    case pocs_cmd::kSetSeed: return pocs_set_seed(c, (uint64_t)p.seed);
+    case pocs_cmd::kSetFootprint: return pocs_set_footprint(c, v[0], v[1], v[2], v[3]);
+    case pocs_cmd::kAddObstacle: {
+      std::vector<double> b = c->boxes;
+      b.insert(b.end(), v.begin(), v.end());
+      return pocs_set_obstacles(c, b.data(), (int)(b.size() / 5));
+    }
+    case pocs_cmd::kClearObstacles: return pocs_set_obstacles(c, nullptr, 0);
+    case pocs_cmd::kSetBatch: return pocs_set_batch(c, (int)p.n);
+    case pocs_cmd::kSetRunAhead: return pocs_set_option(c, POCS_OPT_RUN_AHEAD, p.n);
+    case pocs_cmd::kRunSimulation: case pocs_cmd::kRunGMMEstimation: {               // :75-81, :66-72
+      double prob = 0.0;
+      const int r = (p.id == pocs_cmd::kRunSimulation) ? pocs_run_simulation(c, &prob) : pocs_run_gmm_estimation(c, &prob);
+      if (r) return r;
+      char buf[64];
+      snprintf(buf, sizeof buf, "%.17g", prob);
+      return put(c, out, cap, buf);
+    }
+    case pocs_cmd::kUnknown: break;
+  }
+  return fail(c, POCS_E_UNKNOWN_COMMAND, "unknown command '%s'", p.name.c_str());
+}
+
+}  // extern "C"

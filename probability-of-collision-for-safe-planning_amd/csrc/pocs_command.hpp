@@ -9,7 +9,7 @@
 // are parsed and COUNTED against what the command takes (for the three count-dependent commands: against the
 // counts the earlier commands fixed, handed in as `Shape`), and the result is a value: command id, numbers,
 // integer / seed argument, or an error code of include/pocs.h with its text.  pocs_send_command
-// (pocs_host.hip) dispatches on it; nothing here touches a context, so the grammar is compiled and fuzzed on
+// (pocs_api.hip) dispatches on it; nothing here touches a context, so the grammar is compiled and fuzzed on
 // the CPU under AddressSanitizer / UBSan (tests/command_fuzz.cpp, tests/test_sanitizers.py).
 #pragma once
 #include <math.h>

@@ -1,0 +1,285 @@
+// pocs_ctx.hpp -- what the units of the host runtime share: the context behind the C ABI (include/pocs.h) with its
+// sub-records, error reporting, device buffers, the graph cache's drop, and the functions one unit calls in another.
+//
+//   pocs_stage.hip   host chain, staging layout, run / tree images, look-ahead cache, upload of a call's runs
+//   pocs_host.hip    the run paths: GMM and MC whole calls, their tree forms, the step and exchange API
+//   pocs_api.hip     context life cycle, setters, getters, run-ahead front, text dispatcher
+//   pocs_audit.hip   read-backs of device state for tests and audits, bandwidth and device-math probes, timing getters
+//
+// Host only: none of these units holds a kernel (pocs_kernels.hip does).
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <math.h>
+#include <stdarg.h>
+#include <stdio.h>
+#include <stdlib.h>
+#include <string.h>
+
+#include <algorithm>
+#include <string>
+#include <vector>
+
+#include "../../include/pocs.h"
+#include "pocs_kernels.h"
+
+// Everything internal to the host runtime lives in this namespace and stays out of the library's dynamic symbols.
+#define POCS_HIDDEN __attribute__((visibility("hidden")))
+
+namespace pocs_rt POCS_HIDDEN {
+
+struct DevBuf {
+  void* p = nullptr;
+  size_t cap = 0;
+};
+
+// candidate plans (pocs_set_plans): n > 0 = every run* call evaluates n plans, one run each, in one batch.  The context's W is
+// then the longest plan's length (the stride of every [run][W] array) and its batch = n; the single plan's length and
+// the batch wait in single_W / single_batch (enter_multi) for pocs_set_plans(ctx, 0, ...).
+struct PlanSet {
+  int n = 0;
+  std::vector<int> W;                             // [P]
+  std::vector<size_t> toff, ooff;                 // [P] where plan p starts in traj (3 x W_p) / odom (3 x (W_p - 1))
+  std::vector<double> traj, odom;
+};
+
+// a tree of candidate plans (pocs_set_plan_tree): n > 0 = every run* call evaluates the n nodes once each.  On the device a node
+// is a SLOT: the nodes level by level (BFS), every level a contiguous range of slots, and every per-run array holds one row
+// per slot -- while a tree is set the context's W = 1 and its batch = n (the single plan's length and batch wait in single_W /
+// single_batch, as under pocs_set_plans; a tree and a set of plans exclude each other).
+struct PlanTree {
+  int n = 0;
+  std::vector<int> parent, depth;                 // [T], the caller's node order
+  std::vector<double> pose, odom;                 // 3 x T by component: the node's pose, the control of the edge into it
+  std::vector<int> slot, node;                    // node -> slot, slot -> node
+  std::vector<int> level;                         // [D + 2]: level d = slots [level[d], level[d + 1])
+  std::vector<int> pslot;                         // [T] the slot of every slot's parent (slot 0: 0), as uploaded to d_tparent
+  bool dirty = false;
+};
+
+// Everything that describes the last call: what the getters serve.  A new set of plans and a call that fails after its launches
+// leave none of it (reset_results).
+struct Results {
+  int last_kind = 0;                     // what the last launch was: 1 GMM, 2 MC
+  uint64_t batch_base = 0;               // run_index of run 0 of the last launch
+  int batch_R = 1;                       // runs in the last launch
+  int view = 0;                          // the run of the last launch the getters expose
+  std::vector<double> h_chain;           // (W-1) x POCS_CHAIN_STRIDE
+  std::vector<double> h_mu, h_cov;       // (W-1) x 3, (W-1) x 9 : main EKF after each step
+  std::vector<double> probs;             // W (the selected run of the last batch)
+  std::vector<double> batch_probs;       // final probability of every run of the last batch
+  std::vector<unsigned long long> mc_counts;   // collided particles of every run of the last MC batch (this shard)
+  std::vector<double> last_moments;      // W x K x 11 (the selected run)
+  std::vector<double> batch_moments;     // [W][R][K*11] of the last GMM launch
+  long long last_gmm_count = 0, last_mc_count = 0;
+  int last_gmm_wp = -1;
+  std::vector<int> plan_slot[2];         // the batch slot of plan p in the last call of plans: [0] GMM, [1] MC
+  std::vector<int> plan_E;               // [P] waypoints evaluated per plan in the last GMM call of plans (empty: there was none)
+  std::vector<unsigned long long> mc_wp; // [R][mc_wp_W] first collisions per waypoint of the last MC call, in run / plan order (empty: the call ran without)
+  int mc_wp_W = 0;
+  std::vector<int> plan_E_mc;            // [P] waypoints evaluated per plan in the last MC call of plans under the bound (empty: every plan to its end)
+  int tree_last = 0;                     // what the last call on the tree was: 0 none, 1 GMM, 2 MC
+  int tree_sel = 0;                      // the node the getters show (pocs_select_tree_node)
+  std::vector<double> tree_probs;                 // [T] node order: running probability of the path root -> n
+  std::vector<unsigned char> tree_eval;           // [T] 1 evaluated, 0 cut off below a stopped ancestor
+  std::vector<unsigned long long> tree_F, tree_C; // [T] MC: first collisions at the node, collided at or before it
+  size_t tree_mc_half = 0;                        // MC: elements of one level's half of the particle buffers
+};
+
+}  // namespace pocs_rt
+
+struct pocs_ctx {
+  int device = 0;
+  hipStream_t stream = nullptr;
+  hipStream_t own_stream = nullptr;
+  // A call of many runs is issued as `groups` sub-batches on streams of their own (gmm_groups): while one
+  // sub-batch is in the tail of a waypoint's launch (the last blocks' slower waves, the serial mixture
+  // advance of its closers, the launch boundary) the others' sampling blocks have the SIMDs.
+  hipStream_t side_stream[3] = {nullptr, nullptr, nullptr};
+  hipEvent_t ev_fork = nullptr, ev_join[3] = {nullptr, nullptr, nullptr}, ev_seq[2] = {nullptr, nullptr};
+  double seq_ms = 0.0;                   // POCS_OPT_PROFILE: first launch -> last launch's end of the last whole-run call
+  int seq_groups = 1;
+  std::string err;
+
+  // ---- configuration (what MCSimulator holds, MCSimulator.h:94-136) ----
+  double alphas[4] = {1, 1, 1, 1};      // ones, as the reference ctor leaves them (:143)
+  bool have_alphas = false;
+  pocs_sensor sensor;
+  bool have_q = false, have_landmarks = false;
+  int num_landmarks = -1;
+  long long num_particles = -1;
+  double cov0[9];
+  bool have_cov0 = false;
+  int W = -1;
+  std::vector<double> traj, odom;        // by component: 3 x W, 3 x (W-1)
+  bool have_traj = false, have_odom = false;
+  int K = -1;
+  long long num_gmm = -1;
+  uint64_t seed = 0x5EED0001ull;
+  uint64_t run_index = 0;
+  pocs_footprint fp = {0.0, 0.0, 0.334, 0.334};
+  std::vector<double> boxes;             // M x 5
+  bool have_obstacles = false;           // pocs_set_obstacles / addObstacle / clearObstacles was called at least once
+  long long shard_first = -1, shard_count = -1;
+  long long opt_store = 1, opt_fused = 0, opt_graph = 1, opt_profile = 0, opt_lone = 1, opt_groups = 0, opt_mc_nt = -1;
+  unsigned long long epoch = 0;          // bumped by every setter; part of the graph cache key
+  int batch = 1;                         // independent GMM estimations advanced in lockstep per call
+  // run-ahead (POCS_OPT_RUN_AHEAD): with batch == 1 a run* call evaluates the next `run_ahead` runs
+  // of the context in one launch and the following calls are served from it (res.view: the one served last).
+  int run_ahead = 1;
+  int ra_have = 0;                       // runs of the last launch that may still be served (0: none)
+  int ra_kind = 0;                       // 1 GMM, 2 MC
+  bool ra_internal = false;              // the last launch was an internal run-ahead batch
+
+  pocs_rt::PlanSet plans;
+  pocs_rt::PlanTree tree;
+  int single_W = -1, single_batch = 1;   // the single plan's W / batch while plans or a tree hold the context's (enter_multi)
+  long long opt_plan_seeds = 0;          // POCS_OPT_PLAN_SEEDS
+  // risk bound of calls of plans (pocs_set_plan_risk_bound): a plan whose running probability reaches it is not evaluated
+  // any further (k_gmm_step_risk decides and obeys on the device; gmm_combine restates the rule on the moments read back)
+  double risk_bound = 1.0;               // >= 1: off
+  // first collisions per waypoint of MC calls (POCS_OPT_MC_WAYPOINT_COUNTS) and the risk bound obeyed by them
+  // (POCS_OPT_MC_RISK_BOUND): k_mc_*_counts count, k_mc_step_counts<.., MC_STOP> decides and obeys; run_mc_local restates the
+  // rule on the counts read back
+  long long opt_mc_wp = 0, opt_mc_rb = 0;
+
+  // host image (headers | chains | initial mixtures) of the NEXT batch, computed while the GPU
+  // works on the current one
+  struct {
+    bool valid = false;
+    uint64_t seed = 0, run_index = 0;
+    int R = 0;
+    unsigned long long epoch = 0;
+    std::vector<double> image, chain0, mu0, cov0;
+    std::vector<int> slot_plan;          // a call of plans: the layout the image was built for
+  } ahead;
+
+  // ---- device state ----
+  pocs_rt::DevBuf d_env, d_sensor, d_hdr, d_chain, d_state, d_param, d_moments, d_partial;
+  pocs_rt::DevBuf d_sx, d_sy, d_st, d_flags, d_px, d_py, d_pt, d_hits, d_total, d_ticket, d_tables;
+  pocs_rt::DevBuf d_runplan;             // a call of plans: [R][4] start mean and steps per run (the MC kernels)
+  pocs_rt::DevBuf d_surv;                // a call of plans under a risk bound: [R] running survival product of every run
+  pocs_rt::DevBuf d_tparent;             // a tree of plans: [T] int, the slot of every slot's parent
+  // one-hop exchange (pocs_xchg_*): this rank's buffer, the peers' buffers as mapped here
+  void* xchg_own = nullptr;
+  void* xchg_peer[POCS_XCHG_MAX_WORLD] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+  int xchg_world = 0, xchg_rank = -1;
+  bool xchg_connected = false;
+  unsigned long long xchg_calls = 0;     // begin/end sequences so far: part of every row's epoch
+  double* ext_moments = nullptr;         // caller-owned moments buffer (multi-GPU), or null
+  long long ext_moments_len = 0;
+  void* h_pin = nullptr;                 // pinned staging: hdr | chain | state0 | moments | total
+  size_t h_pin_cap = 0;
+  void* h_copy = nullptr;                // pinned staging of the audit copies (pocs_copy_*, pocs_get_gmm_state): device data
+                                         // reaches caller memory through it, in pieces of POCS_COPY_CHUNK bytes
+  bool env_dirty = true, sensor_dirty = true;
+
+  hipGraphExec_t graph_gmm = nullptr, graph_mc = nullptr;
+  const void* graph_baked[3] = {nullptr, nullptr, nullptr};   // diagnostic build only (POCS_GRAPH_WITH_COPIES)
+  std::string graph_gmm_key, graph_mc_key;
+
+  std::vector<hipEvent_t> events;
+  double prof_ms = 0.0;
+  long long prof_launches = 0;
+
+  pocs_rt::Results res;                  // ---- results of the last run ----
+  int last_gmm_adv = -1;                 // last waypoint whose mixture has been built (step API)
+  bool gmm_open = false;
+};
+
+namespace pocs_rt POCS_HIDDEN {
+
+inline int fail(pocs_ctx* c, int code, const char* fmt, ...) {
+  char buf[512];
+  va_list ap;
+  va_start(ap, fmt);
+  vsnprintf(buf, sizeof buf, fmt, ap);
+  va_end(ap);
+  if (c) c->err = buf;
+  return code;
+}
+
+#define HIPCHK(c, call)                                                                   \
+  do {                                                                                    \
+    hipError_t e_ = (call);                                                               \
+    if (e_ != hipSuccess)                                                                 \
+      return fail((c), POCS_E_DEVICE, "%s failed: %s (%s:%d)", #call, hipGetErrorString(e_), \
+                  __FILE__, __LINE__);                                                    \
+  } while (0)
+
+inline void drop_graphs(pocs_ctx* c) {
+  if (c->graph_gmm) { hipGraphExecDestroy(c->graph_gmm); c->graph_gmm = nullptr; }
+  if (c->graph_mc) { hipGraphExecDestroy(c->graph_mc); c->graph_mc = nullptr; }
+  c->graph_gmm_key.clear();
+  c->graph_mc_key.clear();
+}
+
+// Grow a device buffer.  The captured graphs bake device pointers in (d_hdr and d_chain are shared
+// by the GMM and the MC graph), so replacing ANY buffer drops both of them: the next run captures
+// again against the new pointers.
+inline int ensure(pocs_ctx* c, DevBuf& b, size_t bytes) {
+  if (bytes == 0) bytes = 16;
+  if (b.cap >= bytes) return POCS_OK;
+  if (b.p) {
+    HIPCHK(c, hipStreamSynchronize(c->stream));      // nothing queued may still use the old buffer
+    drop_graphs(c);
+    HIPCHK(c, hipFree(b.p)); b.p = nullptr; b.cap = 0;
+  }
+  HIPCHK(c, hipMalloc(&b.p, bytes));
+  b.cap = bytes;
+  return POCS_OK;
+}
+
+// Run-ahead bookkeeping.  A setter (or any other launch) ends the serving of cached runs: the
+// context's run counter goes back to just after the last run that was handed out, so the sequence
+// of seeds the caller sees is the one it would have seen one run per launch.
+inline void ra_drop(pocs_ctx* c) {
+  if (c->ra_have > 0) c->run_index = c->res.batch_base + (uint64_t)c->res.view + 1;
+  c->ra_have = 0;
+}
+inline void touch(pocs_ctx* c) { ra_drop(c); c->epoch++; }
+
+// The one place that clears the results of the last call.  clear(), not = {}: a planner sets new plans before every call, and
+// the calls' assign / resize then find their buffers still allocated.
+inline void reset_results(pocs_ctx* c) {
+  Results& r = c->res;
+  r.last_kind = 0; r.batch_base = 0; r.batch_R = c->batch; r.view = 0;
+  r.h_chain.clear(); r.h_mu.clear(); r.h_cov.clear();
+  r.probs.clear(); r.batch_probs.clear(); r.mc_counts.clear(); r.last_moments.clear(); r.batch_moments.clear();
+  r.last_gmm_count = 0; r.last_mc_count = 0; r.last_gmm_wp = -1;
+  r.plan_slot[0].clear(); r.plan_slot[1].clear(); r.plan_E.clear();
+  r.mc_wp.clear(); r.mc_wp_W = 0; r.plan_E_mc.clear();
+  r.tree_last = 0; r.tree_sel = 0; r.tree_mc_half = 0;
+  r.tree_probs.clear(); r.tree_eval.clear(); r.tree_F.clear(); r.tree_C.clear();
+}
+
+inline double* moments_dev(pocs_ctx* c) { return c->ext_moments ? c->ext_moments : (double*)c->d_moments.p; }
+inline long long sample_stride_of(long long count) { return count > 0 ? ((count + 1) & ~1LL) : 2; }   // even
+inline uint64_t seed_of_run(const pocs_ctx* c, uint64_t run) { return c->seed + 0x9E3779B97F4A7C15ull * run; }
+
+// ---- pocs_stage.hip ----
+// One plan as the host chain and the initial mixture read it: trajectory 3 x W and odometry 3 x (W-1), by component.
+struct PlanView { const double* traj; const double* odom; int W; };
+PlanView plan_view(const pocs_ctx* c, int p);          // p < 0: the single plan (pocs_set_trajectory / pocs_set_odometry)
+void compute_chain(pocs_ctx* c, uint64_t seed, const PlanView& pv);
+// pinned staging layout (doubles): [0 .. 2R) run headers, then R chains, then R initial mixtures, (a call of plans:
+// then R rows of start mean and steps), then the moments [W][R][K*11], then the MC total
+struct PinLayout { size_t chain, state0, runplan, moments, total, end; };
+PinLayout pin_layout(const pocs_ctx* c);
+int ensure_pin(pocs_ctx* c);
+std::vector<int> plan_layout(const pocs_ctx* c, int G);
+std::vector<int> slot_lengths(const pocs_ctx* c, const std::vector<int>& slot_plan);
+int live_runs(const std::vector<int>& Ws, int lo, int hi, int w);
+uint64_t plan_run(const pocs_ctx* c, int p);
+void prefetch_next_batch(pocs_ctx* c, int groups);
+int stage_and_upload_runs(pocs_ctx* c, int groups, int kind);
+
+// ---- pocs_host.hip ----
+int upload_tables(pocs_ctx* c);
+size_t sync_xwait_offset(const pocs_ctx* c);
+void gmm_select_view(pocs_ctx* c, int v);
+void tree_select_gmm(pocs_ctx* c, int n);
+int run_gmm_full(pocs_ctx* c, double* probability);
+int run_mc_local(pocs_ctx* c);
+
+}  // namespace pocs_rt

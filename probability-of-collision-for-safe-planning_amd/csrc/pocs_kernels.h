@@ -1,4 +1,4 @@
-// pocs_kernels.h -- launch interface between the host runtime (pocs_host.hip) and the gfx950
+// pocs_kernels.h -- launch interface between the host runtime (pocs_host.hip, pocs_ctx.hpp) and the gfx950
 // kernels (pocs_kernels.hip).  Internal; the public boundary is include/pocs.h.
 #pragma once
 #include <hip/hip_runtime.h>

@@ -4,7 +4,7 @@
 // /root/reference/mcsimplugin/).  3x3 matrices are row-major double[9].  Matrix products keep
 // the reference's association, (A*B)*C, and a left-to-right inner sum; no operation is
 // contracted (the TU is built with -ffp-contract=off and these use no fma on purpose).
-// Used by: the host chain (pocs_host.hip) and the per-component device update inside
+// Used by: the host chain (pocs_stage.hip) and the per-component device update inside
 // mixture advance of k_gmm_step / k_gmm_advance (pocs_kernels.hip).
 #pragma once
 #include "pocs_math.h"

@@ -11,7 +11,7 @@ if [ "$1" = "--build-base" ]; then
   git archive $rev $S include | tar -x -C $tmp
   mkdir -p ab_build
   hipcc -O3 --offload-arch=gfx950 -std=c++17 -fPIC -shared -ffp-contract=off -Wno-unused-value \
-    $tmp/$S/pocs_kernels.hip $tmp/$S/pocs_host.hip -o ab_build/libpocs_base.so
+    $tmp/$S/*.hip -o ab_build/libpocs_base.so
   rm -rf $tmp
   echo "built ab_build/libpocs_base.so from $rev"
   exit 0

@@ -8,7 +8,7 @@ cd "$(dirname "$0")/.."
 S=probability-of-collision-for-safe-planning_amd/csrc
 mkdir -p ab_build
 what=${1:-all}
-cc() { hipcc -O3 --offload-arch=gfx950 -std=c++17 -fPIC -shared -ffp-contract=off -Wno-unused-value -DPOCS_TUNING "$@" $S/pocs_kernels.hip $S/pocs_host.hip; }
+cc() { hipcc -O3 --offload-arch=gfx950 -std=c++17 -fPIC -shared -ffp-contract=off -Wno-unused-value -DPOCS_TUNING "$@" $S/*.hip; }
 if [ $what = stamps ] || [ $what = all ]; then
   cc -DPOCS_STAMPS -o ab_build/libpocs_stamps.so 2>/dev/null; echo built ab_build/libpocs_stamps.so
 fi

@@ -5,7 +5,7 @@ S=probability-of-collision-for-safe-planning_amd/csrc
 for vs in 128 64; do
   rm -rf /tmp/vs$vs; mkdir -p /tmp/vs$vs/$S /tmp/vs$vs/include; cp $S/*.h $S/*.hpp $S/*.hip /tmp/vs$vs/$S/; cp include/*.h /tmp/vs$vs/include/
   sed -i "s/#define POCS_GMM_MAX_VS 256/#define POCS_GMM_MAX_VS $vs/; s/POCS_GMM_MAX_VS == 256/POCS_GMM_MAX_VS == $vs/" /tmp/vs$vs/$S/pocs_kernels.h
-  hipcc -O3 --offload-arch=gfx950 -std=c++17 -fPIC -shared -ffp-contract=off -Wno-unused-value /tmp/vs$vs/$S/pocs_kernels.hip /tmp/vs$vs/$S/pocs_host.hip -o ab_build/libpocs_vs$vs.so 2>/dev/null || { echo "build vs$vs failed"; exit 1; }
+  hipcc -O3 --offload-arch=gfx950 -std=c++17 -fPIC -shared -ffp-contract=off -Wno-unused-value /tmp/vs$vs/$S/*.hip -o ab_build/libpocs_vs$vs.so 2>/dev/null || { echo "build vs$vs failed"; exit 1; }
 done
 line() { python -c "import json,sys; d=json.loads(sys.stdin.read()); r=d['roofline']; print('$1: value %.4g ms/step %.4f period %.1f us frac %.3f' % (d['value'], d['ms_per_step'], r['avg_kernel_us'], r['frac']))"; }
 {
