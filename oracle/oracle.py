@@ -269,7 +269,7 @@ class Oracle:
         """run_gmm as `world` ranks compute it through the library's exchange: rank r evaluates its shard
         parallel.shard_range(N, r, world) in the shard's own summation tree (gmm_waypoint), and every waypoint's
         shard sums are added in rank order -- tot = 0.0; tot += m_0; ... tot += m_{world-1}, as the exchange's
-        closer adds the slots (pocs_kernels.hip, gmm_exchange_rows) -- before the next mixture is built from them.
+        closer adds the slots (pocs_dev_advance.hpp, gmm_exchange_rows) -- before the next mixture is built from them.
         world = 1 is run_gmm bit for bit.  Returns the same dict (no samples); "shards" holds the (first, count)s."""
         from importlib import import_module
         import sys

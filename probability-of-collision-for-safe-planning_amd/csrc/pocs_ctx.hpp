@@ -6,7 +6,7 @@
 //   pocs_api.hip     context life cycle, setters, getters, run-ahead front, text dispatcher
 //   pocs_audit.hip   read-backs of device state for tests and audits, bandwidth and device-math probes, timing getters
 //
-// Host only: none of these units holds a kernel (pocs_kernels.hip does).
+// Host only: none of these units holds a kernel (pocs_kernels.hip does, with its parts pocs_dev_*.hpp).
 #pragma once
 #include <hip/hip_runtime.h>
 

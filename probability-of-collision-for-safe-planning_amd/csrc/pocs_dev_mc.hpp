@@ -1,0 +1,310 @@
+// pocs_dev_mc.hpp -- the Monte-Carlo family, a part of pocs_kernels.hip (the only unit with device code; included there,
+// inside its anonymous namespace).  Relies on pocs_dev_prims.hpp (wave_sum_u32, requests_issued) and on pocs_math.h /
+// pocs_collide.h; nothing of the GMM parts.
+//
+//   k_mc_init       P2+P3     initParticles (MCSimulator.h:287-297) + first checkParticleCollisions (:333-347)
+//   k_mc_step       P1+P3     moveParticles (:300-322) + checkParticleCollisions, one waypoint, particles streamed through
+//                             HBM (SoA): 24 B in, 24 B out, u32 RMW; k_mc_step_counts: with first collisions / the stop
+//   k_mc_fused      P1+P3     same arithmetic, whole roll-out in registers (the controls do not depend on the particles,
+//                             SURVEY 3.2), 0 B per evaluation; k_mc_fused_counts
+//   k_mc_tree_step  P1+P3     one level of a tree of plans: the parent's particles moved into the node's place
+//   k_mc_count      P3        getCollisionProportion (:324-330): |{hits > 0}|.
+//
+// Each of these exists once: the block head (stage_mc_head -> mc_head -> mc_world), the initial draw (mc_initial), the motion
+// step (mc_move), the particle accessors (mc_load / mc_store) and the block sum of counts (mc_block_add).
+
+// what a thread keeps of the head behind the barrier: footprint and M in registers, obstacle records and tables where they are
+struct mc_world {
+  const double* obs;
+  const pocs_tables* tab;
+  pocs_footprint fp;
+  int M;
+};
+// Where the head lies in LDS.  world() -- the copies of footprint and M out of LDS -- is a step of its own, which the kernels
+// take BEHIND their run's pointers (mc_view): taken in stage_mc_head, the same instructions come out in another order.
+struct mc_head {
+  const double* obs;
+  const pocs_tables* tab;
+  const pocs_footprint* fp;
+  const int* M;
+  __device__ __forceinline__ mc_world world() const { return {obs, tab, *fp, *M}; }
+};
+// The head of an MC block (POCS_BLOCK threads): the collision world (obstacle records, footprint, M) and the 4 KB sector table --
+// the MC kernels only evaluate the footprint heading -- into LDS, ending in the block's barrier.  Every load is issued before
+// the first is waited for: written as copy loops with the block size as their stride, the compiler kept them loops of load -
+// wait - store, four dependent memory round trips in front of every block's first particle.  (The obstacle array has its
+// full size whatever M is: all of it is requested, M need not be known first.)
+__device__ __forceinline__ mc_head stage_mc_head(const pocs_env_dev* __restrict__ env, const pocs_tables* __restrict__ g) {
+  __shared__ double s_obs[POCS_MAX_OBSTACLES * POCS_OBS_STRIDE];
+  __shared__ pocs_footprint s_fp;
+  __shared__ int s_M;
+  __shared__ pocs_tables s_tab;
+  constexpr int NO = POCS_MAX_OBSTACLES * POCS_OBS_STRIDE, NS = (int)(sizeof(g->sc) / sizeof(double));
+  constexpr int UO = (NO + POCS_BLOCK - 1) / POCS_BLOCK, US = (NS + POCS_BLOCK - 1) / POCS_BLOCK;
+  const int tid = threadIdx.x;
+  const double* src = &g->sc[0][0];
+  double vo[UO], vs[US];
+#pragma unroll
+  for (int u = 0; u < UO; ++u) { const int i = tid + u * POCS_BLOCK; vo[u] = i < NO ? env->obs[i] : 0.0; }
+#pragma unroll
+  for (int u = 0; u < US; ++u) { const int i = tid + u * POCS_BLOCK; vs[u] = i < NS ? src[i] : 0.0; }
+  const pocs_footprint fp = env->fp;
+  const int M = env->M;
+  requests_issued();
+  double* dst = &s_tab.sc[0][0];
+#pragma unroll
+  for (int u = 0; u < UO; ++u) { const int i = tid + u * POCS_BLOCK; if (i < NO) s_obs[i] = vo[u]; }
+#pragma unroll
+  for (int u = 0; u < US; ++u) { const int i = tid + u * POCS_BLOCK; if (i < NS) dst[i] = vs[u]; }
+  if (tid == 0) { s_fp = fp; s_M = M; }
+  __syncthreads();
+  return {s_obs, &s_tab, &s_fp, &s_M};
+}
+
+// MC kernels: blockIdx.y = run of the batch (its own seed, its own noisy controls, its own slice
+// of the particle arrays).
+struct mc_run_view {
+  uint64_t seed;
+  const double* chain;
+  double* x; double* y; double* th;
+  uint32_t* hits;
+};
+__device__ __forceinline__ mc_run_view mc_view(const pocs_mc_launch& a) {
+  const int r = blockIdx.y;
+  const size_t o = (size_t)r * (size_t)a.stride;
+  mc_run_view v;
+  v.seed = a.hdr[r].seed;
+  v.chain = a.chain + (size_t)r * (a.W > 1 ? a.W - 1 : 1) * POCS_CHAIN_STRIDE;
+  v.x = a.x + o; v.y = a.y + o; v.th = a.th + o; v.hits = a.hits + o;
+  return v;
+}
+
+// Where run blockIdx.y starts and how many controls it drives (k_mc_fused): the launch's mu0 / step, or -- a call of
+// plans -- its own plan's start and length (pocs_mc_launch::run_plan).
+struct mc_run_start {
+  double mu[3];
+  int steps;
+};
+__device__ __forceinline__ mc_run_start mc_start(const pocs_mc_launch& a) {
+  mc_run_start s;
+  if (a.run_plan) {
+    const double* q = a.run_plan + 4 * (size_t)blockIdx.y;
+    s.mu[0] = q[0]; s.mu[1] = q[1]; s.mu[2] = q[2];
+    s.steps = (int)q[3];
+  } else {
+    s.mu[0] = a.mu0[0]; s.mu[1] = a.mu0[1]; s.mu[2] = a.mu0[2];
+    s.steps = a.step;
+  }
+  return s;
+}
+
+// First collisions per waypoint (POCS_OPT_MC_WAYPOINT_COUNTS, POCS_OPT_MC_RISK_BOUND).  The MC kernels have one body each,
+// instantiated by MODE: MC_PLAIN is the kernel as it has always been (k_mc_init, k_mc_step, k_mc_fused: not one instruction
+// more), MC_COUNTS also adds to wp_counts[run][w] the particles that collide at waypoint w and at no waypoint before it,
+// MC_STOP (k_mc_step only) also obeys the risk bound.  A particle's first collision is read off the hit counter the kernel
+// holds anyway (old == 0).  Integer counts added with integer atomics: exact, whatever the grid and the shard partition.
+enum { MC_PLAIN = 0, MC_COUNTS = 1, MC_STOP = 2 };
+
+// A block's sum of counts -> dst[at]: every thread's own count, one wave sum, one word per wave in LDS, one atomic per block
+// (integer: order independent, exact) and none when the sum is 0.  Every thread of the block arrives (behind its particle
+// loop).  dst[at] is addressed by thread 0 alone, behind the barrier.
+__device__ __forceinline__ void mc_block_add(unsigned c, unsigned long long* dst, size_t at = 0) {
+  __shared__ unsigned s_c[POCS_BLOCK / 64];
+  c = wave_sum_u32(c);
+  if ((threadIdx.x & 63) == 0) s_c[threadIdx.x >> 6] = c;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    unsigned long long t = 0;
+    for (int w = 0; w < POCS_BLOCK / 64; ++w) t += s_c[w];
+    if (t) atomicAdd(&dst[at], t);
+  }
+}
+
+// The lanes of a wave that are in the particle loop together: those with a first collision at this waypoint, counted by
+// ballot, added by the first of them.
+__device__ __forceinline__ void mc_wave_first_hits(bool first, unsigned long long* dst) {
+  const unsigned long long m = __ballot(first);
+  if (m != 0ull && (threadIdx.x & 63) == (unsigned)__builtin_ctzll(m)) atomicAdd(dst, (unsigned long long)__popcll(m));
+}
+
+// MC_STOP, the head of every block of the launch of control s: is the run stopped?  The run stops at the FIRST waypoint s
+// whose cumulative count C[s] = F[0] + ... + F[s] has (double)C[s] / (double)N >= bound.  F[0..s] were completed by the
+// EARLIER launches of the graph (control s - 1 wrote F[s]); this launch adds to F[s + 1] only, which nobody reads here: all
+// blocks of the run see the same numbers and decide alike.  A stopped run's particles stay where they are, so its later
+// launches find F[s + 1 ...] = 0, the same C and the same answer -- no block reads a word that a block of its own launch
+// writes.  Block 0 of the launch that finds the bound reached for the first time (C[s - 1] was below it) reports s + 1 in the
+// run's stop word, which only the host reads.
+__device__ __forceinline__ bool mc_run_stopped(const pocs_mc_launch& a) {
+  __shared__ unsigned long long s_c[POCS_BLOCK / 64];
+  const int r = blockIdx.y, s = a.step;
+  const unsigned long long* F = a.wp_counts + (size_t)r * (size_t)a.W;
+  unsigned long long part = 0;
+  for (int w = threadIdx.x; w <= s; w += POCS_BLOCK) part += F[w];
+  // (a wave sum of 64-bit counts out of 32-bit ones: three pieces of 22 bits, 64 of which cannot overflow)
+  const unsigned long long c = (unsigned long long)wave_sum_u32((unsigned)(part & 0x3FFFFFull)) +
+                               ((unsigned long long)wave_sum_u32((unsigned)((part >> 22) & 0x3FFFFFull)) << 22) +
+                               ((unsigned long long)wave_sum_u32((unsigned)(part >> 44)) << 44);
+  if ((threadIdx.x & 63) == 0) s_c[threadIdx.x >> 6] = c;
+  __syncthreads();
+  unsigned long long C = 0;
+  for (int w = 0; w < POCS_BLOCK / 64; ++w) C += s_c[w];
+  const double n = (double)a.wp_n;
+  const bool stopped = (double)C / n >= a.wp_bound;
+  if (stopped && blockIdx.x == 0 && threadIdx.x == 0) {
+    const unsigned long long before = C - F[s];          // C[s - 1] (0 for s = 0: waypoint 0 is always evaluated)
+    if (!((double)before / n >= a.wp_bound)) a.wp_stop[r] = (unsigned)s + 1u;
+  }
+  return stopped;
+}
+
+// Particle i of a run at waypoint 0: mu + L0 z, z its own three normals (initParticles).  The pose comes back through
+// references, as mc_move's does: returned as a record, the compiler ordered the callers' instructions differently.
+__device__ __forceinline__ void mc_initial(const pocs_mc_launch& a, uint64_t seed, long long i, const mc_run_start& st,
+                                           double& x, double& y, double& t) {
+  double z[3];
+  uint32_t spare;
+  pocs_normal3(seed, (uint64_t)(a.first + i), 0u, POCS_STREAM_MCINIT, z, &spare);
+  x = fma(a.L0[0], z[0], st.mu[0]);
+  y = fma(a.L0[2], z[1], fma(a.L0[1], z[0], st.mu[1]));
+  t = fma(a.L0[5], z[2], fma(a.L0[4], z[1], fma(a.L0[3], z[0], st.mu[2])));
+}
+
+// The motion model (moveParticles): the pose (x, y, t) driven by the noisy control (u0, u1, u2) -- turn, drive, turn.  The new
+// pose may be written over the old one (k_mc_fused).
+__device__ __forceinline__ void mc_move(const double x, const double y, const double t, const double u0, const double u1,
+                                        const double u2, double& nx, double& ny, double& nt) {
+  double sn, cs;
+  pocs_sincos(t + u0, &sn, &cs);
+  nx = fma(u1, cs, x);
+  ny = fma(u1, sn, y);
+  nt = pocs_wrap_angle(t + u0 + u2);
+}
+
+template <int MODE>
+__global__ __launch_bounds__(POCS_BLOCK) void k_mc_init(pocs_mc_launch a) {
+  const mc_head hd = stage_mc_head(a.env, a.tables);
+  const mc_run_view v = mc_view(a);
+  const mc_world wd = hd.world();
+  const mc_run_start st = mc_start(a);
+  unsigned first = 0;                              // this thread's particles that collide at waypoint 0 (unused: MC_PLAIN)
+  const long long stride = (long long)gridDim.x * POCS_BLOCK;
+  for (long long i = (long long)blockIdx.x * POCS_BLOCK + threadIdx.x; i < a.count; i += stride) {
+    double x, y, t;
+    mc_initial(a, v.seed, i, st, x, y, t);
+    v.x[i] = x; v.y[i] = y; v.th[i] = t;
+    const unsigned h = pocs_pose_collides(x, y, t, &wd.fp, wd.obs, wd.M, wd.tab) ? 1u : 0u;
+    v.hits[i] = h;
+    first += h;
+  }
+  if (MODE != MC_PLAIN) mc_block_add(first, a.wp_counts + (size_t)blockIdx.y * (size_t)a.W);      // waypoint 0
+}
+
+// A particle's words in HBM.  NT: non-temporal accesses, chosen by the host when the particle state of the batch does not
+// fit the 256 MB Infinity Cache anyway (the stream then runs faster past the caches; when it does fit, plain accesses keep
+// it there between waypoint launches).
+template <bool NT, typename T> __device__ __forceinline__ T mc_load(const T* p) { return NT ? __builtin_nontemporal_load(p) : *p; }
+template <bool NT, typename T> __device__ __forceinline__ void mc_store(const T v, T* p) { if (NT) __builtin_nontemporal_store(v, p); else *p = v; }
+
+// One particle per thread and iteration: a two-particle version with 16-byte accesses measured 12 % slower in cache, 7 %
+// faster out of it.
+template <bool NT, int MODE>
+__device__ __forceinline__ void mc_step_body(const pocs_mc_launch& a) {
+  if (MODE == MC_STOP) { if (mc_run_stopped(a)) return; }      // (the same answer in every thread of the block)
+  const mc_head hd = stage_mc_head(a.env, a.tables);
+  const mc_run_view v = mc_view(a);
+  const mc_world wd = hd.world();
+  const double* u = v.chain + (size_t)a.step * POCS_CHAIN_STRIDE + 6;
+  const double u0 = u[0], u1 = u[1], u2 = u[2];
+  unsigned first = 0;                              // this thread's particles whose first collision is this waypoint (unused: MC_PLAIN)
+  const long long stride = (long long)gridDim.x * POCS_BLOCK;
+  for (long long i = (long long)blockIdx.x * POCS_BLOCK + threadIdx.x; i < a.count; i += stride) {
+    const double x = mc_load<NT>(v.x + i), y = mc_load<NT>(v.y + i), t = mc_load<NT>(v.th + i);
+    double nx, ny, nt;
+    mc_move(x, y, t, u0, u1, u2, nx, ny, nt);
+    mc_store<NT>(nx, v.x + i); mc_store<NT>(ny, v.y + i); mc_store<NT>(nt, v.th + i);
+    if (pocs_pose_collides(nx, ny, nt, &wd.fp, wd.obs, wd.M, wd.tab)) {
+      const uint32_t old = v.hits[i];                // the counter is in hand exactly when the particle collides
+      v.hits[i] = old + 1u;
+      first += old == 0u ? 1u : 0u;
+    }
+  }
+  if (MODE != MC_PLAIN) mc_block_add(first, a.wp_counts + (size_t)blockIdx.y * (size_t)a.W + (size_t)a.step + 1);   // control s -> waypoint s + 1
+}
+template <bool NT>
+__global__ __launch_bounds__(POCS_BLOCK) void k_mc_step(pocs_mc_launch a) { mc_step_body<NT, MC_PLAIN>(a); }
+template <bool NT, int MODE>
+__global__ __launch_bounds__(POCS_BLOCK) void k_mc_step_counts(pocs_mc_launch a) { mc_step_body<NT, MODE>(a); }
+
+// MC_COUNTS: a particle has at most one first collision, so per step a wave ballots them and one lane adds the wave's count,
+// only when there is one (no block-level sum: the blocks of a fused launch never meet between steps).
+template <int MODE>
+__device__ __forceinline__ void mc_fused_body(const pocs_mc_launch& a) {
+  const mc_head hd = stage_mc_head(a.env, a.tables);
+  const mc_run_view v = mc_view(a);
+  const mc_world wd = hd.world();
+  const mc_run_start st = mc_start(a);             // (its steps: uniform per block, blockIdx.y being the run)
+  unsigned long long* wp = MODE != MC_PLAIN ? a.wp_counts + (size_t)blockIdx.y * (size_t)a.W : nullptr;
+  const long long stride = (long long)gridDim.x * POCS_BLOCK;
+  for (long long i = (long long)blockIdx.x * POCS_BLOCK + threadIdx.x; i < a.count; i += stride) {
+    double x, y, t;
+    mc_initial(a, v.seed, i, st, x, y, t);
+    unsigned h = pocs_pose_collides(x, y, t, &wd.fp, wd.obs, wd.M, wd.tab) ? 1u : 0u;
+    if (MODE != MC_PLAIN) mc_wave_first_hits(h != 0u, wp);
+    for (int s = 0; s < st.steps; ++s) {
+      const double* u = v.chain + (size_t)s * POCS_CHAIN_STRIDE + 6;   // wave-uniform
+      const double u0 = u[0], u1 = u[1], u2 = u[2];
+      mc_move(x, y, t, u0, u1, u2, x, y, t);
+      const bool hit = pocs_pose_collides(x, y, t, &wd.fp, wd.obs, wd.M, wd.tab);
+      if (MODE != MC_PLAIN) mc_wave_first_hits(hit && h == 0u, wp + s + 1);
+      h += hit ? 1u : 0u;
+    }
+    v.x[i] = x; v.y[i] = y; v.th[i] = t;
+    v.hits[i] = h;
+  }
+}
+__global__ __launch_bounds__(POCS_BLOCK) void k_mc_fused(pocs_mc_launch a) { mc_fused_body<MC_PLAIN>(a); }
+__global__ __launch_bounds__(POCS_BLOCK) void k_mc_fused_counts(pocs_mc_launch a) { mc_fused_body<MC_COUNTS>(a); }
+
+// A tree of plans (pocs_set_plan_tree), one launch per level (at most 256 nodes per launch): blockIdx.y = node of the launch,
+// slot r = tree_lo + blockIdx.y.  The node's particles are its PARENT's, moved by the noisy control of the edge into the node
+// (chain[r], one record per node) -- mc_step_body's arithmetic -- read from the parent's place in the previous level's half of
+// the particle buffers and written to the node's place in this level's half: source != destination, two levels live at a
+// time.  Counted per node: the particles whose FIRST collision on the path root -> node is at the node (wp_counts[r]) and
+// those that have collided at or before it (total[r]); integer atomics, exact whatever the grid.
+template <bool NT>
+__global__ __launch_bounds__(POCS_BLOCK) void k_mc_tree_step(pocs_mc_launch a) {
+  const mc_head hd = stage_mc_head(a.env, a.tables);
+  const int r = a.tree_lo + (int)blockIdx.y, pr = a.tree_parent[r];
+  const size_t so = (size_t)(pr - a.tree_src_lo) * (size_t)a.stride, dso = (size_t)(r - a.tree_dst_lo) * (size_t)a.stride;
+  const double* sx = a.tree_sx + so; const double* sy = a.tree_sy + so; const double* st = a.tree_sth + so;
+  const uint32_t* sh = a.tree_shits + so;
+  double* dx = a.x + dso; double* dy = a.y + dso; double* dt = a.th + dso;
+  uint32_t* dh = a.hits + dso;
+  const mc_world wd = hd.world();
+  const double* u = a.chain + (size_t)r * POCS_CHAIN_STRIDE + 6;
+  const double u0 = u[0], u1 = u[1], u2 = u[2];
+  unsigned first = 0, coll = 0;
+  const long long stride = (long long)gridDim.x * POCS_BLOCK;
+  for (long long i = (long long)blockIdx.x * POCS_BLOCK + threadIdx.x; i < a.count; i += stride) {
+    const double x = mc_load<NT>(sx + i), y = mc_load<NT>(sy + i), t = mc_load<NT>(st + i);
+    const uint32_t old = mc_load<NT>(sh + i);
+    double nx, ny, nt;
+    mc_move(x, y, t, u0, u1, u2, nx, ny, nt);
+    const uint32_t h = old + (pocs_pose_collides(nx, ny, nt, &wd.fp, wd.obs, wd.M, wd.tab) ? 1u : 0u);
+    mc_store<NT>(nx, dx + i); mc_store<NT>(ny, dy + i); mc_store<NT>(nt, dt + i); mc_store<NT>(h, dh + i);
+    first += (old == 0u && h != 0u) ? 1u : 0u;
+    coll += h != 0u ? 1u : 0u;
+  }
+  mc_block_add(first, a.wp_counts + r);
+  __syncthreads();                                   // (mc_block_add's scratch is read by thread 0 of the call above)
+  mc_block_add(coll, a.total + r);
+}
+
+__global__ __launch_bounds__(POCS_BLOCK) void k_mc_count(pocs_mc_launch a) {
+  const mc_run_view v = mc_view(a);
+  unsigned c = 0;
+  const long long stride = (long long)gridDim.x * POCS_BLOCK;
+  for (long long i = (long long)blockIdx.x * POCS_BLOCK + threadIdx.x; i < a.count; i += stride)
+    c += v.hits[i] > 0u ? 1u : 0u;
+  mc_block_add(c, a.total, blockIdx.y);
+}

@@ -193,7 +193,7 @@ int gmm_prepare(pocs_ctx* c) {
   return ensure_pin(c);
 }
 
-// Sub-batches of a whole-run call.  The moment sums do not depend on the launch shape (pocs_kernels.hip,
+// Sub-batches of a whole-run call.  The moment sums do not depend on the launch shape (pocs_dev_gmm.hpp,
 // "summation tree"), so a split changes no bit of any result.  TWO sub-batches on two streams by default where a call
 // has the work for it (round 4, measured on MI355X with numerics v8, 10^6 samples, K = 3, one box, three alternations and
 // a sweep, profiles/r04_sub_batches.txt): while one sub-batch is in the tail of its waypoint -- the slow end of its last

@@ -1,5 +1,6 @@
 // pocs_kernels.h -- launch interface between the host runtime (pocs_host.hip, pocs_ctx.hpp) and the gfx950
-// kernels (pocs_kernels.hip).  Internal; the public boundary is include/pocs.h.
+// kernels (pocs_kernels.hip: the pocs_launch_* functions; the kernels themselves in its parts pocs_dev_prims.hpp,
+// pocs_dev_advance.hpp, pocs_dev_gmm.hpp, pocs_dev_mc.hpp).  Internal; the public boundary is include/pocs.h.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -21,7 +22,7 @@
 // A run's chunks are cut into VS = 2^vs_shift VIRTUAL SLICES, slice j = chunks [j * chunks / VS,
 // (j + 1) * chunks / VS): VS depends on the shard's sample count only (the largest power of two <= min(256,
 // chunks)), never on how many runs share the launch -- the moment sums are defined on the virtual slices
-// (pocs_kernels.hip, "summation tree"), which is what makes a run's result independent of the batch.
+// (pocs_dev_gmm.hpp, "summation tree"), which is what makes a run's result independent of the batch.
 // The launch's work = the flat list of units t = r * VS + j; block b takes units [b * upb, (b + 1) * upb).
 #define POCS_GMM_MAX_VS 256
 // Block size and slice count are part of the NUMERICS (the summation tree is defined on chunks of 512 pairs, 64-lane

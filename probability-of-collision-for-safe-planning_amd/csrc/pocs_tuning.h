@@ -1,4 +1,4 @@
-// pocs_tuning.h -- diagnostic hooks of pocs_kernels.hip and the host units (pocs_host.hip, pocs_api.hip, pocs_audit.hip).  NOT part of the shipped library:
+// pocs_tuning.h -- diagnostic hooks of pocs_kernels.hip (included by its part pocs_dev_prims.hpp) and the host units (pocs_host.hip, pocs_api.hip, pocs_audit.hip).  NOT part of the shipped library:
 // included only when the translation units are compiled with -DPOCS_TUNING (tools/ablate.sh, tools/jobs/stamps.sh);
 // the default build defines the hooks below as no-ops / pass-throughs and sees none of this file.
 //
