@@ -346,6 +346,24 @@ int pocs_probe_device_math(pocs_ctx* ctx, int n, const uint32_t* radius_words, c
    and sin / cos of headings[i] as the footprint test evaluates them -- through the same inline functions, tables and pinned
    constants as k_gmm_step.  A free-running launch meets a given word once in 2^32 draws; this puts the edge words (0, the
    cells' boundaries, 2^32 - 1, a heading on a sector's tie) in front of the oracle directly (tests/test_gpu_parity.py). */
+int pocs_probe_device_collide(pocs_ctx* ctx, int K, const double* params, int n, const double* poses_xyt, int* flag_full, int* flag_pair,
+                              int* flag_pair_eager, int* nkeep, double* kept);
+/* TEST HOOK, no counterpart in the reference: the DEVICE's collision test and the obstacle cull of the GMM sampling kernel on
+   inputs the caller picks, against the collision world and footprint the context holds (pocs_set_obstacles / pocs_set_footprint;
+   nothing else need be configured).  params: the sampler parameters of a mixture of K components, K x 12 doubles (per component
+   mean[3], L00 L10 L11 L20 L21 L22 of the lower Cholesky factor, three unused); poses_xyt: n poses (x, y, theta), 1 <= n <= 2^20.
+   One block stages the world and the mixture as a block of the sampling kernel does and culls the obstacle table against the
+   mixture; then per pose i
+     flag_full[i]        the footprint test on the full table, as the MC kernels stage and call it,
+     flag_pair[i]        the two-pose form on the culled table (poses 2 j and 2 j + 1 one pair; an odd last pose is paired with
+                         itself and gets 2 added should its two slots disagree), as the batch form of the sampling kernel calls it,
+     flag_pair_eager[i]  the same in the form the kernel takes for a call of one run;
+   nkeep: the number of records the cull kept; kept: room for 64 x 8 doubles, the kept records in table order (centre, axis, half
+   extents, and the broad phase sized to the mixture's headings), zeros behind them.  A pose the mixture cannot draw may lose
+   its obstacle to the cull: flag_pair is the kernel's answer only for poses within the mixture's reach.  Puts the poses a
+   free-running launch never draws -- a few ulps from touching, at the edge of the mixture's reach -- in front of the oracle
+   (tests/test_collision_probe.py).  POCS_E_ARG for a null pointer, n or K out of range and ANY input that is not finite;
+   POCS_E_STATE for a context without a collision world. */
 int pocs_get_sequence_time(pocs_ctx* ctx, double* ms, int* concurrent);  /* POCS_OPT_PROFILE=1, whole-run GMM calls: first sampling launch -> end of the last one, and how many
                                                                             sub-batches of the call were in flight side by side (their launches overlap: DESIGN.md section 5) */
 

@@ -87,6 +87,8 @@ SIGNATURES = {
     "pocs_get_sequence_time": (C.c_int, [_vp, _dp, C.POINTER(C.c_int)]),
     "pocs_get_exchange_wait": (C.c_int, [_vp, _dp]),
     "pocs_probe_device_math": (C.c_int, [_vp, C.c_int, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), _dp, _dp, _dp, _dp, _dp, _dp]),
+    "pocs_probe_device_collide": (C.c_int, [_vp, C.c_int, _dp, C.c_int, _dp, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int),
+                                            C.POINTER(C.c_int), _dp]),
 }
 
 _lib = None
@@ -542,6 +544,21 @@ class Context:
         self._chk(self.lib.pocs_probe_device_math(self.h, n, wr.ctypes.data_as(u32), wa.ctypes.data_as(u32), x.ctypes.data_as(_dp),
                                                   *[o.ctypes.data_as(_dp) for o in out]))
         return tuple(out)
+
+    def probe_device_collide(self, params, poses):
+        """Test hook: the device's collision test and the sampling kernel's obstacle cull on chosen inputs, against the
+        context's world (set_env).  params: K x 12 sampler parameters of a mixture (mean[3], L00 L10 L11 L20 L21 L22, ...);
+        poses: n x 3 (x, y, theta).  -> (flag_full, flag_pair, flag_pair_eager: int32[n]; kept: nkeep x 8 records)."""
+        par = _arr(params).reshape(-1, 12)
+        xyt = _arr(poses).reshape(-1, 3)
+        K, n = par.shape[0], xyt.shape[0]
+        flags = [np.full(n, -1, dtype=np.int32) for _ in range(3)]
+        nkeep = C.c_int(-1)
+        kept = np.zeros((64, 8))
+        ip = C.POINTER(C.c_int)
+        self._chk(self.lib.pocs_probe_device_collide(self.h, K, par.ctypes.data_as(_dp), n, xyt.ctypes.data_as(_dp),
+                                                     *[f.ctypes.data_as(ip) for f in flags], C.byref(nkeep), kept.ctypes.data_as(_dp)))
+        return flags[0], flags[1], flags[2], kept[:nkeep.value].copy()
 
     def kernel_time(self):
         ms, n = C.c_double(), C.c_longlong()

@@ -199,6 +199,56 @@ int pocs_probe_device_math(pocs_ctx* c, int n, const uint32_t* radius_words, con
   return rc;
 }
 
+// Test hook: the device's collision test and obstacle cull on chosen poses and a chosen mixture (include/pocs.h).
+int pocs_probe_device_collide(pocs_ctx* c, int K, const double* params, int n, const double* poses, int* flag_full, int* flag_pair,
+                              int* flag_pair_eager, int* nkeep, double* kept) {
+  if (!c) return POCS_E_ARG;
+  if (!params || !poses || !flag_full || !flag_pair || !flag_pair_eager || !nkeep || !kept || n < 1 || n > (1 << 20) || K < 1 || K > POCS_MAX_GAUSSIANS)
+    return fail(c, POCS_E_ARG, "pocs_probe_device_collide: 1 <= n <= 2^20, 1 <= K <= %d, no null pointers", POCS_MAX_GAUSSIANS);
+  if (!c->have_obstacles)
+    return fail(c, POCS_E_STATE, "no collision world: pocs_set_obstacles / addObstacle / clearObstacles missing");
+  // (a heading that is not a number has no sector: nothing of the kind reaches the device)
+  const size_t PS = (size_t)K * POCS_PARAM_STRIDE;
+  for (size_t j = 0; j < PS; ++j)
+    if (!std::isfinite(params[j])) return fail(c, POCS_E_ARG, "pocs_probe_device_collide: parameter %zu is not finite", j);
+  for (size_t j = 0; j < 3 * (size_t)n; ++j)
+    if (!std::isfinite(poses[j])) return fail(c, POCS_E_ARG, "pocs_probe_device_collide: pose %zu is not finite", j / 3);
+  HIPCHK(c, hipSetDevice(c->device));
+  if (int r = upload_world(c)) return r;
+  // [par | x | y | th | kept] doubles, then [flags 3 n | nkeep] ints
+  const size_t nrec = (size_t)POCS_MAX_OBSTACLES * POCS_OBS_STRIDE, nd = PS + 3 * (size_t)n + nrec, ni = 3 * (size_t)n + 1;
+  std::vector<double> h(nd, 0.0);
+  memcpy(h.data(), params, PS * sizeof(double));
+  for (int i = 0; i < n; ++i)
+    for (int j = 0; j < 3; ++j) h[PS + (size_t)j * n + i] = poses[3 * (size_t)i + j];
+  char* buf = nullptr;
+  HIPCHK(c, hipMalloc((void**)&buf, nd * sizeof(double) + ni * sizeof(int)));
+  double* d_par = (double*)buf;
+  double *d_x = d_par + PS, *d_kept = d_x + 3 * (size_t)n;
+  int* d_flags = (int*)(d_kept + nrec);
+  pocs_gmm_launch a;
+  memset(&a, 0, sizeof a);
+  fill_gmm_world(c, &a);
+  a.param = d_par; a.W = 1; a.nruns = 1; a.run_cnt = 1;
+  std::vector<int> f(ni, 0);
+  int rc = POCS_OK;
+  if (hipMemcpy(buf, h.data(), nd * sizeof(double), hipMemcpyHostToDevice) != hipSuccess || hipMemset(d_flags, 0, ni * sizeof(int)) != hipSuccess)
+    rc = fail(c, POCS_E_DEVICE, "probe upload failed");
+  if (rc == POCS_OK && pocs_launch_probe_collide(K, a, n, d_x, d_x + n, d_x + 2 * (size_t)n, d_flags, d_flags + 3 * (size_t)n, d_kept, c->stream) != hipSuccess)
+    rc = fail(c, POCS_E_DEVICE, "probe launch failed");
+  if (rc == POCS_OK && hipStreamSynchronize(c->stream) != hipSuccess) rc = fail(c, POCS_E_DEVICE, "probe kernel failed");
+  if (rc == POCS_OK && (hipMemcpy(f.data(), d_flags, ni * sizeof(int), hipMemcpyDeviceToHost) != hipSuccess ||
+                        hipMemcpy(kept, d_kept, nrec * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess))
+    rc = fail(c, POCS_E_DEVICE, "probe download failed");
+  (void)hipFree(buf);
+  if (rc != POCS_OK) return rc;
+  memcpy(flag_full, f.data(), (size_t)n * sizeof(int));
+  memcpy(flag_pair, f.data() + n, (size_t)n * sizeof(int));
+  memcpy(flag_pair_eager, f.data() + 2 * (size_t)n, (size_t)n * sizeof(int));
+  *nkeep = f[3 * (size_t)n];
+  return POCS_OK;
+}
+
 int pocs_get_sequence_time(pocs_ctx* c, double* ms, int* concurrent) {
   if (!c) return POCS_E_ARG;
   if (ms) *ms = c->seq_ms;

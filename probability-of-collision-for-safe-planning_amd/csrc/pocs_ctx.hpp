@@ -276,6 +276,8 @@ int stage_and_upload_runs(pocs_ctx* c, int groups, int kind);
 
 // ---- pocs_host.hip ----
 int upload_tables(pocs_ctx* c);
+int upload_world(pocs_ctx* c);
+void fill_gmm_world(const pocs_ctx* c, pocs_gmm_launch* a);
 size_t sync_xwait_offset(const pocs_ctx* c);
 void gmm_select_view(pocs_ctx* c, int v);
 void tree_select_gmm(pocs_ctx* c, int n);

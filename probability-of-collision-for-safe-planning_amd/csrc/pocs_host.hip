@@ -73,7 +73,7 @@ int upload_tables(pocs_ctx* c) {               // log / sector tables of the num
   HIPCHK(c, hipMemcpy(c->d_tables.p, &T, sizeof T, hipMemcpyHostToDevice));
   return POCS_OK;
 }
-int upload_static(pocs_ctx* c) {
+int upload_world(pocs_ctx* c) {                // tables + the collision world (obstacle records, footprint)
   if (int r = upload_tables(c)) return r;
   if (c->env_dirty) {
     pocs_env_dev env;
@@ -86,6 +86,10 @@ int upload_static(pocs_ctx* c) {
     HIPCHK(c, hipMemcpy(c->d_env.p, &env, sizeof env, hipMemcpyHostToDevice));
     c->env_dirty = false;
   }
+  return POCS_OK;
+}
+int upload_static(pocs_ctx* c) {
+  if (int r = upload_world(c)) return r;
   if (c->sensor_dirty) {
     if (int r = ensure(c, c->d_sensor, sizeof(pocs_sensor))) return r;
     HIPCHK(c, hipMemcpy(c->d_sensor.p, &c->sensor, sizeof(pocs_sensor), hipMemcpyHostToDevice));
@@ -235,13 +239,21 @@ int gmm_upload_run(pocs_ctx* c) {
 // (pocs_gmm_sample_local / pocs_gmm_step_local) leave the shard's sums to the caller's exchange, whatever the context.
 bool whole_call_exchanges(const pocs_ctx* c) { return c->xchg_connected && c->shard_first >= 0 && !c->ext_moments; }
 
+// The collision world as a GMM launch carries it (upload_world has put it on the device): what the obstacle cull and the
+// collision test of k_gmm_step read -- and all that pocs_probe_device_collide's one-block launch reads besides its mixture.
+void fill_gmm_world(const pocs_ctx* c, pocs_gmm_launch* a) {
+  a->env = (const pocs_env_dev*)c->d_env.p;
+  a->tables = (const pocs_tables*)c->d_tables.p;
+  a->fp = c->fp; a->M = (int)(c->boxes.size() / 5);
+  a->fp_rr = sqrt(c->fp.hx * c->fp.hx + c->fp.hy * c->fp.hy); a->fp_phi = atan2(c->fp.hy, c->fp.hx);
+}
+
 void fill_gmm_launch(pocs_ctx* c, pocs_gmm_launch* a, long long first, long long count, int w,
                      int run_lo = 0, int run_cnt = -1, int groups = 1) {
   memset(a, 0, sizeof *a);
   if (run_cnt < 0) run_cnt = c->batch;
   a->hdr = (const pocs_run_header*)c->d_hdr.p;
-  a->env = (const pocs_env_dev*)c->d_env.p;
-  a->tables = (const pocs_tables*)c->d_tables.p;
+  fill_gmm_world(c, a);
   a->chain = (const double*)c->d_chain.p;
   a->sensor = (const pocs_sensor*)c->d_sensor.p;
   a->state = (double*)c->d_state.p;
@@ -258,8 +270,6 @@ void fill_gmm_launch(pocs_ctx* c, pocs_gmm_launch* a, long long first, long long
   a->x = (double*)c->d_sx.p; a->y = (double*)c->d_sy.p; a->th = (double*)c->d_st.p;
   a->flags = (int16_t*)c->d_flags.p;
   a->first = first; a->count = count; a->n_total = c->num_gmm;
-  a->fp = c->fp; a->M = (int)(c->boxes.size() / 5);
-  a->fp_rr = sqrt(c->fp.hx * c->fp.hx + c->fp.hy * c->fp.hy); a->fp_phi = atan2(c->fp.hy, c->fp.hx);
   a->waypoint = w; a->store = c->opt_store ? 1 : 0;
   a->sample_stride = sample_stride_of(count);
   a->nruns = c->batch; a->W = c->W;

@@ -178,6 +178,10 @@ hipError_t pocs_launch_gmm_exchange(int K, const pocs_gmm_launch& a, const pocs_
 hipError_t pocs_launch_copy(const void* src, void* dst, long long bytes, hipStream_t s);
 hipError_t pocs_launch_fill(void* dst, long long bytes, hipStream_t s);
 hipError_t pocs_launch_probe_math(const pocs_tables* tables, int n, const uint32_t* wr, const uint32_t* wa, const double* x, double* out, hipStream_t s);   // out: 5 x n
+// one block; a: env, tables, param (the K records of ONE mixture: W = 1), fp, fp_rr, fp_phi, M -- nothing else is read.
+// x / y / th: n poses; flags: 3 x n (full table, pair, pair EAGER); nkeep: 1; kept: POCS_MAX_OBSTACLES records
+hipError_t pocs_launch_probe_collide(int K, const pocs_gmm_launch& a, int n, const double* x, const double* y, const double* th,
+                                     int* flags, int* nkeep, double* kept, hipStream_t s);
 hipError_t pocs_launch_mc_init(int nblk, const pocs_mc_launch& a, hipStream_t s);
 hipError_t pocs_launch_mc_step(int nblk, const pocs_mc_launch& a, hipStream_t s);
 hipError_t pocs_launch_mc_fused(int nblk, const pocs_mc_launch& a, hipStream_t s);

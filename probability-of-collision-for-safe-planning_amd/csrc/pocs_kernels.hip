@@ -198,6 +198,67 @@ hipError_t pocs_launch_probe_math(const pocs_tables* tables, int n, const uint32
   hipLaunchKernelGGL(k_probe_math, dim3(1), dim3(POCS_BLOCK), 0, s, tables, n, wr, wa, x, out);
   return hipGetLastError();
 }
+// The hot paths' collision test and k_gmm_step's obstacle cull on poses, a mixture and a world the caller picks
+// (pocs_probe_device_collide: a test hook -- a pose a few ulps from touching, a pose at the edge of what the mixture can
+// draw, which no free-running launch meets): ONE block that does what the kernels' blocks do, through the same inline
+// functions.  The head of gmm_step_block (ticket form, one run): tables, obstacle table and the mixture's parameters ->
+// gmm_smem, wave 0 culls, barrier.  Then the head of an MC block (stage_mc_head: its loops are guarded by the arrays'
+// sizes, so a block of TB >= POCS_BLOCK threads stages the same bytes).  Then per pose the three forms the kernels use:
+//   flags[i]          pocs_pose_collides on the full table, as the MC kernels call it
+//   flags[n + i]      pocs_pair_collides<false> on the culled table, as the batch form of k_gmm_step calls it
+//   flags[2 n + i]    pocs_pair_collides<true> on the culled table, as its lone form does
+// poses 2 p and 2 p + 1 one pair; an odd last pose is paired with itself, and 2 is added to its flag should the two
+// slots of that pair ever disagree.
+template <int K, int TB>
+__global__ __launch_bounds__(TB) void k_probe_collide(pocs_gmm_launch a, int n, const double* __restrict__ x, const double* __restrict__ y,
+                                                      const double* __restrict__ th, int* __restrict__ flags, int* __restrict__ nkeep_out,
+                                                      double* __restrict__ kept) {
+  typedef gmm_smem<K, TB> smem_t;
+  __shared__ smem_t sm;
+  constexpr int PS = K * POCS_PARAM_STRIDE;
+  static_assert(POCS_MAX_OBSTACLES * POCS_OBS_STRIDE <= TB && PS <= TB, "one obstacle element, one sampler parameter per thread");
+  const int tid = threadIdx.x;
+  double tabv[table_regs<TB>::N];
+  request_tables<TB>(a.tables, tid, tabv);
+  const double obs_elem = tid < a.M * POCS_OBS_STRIDE ? a.env->obs[tid] : 0.0;
+  const double parv = tid < PS ? load_wt(&a.param[tid]) : 0.0;
+  requests_issued();
+  commit_tables<TB>(&sm.tab, tid, tabv);
+  if (tid < a.M * POCS_OBS_STRIDE) sm.obs()[tid] = obs_elem;
+  if (tid < PS) sm.par[0][tid] = parv;
+  __syncthreads();
+  if (tid < 64) gmm_cull(a, sm, 0, tid, sm.par[0]);
+  __syncthreads();
+  const int nkeep = __builtin_amdgcn_readfirstlane(sm.nkeep[0]);
+  if (tid == 0) *nkeep_out = nkeep;
+  for (int j = tid; j < nkeep * POCS_OBS_STRIDE; j += TB) kept[j] = sm.keep[0][j];
+  const mc_head hd = stage_mc_head(a.env, a.tables);
+  const mc_world wd = hd.world();
+  for (int i = tid; i < n; i += TB)
+    flags[i] = pocs_pose_collides(x[i], y[i], th[i], &wd.fp, wd.obs, wd.M, wd.tab) ? 1 : 0;
+  const pocs_footprint fp = a.fp;
+  POCS_VCONST(vc_);
+  for (int p = tid; 2 * p < n; p += TB) {
+    const int i0 = 2 * p, i1 = i0 + 1 < n ? i0 + 1 : i0;
+    const double xs[2] = {x[i0], x[i1]}, ys[2] = {y[i0], y[i1]}, ts[2] = {th[i0], th[i1]};
+    bool hits[2];
+    pocs_pair_collides<false>(xs, ys, ts, &fp, sm.keep[0], nkeep, &sm.tab, &vc_, hits);
+    flags[n + i0] = (hits[0] ? 1 : 0) + (i1 == i0 && hits[1] != hits[0] ? 2 : 0);
+    if (i1 != i0) flags[n + i1] = hits[1] ? 1 : 0;
+    pocs_pair_collides<true>(xs, ys, ts, &fp, sm.keep[0], nkeep, &sm.tab, &vc_, hits);
+    flags[2 * n + i0] = (hits[0] ? 1 : 0) + (i1 == i0 && hits[1] != hits[0] ? 2 : 0);
+    if (i1 != i0) flags[2 * n + i1] = hits[1] ? 1 : 0;
+  }
+}
+hipError_t pocs_launch_probe_collide(int K, const pocs_gmm_launch& a, int n, const double* x, const double* y, const double* th,
+                                     int* flags, int* nkeep, double* kept, hipStream_t s) {
+  if (n < 1 || a.M < 0 || a.M > POCS_MAX_OBSTACLES || !a.env || !a.tables || !a.param) return hipErrorInvalidValue;
+  return with_K(K, [&](auto k) {
+    constexpr int KK = decltype(k)::value, TB = POCS_GMM_BLOCK_OF(KK);
+    hipLaunchKernelGGL((k_probe_collide<KK, TB>), dim3(1), dim3(TB), 0, s, a, n, x, y, th, flags, nkeep, kept);
+    return hipGetLastError();
+  });
+}
 hipError_t pocs_launch_fill(void* dst, long long bytes, hipStream_t s) {
   hipLaunchKernelGGL(k_fill, dim3(8192), dim3(POCS_BLOCK), 0, s, (double2*)dst, bytes / 16, 1.5);
   return hipGetLastError();

@@ -60,6 +60,11 @@ int hh_collides(double x, double y, double th, const double* fp4, const double* 
   for (int m = 0; m < M; ++m) pocs_prepare_obstacle(boxes + 5 * m, &fp, obs + m * POCS_OBS_STRIDE);
   return pocs_pose_collides(x, y, th, &fp, obs, M, tabs()) ? 1 : 0;
 }
+// the obstacle record (POCS_OBS_STRIDE doubles) the host prepares for the kernels' table
+void hh_prepare_obstacle(const double* box5, const double* fp4, double* rec) {
+  pocs_footprint fp = {fp4[0], fp4[1], fp4[2], fp4[3]};
+  pocs_prepare_obstacle(box5, &fp, rec);
+}
 // prev/next: K x 16, mom: K x 11 or null, param: K x 12
 void hh_gmm_advance(int K, const double* prev, const double* mom, const double* u, const double* Md,
                     const double* z, int L, const double* lx, const double* ly, double Q,
