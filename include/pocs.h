@@ -43,6 +43,35 @@ const char* pocs_version(void);
 int pocs_set_footprint(pocs_ctx* ctx, double dx, double dy, double half_x, double half_y);
 int pocs_set_obstacles(pocs_ctx* ctx, const double* boxes, int M);
 
+/* ---- moving obstacles: a collision world per waypoint (ours) --------------------------------
+ * A planner with a prediction for a pedestrian, a door or a second robot hands over S worlds of M boxes each:
+ *   boxes: S x M x {cx, cy, half_x, half_y, yaw_rad}, world s = boxes[s], 0 <= M <= 64 (the same M in every step),
+ *   1 <= S <= POCS_MAX_WORLD_STEPS.  Centre, half extents and yaw may all change from step to step (a growing box is how a
+ *   caller expresses the growing uncertainty of a prediction).
+ * World s is the collision world AT WAYPOINT s; waypoints >= S see world S - 1 (the last world holds).  Waypoint 0 is the initial
+ * cloud or mixture, waypoint s + 1 what control s produces: the indexing of pocs_mc_get_waypoint_counts.  The estimator tests
+ * poses at waypoints only, as the reference does: nothing is interpolated between two worlds.
+ * The time axis in every call shape: a single run, a batch, run-ahead, a shard, the step API (pocs_gmm_step_local,
+ * pocs_gmm_sample_local, pocs_gmm_sample_exchange_local) and the whole-call exchange: the waypoint index; a call of plans: each
+ * plan's own waypoint index (all plans start at time 0); a tree: a node's depth.  The risk bound (GMM and MC) works unchanged on
+ * top: it reads counts, not worlds.
+ * S = 1 is pocs_set_obstacles(boxes, M), bit for bit, in every result and getter (for every table this function accepts: it
+ * also refuses values that are not finite, which pocs_set_obstacles, checking the half extents only, takes as it always has).  S = 0 with M = 0 clears the schedule and leaves
+ * an explicitly empty static world, as clearObstacles does.  pocs_set_obstacles and clearObstacles replace the schedule with a
+ * static world; addObstacle replaces it with world 0 plus the new box.  pocs_set_footprint re-prepares the records of every step.
+ * POCS_E_ARG (the context keeps the world it had): a null `boxes` with M > 0, M or S out of range, any value that is not finite,
+ * a half extent <= 0.
+ * pocs_get_world_steps: S of the schedule in force; 1 for a static world; 0 for a context without a collision world.
+ * Launches: every per-waypoint launch (all GMM forms, the tree's levels, the MC init and per-step launches) is handed the record
+ * of its own waypoint and is otherwise what it is under a static world.  The fused MC roll-out (POCS_OPT_MC_FUSED = 1) under
+ * S > 1 is a kernel of its own, which restages the world per step while the step computes (k_mc_fused_sched, DESIGN.md section
+ * 5; kept because it is faster than the per-step form there: profiles/obstacle_schedule_vs_parent.txt); with S = 1 it is the
+ * kernel it has always been.  Particles, hit counters and counts are the same bits in both MC forms.
+ * pocs_probe_device_collide keeps probing world 0.  The text channel has no command for a schedule. */
+#define POCS_MAX_WORLD_STEPS 4096
+int pocs_set_obstacle_schedule(pocs_ctx* ctx, const double* boxes, int M, int S);  /* boxes: S x M x {cx, cy, half_x, half_y, yaw_rad} */
+int pocs_get_world_steps(const pocs_ctx* ctx);                                      /* S of the schedule in force; 1 for a static world; 0 for none */
+
 /* ---- typed twins of the setter commands (argument order = token order of the command) ---- */
 int pocs_set_alphas(pocs_ctx* ctx, const double* alphas, int n);            /* mcsimplugin.cpp:174-187 -> MCSimulator.h:224-230; n must be 4 */
 int pocs_set_q(pocs_ctx* ctx, double q);                                    /* :168-172 -> :232-235 */
@@ -350,7 +379,7 @@ int pocs_probe_device_collide(pocs_ctx* ctx, int K, const double* params, int n,
                               int* flag_pair_eager, int* nkeep, double* kept);
 /* TEST HOOK, no counterpart in the reference: the DEVICE's collision test and the obstacle cull of the GMM sampling kernel on
    inputs the caller picks, against the collision world and footprint the context holds (pocs_set_obstacles / pocs_set_footprint;
-   nothing else need be configured).  params: the sampler parameters of a mixture of K components, K x 12 doubles (per component
+   nothing else need be configured; under an obstacle schedule: world 0).  params: the sampler parameters of a mixture of K components, K x 12 doubles (per component
    mean[3], L00 L10 L11 L20 L21 L22 of the lower Cholesky factor, three unused); poses_xyt: n poses (x, y, theta), 1 <= n <= 2^20.
    One block stages the world and the mixture as a block of the sampling kernel does and culls the obstacle table against the
    mixture; then per pose i

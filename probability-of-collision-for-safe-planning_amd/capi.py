@@ -18,6 +18,7 @@ OPT_SUB_BATCHES, OPT_MC_NONTEMPORAL, OPT_PLAN_SEEDS, OPT_MC_WAYPOINT_COUNTS, OPT
 NMOM = 11
 MAX_PLANS = 256
 MAX_TREE_NODES = 4096
+MAX_WORLD_STEPS = 4096
 
 _dp = C.POINTER(C.c_double)
 _vp = C.c_void_p
@@ -30,6 +31,8 @@ SIGNATURES = {
     "pocs_version": (C.c_char_p, []),
     "pocs_set_footprint": (C.c_int, [_vp, C.c_double, C.c_double, C.c_double, C.c_double]),
     "pocs_set_obstacles": (C.c_int, [_vp, _dp, C.c_int]),
+    "pocs_set_obstacle_schedule": (C.c_int, [_vp, _dp, C.c_int, C.c_int]),
+    "pocs_get_world_steps": (C.c_int, [_vp]),
     "pocs_set_alphas": (C.c_int, [_vp, _dp, C.c_int]),
     "pocs_set_q": (C.c_int, [_vp, C.c_double]),
     "pocs_set_num_landmarks": (C.c_int, [_vp, C.c_int]),
@@ -231,6 +234,18 @@ class Context:
             return
         b = _arr(env["boxes"]).reshape(-1, 5)
         self._chk(self.lib.pocs_set_obstacles(self.h, b.ctypes.data_as(_dp), b.shape[0]))
+
+    def set_obstacle_schedule(self, boxes):
+        """Moving obstacles: boxes of shape (S, M, 5), world s = boxes[s] the collision world at waypoint s; waypoints >= S
+        see the last world (include/pocs.h).  planio.moving_boxes builds one from velocities."""
+        b = _arr(boxes)
+        if b.ndim != 3 or b.shape[2] != 5:
+            raise ValueError("obstacle schedule of shape %s, (S, M, 5) expected" % (b.shape,))
+        self._chk(self.lib.pocs_set_obstacle_schedule(self.h, b.ctypes.data_as(_dp) if b.size else None, b.shape[1], b.shape[0]))
+
+    def world_steps(self):
+        """S of the obstacle schedule in force; 1 for a static world; 0 for a context without a collision world."""
+        return self.lib.pocs_get_world_steps(self.h)
 
     def set_alphas(self, a):
         a = _arr(a)

@@ -128,10 +128,36 @@ int pocs_set_obstacles(pocs_ctx* c, const double* boxes, int M) {
     if (!(boxes[5 * m + 2] > 0) || !(boxes[5 * m + 3] > 0))
       return fail(c, POCS_E_ARG, "obstacle %d: half extents must be > 0", m);
   c->boxes.assign(boxes, boxes + (size_t)M * 5);
+  c->world_S = 1;                                    // (a schedule gives way to the static world)
   c->have_obstacles = true;
   c->env_dirty = true;
   return POCS_OK;
 }
+
+// The obstacle schedule: S worlds of M boxes each, world s the collision world at waypoint s (upload_world prepares one
+// record per step; every launch takes the record of its waypoint: world_at).  S = 1 is pocs_set_obstacles.
+int pocs_set_obstacle_schedule(pocs_ctx* c, const double* boxes, int M, int S) {
+  if (c) touch(c);
+  if (!c) return POCS_E_ARG;
+  if (M < 0 || M > POCS_MAX_OBSTACLES) return fail(c, POCS_E_ARG, "obstacle count %d outside 0..%d", M, POCS_MAX_OBSTACLES);
+  if (S == 0 && M == 0) return pocs_set_obstacles(c, nullptr, 0);      // no schedule, an explicitly empty world
+  if (S < 1 || S > POCS_MAX_WORLD_STEPS) return fail(c, POCS_E_ARG, "obstacle schedule of %d steps outside 1..%d", S, POCS_MAX_WORLD_STEPS);
+  if (M > 0 && !boxes) return fail(c, POCS_E_ARG, "obstacle schedule: null boxes");
+  for (int s = 0; s < S; ++s)
+    for (int m = 0; m < M; ++m) {
+      const double* b = boxes + ((size_t)s * (size_t)M + (size_t)m) * 5;
+      for (int j = 0; j < 5; ++j)
+        if (!std::isfinite(b[j])) return fail(c, POCS_E_ARG, "obstacle schedule: step %d, obstacle %d: value %d is not finite", s, m, j);
+      if (!(b[2] > 0) || !(b[3] > 0)) return fail(c, POCS_E_ARG, "obstacle schedule: step %d, obstacle %d: half extents must be > 0", s, m);
+    }
+  c->boxes.assign(boxes, boxes + (size_t)S * (size_t)M * 5);
+  c->world_S = S;
+  c->have_obstacles = true;
+  c->env_dirty = true;
+  return POCS_OK;
+}
+
+int pocs_get_world_steps(const pocs_ctx* c) { return (c && c->have_obstacles) ? c->world_S : 0; }
 
 int pocs_set_alphas(pocs_ctx* c, const double* a, int n) {
   if (c) touch(c);
@@ -688,7 +714,7 @@ int pocs_send_command(pocs_ctx* c, const char* line, char* out, size_t cap) {
     case pocs_cmd::kSetSeed: return pocs_set_seed(c, (uint64_t)p.seed);
     case pocs_cmd::kSetFootprint: return pocs_set_footprint(c, v[0], v[1], v[2], v[3]);
     case pocs_cmd::kAddObstacle: {
-      std::vector<double> b = c->boxes;
+      std::vector<double> b(c->boxes.begin(), c->boxes.begin() + (size_t)world_boxes(c) * 5);   // (under a schedule: world 0)
       b.insert(b.end(), v.begin(), v.end());
       return pocs_set_obstacles(c, b.data(), (int)(b.size() / 5));
     }

@@ -228,7 +228,7 @@ int pocs_probe_device_collide(pocs_ctx* c, int K, const double* params, int n, c
   int* d_flags = (int*)(d_kept + nrec);
   pocs_gmm_launch a;
   memset(&a, 0, sizeof a);
-  fill_gmm_world(c, &a);
+  fill_gmm_world(c, &a, 0);                         // (under an obstacle schedule: world 0)
   a.param = d_par; a.W = 1; a.nruns = 1; a.run_cnt = 1;
   std::vector<int> f(ni, 0);
   int rc = POCS_OK;

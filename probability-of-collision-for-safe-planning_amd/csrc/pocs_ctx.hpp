@@ -118,7 +118,8 @@ struct pocs_ctx {
   uint64_t seed = 0x5EED0001ull;
   uint64_t run_index = 0;
   pocs_footprint fp = {0.0, 0.0, 0.334, 0.334};
-  std::vector<double> boxes;             // M x 5
+  std::vector<double> boxes;             // world_S x M x 5: world s is the collision world at waypoint s (the last one holds behind it)
+  int world_S = 1;                       // steps of the obstacle schedule (pocs_set_obstacle_schedule); 1: a static world (pocs_set_obstacles)
   bool have_obstacles = false;           // pocs_set_obstacles / addObstacle / clearObstacles was called at least once
   long long shard_first = -1, shard_count = -1;
   long long opt_store = 1, opt_fused = 0, opt_graph = 1, opt_profile = 0, opt_lone = 1, opt_groups = 0, opt_mc_nt = -1;
@@ -253,6 +254,13 @@ inline void reset_results(pocs_ctx* c) {
   r.tree_probs.clear(); r.tree_eval.clear(); r.tree_F.clear(); r.tree_C.clear();
 }
 
+// The collision world: M boxes per step, and the record of the device's env array ([world_S] pocs_env_dev) that waypoint w --
+// a launch's waypoint, a tree level's depth -- is tested against.
+inline int world_boxes(const pocs_ctx* c) { return (int)(c->boxes.size() / 5 / (size_t)c->world_S); }
+inline const pocs_env_dev* world_at(const pocs_ctx* c, int w) {
+  return (const pocs_env_dev*)c->d_env.p + (w < 0 ? 0 : w < c->world_S ? w : c->world_S - 1);
+}
+
 inline double* moments_dev(pocs_ctx* c) { return c->ext_moments ? c->ext_moments : (double*)c->d_moments.p; }
 inline long long sample_stride_of(long long count) { return count > 0 ? ((count + 1) & ~1LL) : 2; }   // even
 inline uint64_t seed_of_run(const pocs_ctx* c, uint64_t run) { return c->seed + 0x9E3779B97F4A7C15ull * run; }
@@ -277,7 +285,7 @@ int stage_and_upload_runs(pocs_ctx* c, int groups, int kind);
 // ---- pocs_host.hip ----
 int upload_tables(pocs_ctx* c);
 int upload_world(pocs_ctx* c);
-void fill_gmm_world(const pocs_ctx* c, pocs_gmm_launch* a);
+void fill_gmm_world(const pocs_ctx* c, pocs_gmm_launch* a, int w);
 size_t sync_xwait_offset(const pocs_ctx* c);
 void gmm_select_view(pocs_ctx* c, int v);
 void tree_select_gmm(pocs_ctx* c, int n);

@@ -6,7 +6,7 @@
 //   k_mc_step       P1+P3     moveParticles (:300-322) + checkParticleCollisions, one waypoint, particles streamed through
 //                             HBM (SoA): 24 B in, 24 B out, u32 RMW; k_mc_step_counts: with first collisions / the stop
 //   k_mc_fused      P1+P3     same arithmetic, whole roll-out in registers (the controls do not depend on the particles,
-//                             SURVEY 3.2), 0 B per evaluation; k_mc_fused_counts
+//                             SURVEY 3.2), 0 B per evaluation; k_mc_fused_counts; k_mc_fused_sched: under an obstacle schedule
 //   k_mc_tree_step  P1+P3     one level of a tree of plans: the parent's particles moved into the node's place
 //   k_mc_count      P3        getCollisionProportion (:324-330): |{hits > 0}|.
 //
@@ -264,6 +264,83 @@ __device__ __forceinline__ void mc_fused_body(const pocs_mc_launch& a) {
 }
 __global__ __launch_bounds__(POCS_BLOCK) void k_mc_fused(pocs_mc_launch a) { mc_fused_body<MC_PLAIN>(a); }
 __global__ __launch_bounds__(POCS_BLOCK) void k_mc_fused_counts(pocs_mc_launch a) { mc_fused_body<MC_COUNTS>(a); }
+
+// The fused roll-out under an obstacle schedule (pocs_set_obstacle_schedule, S = env_steps > 1): waypoint w is tested against
+// record min(w, S - 1) of the env array, so a block cannot stage one world and keep it.  Step-outer per tile of POCS_BLOCK
+// particles, one particle per thread in registers; the world of the current waypoint in one of TWO LDS buffers.  The M records
+// of the next waypoint (the next tile's waypoint 0 behind a tile's last) are requested BEFORE the current waypoint's move and
+// collision test and stored into the other buffer behind it: the requests are in flight while the step computes, and a step
+// costs one block barrier, not a memory round trip.  The other buffer was last read one waypoint ago, in front of the previous
+// barrier.  Every thread of a block makes the same trips through both loops (the tile loop runs on the block's first index,
+// the steps are the run's: blockIdx.y); a thread without a particle only stages.  Footprint and M are the same in every
+// record.  Per particle and waypoint the arithmetic of mc_fused_body through the same functions: the same bits.
+template <int MODE>
+__global__ __launch_bounds__(POCS_BLOCK) void k_mc_fused_sched(pocs_mc_launch a) {
+  constexpr int NO = POCS_MAX_OBSTACLES * POCS_OBS_STRIDE, NS = (int)(sizeof(a.tables->sc) / sizeof(double));
+  constexpr int UO = (NO + POCS_BLOCK - 1) / POCS_BLOCK, US = (NS + POCS_BLOCK - 1) / POCS_BLOCK;
+  __shared__ double s_obs[2][NO];
+  __shared__ pocs_tables s_tab;
+  const int tid = threadIdx.x;
+  {                                                    // the head: world 0 and the sector table, as stage_mc_head stages them
+    const double* src = &a.tables->sc[0][0];
+    double vo[UO], vs[US];
+#pragma unroll
+    for (int u = 0; u < UO; ++u) { const int j = tid + u * POCS_BLOCK; vo[u] = j < NO ? a.env->obs[j] : 0.0; }
+#pragma unroll
+    for (int u = 0; u < US; ++u) { const int j = tid + u * POCS_BLOCK; vs[u] = j < NS ? src[j] : 0.0; }
+    requests_issued();
+    double* dst = &s_tab.sc[0][0];
+#pragma unroll
+    for (int u = 0; u < UO; ++u) { const int j = tid + u * POCS_BLOCK; if (j < NO) s_obs[0][j] = vo[u]; }
+#pragma unroll
+    for (int u = 0; u < US; ++u) { const int j = tid + u * POCS_BLOCK; if (j < NS) dst[j] = vs[u]; }
+  }
+  const pocs_footprint fp = a.env->fp;
+  const int M = a.env->M < POCS_MAX_OBSTACLES ? a.env->M : POCS_MAX_OBSTACLES, nrec = M * POCS_OBS_STRIDE;
+  const int last = a.env_steps - 1;
+  __syncthreads();
+  const mc_run_view v = mc_view(a);
+  const mc_run_start st = mc_start(a);             // (its steps: uniform per block, blockIdx.y being the run)
+  unsigned long long* wp = MODE != MC_PLAIN ? a.wp_counts + (size_t)blockIdx.y * (size_t)a.W : nullptr;
+  int cur = 0;                                     // the buffer that holds the current waypoint's world
+  const long long stride = (long long)gridDim.x * POCS_BLOCK;
+  for (long long base = (long long)blockIdx.x * POCS_BLOCK; base < a.count; base += stride) {      // (block-uniform)
+    const long long i = base + tid;
+    const bool live = i < a.count;
+    double x = 0.0, y = 0.0, t = 0.0, u0 = 0.0, u1 = 0.0, u2 = 0.0;
+    unsigned h = 0;
+    for (int w = 0; w <= st.steps; ++w) {
+      // what the NEXT waypoint needs -- its control (control w produces waypoint w + 1) and its world's records -- is requested
+      // here and first used behind this waypoint's test.  No request sits in a branch (a lane past the M records asks for
+      // record 0 again, and a tile's last waypoint for control 0): the only wait of the step is the one in front of the stores
+      const double* nu = v.chain + (size_t)(w < st.steps ? w : 0) * POCS_CHAIN_STRIDE + 6;   // wave-uniform
+      const double n0 = nu[0], n1 = nu[1], n2 = nu[2];
+      const int nw = w < st.steps ? w + 1 : 0;
+      const double* nsrc = a.env[nw < last ? nw : last].obs;
+      double vo[UO];
+#pragma unroll
+      for (int q = 0; q < UO; ++q) { const int j = tid + q * POCS_BLOCK; vo[q] = nsrc[j < nrec ? j : 0]; }
+      requests_issued();
+      if (live) {
+        if (w == 0) mc_initial(a, v.seed, i, st, x, y, t);
+        else mc_move(x, y, t, u0, u1, u2, x, y, t);
+        const bool hit = pocs_pose_collides(x, y, t, &fp, s_obs[cur], M, &s_tab);
+        if (MODE != MC_PLAIN) mc_wave_first_hits(hit && h == 0u, wp + w);
+        h += hit ? 1u : 0u;
+      }
+      requests_issued();
+      u0 = n0; u1 = n1; u2 = n2;
+#pragma unroll
+      for (int q = 0; q < UO; ++q) { const int j = tid + q * POCS_BLOCK; if (j < nrec) s_obs[cur ^ 1][j] = vo[q]; }
+      __syncthreads();
+      cur ^= 1;
+    }
+    if (live) {
+      v.x[i] = x; v.y[i] = y; v.th[i] = t;
+      v.hits[i] = h;
+    }
+  }
+}
 
 // A tree of plans (pocs_set_plan_tree), one launch per level (at most 256 nodes per launch): blockIdx.y = node of the launch,
 // slot r = tree_lo + blockIdx.y.  The node's particles are its PARENT's, moved by the noisy control of the edge into the node

@@ -73,17 +73,22 @@ int upload_tables(pocs_ctx* c) {               // log / sector tables of the num
   HIPCHK(c, hipMemcpy(c->d_tables.p, &T, sizeof T, hipMemcpyHostToDevice));
   return POCS_OK;
 }
-int upload_world(pocs_ctx* c) {                // tables + the collision world (obstacle records, footprint)
+int upload_world(pocs_ctx* c) {                // tables + the collision world: one record (obstacle records, footprint) per step of the schedule
   if (int r = upload_tables(c)) return r;
   if (c->env_dirty) {
-    pocs_env_dev env;
-    memset(&env, 0, sizeof env);
-    env.fp = c->fp;
-    env.M = (int)(c->boxes.size() / 5);
-    for (int m = 0; m < env.M; ++m)
-      pocs_prepare_obstacle(&c->boxes[(size_t)m * 5], &c->fp, &env.obs[(size_t)m * POCS_OBS_STRIDE]);
-    if (int r = ensure(c, c->d_env, sizeof env)) return r;
-    HIPCHK(c, hipMemcpy(c->d_env.p, &env, sizeof env, hipMemcpyHostToDevice));
+    const size_t S = (size_t)c->world_S;
+    const int M = world_boxes(c);
+    std::vector<pocs_env_dev> env(S);
+    memset(env.data(), 0, S * sizeof(pocs_env_dev));
+    for (size_t s = 0; s < S; ++s) {
+      env[s].fp = c->fp;
+      env[s].M = M;
+      for (int m = 0; m < M; ++m)
+        pocs_prepare_obstacle(&c->boxes[(s * (size_t)M + (size_t)m) * 5], &c->fp, &env[s].obs[(size_t)m * POCS_OBS_STRIDE]);
+    }
+    if (int r = ensure(c, c->d_env, S * sizeof(pocs_env_dev))) return r;      // (a schedule that grows: the graphs go with the old table)
+    HIPCHK(c, hipStreamSynchronize(c->stream));      // (nothing queued may still read the last world's)
+    HIPCHK(c, hipMemcpy(c->d_env.p, env.data(), S * sizeof(pocs_env_dev), hipMemcpyHostToDevice));
     c->env_dirty = false;
   }
   return POCS_OK;
@@ -241,10 +246,11 @@ bool whole_call_exchanges(const pocs_ctx* c) { return c->xchg_connected && c->sh
 
 // The collision world as a GMM launch carries it (upload_world has put it on the device): what the obstacle cull and the
 // collision test of k_gmm_step read -- and all that pocs_probe_device_collide's one-block launch reads besides its mixture.
-void fill_gmm_world(const pocs_ctx* c, pocs_gmm_launch* a) {
-  a->env = (const pocs_env_dev*)c->d_env.p;
+// `w`: the launch's waypoint, which picks the step of an obstacle schedule (the probe: world 0).
+void fill_gmm_world(const pocs_ctx* c, pocs_gmm_launch* a, int w) {
+  a->env = world_at(c, w);
   a->tables = (const pocs_tables*)c->d_tables.p;
-  a->fp = c->fp; a->M = (int)(c->boxes.size() / 5);
+  a->fp = c->fp; a->M = world_boxes(c);
   a->fp_rr = sqrt(c->fp.hx * c->fp.hx + c->fp.hy * c->fp.hy); a->fp_phi = atan2(c->fp.hy, c->fp.hx);
 }
 
@@ -253,7 +259,7 @@ void fill_gmm_launch(pocs_ctx* c, pocs_gmm_launch* a, long long first, long long
   memset(a, 0, sizeof *a);
   if (run_cnt < 0) run_cnt = c->batch;
   a->hdr = (const pocs_run_header*)c->d_hdr.p;
-  fill_gmm_world(c, a);
+  fill_gmm_world(c, a, w);                           // (a tree: w is the level's depth)
   a->chain = (const double*)c->d_chain.p;
   a->sensor = (const pocs_sensor*)c->d_sensor.p;
   a->state = (double*)c->d_state.p;
@@ -703,7 +709,7 @@ size_t mc_total_words(const pocs_ctx* c) {
 int mc_launch_base(pocs_ctx* c, long long count, double live_particles, pocs_mc_launch* a) {
   memset(a, 0, sizeof *a);
   a->hdr = (const pocs_run_header*)c->d_hdr.p;
-  a->env = (const pocs_env_dev*)c->d_env.p;
+  a->env = world_at(c, 0);                           // (k_mc_init: waypoint 0; the launches of later waypoints set their own)
   a->tables = (const pocs_tables*)c->d_tables.p;
   a->chain = (const double*)c->d_chain.p;
   a->total = (unsigned long long*)c->d_total.p;
@@ -737,6 +743,7 @@ int enqueue_mc_all(pocs_ctx* c, long long first, long long count, bool prof) {
   const std::vector<int> Ws = slot_lengths(c, plan_layout(c, 1));
   if (mc_fused_form(c)) {
     a.step = W - 1;
+    a.env_steps = c->world_S;                        // (> 1: k_mc_fused_sched, which restages the world per step)
     if (prof) HIPCHK(c, hipEventRecord(c->events[0], c->stream));
     HIPCHK(c, pocs_launch_mc_fused(nblk, a, c->stream));
     if (prof) HIPCHK(c, hipEventRecord(c->events[1], c->stream));
@@ -746,6 +753,7 @@ int enqueue_mc_all(pocs_ctx* c, long long first, long long count, bool prof) {
     for (int s = 0; s < W - 1; ++s) {
       a.step = s;
       pocs_mc_launch as = a;
+      as.env = world_at(c, s + 1);                   // control s produces waypoint s + 1
       int nb = nblk;
       if (c->plans.n) {
         as.nruns = live_runs(Ws, 0, R, s + 1);       // plans with a control at step s: W_p - 1 > s
@@ -833,6 +841,7 @@ int enqueue_mc_tree(pocs_ctx* c, long long count) {
     pocs_mc_launch prev = a;
     half_of(&prev, d - 1);
     half_of(&a, d);
+    a.env = world_at(c, d);
     a.tree_sx = prev.x; a.tree_sy = prev.y; a.tree_sth = prev.th; a.tree_shits = prev.hits;
     a.tree_dst_lo = lo; a.tree_src_lo = c->tree.level[(size_t)d - 1];
     for (int s = lo; s < hi; s += 256) {

@@ -41,7 +41,7 @@ static_assert(POCS_GMM_BLOCK_OF(3) == 512 && POCS_GMM_MAX_VS == 256, "summation 
 #define POCS_CHAIN_STRIDE 48
 static_assert(POCS_CHAIN_Z + POCS_MAX_LANDMARKS <= POCS_CHAIN_STRIDE, "chain record too small");
 
-struct pocs_env_dev {            // collision world as the kernels see it (one copy in HBM, staged to LDS)
+struct pocs_env_dev {            // collision world as the kernels see it (in HBM one record per step of the obstacle schedule, staged to LDS)
   pocs_footprint fp;
   int M;
   int pad;
@@ -166,6 +166,10 @@ struct pocs_mc_launch {               // blockIdx.y = run of the batch, like poc
   const double* tree_sx; const double* tree_sy; const double* tree_sth;
   const uint32_t* tree_shits;
   int tree_lo, tree_dst_lo, tree_src_lo, tree_pad;   // the launch's first slot, its level's, the previous level's
+  // an obstacle schedule (pocs_set_obstacle_schedule; behind everything else again).  Every per-waypoint launch gets the record
+  // of its own waypoint in `env` above; only the fused roll-out walks the array: env[min(w, env_steps - 1)] at waypoint w
+  int env_steps;                       // pocs_launch_mc_fused: > 1 = k_mc_fused_sched over env[0 .. env_steps); 0 / 1: one world, k_mc_fused
+  int env_pad;
 };
 
 

@@ -8,7 +8,7 @@
 //                         exchange of a run's moments between the GPUs of a node                 (prims)
 //   pocs_dev_gmm.hpp      k_gmm_step, k_gmm_step_risk, k_gmm_step_tree, k_gmm_close: one waypoint of truncateGMM in one
 //                         launch -- sampling, collision test, moment sums, closer                (prims, advance)
-//   pocs_dev_mc.hpp       k_mc_init, k_mc_step, k_mc_fused, k_mc_tree_step, k_mc_count           (prims)
+//   pocs_dev_mc.hpp       k_mc_init, k_mc_step, k_mc_fused, k_mc_fused_sched, k_mc_tree_step, k_mc_count (prims)
 //
 // Bound: these are FP64-VALU / HBM streaming kernels, no contraction => no MFMA.  Mixture
 // parameters, the obstacle table and the 12 KB of log/sector tables are staged in LDS once per
@@ -138,8 +138,11 @@ hipError_t pocs_launch_mc_step(int nblk, const pocs_mc_launch& a, hipStream_t s)
 }
 hipError_t pocs_launch_mc_fused(int nblk, const pocs_mc_launch& a, hipStream_t s) {
   if (a.wp_mode == 2 || (a.wp_mode != 0 && !a.wp_counts)) return hipErrorInvalidValue;      // (no stop without a launch boundary per step)
-  if (a.wp_mode) hipLaunchKernelGGL(k_mc_fused_counts, dim3(nblk, a.nruns), dim3(POCS_BLOCK), 0, s, a);
-  else           hipLaunchKernelGGL(k_mc_fused, dim3(nblk, a.nruns), dim3(POCS_BLOCK), 0, s, a);
+  if (a.env_steps > 1) {                              // an obstacle schedule: the world is restaged per step
+    if (a.wp_mode) hipLaunchKernelGGL(k_mc_fused_sched<MC_COUNTS>, dim3(nblk, a.nruns), dim3(POCS_BLOCK), 0, s, a);
+    else           hipLaunchKernelGGL(k_mc_fused_sched<MC_PLAIN>, dim3(nblk, a.nruns), dim3(POCS_BLOCK), 0, s, a);
+  } else if (a.wp_mode) hipLaunchKernelGGL(k_mc_fused_counts, dim3(nblk, a.nruns), dim3(POCS_BLOCK), 0, s, a);
+  else                  hipLaunchKernelGGL(k_mc_fused, dim3(nblk, a.nruns), dim3(POCS_BLOCK), 0, s, a);
   return hipGetLastError();
 }
 hipError_t pocs_launch_mc_count(int nblk, const pocs_mc_launch& a, hipStream_t s) {

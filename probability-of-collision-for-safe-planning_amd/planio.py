@@ -161,3 +161,23 @@ def tree_path(parent, poses, odoms, n):
         n = int(parent[n])
     path.reverse()
     return dict(traj=poses[path].copy(), odom=odoms[path[1:]].copy().reshape(-1, 3))
+
+
+def moving_boxes(boxes0, velocity, S):
+    """An obstacle schedule (Context.set_obstacle_schedule) from boxes that move at constant velocity: boxes0 M x 5
+    (cx, cy, half_x, half_y, yaw), velocity M x 3 = (vx, vy, omega) per waypoint.  Returns S x M x 5; step s of box m is
+    (cx + s * vx, cy + s * vy, half_x, half_y, yaw + s * omega), each one multiplication and one addition in IEEE double."""
+    b = np.asarray(boxes0, dtype=np.float64).reshape(-1, 5)
+    v = np.asarray(velocity, dtype=np.float64).reshape(-1, 3)
+    S = int(S)
+    if v.shape[0] != b.shape[0]:
+        raise ValueError("velocity of %d boxes for %d boxes" % (v.shape[0], b.shape[0]))
+    if S < 1:
+        raise ValueError("a schedule has at least one step, got %d" % S)
+    out = np.empty((S, b.shape[0], 5))
+    for s in range(S):
+        out[s] = b
+        out[s, :, 0] = b[:, 0] + float(s) * v[:, 0]
+        out[s, :, 1] = b[:, 1] + float(s) * v[:, 1]
+        out[s, :, 4] = b[:, 4] + float(s) * v[:, 2]
+    return out
