@@ -139,6 +139,11 @@ int pocs_send_command(pocs_ctx* ctx, const char* line, char* out, size_t cap);
                                       stops a plan at the first waypoint where its share of collided particles reaches the bound
                                       (pocs_set_plan_risk_bound); such a call counts as under POCS_OPT_MC_WAYPOINT_COUNTS and takes the per-step
                                       launch form whatever POCS_OPT_MC_FUSED says.  No effect without plans or with the bound off */
+#define POCS_OPT_OBSTACLE_COUNTS 13 /* 0 (default): every call is what it has always been.  1: every pocs_run_gmm_estimation, pocs_run_simulation and
+                                      step-API sequence also fills, per run / plan / tree node, a table of collision counts per waypoint and
+                                      obstacle box (pocs_get_obstacle_counts); the launches are then counting forms of the kernels, and an
+                                      MC call counts as under POCS_OPT_MC_WAYPOINT_COUNTS.  No other result changes by a bit.  Not inside a
+                                      begin/end sequence (POCS_E_ORDER) */
 int pocs_set_option(pocs_ctx* ctx, int option, long long value);
 
 /* ---- batches of independent runs (ours) --------------------------------------------------
@@ -352,6 +357,22 @@ int pocs_mc_get_batch_counts(pocs_ctx* ctx, unsigned long long* out, int cap);  
  * partition.  Writes and returns the number of waypoints covered (a plan's own length, or the waypoints before its stop).
  * POCS_E_BUFFER for a short buffer; POCS_E_STATE when the last call was not an MC call or ran with the option off. */
 int pocs_mc_get_waypoint_counts(pocs_ctx* ctx, unsigned long long* out, int cap);
+/* Under POCS_OPT_OBSTACLE_COUNTS: which box a plan's risk comes from.  The table A[w][m] of the selected run (pocs_select_batch_run;
+ * plan p while plans are set; the path root -> n for pocs_select_tree_node(n); the run served last under run-ahead), m = the index
+ * of the box in the table the caller handed over (pocs_set_obstacles, addObstacle order, world min(w, S - 1) of
+ * pocs_set_obstacle_schedule):
+ *   GMM  A[w][m] = the shard's samples drawn at waypoint w whose footprint touches box m;
+ *   MC   A[w][m] = the shard's particles whose FIRST collision is at waypoint w and which touch box m there: the split of
+ *        pocs_mc_get_waypoint_counts by box.
+ * Not exclusive: a sample or particle that touches two boxes counts for both, so max_m A[w][m] <= collisions at w <= sum_m A[w][m].
+ * "Touches" is the collision test's own answer for that box: a pose collides exactly when it touches at least one.  Integer counts:
+ * the same whatever the launch form, the grid and the shard partition; the table is the shard's, the shards' tables add up to the
+ * whole run's (the in-library exchange does not carry them).
+ * Writes E x M values row-major (waypoint-major), *boxes = M, and returns E, the waypoints covered: a plan's own length, or the
+ * waypoints before its stop under a risk bound, or depth + 1 for a tree node (the evaluated part under a GMM bound).  M = 0 writes
+ * nothing and returns E.  POCS_E_BUFFER for cap < E * M; POCS_E_STATE when the last call ran with the option off (or the option was
+ * touched since, or there was no call); POCS_E_ARG for null pointers.  Every call shape serves it: none is refused. */
+int pocs_get_obstacle_counts(pocs_ctx* ctx, unsigned long long* out, int cap, int* boxes);
 
 /* ---- results of the last run, for audits and parity tests ------------------------------- */
 int pocs_get_path_length(const pocs_ctx* ctx);

@@ -15,6 +15,8 @@ POCS_OK = 0
 E_ARG, E_ORDER, E_STATE, E_DEVICE, E_UNKNOWN_COMMAND, E_BUFFER = -1, -2, -3, -4, -5, -6
 OPT_STORE_SAMPLES, OPT_MC_FUSED, OPT_USE_GRAPH, OPT_PROFILE, OPT_RUN_AHEAD, OPT_PERSISTENT, OPT_LONE_CALL = 1, 2, 3, 4, 5, 6, 7
 OPT_SUB_BATCHES, OPT_MC_NONTEMPORAL, OPT_PLAN_SEEDS, OPT_MC_WAYPOINT_COUNTS, OPT_MC_RISK_BOUND = 8, 9, 10, 11, 12
+OPT_OBSTACLE_COUNTS = 13
+MAX_OBSTACLES = 64                 # POCS_MAX_OBSTACLES: the widest table pocs_get_obstacle_counts writes
 NMOM = 11
 MAX_PLANS = 256
 MAX_TREE_NODES = 4096
@@ -73,6 +75,7 @@ SIGNATURES = {
     "pocs_mc_run_local": (C.c_int, [_vp, C.POINTER(C.c_ulonglong)]),
     "pocs_mc_get_batch_counts": (C.c_int, [_vp, C.POINTER(C.c_ulonglong), C.c_int]),
     "pocs_mc_get_waypoint_counts": (C.c_int, [_vp, C.POINTER(C.c_ulonglong), C.c_int]),
+    "pocs_get_obstacle_counts": (C.c_int, [_vp, C.POINTER(C.c_ulonglong), C.c_int, C.POINTER(C.c_int)]),
     "pocs_xchg_create": (C.c_int, [_vp, C.c_int, C.c_int, C.c_void_p]),
     "pocs_xchg_connect": (C.c_int, [_vp, C.c_void_p, C.c_int]),
     "pocs_gmm_exchange_local": (C.c_int, [_vp, C.c_int]),
@@ -426,6 +429,16 @@ class Context:
         out = np.zeros(W, dtype=np.uint64)
         got = self._chk(self.lib.pocs_mc_get_waypoint_counts(self.h, out.ctypes.data_as(C.POINTER(C.c_ulonglong)), W))
         return out[:got]
+
+    def obstacle_counts(self):
+        """Collision counts per waypoint and obstacle box of the current selection (run, plan or tree path) of the last call
+        under OPT_OBSTACLE_COUNTS: a (E, M) uint64 array, entry [w, m] = samples at waypoint w that touch box m (GMM), or
+        particles whose first collision is at w and which touch box m there (MC); include/pocs.h."""
+        E = max(self.path_length(), 1)
+        out = np.zeros(E * MAX_OBSTACLES, dtype=np.uint64)
+        M = C.c_int(0)
+        got = self._chk(self.lib.pocs_get_obstacle_counts(self.h, out.ctypes.data_as(C.POINTER(C.c_ulonglong)), out.size, C.byref(M)))
+        return out[:got * M.value].reshape(got, M.value)
 
     def gmm_begin(self):
         self._chk(self.lib.pocs_gmm_begin(self.h))

@@ -96,7 +96,8 @@ void pocs_destroy(pocs_ctx* c) {
     if (c->ev_seq[1]) hipEventDestroy(c->ev_seq[1]);
     DevBuf* all[] = {&c->d_env, &c->d_sensor, &c->d_hdr, &c->d_chain, &c->d_state, &c->d_param,
                      &c->d_moments, &c->d_partial, &c->d_sx, &c->d_sy, &c->d_st, &c->d_flags,
-                     &c->d_px, &c->d_py, &c->d_pt, &c->d_hits, &c->d_total, &c->d_ticket, &c->d_tables, &c->d_runplan, &c->d_surv, &c->d_tparent};
+                     &c->d_px, &c->d_py, &c->d_pt, &c->d_hits, &c->d_total, &c->d_ticket, &c->d_tables, &c->d_runplan, &c->d_surv, &c->d_tparent,
+                     &c->d_obsct};
     for (DevBuf* b : all) if (b->p) hipFree(b->p);
     if (c->h_pin) hipHostFree(c->h_pin);
     if (c->h_copy) hipHostFree(c->h_copy);
@@ -305,6 +306,12 @@ int pocs_set_option(pocs_ctx* c, int option, long long value) {
     case POCS_OPT_MC_RISK_BOUND:
       if (value < 0 || value > 1) return fail(c, POCS_E_ARG, "POCS_OPT_MC_RISK_BOUND takes 0 (MC calls ignore the risk bound) or 1");
       c->opt_mc_rb = value;
+      break;
+    case POCS_OPT_OBSTACLE_COUNTS:
+      if (value < 0 || value > 1) return fail(c, POCS_E_ARG, "POCS_OPT_OBSTACLE_COUNTS takes 0 or 1");
+      if (c->gmm_open) return fail(c, POCS_E_ORDER, "POCS_OPT_OBSTACLE_COUNTS inside a begin/end sequence");
+      c->opt_obs_counts = value;
+      c->res.oc_kind = 0;                            // (a table is served until the option is touched or the next call)
       break;
     case POCS_OPT_RUN_AHEAD:
       if (value < 0 || value > 256) return fail(c, POCS_E_ARG, "run-ahead %lld outside 0..256", value);

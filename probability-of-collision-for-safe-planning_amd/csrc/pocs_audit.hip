@@ -138,6 +138,52 @@ long long pocs_copy_particles(pocs_ctx* c, double* aos, uint32_t* hits, long lon
   return n;
 }
 
+// POCS_OPT_OBSTACLE_COUNTS: the table A[w][m] of the selected run, plan or tree path (include/pocs.h), read from the device's
+// [slot][oc_W][POCS_MAX_OBSTACLES] array the last call filled: a run's or a plan's rows lie one behind the other, a path's one per
+// node.  Row-major E x M, M = the boxes of the call's world.
+int pocs_get_obstacle_counts(pocs_ctx* c, unsigned long long* out, int cap, int* boxes) {
+  if (!c) return POCS_E_ARG;
+  if (!out || !boxes) return fail(c, POCS_E_ARG, "pocs_get_obstacle_counts: null output");
+  const int kind = c->res.oc_kind;
+  if (!kind || kind != c->res.last_kind || !c->d_obsct.p)
+    return fail(c, POCS_E_STATE, "pocs_get_obstacle_counts: the last call ran without POCS_OPT_OBSTACLE_COUNTS (or there was none)");
+  const size_t M = (size_t)c->res.oc_M, Wr = (size_t)c->res.oc_W, row = POCS_MAX_OBSTACLES;
+  std::vector<size_t> rows;                          // the device rows ([slot * oc_W + w]) of the view's waypoints, in order
+  if (c->tree.n) {
+    if (c->res.tree_last != kind) return fail(c, POCS_E_STATE, "pocs_get_obstacle_counts: the last call was not a call on the tree");
+    for (int v = c->res.tree_sel; v >= 0; v = c->tree.parent[(size_t)v])
+      if (kind == 2 || c->res.tree_eval[(size_t)v]) rows.push_back((size_t)c->tree.slot[(size_t)v]);      // (GMM under a bound: the evaluated part)
+    std::reverse(rows.begin(), rows.end());
+  } else {
+    const size_t r = (size_t)c->res.view;
+    int E = (int)Wr;                                   // a plan's own length, or the waypoints before its stop
+    if (c->plans.n && r < c->res.plan_slot[kind - 1].size()) {
+      if (kind == 1) E = r < c->res.plan_E.size() ? c->res.plan_E[r] : c->plans.W[r];
+      else E = c->res.plan_E_mc.empty() ? c->plans.W[r] : c->res.plan_E_mc[r];
+    }
+    if (r >= (size_t)c->res.batch_R && kind == 1) return fail(c, POCS_E_STATE, "pocs_get_obstacle_counts: no run %zu in the last call", r);
+    const size_t slot = view_slot(c, kind - 1);
+    for (int w = 0; w < E; ++w) rows.push_back(slot * Wr + (size_t)w);
+  }
+  *boxes = (int)M;
+  const size_t E = rows.size();
+  if ((size_t)(cap < 0 ? 0 : cap) < E * M) return fail(c, POCS_E_BUFFER, "need %zu counters", E * M);
+  if (M == 0 || E == 0) return (int)E;
+  if ((rows.back() + 1) * row * sizeof(unsigned long long) > c->d_obsct.cap) return fail(c, POCS_E_STATE, "pocs_get_obstacle_counts: the table does not cover the selection");
+  HIPCHK(c, hipSetDevice(c->device));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  std::vector<unsigned long long> h(E * row);
+  const unsigned long long* dev = (const unsigned long long*)c->d_obsct.p;
+  if (!c->tree.n) {                                  // one piece
+    if (int r = copy_out(c, h.data(), dev + rows[0] * row, E * row * sizeof(unsigned long long), 1, 0)) return r;
+  } else {
+    for (size_t w = 0; w < E; ++w)
+      if (int r = copy_out(c, &h[w * row], dev + rows[w] * row, row * sizeof(unsigned long long), 1, 0)) return r;
+  }
+  for (size_t w = 0; w < E; ++w) memcpy(out + w * M, &h[w * row], M * sizeof(unsigned long long));
+  return (int)E;
+}
+
 // Measured streaming bandwidth of this GPU (GB/s), best of 5 timed with hipEvents on the context's stream: of a plain
 // 16-B-per-lane copy of `bytes` (rounded down to 16; read + written bytes per second) -- the ceiling the streaming kernels are
 // compared with next to the datasheet's 8 TB/s -- or, write-only, of a plain fill of `bytes` (bytes written per second).

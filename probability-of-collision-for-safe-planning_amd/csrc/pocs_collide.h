@@ -146,6 +146,77 @@ POCS_HD void pocs_pair_collides(const double x[2], const double y[2], const doub
   }
 }
 
+// The two predicates above with every record's own answer kept (POCS_OPT_OBSTACLE_COUNTS: which box a collision comes
+// from).  Per pose the same operations in the same order -- pocs_box_hit against record m, the flag set under the same
+// condition -- and each answer handed to `each` before the next record is looked at: each(m, touched) for one pose,
+// each(m, h, touched) for pose h of a pair, called by every lane that runs the loop, outside the test's own branches (a
+// caller may ballot in it).  The flag is set exactly when some record's answer is.  Functions of their own: the forms
+// above stay, instruction for instruction, what they are.
+template <class Each>
+POCS_HD bool pocs_pose_collides_each(double x, double y, double th, const pocs_footprint* fp, const double* obs, int M,
+                                     const pocs_tables* T, Each each, const pocs_vconst* V = nullptr) {
+  if (M <= 0) return false;
+  double sn, cs;
+  pocs_sincos_tab(th, T, &sn, &cs, V);
+  double px = x, py = y;
+  if (!(fp->dx == 0.0 && fp->dy == 0.0)) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    asm volatile("; offset footprint");
+#endif
+    px = x + fma(cs, fp->dx, -(sn * fp->dy));
+    py = y + fma(sn, fp->dx, cs * fp->dy);
+  }
+  bool hit = false;
+  for (int m = 0; m < M; ++m) {
+    const bool t = pocs_box_hit(px, py, sn, cs, fp->hx, fp->hy, obs + m * POCS_OBS_STRIDE);
+    if (t) hit = true;
+    each(m, t);
+  }
+  return hit;
+}
+
+template <bool EAGER = false, class Each>
+POCS_HD void pocs_pair_collides_each(const double x[2], const double y[2], const double th[2], const pocs_footprint* fp,
+                                     const double* obs, int M, const pocs_tables* T, const pocs_vconst* V, bool hit[2], Each each) {
+  hit[0] = false; hit[1] = false;
+  if (M <= 0) return;
+  double sn[2], cs[2], px[2], py[2];
+#if defined(__HIP_DEVICE_COMPILE__)
+#pragma unroll
+#endif
+  for (int h = 0; h < 2; ++h) {
+    pocs_sincos_tab(th[h], T, &sn[h], &cs[h], V);
+    px[h] = x[h]; py[h] = y[h];
+  }
+  if (!(fp->dx == 0.0 && fp->dy == 0.0)) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    asm volatile("; offset footprint");
+#endif
+    for (int h = 0; h < 2; ++h) {
+      px[h] = x[h] + fma(cs[h], fp->dx, -(sn[h] * fp->dy));
+      py[h] = y[h] + fma(sn[h], fp->dx, cs[h] * fp->dy);
+    }
+  }
+  for (int m = 0; m < M; ++m) {
+    const double* o = obs + m * POCS_OBS_STRIDE;
+#if defined(__HIP_DEVICE_COMPILE__)
+    double rec[POCS_OBS_STRIDE];
+    if (EAGER) {
+#pragma unroll
+      for (int q = 0; q < POCS_OBS_STRIDE; ++q) rec[q] = o[q];
+      asm volatile("" : "+v"(rec[0]), "+v"(rec[1]), "+v"(rec[2]), "+v"(rec[3]), "+v"(rec[4]), "+v"(rec[5]), "+v"(rec[6]), "+v"(rec[7]));
+      o = rec;
+    }
+#pragma unroll
+#endif
+    for (int h = 0; h < 2; ++h) {
+      const bool t = pocs_box_hit(px[h], py[h], sn[h], cs[h], fp->hx, fp->hy, o);
+      if (t) hit[h] = true;
+      each(m, h, t);
+    }
+  }
+}
+
 // The footprint's largest half-extent along world x over all headings in [lo, hi] (along world y: the
 // same function of [lo - pi/2, hi - pi/2]): an upper bound, never more than the bounding radius.
 //   f(t) = rx |cos t| + ry |sin t| is concave between the multiples of pi/2 and peaks with the bounding

@@ -84,6 +84,10 @@ struct Results {
   std::vector<unsigned char> tree_eval;           // [T] 1 evaluated, 0 cut off below a stopped ancestor
   std::vector<unsigned long long> tree_F, tree_C; // [T] MC: first collisions at the node, collided at or before it
   size_t tree_mc_half = 0;                        // MC: elements of one level's half of the particle buffers
+  // per-obstacle collision counts (POCS_OPT_OBSTACLE_COUNTS): the table stays on the device ([slot][oc_W][POCS_MAX_OBSTACLES], d_obsct)
+  // and pocs_get_obstacle_counts reads the selected run's rows; this is what the last call left there
+  int oc_kind = 0;                                // 0: the last call ran with the option off (or there was none); 1 GMM, 2 MC
+  int oc_M = 0, oc_W = 0;                         // boxes of the call's world, rows per slot
 };
 
 }  // namespace pocs_rt
@@ -143,6 +147,8 @@ struct pocs_ctx {
   // (POCS_OPT_MC_RISK_BOUND): k_mc_*_counts count, k_mc_step_counts<.., MC_STOP> decides and obeys; run_mc_local restates the
   // rule on the counts read back
   long long opt_mc_wp = 0, opt_mc_rb = 0;
+  // per-obstacle collision counts (POCS_OPT_OBSTACLE_COUNTS): the launches are the kernels' _boxes / MC_BOXES forms
+  long long opt_obs_counts = 0;
 
   // host image (headers | chains | initial mixtures) of the NEXT batch, computed while the GPU
   // works on the current one
@@ -161,6 +167,7 @@ struct pocs_ctx {
   pocs_rt::DevBuf d_runplan;             // a call of plans: [R][4] start mean and steps per run (the MC kernels)
   pocs_rt::DevBuf d_surv;                // a call of plans under a risk bound: [R] running survival product of every run
   pocs_rt::DevBuf d_tparent;             // a tree of plans: [T] int, the slot of every slot's parent
+  pocs_rt::DevBuf d_obsct;               // POCS_OPT_OBSTACLE_COUNTS: [slots][W][POCS_MAX_OBSTACLES] u64, zeroed by a kernel at the head of every call's launches
   // one-hop exchange (pocs_xchg_*): this rank's buffer, the peers' buffers as mapped here
   void* xchg_own = nullptr;
   void* xchg_peer[POCS_XCHG_MAX_WORLD] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
@@ -252,6 +259,7 @@ inline void reset_results(pocs_ctx* c) {
   r.mc_wp.clear(); r.mc_wp_W = 0; r.plan_E_mc.clear();
   r.tree_last = 0; r.tree_sel = 0; r.tree_mc_half = 0;
   r.tree_probs.clear(); r.tree_eval.clear(); r.tree_F.clear(); r.tree_C.clear();
+  r.oc_kind = 0; r.oc_M = 0; r.oc_W = 0;
 }
 
 // The collision world: M boxes per step, and the record of the device's env array ([world_S] pocs_env_dev) that waypoint w --
@@ -286,6 +294,7 @@ int stage_and_upload_runs(pocs_ctx* c, int groups, int kind);
 int upload_tables(pocs_ctx* c);
 int upload_world(pocs_ctx* c);
 void fill_gmm_world(const pocs_ctx* c, pocs_gmm_launch* a, int w);
+size_t obs_count_words(const pocs_ctx* c);
 size_t sync_xwait_offset(const pocs_ctx* c);
 void gmm_select_view(pocs_ctx* c, int v);
 void tree_select_gmm(pocs_ctx* c, int n);

@@ -25,7 +25,9 @@
 //                                   after it has exchanged the run's moments with the other ranks (IPC
 //                                   slots, one hop over xGMI) in the same tail.
 //                             The waypoint loop never returns to the host.  (k_gmm_step_risk, k_gmm_step_tree: the same block
-//                             under a risk bound / for one level of a tree of plans; k_gmm_close: the lone form's last rows.)
+//                             under a risk bound / for one level of a tree of plans; k_gmm_close: the lone form's last rows;
+//                             k_gmm_step_boxes, k_gmm_step_risk_boxes, k_gmm_step_tree_boxes: the counting forms of the three, which
+//                             also count per obstacle box the samples that touch it, POCS_OPT_OBSTACLE_COUNTS.)
 
 // LDS of k_gmm_step.  A block works through a contiguous range of the launch's UNITS -- (run, virtual slice)
 // pairs, pocs_kernels.h -- that may cross from one run into the next: everything per run is held twice.
@@ -35,8 +37,16 @@
 //   slot   wave sums (survivors, nine sums) of the unit's FIRST component, per virtual slice held and wave;
 //          once the rows are out, the mixture advance's scratch
 //   xtra   ... of a component that STARTS inside the unit (a wave meets the start of a component once per run)
-template <int K, int TB>
-struct gmm_smem {
+//   occ / oci  (the counting form only, POCS_OPT_OBSTACLE_COUNTS: an empty base otherwise, the layout below as it is) per run
+//          buffer and KEPT record: the block's samples that touch it, and the record's index in the caller's table (gmm_cull
+//          compacts): 1 KB
+template <bool OC> struct gmm_oc_smem {};
+template <> struct gmm_oc_smem<true> {
+  unsigned occ[2][POCS_MAX_OBSTACLES];
+  int oci[2][POCS_MAX_OBSTACLES];
+};
+template <int K, int TB, bool OC = false>
+struct gmm_smem : gmm_oc_smem<OC> {
   static constexpr int NC = K * POCS_NMOM;
   static constexpr int NW = TB / 64;
   static constexpr int SUB = POCS_GMM_SUB;
@@ -87,8 +97,8 @@ __device__ __forceinline__ double oct_sum(double s) {     // lanes 8 j .. 8 j + 
 // wave's xtra entry of k), and the chains restart.  By LDS transposition, five then four sums at a
 // time: every lane writes its values, lane 8 j + q adds lanes 8 q .. 8 q + 7 of sum j, oct_sum adds the
 // eight q.  One wave: the LDS executes a wave's instructions in order, nothing else synchronises.
-template <int K, int TB>
-__device__ __forceinline__ void flush_unit(gmm_smem<K, TB>& sm, const int wave, const int lane, const int rb, const int tl,
+template <int K, int TB, bool OC>
+__device__ __forceinline__ void flush_unit(gmm_smem<K, TB, OC>& sm, const int wave, const int lane, const int rb, const int tl,
                                            const int k, bool& first, double (&acc)[9], int& nfree) {
   double* const T = &sm.tr[wave][0][0];
   double* const dst = first ? &sm.slot[tl][wave][0] : &sm.xtra[rb][wave][k][0];
@@ -134,8 +144,8 @@ __device__ __forceinline__ void flush_unit(gmm_smem<K, TB>& sm, const int wave, 
 // robot's heading is known to a fraction of a radian -- most of a plan -- far fewer poses reach the
 // narrow phase, and none that could touch is lost: the flags do not change.
 //   (pocs_footprint_extent, pocs_collide.h: host + device, checked on the CPU against a dense scan)
-template <int K, int TB>
-__device__ __forceinline__ void gmm_cull(const pocs_gmm_launch& a, gmm_smem<K, TB>& sm, const int rb, const int lane, const double* par) {
+template <int K, int TB, bool OC>
+__device__ __forceinline__ void gmm_cull(const pocs_gmm_launch& a, gmm_smem<K, TB, OC>& sm, const int rb, const int lane, const double* par) {
   const pocs_footprint fp = a.fp;
   const int M = a.M;
   const double* const obs = sm.obs();
@@ -177,7 +187,9 @@ __device__ __forceinline__ void gmm_cull(const pocs_gmm_launch& a, gmm_smem<K, T
     for (int j = 0; j < 6; ++j) sm.keep[rb][pos * POCS_OBS_STRIDE + j] = obs[lane * POCS_OBS_STRIDE + j];
     sm.keep[rb][pos * POCS_OBS_STRIDE + 6] = bx;
     sm.keep[rb][pos * POCS_OBS_STRIDE + 7] = by;
+    if constexpr (OC) sm.oci[rb][pos] = lane;      // the kept slot's index in the caller's table: its counter leaves under it
   }
+  if constexpr (OC) sm.occ[rb][lane] = 0u;           // (one wave, POCS_MAX_OBSTACLES = 64 lanes: every counter of the buffer)
   if (lane == 0) sm.nkeep[rb] = __popcll(mask);
 }
 
@@ -193,8 +205,12 @@ __device__ __forceinline__ void gmm_cull(const pocs_gmm_launch& a, gmm_smem<K, T
 //   zpre / npre (the lone form, LONE_PRE): the normals of the unit's first `npre` iterations, drawn in the block's head by
 //   the waves that waited there ([iteration][sample of the pair x 3][thread]); the same function of the same arguments,
 //   the same bits -- a call of one run then spends its sampling phase on what depends on the mixture only
-template <int K, bool STORE, int TB, bool LONE_PRE = false>
-__device__ __forceinline__ void gmm_units(const pocs_gmm_launch& a, gmm_smem<K, TB>& sm, const int w, const int r0,
+//   OC (POCS_OPT_OBSTACLE_COUNTS): per kept record and pose of the pair, the lanes that touch it and whose sample exists are
+//   balloted; hits are rare, so a zero ballot -- nearly all of them -- is skipped by a scalar branch, and otherwise one lane
+//   adds the population count to the block's LDS counter of (run buffer, kept slot).  Nothing else differs: pocs_pair_collides_each
+//   is pocs_pair_collides with every record's answer handed out.
+template <int K, bool STORE, int TB, bool LONE_PRE = false, bool OC = false>
+__device__ __forceinline__ void gmm_units(const pocs_gmm_launch& a, gmm_smem<K, TB, OC>& sm, const int w, const int r0,
                                           const int ta, const int tb, const double* zpre = nullptr, const int npre = 0) {
   const pocs_tables* const s_tab = &sm.tab;
   const int tid = threadIdx.x, lane = tid & 63;
@@ -296,7 +312,16 @@ __device__ __forceinline__ void gmm_units(const pocs_gmm_launch& a, gmm_smem<K, 
       ks[h] = k;
     }
     POCS_TUNE_COLLIDE_STATS();
+    if constexpr (OC) {
+      unsigned* const occ = sm.occ[rb];
+      pocs_pair_collides_each<LONE_PRE>(xs, ys, ts, &fp, s_keep, nkeep, s_tab, vc, hits, [&](const int m, const int h, const bool t) {
+        const unsigned long long b = __ballot(t && (h == 0 ? live : two));      // the odd shard's unused twin does not count
+        if (b != 0ull && lane == (int)__builtin_ctzll(b))
+          __hip_atomic_fetch_add(&occ[m], (unsigned)__popcll(b), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+      });
+    } else {
     POCS_TUNE_COLLIDE(pocs_pair_collides<LONE_PRE>(xs, ys, ts, &fp, s_keep, nkeep, s_tab, vc, hits));
+    }
     if constexpr (POCS_TUNE_SKIP_MOMENTS) { POCS_TUNE_MOMENTS_ALT(); } else {
     // T1 sums over the collision-free samples of the component being accumulated:
     //   (x, y, t, x x, x y, x t, y y, y t, t t) with the products inside the fma; survivors by population count.
@@ -421,8 +446,8 @@ __device__ __forceinline__ void gmm_units(const pocs_gmm_launch& a, gmm_smem<K, 
 // order -- whichever of them the unit has: slot if the component was the wave's first there, xtra if it
 // started inside the wave's share, +0 otherwise -- stored write-through to the run's partial rows.
 // Column 1 (collisions) stays 0: a component's collisions are what is left of its block (gmm_close_sums).
-template <int K, int TB>
-__device__ __forceinline__ void gmm_emit_rows(const pocs_gmm_launch& a, gmm_smem<K, TB>& sm, const int r0, const int ta, const int tb) {
+template <int K, int TB, bool OC>
+__device__ __forceinline__ void gmm_emit_rows(const pocs_gmm_launch& a, gmm_smem<K, TB, OC>& sm, const int r0, const int ta, const int tb) {
   constexpr int NC = K * POCS_NMOM, NW = TB / 64;
   for (int i = threadIdx.x; i < (tb - ta) * NC; i += TB) {
     const int tl = i / NC, c = i - tl * NC, k = c / POCS_NMOM, col = c - k * POCS_NMOM;
@@ -582,9 +607,15 @@ __device__ __forceinline__ void gmm_close_sums(const pocs_gmm_launch& a, const i
 // its slot alone (the host lays them out [slot], i.e. W = 1, row 0).  The mixtures were built by k_gmm_tree_advance, which
 // under RISK has also handed the parent's stop and survival product down: the heads and closers below do what they do for
 // waypoint `depth` of a plan.
-template <int K, bool STORE, int TB, bool LONE, bool RISK, bool TREE = false>
+//
+// OC (POCS_OPT_OBSTACLE_COUNTS; the kernels k_gmm_step_boxes, k_gmm_step_risk_boxes, k_gmm_step_tree_boxes): the block also counts,
+// per run buffer and kept obstacle record, its samples that touch the record (gmm_units), in LDS counters that gmm_cull zeroes;
+// behind the units the nonzero ones leave with one integer atomic each to obs_counts[run][waypoint][the record's index in the
+// caller's table] -- exact whatever the grid.  A stopped run's blocks add nothing; the table is the shard's, the exchange does
+// not carry it.
+template <int K, bool STORE, int TB, bool LONE, bool RISK, bool TREE = false, bool OC = false>
 __device__ __forceinline__ void gmm_step_block(const pocs_gmm_launch a) {      // (by value, as a kernel holds its argument)
-  typedef gmm_smem<K, TB> smem_t;
+  typedef gmm_smem<K, TB, OC> smem_t;
   static_assert(!(LONE && RISK), "the lone form closes in its heads: a call under a risk bound takes the ticket form");
   static_assert(!(TREE && (LONE || STORE)), "a tree's levels take the ticket form and store no samples");
   constexpr int SUB = smem_t::SUB, NW = smem_t::NW;
@@ -706,7 +737,7 @@ __device__ __forceinline__ void gmm_step_block(const pocs_gmm_launch a) {      /
   POCS_STAMP(0);
   for (int ta = t0; ta < t1; ta += SUB) {
     const int tb = (ta + SUB < t1) ? ta + SUB : t1;
-    gmm_units<K, STORE, TB, LONE>(a, sm, w, r0, ta, tb, s_zpre, ta == t0 ? npre : 0);
+    gmm_units<K, STORE, TB, LONE, OC>(a, sm, w, r0, ta, tb, s_zpre, ta == t0 ? npre : 0);
     POCS_STAMP(1);
     __syncthreads();
     POCS_STAMP(2);
@@ -715,6 +746,15 @@ __device__ __forceinline__ void gmm_step_block(const pocs_gmm_launch a) {      /
       __syncthreads();
       for (int j = tid; j < 2 * NW * K; j += TB) (&sm.xj[0][0][0])[j] = -1;
       __syncthreads();
+    }
+  }
+  if constexpr (OC) {
+    // (every wave's LDS additions lie in front of the barrier behind the last gmm_units; nkeep[] is reused by the closer's
+    // exchange only, further down)
+    const int rb = tid >> 6, j = tid & 63;
+    if (rb <= r1 - r0 && j < sm.nkeep[rb]) {
+      const unsigned n = sm.occ[rb][j];
+      if (n) atomicAdd(&a.obs_counts[((size_t)(r0 + rb) * a.W + wr) * POCS_MAX_OBSTACLES + sm.oci[rb][j]], (unsigned long long)n);
     }
   }
   if (LONE) return;                                  // the rows leave through the kernel boundary; the next launch's heads add them
@@ -816,6 +856,20 @@ __global__ __launch_bounds__(TB, POCS_GMM_BLOCKS_PER_CU * TB / 256) void k_gmm_s
 template <int K, int TB, bool RISK>
 __global__ __launch_bounds__(TB, POCS_GMM_BLOCKS_PER_CU * TB / 256) void k_gmm_step_tree(pocs_gmm_launch a) {
   gmm_step_block<K, false, TB, false, RISK, true>(a);
+}
+
+// The counting forms (POCS_OPT_OBSTACLE_COUNTS): kernels of their own names, so that the ones above stay what they are.
+template <int K, bool STORE, int TB, bool LONE>
+__global__ __launch_bounds__(TB, (LONE ? 1 : POCS_GMM_BLOCKS_PER_CU) * TB / 256) void k_gmm_step_boxes(pocs_gmm_launch a) {
+  gmm_step_block<K, STORE, TB, LONE, false, false, true>(a);
+}
+template <int K, bool STORE, int TB>
+__global__ __launch_bounds__(TB, POCS_GMM_BLOCKS_PER_CU * TB / 256) void k_gmm_step_risk_boxes(pocs_gmm_launch a) {
+  gmm_step_block<K, STORE, TB, false, true, false, true>(a);
+}
+template <int K, int TB, bool RISK>
+__global__ __launch_bounds__(TB, POCS_GMM_BLOCKS_PER_CU * TB / 256) void k_gmm_step_tree_boxes(pocs_gmm_launch a) {
+  gmm_step_block<K, false, TB, false, RISK, true, true>(a);
 }
 
 // Lone call, behind the last waypoint's launch: its rows -> moments[W-1] (one block).

@@ -9,6 +9,8 @@
 //                             SURVEY 3.2), 0 B per evaluation; k_mc_fused_counts; k_mc_fused_sched: under an obstacle schedule
 //   k_mc_tree_step  P1+P3     one level of a tree of plans: the parent's particles moved into the node's place
 //   k_mc_count      P3        getCollisionProportion (:324-330): |{hits > 0}|.
+//   MC_BOXES forms of k_mc_init / k_mc_step_counts / k_mc_fused_sched, k_mc_fused_boxes, k_mc_tree_step_boxes: ... with the first
+//                             collisions split by obstacle box (POCS_OPT_OBSTACLE_COUNTS)
 //
 // Each of these exists once: the block head (stage_mc_head -> mc_head -> mc_world), the initial draw (mc_initial), the motion
 // step (mc_move), the particle accessors (mc_load / mc_store) and the block sum of counts (mc_block_add).
@@ -103,7 +105,49 @@ __device__ __forceinline__ mc_run_start mc_start(const pocs_mc_launch& a) {
 // more), MC_COUNTS also adds to wp_counts[run][w] the particles that collide at waypoint w and at no waypoint before it,
 // MC_STOP (k_mc_step only) also obeys the risk bound.  A particle's first collision is read off the hit counter the kernel
 // holds anyway (old == 0).  Integer counts added with integer atomics: exact, whatever the grid and the shard partition.
-enum { MC_PLAIN = 0, MC_COUNTS = 1, MC_STOP = 2 };
+//
+// MC_BOXES (POCS_OPT_OBSTACLE_COUNTS), a flag on top of MC_COUNTS or MC_STOP: the first collisions are also split by obstacle
+// box -- obs_counts[run][w][m], the particles whose first collision is at waypoint w and which touch box m there (a particle
+// that touches two boxes counts for both).  The collision test is then pocs_pose_collides_each, which hands out every record's
+// answer; a thread keeps them as a 64-bit mask (POCS_MAX_OBSTACLES = 64: box 63 is bit 63), and the mask matters only for a
+// particle with old == 0 && hit.  The forms without the flag are the kernels as they are.
+enum { MC_PLAIN = 0, MC_COUNTS = 1, MC_STOP = 2, MC_BOXES = 4 };
+static_assert(POCS_MAX_OBSTACLES <= 64, "a particle's touched boxes are a 64-bit mask");
+
+// pocs_pose_collides with the touched boxes as a mask (the flag: mask != 0, as the plain form's).
+__device__ __forceinline__ bool mc_collides_mask(double x, double y, double t, const pocs_footprint* fp, const double* obs, int M,
+                                                 const pocs_tables* tab, unsigned long long& mask) {
+  mask = 0ull;
+  return pocs_pose_collides_each(x, y, t, fp, obs, M, tab, [&](const int m, const bool touched) { if (touched) mask |= 1ull << m; });
+}
+
+// The lanes of a wave that are in the particle loop together, `first` = a first collision at this waypoint with touched boxes
+// `mask`: per box that any of them touches one ballot, and the first lane of the ballot adds its population count to dst[m]
+// (the block's LDS counters, or -- the fused kernels -- the run's row in global memory, as mc_wave_first_hits does).  No first
+// collision in the wave (nearly always): one ballot and a scalar branch.
+__device__ __forceinline__ void mc_wave_box_hits(bool first, unsigned long long mask, int M, unsigned long long* dst) {
+  if (__ballot(first) == 0ull) return;
+  for (int m = 0; m < M; ++m) {
+    const unsigned long long b = __ballot(first && ((mask >> m) & 1ull) != 0ull);
+    if (b != 0ull && (threadIdx.x & 63) == (unsigned)__builtin_ctzll(b)) atomicAdd(&dst[m], (unsigned long long)__popcll(b));
+  }
+}
+// The block's LDS counters of the kernels that meet a block boundary per waypoint (k_mc_init, k_mc_step, k_mc_tree_step):
+// zeroed in front of the head's barrier, and behind the particle loop the nonzero ones leave with one atomic each, thread m
+// box m.
+struct mc_box_counters {
+  unsigned long long* c;
+  __device__ __forceinline__ void out(int M, unsigned long long* row) const {
+    __syncthreads();
+    const int m = threadIdx.x;
+    if (m < M) { const unsigned long long n = c[m]; if (n) atomicAdd(&row[m], n); }
+  }
+};
+__device__ __forceinline__ mc_box_counters mc_box_counters_zeroed() {
+  __shared__ unsigned long long s_box[POCS_MAX_OBSTACLES];
+  if (threadIdx.x < POCS_MAX_OBSTACLES) s_box[threadIdx.x] = 0ull;
+  return {s_box};
+}
 
 // A block's sum of counts -> dst[at]: every thread's own count, one wave sum, one word per wave in LDS, one atomic per block
 // (integer: order independent, exact) and none when the sum is 0.  Every thread of the block arrives (behind its particle
@@ -182,6 +226,8 @@ __device__ __forceinline__ void mc_move(const double x, const double y, const do
 
 template <int MODE>
 __global__ __launch_bounds__(POCS_BLOCK) void k_mc_init(pocs_mc_launch a) {
+  mc_box_counters box = {nullptr};
+  if constexpr ((MODE & MC_BOXES) != 0) box = mc_box_counters_zeroed();      // (in front of the head's barrier)
   const mc_head hd = stage_mc_head(a.env, a.tables);
   const mc_run_view v = mc_view(a);
   const mc_world wd = hd.world();
@@ -192,11 +238,19 @@ __global__ __launch_bounds__(POCS_BLOCK) void k_mc_init(pocs_mc_launch a) {
     double x, y, t;
     mc_initial(a, v.seed, i, st, x, y, t);
     v.x[i] = x; v.y[i] = y; v.th[i] = t;
-    const unsigned h = pocs_pose_collides(x, y, t, &wd.fp, wd.obs, wd.M, wd.tab) ? 1u : 0u;
+    unsigned h;
+    if constexpr ((MODE & MC_BOXES) != 0) {
+      unsigned long long mask;
+      h = mc_collides_mask(x, y, t, &wd.fp, wd.obs, wd.M, wd.tab, mask) ? 1u : 0u;
+      mc_wave_box_hits(h != 0u, mask, wd.M, box.c);
+    } else {
+      h = pocs_pose_collides(x, y, t, &wd.fp, wd.obs, wd.M, wd.tab) ? 1u : 0u;
+    }
     v.hits[i] = h;
     first += h;
   }
   if (MODE != MC_PLAIN) mc_block_add(first, a.wp_counts + (size_t)blockIdx.y * (size_t)a.W);      // waypoint 0
+  if constexpr ((MODE & MC_BOXES) != 0) box.out(wd.M, a.obs_counts + (size_t)blockIdx.y * (size_t)a.W * POCS_MAX_OBSTACLES);
 }
 
 // A particle's words in HBM.  NT: non-temporal accesses, chosen by the host when the particle state of the batch does not
@@ -209,7 +263,9 @@ template <bool NT, typename T> __device__ __forceinline__ void mc_store(const T 
 // faster out of it.
 template <bool NT, int MODE>
 __device__ __forceinline__ void mc_step_body(const pocs_mc_launch& a) {
-  if (MODE == MC_STOP) { if (mc_run_stopped(a)) return; }      // (the same answer in every thread of the block)
+  if ((MODE & 3) == MC_STOP) { if (mc_run_stopped(a)) return; }      // (the same answer in every thread of the block)
+  mc_box_counters box = {nullptr};
+  if constexpr ((MODE & MC_BOXES) != 0) box = mc_box_counters_zeroed();      // (in front of the head's barrier)
   const mc_head hd = stage_mc_head(a.env, a.tables);
   const mc_run_view v = mc_view(a);
   const mc_world wd = hd.world();
@@ -222,13 +278,26 @@ __device__ __forceinline__ void mc_step_body(const pocs_mc_launch& a) {
     double nx, ny, nt;
     mc_move(x, y, t, u0, u1, u2, nx, ny, nt);
     mc_store<NT>(nx, v.x + i); mc_store<NT>(ny, v.y + i); mc_store<NT>(nt, v.th + i);
+    if constexpr ((MODE & MC_BOXES) != 0) {
+      unsigned long long mask;
+      bool fresh = false;
+      if (mc_collides_mask(nx, ny, nt, &wd.fp, wd.obs, wd.M, wd.tab, mask)) {
+        const uint32_t old = v.hits[i];
+        v.hits[i] = old + 1u;
+        fresh = old == 0u;
+        first += fresh ? 1u : 0u;
+      }
+      mc_wave_box_hits(fresh, mask, wd.M, box.c);
+    } else {
     if (pocs_pose_collides(nx, ny, nt, &wd.fp, wd.obs, wd.M, wd.tab)) {
       const uint32_t old = v.hits[i];                // the counter is in hand exactly when the particle collides
       v.hits[i] = old + 1u;
       first += old == 0u ? 1u : 0u;
     }
+    }
   }
   if (MODE != MC_PLAIN) mc_block_add(first, a.wp_counts + (size_t)blockIdx.y * (size_t)a.W + (size_t)a.step + 1);   // control s -> waypoint s + 1
+  if constexpr ((MODE & MC_BOXES) != 0) box.out(wd.M, a.obs_counts + ((size_t)blockIdx.y * (size_t)a.W + (size_t)a.step + 1) * POCS_MAX_OBSTACLES);
 }
 template <bool NT>
 __global__ __launch_bounds__(POCS_BLOCK) void k_mc_step(pocs_mc_launch a) { mc_step_body<NT, MC_PLAIN>(a); }
@@ -248,13 +317,28 @@ __device__ __forceinline__ void mc_fused_body(const pocs_mc_launch& a) {
   for (long long i = (long long)blockIdx.x * POCS_BLOCK + threadIdx.x; i < a.count; i += stride) {
     double x, y, t;
     mc_initial(a, v.seed, i, st, x, y, t);
-    unsigned h = pocs_pose_collides(x, y, t, &wd.fp, wd.obs, wd.M, wd.tab) ? 1u : 0u;
+    unsigned long long* const bx = (MODE & MC_BOXES) != 0 ? a.obs_counts + (size_t)blockIdx.y * (size_t)a.W * POCS_MAX_OBSTACLES : nullptr;
+    unsigned h;
+    if constexpr ((MODE & MC_BOXES) != 0) {
+      unsigned long long mask;
+      h = mc_collides_mask(x, y, t, &wd.fp, wd.obs, wd.M, wd.tab, mask) ? 1u : 0u;
+      mc_wave_box_hits(h != 0u, mask, wd.M, bx);
+    } else {
+      h = pocs_pose_collides(x, y, t, &wd.fp, wd.obs, wd.M, wd.tab) ? 1u : 0u;
+    }
     if (MODE != MC_PLAIN) mc_wave_first_hits(h != 0u, wp);
     for (int s = 0; s < st.steps; ++s) {
       const double* u = v.chain + (size_t)s * POCS_CHAIN_STRIDE + 6;   // wave-uniform
       const double u0 = u[0], u1 = u[1], u2 = u[2];
       mc_move(x, y, t, u0, u1, u2, x, y, t);
-      const bool hit = pocs_pose_collides(x, y, t, &wd.fp, wd.obs, wd.M, wd.tab);
+      bool hit;
+      if constexpr ((MODE & MC_BOXES) != 0) {
+        unsigned long long mask;
+        hit = mc_collides_mask(x, y, t, &wd.fp, wd.obs, wd.M, wd.tab, mask);
+        mc_wave_box_hits(hit && h == 0u, mask, wd.M, bx + (size_t)(s + 1) * POCS_MAX_OBSTACLES);
+      } else {
+        hit = pocs_pose_collides(x, y, t, &wd.fp, wd.obs, wd.M, wd.tab);
+      }
       if (MODE != MC_PLAIN) mc_wave_first_hits(hit && h == 0u, wp + s + 1);
       h += hit ? 1u : 0u;
     }
@@ -264,6 +348,7 @@ __device__ __forceinline__ void mc_fused_body(const pocs_mc_launch& a) {
 }
 __global__ __launch_bounds__(POCS_BLOCK) void k_mc_fused(pocs_mc_launch a) { mc_fused_body<MC_PLAIN>(a); }
 __global__ __launch_bounds__(POCS_BLOCK) void k_mc_fused_counts(pocs_mc_launch a) { mc_fused_body<MC_COUNTS>(a); }
+__global__ __launch_bounds__(POCS_BLOCK) void k_mc_fused_boxes(pocs_mc_launch a) { mc_fused_body<MC_COUNTS | MC_BOXES>(a); }
 
 // The fused roll-out under an obstacle schedule (pocs_set_obstacle_schedule, S = env_steps > 1): waypoint w is tested against
 // record min(w, S - 1) of the env array, so a block cannot stage one world and keep it.  Step-outer per tile of POCS_BLOCK
@@ -302,6 +387,7 @@ __global__ __launch_bounds__(POCS_BLOCK) void k_mc_fused_sched(pocs_mc_launch a)
   const mc_run_view v = mc_view(a);
   const mc_run_start st = mc_start(a);             // (its steps: uniform per block, blockIdx.y being the run)
   unsigned long long* wp = MODE != MC_PLAIN ? a.wp_counts + (size_t)blockIdx.y * (size_t)a.W : nullptr;
+  unsigned long long* const bx = (MODE & MC_BOXES) != 0 ? a.obs_counts + (size_t)blockIdx.y * (size_t)a.W * POCS_MAX_OBSTACLES : nullptr;
   int cur = 0;                                     // the buffer that holds the current waypoint's world
   const long long stride = (long long)gridDim.x * POCS_BLOCK;
   for (long long base = (long long)blockIdx.x * POCS_BLOCK; base < a.count; base += stride) {      // (block-uniform)
@@ -324,7 +410,14 @@ __global__ __launch_bounds__(POCS_BLOCK) void k_mc_fused_sched(pocs_mc_launch a)
       if (live) {
         if (w == 0) mc_initial(a, v.seed, i, st, x, y, t);
         else mc_move(x, y, t, u0, u1, u2, x, y, t);
-        const bool hit = pocs_pose_collides(x, y, t, &fp, s_obs[cur], M, &s_tab);
+        bool hit;
+        if constexpr ((MODE & MC_BOXES) != 0) {
+          unsigned long long mask;
+          hit = mc_collides_mask(x, y, t, &fp, s_obs[cur], M, &s_tab, mask);
+          mc_wave_box_hits(hit && h == 0u, mask, M, bx + (size_t)w * POCS_MAX_OBSTACLES);
+        } else {
+          hit = pocs_pose_collides(x, y, t, &fp, s_obs[cur], M, &s_tab);
+        }
         if (MODE != MC_PLAIN) mc_wave_first_hits(hit && h == 0u, wp + w);
         h += hit ? 1u : 0u;
       }
@@ -348,8 +441,11 @@ __global__ __launch_bounds__(POCS_BLOCK) void k_mc_fused_sched(pocs_mc_launch a)
 // the particle buffers and written to the node's place in this level's half: source != destination, two levels live at a
 // time.  Counted per node: the particles whose FIRST collision on the path root -> node is at the node (wp_counts[r]) and
 // those that have collided at or before it (total[r]); integer atomics, exact whatever the grid.
-template <bool NT>
-__global__ __launch_bounds__(POCS_BLOCK) void k_mc_tree_step(pocs_mc_launch a) {
+//   BOXES (k_mc_tree_step_boxes, POCS_OPT_OBSTACLE_COUNTS): ... and the node's first collisions by obstacle box, obs_counts[r].
+template <bool NT, bool BOXES>
+__device__ __forceinline__ void mc_tree_step_body(const pocs_mc_launch& a) {
+  mc_box_counters box = {nullptr};
+  if constexpr (BOXES) box = mc_box_counters_zeroed();      // (in front of the head's barrier)
   const mc_head hd = stage_mc_head(a.env, a.tables);
   const int r = a.tree_lo + (int)blockIdx.y, pr = a.tree_parent[r];
   const size_t so = (size_t)(pr - a.tree_src_lo) * (size_t)a.stride, dso = (size_t)(r - a.tree_dst_lo) * (size_t)a.stride;
@@ -367,7 +463,15 @@ __global__ __launch_bounds__(POCS_BLOCK) void k_mc_tree_step(pocs_mc_launch a) {
     const uint32_t old = mc_load<NT>(sh + i);
     double nx, ny, nt;
     mc_move(x, y, t, u0, u1, u2, nx, ny, nt);
-    const uint32_t h = old + (pocs_pose_collides(nx, ny, nt, &wd.fp, wd.obs, wd.M, wd.tab) ? 1u : 0u);
+    uint32_t h;
+    if constexpr (BOXES) {
+      unsigned long long mask;
+      const bool hit = mc_collides_mask(nx, ny, nt, &wd.fp, wd.obs, wd.M, wd.tab, mask);
+      h = old + (hit ? 1u : 0u);
+      mc_wave_box_hits(hit && old == 0u, mask, wd.M, box.c);
+    } else {
+      h = old + (pocs_pose_collides(nx, ny, nt, &wd.fp, wd.obs, wd.M, wd.tab) ? 1u : 0u);
+    }
     mc_store<NT>(nx, dx + i); mc_store<NT>(ny, dy + i); mc_store<NT>(nt, dt + i); mc_store<NT>(h, dh + i);
     first += (old == 0u && h != 0u) ? 1u : 0u;
     coll += h != 0u ? 1u : 0u;
@@ -375,7 +479,12 @@ __global__ __launch_bounds__(POCS_BLOCK) void k_mc_tree_step(pocs_mc_launch a) {
   mc_block_add(first, a.wp_counts + r);
   __syncthreads();                                   // (mc_block_add's scratch is read by thread 0 of the call above)
   mc_block_add(coll, a.total + r);
+  if constexpr (BOXES) box.out(wd.M, a.obs_counts + (size_t)r * POCS_MAX_OBSTACLES);
 }
+template <bool NT>
+__global__ __launch_bounds__(POCS_BLOCK) void k_mc_tree_step(pocs_mc_launch a) { mc_tree_step_body<NT, false>(a); }
+template <bool NT>
+__global__ __launch_bounds__(POCS_BLOCK) void k_mc_tree_step_boxes(pocs_mc_launch a) { mc_tree_step_body<NT, true>(a); }
 
 __global__ __launch_bounds__(POCS_BLOCK) void k_mc_count(pocs_mc_launch a) {
   const mc_run_view v = mc_view(a);

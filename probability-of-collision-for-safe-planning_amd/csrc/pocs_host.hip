@@ -154,6 +154,25 @@ int gmm_shard(pocs_ctx* c, long long* first, long long* count) {
 // memset, the same copies.
 bool risk_active(const pocs_ctx* c) { return (c->plans.n > 0 || c->tree.n > 0) && c->risk_bound < 1.0; }
 
+// Per-obstacle collision counts (POCS_OPT_OBSTACLE_COUNTS): d_obsct holds [batch][W][POCS_MAX_OBSTACLES] u64 (a tree: W = 1, one row
+// per slot).  It is zeroed by the first launch of every call -- a kernel, inside the replayed graph -- and read by the getter
+// (pocs_audit.hip).  Off: no buffer, no launch, and every launch is the kernel it has always been.
+size_t obs_count_words(const pocs_ctx* c) { return (size_t)c->batch * (size_t)(c->W > 0 ? c->W : 1) * POCS_MAX_OBSTACLES; }
+int ensure_obs_counts(pocs_ctx* c) {
+  return c->opt_obs_counts ? ensure(c, c->d_obsct, obs_count_words(c) * sizeof(unsigned long long)) : POCS_OK;
+}
+int enqueue_obs_counts_reset(pocs_ctx* c) {
+  if (!c->opt_obs_counts) return POCS_OK;
+  HIPCHK(c, pocs_launch_zero_counts((unsigned long long*)c->d_obsct.p, obs_count_words(c), c->stream));
+  return POCS_OK;
+}
+// what the getter needs to know of the call that has just filled the table (kind: 1 GMM, 2 MC; 0 with the option off)
+void note_obs_counts(pocs_ctx* c, int kind) {
+  c->res.oc_kind = c->opt_obs_counts ? kind : 0;
+  c->res.oc_M = world_boxes(c);
+  c->res.oc_W = c->W > 0 ? c->W : 1;
+}
+
 // The synchronisation words of one call (pocs_kernels.h): [1] give-up code, [0], [2..3] pad, then -- under a risk bound -- the
 // runs' stop words [R] (padded to 4: they travel back with the give-up word in one copy), then the
 // tickets [R][W], then -- sharded runs -- the closers' exchange waits [R][W]; a block of its own, a multiple of
@@ -192,6 +211,7 @@ int gmm_prepare(pocs_ctx* c) {
     if (int r = ensure(c, c->d_surv, R * sizeof(double))) return r;
   if (c->tree.n)
     if (int r = upload_tree(c)) return r;
+  if (int r = ensure_obs_counts(c)) return r;
   if (c->opt_store && !c->tree.n) {                   // (a call on a tree stores no samples)
     const size_t n = R * (size_t)sample_stride_of(count);
     if (int r = ensure(c, c->d_sx, n * sizeof(double))) return r;
@@ -279,6 +299,7 @@ void fill_gmm_launch(pocs_ctx* c, pocs_gmm_launch* a, long long first, long long
   a->waypoint = w; a->store = c->opt_store ? 1 : 0;
   a->sample_stride = sample_stride_of(count);
   a->nruns = c->batch; a->W = c->W;
+  a->obs_counts = c->opt_obs_counts ? (unsigned long long*)c->d_obsct.p : nullptr;      // (non-null: the sampling launch is the counting form)
 }
 
 // state/param[w] from state/moments[w-1]: its own tiny launch for waypoint 0 and, when sharded,
@@ -354,6 +375,7 @@ size_t gmm_hot_launches(const pocs_ctx* c) { return (size_t)c->W; }
 int enqueue_gmm_tree(pocs_ctx* c, long long count) {
   const bool risk = risk_active(c);
   const int D = (int)c->tree.level.size() - 2;
+  if (int r = enqueue_obs_counts_reset(c)) return r;
   auto tree_launch = [&](pocs_gmm_launch* a, int d, int lo, int cnt) {
     fill_gmm_launch(c, a, 0, count, d, lo, cnt, 1);
     a->store = 0;
@@ -378,6 +400,7 @@ int enqueue_gmm_tree(pocs_ctx* c, long long count) {
 int enqueue_gmm_all(pocs_ctx* c, long long first, long long count, bool prof) {
   if (c->tree.n) return enqueue_gmm_tree(c, count);
   const int W = c->W, R = c->batch, G = gmm_groups(c);
+  if (int r = enqueue_obs_counts_reset(c)) return r;     // (ahead of the fork: every sub-batch's launches lie behind it)
   if (int r = enqueue_advance(c, 0)) return r;
   if (prof) HIPCHK(c, hipEventRecord(c->ev_seq[0], c->stream));
   if (G > 1) HIPCHK(c, hipEventRecord(c->ev_fork, c->stream));
@@ -554,9 +577,9 @@ int gmm_combine(pocs_ctx* c, const double* moments, double* probability, const u
 
 std::string config_key(const pocs_ctx* c, long long first, long long count, const char* tag) {
   char buf[256];
-  snprintf(buf, sizeof buf, "%s e%llu W%d K%d R%d g%d l%d x%d n%lld f%lld c%lld s%lld fu%lld st%p em%p", tag, c->epoch,
+  snprintf(buf, sizeof buf, "%s e%llu W%d K%d R%d g%d l%d x%d n%lld f%lld c%lld s%lld fu%lld oc%lld st%p em%p", tag, c->epoch,
            c->W, c->K, c->batch, gmm_groups(c), lone_call(c) ? 1 : 0, (c->xchg_connected && c->shard_first >= 0 && !c->ext_moments) ? c->xchg_world : 0,
-           c->num_gmm, first, count, c->opt_store, c->opt_fused, (void*)c->stream, (void*)c->ext_moments);
+           c->num_gmm, first, count, c->opt_store, c->opt_fused, c->opt_obs_counts, (void*)c->stream, (void*)c->ext_moments);
   std::string key = buf;
   if (c->tree.n) {                                   // a tree: the launches follow its shape (the levels' widths, the parents on the device)
     unsigned long long h = 1469598103934665603ull;   // FNV-1a over the slots' parents
@@ -605,6 +628,7 @@ int run_gmm_full(pocs_ctx* c, double* probability) {
 #else
   auto lap = [](const char*) {};
 #endif
+  c->res.oc_kind = 0;                                  // (the per-obstacle table is rewritten from here on; noted again behind the combine)
   if (int r = gmm_prepare(c)) return r;
   long long first, count;
   if (int r = gmm_shard(c, &first, &count)) return r;
@@ -668,6 +692,7 @@ int run_gmm_full(pocs_ctx* c, double* probability) {
     const unsigned* stop = risk_active(c) ? (const unsigned*)((double*)c->h_pin + pl.total + c->batch + 1) + 3 : nullptr;
     if (int r = gmm_combine(c, (double*)c->h_pin + pl.moments, probability, stop)) { reset_results(c); return r; }
   }
+  note_obs_counts(c, 1);
   c->res.last_gmm_count = count;
   c->res.last_gmm_wp = c->W - 1;
   lap("combined");
@@ -689,7 +714,7 @@ int mc_shard(pocs_ctx* c, long long* first, long long* count) {
 // call, or any MC call under POCS_OPT_MC_WAYPOINT_COUNTS, counts the first collisions per waypoint.  Both off: the launches,
 // the memset and the copies of an MC call are what they have always been.
 bool mc_stop_active(const pocs_ctx* c) { return c->opt_mc_rb && risk_active(c) && !c->tree.n; }     // (an MC call on a tree ignores the bound)
-bool mc_counts_active(const pocs_ctx* c) { return c->opt_mc_wp || mc_stop_active(c); }
+bool mc_counts_active(const pocs_ctx* c) { return c->opt_mc_wp || c->opt_obs_counts || mc_stop_active(c); }      // (the per-box counts split the per-waypoint ones)
 // The fused kernel carries a particle through all its steps and meets no other block on the way: a call that stops on a count
 // takes the per-step form.
 bool mc_fused_form(const pocs_ctx* c) { return c->opt_fused && !mc_stop_active(c); }
@@ -732,6 +757,10 @@ int enqueue_mc_all(pocs_ctx* c, long long first, long long count, bool prof) {
     a.wp_stop = (unsigned*)(a.wp_counts + (size_t)R * (size_t)W);
     a.wp_n = c->num_particles;                       // (a context with plans holds no shard: the run's particles)
     a.wp_bound = c->risk_bound;
+  }
+  if (c->opt_obs_counts) {
+    a.obs_counts = (unsigned long long*)c->d_obsct.p;
+    if (int r = enqueue_obs_counts_reset(c)) return r;
   }
   if (c->plans.n) {
     a.run_plan = (const double*)c->d_runplan.p;      // every run its own start mean and steps
@@ -828,6 +857,10 @@ int enqueue_mc_tree(pocs_ctx* c, long long count) {
   a.wp_counts = a.total + T;                         // [T] first collisions, by slot (W = 1: k_mc_init's row of run 0 is the root's)
   a.W = 1;
   a.mu0[0] = c->tree.pose[0]; a.mu0[1] = c->tree.pose[(size_t)T]; a.mu0[2] = c->tree.pose[2 * (size_t)T];
+  if (c->opt_obs_counts) {
+    a.obs_counts = (unsigned long long*)c->d_obsct.p;      // [T][64], by slot
+    if (int r = enqueue_obs_counts_reset(c)) return r;
+  }
   auto half_of = [&](pocs_mc_launch* l, int d) {
     const size_t o = (size_t)(d & 1) * half;
     l->x = (double*)c->d_px.p + o; l->y = (double*)c->d_py.p + o; l->th = (double*)c->d_pt.p + o; l->hits = (uint32_t*)c->d_hits.p + o;
@@ -854,6 +887,7 @@ int enqueue_mc_tree(pocs_ctx* c, long long count) {
 }
 
 int run_mc_tree(pocs_ctx* c) {
+  c->res.oc_kind = 0;
   if (int r = check_common(c)) return r;
   if (c->num_particles < 1) return fail(c, POCS_E_STATE, "setNumParticles missing");
   if (int r = upload_static(c)) return r;
@@ -872,6 +906,7 @@ int run_mc_tree(pocs_ctx* c) {
   if (int r = ensure(c, c->d_hits, 2 * half * sizeof(uint32_t))) return r;
   const size_t total_bytes = 2 * T * sizeof(unsigned long long);       // [T] collided at or before the node | [T] first collisions at it
   if (int r = ensure(c, c->d_total, total_bytes + 16)) return r;
+  if (int r = ensure_obs_counts(c)) return r;
   if (int r = ensure_pin(c)) return r;
   if (int r = stage_and_upload_runs(c, 1, 1)) return r;
   HIPCHK(c, hipMemsetAsync(c->d_total.p, 0, total_bytes, c->stream));
@@ -910,12 +945,14 @@ int run_mc_tree(pocs_ctx* c) {
   c->res.last_kind = 2;
   c->res.tree_last = 2;
   c->res.tree_sel = 0;
+  note_obs_counts(c, 2);
   return POCS_OK;
 }
 
 // One batch of MC roll-outs (runSimulation x batch) over this context's shard; fills c->res.mc_counts.
 int run_mc_local(pocs_ctx* c) {
   if (c->tree.n) return run_mc_tree(c);
+  c->res.oc_kind = 0;
   if (int r = check_common(c)) return r;
   if (c->num_particles < 1) return fail(c, POCS_E_STATE, "setNumParticles missing");
   long long first, count;
@@ -932,6 +969,7 @@ int run_mc_local(pocs_ctx* c) {
   if (int r = ensure(c, c->d_total, total_bytes + 16)) return r;
   if (c->plans.n)
     if (int r = ensure(c, c->d_runplan, R * 4 * sizeof(double))) return r;
+  if (int r = ensure_obs_counts(c)) return r;
   if (int r = ensure_pin(c)) return r;
   if (int r = stage_and_upload_runs(c, 1, 1)) return r;
   const bool prof = c->opt_profile == 1, span = c->opt_profile == 2 && c->opt_graph;      // (as run_gmm_full)
@@ -972,6 +1010,7 @@ int run_mc_local(pocs_ctx* c) {
   c->res.mc_wp.clear(); c->res.plan_E_mc.clear();
   if (mc_counts_active(c))
     if (int r = mc_read_waypoint_counts(c, (const unsigned long long*)((double*)c->h_pin + pl.total))) { reset_results(c); return r; }
+  note_obs_counts(c, 2);
   return POCS_OK;
 }
 
@@ -992,6 +1031,8 @@ int pocs_gmm_begin(pocs_ctx* c) {
   if (int r = gmm_upload_run(c)) return r;
   if (int r = prof_begin(c, (size_t)c->W)) return r;
   if (int r = enqueue_ticket_reset(c)) return r;
+  if (int r = enqueue_obs_counts_reset(c)) return r;
+  c->res.oc_kind = 0;                                 // (the table is this sequence's from here on; served once pocs_gmm_end has closed it)
   c->xchg_calls += 1;
   c->gmm_open = true;
   c->res.last_gmm_wp = -1;
@@ -1098,6 +1139,7 @@ int pocs_gmm_end(pocs_ctx* c, double* probability) {
   if (gave_up) { c->gmm_open = false; return fail(c, POCS_E_DEVICE, "a bounded wait expired on the device (code %u: 4 = a peer's moments never arrived); results discarded", gave_up); }
   if (int r = prof_collect(c, (size_t)c->W)) return r;
   (void)gmm_combine(c, (double*)c->h_pin + pl.moments, probability);      // (no risk bound in the step API: cannot fail)
+  note_obs_counts(c, 1);
   c->gmm_open = false;
   return POCS_OK;
 }

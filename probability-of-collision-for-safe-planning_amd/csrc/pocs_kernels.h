@@ -127,6 +127,10 @@ struct pocs_gmm_launch {
   // a tree of plans (pocs_set_plan_tree; behind everything else again).  Its launches work on the nodes of ONE level: a "run" is a
   // node's slot, nruns the number of nodes, W = 1 (every [run][W] array holds one row per node), `waypoint` the level's depth.
   const int* tree_parent;        // [nruns] the slot of every slot's parent (slot 0, the root: 0); null: not a tree launch
+  // per-obstacle collision counts (POCS_OPT_OBSTACLE_COUNTS; behind everything else again)
+  unsigned long long* obs_counts; // [nruns][W][POCS_MAX_OBSTACLES] samples of the shard drawn at (run, waypoint) whose footprint touches box m of
+                                 // the caller's table; non-null: the launch is the kernel's _boxes form.  Zeroed by pocs_launch_zero_counts
+                                 // at the head of the call's launches
 };
 // a tree's stop words: 0 = live, depth + 1 = the node's own closer found the bound reached, this bit = below such a node
 #define POCS_TREE_STOP_INHERITED 0x80000000u
@@ -170,6 +174,9 @@ struct pocs_mc_launch {               // blockIdx.y = run of the batch, like poc
   // of its own waypoint in `env` above; only the fused roll-out walks the array: env[min(w, env_steps - 1)] at waypoint w
   int env_steps;                       // pocs_launch_mc_fused: > 1 = k_mc_fused_sched over env[0 .. env_steps); 0 / 1: one world, k_mc_fused
   int env_pad;
+  // per-obstacle collision counts (POCS_OPT_OBSTACLE_COUNTS; behind everything else again): needs wp_mode != 0
+  unsigned long long* obs_counts;      // [nruns][W][POCS_MAX_OBSTACLES] particles of the shard whose FIRST collision is at waypoint w and which touch
+                                       // box m there (a tree: one row per slot); non-null: the kernels' MC_BOXES forms
 };
 
 
@@ -179,6 +186,7 @@ hipError_t pocs_launch_gmm_tree_advance(int K, const pocs_gmm_launch& a, hipStre
 hipError_t pocs_launch_gmm_tree_step(int K, const pocs_gmm_launch& a, hipStream_t s);       // grid = a.blocks
 hipError_t pocs_launch_gmm_close(int K, const pocs_gmm_launch& a, hipStream_t s);             // lone call: the last waypoint's rows -> moments
 hipError_t pocs_launch_gmm_exchange(int K, const pocs_gmm_launch& a, const pocs_xchg_dev& x, hipStream_t s);   // grid = a.nruns
+hipError_t pocs_launch_zero_counts(unsigned long long* p, size_t words, hipStream_t s);     // a kernel, not a memset: it sits inside the replayed graphs
 hipError_t pocs_launch_copy(const void* src, void* dst, long long bytes, hipStream_t s);
 hipError_t pocs_launch_fill(void* dst, long long bytes, hipStream_t s);
 hipError_t pocs_launch_probe_math(const pocs_tables* tables, int n, const uint32_t* wr, const uint32_t* wa, const double* x, double* out, hipStream_t s);   // out: 5 x n

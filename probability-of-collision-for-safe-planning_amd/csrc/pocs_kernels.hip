@@ -52,7 +52,20 @@ hipError_t with_K(const int K, F f) {
 hipError_t pocs_launch_gmm_step(int K, const pocs_gmm_launch& a, hipStream_t s) {
   return with_K(K, [&](auto k) {
     constexpr int KK = decltype(k)::value, TB = POCS_GMM_BLOCK_OF(KK);
-    if (a.risk) {
+    if (a.obs_counts) {                                // POCS_OPT_OBSTACLE_COUNTS: the same choice among the counting forms
+      if (a.M > POCS_MAX_OBSTACLES) return hipErrorInvalidValue;
+      if (a.risk) {
+        if (a.lone || a.exchange_in_tail || !a.stop || !a.surv) return hipErrorInvalidValue;
+        if (a.store) hipLaunchKernelGGL((k_gmm_step_risk_boxes<KK, true, TB>), dim3(a.blocks), dim3(TB), 0, s, a);
+        else         hipLaunchKernelGGL((k_gmm_step_risk_boxes<KK, false, TB>), dim3(a.blocks), dim3(TB), 0, s, a);
+      } else if (a.lone) {
+        if (a.store) hipLaunchKernelGGL((k_gmm_step_boxes<KK, true, TB, true>), dim3(a.blocks), dim3(TB), 0, s, a);
+        else         hipLaunchKernelGGL((k_gmm_step_boxes<KK, false, TB, true>), dim3(a.blocks), dim3(TB), 0, s, a);
+      } else {
+        if (a.store) hipLaunchKernelGGL((k_gmm_step_boxes<KK, true, TB, false>), dim3(a.blocks), dim3(TB), 0, s, a);
+        else         hipLaunchKernelGGL((k_gmm_step_boxes<KK, false, TB, false>), dim3(a.blocks), dim3(TB), 0, s, a);
+      }
+    } else if (a.risk) {
       if (a.lone || a.exchange_in_tail || !a.stop || !a.surv) return hipErrorInvalidValue;
       if (a.store) hipLaunchKernelGGL((k_gmm_step_risk<KK, true, TB>), dim3(a.blocks), dim3(TB), 0, s, a);
       else         hipLaunchKernelGGL((k_gmm_step_risk<KK, false, TB>), dim3(a.blocks), dim3(TB), 0, s, a);
@@ -90,8 +103,11 @@ hipError_t pocs_launch_gmm_tree_step(int K, const pocs_gmm_launch& a, hipStream_
     return hipErrorInvalidValue;
   return with_K(K, [&](auto k) {
     constexpr int KK = decltype(k)::value, TB = POCS_GMM_BLOCK_OF(KK);
-    if (a.risk) hipLaunchKernelGGL((k_gmm_step_tree<KK, TB, true>), dim3(a.blocks), dim3(TB), 0, s, a);
-    else        hipLaunchKernelGGL((k_gmm_step_tree<KK, TB, false>), dim3(a.blocks), dim3(TB), 0, s, a);
+    if (a.obs_counts) {
+      if (a.risk) hipLaunchKernelGGL((k_gmm_step_tree_boxes<KK, TB, true>), dim3(a.blocks), dim3(TB), 0, s, a);
+      else        hipLaunchKernelGGL((k_gmm_step_tree_boxes<KK, TB, false>), dim3(a.blocks), dim3(TB), 0, s, a);
+    } else if (a.risk) hipLaunchKernelGGL((k_gmm_step_tree<KK, TB, true>), dim3(a.blocks), dim3(TB), 0, s, a);
+    else               hipLaunchKernelGGL((k_gmm_step_tree<KK, TB, false>), dim3(a.blocks), dim3(TB), 0, s, a);
     return hipGetLastError();
   });
 }
@@ -110,21 +126,34 @@ hipError_t pocs_launch_mc_tree_step(int nblk, const pocs_mc_launch& a, hipStream
       a.tree_dst_lo < 1 || a.tree_lo < a.tree_dst_lo || a.tree_src_lo < 0 || a.tree_src_lo >= a.tree_dst_lo || a.tree_sx == a.x)
     return hipErrorInvalidValue;
   const dim3 grid(nblk, a.nruns), block(POCS_BLOCK);
-  if (a.nontemporal) hipLaunchKernelGGL(k_mc_tree_step<true>, grid, block, 0, s, a);
-  else               hipLaunchKernelGGL(k_mc_tree_step<false>, grid, block, 0, s, a);
+  if (a.obs_counts) {
+    if (a.nontemporal) hipLaunchKernelGGL(k_mc_tree_step_boxes<true>, grid, block, 0, s, a);
+    else               hipLaunchKernelGGL(k_mc_tree_step_boxes<false>, grid, block, 0, s, a);
+  } else if (a.nontemporal) hipLaunchKernelGGL(k_mc_tree_step<true>, grid, block, 0, s, a);
+  else                      hipLaunchKernelGGL(k_mc_tree_step<false>, grid, block, 0, s, a);
   return hipGetLastError();
 }
 
 hipError_t pocs_launch_mc_init(int nblk, const pocs_mc_launch& a, hipStream_t s) {
-  if (a.wp_mode != 0 && !a.wp_counts) return hipErrorInvalidValue;
-  if (a.wp_mode) hipLaunchKernelGGL(k_mc_init<MC_COUNTS>, dim3(nblk, a.nruns), dim3(POCS_BLOCK), 0, s, a);
+  if ((a.wp_mode != 0 && !a.wp_counts) || (a.obs_counts && !a.wp_mode)) return hipErrorInvalidValue;
+  if (a.obs_counts) hipLaunchKernelGGL(k_mc_init<MC_COUNTS | MC_BOXES>, dim3(nblk, a.nruns), dim3(POCS_BLOCK), 0, s, a);
+  else if (a.wp_mode) hipLaunchKernelGGL(k_mc_init<MC_COUNTS>, dim3(nblk, a.nruns), dim3(POCS_BLOCK), 0, s, a);
   else           hipLaunchKernelGGL(k_mc_init<MC_PLAIN>, dim3(nblk, a.nruns), dim3(POCS_BLOCK), 0, s, a);
   return hipGetLastError();
 }
 hipError_t pocs_launch_mc_step(int nblk, const pocs_mc_launch& a, hipStream_t s) {
   const dim3 grid(nblk, a.nruns), block(POCS_BLOCK);
-  if (a.wp_mode != 0 && !a.wp_counts) return hipErrorInvalidValue;
-  if (a.wp_mode == 2) {                               // first collisions per waypoint, and the risk bound obeyed
+  if ((a.wp_mode != 0 && !a.wp_counts) || (a.obs_counts && !a.wp_mode)) return hipErrorInvalidValue;
+  if (a.obs_counts) {                                 // ... and per obstacle box: the MC_BOXES forms of the two below
+    if (a.step < 0 || a.step + 1 >= a.W || (a.wp_mode == 2 && (!a.wp_stop || a.wp_n < 1))) return hipErrorInvalidValue;
+    if (a.wp_mode == 2) {
+      if (a.nontemporal) hipLaunchKernelGGL((k_mc_step_counts<true, MC_STOP | MC_BOXES>), grid, block, 0, s, a);
+      else               hipLaunchKernelGGL((k_mc_step_counts<false, MC_STOP | MC_BOXES>), grid, block, 0, s, a);
+    } else {
+      if (a.nontemporal) hipLaunchKernelGGL((k_mc_step_counts<true, MC_COUNTS | MC_BOXES>), grid, block, 0, s, a);
+      else               hipLaunchKernelGGL((k_mc_step_counts<false, MC_COUNTS | MC_BOXES>), grid, block, 0, s, a);
+    }
+  } else if (a.wp_mode == 2) {                               // first collisions per waypoint, and the risk bound obeyed
     if (!a.wp_stop || a.wp_n < 1 || a.step < 0 || a.step + 1 >= a.W) return hipErrorInvalidValue;
     if (a.nontemporal) hipLaunchKernelGGL((k_mc_step_counts<true, MC_STOP>), grid, block, 0, s, a);
     else               hipLaunchKernelGGL((k_mc_step_counts<false, MC_STOP>), grid, block, 0, s, a);
@@ -137,8 +166,11 @@ hipError_t pocs_launch_mc_step(int nblk, const pocs_mc_launch& a, hipStream_t s)
   return hipGetLastError();
 }
 hipError_t pocs_launch_mc_fused(int nblk, const pocs_mc_launch& a, hipStream_t s) {
-  if (a.wp_mode == 2 || (a.wp_mode != 0 && !a.wp_counts)) return hipErrorInvalidValue;      // (no stop without a launch boundary per step)
-  if (a.env_steps > 1) {                              // an obstacle schedule: the world is restaged per step
+  if (a.wp_mode == 2 || (a.wp_mode != 0 && !a.wp_counts) || (a.obs_counts && !a.wp_mode)) return hipErrorInvalidValue;      // (no stop without a launch boundary per step)
+  if (a.obs_counts) {
+    if (a.env_steps > 1) hipLaunchKernelGGL(k_mc_fused_sched<MC_COUNTS | MC_BOXES>, dim3(nblk, a.nruns), dim3(POCS_BLOCK), 0, s, a);
+    else                 hipLaunchKernelGGL(k_mc_fused_boxes, dim3(nblk, a.nruns), dim3(POCS_BLOCK), 0, s, a);
+  } else if (a.env_steps > 1) {                              // an obstacle schedule: the world is restaged per step
     if (a.wp_mode) hipLaunchKernelGGL(k_mc_fused_sched<MC_COUNTS>, dim3(nblk, a.nruns), dim3(POCS_BLOCK), 0, s, a);
     else           hipLaunchKernelGGL(k_mc_fused_sched<MC_PLAIN>, dim3(nblk, a.nruns), dim3(POCS_BLOCK), 0, s, a);
   } else if (a.wp_mode) hipLaunchKernelGGL(k_mc_fused_counts, dim3(nblk, a.nruns), dim3(POCS_BLOCK), 0, s, a);
@@ -147,6 +179,20 @@ hipError_t pocs_launch_mc_fused(int nblk, const pocs_mc_launch& a, hipStream_t s
 }
 hipError_t pocs_launch_mc_count(int nblk, const pocs_mc_launch& a, hipStream_t s) {
   hipLaunchKernelGGL(k_mc_count, dim3(nblk, a.nruns), dim3(POCS_BLOCK), 0, s, a);
+  return hipGetLastError();
+}
+
+// The per-obstacle counts of a call start at zero (POCS_OPT_OBSTACLE_COUNTS): a kernel, so that the replayed graph -- kernel
+// nodes only -- zeroes them itself.
+__global__ __launch_bounds__(POCS_BLOCK) void k_zero_counts(unsigned long long* __restrict__ p, size_t n) {
+  const size_t stride = (size_t)gridDim.x * POCS_BLOCK;
+  for (size_t i = (size_t)blockIdx.x * POCS_BLOCK + threadIdx.x; i < n; i += stride) p[i] = 0ull;
+}
+hipError_t pocs_launch_zero_counts(unsigned long long* p, size_t words, hipStream_t s) {
+  if (!p) return hipErrorInvalidValue;
+  if (words == 0) return hipSuccess;
+  const size_t nb = (words + POCS_BLOCK - 1) / POCS_BLOCK;
+  hipLaunchKernelGGL(k_zero_counts, dim3((unsigned)(nb < POCS_MAX_BLOCKS ? nb : POCS_MAX_BLOCKS)), dim3(POCS_BLOCK), 0, s, p, words);
   return hipGetLastError();
 }
 
