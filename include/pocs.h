@@ -72,6 +72,41 @@ int pocs_set_obstacles(pocs_ctx* ctx, const double* boxes, int M);
 int pocs_set_obstacle_schedule(pocs_ctx* ctx, const double* boxes, int M, int S);  /* boxes: S x M x {cx, cy, half_x, half_y, yaw_rad} */
 int pocs_get_world_steps(const pocs_ctx* ctx);                                      /* S of the schedule in force; 1 for a static world; 0 for none */
 
+/* ---- large worlds: up to POCS_MAX_WORLD_BOXES boxes (ours) -----------------------------------
+ * What a planner hands over is often an occupancy grid or a wall made of many small boxes: hundreds to thousands of boxes, almost
+ * none of them near the robot at any one waypoint.  pocs_set_world takes such a table:
+ *   boxes: M x {cx, cy, half_x, half_y, yaw_rad}, 0 <= M <= POCS_MAX_WORLD_BOXES.
+ * With M <= 64 it IS pocs_set_obstacles(boxes, M): the same device state, the same kernels, the same bits.  With M > 64 it installs a
+ * LARGE static world, and 64 (POCS_MAX_OBSTACLES) becomes the number of boxes that may be IN REACH of one run at one waypoint:
+ *   - both estimators compute, bit for bit, what the full loop over all M boxes computes (what the CPU oracle computes).  Nothing
+ *     spatial is built: the GMM path culls the table by brute force once per run and waypoint -- one small launch in front of every
+ *     waypoint's sampling launch, inside the same replayed graph -- against the box of every pose the run's mixture can draw; the MC
+ *     path culls it per wave and particle iteration against the box of the wave's 64 poses (DESIGN.md sections 1 and 5);
+ *   - a GMM call in which some run has more than 64 boxes in reach at some waypoint fails with POCS_E_STATE (the message names the
+ *     lowest such waypoint and its count), its results are discarded and the context stays usable; an MC call has no such limit;
+ *   - pocs_get_world_reach: for the selected run (pocs_select_batch_run; plan p while plans are set; the run served last under
+ *     run-ahead) of the last GMM call, per waypoint the number of boxes its cull kept; a waypoint that was not evaluated (behind a
+ *     stop under the risk bound) gives 0.  Writes and returns the run's (the plan's) number of waypoints; stays readable after a
+ *     call that failed on overflow; POCS_E_STATE when the last GMM call did not run under a large world, POCS_E_BUFFER for a short
+ *     buffer;
+ *   - batches, run-ahead, sub-batches, pocs_set_plans, the risk bound (GMM and MC), POCS_OPT_MC_WAYPOINT_COUNTS, POCS_OPT_STORE_SAMPLES,
+ *     POCS_OPT_MC_NONTEMPORAL work as under a small world and give the bits a small world with the same boxes in reach gives.  A GMM
+ *     call of ONE run takes the ticket form (the lone form builds a waypoint's mixture in its own heads, so nothing could cull ahead
+ *     of it): POCS_OPT_LONE_CALL has no effect under a large world; the results are the same bits either way.
+ * It replaces whatever world or schedule was set; pocs_set_obstacles, pocs_set_obstacle_schedule and clearObstacles replace a large
+ * world.  pocs_set_footprint re-prepares its records.  pocs_get_world_steps answers 1.
+ * REFUSED under a large world, each with a message that names the combination, the context left as it was: POCS_OPT_OBSTACLE_COUNTS = 1
+ * and POCS_OPT_MC_FUSED = 1 (POCS_E_STATE, whichever of the two is set second), pocs_set_plan_tree, pocs_set_shard, the step API
+ * (pocs_gmm_begin, pocs_gmm_bind_moments), the exchange (pocs_xchg_create / pocs_xchg_connect), pocs_probe_device_collide
+ * (POCS_E_STATE); addObstacle (POCS_E_ARG); an obstacle schedule keeps its limit of 64 boxes per step.
+ * POCS_E_ARG (the world in force stays): M out of range, a null `boxes` with M > 0, a half extent <= 0, and for M > 64 any value that
+ * is not finite.  The text channel has no command for it.
+ * pocs_get_world_boxes: M of the world in force -- a large world's, a static world's, a schedule's boxes per step; 0 without one. */
+#define POCS_MAX_WORLD_BOXES 4096
+int pocs_set_world(pocs_ctx* ctx, const double* boxes, int M);          /* boxes: M x {cx, cy, half_x, half_y, yaw_rad} */
+int pocs_get_world_boxes(const pocs_ctx* ctx);
+int pocs_get_world_reach(pocs_ctx* ctx, int* out, int cap);             /* per waypoint: boxes in reach of the selected run in the last GMM call */
+
 /* ---- typed twins of the setter commands (argument order = token order of the command) ---- */
 int pocs_set_alphas(pocs_ctx* ctx, const double* alphas, int n);            /* mcsimplugin.cpp:174-187 -> MCSimulator.h:224-230; n must be 4 */
 int pocs_set_q(pocs_ctx* ctx, double q);                                    /* :168-172 -> :232-235 */
@@ -119,7 +154,8 @@ int pocs_send_command(pocs_ctx* ctx, const char* line, char* out, size_t cap);
 #define POCS_OPT_LONE_CALL 7       /* 1 (default): a whole-run GMM call of ONE run (batch 1, no run-ahead, one GPU) uses launches that close
                                       the previous waypoint in every block's head instead of tickets and a closing block (no one else
                                       is in flight to hide a closer behind): 10 % less time per waypoint, the same bits
-                                      (tests/test_gpu_parity.py::test_lone_call_changes_no_bit).  0: the ticket form always. */
+                                      (tests/test_gpu_parity.py::test_lone_call_changes_no_bit).  0: the ticket form always.  No effect under
+                                      a large world (pocs_set_world with more than 64 boxes): the ticket form always, the same bits. */
 #define POCS_OPT_SUB_BATCHES 8     /* 0 (default): a whole-run call of >= 8 runs and >= 1.2e6 evaluations per waypoint is issued as TWO sub-batches
                                       on two streams, so that one sub-batch's launch tail (its last blocks' slow end, the serial mixture advance
                                       of its last closer, the launch boundary) is covered by the other's sampling blocks: +4 ... +11 % measured;

@@ -21,6 +21,7 @@ NMOM = 11
 MAX_PLANS = 256
 MAX_TREE_NODES = 4096
 MAX_WORLD_STEPS = 4096
+MAX_WORLD_BOXES = 4096             # POCS_MAX_WORLD_BOXES: the largest table pocs_set_world takes
 
 _dp = C.POINTER(C.c_double)
 _vp = C.c_void_p
@@ -35,6 +36,9 @@ SIGNATURES = {
     "pocs_set_obstacles": (C.c_int, [_vp, _dp, C.c_int]),
     "pocs_set_obstacle_schedule": (C.c_int, [_vp, _dp, C.c_int, C.c_int]),
     "pocs_get_world_steps": (C.c_int, [_vp]),
+    "pocs_set_world": (C.c_int, [_vp, _dp, C.c_int]),
+    "pocs_get_world_boxes": (C.c_int, [_vp]),
+    "pocs_get_world_reach": (C.c_int, [_vp, C.POINTER(C.c_int), C.c_int]),
     "pocs_set_alphas": (C.c_int, [_vp, _dp, C.c_int]),
     "pocs_set_q": (C.c_int, [_vp, C.c_double]),
     "pocs_set_num_landmarks": (C.c_int, [_vp, C.c_int]),
@@ -249,6 +253,24 @@ class Context:
     def world_steps(self):
         """S of the obstacle schedule in force; 1 for a static world; 0 for a context without a collision world."""
         return self.lib.pocs_get_world_steps(self.h)
+
+    def set_world(self, boxes):
+        """A static world of up to MAX_WORLD_BOXES boxes, shape (M, 5) = {cx, cy, half_x, half_y, yaw}; the footprint stays as set
+        (set_env, configure).  Up to 64 boxes it is set_env's world; above, a large world (include/pocs.h)."""
+        b = _arr(boxes).reshape(-1, 5)
+        self._chk(self.lib.pocs_set_world(self.h, b.ctypes.data_as(_dp) if b.size else None, b.shape[0]))
+
+    def world_boxes(self):
+        """Boxes of the world in force (a large world's, a static world's, a schedule's per step); 0 without a world."""
+        return self.lib.pocs_get_world_boxes(self.h)
+
+    def world_reach(self):
+        """Per waypoint of the selected run (or plan) of the last GMM call under a large world: how many boxes its cull kept
+        (int32 array; 0 for a waypoint that was not evaluated).  Readable after a call that failed on overflow."""
+        W = max(self.path_length(), 1)
+        out = np.zeros(W, dtype=np.int32)
+        got = self._chk(self.lib.pocs_get_world_reach(self.h, out.ctypes.data_as(C.POINTER(C.c_int)), W))
+        return out[:got]
 
     def set_alphas(self, a):
         a = _arr(a)

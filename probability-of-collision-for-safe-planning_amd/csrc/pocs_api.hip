@@ -97,7 +97,7 @@ void pocs_destroy(pocs_ctx* c) {
     DevBuf* all[] = {&c->d_env, &c->d_sensor, &c->d_hdr, &c->d_chain, &c->d_state, &c->d_param,
                      &c->d_moments, &c->d_partial, &c->d_sx, &c->d_sy, &c->d_st, &c->d_flags,
                      &c->d_px, &c->d_py, &c->d_pt, &c->d_hits, &c->d_total, &c->d_ticket, &c->d_tables, &c->d_runplan, &c->d_surv, &c->d_tparent,
-                     &c->d_obsct};
+                     &c->d_obsct, &c->d_world, &c->d_kept, &c->d_keptidx, &c->d_reach};
     for (DevBuf* b : all) if (b->p) hipFree(b->p);
     if (c->h_pin) hipHostFree(c->h_pin);
     if (c->h_copy) hipHostFree(c->h_copy);
@@ -130,6 +130,7 @@ int pocs_set_obstacles(pocs_ctx* c, const double* boxes, int M) {
       return fail(c, POCS_E_ARG, "obstacle %d: half extents must be > 0", m);
   c->boxes.assign(boxes, boxes + (size_t)M * 5);
   c->world_S = 1;                                    // (a schedule gives way to the static world)
+  c->world.clear();                                  // (and so does a large world)
   c->have_obstacles = true;
   c->env_dirty = true;
   return POCS_OK;
@@ -153,12 +154,66 @@ int pocs_set_obstacle_schedule(pocs_ctx* c, const double* boxes, int M, int S) {
     }
   c->boxes.assign(boxes, boxes + (size_t)S * (size_t)M * 5);
   c->world_S = S;
+  c->world.clear();                                  // (a large world gives way to the schedule)
   c->have_obstacles = true;
   c->env_dirty = true;
   return POCS_OK;
 }
 
 int pocs_get_world_steps(const pocs_ctx* c) { return (c && c->have_obstacles) ? c->world_S : 0; }
+
+// What a large world does not serve, checked where the world or the other half of the combination is set: the context keeps what
+// it had.  `what`: the caller's name for the message.
+static int refuse_with_large_world(pocs_ctx* c, const char* what) {
+  if (c->opt_obs_counts) return fail(c, POCS_E_STATE, "%s: POCS_OPT_OBSTACLE_COUNTS is on; the per-box counts serve worlds of at most %d boxes", what, POCS_MAX_OBSTACLES);
+  if (c->opt_fused) return fail(c, POCS_E_STATE, "%s: POCS_OPT_MC_FUSED is on; the fused roll-out serves worlds of at most %d boxes", what, POCS_MAX_OBSTACLES);
+  if (c->tree.n) return fail(c, POCS_E_STATE, "%s: a tree of plans is set; trees serve worlds of at most %d boxes", what, POCS_MAX_OBSTACLES);
+  if (c->shard_first >= 0) return fail(c, POCS_E_STATE, "%s: a shard is set; sharded runs serve worlds of at most %d boxes", what, POCS_MAX_OBSTACLES);
+  if (c->xchg_own || c->xchg_connected) return fail(c, POCS_E_STATE, "%s: the context takes part in the in-library exchange, which serves worlds of at most %d boxes", what, POCS_MAX_OBSTACLES);
+  if (c->ext_moments) return fail(c, POCS_E_STATE, "%s: a caller-owned moments buffer is bound (the step API), which serves worlds of at most %d boxes", what, POCS_MAX_OBSTACLES);
+  if (c->gmm_open) return fail(c, POCS_E_ORDER, "%s inside a begin/end sequence", what);
+  return POCS_OK;
+}
+
+// A static world of up to POCS_MAX_WORLD_BOXES boxes.  Up to POCS_MAX_OBSTACLES it IS pocs_set_obstacles; above, the boxes are kept
+// apart from the staged table (which is then empty): upload_world prepares their records, the GMM launches get a cull launch in
+// front of each waypoint and the _world forms of the sampling kernel, the MC launches the _world forms of theirs.
+int pocs_set_world(pocs_ctx* c, const double* boxes, int M) {
+  if (c) touch(c);
+  if (!c) return POCS_E_ARG;
+  if (M < 0 || M > POCS_MAX_WORLD_BOXES || (M > 0 && !boxes))
+    return fail(c, POCS_E_ARG, "world of %d boxes outside 0..%d (or null boxes)", M, POCS_MAX_WORLD_BOXES);
+  if (M <= POCS_MAX_OBSTACLES) return pocs_set_obstacles(c, boxes, M);
+  for (int m = 0; m < M; ++m) {
+    for (int j = 0; j < 5; ++j)
+      if (!std::isfinite(boxes[5 * (size_t)m + j])) return fail(c, POCS_E_ARG, "world: box %d: value %d is not finite", m, j);
+    if (!(boxes[5 * (size_t)m + 2] > 0) || !(boxes[5 * (size_t)m + 3] > 0))
+      return fail(c, POCS_E_ARG, "world: box %d: half extents must be > 0", m);
+  }
+  if (int r = refuse_with_large_world(c, "pocs_set_world with more than 64 boxes")) return r;
+  c->world.assign(boxes, boxes + (size_t)M * 5);
+  c->boxes.clear();                                  // (the staged table holds nothing; a schedule gives way)
+  c->world_S = 1;
+  c->have_obstacles = true;
+  c->env_dirty = true;
+  return POCS_OK;
+}
+
+int pocs_get_world_boxes(const pocs_ctx* c) {
+  if (!c || !c->have_obstacles) return 0;
+  return large_world(c) ? large_boxes(c) : world_boxes(c);
+}
+
+int pocs_get_world_reach(pocs_ctx* c, int* out, int cap) {
+  if (!c || !out) return POCS_E_ARG;
+  if (c->reach_R < 1 || c->reach.empty())
+    return fail(c, POCS_E_STATE, "pocs_get_world_reach: the last GMM call did not run under a large world (pocs_set_world with more than %d boxes)", POCS_MAX_OBSTACLES);
+  const int r = c->res.view >= 0 && c->res.view < c->reach_R ? c->res.view : 0;
+  const int n = c->reach_len[(size_t)r];
+  if (n > cap) return fail(c, POCS_E_BUFFER, "need %d ints", n);
+  memcpy(out, &c->reach[(size_t)r * (size_t)c->reach_W], (size_t)n * sizeof(int));
+  return n;
+}
 
 int pocs_set_alphas(pocs_ctx* c, const double* a, int n) {
   if (c) touch(c);
@@ -275,7 +330,10 @@ int pocs_set_option(pocs_ctx* c, int option, long long value) {
   if (!c) return POCS_E_ARG;
   switch (option) {
     case POCS_OPT_STORE_SAMPLES: c->opt_store = value ? 1 : 0; break;
-    case POCS_OPT_MC_FUSED: c->opt_fused = value ? 1 : 0; break;
+    case POCS_OPT_MC_FUSED:
+      if (value && large_world(c)) return fail(c, POCS_E_STATE, "POCS_OPT_MC_FUSED = 1 under a large world of %d boxes (pocs_set_world): the fused roll-out serves worlds of at most %d boxes", large_boxes(c), POCS_MAX_OBSTACLES);
+      c->opt_fused = value ? 1 : 0;
+      break;
     case POCS_OPT_USE_GRAPH: c->opt_graph = value ? 1 : 0; break;
     case POCS_OPT_PROFILE:
       if (value < 0 || value > 2) return fail(c, POCS_E_ARG, "POCS_OPT_PROFILE takes 0, 1 or 2");
@@ -310,6 +368,7 @@ int pocs_set_option(pocs_ctx* c, int option, long long value) {
     case POCS_OPT_OBSTACLE_COUNTS:
       if (value < 0 || value > 1) return fail(c, POCS_E_ARG, "POCS_OPT_OBSTACLE_COUNTS takes 0 or 1");
       if (c->gmm_open) return fail(c, POCS_E_ORDER, "POCS_OPT_OBSTACLE_COUNTS inside a begin/end sequence");
+      if (value && large_world(c)) return fail(c, POCS_E_STATE, "POCS_OPT_OBSTACLE_COUNTS = 1 under a large world of %d boxes (pocs_set_world): the per-box counts serve worlds of at most %d boxes", large_boxes(c), POCS_MAX_OBSTACLES);
       c->opt_obs_counts = value;
       c->res.oc_kind = 0;                            // (a table is served until the option is touched or the next call)
       break;
@@ -411,6 +470,7 @@ int pocs_set_plan_tree(pocs_ctx* c, int nodes, const int* parent, const double* 
     return POCS_OK;
   }
   if (c->plans.n) return fail(c, POCS_E_ORDER, "pocs_set_plan_tree while plans are set: clear them first with pocs_set_plans(ctx, 0, ...)");
+  if (large_world(c)) return fail(c, POCS_E_STATE, "pocs_set_plan_tree under a large world of %d boxes (pocs_set_world): trees serve worlds of at most %d boxes", large_boxes(c), POCS_MAX_OBSTACLES);
   if (!parent || !poses || (nodes > 1 && !odoms)) return fail(c, POCS_E_ARG, "tree: null parents, poses or controls");
   if (parent[0] != -1) return fail(c, POCS_E_ARG, "tree: node 0 is the root, its parent must be -1 (got %d)", parent[0]);
   for (int n = 1; n < nodes; ++n)
@@ -501,6 +561,7 @@ int pocs_set_shard(pocs_ctx* c, long long first, long long count) {
   if (first == -1 && count == -1) { c->shard_first = -1; c->shard_count = -1; return POCS_OK; }   // whole range
   if (c->plans.n) return fail(c, POCS_E_STATE, "pocs_set_shard: plans are set (multi-GPU plan batches are not supported)");
   if (c->tree.n) return fail(c, POCS_E_STATE, "pocs_set_shard: a tree of plans is set (trees run on one GPU)");
+  if (large_world(c)) return fail(c, POCS_E_STATE, "pocs_set_shard under a large world of %d boxes (pocs_set_world): sharded runs serve worlds of at most %d boxes", large_boxes(c), POCS_MAX_OBSTACLES);
   if (first < 0 || count < 0) return fail(c, POCS_E_ARG, "negative shard");
   c->shard_first = first; c->shard_count = count;
   return POCS_OK;
@@ -517,6 +578,7 @@ int pocs_set_stream(pocs_ctx* c, void* s) {
 int pocs_gmm_bind_moments(pocs_ctx* c, void* dptr, long long len) {
   if (c) touch(c);
   if (!c) return POCS_E_ARG;
+  if (dptr && large_world(c)) return fail(c, POCS_E_STATE, "pocs_gmm_bind_moments under a large world of %d boxes (pocs_set_world): the step API serves worlds of at most %d boxes", large_boxes(c), POCS_MAX_OBSTACLES);
   c->ext_moments = (double*)dptr; c->ext_moments_len = dptr ? len : 0;
   drop_graphs(c);
   return POCS_OK;
@@ -638,6 +700,7 @@ int pocs_xchg_create(pocs_ctx* c, int world, int rank, void* handle64) {
   static_assert(sizeof(hipIpcMemHandle_t) == 64, "pocs.h promises a 64-byte handle");
   if (c->plans.n) return fail(c, POCS_E_STATE, "pocs_xchg_create: plans are set (multi-GPU plan batches are not supported)");
   if (c->tree.n) return fail(c, POCS_E_STATE, "pocs_xchg_create: a tree of plans is set (trees run on one GPU)");
+  if (large_world(c)) return fail(c, POCS_E_STATE, "pocs_xchg_create under a large world of %d boxes (pocs_set_world): the exchange serves worlds of at most %d boxes", large_boxes(c), POCS_MAX_OBSTACLES);
   HIPCHK(c, hipSetDevice(c->device));
   if (!c->xchg_own) {
     // FINE-GRAINED device memory: other GPUs write into it and this GPU polls it inside a running kernel.
@@ -658,6 +721,7 @@ int pocs_xchg_connect(pocs_ctx* c, const void* handles, int world) {
   if (!c || !handles) return POCS_E_ARG;
   if (c->plans.n) return fail(c, POCS_E_STATE, "pocs_xchg_connect: plans are set (multi-GPU plan batches are not supported)");
   if (c->tree.n) return fail(c, POCS_E_STATE, "pocs_xchg_connect: a tree of plans is set (trees run on one GPU)");
+  if (large_world(c)) return fail(c, POCS_E_STATE, "pocs_xchg_connect under a large world of %d boxes (pocs_set_world): the exchange serves worlds of at most %d boxes", large_boxes(c), POCS_MAX_OBSTACLES);
   if (!c->xchg_own || world != c->xchg_world) return fail(c, POCS_E_ORDER, "pocs_xchg_connect before pocs_xchg_create (or another world size)");
   HIPCHK(c, hipSetDevice(c->device));
   for (int q = 0; q < world; ++q) {
@@ -721,6 +785,7 @@ int pocs_send_command(pocs_ctx* c, const char* line, char* out, size_t cap) {
     case pocs_cmd::kSetSeed: return pocs_set_seed(c, (uint64_t)p.seed);
     case pocs_cmd::kSetFootprint: return pocs_set_footprint(c, v[0], v[1], v[2], v[3]);
     case pocs_cmd::kAddObstacle: {
+      if (large_world(c)) return fail(c, POCS_E_ARG, "addObstacle: the world holds %d boxes (pocs_set_world); the text channel serves worlds of at most %d", large_boxes(c), POCS_MAX_OBSTACLES);
       std::vector<double> b(c->boxes.begin(), c->boxes.begin() + (size_t)world_boxes(c) * 5);   // (under a schedule: world 0)
       b.insert(b.end(), v.begin(), v.end());
       return pocs_set_obstacles(c, b.data(), (int)(b.size() / 5));

@@ -253,6 +253,8 @@ int pocs_probe_device_collide(pocs_ctx* c, int K, const double* params, int n, c
     return fail(c, POCS_E_ARG, "pocs_probe_device_collide: 1 <= n <= 2^20, 1 <= K <= %d, no null pointers", POCS_MAX_GAUSSIANS);
   if (!c->have_obstacles)
     return fail(c, POCS_E_STATE, "no collision world: pocs_set_obstacles / addObstacle / clearObstacles missing");
+  if (large_world(c))
+    return fail(c, POCS_E_STATE, "pocs_probe_device_collide under a large world of %d boxes (pocs_set_world): the probe stages worlds of at most %d boxes", large_boxes(c), POCS_MAX_OBSTACLES);
   // (a heading that is not a number has no sector: nothing of the kind reaches the device)
   const size_t PS = (size_t)K * POCS_PARAM_STRIDE;
   for (size_t j = 0; j < PS; ++j)

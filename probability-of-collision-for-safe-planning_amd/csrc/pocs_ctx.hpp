@@ -125,6 +125,14 @@ struct pocs_ctx {
   std::vector<double> boxes;             // world_S x M x 5: world s is the collision world at waypoint s (the last one holds behind it)
   int world_S = 1;                       // steps of the obstacle schedule (pocs_set_obstacle_schedule); 1: a static world (pocs_set_obstacles)
   bool have_obstacles = false;           // pocs_set_obstacles / addObstacle / clearObstacles was called at least once
+  // a large static world (pocs_set_world with more than POCS_MAX_OBSTACLES boxes): M x 5, and `boxes` above is empty -- the table
+  // of at most POCS_MAX_OBSTACLES records that every kernel stages holds nothing then; empty: no large world
+  std::vector<double> world;
+  // how many records the cull of the last GMM call under a large world kept per waypoint (pocs_get_world_reach), in run / plan
+  // order: [reach_R][reach_W], and the waypoints of each row that mean something.  Not part of `res`: it outlives a call that
+  // failed on overflow
+  std::vector<int> reach, reach_len;
+  int reach_R = 0, reach_W = 0;
   long long shard_first = -1, shard_count = -1;
   long long opt_store = 1, opt_fused = 0, opt_graph = 1, opt_profile = 0, opt_lone = 1, opt_groups = 0, opt_mc_nt = -1;
   unsigned long long epoch = 0;          // bumped by every setter; part of the graph cache key
@@ -167,6 +175,10 @@ struct pocs_ctx {
   pocs_rt::DevBuf d_runplan;             // a call of plans: [R][4] start mean and steps per run (the MC kernels)
   pocs_rt::DevBuf d_surv;                // a call of plans under a risk bound: [R] running survival product of every run
   pocs_rt::DevBuf d_tparent;             // a tree of plans: [T] int, the slot of every slot's parent
+  // a large world: its prepared records [M][POCS_OBS_STRIDE]; per batch slot the records k_world_cull kept for the waypoint being
+  // sampled [slots][POCS_MAX_OBSTACLES][POCS_OBS_STRIDE], their indices in the caller's table [slots][POCS_MAX_OBSTACLES] int, and the
+  // kept counts [slots][W] int, zeroed at the head of every call
+  pocs_rt::DevBuf d_world, d_kept, d_keptidx, d_reach;
   pocs_rt::DevBuf d_obsct;               // POCS_OPT_OBSTACLE_COUNTS: [slots][W][POCS_MAX_OBSTACLES] u64, zeroed by a kernel at the head of every call's launches
   // one-hop exchange (pocs_xchg_*): this rank's buffer, the peers' buffers as mapped here
   void* xchg_own = nullptr;
@@ -268,6 +280,11 @@ inline int world_boxes(const pocs_ctx* c) { return (int)(c->boxes.size() / 5 / (
 inline const pocs_env_dev* world_at(const pocs_ctx* c, int w) {
   return (const pocs_env_dev*)c->d_env.p + (w < 0 ? 0 : w < c->world_S ? w : c->world_S - 1);
 }
+
+// A large world is in force (pocs_set_world with more than POCS_MAX_OBSTACLES boxes), and its number of boxes.
+static_assert(POCS_MAX_WORLD_RECORDS == POCS_MAX_WORLD_BOXES, "pocs_kernels.h restates the public limit");
+inline bool large_world(const pocs_ctx* c) { return !c->world.empty(); }
+inline int large_boxes(const pocs_ctx* c) { return (int)(c->world.size() / 5); }
 
 inline double* moments_dev(pocs_ctx* c) { return c->ext_moments ? c->ext_moments : (double*)c->d_moments.p; }
 inline long long sample_stride_of(long long count) { return count > 0 ? ((count + 1) & ~1LL) : 2; }   // even

@@ -27,7 +27,9 @@
 //                             The waypoint loop never returns to the host.  (k_gmm_step_risk, k_gmm_step_tree: the same block
 //                             under a risk bound / for one level of a tree of plans; k_gmm_close: the lone form's last rows;
 //                             k_gmm_step_boxes, k_gmm_step_risk_boxes, k_gmm_step_tree_boxes: the counting forms of the three, which
-//                             also count per obstacle box the samples that touch it, POCS_OPT_OBSTACLE_COUNTS.)
+//                             also count per obstacle box the samples that touch it, POCS_OPT_OBSTACLE_COUNTS; k_gmm_step_world,
+//                             k_gmm_step_risk_world: the forms under a large collision world, pocs_set_world, whose heads fetch the
+//                             records that k_world_cull -- one launch in front of each of theirs -- has left for their runs.)
 
 // LDS of k_gmm_step.  A block works through a contiguous range of the launch's UNITS -- (run, virtual slice)
 // pairs, pocs_kernels.h -- that may cross from one run into the next: everything per run is held twice.
@@ -144,6 +146,26 @@ __device__ __forceinline__ void flush_unit(gmm_smem<K, TB, OC>& sm, const int wa
 // robot's heading is known to a fraction of a radian -- most of a plan -- far fewer poses reach the
 // narrow phase, and none that could touch is lost: the flags do not change.
 //   (pocs_footprint_extent, pocs_collide.h: host + device, checked on the CPU against a dense scan)
+// The run's reach and the footprint's extents over its headings as ONE wave forms them (all 64 lanes), for k_world_cull: the
+// arithmetic of gmm_cull below through the host + device functions of pocs_world.h, the four end values side by side in lanes
+// 0 .. 3 as there.  (gmm_cull keeps its own text: built on top of this function it computed the same values with the
+// instructions of every sampling kernel in another order -- profiles/large_world_isa.txt.)
+template <int K>
+__device__ __forceinline__ void gmm_reach(const pocs_footprint& fp, const double fp_rr, const double fp_phi, const int lane, const double* par,
+                                          pocs_reach& rc, double& ext_x, double& ext_y) {
+  pocs_world_reach_box(par, K, fp, rc);
+  const double tlo = rc.tlo, thi = rc.thi;
+  const double HALF_PI = 1.57079632679489661923;
+  // pocs_footprint_extent_pre for world x (the range as it is) and world y (shifted by a quarter turn), with the four end
+  // values -- a general sine and cosine each, ~70 dependent operations -- evaluated side by side in lanes 0 .. 3 instead of
+  // one after the other in every lane: the same functions of the same arguments, a quarter of the wave's time
+  const double end_t = ((lane & 1) ? thi : tlo) - ((lane & 2) ? HALF_PI : 0.0);      // tlo, thi, tlo - pi/2, thi - pi/2
+  const double end_f = pocs_footprint_extent_end(fp.hx, fp.hy, end_t);
+  ext_x = pocs_footprint_extent_is_radius(fp_phi, tlo, thi) ? fp_rr
+        : pocs_footprint_extent_of_ends(fp_rr, lane_value(end_f, 0), lane_value(end_f, 1));
+  ext_y = pocs_footprint_extent_is_radius(fp_phi, tlo - HALF_PI, thi - HALF_PI) ? fp_rr
+        : pocs_footprint_extent_of_ends(fp_rr, lane_value(end_f, 2), lane_value(end_f, 3));
+}
 template <int K, int TB, bool OC>
 __device__ __forceinline__ void gmm_cull(const pocs_gmm_launch& a, gmm_smem<K, TB, OC>& sm, const int rb, const int lane, const double* par) {
   const pocs_footprint fp = a.fp;
@@ -613,9 +635,17 @@ __device__ __forceinline__ void gmm_close_sums(const pocs_gmm_launch& a, const i
 // behind the units the nonzero ones leave with one integer atomic each to obs_counts[run][waypoint][the record's index in the
 // caller's table] -- exact whatever the grid.  A stopped run's blocks add nothing; the table is the shard's, the exchange does
 // not carry it.
-template <int K, bool STORE, int TB, bool LONE, bool RISK, bool TREE = false, bool OC = false>
+//
+// WORLD (a large collision world, pocs_set_world; the kernels k_gmm_step_world, k_gmm_step_risk_world: ticket form, never LONE, TREE
+// or OC): there is no table to stage and to cull -- k_world_cull, the launch in front of this one, has left the records in reach of
+// every run of the launch in a.kept and their number in a.reach.  The head asks for the (up to) two runs' records and counts with
+// its other requests, the same single round trip, and commits min(reach, POCS_MAX_OBSTACLES) records to sm.keep[rb] -- what gmm_cull
+// leaves there otherwise.  The body does not know the difference.
+template <int K, bool STORE, int TB, bool LONE, bool RISK, bool TREE = false, bool OC = false, bool WORLD = false>
 __device__ __forceinline__ void gmm_step_block(const pocs_gmm_launch a) {      // (by value, as a kernel holds its argument)
   typedef gmm_smem<K, TB, OC> smem_t;
+  static_assert(!(WORLD && (LONE || TREE || OC)), "a large world: the ticket form of a batch or of plans, no per-box counts");
+  static_assert(!WORLD || TB == POCS_MAX_OBSTACLES * POCS_OBS_STRIDE, "one element of a run's kept records per thread");
   static_assert(!(LONE && RISK), "the lone form closes in its heads: a call under a risk bound takes the ticket form");
   static_assert(!(TREE && (LONE || STORE)), "a tree's levels take the ticket form and store no samples");
   constexpr int SUB = smem_t::SUB, NW = smem_t::NW;
@@ -644,7 +674,8 @@ __device__ __forceinline__ void gmm_step_block(const pocs_gmm_launch a) {      /
   static_assert(POCS_ADV_STAGE_MAX <= 4 * TB, "the advance's inputs in one batch");
   double tabv[table_regs<TB>::N];
   request_tables<TB>(a.tables, tid, tabv);
-  const double obs_elem = tid < a.M * POCS_OBS_STRIDE ? a.env->obs[tid] : 0.0;
+  double obs_elem = 0.0;
+  if constexpr (!WORLD) obs_elem = tid < a.M * POCS_OBS_STRIDE ? a.env->obs[tid] : 0.0;
   if (LONE && w > 0) {
     // close waypoint w - 1 and advance to w, here (r0 is the call's one run)
     const bool out = blockIdx.x == 0;
@@ -703,6 +734,31 @@ __device__ __forceinline__ void gmm_step_block(const pocs_gmm_launch a) {      /
     const int rp = tid / PS, jp = tid - rp * PS;
     const double parv = tid < (r1 - r0 + 1) * PS ? load_wt(&a.param[((size_t)(r0 + rp) * a.W + wr) * PS + jp]) : 0.0;
     const unsigned long long seedv = tid <= r1 - r0 ? a.hdr[r0 + tid].seed : 0ull;
+    // WORLD: element `tid` of the kept records of the block's first and second run (a block of one run asks for its records twice)
+    // and the two counts; `shift` as below: a live second run whose first has stopped lands in buffer 0
+    double keptv[2] = {0.0, 0.0};
+    int reachv[2] = {0, 0};
+    if constexpr (WORLD) {
+#pragma unroll
+      for (int q = 0; q < 2; ++q) {
+        const int rq = r0_all + q <= r1_all ? r0_all + q : r1_all;
+        keptv[q] = load_wt(&a.kept[(size_t)rq * (POCS_MAX_OBSTACLES * POCS_OBS_STRIDE) + tid]);
+        reachv[q] = __hip_atomic_load(&a.reach[(size_t)rq * a.W + wr], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      }
+    }
+    auto commit_world = [&](const int shift) __attribute__((always_inline)) {
+      if constexpr (WORLD) {
+#pragma unroll
+        for (int q = 0; q < 2; ++q) {
+          const int rb = q - shift;
+          if (q <= r1_all - r0_all && rb >= 0 && rb <= r1 - r0) {
+            const int n = reachv[q] < POCS_MAX_OBSTACLES ? reachv[q] : POCS_MAX_OBSTACLES;      // (an overflow fails the call on the host; nothing is read past the 64)
+            if (tid < n * POCS_OBS_STRIDE) sm.keep[rb][tid] = keptv[q];
+            if (tid == 0) sm.nkeep[rb] = n;
+          }
+        }
+      }
+    };
     if constexpr (RISK) {
       // the stop words of the block's runs, every lane the same two addresses, in flight with everything above (a stopped run's
       // param[w] was never built: what was requested of it is dropped below, unread)
@@ -719,6 +775,7 @@ __device__ __forceinline__ void gmm_step_block(const pocs_gmm_launch a) {      /
       if (tid < (r1_all - r0_all + 1) * PS && rp >= shift && rp - shift <= r1 - r0) sm.par[rp - shift][jp] = parv;
       for (int j = tid; j < 2 * NW * K; j += TB) (&sm.xj[0][0][0])[j] = -1;
       if (tid <= r1_all - r0_all && tid >= shift && tid - shift <= r1 - r0) sm.seed[tid - shift] = seedv;
+      commit_world(shift);
     } else {
     requests_issued();
     commit_tables<TB>(&sm.tab, tid, tabv);
@@ -726,14 +783,17 @@ __device__ __forceinline__ void gmm_step_block(const pocs_gmm_launch a) {      /
     if (tid < (r1 - r0 + 1) * PS) sm.par[rp][jp] = parv;
     for (int j = tid; j < 2 * NW * K; j += TB) (&sm.xj[0][0][0])[j] = -1;
     if (tid <= r1 - r0) sm.seed[tid] = seedv;
+    commit_world(0);
     }
   }
   __syncthreads();
+  if constexpr (!WORLD) {
   if (!(LONE && w > 0)) {                            // (scalar; the lone form's heads have culled already, above)
     if (tid < 64) gmm_cull(a, sm, 0, tid, sm.par[0]);
     else if (tid < 128 && r1 > r0) gmm_cull(a, sm, 1, tid - 64, sm.par[1]);
     __syncthreads();
   }                                                  // from here on the transpose scratch is the waves'
+  }
   POCS_STAMP(0);
   for (int ta = t0; ta < t1; ta += SUB) {
     const int tb = (ta + SUB < t1) ? ta + SUB : t1;
@@ -870,6 +930,98 @@ __global__ __launch_bounds__(TB, POCS_GMM_BLOCKS_PER_CU * TB / 256) void k_gmm_s
 template <int K, int TB, bool RISK>
 __global__ __launch_bounds__(TB, POCS_GMM_BLOCKS_PER_CU * TB / 256) void k_gmm_step_tree_boxes(pocs_gmm_launch a) {
   gmm_step_block<K, false, TB, false, RISK, true, true>(a);
+}
+
+// The forms under a large collision world (WORLD above): kernels of their own names again.
+template <int K, bool STORE, int TB>
+__global__ __launch_bounds__(TB, POCS_GMM_BLOCKS_PER_CU * TB / 256) void k_gmm_step_world(pocs_gmm_launch a) {
+  gmm_step_block<K, STORE, TB, false, false, false, false, true>(a);
+}
+template <int K, bool STORE, int TB>
+__global__ __launch_bounds__(TB, POCS_GMM_BLOCKS_PER_CU * TB / 256) void k_gmm_step_risk_world(pocs_gmm_launch a) {
+  gmm_step_block<K, STORE, TB, false, true, false, false, true>(a);
+}
+
+// The cull of a large world for one waypoint: one block per run of the launch's run range, in front of the waypoint's sampling
+// launch on the same stream (a kernel node of the replayed graph like the others).  The block forms the run's reach from
+// param[run][waypoint] as gmm_cull does (gmm_reach), tests all world_M records with gmm_cull's keep test (pocs_world_keep) and
+// writes the kept ones in the caller's order: per pass of POCS_CULL_BLOCK records a ballot per wave, the (pass, wave) counts
+// through LDS, one prefix over them by wave 0 -- no atomics, so the list is the same in every replay.  The first
+// POCS_MAX_OBSTACLES kept records go to kept[run] (fields 6 and 7 tightened, as gmm_cull leaves them) with their indices, the full
+// count to reach[run][waypoint].  A run stopped under the risk bound has no param[waypoint]: its reach is 0 (a NaN box would keep
+// everything and report an overflow that is none).
+template <int K>
+__global__ __launch_bounds__(POCS_CULL_BLOCK) void k_world_cull(pocs_gmm_launch a) {
+  constexpr int NT = POCS_CULL_BLOCK, NW = NT / 64, PS = K * POCS_PARAM_STRIDE, NIT = POCS_MAX_WORLD_RECORDS / NT;
+  static_assert(NIT * NW == 64 && NIT <= 32, "the (pass, wave) counts are one wave's worth; a thread's keep bits fit a word");
+  static_assert(PS <= NT, "one sampler parameter per thread");
+  __shared__ double s_par[PS];
+  __shared__ int s_cnt[NIT * NW];
+  __shared__ int s_total;
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int r = a.run_lo + (int)blockIdx.x, w = a.waypoint;
+  const int M = a.world_M < POCS_MAX_WORLD_RECORDS ? a.world_M : POCS_MAX_WORLD_RECORDS;
+  int* const reach = &a.reach[(size_t)r * a.W + w];
+  unsigned stopw = 0u;
+  if (a.stop) stopw = __hip_atomic_load(&a.stop[r], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  const double parv = tid < PS ? load_wt(&a.param[((size_t)r * a.W + w) * PS + tid]) : 0.0;
+  requests_issued();
+  if (__builtin_amdgcn_readfirstlane((int)stopw) != 0) {      // (the same word in every thread of the block)
+    if (tid == 0) __hip_atomic_store(reach, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    return;
+  }
+  if (tid < PS) s_par[tid] = parv;
+  if (tid < NIT * NW) s_cnt[tid] = 0;
+  __syncthreads();
+  pocs_reach rc;
+  double ext_x, ext_y;
+  gmm_reach<K>(a.fp, a.fp_rr, a.fp_phi, lane, s_par, rc, ext_x, ext_y);      // (every wave for itself: all 64 lanes)
+  const int nit = (M + NT - 1) / NT;                  // (block-uniform: every lane of a wave is at every ballot)
+  unsigned keepbits = 0u;
+  for (int it = 0; it < nit; ++it) {
+    const int m = it * NT + tid;
+    bool keep = false;
+    double bx, by;
+    if (m < M) keep = pocs_world_keep(a.world + (size_t)m * POCS_OBS_STRIDE, rc, ext_x, ext_y, bx, by);
+    const unsigned long long b = __ballot(keep);
+    if (keep) keepbits |= 1u << it;
+    if (lane == 0) s_cnt[it * NW + wave] = __popcll(b);
+  }
+  __syncthreads();
+  if (tid < 64) {                                     // exclusive prefix of the 64 counts, which lie in record order
+    const int v = s_cnt[tid];
+    int inc = v;
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+      const int t = __shfl_up(inc, d);
+      if (lane >= d) inc += t;
+    }
+    s_cnt[tid] = inc - v;
+    if (tid == 63) s_total = inc;
+  }
+  __syncthreads();
+  double* const kept = a.kept + (size_t)r * (POCS_MAX_OBSTACLES * POCS_OBS_STRIDE);
+  int* const kept_idx = a.kept_idx + (size_t)r * POCS_MAX_OBSTACLES;
+  for (int it = 0; it < nit; ++it) {
+    const bool keep = ((keepbits >> it) & 1u) != 0u;
+    const unsigned long long b = __ballot(keep);
+    if (keep) {
+      const int pos = s_cnt[it * NW + wave] + __popcll(b & ((1ull << lane) - 1ull));
+      if (pos < POCS_MAX_OBSTACLES) {
+        const int m = it * NT + tid;
+        const double* o = a.world + (size_t)m * POCS_OBS_STRIDE;
+        double bx, by;
+        (void)pocs_world_keep(o, rc, ext_x, ext_y, bx, by);      // (the same function of the same arguments: the tightened broad phase)
+#pragma unroll
+        for (int j = 0; j < 6; ++j) store_wt(&kept[pos * POCS_OBS_STRIDE + j], o[j]);
+        store_wt(&kept[pos * POCS_OBS_STRIDE + 6], bx);
+        store_wt(&kept[pos * POCS_OBS_STRIDE + 7], by);
+        __hip_atomic_store(&kept_idx[pos], m, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      }
+    }
+  }
+  if (tid == 0) __hip_atomic_store(reach, s_total, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
 // Lone call, behind the last waypoint's launch: its rows -> moments[W-1] (one block).

@@ -9,6 +9,8 @@
 //                             SURVEY 3.2), 0 B per evaluation; k_mc_fused_counts; k_mc_fused_sched: under an obstacle schedule
 //   k_mc_tree_step  P1+P3     one level of a tree of plans: the parent's particles moved into the node's place
 //   k_mc_count      P3        getCollisionProportion (:324-330): |{hits > 0}|.
+//   k_mc_init_world, k_mc_step_world: k_mc_init and k_mc_step against a large collision world (pocs_set_world), culled per wave
+//                             and particle iteration (mc_world_collides)
 //   MC_BOXES forms of k_mc_init / k_mc_step_counts / k_mc_fused_sched, k_mc_fused_boxes, k_mc_tree_step_boxes: ... with the first
 //                             collisions split by obstacle box (POCS_OPT_OBSTACLE_COUNTS)
 //
@@ -224,6 +226,96 @@ __device__ __forceinline__ void mc_move(const double x, const double y, const do
   nt = pocs_wrap_angle(t + u0 + u2);
 }
 
+// ---- a large collision world (pocs_set_world with more than POCS_MAX_OBSTACLES boxes; k_mc_init_world, k_mc_step_world) ----
+// The particles of a block are not bounded ahead of time, so the table is culled per wave and particle iteration, against the box
+// of the wave's 64 footprint centres (mc_world_collides).  Nothing of the table is staged: the head is the sector table and the
+// footprint.
+__device__ __forceinline__ mc_world stage_mc_head_world(const pocs_mc_launch& a) {
+  __shared__ pocs_tables s_tab;
+  constexpr int NS = (int)(sizeof(a.tables->sc) / sizeof(double)), US = (NS + POCS_BLOCK - 1) / POCS_BLOCK;
+  const int tid = threadIdx.x;
+  const double* src = &a.tables->sc[0][0];
+  double vs[US];
+#pragma unroll
+  for (int u = 0; u < US; ++u) { const int i = tid + u * POCS_BLOCK; vs[u] = i < NS ? src[i] : 0.0; }
+  const pocs_footprint fp = a.env->fp;
+  requests_issued();
+  double* dst = &s_tab.sc[0][0];
+#pragma unroll
+  for (int u = 0; u < US; ++u) { const int i = tid + u * POCS_BLOCK; if (i < NS) dst[i] = vs[u]; }
+  __syncthreads();
+  return {a.world, &s_tab, fp, a.world_M};
+}
+// the wave's minimum / maximum of v, in every lane (all 64 lanes active): row steps by DPP, the four rows through scalar registers
+__device__ __forceinline__ double wave_min_f64(double v) {
+  v = fmin(v, dpp_f64<0xB1>(v)); v = fmin(v, dpp_f64<0x4E>(v)); v = fmin(v, dpp_f64<0x141>(v)); v = fmin(v, dpp_f64<0x140>(v));
+  return fmin(fmin(lane_value(v, 0), lane_value(v, 16)), fmin(lane_value(v, 32), lane_value(v, 48)));
+}
+__device__ __forceinline__ double wave_max_f64(double v) {
+  v = fmax(v, dpp_f64<0xB1>(v)); v = fmax(v, dpp_f64<0x4E>(v)); v = fmax(v, dpp_f64<0x141>(v)); v = fmax(v, dpp_f64<0x140>(v));
+  return fmax(fmax(lane_value(v, 0), lane_value(v, 16)), fmax(lane_value(v, 32), lane_value(v, 48)));
+}
+// pocs_pose_collides against a table of any length, for the 64 poses of a wave at once -- ALL 64 lanes arrive (the callers' particle
+// loops run on a wave-uniform bound; a lane without a particle, `live` false, carries a dead pose that adds +-infinity to the
+// bounds below and whose flag is dropped).  Per lane the footprint centre and the heading's sine and cosine exactly as
+// pocs_pose_collides forms them (pocs_world_pose); the wave's bounding box of the centres; then per 64 records: lane l looks at
+// record base + l and rejects it if the box cannot reach it (pocs_world_wave_rejects: exact, pocs_world.h), one ballot, and for
+// every record left -- a scalar loop over the ballot's bits -- all lanes run pocs_box_hit on it through a wave-uniform pointer.
+// Every record that is not rejected for the whole wave goes through pocs_box_hit itself: the flags of the full loop over M.
+__device__ __forceinline__ bool mc_world_collides(const bool live, const double x, const double y, const double t, const mc_world& wd) {
+  const int lane = threadIdx.x & 63;
+  double px, py, sn, cs;
+  pocs_world_pose(x, y, t, &wd.fp, wd.tab, &px, &py, &sn, &cs);
+  const double inf = __builtin_inf();
+  const double xlo = wave_min_f64(live ? px : inf), xhi = wave_max_f64(live ? px : -inf);
+  const double ylo = wave_min_f64(live ? py : inf), yhi = wave_max_f64(live ? py : -inf);
+  bool hit = false;
+  for (int base = 0; base < wd.M; base += 64) {        // (wave-uniform)
+    const int m = base + lane;
+    bool cand = false;
+    if (m < wd.M) {
+      const double* o = wd.obs + (size_t)m * POCS_OBS_STRIDE;
+      cand = !pocs_world_wave_rejects(o[0], o[1], o[6], o[7], xlo, xhi, ylo, yhi);
+    }
+    unsigned long long b = __ballot(cand);
+    while (b != 0ull) {                                // (scalar)
+      const int j = __builtin_amdgcn_readfirstlane((int)__builtin_ctzll(b));
+      b &= b - 1ull;
+      const double* o = wd.obs + (size_t)(base + j) * POCS_OBS_STRIDE;
+      if (pocs_box_hit(px, py, sn, cs, wd.fp.hx, wd.fp.hy, o)) hit = true;
+    }
+  }
+  return hit && live;
+}
+
+// WORLD (k_mc_init_world): the same particle, the same stores, the collision test against the large world; the loop runs on the
+// wave's first index, so that every lane of a wave is at the cross-lane steps of mc_world_collides.
+template <int MODE, bool WORLD = false>
+__device__ __forceinline__ void mc_init_body(const pocs_mc_launch& a) {
+  static_assert(WORLD && (MODE & MC_BOXES) == 0, "the body of k_mc_init_world; k_mc_init keeps its own");
+  const mc_world wd = stage_mc_head_world(a);
+  const mc_run_view v = mc_view(a);
+  const mc_run_start st = mc_start(a);
+  unsigned first = 0;
+  const int lane = threadIdx.x & 63;
+  const long long stride = (long long)gridDim.x * POCS_BLOCK;
+  for (long long i0 = (long long)blockIdx.x * POCS_BLOCK + (threadIdx.x - lane); i0 < a.count; i0 += stride) {      // (wave-uniform)
+    const long long i = i0 + lane;
+    const bool live = i < a.count;
+    double x = 0.0, y = 0.0, t = 0.0;
+    if (live) {
+      mc_initial(a, v.seed, i, st, x, y, t);
+      v.x[i] = x; v.y[i] = y; v.th[i] = t;
+    }
+    const unsigned h = mc_world_collides(live, x, y, t, wd) ? 1u : 0u;
+    if (live) v.hits[i] = h;
+    first += h;
+  }
+  if (MODE != MC_PLAIN) mc_block_add(first, a.wp_counts + (size_t)blockIdx.y * (size_t)a.W);      // waypoint 0
+}
+template <int MODE>
+__global__ __launch_bounds__(POCS_BLOCK) void k_mc_init_world(pocs_mc_launch a) { mc_init_body<MODE, true>(a); }
+
 template <int MODE>
 __global__ __launch_bounds__(POCS_BLOCK) void k_mc_init(pocs_mc_launch a) {
   mc_box_counters box = {nullptr};
@@ -261,9 +353,38 @@ template <bool NT, typename T> __device__ __forceinline__ void mc_store(const T 
 
 // One particle per thread and iteration: a two-particle version with 16-byte accesses measured 12 % slower in cache, 7 %
 // faster out of it.
-template <bool NT, int MODE>
+//   WORLD (k_mc_step_world): the collision test against a large world (mc_world_collides), the particle loop on the wave's first
+//   index so that every lane of a wave is at its cross-lane steps; MC_BOXES is not served there
+template <bool NT, int MODE, bool WORLD = false>
 __device__ __forceinline__ void mc_step_body(const pocs_mc_launch& a) {
   if ((MODE & 3) == MC_STOP) { if (mc_run_stopped(a)) return; }      // (the same answer in every thread of the block)
+  if constexpr (WORLD) {
+    static_assert(!WORLD || (MODE & MC_BOXES) == 0, "no per-box counts under a large world");
+    const mc_world wd = stage_mc_head_world(a);
+    const mc_run_view v = mc_view(a);
+    const double* u = v.chain + (size_t)a.step * POCS_CHAIN_STRIDE + 6;
+    const double u0 = u[0], u1 = u[1], u2 = u[2];
+    unsigned first = 0;
+    const int lane = threadIdx.x & 63;
+    const long long stride = (long long)gridDim.x * POCS_BLOCK;
+    for (long long i0 = (long long)blockIdx.x * POCS_BLOCK + (threadIdx.x - lane); i0 < a.count; i0 += stride) {      // (wave-uniform)
+      const long long i = i0 + lane;
+      const bool live = i < a.count;
+      double nx = 0.0, ny = 0.0, nt = 0.0;
+      if (live) {
+        const double x = mc_load<NT>(v.x + i), y = mc_load<NT>(v.y + i), t = mc_load<NT>(v.th + i);
+        mc_move(x, y, t, u0, u1, u2, nx, ny, nt);
+        mc_store<NT>(nx, v.x + i); mc_store<NT>(ny, v.y + i); mc_store<NT>(nt, v.th + i);
+      }
+      if (mc_world_collides(live, nx, ny, nt, wd)) {
+        const uint32_t old = v.hits[i];
+        v.hits[i] = old + 1u;
+        first += old == 0u ? 1u : 0u;
+      }
+    }
+    if (MODE != MC_PLAIN) mc_block_add(first, a.wp_counts + (size_t)blockIdx.y * (size_t)a.W + (size_t)a.step + 1);
+    return;
+  }
   mc_box_counters box = {nullptr};
   if constexpr ((MODE & MC_BOXES) != 0) box = mc_box_counters_zeroed();      // (in front of the head's barrier)
   const mc_head hd = stage_mc_head(a.env, a.tables);
@@ -303,6 +424,8 @@ template <bool NT>
 __global__ __launch_bounds__(POCS_BLOCK) void k_mc_step(pocs_mc_launch a) { mc_step_body<NT, MC_PLAIN>(a); }
 template <bool NT, int MODE>
 __global__ __launch_bounds__(POCS_BLOCK) void k_mc_step_counts(pocs_mc_launch a) { mc_step_body<NT, MODE>(a); }
+template <bool NT, int MODE>
+__global__ __launch_bounds__(POCS_BLOCK) void k_mc_step_world(pocs_mc_launch a) { mc_step_body<NT, MODE, true>(a); }
 
 // MC_COUNTS: a particle has at most one first collision, so per step a wave ballots them and one lane adds the wave's count,
 // only when there is one (no block-level sum: the blocks of a fused launch never meet between steps).

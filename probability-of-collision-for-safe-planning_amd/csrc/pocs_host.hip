@@ -89,6 +89,13 @@ int upload_world(pocs_ctx* c) {                // tables + the collision world: 
     if (int r = ensure(c, c->d_env, S * sizeof(pocs_env_dev))) return r;      // (a schedule that grows: the graphs go with the old table)
     HIPCHK(c, hipStreamSynchronize(c->stream));      // (nothing queued may still read the last world's)
     HIPCHK(c, hipMemcpy(c->d_env.p, env.data(), S * sizeof(pocs_env_dev), hipMemcpyHostToDevice));
+    if (large_world(c)) {                            // the large world's records (the env record above then holds the footprint and M = 0)
+      const size_t LM = (size_t)large_boxes(c);
+      std::vector<double> rec(LM * POCS_OBS_STRIDE);
+      for (size_t m = 0; m < LM; ++m) pocs_prepare_obstacle(&c->world[m * 5], &c->fp, &rec[m * POCS_OBS_STRIDE]);
+      if (int r = ensure(c, c->d_world, rec.size() * sizeof(double))) return r;
+      HIPCHK(c, hipMemcpy(c->d_world.p, rec.data(), rec.size() * sizeof(double), hipMemcpyHostToDevice));
+    }
     c->env_dirty = false;
   }
   return POCS_OK;
@@ -212,6 +219,11 @@ int gmm_prepare(pocs_ctx* c) {
   if (c->tree.n)
     if (int r = upload_tree(c)) return r;
   if (int r = ensure_obs_counts(c)) return r;
+  if (large_world(c)) {
+    if (int r = ensure(c, c->d_kept, R * POCS_MAX_OBSTACLES * POCS_OBS_STRIDE * sizeof(double))) return r;
+    if (int r = ensure(c, c->d_keptidx, R * POCS_MAX_OBSTACLES * sizeof(int))) return r;
+    if (int r = ensure(c, c->d_reach, R * W * sizeof(int))) return r;
+  }
   if (c->opt_store && !c->tree.n) {                   // (a call on a tree stores no samples)
     const size_t n = R * (size_t)sample_stride_of(count);
     if (int r = ensure(c, c->d_sx, n * sizeof(double))) return r;
@@ -272,6 +284,10 @@ void fill_gmm_world(const pocs_ctx* c, pocs_gmm_launch* a, int w) {
   a->tables = (const pocs_tables*)c->d_tables.p;
   a->fp = c->fp; a->M = world_boxes(c);
   a->fp_rr = sqrt(c->fp.hx * c->fp.hx + c->fp.hy * c->fp.hy); a->fp_phi = atan2(c->fp.hy, c->fp.hx);
+  if (large_world(c)) {                              // (M above is 0 then: the staged table is empty)
+    a->world = (const double*)c->d_world.p; a->world_M = large_boxes(c);
+    a->kept = (double*)c->d_kept.p; a->kept_idx = (int*)c->d_keptidx.p; a->reach = (int*)c->d_reach.p;
+  }
 }
 
 void fill_gmm_launch(pocs_ctx* c, pocs_gmm_launch* a, long long first, long long count, int w,
@@ -314,7 +330,9 @@ int enqueue_advance(pocs_ctx* c, int w) {
 // One run per call (no batch, no run-ahead) on one GPU: the launches close the previous waypoint in their heads
 // (k_gmm_step, "LONE"): 30.6 -> 27.5 us per waypoint at 10^6 samples, K = 3 (MI355X).  POCS_OPT_LONE_CALL = 0
 // keeps the ticket-and-closer form; the results are the same bits.
-bool lone_call(const pocs_ctx* c) { return c->opt_lone && c->batch == 1 && !c->tree.n && !c->ext_moments && !(c->xchg_connected && c->shard_first >= 0) && !risk_active(c); }
+// (Under a large world the cull of waypoint w reads param[w] ahead of the sampling launch; the lone form builds param[w] in its own
+// heads, so a call of one run takes the ticket form there: the same bits.)
+bool lone_call(const pocs_ctx* c) { return c->opt_lone && !large_world(c) && c->batch == 1 && !c->tree.n && !c->ext_moments && !(c->xchg_connected && c->shard_first >= 0) && !risk_active(c); }
 void set_risk(pocs_ctx* c, pocs_gmm_launch* a) {      // under a risk bound the launch is k_gmm_step_risk (whole calls of plans or on a tree only)
   a->risk = 1;
   a->stop = a->sync + sync_stop_offset(c);
@@ -346,6 +364,7 @@ int enqueue_step(pocs_ctx* c, long long first, long long count, int w, bool adva
     for (int q = 0; q < c->xchg_world; ++q) a.xchg.buf[q] = (double*)c->xchg_peer[q];
     a.xchg.world = c->xchg_world; a.xchg.rank = c->xchg_rank;
   }
+  if (a.world) HIPCHK(c, pocs_launch_world_cull(c->K, a, stream));      // a large world: cull(w) in front of step(w), same stream, same runs
   if (prof_slot >= 0) HIPCHK(c, hipEventRecord(c->events[2 * prof_slot], stream));
   HIPCHK(c, pocs_launch_gmm_step(c->K, a, stream));
   if (prof_slot >= 0) HIPCHK(c, hipEventRecord(c->events[2 * prof_slot + 1], stream));
@@ -354,6 +373,8 @@ int enqueue_step(pocs_ctx* c, long long first, long long count, int w, bool adva
 
 int enqueue_ticket_reset(pocs_ctx* c) {
   HIPCHK(c, hipMemsetAsync(c->d_ticket.p, 0, sync_words(c) * sizeof(unsigned), c->stream));
+  if (large_world(c))                                // (a waypoint that no cull launch covers -- a plan's end, a stop -- reports no reach)
+    HIPCHK(c, hipMemsetAsync(c->d_reach.p, 0, (size_t)c->batch * (size_t)c->W * sizeof(int), c->stream));
   return POCS_OK;
 }
 
@@ -447,6 +468,36 @@ int enqueue_gmm_results(pocs_ctx* c) {
   static_assert(POCS_SYNC_ABORT == 1, "the stop words follow the give-up word and two pad words");
   HIPCHK(c, hipMemcpyAsync((double*)c->h_pin + pl.total + c->batch + 1, (unsigned*)c->d_ticket.p + POCS_SYNC_ABORT,
                            (risk_active(c) ? 3 + (size_t)c->batch : 1) * sizeof(unsigned), hipMemcpyDeviceToHost, c->stream));
+  if (large_world(c)) {                              // the kept counts [R][W]: into the context's own table, slot order (gmm_read_reach sorts them)
+    c->reach.assign((size_t)c->batch * (size_t)c->W, 0);
+    HIPCHK(c, hipMemcpyAsync(c->reach.data(), c->d_reach.p, c->reach.size() * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+  }
+  return POCS_OK;
+}
+
+// The kept counts of a GMM call under a large world, as enqueue_gmm_results brought them back in slot order -> run / plan order
+// (pocs_get_world_reach), and the overflow check: a (run, waypoint) whose cull kept more than POCS_MAX_OBSTACLES records was sampled
+// against the first POCS_MAX_OBSTACLES of them only, so the call fails -- naming the lowest such waypoint and its count.  The table
+// it leaves stays readable.
+int gmm_read_reach(pocs_ctx* c) {
+  const int R = c->batch, W = c->W;
+  const bool plans = c->plans.n && !c->res.plan_slot[0].empty();
+  const std::vector<int> by_slot = c->reach;
+  c->reach_R = R; c->reach_W = W;
+  c->reach_len.assign((size_t)R, W);
+  int bad_w = -1, bad_n = 0, bad_r = 0;
+  for (int r = 0; r < R; ++r) {
+    const int slot = plans ? c->res.plan_slot[0][(size_t)r] : r;
+    if (plans) c->reach_len[(size_t)r] = c->plans.W[(size_t)r];
+    for (int w = 0; w < W; ++w) {
+      const int n = by_slot[(size_t)slot * W + w];
+      c->reach[(size_t)r * W + w] = n;
+      if (n > POCS_MAX_OBSTACLES && (bad_w < 0 || w < bad_w)) { bad_w = w; bad_n = n; bad_r = r; }
+    }
+  }
+  if (bad_w >= 0)
+    return fail(c, POCS_E_STATE, "large world: %d boxes are in reach of run %d at waypoint %d, more than the %d a run may meet at one waypoint; results discarded",
+                bad_n, bad_r, bad_w, POCS_MAX_OBSTACLES);
   return POCS_OK;
 }
 
@@ -581,6 +632,7 @@ std::string config_key(const pocs_ctx* c, long long first, long long count, cons
            c->W, c->K, c->batch, gmm_groups(c), lone_call(c) ? 1 : 0, (c->xchg_connected && c->shard_first >= 0 && !c->ext_moments) ? c->xchg_world : 0,
            c->num_gmm, first, count, c->opt_store, c->opt_fused, c->opt_obs_counts, (void*)c->stream, (void*)c->ext_moments);
   std::string key = buf;
+  if (large_world(c)) key += " lw" + std::to_string(large_boxes(c));      // the launches and their kernels are another set
   if (c->tree.n) {                                   // a tree: the launches follow its shape (the levels' widths, the parents on the device)
     unsigned long long h = 1469598103934665603ull;   // FNV-1a over the slots' parents
     for (int v : c->tree.pslot) { h ^= (unsigned)v; h *= 1099511628211ull; }
@@ -629,6 +681,7 @@ int run_gmm_full(pocs_ctx* c, double* probability) {
   auto lap = [](const char*) {};
 #endif
   c->res.oc_kind = 0;                                  // (the per-obstacle table is rewritten from here on; noted again behind the combine)
+  c->reach.clear(); c->reach_len.clear(); c->reach_R = 0; c->reach_W = 0;      // (pocs_get_world_reach covers the last GMM call)
   if (int r = gmm_prepare(c)) return r;
   long long first, count;
   if (int r = gmm_shard(c, &first, &count)) return r;
@@ -690,6 +743,7 @@ int run_gmm_full(pocs_ctx* c, double* probability) {
     if (gave_up) return fail(c, POCS_E_DEVICE, "a bounded wait expired on the device (code %u); results discarded", gave_up);
     // (the stop words: behind the give-up word and its two pad words)
     const unsigned* stop = risk_active(c) ? (const unsigned*)((double*)c->h_pin + pl.total + c->batch + 1) + 3 : nullptr;
+    if (large_world(c)) if (int r = gmm_read_reach(c)) { reset_results(c); return r; }
     if (int r = gmm_combine(c, (double*)c->h_pin + pl.moments, probability, stop)) { reset_results(c); return r; }
   }
   note_obs_counts(c, 1);
@@ -736,6 +790,7 @@ int mc_launch_base(pocs_ctx* c, long long count, double live_particles, pocs_mc_
   a->hdr = (const pocs_run_header*)c->d_hdr.p;
   a->env = world_at(c, 0);                           // (k_mc_init: waypoint 0; the launches of later waypoints set their own)
   a->tables = (const pocs_tables*)c->d_tables.p;
+  if (large_world(c)) { a->world = (const double*)c->d_world.p; a->world_M = large_boxes(c); }      // (k_mc_init_world, k_mc_step_world)
   a->chain = (const double*)c->d_chain.p;
   a->total = (unsigned long long*)c->d_total.p;
   a->count = count; a->stride = sample_stride_of(count);
@@ -980,7 +1035,7 @@ int run_mc_local(pocs_ctx* c) {
   HIPCHK(c, hipMemsetAsync(c->d_total.p, 0, total_bytes, c->stream));
   if (c->opt_graph && !prof) {
     // (the two options select the kernels; the bound an MC stop obeys is in the key already: config_key, "rb")
-    const std::string key = config_key(c, first, count, "mc") + std::to_string(c->num_particles) +
+    const std::string key = config_key(c, first, count, "mc") + " " + std::to_string(c->num_particles) +
                             (mc_stop_active(c) ? " wp2" : mc_counts_active(c) ? " wp1" : "");
     if (int r = ensure_graph(c, c->graph_mc, c->graph_mc_key, key, [&] { return enqueue_mc_all(c, first, count, false); })) return r;
     if (span) HIPCHK(c, hipEventRecord(c->ev_seq[0], c->stream));
@@ -1024,6 +1079,7 @@ int pocs_gmm_begin(pocs_ctx* c) {
   if (!c) return POCS_E_ARG;
   if (c->plans.n) return fail(c, POCS_E_STATE, "pocs_gmm_begin: plans are set (the step API serves a single plan)");
   if (c->tree.n) return fail(c, POCS_E_STATE, "pocs_gmm_begin: a tree of plans is set (the step API serves a single plan)");
+  if (large_world(c)) return fail(c, POCS_E_STATE, "pocs_gmm_begin: a large world of %d boxes is set (pocs_set_world): the step API serves worlds of at most %d boxes", large_boxes(c), POCS_MAX_OBSTACLES);
   HIPCHK(c, hipSetDevice(c->device));
   ra_drop(c);
   c->ra_internal = false;

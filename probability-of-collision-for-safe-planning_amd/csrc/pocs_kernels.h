@@ -6,6 +6,7 @@
 #include <stdint.h>
 #include "pocs_collide.h"
 #include "pocs_model.h"
+#include "pocs_world.h"
 
 #define POCS_BLOCK 256        // MC kernels
 // GMM kernels: TWO blocks of 512 threads per CU = four waves per SIMD at <= 128 VGPRs.  The sampling body
@@ -131,7 +132,19 @@ struct pocs_gmm_launch {
   unsigned long long* obs_counts; // [nruns][W][POCS_MAX_OBSTACLES] samples of the shard drawn at (run, waypoint) whose footprint touches box m of
                                  // the caller's table; non-null: the launch is the kernel's _boxes form.  Zeroed by pocs_launch_zero_counts
                                  // at the head of the call's launches
+  // a large collision world (pocs_set_world with more than POCS_MAX_OBSTACLES boxes; behind everything else again).  `env` then holds
+  // no record (M = 0 above); k_world_cull, one launch in front of every waypoint's sampling launch, leaves per run the records in
+  // the run's reach, and the sampling launch is the kernel's _world form, whose heads fetch those instead of culling the table
+  const double* world;           // [world_M][POCS_OBS_STRIDE] the prepared records; non-null: a large world
+  int world_M;
+  int world_pad;
+  double* kept;                  // [nruns][POCS_MAX_OBSTACLES][POCS_OBS_STRIDE] the first POCS_MAX_OBSTACLES kept records of (run, this waypoint), in
+                                 // the caller's order, fields 6 and 7 tightened to the run's headings
+  int* kept_idx;                 // [nruns][POCS_MAX_OBSTACLES] their indices in the caller's table
+  int* reach;                    // [nruns][W] how many records the cull kept at (run, waypoint), the overflow included; zeroed per call
 };
+#define POCS_MAX_WORLD_RECORDS 4096   // = POCS_MAX_WORLD_BOXES (include/pocs.h; pocs_ctx.hpp checks)
+#define POCS_CULL_BLOCK 256           // k_world_cull
 // a tree's stop words: 0 = live, depth + 1 = the node's own closer found the bound reached, this bit = below such a node
 #define POCS_TREE_STOP_INHERITED 0x80000000u
 #define POCS_SYNC_ABORT 1
@@ -177,10 +190,16 @@ struct pocs_mc_launch {               // blockIdx.y = run of the batch, like poc
   // per-obstacle collision counts (POCS_OPT_OBSTACLE_COUNTS; behind everything else again): needs wp_mode != 0
   unsigned long long* obs_counts;      // [nruns][W][POCS_MAX_OBSTACLES] particles of the shard whose FIRST collision is at waypoint w and which touch
                                        // box m there (a tree: one row per slot); non-null: the kernels' MC_BOXES forms
+  // a large collision world (pocs_set_world; behind everything else again): k_mc_init_world / k_mc_step_world, which cull the table
+  // per wave and particle iteration (mc_world_collides); `env` carries the footprint and no record
+  const double* world;                 // [world_M][POCS_OBS_STRIDE]; non-null: a large world
+  int world_M;
+  int world_pad;
 };
 
 
 hipError_t pocs_launch_gmm_step(int K, const pocs_gmm_launch& a, hipStream_t s);              // grid = a.blocks
+hipError_t pocs_launch_world_cull(int K, const pocs_gmm_launch& a, hipStream_t s);            // grid = a.run_cnt: one block per run of the launch
 hipError_t pocs_launch_gmm_advance(int K, const pocs_gmm_launch& a, hipStream_t s);
 hipError_t pocs_launch_gmm_tree_advance(int K, const pocs_gmm_launch& a, hipStream_t s);    // grid = a.run_cnt: the nodes of one level
 hipError_t pocs_launch_gmm_tree_step(int K, const pocs_gmm_launch& a, hipStream_t s);       // grid = a.blocks

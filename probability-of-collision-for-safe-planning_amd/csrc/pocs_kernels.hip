@@ -7,8 +7,10 @@
 //   pocs_dev_advance.hpp  k_gmm_advance, k_gmm_tree_advance, k_gmm_exchange: the mixture advance and the one-hop
 //                         exchange of a run's moments between the GPUs of a node                 (prims)
 //   pocs_dev_gmm.hpp      k_gmm_step, k_gmm_step_risk, k_gmm_step_tree, k_gmm_close: one waypoint of truncateGMM in one
-//                         launch -- sampling, collision test, moment sums, closer                (prims, advance)
-//   pocs_dev_mc.hpp       k_mc_init, k_mc_step, k_mc_fused, k_mc_fused_sched, k_mc_tree_step, k_mc_count (prims)
+//                         launch -- sampling, collision test, moment sums, closer; k_world_cull, k_gmm_step_world,
+//                         k_gmm_step_risk_world: the same under a large collision world          (prims, advance)
+//   pocs_dev_mc.hpp       k_mc_init, k_mc_step, k_mc_fused, k_mc_fused_sched, k_mc_tree_step, k_mc_count, and k_mc_init_world,
+//                         k_mc_step_world under a large collision world                          (prims)
 //
 // Bound: these are FP64-VALU / HBM streaming kernels, no contraction => no MFMA.  Mixture
 // parameters, the obstacle table and the 12 KB of log/sector tables are staged in LDS once per
@@ -52,6 +54,18 @@ hipError_t with_K(const int K, F f) {
 hipError_t pocs_launch_gmm_step(int K, const pocs_gmm_launch& a, hipStream_t s) {
   return with_K(K, [&](auto k) {
     constexpr int KK = decltype(k)::value, TB = POCS_GMM_BLOCK_OF(KK);
+    if (a.world) {                                     // a large world: the ticket forms that fetch what k_world_cull has left
+      if (a.lone || a.obs_counts || a.exchange_in_tail || a.tree_parent || !a.kept || !a.reach || a.M != 0 ||
+          (a.risk && (!a.stop || !a.surv)))
+        return hipErrorInvalidValue;
+      if (a.risk) {
+        if (a.store) hipLaunchKernelGGL((k_gmm_step_risk_world<KK, true, TB>), dim3(a.blocks), dim3(TB), 0, s, a);
+        else         hipLaunchKernelGGL((k_gmm_step_risk_world<KK, false, TB>), dim3(a.blocks), dim3(TB), 0, s, a);
+      } else {
+        if (a.store) hipLaunchKernelGGL((k_gmm_step_world<KK, true, TB>), dim3(a.blocks), dim3(TB), 0, s, a);
+        else         hipLaunchKernelGGL((k_gmm_step_world<KK, false, TB>), dim3(a.blocks), dim3(TB), 0, s, a);
+      }
+    } else
     if (a.obs_counts) {                                // POCS_OPT_OBSTACLE_COUNTS: the same choice among the counting forms
       if (a.M > POCS_MAX_OBSTACLES) return hipErrorInvalidValue;
       if (a.risk) {
@@ -76,6 +90,18 @@ hipError_t pocs_launch_gmm_step(int K, const pocs_gmm_launch& a, hipStream_t s) 
       if (a.store) hipLaunchKernelGGL((k_gmm_step<KK, true, TB, false>), dim3(a.blocks), dim3(TB), 0, s, a);
       else         hipLaunchKernelGGL((k_gmm_step<KK, false, TB, false>), dim3(a.blocks), dim3(TB), 0, s, a);
     }
+    return hipGetLastError();
+  });
+}
+// The cull of a large world in front of a waypoint's sampling launch: one block per run of the launch's run range.
+hipError_t pocs_launch_world_cull(int K, const pocs_gmm_launch& a, hipStream_t s) {
+  if (!a.world || a.world_M < 1 || a.world_M > POCS_MAX_WORLD_RECORDS || !a.kept || !a.kept_idx || !a.reach || !a.param || a.run_cnt < 1 ||
+      a.run_lo < 0 || a.run_lo + a.run_cnt > a.nruns || a.waypoint < 0 || a.waypoint >= a.W || (a.risk && !a.stop))
+    return hipErrorInvalidValue;
+  return with_K(K, [&](auto k) {
+    pocs_gmm_launch c = a;
+    if (!a.risk) c.stop = nullptr;                     // (the kernel reads the stop word where there is one)
+    hipLaunchKernelGGL((k_world_cull<decltype(k)::value>), dim3(a.run_cnt), dim3(POCS_CULL_BLOCK), 0, s, c);
     return hipGetLastError();
   });
 }
@@ -122,6 +148,7 @@ hipError_t pocs_launch_gmm_tree_advance(int K, const pocs_gmm_launch& a, hipStre
 }
 // One level of a tree of plans on the MC path: grid (nblk, a.nruns), a.nruns = the launch's nodes, slots tree_lo ...
 hipError_t pocs_launch_mc_tree_step(int nblk, const pocs_mc_launch& a, hipStream_t s) {
+  if (a.world) return hipErrorInvalidValue;
   if (!a.tree_parent || !a.tree_sx || !a.tree_sy || !a.tree_sth || !a.tree_shits || !a.wp_counts || !a.total || a.nruns < 1 || a.nruns > 256 ||
       a.tree_dst_lo < 1 || a.tree_lo < a.tree_dst_lo || a.tree_src_lo < 0 || a.tree_src_lo >= a.tree_dst_lo || a.tree_sx == a.x)
     return hipErrorInvalidValue;
@@ -136,6 +163,11 @@ hipError_t pocs_launch_mc_tree_step(int nblk, const pocs_mc_launch& a, hipStream
 
 hipError_t pocs_launch_mc_init(int nblk, const pocs_mc_launch& a, hipStream_t s) {
   if ((a.wp_mode != 0 && !a.wp_counts) || (a.obs_counts && !a.wp_mode)) return hipErrorInvalidValue;
+  if (a.world) {                                      // a large world (no per-box counts there)
+    if (a.obs_counts || a.world_M < 1 || a.world_M > POCS_MAX_WORLD_RECORDS) return hipErrorInvalidValue;
+    if (a.wp_mode) hipLaunchKernelGGL(k_mc_init_world<MC_COUNTS>, dim3(nblk, a.nruns), dim3(POCS_BLOCK), 0, s, a);
+    else           hipLaunchKernelGGL(k_mc_init_world<MC_PLAIN>, dim3(nblk, a.nruns), dim3(POCS_BLOCK), 0, s, a);
+  } else
   if (a.obs_counts) hipLaunchKernelGGL(k_mc_init<MC_COUNTS | MC_BOXES>, dim3(nblk, a.nruns), dim3(POCS_BLOCK), 0, s, a);
   else if (a.wp_mode) hipLaunchKernelGGL(k_mc_init<MC_COUNTS>, dim3(nblk, a.nruns), dim3(POCS_BLOCK), 0, s, a);
   else           hipLaunchKernelGGL(k_mc_init<MC_PLAIN>, dim3(nblk, a.nruns), dim3(POCS_BLOCK), 0, s, a);
@@ -144,6 +176,20 @@ hipError_t pocs_launch_mc_init(int nblk, const pocs_mc_launch& a, hipStream_t s)
 hipError_t pocs_launch_mc_step(int nblk, const pocs_mc_launch& a, hipStream_t s) {
   const dim3 grid(nblk, a.nruns), block(POCS_BLOCK);
   if ((a.wp_mode != 0 && !a.wp_counts) || (a.obs_counts && !a.wp_mode)) return hipErrorInvalidValue;
+  if (a.world) {                                      // a large world: the same three modes, no per-box counts
+    if (a.obs_counts || a.world_M < 1 || a.world_M > POCS_MAX_WORLD_RECORDS) return hipErrorInvalidValue;
+    if (a.wp_mode != 0 && (a.step < 0 || a.step + 1 >= a.W || (a.wp_mode == 2 && (!a.wp_stop || a.wp_n < 1)))) return hipErrorInvalidValue;
+    if (a.wp_mode == 2) {
+      if (a.nontemporal) hipLaunchKernelGGL((k_mc_step_world<true, MC_STOP>), grid, block, 0, s, a);
+      else               hipLaunchKernelGGL((k_mc_step_world<false, MC_STOP>), grid, block, 0, s, a);
+    } else if (a.wp_mode == 1) {
+      if (a.nontemporal) hipLaunchKernelGGL((k_mc_step_world<true, MC_COUNTS>), grid, block, 0, s, a);
+      else               hipLaunchKernelGGL((k_mc_step_world<false, MC_COUNTS>), grid, block, 0, s, a);
+    } else {
+      if (a.nontemporal) hipLaunchKernelGGL((k_mc_step_world<true, MC_PLAIN>), grid, block, 0, s, a);
+      else               hipLaunchKernelGGL((k_mc_step_world<false, MC_PLAIN>), grid, block, 0, s, a);
+    }
+  } else
   if (a.obs_counts) {                                 // ... and per obstacle box: the MC_BOXES forms of the two below
     if (a.step < 0 || a.step + 1 >= a.W || (a.wp_mode == 2 && (!a.wp_stop || a.wp_n < 1))) return hipErrorInvalidValue;
     if (a.wp_mode == 2) {
@@ -167,6 +213,7 @@ hipError_t pocs_launch_mc_step(int nblk, const pocs_mc_launch& a, hipStream_t s)
 }
 hipError_t pocs_launch_mc_fused(int nblk, const pocs_mc_launch& a, hipStream_t s) {
   if (a.wp_mode == 2 || (a.wp_mode != 0 && !a.wp_counts) || (a.obs_counts && !a.wp_mode)) return hipErrorInvalidValue;      // (no stop without a launch boundary per step)
+  if (a.world) return hipErrorInvalidValue;           // (a large world is not staged: no fused form)
   if (a.obs_counts) {
     if (a.env_steps > 1) hipLaunchKernelGGL(k_mc_fused_sched<MC_COUNTS | MC_BOXES>, dim3(nblk, a.nruns), dim3(POCS_BLOCK), 0, s, a);
     else                 hipLaunchKernelGGL(k_mc_fused_boxes, dim3(nblk, a.nruns), dim3(POCS_BLOCK), 0, s, a);

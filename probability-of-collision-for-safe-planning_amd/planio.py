@@ -181,3 +181,36 @@ def moving_boxes(boxes0, velocity, S):
         out[s, :, 1] = b[:, 1] + float(s) * v[:, 1]
         out[s, :, 4] = b[:, 4] + float(s) * v[:, 2]
     return out
+
+
+MAX_WORLD_BOXES = 4096
+
+
+def grid_boxes(occupancy, cell, origin=(0.0, 0.0)):
+    """A 2-D boolean occupancy grid -> boxes M x 5 (cx, cy, half_x, half_y, yaw = 0) as Context.set_world takes them: one box per
+    maximal horizontal run of occupied cells.  occupancy[r][c] is the cell [origin_x + c * cell, origin_x + (c + 1) * cell] x
+    [origin_y + r * cell, origin_y + (r + 1) * cell]; the boxes come row by row, left to right.  ValueError for a grid that is not
+    2-D, a cell size that is not positive, or more than 4096 boxes."""
+    occ = np.asarray(occupancy).astype(bool)
+    cell = float(cell)
+    if occ.ndim != 2:
+        raise ValueError("an occupancy grid is 2-D, got shape %s" % (occ.shape,))
+    if not cell > 0.0:
+        raise ValueError("the cell size must be positive, got %r" % cell)
+    x0, y0 = float(origin[0]), float(origin[1])
+    boxes = []
+    for r in range(occ.shape[0]):
+        c = 0
+        while c < occ.shape[1]:
+            if not occ[r, c]:
+                c += 1
+                continue
+            c1 = c
+            while c1 + 1 < occ.shape[1] and occ[r, c1 + 1]:
+                c1 += 1
+            n = c1 - c + 1
+            boxes.append([x0 + cell * (c + 0.5 * n), y0 + cell * (r + 0.5), 0.5 * cell * n, 0.5 * cell, 0.0])
+            c = c1 + 1
+    if len(boxes) > MAX_WORLD_BOXES:
+        raise ValueError("the grid makes %d boxes, a world holds at most %d" % (len(boxes), MAX_WORLD_BOXES))
+    return np.array(boxes, dtype=np.float64).reshape(-1, 5)
