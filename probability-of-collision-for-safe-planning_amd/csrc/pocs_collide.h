@@ -100,28 +100,151 @@ POCS_HD bool pocs_pose_collides(double x, double y, double th, const pocs_footpr
 }
 
 // The same predicate for the two poses a thread of k_gmm_step draws per iteration, with ONE pass over the obstacle
-// table: every record is read once for both poses (the table sits in LDS), the loop's bookkeeping is paid once.
-// Per pose exactly the operations of pocs_pose_collides, in the same order: the same flags.
-//   EAGER (k_gmm_step's lone form, whose sampling phase is latency): a record's eight doubles are all requested at the
-//   head of its iteration and waited for once, instead of field by field as the tests get to them (three LDS round
-//   trips per pose where lanes reach the narrow phase)
+// table (it sits in LDS) and the loop's bookkeeping paid once.  Per pose exactly the operations of pocs_pose_collides, in
+// the same order: the same flags.  On the device (pocs_pair_loop) the compiled loop
+//   - fetches a record ONCE for both poses, as 16-byte reads from an address held in one vector register that advances
+//     per record: (cx, cy) and (bx, by) for the broad phase, and (ax, ay), (hx, hy) where some lane of either pose is
+//     inside the record's box (the compiler issues that second pair behind the scalar branch);
+//   - computes the headings' sines and cosines once per call at most, the first time some lane of either pose passes a
+//     record's broad phase (a wave-uniform branch), when the footprint is centred: x, y and the record decide the broad
+//     phase alone then, and are used in place.  An offset footprint needs the heading for (px, py) and keeps it in front;
+//   - hands back each pose's flag as a 64-bit LANE MASK in scalar registers: a record's answer is balloted where the
+//     narrow phase has given it and or-ed in by a scalar instruction.  The mask is zero when M <= 0.
+//   EAGER (k_gmm_step's lone form, whose sampling phase is latency): a record's eight doubles are all waited for at the
+//   head of its iteration, once.
+// The host path keeps the plain loop below.
+#if defined(__HIPCC__)
+typedef double pocs_v2d __attribute__((ext_vector_type(2)));
+struct pocs_each_none { __device__ __forceinline__ void operator()(int, int, bool) const {} };
+
+// pocs_box_margins for the lanes of `pm` (those inside the record's broad-phase box), the answer as a lane mask.  Every
+// branch is wave-uniform: the wave computes with all its lanes -- a vector instruction costs the same under any exec mask
+// -- and the lanes that count are picked by scalar ands of compare results, so no flag ever lives in a vector register.
+// Per lane the operations of pocs_box_margins, in its order, with its early return after the obstacle's own axes.
+__device__ __forceinline__ unsigned long long pocs_box_margins_mask(unsigned long long pm, double dx, double dy, double sn, double cs,
+                                                                    double rx, double ry, double hx, double hy,
+                                                                    double cr, double sr, double e1, double e2,
+                                                                    double p3, double p4) {
+  // p3, p4: the footprint's extents along the obstacle's axes, fma(rx, |cr|, ry * |sr|) and fma(rx, |sr|, ry * |cr|) -- the
+  // caller's, because for an axis-aligned record they are functions of the heading alone, formed once with it
+  const double m3 = fabs(e1) - (hx + p3);
+  const double m4 = fabs(e2) - (hy + p4);
+  const unsigned long long near = pm & __builtin_amdgcn_ballot_w64(!(fmax(m3, m4) > 0.0));
+  if (near == 0ull) return 0ull;
+  asm volatile("; footprint axes");                                // keeps the early return a branch
+  const double d1 = fma(dx, cs, dy * sn);
+  const double d2 = fma(dy, cs, -(dx * sn));
+  const double m1 = fabs(d1) - (rx + fma(hx, fabs(cr), hy * fabs(sr)));
+  const double m2 = fabs(d2) - (ry + fma(hx, fabs(sr), hy * fabs(cr)));
+  return near & __builtin_amdgcn_ballot_w64(!(fmax(m1, m2) > 0.0));
+}
+
+template <bool EAGER, bool CENTRED, class Each>
+__device__ __forceinline__ void pocs_pair_loop(const double x[2], const double y[2], const double th[2], const pocs_footprint* fp,
+                                               const double* obs, int M, const pocs_tables* T, const pocs_vconst* V,
+                                               unsigned long long mask[2], Each each) {
+  const double rx = fp->hx, ry = fp->hy;
+  double sn[2], cs[2], px[2], py[2];
+  double ex[2], ey[2];                                             // the footprint's extents along world x and y at the two headings
+  bool heading = false;                                            // (wave-uniform) sn, cs, ex, ey hold the two headings' values
+  // (until then they hold nothing: said to the compiler, which otherwise zeroes them in front of the loop)
+  if (CENTRED) asm volatile("" : "=v"(sn[0]), "=v"(cs[0]), "=v"(sn[1]), "=v"(cs[1]), "=v"(ex[0]), "=v"(ey[0]), "=v"(ex[1]), "=v"(ey[1]));
+  if (!CENTRED) {
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+      pocs_sincos_tab(th[h], T, &sn[h], &cs[h], V);
+      px[h] = x[h] + fma(cs[h], fp->dx, -(sn[h] * fp->dy));
+      py[h] = y[h] + fma(sn[h], fp->dx, cs[h] * fp->dy);
+      ex[h] = fma(rx, fabs(cs[h]), ry * fabs(sn[h]));
+      ey[h] = fma(rx, fabs(sn[h]), ry * fabs(cs[h]));
+    }
+    heading = true;
+  }
+  unsigned long long m0 = 0ull, m1 = 0ull;
+  // the record's address: LDS, one vector register, advanced per record (left to itself the compiler keeps it scalar and
+  // moves it into a vector register in front of every read)
+  const __attribute__((address_space(3))) pocs_v2d* o = (const __attribute__((address_space(3))) pocs_v2d*)obs;
+  asm volatile("" : "+v"(o));
+  for (int m = 0; m < M; ++m, o += POCS_OBS_STRIDE / 2) {
+    pocs_v2d c = o[0], b = o[3], a = o[1], e = o[2];               // (cx, cy) (bx, by) | (ax, ay) (hx, hy)
+    if (EAGER) asm volatile("" : "+v"(c), "+v"(b), "+v"(a), "+v"(e));
+    double dx[2], dy[2];
+    unsigned long long pm[2], bt[2] = {0ull, 0ull};
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {                                  // pocs_box_hit's broad phase
+      dx[h] = c.x - (CENTRED ? x[h] : px[h]);
+      dy[h] = c.y - (CENTRED ? y[h] : py[h]);
+      pm[h] = __builtin_amdgcn_ballot_w64(!(fabs(dx[h]) > b.x)) & __builtin_amdgcn_ballot_w64(!(fabs(dy[h]) > b.y));
+    }
+    if ((pm[0] | pm[1]) != 0ull) {                                 // pocs_box_narrow for the lanes inside the box
+      if (CENTRED && !heading) {
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+          double t = th[h];
+          asm volatile("" : "+v"(t));                              // the argument reduction stays in here too: not hoisted in front of the loop
+          pocs_sincos_tab(t, T, &sn[h], &cs[h], V);
+          ex[h] = fma(rx, fabs(cs[h]), ry * fabs(sn[h]));
+          ey[h] = fma(rx, fabs(sn[h]), ry * fabs(cs[h]));
+        }
+        heading = true;
+      }
+      // an axis-aligned record (every lane reads the same one): the relative yaw IS the heading, the offset as it is
+      const bool turned = (__builtin_amdgcn_ballot_w64(a.x != 1.0) | __builtin_amdgcn_ballot_w64(a.y != 0.0)) != 0ull;
+#pragma unroll
+      for (int h = 0; h < 2; ++h) {
+        if (pm[h] == 0ull) continue;
+        if (!turned)
+          bt[h] = pocs_box_margins_mask(pm[h], dx[h], dy[h], sn[h], cs[h], rx, ry, e.x, e.y, cs[h], sn[h], dx[h], dy[h], ex[h], ey[h]);
+        else {
+          const double cr = fma(cs[h], a.x, sn[h] * a.y), sr = fma(sn[h], a.x, -(cs[h] * a.y));      // the relative yaw
+          bt[h] = pocs_box_margins_mask(pm[h], dx[h], dy[h], sn[h], cs[h], rx, ry, e.x, e.y, cr, sr,
+                                        fma(dx[h], a.x, dy[h] * a.y), fma(dy[h], a.x, -(dx[h] * a.y)),   // d in the obstacle frame
+                                        fma(rx, fabs(cr), ry * fabs(sr)), fma(rx, fabs(sr), ry * fabs(cr)));
+        }
+      }
+      m0 |= bt[0]; m1 |= bt[1];
+    }
+#pragma unroll
+    for (int h = 0; h < 2; ++h) each(m, h, __builtin_amdgcn_inverse_ballot_w64(bt[h]));
+  }
+  mask[0] = m0; mask[1] = m1;
+}
+
+// The pair's flags as lane masks (bit l: lane l's pose h touches some record; lanes that do not run the call stay 0).
+template <bool EAGER = false, class Each = pocs_each_none>
+__device__ __forceinline__ void pocs_pair_collides_masks(const double x[2], const double y[2], const double th[2], const pocs_footprint* fp,
+                                                         const double* obs, int M, const pocs_tables* T, const pocs_vconst* V,
+                                                         unsigned long long mask[2], Each each = Each()) {
+  mask[0] = 0ull; mask[1] = 0ull;
+  if (M <= 0) return;
+  // (scalar) the loop twice, not one loop behind a merge of (x, y) with (px, py): merged, the centred footprint pays four
+  // 64-bit register copies per call for values it already holds
+  if (fp->dx == 0.0 && fp->dy == 0.0) {
+    pocs_pair_loop<EAGER, true>(x, y, th, fp, obs, M, T, V, mask, each);
+  } else {
+    asm volatile("; offset footprint");
+    pocs_pair_loop<EAGER, false>(x, y, th, fp, obs, M, T, V, mask, each);
+  }
+}
+#endif
+
 template <bool EAGER = false>
 POCS_HD void pocs_pair_collides(const double x[2], const double y[2], const double th[2], const pocs_footprint* fp,
                                 const double* obs, int M, const pocs_tables* T, const pocs_vconst* V, bool hit[2]) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  unsigned long long mask[2];
+  pocs_pair_collides_masks<EAGER>(x, y, th, fp, obs, M, T, V, mask);
+  hit[0] = __builtin_amdgcn_inverse_ballot_w64(mask[0]);
+  hit[1] = __builtin_amdgcn_inverse_ballot_w64(mask[1]);
+#else
   hit[0] = false; hit[1] = false;
   if (M <= 0) return;
   double sn[2], cs[2], px[2], py[2];
-#if defined(__HIP_DEVICE_COMPILE__)
-#pragma unroll
-#endif
   for (int h = 0; h < 2; ++h) {
     pocs_sincos_tab(th[h], T, &sn[h], &cs[h], V);
     px[h] = x[h]; py[h] = y[h];
   }
   if (!(fp->dx == 0.0 && fp->dy == 0.0)) {
-#if defined(__HIP_DEVICE_COMPILE__)
-    asm volatile("; offset footprint");
-#endif
     for (int h = 0; h < 2; ++h) {
       px[h] = x[h] + fma(cs[h], fp->dx, -(sn[h] * fp->dy));
       py[h] = y[h] + fma(sn[h], fp->dx, cs[h] * fp->dy);
@@ -129,29 +252,19 @@ POCS_HD void pocs_pair_collides(const double x[2], const double y[2], const doub
   }
   for (int m = 0; m < M; ++m) {
     const double* o = obs + m * POCS_OBS_STRIDE;
-#if defined(__HIP_DEVICE_COMPILE__)
-    double rec[POCS_OBS_STRIDE];
-    if (EAGER) {
-#pragma unroll
-      for (int q = 0; q < POCS_OBS_STRIDE; ++q) rec[q] = o[q];
-      asm volatile("" : "+v"(rec[0]), "+v"(rec[1]), "+v"(rec[2]), "+v"(rec[3]), "+v"(rec[4]), "+v"(rec[5]), "+v"(rec[6]), "+v"(rec[7]));
-      o = rec;
-    }
-#pragma unroll
-#endif
-    // `if (...) hit = true`, not `hit |= ...`: the flag then stays a lane mask in scalar registers across the
-    // loop, merged by scalar instructions; or-ed in as an integer it cost a v_cndmask and a v_or per record and pose
     for (int h = 0; h < 2; ++h)
       if (pocs_box_hit(px[h], py[h], sn[h], cs[h], fp->hx, fp->hy, o)) hit[h] = true;
   }
+#endif
 }
 
 // The two predicates above with every record's own answer kept (POCS_OPT_OBSTACLE_COUNTS: which box a collision comes
 // from).  Per pose the same operations in the same order -- pocs_box_hit against record m, the flag set under the same
 // condition -- and each answer handed to `each` before the next record is looked at: each(m, touched) for one pose,
 // each(m, h, touched) for pose h of a pair, called by every lane that runs the loop, outside the test's own branches (a
-// caller may ballot in it).  The flag is set exactly when some record's answer is.  Functions of their own: the forms
-// above stay, instruction for instruction, what they are.
+// caller may ballot in it).  The flag is set exactly when some record's answer is.  The single-pose form is a function of
+// its own: pocs_pose_collides stays, instruction for instruction, what it is.  On the device the pair's form is the one
+// loop of pocs_pair_collides_masks with a callback: every lane's answer for record m comes from that record's lane mask.
 template <class Each>
 POCS_HD bool pocs_pose_collides_each(double x, double y, double th, const pocs_footprint* fp, const double* obs, int M,
                                      const pocs_tables* T, Each each, const pocs_vconst* V = nullptr) {
@@ -178,20 +291,20 @@ POCS_HD bool pocs_pose_collides_each(double x, double y, double th, const pocs_f
 template <bool EAGER = false, class Each>
 POCS_HD void pocs_pair_collides_each(const double x[2], const double y[2], const double th[2], const pocs_footprint* fp,
                                      const double* obs, int M, const pocs_tables* T, const pocs_vconst* V, bool hit[2], Each each) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  unsigned long long mask[2];
+  pocs_pair_collides_masks<EAGER>(x, y, th, fp, obs, M, T, V, mask, each);
+  hit[0] = __builtin_amdgcn_inverse_ballot_w64(mask[0]);
+  hit[1] = __builtin_amdgcn_inverse_ballot_w64(mask[1]);
+#else
   hit[0] = false; hit[1] = false;
   if (M <= 0) return;
   double sn[2], cs[2], px[2], py[2];
-#if defined(__HIP_DEVICE_COMPILE__)
-#pragma unroll
-#endif
   for (int h = 0; h < 2; ++h) {
     pocs_sincos_tab(th[h], T, &sn[h], &cs[h], V);
     px[h] = x[h]; py[h] = y[h];
   }
   if (!(fp->dx == 0.0 && fp->dy == 0.0)) {
-#if defined(__HIP_DEVICE_COMPILE__)
-    asm volatile("; offset footprint");
-#endif
     for (int h = 0; h < 2; ++h) {
       px[h] = x[h] + fma(cs[h], fp->dx, -(sn[h] * fp->dy));
       py[h] = y[h] + fma(sn[h], fp->dx, cs[h] * fp->dy);
@@ -199,22 +312,13 @@ POCS_HD void pocs_pair_collides_each(const double x[2], const double y[2], const
   }
   for (int m = 0; m < M; ++m) {
     const double* o = obs + m * POCS_OBS_STRIDE;
-#if defined(__HIP_DEVICE_COMPILE__)
-    double rec[POCS_OBS_STRIDE];
-    if (EAGER) {
-#pragma unroll
-      for (int q = 0; q < POCS_OBS_STRIDE; ++q) rec[q] = o[q];
-      asm volatile("" : "+v"(rec[0]), "+v"(rec[1]), "+v"(rec[2]), "+v"(rec[3]), "+v"(rec[4]), "+v"(rec[5]), "+v"(rec[6]), "+v"(rec[7]));
-      o = rec;
-    }
-#pragma unroll
-#endif
     for (int h = 0; h < 2; ++h) {
       const bool t = pocs_box_hit(px[h], py[h], sn[h], cs[h], fp->hx, fp->hy, o);
       if (t) hit[h] = true;
       each(m, h, t);
     }
   }
+#endif
 }
 
 // The footprint's largest half-extent along world x over all headings in [lo, hi] (along world y: the

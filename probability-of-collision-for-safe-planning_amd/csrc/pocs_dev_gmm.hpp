@@ -229,8 +229,8 @@ __device__ __forceinline__ void gmm_cull(const pocs_gmm_launch& a, gmm_smem<K, T
 //   the same bits -- a call of one run then spends its sampling phase on what depends on the mixture only
 //   OC (POCS_OPT_OBSTACLE_COUNTS): per kept record and pose of the pair, the lanes that touch it and whose sample exists are
 //   balloted; hits are rare, so a zero ballot -- nearly all of them -- is skipped by a scalar branch, and otherwise one lane
-//   adds the population count to the block's LDS counter of (run buffer, kept slot).  Nothing else differs: pocs_pair_collides_each
-//   is pocs_pair_collides with every record's answer handed out.
+//   adds the population count to the block's LDS counter of (run buffer, kept slot).  Nothing else differs: the same
+//   pocs_pair_collides_masks, with every record's answer handed out.
 template <int K, bool STORE, int TB, bool LONE_PRE = false, bool OC = false>
 __device__ __forceinline__ void gmm_units(const pocs_gmm_launch& a, gmm_smem<K, TB, OC>& sm, const int w, const int r0,
                                           const int ta, const int tb, const double* zpre = nullptr, const int npre = 0) {
@@ -313,7 +313,7 @@ __device__ __forceinline__ void gmm_units(const pocs_gmm_launch& a, gmm_smem<K, 
     const int i0 = 2 * lp;
     const bool two = WHOLE || (live && (i0 + 1) < count);  // false only for the last sample of an odd shard
     double xs[2], ys[2], ts[2];
-    bool hits[2];
+    unsigned long long hits[2];                     // the two poses' flags as lane masks (pocs_pair_collides_masks)
     int ks[2];
 #pragma unroll
     for (int h = 0; h < 2; ++h) {
@@ -336,13 +336,13 @@ __device__ __forceinline__ void gmm_units(const pocs_gmm_launch& a, gmm_smem<K, 
     POCS_TUNE_COLLIDE_STATS();
     if constexpr (OC) {
       unsigned* const occ = sm.occ[rb];
-      pocs_pair_collides_each<LONE_PRE>(xs, ys, ts, &fp, s_keep, nkeep, s_tab, vc, hits, [&](const int m, const int h, const bool t) {
+      pocs_pair_collides_masks<LONE_PRE>(xs, ys, ts, &fp, s_keep, nkeep, s_tab, vc, hits, [&](const int m, const int h, const bool t) {
         const unsigned long long b = __ballot(t && (h == 0 ? live : two));      // the odd shard's unused twin does not count
         if (b != 0ull && lane == (int)__builtin_ctzll(b))
           __hip_atomic_fetch_add(&occ[m], (unsigned)__popcll(b), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
       });
     } else {
-    POCS_TUNE_COLLIDE(pocs_pair_collides<LONE_PRE>(xs, ys, ts, &fp, s_keep, nkeep, s_tab, vc, hits));
+    POCS_TUNE_COLLIDE(pocs_pair_collides_masks<LONE_PRE>(xs, ys, ts, &fp, s_keep, nkeep, s_tab, vc, hits));
     }
     if constexpr (POCS_TUNE_SKIP_MOMENTS) { POCS_TUNE_MOMENTS_ALT(); } else {
     // T1 sums over the collision-free samples of the component being accumulated:
@@ -350,8 +350,8 @@ __device__ __forceinline__ void gmm_units(const pocs_gmm_launch& a, gmm_smem<K, 
     if (WHOLE) {
 #pragma unroll
       for (int h = 0; h < 2; ++h) {
-        nfree += __popcll(__ballot(!hits[h]));
-        if (!hits[h]) {                             // the few lanes that collided sit this out
+        nfree += __popcll(~hits[h]);                // every lane is live: the survivors are the mask's zero bits
+        if (!__builtin_amdgcn_inverse_ballot_w64(hits[h])) {      // the few lanes that collided sit this out: exec from the mask
           const double x = xs[h], y = ys[h], t = ts[h];
           acc[0] += x; acc[1] += y; acc[2] += t;
           acc[3] = fma(x, x, acc[3]); acc[4] = fma(x, y, acc[4]); acc[5] = fma(x, t, acc[5]);
@@ -374,7 +374,7 @@ __device__ __forceinline__ void gmm_units(const pocs_gmm_launch& a, gmm_smem<K, 
 #pragma unroll
         for (int h = 0; h < 2; ++h) {
           const bool sel = (h == 0 ? live : two) && ks[h] == kk;
-          const bool cnt = sel && !hits[h];
+          const bool cnt = sel && !__builtin_amdgcn_inverse_ballot_w64(hits[h]);
           nfree += __popcll(__ballot(cnt));
           const double ind = cnt ? 1.0 : 0.0;
           const double xm = ind * xs[h], ym = ind * ys[h], tm = ind * ts[h];
@@ -392,7 +392,8 @@ __device__ __forceinline__ void gmm_units(const pocs_gmm_launch& a, gmm_smem<K, 
       // past the caches.  The loop counter is wave-uniform (SGPRs) and the lane adds its tid: the store
       // addresses are a scalar base per iteration plus a constant 16*tid, no per-lane 64-bit arithmetic.
       const size_t ub = 2 * (size_t)(unsigned)base;
-      const int fl = (hits[0] ? 1 : 0) | ((two && hits[1]) ? 0x10000 : 0);
+      const int fl = (__builtin_amdgcn_inverse_ballot_w64(hits[0]) ? 1 : 0) |
+                     ((two && __builtin_amdgcn_inverse_ballot_w64(hits[1])) ? 0x10000 : 0);      // selects on the masks
       store16_nt(xr + ub, 16u * (unsigned)tid, (v2d){xs[0], xs[1]});
       store16_nt(yr + ub, 16u * (unsigned)tid, (v2d){ys[0], ys[1]});
       store16_nt(tr + ub, 16u * (unsigned)tid, (v2d){ts[0], ts[1]});

@@ -63,13 +63,13 @@ __device__ unsigned long long g_stamps[24 * 256];            // a set per block 
 #define POCS_TUNE_NORMALS(...) __VA_ARGS__
 #endif
 #if defined(POCS_ABLATE_COLLIDE)
-#define POCS_TUNE_COLLIDE(...) hits[0] = xs[0] > ts[0]; hits[1] = xs[1] > ts[1]
+#define POCS_TUNE_COLLIDE(...) hits[0] = __ballot(xs[0] > ts[0]); hits[1] = __ballot(xs[1] > ts[1])
 #else
 #define POCS_TUNE_COLLIDE(...) __VA_ARGS__
 #endif
 #if defined(POCS_ABLATE_MOMENTS)
 #define POCS_TUNE_SKIP_MOMENTS true
-#define POCS_TUNE_MOMENTS_ALT() do { acc[1] += xs[0] + ys[0] + ts[0] + xs[1]; nfree += (hits[0] || (two && ks[1] == 0)) ? 0 : 1; } while (0)
+#define POCS_TUNE_MOMENTS_ALT() do { acc[1] += xs[0] + ys[0] + ts[0] + xs[1]; nfree += (__builtin_amdgcn_inverse_ballot_w64(hits[0]) || (two && ks[1] == 0)) ? 0 : 1; } while (0)
 #else
 #define POCS_TUNE_SKIP_MOMENTS false
 #define POCS_TUNE_MOMENTS_ALT() do { } while (0)
