@@ -421,6 +421,10 @@ long long pocs_copy_particles(pocs_ctx* ctx, double* xyt_aos, uint32_t* hits, lo
 int pocs_measure_copy_bandwidth(pocs_ctx* ctx, long long bytes, double* gbps);  /* read+write GB/s of a plain streaming copy on this GPU: the measured HBM ceiling */
 int pocs_measure_fill_bandwidth(pocs_ctx* ctx, long long bytes, double* gbps);  /* written GB/s of a plain streaming fill: the write-only ceiling (the GMM kernels read nothing) */
 int pocs_get_kernel_time(pocs_ctx* ctx, double* total_ms, long long* launches);  /* hot-kernel time of the last run with POCS_OPT_PROFILE=1 (of the launches on the context's stream) */
+int pocs_get_graph_captures(pocs_ctx* ctx, long long* gmm, long long* mc);  /* how often the launches of the whole GMM call and of the MC call have been captured into a
+                                                                               hipGraph since the context was created (either may be null).  A call replays the cached graph
+                                                                               while its launches -- kernels, grids, streams, argument bytes -- are the captured ones: setters
+                                                                               that change none of them (a seed, a plan of the same length, obstacles of the same count) add nothing */
 int pocs_get_exchange_wait(pocs_ctx* ctx, double* min_median_max_us);  /* sharded GMM calls through the library's own exchange (pocs_gmm_exchange_local /
                                                                           pocs_gmm_sample_exchange_local): how long the closers of the last begin..end sequence
                                                                           waited for the other ranks' moments, over its (run, waypoint) pairs -- the first thing

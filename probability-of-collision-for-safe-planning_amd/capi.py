@@ -96,6 +96,7 @@ SIGNATURES = {
     "pocs_get_kernel_time": (C.c_int, [_vp, _dp, C.POINTER(C.c_longlong)]),
     "pocs_get_sequence_time": (C.c_int, [_vp, _dp, C.POINTER(C.c_int)]),
     "pocs_get_exchange_wait": (C.c_int, [_vp, _dp]),
+    "pocs_get_graph_captures": (C.c_int, [_vp, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong)]),
     "pocs_probe_device_math": (C.c_int, [_vp, C.c_int, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), _dp, _dp, _dp, _dp, _dp, _dp]),
     "pocs_probe_device_collide": (C.c_int, [_vp, C.c_int, _dp, C.c_int, _dp, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int),
                                             C.POINTER(C.c_int), _dp]),
@@ -609,6 +610,12 @@ class Context:
         self._chk(self.lib.pocs_probe_device_collide(self.h, K, par.ctypes.data_as(_dp), n, xyt.ctypes.data_as(_dp),
                                                      *[f.ctypes.data_as(ip) for f in flags], C.byref(nkeep), kept.ctypes.data_as(_dp)))
         return flags[0], flags[1], flags[2], kept[:nkeep.value].copy()
+
+    def graph_captures(self):
+        """(gmm, mc): how often the whole GMM call's and the MC call's launches have been captured into a graph so far."""
+        g, m = C.c_longlong(), C.c_longlong()
+        self._chk(self.lib.pocs_get_graph_captures(self.h, C.byref(g), C.byref(m)))
+        return g.value, m.value
 
     def kernel_time(self):
         ms, n = C.c_double(), C.c_longlong()

@@ -442,7 +442,7 @@ int pocs_set_plans(pocs_ctx* c, int P, const int* W, const double* trajs, const 
 
 int pocs_set_plan_risk_bound(pocs_ctx* c, double bound) {
   if (!c) return POCS_E_ARG;
-  touch(c);                                          // (the epoch is part of the graphs' key: no graph captured for another bound is replayed)
+  touch(c);
   if (!(bound > 0.0)) return fail(c, POCS_E_ARG, "risk bound %g: a probability in (0, 1), or >= 1 for none", bound);     // (NaN too)
   if (c->gmm_open) return fail(c, POCS_E_ORDER, "pocs_set_plan_risk_bound inside a begin/end sequence");
   c->risk_bound = bound < 1.0 ? bound : 1.0;
@@ -571,7 +571,6 @@ int pocs_set_stream(pocs_ctx* c, void* s) {
   if (c) touch(c);
   if (!c) return POCS_E_ARG;
   c->stream = s ? (hipStream_t)s : c->own_stream;
-  drop_graphs(c);
   return POCS_OK;
 }
 
@@ -580,7 +579,6 @@ int pocs_gmm_bind_moments(pocs_ctx* c, void* dptr, long long len) {
   if (!c) return POCS_E_ARG;
   if (dptr && large_world(c)) return fail(c, POCS_E_STATE, "pocs_gmm_bind_moments under a large world of %d boxes (pocs_set_world): the step API serves worlds of at most %d boxes", large_boxes(c), POCS_MAX_OBSTACLES);
   c->ext_moments = (double*)dptr; c->ext_moments_len = dptr ? len : 0;
-  drop_graphs(c);
   return POCS_OK;
 }
 

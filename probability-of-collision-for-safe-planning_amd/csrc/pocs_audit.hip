@@ -308,16 +308,23 @@ int pocs_get_sequence_time(pocs_ctx* c, double* ms, int* concurrent) {
 // for the other ranks' moments, over its (run, waypoint) pairs: min, median, max in microseconds.
 int pocs_get_exchange_wait(pocs_ctx* c, double* min_median_max_us) {
   if (!c || !min_median_max_us) return POCS_E_ARG;
-  if (c->W < 1 || c->batch < 1 || !c->d_ticket.p) return fail(c, POCS_E_STATE, "no GMM call yet");
+  if (!c->sync.cells || !c->d_ticket.p) return fail(c, POCS_E_STATE, "no GMM call yet");
   HIPCHK(c, hipSetDevice(c->device));
-  const size_t n = (size_t)c->batch * (size_t)c->W;
+  const size_t n = c->sync.cells;                      // (the layout of the call that filled the block, whatever the setters have said since)
   std::vector<unsigned> v(n);
   HIPCHK(c, hipStreamSynchronize(c->stream));
-  if (int r = copy_out(c, v.data(), (unsigned*)c->d_ticket.p + sync_xwait_offset(c), n * sizeof(unsigned), sizeof(unsigned), sizeof(unsigned))) return r;
+  if (int r = copy_out(c, v.data(), (unsigned*)c->d_ticket.p + c->sync.xwait, n * sizeof(unsigned), sizeof(unsigned), sizeof(unsigned))) return r;
   std::sort(v.begin(), v.end());
   min_median_max_us[0] = 0.01 * v.front();
   min_median_max_us[1] = 0.01 * ((n & 1) ? v[n / 2] : 0.5 * ((double)v[n / 2 - 1] + (double)v[n / 2]));
   min_median_max_us[2] = 0.01 * v.back();
+  return POCS_OK;
+}
+
+int pocs_get_graph_captures(pocs_ctx* c, long long* gmm, long long* mc) {      // captures of either graph since pocs_create
+  if (!c) return POCS_E_ARG;
+  if (gmm) *gmm = c->graph_gmm.captures;
+  if (mc) *mc = c->graph_mc.captures;
   return POCS_OK;
 }
 

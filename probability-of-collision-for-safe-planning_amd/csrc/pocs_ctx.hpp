@@ -1,5 +1,5 @@
 // pocs_ctx.hpp -- what the units of the host runtime share: the context behind the C ABI (include/pocs.h) with its
-// sub-records, error reporting, device buffers, the graph cache's drop, and the functions one unit calls in another.
+// sub-records, error reporting, device buffers, the graph cache's slots, and the functions one unit calls in another.
 //
 //   pocs_stage.hip   host chain, staging layout, run / tree images, look-ahead cache, upload of a call's runs
 //   pocs_host.hip    the run paths: GMM and MC whole calls, their tree forms, the step and exchange API
@@ -90,6 +90,19 @@ struct Results {
   int oc_M = 0, oc_W = 0;                         // boxes of the call's world, rows per slot
 };
 
+// One cached graph and its signature: the bytes of its launches in issue order (Issuer, pocs_host.hip), compared before a replay.
+struct GraphSlot { hipGraphExec_t exec = nullptr; std::vector<unsigned char> sig; long long captures = 0; };
+
+// The synchronisation words of one GMM call (pocs_kernels.h), a block of d_ticket that ONE memset zeroes at the head of the call:
+// [1] give-up code, [0], [2..3] pad, then -- under a risk bound -- the runs' stop words [R] (padded to 4: they travel back with the
+// give-up word in one copy), the tickets [R][W], the closers' exchange waits [R][W].  Computed once per call (gmm_prepare) and
+// kept as the layout of the LAST call: what its getters read with.
+struct SyncLayout {
+  size_t stop = 4, ticket = 4, xwait = 4, words = 0;      // word offsets; the block's words, a multiple of 4 (0: no GMM call yet)
+  size_t cells = 0;                                        // R x W: tickets, and exchange waits
+  size_t pin = 0, copy_words = 1;                          // the give-up word's place in pinned memory (doubles from h_pin) and the words
+};                                                         // its copy moves: the stop words land stop - POCS_SYNC_ABORT behind it
+
 }  // namespace pocs_rt
 
 struct pocs_ctx {
@@ -135,7 +148,7 @@ struct pocs_ctx {
   int reach_R = 0, reach_W = 0;
   long long shard_first = -1, shard_count = -1;
   long long opt_store = 1, opt_fused = 0, opt_graph = 1, opt_profile = 0, opt_lone = 1, opt_groups = 0, opt_mc_nt = -1;
-  unsigned long long epoch = 0;          // bumped by every setter; part of the graph cache key
+  unsigned long long epoch = 0;          // bumped by every setter: the look-ahead image (`ahead`) is valid for one epoch
   int batch = 1;                         // independent GMM estimations advanced in lockstep per call
   // run-ahead (POCS_OPT_RUN_AHEAD): with batch == 1 a run* call evaluates the next `run_ahead` runs
   // of the context in one launch and the following calls are served from it (res.view: the one served last).
@@ -194,9 +207,9 @@ struct pocs_ctx {
                                          // reaches caller memory through it, in pieces of POCS_COPY_CHUNK bytes
   bool env_dirty = true, sensor_dirty = true;
 
-  hipGraphExec_t graph_gmm = nullptr, graph_mc = nullptr;
-  const void* graph_baked[3] = {nullptr, nullptr, nullptr};   // diagnostic build only (POCS_GRAPH_WITH_COPIES)
-  std::string graph_gmm_key, graph_mc_key;
+  pocs_rt::GraphSlot graph_gmm, graph_mc;
+  std::vector<unsigned char> sig;        // the signature of the call being made (kept for its capacity)
+  pocs_rt::SyncLayout sync;              // of the last GMM call
 
   std::vector<hipEvent_t> events;
   double prof_ms = 0.0;
@@ -228,21 +241,18 @@ inline int fail(pocs_ctx* c, int code, const char* fmt, ...) {
   } while (0)
 
 inline void drop_graphs(pocs_ctx* c) {
-  if (c->graph_gmm) { hipGraphExecDestroy(c->graph_gmm); c->graph_gmm = nullptr; }
-  if (c->graph_mc) { hipGraphExecDestroy(c->graph_mc); c->graph_mc = nullptr; }
-  c->graph_gmm_key.clear();
-  c->graph_mc_key.clear();
+  for (GraphSlot* g : {&c->graph_gmm, &c->graph_mc}) {
+    if (g->exec) { hipGraphExecDestroy(g->exec); g->exec = nullptr; }
+    g->sig.clear();
+  }
 }
 
-// Grow a device buffer.  The captured graphs bake device pointers in (d_hdr and d_chain are shared
-// by the GMM and the MC graph), so replacing ANY buffer drops both of them: the next run captures
-// again against the new pointers.
+// Grow a device buffer (its pointer is part of the signature of the launches that use it: the next call captures its graph again).
 inline int ensure(pocs_ctx* c, DevBuf& b, size_t bytes) {
   if (bytes == 0) bytes = 16;
   if (b.cap >= bytes) return POCS_OK;
   if (b.p) {
     HIPCHK(c, hipStreamSynchronize(c->stream));      // nothing queued may still use the old buffer
-    drop_graphs(c);
     HIPCHK(c, hipFree(b.p)); b.p = nullptr; b.cap = 0;
   }
   HIPCHK(c, hipMalloc(&b.p, bytes));
@@ -312,7 +322,6 @@ int upload_tables(pocs_ctx* c);
 int upload_world(pocs_ctx* c);
 void fill_gmm_world(const pocs_ctx* c, pocs_gmm_launch* a, int w);
 size_t obs_count_words(const pocs_ctx* c);
-size_t sync_xwait_offset(const pocs_ctx* c);
 void gmm_select_view(pocs_ctx* c, int v);
 void tree_select_gmm(pocs_ctx* c, int n);
 int run_gmm_full(pocs_ctx* c, double* probability);

@@ -141,6 +141,69 @@ int prof_collect(pocs_ctx* c, size_t launches) {
 }
 
 // ------------------------------------------------------------------------------------------
+// The issuer and the graph cache
+// ------------------------------------------------------------------------------------------
+// Every kernel launch of a call, the fork and join of its sub-batches and its profiling events go through an Issuer.  In Sign mode
+// (`sig` set) it launches nothing and appends to `sig`, in issue order: per launch the launch function (its address is the tag),
+// the stream's slot (0 = the call's stream, g = side stream g - 1) and the object bytes of every argument, scalar or struct; per
+// fork / join a null tag and the two slots.  Those bytes determine every kernel node of the captured graph, so they are the
+// graph's key: argument structs are zero-filled before they are filled in and copied with memcpy, padding included.
+struct Issuer {
+  pocs_ctx* c;
+  std::vector<unsigned char>* sig;                   // Sign mode; null: Issue mode, which does the work
+  hipStream_t stream(int slot) const { return slot ? c->side_stream[slot - 1] : c->stream; }
+  void put(const void* p, size_t n) { sig->insert(sig->end(), (const unsigned char*)p, (const unsigned char*)p + n); }
+  template <class Fn, class... Args>
+  int launch(Fn* fn, int slot, const Args&... args) {      // fn(args..., stream)
+    if (sig) { put(&fn, sizeof fn); put(&slot, sizeof slot); (put(&args, sizeof args), ...); return POCS_OK; }
+    HIPCHK(c, fn(args..., stream(slot)));
+    return POCS_OK;
+  }
+  int order(int from, int to, hipEvent_t e, bool record = true) {      // fork / join: stream `to` waits for `e`, recorded on stream `from`
+    if (sig) { const void* none = nullptr; put(&none, sizeof none); put(&from, sizeof from); put(&to, sizeof to); return POCS_OK; }
+    if (record) HIPCHK(c, hipEventRecord(e, stream(from)));
+    HIPCHK(c, hipStreamWaitEvent(stream(to), e, 0));
+    return POCS_OK;
+  }
+  int mark(hipEvent_t e, int slot = 0) { if (!sig) HIPCHK(c, hipEventRecord(e, stream(slot))); return POCS_OK; }      // a profiling event: not signed
+};
+
+// The graph cache: leaves in `slot.exec` the graph of `enqueue`'s launches.  `enqueue` runs in Sign mode first: behind the call's
+// stream handle its launches are the call's signature, and the cached graph is good while its own is the same, byte for byte.
+// Otherwise the same function runs in Issue mode under capture.  A setter that changes no launch keeps the graph; a buffer that
+// moved, another stream, a reconnected peer do not -- and nobody has to say so.
+template <class Enqueue>
+int ensure_graph(pocs_ctx* c, GraphSlot& slot, Enqueue enqueue) {
+  c->sig.clear();
+  Issuer{c, &c->sig}.put(&c->stream, sizeof c->stream);
+  if (int r = enqueue(Issuer{c, &c->sig})) return r;
+  if (slot.exec && c->sig == slot.sig) return POCS_OK;
+  if (slot.exec) { hipGraphExecDestroy(slot.exec); slot.exec = nullptr; }
+  hipGraph_t g = nullptr;
+  HIPCHK(c, hipStreamBeginCapture(c->stream, hipStreamCaptureModeThreadLocal));
+  const int r = enqueue(Issuer{c, nullptr});
+  hipError_t e = hipStreamEndCapture(c->stream, &g);
+  if (r) { if (g) hipGraphDestroy(g); return r; }
+  HIPCHK(c, e);
+  e = hipGraphInstantiate(&slot.exec, g, nullptr, nullptr, 0);
+  hipGraphDestroy(g);
+  HIPCHK(c, e);
+  slot.sig = c->sig; slot.captures += 1;
+  return POCS_OK;
+}
+// Run a call's launches: eagerly (POCS_OPT_GRAPH = 0, or POCS_OPT_PROFILE = 1, whose events sit between the launches), or as the
+// replay of their graph -- `span`: between the ev_seq pair (POCS_OPT_PROFILE = 2).
+template <class Enqueue>
+int run_launches(pocs_ctx* c, GraphSlot& slot, bool span, Enqueue enqueue) {
+  if (!c->opt_graph || c->opt_profile == 1) return enqueue(Issuer{c, nullptr});
+  if (int r = ensure_graph(c, slot, enqueue)) return r;
+  if (span) HIPCHK(c, hipEventRecord(c->ev_seq[0], c->stream));
+  HIPCHK(c, hipGraphLaunch(slot.exec, c->stream));
+  if (span) HIPCHK(c, hipEventRecord(c->ev_seq[1], c->stream));
+  return POCS_OK;
+}
+
+// ------------------------------------------------------------------------------------------
 // GMM path
 // ------------------------------------------------------------------------------------------
 int gmm_shard(pocs_ctx* c, long long* first, long long* count) {
@@ -168,10 +231,10 @@ size_t obs_count_words(const pocs_ctx* c) { return (size_t)c->batch * (size_t)(c
 int ensure_obs_counts(pocs_ctx* c) {
   return c->opt_obs_counts ? ensure(c, c->d_obsct, obs_count_words(c) * sizeof(unsigned long long)) : POCS_OK;
 }
-int enqueue_obs_counts_reset(pocs_ctx* c) {
+int enqueue_obs_counts_reset(Issuer is) {
+  pocs_ctx* c = is.c;
   if (!c->opt_obs_counts) return POCS_OK;
-  HIPCHK(c, pocs_launch_zero_counts((unsigned long long*)c->d_obsct.p, obs_count_words(c), c->stream));
-  return POCS_OK;
+  return is.launch(pocs_launch_zero_counts, 0, (unsigned long long*)c->d_obsct.p, obs_count_words(c));
 }
 // what the getter needs to know of the call that has just filled the table (kind: 1 GMM, 2 MC; 0 with the option off)
 void note_obs_counts(pocs_ctx* c, int kind) {
@@ -180,16 +243,19 @@ void note_obs_counts(pocs_ctx* c, int kind) {
   c->res.oc_W = c->W > 0 ? c->W : 1;
 }
 
-// The synchronisation words of one call (pocs_kernels.h): [1] give-up code, [0], [2..3] pad, then -- under a risk bound -- the
-// runs' stop words [R] (padded to 4: they travel back with the give-up word in one copy), then the
-// tickets [R][W], then -- sharded runs -- the closers' exchange waits [R][W]; a block of its own, a multiple of
-// 16 bytes, zeroed by ONE memset at the head of every call.
-size_t sync_stop_offset(const pocs_ctx*) { return 4; }
-size_t sync_ticket_offset(const pocs_ctx* c) { return 4 + (risk_active(c) ? (((size_t)c->batch + 3) & ~(size_t)3) : 0); }
-size_t sync_xwait_offset(const pocs_ctx* c) { return sync_ticket_offset(c) + (size_t)c->batch * (size_t)(c->W > 0 ? c->W : 1); }
-size_t sync_words(const pocs_ctx* c) {
-  const size_t n = sync_xwait_offset(c) + (size_t)c->batch * (size_t)(c->W > 0 ? c->W : 1);      // tickets, then the exchange waits
-  return (n + 3) & ~(size_t)3;
+// The call's synchronisation words (SyncLayout, pocs_ctx.hpp); the copy behind the launches starts at the give-up word and,
+// under a risk bound, runs on through the pad and the stop words.
+SyncLayout sync_layout(const pocs_ctx* c) {
+  static_assert(POCS_SYNC_ABORT < 4, "the give-up word lies ahead of the stop words");
+  SyncLayout s;
+  const size_t R = (size_t)c->batch, stops = risk_active(c) ? R : 0;
+  s.cells = R * (size_t)(c->W > 0 ? c->W : 1);
+  s.ticket = s.stop + ((stops + 3) & ~(size_t)3);
+  s.xwait = s.ticket + s.cells;
+  s.words = (s.xwait + s.cells + 3) & ~(size_t)3;
+  s.pin = pin_layout(c).total + R + 1;
+  s.copy_words = stops ? s.stop - POCS_SYNC_ABORT + stops : 1;
+  return s;
 }
 
 int gmm_prepare(pocs_ctx* c) {
@@ -211,7 +277,8 @@ int gmm_prepare(pocs_ctx* c) {
     return fail(c, POCS_E_BUFFER, "bound moments buffer too small");
   // (x 2: a lone call alternates halves; a tree: its launches cover at most 256 nodes and use the rows one after the other)
   if (int r = ensure(c, c->d_partial, 2 * ((c->tree.n && R > 256 ? (size_t)256 : R) << geo.vs_shift) * K * POCS_NMOM * sizeof(double))) return r;
-  if (int r = ensure(c, c->d_ticket, sync_words(c) * sizeof(unsigned))) return r;
+  c->sync = sync_layout(c);
+  if (int r = ensure(c, c->d_ticket, c->sync.words * sizeof(unsigned))) return r;
   if (c->plans.n)
     if (int r = ensure(c, c->d_runplan, R * 4 * sizeof(double))) return r;
   if (risk_active(c))
@@ -290,12 +357,11 @@ void fill_gmm_world(const pocs_ctx* c, pocs_gmm_launch* a, int w) {
   }
 }
 
-void fill_gmm_launch(pocs_ctx* c, pocs_gmm_launch* a, long long first, long long count, int w,
-                     int run_lo = 0, int run_cnt = -1, int groups = 1) {
+// What the GMM launches of a call share: filled once per call, and every launch is a memcpy of it aimed at its waypoint and runs.
+void fill_gmm_launch(pocs_ctx* c, pocs_gmm_launch* a, long long first, long long count) {
   memset(a, 0, sizeof *a);
-  if (run_cnt < 0) run_cnt = c->batch;
   a->hdr = (const pocs_run_header*)c->d_hdr.p;
-  fill_gmm_world(c, a, w);                           // (a tree: w is the level's depth)
+  fill_gmm_world(c, a, 0);
   a->chain = (const double*)c->d_chain.p;
   a->sensor = (const pocs_sensor*)c->d_sensor.p;
   a->state = (double*)c->d_state.p;
@@ -304,27 +370,44 @@ void fill_gmm_launch(pocs_ctx* c, pocs_gmm_launch* a, long long first, long long
   a->partial = (double*)c->d_partial.p;
   a->partial_prev = a->partial;
   a->sync = (unsigned*)c->d_ticket.p;
-  a->ticket = a->sync + sync_ticket_offset(c);
-  a->xwait = a->sync + sync_xwait_offset(c);
-  const GmmGeometry geo = gmm_geometry(count, run_cnt, c->K, groups);
-  a->chunks = geo.chunks; a->vs_shift = geo.vs_shift; a->upb = geo.upb; a->blocks = geo.blocks;
-  a->run_lo = run_lo; a->run_cnt = run_cnt;
+  a->ticket = a->sync + c->sync.ticket;
+  a->xwait = a->sync + c->sync.xwait;
   a->x = (double*)c->d_sx.p; a->y = (double*)c->d_sy.p; a->th = (double*)c->d_st.p;
   a->flags = (int16_t*)c->d_flags.p;
   a->first = first; a->count = count; a->n_total = c->num_gmm;
-  a->waypoint = w; a->store = c->opt_store ? 1 : 0;
+  a->store = c->opt_store ? 1 : 0;
   a->sample_stride = sample_stride_of(count);
   a->nruns = c->batch; a->W = c->W;
   a->obs_counts = c->opt_obs_counts ? (unsigned long long*)c->d_obsct.p : nullptr;      // (non-null: the sampling launch is the counting form)
 }
+// `w`: the waypoint (a tree: the level's depth), which picks the step of an obstacle schedule; runs [run_lo, run_lo + run_cnt)
+// (run_cnt < 0: the batch), with the geometry of a launch that shares the chip with `groups` - 1 others.
+void aim_gmm_launch(const pocs_ctx* c, pocs_gmm_launch* a, int w, int run_lo = 0, int run_cnt = -1, int groups = 1) {
+  if (run_cnt < 0) run_cnt = c->batch;
+  a->env = world_at(c, w); a->waypoint = w;
+  const GmmGeometry geo = gmm_geometry(a->count, run_cnt, c->K, groups);
+  a->chunks = geo.chunks; a->vs_shift = geo.vs_shift; a->upb = geo.upb; a->blocks = geo.blocks;
+  a->run_lo = run_lo; a->run_cnt = run_cnt;
+}
+
+// The exchange of waypoint w's moments with the connected peers.  `epoch_from_headers`: the kernel forms the rows' epoch and the
+// slot set's parity itself, from the call number in the run headers (a whole call replayed from a graph bakes its arguments in).
+void fill_xchg(const pocs_ctx* c, pocs_xchg_dev* x, int w, bool epoch_from_headers) {
+  memset(x, 0, sizeof *x);
+  for (int q = 0; q < c->xchg_world; ++q) x->buf[q] = (double*)c->xchg_peer[q];
+  x->world = c->xchg_world; x->rank = c->xchg_rank;
+  if (epoch_from_headers) return;
+  x->epoch = (c->xchg_calls << 20) | (unsigned long long)(w + 1);
+  x->parity = (int)((c->xchg_calls * (unsigned long long)c->W + (unsigned long long)w) & 1ull);
+}
 
 // state/param[w] from state/moments[w-1]: its own tiny launch for waypoint 0 and, when sharded,
 // after the caller's all-reduce; on one GPU the last block of k_gmm_step(w-1) has done it already.
-int enqueue_advance(pocs_ctx* c, int w) {
+int enqueue_advance(Issuer is, int w) {
   pocs_gmm_launch a;
-  fill_gmm_launch(c, &a, 0, 0, w);
-  HIPCHK(c, pocs_launch_gmm_advance(c->K, a, c->stream));
-  return POCS_OK;
+  fill_gmm_launch(is.c, &a, 0, 0);
+  aim_gmm_launch(is.c, &a, w);
+  return is.launch(pocs_launch_gmm_advance, 0, is.c->K, a);
 }
 
 // One run per call (no batch, no run-ahead) on one GPU: the launches close the previous waypoint in their heads
@@ -335,7 +418,7 @@ int enqueue_advance(pocs_ctx* c, int w) {
 bool lone_call(const pocs_ctx* c) { return c->opt_lone && !large_world(c) && c->batch == 1 && !c->tree.n && !c->ext_moments && !(c->xchg_connected && c->shard_first >= 0) && !risk_active(c); }
 void set_risk(pocs_ctx* c, pocs_gmm_launch* a) {      // under a risk bound the launch is k_gmm_step_risk (whole calls of plans or on a tree only)
   a->risk = 1;
-  a->stop = a->sync + sync_stop_offset(c);
+  a->stop = a->sync + c->sync.stop;
   a->surv = (double*)c->d_surv.p;
   a->risk_bound = c->risk_bound;
 }
@@ -347,32 +430,38 @@ void set_lone(pocs_ctx* c, pocs_gmm_launch* a, int w) {
   a->partial_prev = (double*)c->d_partial.p + (size_t)((w + 1) & 1) * half;
 }
 
-// adv_cnt >= 0 (a call of plans): only the first adv_cnt of the launch's runs go on past waypoint w.  exchange: the closers
-// exchange the run's moments with the peers, the call's number read from the run headers (the whole-run call only, above)
-int enqueue_step(pocs_ctx* c, long long first, long long count, int w, bool advance_in_tail, bool exchange, int prof_slot,
-                 hipStream_t stream = nullptr, int run_lo = 0, int run_cnt = -1, int groups = 1, bool lone = false, int adv_cnt = -1,
-                 bool risk = false) {
+// The launches of one waypoint for one sub-batch of a call, or for the step API's batch.
+struct StepLaunch {
+  int slot = 0;                                      // the stream: 0 = the call's, g = side stream g - 1
+  int run_lo = 0, run_cnt = -1, groups = 1;          // the runs (run_cnt < 0: the batch), the launches that share the chip
+  bool advance = false;                              // the closers build the next waypoint's mixture in the launch's tail ...
+  int adv_cnt = -1;                                  // ... of the first adv_cnt runs only (a call of plans: the others end here); < 0: all
+  enum { NONE, FROM_CONTEXT, FROM_HEADERS } exchange = NONE;      // ... behind the moments' exchange with the peers; the call's number from the
+  bool lone = false, risk = false;                   // context (step API) or the run headers (the whole-run call ONLY, above).  The lone form;
+  int prof_slot = -1;                                // k_gmm_step_risk (whole calls of plans only).  >= 0: profiling events around the sampling launch
+};
+int enqueue_step(Issuer is, const pocs_gmm_launch& base, int w, const StepLaunch& s) {
+  pocs_ctx* c = is.c;
   pocs_gmm_launch a;
-  if (!stream) stream = c->stream;
-  fill_gmm_launch(c, &a, first, count, w, run_lo, run_cnt, groups);
-  a.advance_in_tail = (advance_in_tail && w + 1 < c->W) ? a.run_lo + (adv_cnt >= 0 ? adv_cnt : a.run_cnt) : 0;   // (the runs below it advance)
-  if (lone) set_lone(c, &a, w);
-  if (risk) set_risk(c, &a);                         // (the whole call of plans only: enqueue_gmm_all)
-  if (exchange) {
+  memcpy(&a, &base, sizeof a);
+  aim_gmm_launch(c, &a, w, s.run_lo, s.run_cnt, s.groups);
+  a.advance_in_tail = (s.advance && w + 1 < c->W) ? a.run_lo + (s.adv_cnt >= 0 ? s.adv_cnt : a.run_cnt) : 0;   // (the runs below it advance)
+  if (s.lone) set_lone(c, &a, w);
+  if (s.risk) set_risk(c, &a);
+  if (s.exchange != StepLaunch::NONE) {
     a.exchange_in_tail = 1;
-    a.xchg_epoch_from_header = 1;
-    for (int q = 0; q < c->xchg_world; ++q) a.xchg.buf[q] = (double*)c->xchg_peer[q];
-    a.xchg.world = c->xchg_world; a.xchg.rank = c->xchg_rank;
+    a.xchg_epoch_from_header = s.exchange == StepLaunch::FROM_HEADERS;
+    fill_xchg(c, &a.xchg, w, a.xchg_epoch_from_header);
   }
-  if (a.world) HIPCHK(c, pocs_launch_world_cull(c->K, a, stream));      // a large world: cull(w) in front of step(w), same stream, same runs
-  if (prof_slot >= 0) HIPCHK(c, hipEventRecord(c->events[2 * prof_slot], stream));
-  HIPCHK(c, pocs_launch_gmm_step(c->K, a, stream));
-  if (prof_slot >= 0) HIPCHK(c, hipEventRecord(c->events[2 * prof_slot + 1], stream));
+  if (a.world) if (int r = is.launch(pocs_launch_world_cull, s.slot, c->K, a)) return r;      // a large world: cull(w) in front of step(w), same stream, same runs
+  if (s.prof_slot >= 0) if (int r = is.mark(c->events[2 * s.prof_slot], s.slot)) return r;
+  if (int r = is.launch(pocs_launch_gmm_step, s.slot, c->K, a)) return r;
+  if (s.prof_slot >= 0) if (int r = is.mark(c->events[2 * s.prof_slot + 1], s.slot)) return r;
   return POCS_OK;
 }
 
 int enqueue_ticket_reset(pocs_ctx* c) {
-  HIPCHK(c, hipMemsetAsync(c->d_ticket.p, 0, sync_words(c) * sizeof(unsigned), c->stream));
+  HIPCHK(c, hipMemsetAsync(c->d_ticket.p, 0, c->sync.words * sizeof(unsigned), c->stream));
   if (large_world(c))                                // (a waypoint that no cull launch covers -- a plan's end, a stop -- reports no reach)
     HIPCHK(c, hipMemsetAsync(c->d_reach.p, 0, (size_t)c->batch * (size_t)c->W * sizeof(int), c->stream));
   return POCS_OK;
@@ -393,69 +482,69 @@ size_t gmm_hot_launches(const pocs_ctx* c) { return (size_t)c->W; }
 // tail, whose closers leave the nodes' moments (k_gmm_step_tree) -- a level wider than 256 nodes as several launches of at most
 // 256.  The launches of a level read what the launches of the level above wrote: one stream, one after the other.  A launch's
 // rows of partial sums start at the head of the row buffer whatever its first slot is (the kernels address them by slot).
-int enqueue_gmm_tree(pocs_ctx* c, long long count) {
-  const bool risk = risk_active(c);
+int enqueue_gmm_tree(Issuer is, long long count) {
+  pocs_ctx* c = is.c;
   const int D = (int)c->tree.level.size() - 2;
-  if (int r = enqueue_obs_counts_reset(c)) return r;
-  auto tree_launch = [&](pocs_gmm_launch* a, int d, int lo, int cnt) {
-    fill_gmm_launch(c, a, 0, count, d, lo, cnt, 1);
-    a->store = 0;
-    a->tree_parent = (const int*)c->d_tparent.p;
-    a->partial = (double*)((uintptr_t)c->d_partial.p - (uintptr_t)(((size_t)lo << a->vs_shift) * (size_t)c->K * POCS_NMOM * sizeof(double)));
-    a->partial_prev = a->partial;
-    if (risk) set_risk(c, a);
+  if (int r = enqueue_obs_counts_reset(is)) return r;
+  pocs_gmm_launch base, a;
+  fill_gmm_launch(c, &base, 0, count);
+  base.store = 0; base.tree_parent = (const int*)c->d_tparent.p;
+  if (risk_active(c)) set_risk(c, &base);
+  auto tree_launch = [&](int d, int lo, int cnt) {
+    memcpy(&a, &base, sizeof a);
+    aim_gmm_launch(c, &a, d, lo, cnt);
+    a.partial = (double*)((uintptr_t)c->d_partial.p - (uintptr_t)(((size_t)lo << a.vs_shift) * (size_t)c->K * POCS_NMOM * sizeof(double)));
+    a.partial_prev = a.partial;
   };
   for (int d = 0; d <= D; ++d) {
     const int lo = c->tree.level[(size_t)d], hi = c->tree.level[(size_t)d + 1];
-    pocs_gmm_launch a;
-    tree_launch(&a, d, lo, hi - lo);
-    HIPCHK(c, pocs_launch_gmm_tree_advance(c->K, a, c->stream));
+    tree_launch(d, lo, hi - lo);
+    if (int r = is.launch(pocs_launch_gmm_tree_advance, 0, c->K, a)) return r;
     for (int s = lo; s < hi; s += 256) {
-      tree_launch(&a, d, s, hi - s < 256 ? hi - s : 256);
-      HIPCHK(c, pocs_launch_gmm_tree_step(c->K, a, c->stream));
+      tree_launch(d, s, hi - s < 256 ? hi - s : 256);
+      if (int r = is.launch(pocs_launch_gmm_tree_step, 0, c->K, a)) return r;
     }
   }
   return POCS_OK;
 }
 
-int enqueue_gmm_all(pocs_ctx* c, long long first, long long count, bool prof) {
-  if (c->tree.n) return enqueue_gmm_tree(c, count);
+int enqueue_gmm_all(Issuer is, long long first, long long count, bool prof) {
+  pocs_ctx* c = is.c;
+  if (c->tree.n) return enqueue_gmm_tree(is, count);
   const int W = c->W, R = c->batch, G = gmm_groups(c);
-  if (int r = enqueue_obs_counts_reset(c)) return r;     // (ahead of the fork: every sub-batch's launches lie behind it)
-  if (int r = enqueue_advance(c, 0)) return r;
-  if (prof) HIPCHK(c, hipEventRecord(c->ev_seq[0], c->stream));
-  if (G > 1) HIPCHK(c, hipEventRecord(c->ev_fork, c->stream));
-  for (int g = 1; g < G; ++g) HIPCHK(c, hipStreamWaitEvent(c->side_stream[g - 1], c->ev_fork, 0));
-  const bool lone = lone_call(c), exchange = whole_call_exchanges(c), risk = risk_active(c);
+  if (int r = enqueue_obs_counts_reset(is)) return r;    // (ahead of the fork: every sub-batch's launches lie behind it)
+  if (int r = enqueue_advance(is, 0)) return r;
+  if (prof) if (int r = is.mark(c->ev_seq[0])) return r;
+  for (int g = 1; g < G; ++g) if (int r = is.order(0, g, c->ev_fork, g == 1)) return r;
+  pocs_gmm_launch base;
+  fill_gmm_launch(c, &base, first, count);
+  StepLaunch s;
+  s.groups = G; s.advance = true; s.lone = lone_call(c); s.risk = risk_active(c);
+  if (whole_call_exchanges(c)) s.exchange = StepLaunch::FROM_HEADERS;
   // a call of plans: the launch of waypoint w covers the runs whose plan is longer than w -- a prefix of every
   // sub-batch's slots (plan_layout) -- and the closers of those whose plan ends at w do not advance
   const std::vector<int> Ws = slot_lengths(c, plan_layout(c, G));
   for (int w = 0; w < W; ++w)
     for (int g = 0; g < G; ++g) {                    // sub-batch g = runs [g R / G, (g + 1) R / G); events bracket sub-batch 0's launches
       const int lo = (int)((long long)g * R / G), hi = (int)((long long)(g + 1) * R / G);
-      hipStream_t st = g == 0 ? c->stream : c->side_stream[g - 1];
-      int cnt = hi - lo, adv = -1;
+      s.slot = g; s.run_lo = lo; s.run_cnt = hi - lo; s.adv_cnt = -1; s.prof_slot = (prof && g == 0) ? w : -1;
       if (c->plans.n) {
-        cnt = live_runs(Ws, lo, hi, w);
-        adv = live_runs(Ws, lo, hi, w + 1);
-        if (cnt == 0) {                              // this sub-batch's plans have all ended
-          if (prof && g == 0) { HIPCHK(c, hipEventRecord(c->events[2 * w], st)); HIPCHK(c, hipEventRecord(c->events[2 * w + 1], st)); }
+        s.run_cnt = live_runs(Ws, lo, hi, w);
+        s.adv_cnt = live_runs(Ws, lo, hi, w + 1);
+        if (s.run_cnt == 0) {                        // this sub-batch's plans have all ended
+          if (s.prof_slot >= 0) { if (int r = is.mark(c->events[2 * w])) return r; if (int r = is.mark(c->events[2 * w + 1])) return r; }
           continue;
         }
       }
-      if (int r = enqueue_step(c, first, count, w, true, exchange, (prof && g == 0) ? w : -1, st, lo, cnt, G, lone, adv, risk)) return r;
+      if (int r = enqueue_step(is, base, w, s)) return r;
     }
-  if (lone) {                                        // the last waypoint's rows -> moments[W-1]
-    pocs_gmm_launch a;
-    fill_gmm_launch(c, &a, first, count, W - 1, 0, 1, 1);
-    set_lone(c, &a, W - 1);
-    HIPCHK(c, pocs_launch_gmm_close(c->K, a, c->stream));
+  if (s.lone) {                                      // the last waypoint's rows -> moments[W-1]
+    aim_gmm_launch(c, &base, W - 1, 0, 1, 1);
+    set_lone(c, &base, W - 1);
+    if (int r = is.launch(pocs_launch_gmm_close, 0, c->K, base)) return r;
   }
-  for (int g = 1; g < G; ++g) {
-    HIPCHK(c, hipEventRecord(c->ev_join[g - 1], c->side_stream[g - 1]));
-    HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_join[g - 1], 0));
-  }
-  if (prof) HIPCHK(c, hipEventRecord(c->ev_seq[1], c->stream));
+  for (int g = 1; g < G; ++g) if (int r = is.order(g, 0, c->ev_join[g - 1])) return r;
+  if (prof) if (int r = is.mark(c->ev_seq[1])) return r;
   return POCS_OK;
 }
 int enqueue_gmm_results(pocs_ctx* c) {
@@ -463,16 +552,21 @@ int enqueue_gmm_results(pocs_ctx* c) {
   const PinLayout pl = pin_layout(c);
   HIPCHK(c, hipMemcpyAsync((double*)c->h_pin + pl.moments, moments_dev(c),
                            (size_t)W * c->batch * c->K * POCS_NMOM * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-  // the call's give-up word travels back with the results -- and, under a risk bound, the runs' stop words [R] behind it
-  // (words 4 .. 4 + R of the block: the same copy, 3 + R words instead of one)
-  static_assert(POCS_SYNC_ABORT == 1, "the stop words follow the give-up word and two pad words");
-  HIPCHK(c, hipMemcpyAsync((double*)c->h_pin + pl.total + c->batch + 1, (unsigned*)c->d_ticket.p + POCS_SYNC_ABORT,
-                           (risk_active(c) ? 3 + (size_t)c->batch : 1) * sizeof(unsigned), hipMemcpyDeviceToHost, c->stream));
+  // the call's give-up word travels back with the results -- and, under a risk bound, the runs' stop words behind it (SyncLayout)
+  HIPCHK(c, hipMemcpyAsync((double*)c->h_pin + c->sync.pin, (unsigned*)c->d_ticket.p + POCS_SYNC_ABORT,
+                           c->sync.copy_words * sizeof(unsigned), hipMemcpyDeviceToHost, c->stream));
   if (large_world(c)) {                              // the kept counts [R][W]: into the context's own table, slot order (gmm_read_reach sorts them)
     c->reach.assign((size_t)c->batch * (size_t)c->W, 0);
     HIPCHK(c, hipMemcpyAsync(c->reach.data(), c->d_reach.p, c->reach.size() * sizeof(int), hipMemcpyDeviceToHost, c->stream));
   }
   return POCS_OK;
+}
+
+// A bounded wait that expired on the device fails the call that has just synchronised (`what`: the caller's message, with %u).
+int gmm_check_gave_up(pocs_ctx* c, const char* what) {
+  unsigned gave_up = 0;
+  memcpy(&gave_up, (double*)c->h_pin + c->sync.pin, sizeof gave_up);
+  return gave_up ? fail(c, POCS_E_DEVICE, what, gave_up) : POCS_OK;
 }
 
 // The kept counts of a GMM call under a large world, as enqueue_gmm_results brought them back in slot order -> run / plan order
@@ -626,51 +720,6 @@ int gmm_combine(pocs_ctx* c, const double* moments, double* probability, const u
   return POCS_OK;
 }
 
-std::string config_key(const pocs_ctx* c, long long first, long long count, const char* tag) {
-  char buf[256];
-  snprintf(buf, sizeof buf, "%s e%llu W%d K%d R%d g%d l%d x%d n%lld f%lld c%lld s%lld fu%lld oc%lld st%p em%p", tag, c->epoch,
-           c->W, c->K, c->batch, gmm_groups(c), lone_call(c) ? 1 : 0, (c->xchg_connected && c->shard_first >= 0 && !c->ext_moments) ? c->xchg_world : 0,
-           c->num_gmm, first, count, c->opt_store, c->opt_fused, c->opt_obs_counts, (void*)c->stream, (void*)c->ext_moments);
-  std::string key = buf;
-  if (large_world(c)) key += " lw" + std::to_string(large_boxes(c));      // the launches and their kernels are another set
-  if (c->tree.n) {                                   // a tree: the launches follow its shape (the levels' widths, the parents on the device)
-    unsigned long long h = 1469598103934665603ull;   // FNV-1a over the slots' parents
-    for (int v : c->tree.pslot) { h ^= (unsigned)v; h *= 1099511628211ull; }
-    char tb[96];
-    snprintf(tb, sizeof tb, " T%d D%zu h%llx rb%a", c->tree.n, c->tree.level.size() - 2, h, c->risk_bound);
-    key += tb;
-  }
-  if (c->plans.n) {                                   // a call of plans: one launch per waypoint and LIVE sub-batch, by the plans' lengths
-    key += " P";
-    for (int p = 0; p < c->plans.n; ++p) key += (p ? "," : "") + std::to_string(c->plans.W[(size_t)p]);
-    if (risk_active(c)) {                            // the bound is baked into the launches (and selects their kernel)
-      char rb[48];
-      snprintf(rb, sizeof rb, " rb%a", c->risk_bound);
-      key += rb;
-    }
-  }
-  return key;
-}
-
-// The graph cache: a call's launches are captured once and replayed until `key` -- everything their shape and arguments depend
-// on (config_key) -- changes.  Leaves in `exec` the graph of `enqueue`'s launches; the caller launches it.
-template <class Enqueue>
-int ensure_graph(pocs_ctx* c, hipGraphExec_t& exec, std::string& have, const std::string& key, Enqueue enqueue) {
-  if (exec && key == have) return POCS_OK;
-  if (exec) { hipGraphExecDestroy(exec); exec = nullptr; }
-  hipGraph_t g = nullptr;
-  HIPCHK(c, hipStreamBeginCapture(c->stream, hipStreamCaptureModeThreadLocal));
-  const int r = enqueue();
-  hipError_t e = hipStreamEndCapture(c->stream, &g);
-  if (r) { if (g) hipGraphDestroy(g); return r; }
-  HIPCHK(c, e);
-  e = hipGraphInstantiate(&exec, g, nullptr, nullptr, 0);
-  hipGraphDestroy(g);
-  HIPCHK(c, e);
-  have = key;
-  return POCS_OK;
-}
-
 int run_gmm_full(pocs_ctx* c, double* probability) {
   if (!probability) return fail(c, POCS_E_ARG, "null output");
 #if defined(POCS_TUNING) && defined(POCS_CALL_TIMES)                          // tuning build: host-side phases of a call on stderr
@@ -699,31 +748,9 @@ int run_gmm_full(pocs_ctx* c, double* probability) {
   // (a call on a tree is not bracketed launch by launch: POCS_OPT_PROFILE = 1 runs it eagerly, untimed)
   const bool prof = c->opt_profile == 1 && !c->tree.n, span = c->opt_profile == 2 && c->opt_graph;
   if (int r = prof_begin(c, gmm_hot_launches(c))) return r;
-#if defined(POCS_TUNING) && defined(POCS_GRAPH_WITH_COPIES)      // diagnostic build: round 2's graph shape (the memset and the two result copies as graph nodes)
-  const bool copies_in_graph = c->opt_graph && !prof;
-#else
-  const bool copies_in_graph = false;
-#endif
-  if (!copies_in_graph) if (int r = enqueue_ticket_reset(c)) return r;
-  if (c->opt_graph && c->opt_profile != 1) {
-    if (int r = ensure_graph(c, c->graph_gmm, c->graph_gmm_key, config_key(c, first, count, "gmm"), [&] {
-          int r = copies_in_graph ? enqueue_ticket_reset(c) : POCS_OK;
-          if (!r) r = enqueue_gmm_all(c, first, count, false);
-          if (!r && copies_in_graph) r = enqueue_gmm_results(c);
-          if (copies_in_graph) {                       // the pointers the memset / memcpy nodes bake in: a stale one would show here
-            c->graph_baked[0] = c->d_ticket.p; c->graph_baked[1] = c->h_pin; c->graph_baked[2] = moments_dev(c);
-          }
-          return r;
-        })) return r;
-    if (copies_in_graph && (c->graph_baked[0] != c->d_ticket.p || c->graph_baked[1] != c->h_pin || c->graph_baked[2] != moments_dev(c)))
-      return fail(c, POCS_E_STATE, "a pointer baked into the graph's memset / memcpy nodes changed between capture and replay");
-    if (span) HIPCHK(c, hipEventRecord(c->ev_seq[0], c->stream));
-    HIPCHK(c, hipGraphLaunch(c->graph_gmm, c->stream));
-    if (span) HIPCHK(c, hipEventRecord(c->ev_seq[1], c->stream));
-  } else {
-    if (int r = enqueue_gmm_all(c, first, count, prof)) return r;
-  }
-  if (!copies_in_graph) if (int r = enqueue_gmm_results(c)) return r;
+  if (int r = enqueue_ticket_reset(c)) return r;
+  if (int r = run_launches(c, c->graph_gmm, span, [&](Issuer is) { return enqueue_gmm_all(is, first, count, prof); })) return r;
+  if (int r = enqueue_gmm_results(c)) return r;
   lap("launched");
   prefetch_next_batch(c, gmm_groups(c));          // host chains of the next batch, while the GPU works on this one
   lap("next batch prepared");
@@ -736,16 +763,10 @@ int run_gmm_full(pocs_ctx* c, double* probability) {
     c->seq_ms = ms; c->seq_groups = gmm_groups(c);
     if (span) { c->prof_ms = ms; c->prof_launches = (long long)gmm_hot_launches(c); }      // pocs_get_kernel_time: span / W
   }
-  {
-    const PinLayout pl = pin_layout(c);
-    unsigned gave_up = 0;
-    memcpy(&gave_up, (double*)c->h_pin + pl.total + c->batch + 1, sizeof gave_up);
-    if (gave_up) return fail(c, POCS_E_DEVICE, "a bounded wait expired on the device (code %u); results discarded", gave_up);
-    // (the stop words: behind the give-up word and its two pad words)
-    const unsigned* stop = risk_active(c) ? (const unsigned*)((double*)c->h_pin + pl.total + c->batch + 1) + 3 : nullptr;
-    if (large_world(c)) if (int r = gmm_read_reach(c)) { reset_results(c); return r; }
-    if (int r = gmm_combine(c, (double*)c->h_pin + pl.moments, probability, stop)) { reset_results(c); return r; }
-  }
+  if (int r = gmm_check_gave_up(c, "a bounded wait expired on the device (code %u); results discarded")) return r;
+  const unsigned* stop = risk_active(c) ? (const unsigned*)((double*)c->h_pin + c->sync.pin) + (c->sync.stop - POCS_SYNC_ABORT) : nullptr;
+  if (large_world(c)) if (int r = gmm_read_reach(c)) { reset_results(c); return r; }
+  if (int r = gmm_combine(c, (double*)c->h_pin + pin_layout(c).moments, probability, stop)) { reset_results(c); return r; }
   note_obs_counts(c, 1);
   c->res.last_gmm_count = count;
   c->res.last_gmm_wp = c->W - 1;
@@ -799,7 +820,8 @@ int mc_launch_base(pocs_ctx* c, long long count, double live_particles, pocs_mc_
   return POCS_OK;
 }
 
-int enqueue_mc_all(pocs_ctx* c, long long first, long long count, bool prof) {
+int enqueue_mc_all(Issuer is, long long first, long long count, bool prof) {
+  pocs_ctx* c = is.c;
   const int W = c->W, R = c->batch, nblk = grid_for_mc(count, R);
   pocs_mc_launch a;
   if (int r = mc_launch_base(c, count, (double)R * (double)sample_stride_of(count), &a)) return r;
@@ -815,7 +837,7 @@ int enqueue_mc_all(pocs_ctx* c, long long first, long long count, bool prof) {
   }
   if (c->opt_obs_counts) {
     a.obs_counts = (unsigned long long*)c->d_obsct.p;
-    if (int r = enqueue_obs_counts_reset(c)) return r;
+    if (int r = enqueue_obs_counts_reset(is)) return r;
   }
   if (c->plans.n) {
     a.run_plan = (const double*)c->d_runplan.p;      // every run its own start mean and steps
@@ -828,28 +850,28 @@ int enqueue_mc_all(pocs_ctx* c, long long first, long long count, bool prof) {
   if (mc_fused_form(c)) {
     a.step = W - 1;
     a.env_steps = c->world_S;                        // (> 1: k_mc_fused_sched, which restages the world per step)
-    if (prof) HIPCHK(c, hipEventRecord(c->events[0], c->stream));
-    HIPCHK(c, pocs_launch_mc_fused(nblk, a, c->stream));
-    if (prof) HIPCHK(c, hipEventRecord(c->events[1], c->stream));
+    if (prof) if (int r = is.mark(c->events[0])) return r;
+    if (int r = is.launch(pocs_launch_mc_fused, 0, nblk, a)) return r;
+    if (prof) if (int r = is.mark(c->events[1])) return r;
   } else {
     a.step = 0;
-    HIPCHK(c, pocs_launch_mc_init(nblk, a, c->stream));
+    if (int r = is.launch(pocs_launch_mc_init, 0, nblk, a)) return r;
     for (int s = 0; s < W - 1; ++s) {
       a.step = s;
-      pocs_mc_launch as = a;
+      pocs_mc_launch as;
+      memcpy(&as, &a, sizeof as);
       as.env = world_at(c, s + 1);                   // control s produces waypoint s + 1
       int nb = nblk;
       if (c->plans.n) {
         as.nruns = live_runs(Ws, 0, R, s + 1);       // plans with a control at step s: W_p - 1 > s
         nb = grid_for_mc(count, as.nruns);
       }
-      if (prof) HIPCHK(c, hipEventRecord(c->events[2 * s], c->stream));
-      if (as.nruns > 0) HIPCHK(c, pocs_launch_mc_step(nb, as, c->stream));
-      if (prof) HIPCHK(c, hipEventRecord(c->events[2 * s + 1], c->stream));
+      if (prof) if (int r = is.mark(c->events[2 * s])) return r;
+      if (as.nruns > 0) if (int r = is.launch(pocs_launch_mc_step, 0, nb, as)) return r;
+      if (prof) if (int r = is.mark(c->events[2 * s + 1])) return r;
     }
   }
-  HIPCHK(c, pocs_launch_mc_count(nblk, a, c->stream));
-  return POCS_OK;
+  return is.launch(pocs_launch_mc_count, 0, nblk, a);
 }
 
 // The first collisions per waypoint as the call's copy brought them back (`words`: mc_total_words, slot order) -> c->res.mc_wp in
@@ -903,7 +925,8 @@ size_t tree_max_width(const pocs_ctx* c) {
   return w;
 }
 #define POCS_TREE_MC_MAX_BYTES (64ull << 30)      // both halves of the particle state of an MC call on a tree
-int enqueue_mc_tree(pocs_ctx* c, long long count) {
+int enqueue_mc_tree(Issuer is, long long count) {
+  pocs_ctx* c = is.c;
   const int T = c->tree.n, D = (int)c->tree.level.size() - 2;
   const size_t half = c->res.tree_mc_half;
   pocs_mc_launch a;
@@ -914,7 +937,7 @@ int enqueue_mc_tree(pocs_ctx* c, long long count) {
   a.mu0[0] = c->tree.pose[0]; a.mu0[1] = c->tree.pose[(size_t)T]; a.mu0[2] = c->tree.pose[2 * (size_t)T];
   if (c->opt_obs_counts) {
     a.obs_counts = (unsigned long long*)c->d_obsct.p;      // [T][64], by slot
-    if (int r = enqueue_obs_counts_reset(c)) return r;
+    if (int r = enqueue_obs_counts_reset(is)) return r;
   }
   auto half_of = [&](pocs_mc_launch* l, int d) {
     const size_t o = (size_t)(d & 1) * half;
@@ -922,30 +945,48 @@ int enqueue_mc_tree(pocs_ctx* c, long long count) {
   };
   half_of(&a, 0);
   a.nruns = 1;
-  HIPCHK(c, pocs_launch_mc_init(grid_for_mc(count, 1), a, c->stream));
+  if (int r = is.launch(pocs_launch_mc_init, 0, grid_for_mc(count, 1), a)) return r;
   a.tree_parent = (const int*)c->d_tparent.p;
   for (int d = 1; d <= D; ++d) {
     const int lo = c->tree.level[(size_t)d], hi = c->tree.level[(size_t)d + 1];
-    pocs_mc_launch prev = a;
-    half_of(&prev, d - 1);
+    a.tree_sx = a.x; a.tree_sy = a.y; a.tree_sth = a.th; a.tree_shits = a.hits;      // (the previous level's half)
     half_of(&a, d);
     a.env = world_at(c, d);
-    a.tree_sx = prev.x; a.tree_sy = prev.y; a.tree_sth = prev.th; a.tree_shits = prev.hits;
     a.tree_dst_lo = lo; a.tree_src_lo = c->tree.level[(size_t)d - 1];
     for (int s = lo; s < hi; s += 256) {
       a.tree_lo = s;
       a.nruns = hi - s < 256 ? hi - s : 256;
-      HIPCHK(c, pocs_launch_mc_tree_step(grid_for_mc(count, a.nruns), a, c->stream));
+      if (int r = is.launch(pocs_launch_mc_tree_step, 0, grid_for_mc(count, a.nruns), a)) return r;
     }
   }
   return POCS_OK;
 }
 
-int run_mc_tree(pocs_ctx* c) {
-  c->res.oc_kind = 0;
-  if (int r = check_common(c)) return r;
-  if (c->num_particles < 1) return fail(c, POCS_E_STATE, "setNumParticles missing");
-  if (int r = upload_static(c)) return r;
+// What both MC paths share behind run_mc_local's checks: the common buffers and the runs' upload (mc_prepare), and the call's
+// tail (mc_run): counters zeroed, launches run, counters copied to the pin's `total` words (-> *tot), stream synchronised.  (The
+// reset and the copy are plain stream operations: the captured graph holds kernel nodes only, like the GMM path's.)
+int mc_prepare(pocs_ctx* c, size_t runs, size_t chain_rows, size_t elems, size_t total_bytes) {
+  if (int r = ensure(c, c->d_hdr, runs * sizeof(pocs_run_header))) return r;
+  if (int r = ensure(c, c->d_chain, chain_rows * POCS_CHAIN_STRIDE * sizeof(double))) return r;
+  for (DevBuf* b : {&c->d_px, &c->d_py, &c->d_pt}) if (int r = ensure(c, *b, elems * sizeof(double))) return r;
+  if (int r = ensure(c, c->d_hits, elems * sizeof(uint32_t))) return r;
+  if (int r = ensure(c, c->d_total, total_bytes + 16)) return r;
+  if (int r = ensure_obs_counts(c)) return r;
+  if (int r = ensure_pin(c)) return r;
+  return stage_and_upload_runs(c, 1, 1);
+}
+template <class Enqueue>
+int mc_run(pocs_ctx* c, size_t total_bytes, bool span, const unsigned long long** tot, Enqueue enqueue) {
+  HIPCHK(c, hipMemsetAsync(c->d_total.p, 0, total_bytes, c->stream));
+  if (int r = run_launches(c, c->graph_mc, span, enqueue)) return r;
+  *tot = (const unsigned long long*)((double*)c->h_pin + pin_layout(c).total);
+  HIPCHK(c, hipMemcpyAsync((void*)*tot, c->d_total.p, total_bytes, hipMemcpyDeviceToHost, c->stream));
+  prefetch_next_batch(c, 1);       // host chains of the next batch, while the GPU works on this one
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  return POCS_OK;
+}
+
+int run_mc_tree(pocs_ctx* c) {                      // (behind run_mc_local's checks)
   if (int r = upload_tree(c)) return r;
   const long long count = c->num_particles;
   const size_t T = (size_t)c->tree.n, stride = (size_t)sample_stride_of(count), half = tree_max_width(c) * stride;
@@ -953,30 +994,11 @@ int run_mc_tree(pocs_ctx* c) {
     return fail(c, POCS_E_ARG, "MC on a tree: its widest level has %zu nodes; two levels of %lld particles each need %.1f GB of particle state, more than the %llu GB an MC call on a tree may hold",
                 tree_max_width(c), count, (double)half * 2.0 * 28.0 / 1e9, (unsigned long long)(POCS_TREE_MC_MAX_BYTES >> 30));
   c->res.tree_mc_half = half;
-  if (int r = ensure(c, c->d_hdr, T * sizeof(pocs_run_header))) return r;
-  if (int r = ensure(c, c->d_chain, T * POCS_CHAIN_STRIDE * sizeof(double))) return r;
-  if (int r = ensure(c, c->d_px, 2 * half * sizeof(double))) return r;
-  if (int r = ensure(c, c->d_py, 2 * half * sizeof(double))) return r;
-  if (int r = ensure(c, c->d_pt, 2 * half * sizeof(double))) return r;
-  if (int r = ensure(c, c->d_hits, 2 * half * sizeof(uint32_t))) return r;
   const size_t total_bytes = 2 * T * sizeof(unsigned long long);       // [T] collided at or before the node | [T] first collisions at it
-  if (int r = ensure(c, c->d_total, total_bytes + 16)) return r;
-  if (int r = ensure_obs_counts(c)) return r;
-  if (int r = ensure_pin(c)) return r;
-  if (int r = stage_and_upload_runs(c, 1, 1)) return r;
-  HIPCHK(c, hipMemsetAsync(c->d_total.p, 0, total_bytes, c->stream));
-  if (c->opt_graph && c->opt_profile != 1) {
-    const std::string key = config_key(c, 0, count, "mc-tree") + std::to_string(c->num_particles) + "h" + std::to_string(half);
-    if (int r = ensure_graph(c, c->graph_mc, c->graph_mc_key, key, [&] { return enqueue_mc_tree(c, count); })) return r;
-    HIPCHK(c, hipGraphLaunch(c->graph_mc, c->stream));
-  } else {
-    if (int r = enqueue_mc_tree(c, count)) return r;
-  }
-  const PinLayout pl = pin_layout(c);
-  HIPCHK(c, hipMemcpyAsync((double*)c->h_pin + pl.total, c->d_total.p, total_bytes, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
+  if (int r = mc_prepare(c, T, T, 2 * half, total_bytes)) return r;
+  const unsigned long long* tot;
+  if (int r = mc_run(c, total_bytes, false, &tot, [&](Issuer is) { return enqueue_mc_tree(is, count); })) return r;
   c->prof_ms = 0.0; c->prof_launches = 0;
-  const unsigned long long* tot = (const unsigned long long*)((double*)c->h_pin + pl.total);
   const unsigned long long* F = tot + T;
   c->res.tree_F.assign(T, 0ull); c->res.tree_C.assign(T, 0ull);
   c->res.tree_probs.assign(T, 0.0); c->res.tree_eval.assign(T, 1);
@@ -1006,48 +1028,23 @@ int run_mc_tree(pocs_ctx* c) {
 
 // One batch of MC roll-outs (runSimulation x batch) over this context's shard; fills c->res.mc_counts.
 int run_mc_local(pocs_ctx* c) {
-  if (c->tree.n) return run_mc_tree(c);
   c->res.oc_kind = 0;
   if (int r = check_common(c)) return r;
   if (c->num_particles < 1) return fail(c, POCS_E_STATE, "setNumParticles missing");
+  if (int r = upload_static(c)) return r;
+  if (c->tree.n) return run_mc_tree(c);
   long long first, count;
   if (int r = mc_shard(c, &first, &count)) return r;
-  if (int r = upload_static(c)) return r;
-  const size_t W = (size_t)c->W, R = (size_t)c->batch, n = R * (size_t)sample_stride_of(count);
-  if (int r = ensure(c, c->d_hdr, R * sizeof(pocs_run_header))) return r;
-  if (int r = ensure(c, c->d_chain, R * (W > 1 ? W - 1 : 1) * POCS_CHAIN_STRIDE * sizeof(double))) return r;
-  if (int r = ensure(c, c->d_px, n * sizeof(double))) return r;
-  if (int r = ensure(c, c->d_py, n * sizeof(double))) return r;
-  if (int r = ensure(c, c->d_pt, n * sizeof(double))) return r;
-  if (int r = ensure(c, c->d_hits, n * sizeof(uint32_t))) return r;
+  const size_t W = (size_t)c->W, R = (size_t)c->batch;
   const size_t total_bytes = mc_total_words(c) * sizeof(unsigned long long);
-  if (int r = ensure(c, c->d_total, total_bytes + 16)) return r;
   if (c->plans.n)
     if (int r = ensure(c, c->d_runplan, R * 4 * sizeof(double))) return r;
-  if (int r = ensure_obs_counts(c)) return r;
-  if (int r = ensure_pin(c)) return r;
-  if (int r = stage_and_upload_runs(c, 1, 1)) return r;
+  if (int r = mc_prepare(c, R, R * (W > 1 ? W - 1 : 1), R * (size_t)sample_stride_of(count), total_bytes)) return r;
   const bool prof = c->opt_profile == 1, span = c->opt_profile == 2 && c->opt_graph;      // (as run_gmm_full)
   const size_t nprof = mc_fused_form(c) ? 1 : (W > 1 ? W - 1 : 0);
   if (int r = prof_begin(c, nprof > 0 ? nprof : 1)) return r;
-  // (the counter reset ahead of the launches and the result copy behind them are plain stream operations: the
-  // captured graph holds kernel nodes only, like the GMM path's)
-  HIPCHK(c, hipMemsetAsync(c->d_total.p, 0, total_bytes, c->stream));
-  if (c->opt_graph && !prof) {
-    // (the two options select the kernels; the bound an MC stop obeys is in the key already: config_key, "rb")
-    const std::string key = config_key(c, first, count, "mc") + " " + std::to_string(c->num_particles) +
-                            (mc_stop_active(c) ? " wp2" : mc_counts_active(c) ? " wp1" : "");
-    if (int r = ensure_graph(c, c->graph_mc, c->graph_mc_key, key, [&] { return enqueue_mc_all(c, first, count, false); })) return r;
-    if (span) HIPCHK(c, hipEventRecord(c->ev_seq[0], c->stream));
-    HIPCHK(c, hipGraphLaunch(c->graph_mc, c->stream));
-    if (span) HIPCHK(c, hipEventRecord(c->ev_seq[1], c->stream));
-  } else {
-    if (int r = enqueue_mc_all(c, first, count, prof)) return r;
-  }
-  const PinLayout pl = pin_layout(c);
-  HIPCHK(c, hipMemcpyAsync((double*)c->h_pin + pl.total, c->d_total.p, total_bytes, hipMemcpyDeviceToHost, c->stream));
-  prefetch_next_batch(c, 1);       // host chains of the next batch, while the GPU works on this one
-  HIPCHK(c, hipStreamSynchronize(c->stream));
+  const unsigned long long* tot;
+  if (int r = mc_run(c, total_bytes, span, &tot, [&](Issuer is) { return enqueue_mc_all(is, first, count, prof); })) return r;
   if (int r = prof_collect(c, nprof)) return r;
   if (span) {                                          // the graph's span over its W - 1 hot launches (+ the init and count launches: an upper bound)
     float ms = 0.f;
@@ -1055,7 +1052,7 @@ int run_mc_local(pocs_ctx* c) {
     c->prof_ms = ms; c->prof_launches = (long long)(nprof > 0 ? nprof : 1);
   }
   c->res.mc_counts.resize(R);
-  memcpy(c->res.mc_counts.data(), (double*)c->h_pin + pl.total, R * sizeof(unsigned long long));
+  memcpy(c->res.mc_counts.data(), tot, R * sizeof(unsigned long long));
   if (c->plans.n) {                                     // slot order -> the caller's plan order
     const std::vector<unsigned long long> by_slot = c->res.mc_counts;
     for (size_t p = 0; p < R; ++p) c->res.mc_counts[p] = by_slot[(size_t)c->res.plan_slot[1][p]];
@@ -1064,7 +1061,7 @@ int run_mc_local(pocs_ctx* c) {
   c->res.last_kind = 2;
   c->res.mc_wp.clear(); c->res.plan_E_mc.clear();
   if (mc_counts_active(c))
-    if (int r = mc_read_waypoint_counts(c, (const unsigned long long*)((double*)c->h_pin + pl.total))) { reset_results(c); return r; }
+    if (int r = mc_read_waypoint_counts(c, tot)) { reset_results(c); return r; }
   note_obs_counts(c, 2);
   return POCS_OK;
 }
@@ -1074,6 +1071,22 @@ int run_mc_local(pocs_ctx* c) {
 using namespace pocs_rt;
 
 extern "C" {
+
+// The step API's sampling launch of waypoint w, eager -- `exchange`: with the moments' exchange and the advance in its tail.
+static int step_api_sample(pocs_ctx* c, int w, bool exchange) {
+  long long first, count;
+  if (int r = gmm_shard(c, &first, &count)) return r;
+  pocs_gmm_launch base;
+  fill_gmm_launch(c, &base, first, count);
+  StepLaunch s;
+  s.prof_slot = c->opt_profile == 1 ? w : -1;
+  if (exchange) { s.advance = true; s.exchange = StepLaunch::FROM_CONTEXT; }
+  if (int r = enqueue_step({c, nullptr}, base, w, s)) return r;
+  c->res.last_gmm_wp = w;
+  c->res.last_gmm_count = count;
+  if (exchange && w + 1 < c->W) c->last_gmm_adv = w + 1;
+  return POCS_OK;
+}
 
 int pocs_gmm_begin(pocs_ctx* c) {
   if (!c) return POCS_E_ARG;
@@ -1087,7 +1100,7 @@ int pocs_gmm_begin(pocs_ctx* c) {
   if (int r = gmm_upload_run(c)) return r;
   if (int r = prof_begin(c, (size_t)c->W)) return r;
   if (int r = enqueue_ticket_reset(c)) return r;
-  if (int r = enqueue_obs_counts_reset(c)) return r;
+  if (int r = enqueue_obs_counts_reset({c, nullptr})) return r;
   c->res.oc_kind = 0;                                 // (the table is this sequence's from here on; served once pocs_gmm_end has closed it)
   c->xchg_calls += 1;
   c->gmm_open = true;
@@ -1101,7 +1114,7 @@ int pocs_gmm_advance_local(pocs_ctx* c, int w) {
   if (!c->gmm_open) return fail(c, POCS_E_ORDER, "pocs_gmm_advance_local before pocs_gmm_begin");
   if (w != c->res.last_gmm_wp + 1 || w != c->last_gmm_adv + 1 || w >= c->W)
     return fail(c, POCS_E_ORDER, "advance of waypoint %d out of sequence", w);
-  if (int r = enqueue_advance(c, w)) return r;        // folds the (reduced) moments of w-1
+  if (int r = enqueue_advance({c, nullptr}, w)) return r;    // folds the (reduced) moments of w-1
   c->last_gmm_adv = w;
   return POCS_OK;
 }
@@ -1111,12 +1124,7 @@ int pocs_gmm_sample_local(pocs_ctx* c, int w) {
   if (!c->gmm_open) return fail(c, POCS_E_ORDER, "pocs_gmm_sample_local before pocs_gmm_begin");
   if (w != c->res.last_gmm_wp + 1 || w >= c->W) return fail(c, POCS_E_ORDER, "waypoint %d out of sequence", w);
   if (w != c->last_gmm_adv) return fail(c, POCS_E_ORDER, "waypoint %d sampled before pocs_gmm_advance_local(%d)", w, w);
-  long long first, count;
-  if (int r = gmm_shard(c, &first, &count)) return r;
-  if (int r = enqueue_step(c, first, count, w, false, false, c->opt_profile == 1 ? w : -1)) return r;
-  c->res.last_gmm_wp = w;
-  c->res.last_gmm_count = count;
-  return POCS_OK;
+  return step_api_sample(c, w, false);
 }
 
 int pocs_gmm_step_local(pocs_ctx* c, int w) {
@@ -1139,14 +1147,11 @@ int pocs_gmm_exchange_local(pocs_ctx* c, int w) {
   if (w != c->res.last_gmm_wp || w != c->last_gmm_adv) return fail(c, POCS_E_ORDER, "exchange of waypoint %d out of sequence", w);
   if (c->batch > POCS_XCHG_MAX_RUNS) return fail(c, POCS_E_ARG, "exchange: at most %d runs per call", POCS_XCHG_MAX_RUNS);
   pocs_gmm_launch a;
-  fill_gmm_launch(c, &a, 0, 0, w);
+  fill_gmm_launch(c, &a, 0, 0);
+  aim_gmm_launch(c, &a, w);
   pocs_xchg_dev x;
-  memset(&x, 0, sizeof x);
-  for (int q = 0; q < c->xchg_world; ++q) x.buf[q] = (double*)c->xchg_peer[q];
-  x.world = c->xchg_world; x.rank = c->xchg_rank;
-  x.epoch = (c->xchg_calls << 20) | (unsigned long long)(w + 1);
-  x.parity = (int)((c->xchg_calls * (unsigned long long)c->W + (unsigned long long)w) & 1ull);
-  HIPCHK(c, pocs_launch_gmm_exchange(c->K, a, x, c->stream));
+  fill_xchg(c, &x, w, false);
+  if (int r = Issuer{c, nullptr}.launch(pocs_launch_gmm_exchange, 0, c->K, a, x)) return r;
   if (w + 1 < c->W) c->last_gmm_adv = w + 1;          // the exchange launch has built the mixture of w + 1
   return POCS_OK;
 }
@@ -1161,24 +1166,7 @@ int pocs_gmm_sample_exchange_local(pocs_ctx* c, int w) {
   if (w != c->res.last_gmm_wp + 1 || w >= c->W) return fail(c, POCS_E_ORDER, "waypoint %d out of sequence", w);
   if (w != c->last_gmm_adv) return fail(c, POCS_E_ORDER, "waypoint %d sampled before its mixture exists", w);
   if (c->batch > POCS_XCHG_MAX_RUNS) return fail(c, POCS_E_ARG, "exchange: at most %d runs per call", POCS_XCHG_MAX_RUNS);
-  long long first, count;
-  if (int r = gmm_shard(c, &first, &count)) return r;
-  pocs_gmm_launch a;
-  fill_gmm_launch(c, &a, first, count, w);
-  a.advance_in_tail = (w + 1 < c->W) ? a.run_lo + a.run_cnt : 0;
-  a.exchange_in_tail = 1;
-  for (int q = 0; q < c->xchg_world; ++q) a.xchg.buf[q] = (double*)c->xchg_peer[q];
-  a.xchg.world = c->xchg_world; a.xchg.rank = c->xchg_rank;
-  a.xchg.epoch = (c->xchg_calls << 20) | (unsigned long long)(w + 1);
-  a.xchg.parity = (int)((c->xchg_calls * (unsigned long long)c->W + (unsigned long long)w) & 1ull);
-  const int slot = c->opt_profile == 1 ? w : -1;
-  if (slot >= 0) HIPCHK(c, hipEventRecord(c->events[2 * slot], c->stream));
-  HIPCHK(c, pocs_launch_gmm_step(c->K, a, c->stream));
-  if (slot >= 0) HIPCHK(c, hipEventRecord(c->events[2 * slot + 1], c->stream));
-  c->res.last_gmm_wp = w;
-  c->res.last_gmm_count = count;
-  if (w + 1 < c->W) c->last_gmm_adv = w + 1;
-  return POCS_OK;
+  return step_api_sample(c, w, true);
 }
 
 int pocs_gmm_end(pocs_ctx* c, double* probability) {
@@ -1186,15 +1174,12 @@ int pocs_gmm_end(pocs_ctx* c, double* probability) {
   if (!c->gmm_open) return fail(c, POCS_E_ORDER, "pocs_gmm_end before pocs_gmm_begin");
   if (c->res.last_gmm_wp != c->W - 1) return fail(c, POCS_E_ORDER, "pocs_gmm_end after %d of %d waypoints", c->res.last_gmm_wp + 1, c->W);
   if (!probability) return fail(c, POCS_E_ARG, "null output");
-  const PinLayout pl = pin_layout(c);
   if (int r = enqueue_gmm_results(c)) return r;   // (no plans, no tree here: the moments and the give-up word alone)
   prefetch_next_batch(c, gmm_groups(c));          // host chains of the next batch, while the queued work drains
   HIPCHK(c, hipStreamSynchronize(c->stream));
-  unsigned gave_up = 0;
-  memcpy(&gave_up, (double*)c->h_pin + pl.total + c->batch + 1, sizeof gave_up);
-  if (gave_up) { c->gmm_open = false; return fail(c, POCS_E_DEVICE, "a bounded wait expired on the device (code %u: 4 = a peer's moments never arrived); results discarded", gave_up); }
+  if (int r = gmm_check_gave_up(c, "a bounded wait expired on the device (code %u: 4 = a peer's moments never arrived); results discarded")) { c->gmm_open = false; return r; }
   if (int r = prof_collect(c, (size_t)c->W)) return r;
-  (void)gmm_combine(c, (double*)c->h_pin + pl.moments, probability);      // (no risk bound in the step API: cannot fail)
+  (void)gmm_combine(c, (double*)c->h_pin + pin_layout(c).moments, probability);      // (no risk bound in the step API: cannot fail)
   note_obs_counts(c, 1);
   c->gmm_open = false;
   return POCS_OK;

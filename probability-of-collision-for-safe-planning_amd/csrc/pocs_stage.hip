@@ -127,7 +127,6 @@ int ensure_pin(pocs_ctx* c) {
   if (c->h_pin) { HIPCHK(c, hipHostFree(c->h_pin)); c->h_pin = nullptr; c->h_pin_cap = 0; }
   HIPCHK(c, hipHostMalloc(&c->h_pin, bytes, hipHostMallocDefault));
   c->h_pin_cap = bytes;
-  drop_graphs(c);   // captured copies hold the old staging pointers
   return POCS_OK;
 }
 

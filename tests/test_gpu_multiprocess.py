@@ -86,9 +86,14 @@ def _worker_onehop(rank, world, port, n_local, K, seed, batch, out):
     c.configure(plan, env, K=K, N=N, seed=seed)
     c.set_batch(batch)
     c.set_shard(rank * n_local, n_local)
-    par.connect_contexts(c, dist, rank, world)
+    handles = [None] * world                              # (par.connect_contexts, with the handles kept for the reconnect below)
+    dist.all_gather_object(handles, c.xchg_create(world, rank))
+    c.xchg_connect(handles)
     whole = {}
-    for tag, groups in (("one", 1), ("sub2", 2), ("again", 0)):
+    for tag, groups in (("one", 1), ("sub2", 2), ("again", 0), ("reconnected", 0)):
+        if tag == "reconnected":                          # every rank maps its peers' buffers again, wherever they land: the cached
+            c.xchg_connect(handles)                       # graph's launches hold the old mappings, so the call is captured anew
+            dist.barrier()
         c.set_option(pocs_amd.OPT_SUB_BATCHES, groups)
         c.set_seed(seed)
         c.run_gmm_estimation()
@@ -148,7 +153,7 @@ def _worker_onehop(rank, world, port, n_local, K, seed, batch, out):
         np.savez(out, p_gloo=res["gloo"][0], p_one=res["onehop"][0], m_gloo=res["gloo"][1], m_one=res["onehop"][1],
                  p_again=res["onehop_again"][0], p_fused=res["fused"][0], m_fused=res["fused"][1],
                  p_whole=whole["one"][0], m_whole=whole["one"][1], p_whole2=whole["sub2"][0], m_whole2=whole["sub2"][1],
-                 p_whole3=whole["again"][0], p_whole_next=whole["next"][0],
+                 p_whole3=whole["again"][0], p_whole4=whole["reconnected"][0], m_whole4=whole["reconnected"][1], p_whole_next=whole["next"][0],
                  odd_gloo=res["gloo_odd"], odd_fused=res["fused_odd"], odd_onehop=res["onehop_odd"],
                  two_gloo=res["gloo2"], two_fused=res["fused2"])
     dist.destroy_process_group()
@@ -174,6 +179,8 @@ def test_onehop_exchange_equals_the_collective(tmp_path, pocs, plan, env):
     assert list(got["p_whole"]) == list(got["p_gloo"]) and np.array_equal(got["m_whole"], got["m_gloo"])
     assert list(got["p_whole2"]) == list(got["p_gloo"]) and np.array_equal(got["m_whole2"], got["m_gloo"])
     assert list(got["p_whole3"]) == list(got["p_gloo"])
+    # ... and a fourth after every rank has connected to its peers again (pocs_xchg_connect with the same handles)
+    assert list(got["p_whole4"]) == list(got["p_gloo"]) and np.array_equal(got["m_whole4"], got["m_gloo"])
     assert list(got["p_whole_next"]) != list(got["p_gloo"]) and all(0 < p < 1 for p in got["p_whole_next"])
     # 21 waypoints, three calls in a row on the same buffers: every call of both one-hop forms equals the collective's
     assert list(got["odd_fused"]) == list(got["odd_gloo"]) and list(got["odd_onehop"]) == list(got["odd_gloo"])

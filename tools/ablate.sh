@@ -19,8 +19,7 @@ if [ $what = ablate ] || [ $what = all ]; then
   done
 fi
 if [ $what = graphdiag ] || [ $what = all ]; then
-  # which of round 3's two changes cures the lost graph replay: the graph's shape or the getters' staging
-  cc -DPOCS_GRAPH_WITH_COPIES -o ab_build/libpocs_graphcopies.so 2>/dev/null; echo built ab_build/libpocs_graphcopies.so
+  # round 2's getters under the kernel-only graph (the other half of that diagnosis, round 2's graph shape, is settled and
+  # retired: profiles/r04_graphdiag.txt)
   cc -DPOCS_PAGEABLE_GETTERS -o ab_build/libpocs_pageable.so 2>/dev/null; echo built ab_build/libpocs_pageable.so
-  cc -DPOCS_GRAPH_WITH_COPIES -DPOCS_PAGEABLE_GETTERS -o ab_build/libpocs_both.so 2>/dev/null; echo built ab_build/libpocs_both.so
 fi
