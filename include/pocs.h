@@ -95,10 +95,9 @@ int pocs_get_world_steps(const pocs_ctx* ctx);                                  
  *     of it): POCS_OPT_LONE_CALL has no effect under a large world; the results are the same bits either way.
  * It replaces whatever world or schedule was set; pocs_set_obstacles, pocs_set_obstacle_schedule and clearObstacles replace a large
  * world.  pocs_set_footprint re-prepares its records.  pocs_get_world_steps answers 1.
- * REFUSED under a large world, each with a message that names the combination, the context left as it was: POCS_OPT_OBSTACLE_COUNTS = 1
- * and POCS_OPT_MC_FUSED = 1 (POCS_E_STATE, whichever of the two is set second), pocs_set_plan_tree, pocs_set_shard, the step API
- * (pocs_gmm_begin, pocs_gmm_bind_moments), the exchange (pocs_xchg_create / pocs_xchg_connect), pocs_probe_device_collide
- * (POCS_E_STATE); addObstacle (POCS_E_ARG); an obstacle schedule keeps its limit of 64 boxes per step.
+ * What a large world does not combine with is refused, with a message that names the call and the mode in its way, the context left
+ * as it was: the matrix of all mode combinations and their codes is DESIGN.md section 9 (from csrc/pocs_modes.hpp).  An obstacle
+ * schedule keeps its limit of 64 boxes per step.
  * POCS_E_ARG (the world in force stays): M out of range, a null `boxes` with M > 0, a half extent <= 0, and for M > 64 any value that
  * is not finite.  The text channel has no command for it.
  * pocs_get_world_boxes: M of the world in force -- a large world's, a static world's, a schedule's boxes per step; 0 without one. */
@@ -287,10 +286,9 @@ int pocs_get_plan_evaluated(pocs_ctx* ctx, int* out, int cap);
  *     the nodes of the DEEPEST level only (an MC call keeps two levels of particle state, not T clouds) and returns
  *     POCS_E_STATE for any other node.  A new call selects node 0;
  *   - samples are NOT stored, whatever POCS_OPT_STORE_SAMPLES says: pocs_copy_gmm_samples returns POCS_E_STATE;
- *   - a tree and a set of plans exclude each other: pocs_set_plans while a tree is set, pocs_set_plan_tree while plans are set,
- *     and pocs_set_batch, pocs_set_path_length, pocs_set_trajectory, pocs_set_odometry, pocs_select_batch_run return
- *     POCS_E_ORDER; a shard, the step API (pocs_gmm_begin) and the in-library exchange (pocs_xchg_*) return POCS_E_STATE;
- *     run-ahead is not applied; POCS_OPT_PROFILE = 1 runs the call eagerly without per-launch times.
+ *   - what a tree does not combine with (a set of plans, the single plan's setters, a shard, the step API, the exchange, a large
+ *     world) is refused: the matrix with its codes is DESIGN.md section 9; run-ahead is not applied; POCS_OPT_PROFILE = 1 runs
+ *     the call eagerly without per-launch times.
  * Risk bound (pocs_set_plan_risk_bound in (0, 1)): a GMM call does not evaluate the descendants of a node whose running
  * probability has reached the bound.  The stop is decided on the device -- a node's launch reads its parent's stop word and
  * inherits it -- and the host restates the rule on what it reads back (a mismatch: POCS_E_DEVICE).  A stopped node's entry of

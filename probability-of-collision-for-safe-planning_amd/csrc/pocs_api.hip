@@ -43,6 +43,99 @@ static const char* kHelp =
     "setRunAhead      r: with one run per command, evaluate the next r runs in one launch and serve the following commands from it (new)\n"
     "help             this text\n";
 
+// ---- the shapes every setter and getter shares ----
+// A setter's prologue: false for a null context; otherwise it TOUCHES before it validates (a refused setter ends run-ahead serving too).
+static bool setter(pocs_ctx* c) {
+  if (c) touch(c);
+  return c != nullptr;
+}
+
+// `rows` boxes of {cx, cy, half_x, half_y, yaw}, `per_step` of them per step of a schedule: half extents > 0 and -- where the
+// setter asks for it (`finite`; pocs_set_obstacles never has) -- every value finite.
+static int check_boxes(pocs_ctx* c, const char* what, const double* boxes, size_t rows, size_t per_step, bool finite) {
+  for (size_t i = 0; i < rows; ++i) {
+    const double* b = boxes + 5 * i;
+    const int step = (int)(i / per_step), m = (int)(i % per_step);
+    for (int j = 0; finite && j < 5; ++j)
+      if (!std::isfinite(b[j])) return fail(c, POCS_E_ARG, "%s: step %d, box %d: value %d is not finite", what, step, m, j);
+    if (!(b[2] > 0) || !(b[3] > 0)) return fail(c, POCS_E_ARG, "%s: step %d, box %d: half extents must be > 0", what, step, m);
+  }
+  return POCS_OK;
+}
+
+// A vector getter's tail: POCS_E_BUFFER when the caller's `cap` elements do not hold the `n` there are, else the copy and n.
+template <class T>
+static int copy_out(pocs_ctx* c, T* out, int cap, const T* src, size_t n, const char* unit) {
+  if ((long long)n > (long long)cap) return fail(c, POCS_E_BUFFER, "need %zu %s", n, unit);
+  if (n) memcpy(out, src, n * sizeof(T));
+  return (int)n;
+}
+template <class T>
+static int copy_out(pocs_ctx* c, T* out, int cap, const std::vector<T>& v, const char* unit) { return copy_out(c, out, cap, v.data(), v.size(), unit); }
+// ... of the two per-run getters: after an internal run-ahead batch the caller asked for one run at a time, and gets that one.
+template <class T>
+static int batch_out(pocs_ctx* c, T* out, int cap, const std::vector<T>& v, const char* unit) {
+  if (!c->ra_internal) return copy_out(c, out, cap, v, unit);
+  if (cap < 1 || v.empty()) return fail(c, POCS_E_BUFFER, "need 1 %s", unit);
+  out[0] = v[(size_t)c->res.view];
+  return 1;
+}
+
+// The collision world in force: `steps` tables of `small` boxes each in the table every kernel stages, OR a large world of `large` boxes
+// beside it (the staged table is then empty); each gives way to the other.
+static int install_world(pocs_ctx* c, const double* boxes, size_t small, int steps, size_t large) {
+  c->boxes.assign(boxes, boxes + (size_t)steps * small * 5);
+  c->world.assign(boxes, boxes + large * 5);
+  c->world_S = steps;
+  c->have_obstacles = true;
+  c->env_dirty = true;
+  return POCS_OK;
+}
+
+// ---- the run-ahead front ----
+// run* with run-ahead: serve the next cached run, or evaluate the next `run_ahead` runs at once.
+static bool ra_can_serve(const pocs_ctx* c, Kind kind) {
+  return c->ra_have > 0 && c->ra_kind == kind && c->batch == 1 && c->res.view + 1 < c->ra_have;
+}
+// Runs evaluated per launch when run-ahead is on.  0 (automatic): enough runs to keep the chip busy for the
+// launch's fixed cost to fade -- 1.6 x 10^7 mixture samples or 8 x 10^6 particles (what stays in the
+// Infinity Cache between two waypoint launches) per launch, at least 8, at most 64: the reference's
+// own 200 runs of 10^4 samples go 64 at a time, a 10^6-sample estimation 16 at a time.
+static int ra_depth(const pocs_ctx* c, Kind kind) {
+  if (c->run_ahead != 0) return c->run_ahead;
+  const long long n = kind == Kind::Gmm ? c->num_gmm : c->num_particles;
+  const long long want = (kind == Kind::Gmm ? 16000000LL : 8000000LL) / (n > 0 ? n : 1);
+  return (int)(want < 8 ? 8 : want > 64 ? 64 : want);
+}
+static bool ra_wanted(const pocs_ctx* c, Kind kind) {
+  using namespace pocs_modes;
+  return ra_depth(c, kind) > 1 && c->batch == 1 && !c->opt_profile && !in_mode(c, kPlans | kTree | kShard | kMoments | kSequence);
+}
+// The front of every run* call: serve the next cached run of `kind` (`ahead`: the call takes part in run-ahead), or drop what is
+// cached, size the launch, make it (`run`) and remember what it left; res.view is then the run the call hands out.
+template <class Run>
+static int ra_front(pocs_ctx* c, Kind kind, bool ahead, Run run) {
+  HIPCHK(c, hipSetDevice(c->device));
+  if (ahead && ra_can_serve(c, kind)) {
+    if (kind == Kind::Gmm) gmm_select_view(c, c->res.view + 1); else c->res.view += 1;
+    return POCS_OK;
+  }
+  ra_drop(c);
+  c->ra_internal = false;
+  const int depth = ahead && ra_wanted(c, kind) ? ra_depth(c, kind) : 0;
+  if (depth) c->batch = depth;
+  const int rc = run();
+  if (depth) c->batch = 1;
+  if (rc == POCS_OK && depth) { c->ra_have = depth; c->ra_kind = kind; c->ra_internal = true; }
+  return rc;
+}
+static void mc_fill_probs(pocs_ctx* c) {
+  // getCollisionProportion, MCSimulator.h:324-330 (of the particles this context evaluated)
+  const double den = (double)(c->res.last_mc_count > 0 ? c->res.last_mc_count : 1);
+  c->res.batch_probs.assign(c->res.mc_counts.size(), 0.0);
+  for (size_t r = 0; r < c->res.mc_counts.size(); ++r) c->res.batch_probs[r] = (double)c->res.mc_counts[r] / den;
+}
+
 extern "C" {
 
 const char* pocs_version(void) { return POCS_VERSION_STRING; }
@@ -94,11 +187,6 @@ void pocs_destroy(pocs_ctx* c) {
     if (c->ev_fork) hipEventDestroy(c->ev_fork);
     if (c->ev_seq[0]) hipEventDestroy(c->ev_seq[0]);
     if (c->ev_seq[1]) hipEventDestroy(c->ev_seq[1]);
-    DevBuf* all[] = {&c->d_env, &c->d_sensor, &c->d_hdr, &c->d_chain, &c->d_state, &c->d_param,
-                     &c->d_moments, &c->d_partial, &c->d_sx, &c->d_sy, &c->d_st, &c->d_flags,
-                     &c->d_px, &c->d_py, &c->d_pt, &c->d_hits, &c->d_total, &c->d_ticket, &c->d_tables, &c->d_runplan, &c->d_surv, &c->d_tparent,
-                     &c->d_obsct, &c->d_world, &c->d_kept, &c->d_keptidx, &c->d_reach};
-    for (DevBuf* b : all) if (b->p) hipFree(b->p);
     if (c->h_pin) hipHostFree(c->h_pin);
     if (c->h_copy) hipHostFree(c->h_copy);
     for (int q = 0; q < POCS_XCHG_MAX_WORLD; ++q)
@@ -106,14 +194,13 @@ void pocs_destroy(pocs_ctx* c) {
     if (c->xchg_own) (void)hipFree(c->xchg_own);
     hipStreamDestroy(c->own_stream);
   }
-  delete c;
+  delete c;                                          // (every DevBuf frees itself: the device is selected above)
 }
 
 const char* pocs_last_error(const pocs_ctx* c) { return c ? c->err.c_str() : "null context"; }
 
 int pocs_set_footprint(pocs_ctx* c, double dx, double dy, double hx, double hy) {
-  if (c) touch(c);
-  if (!c) return POCS_E_ARG;
+  if (!setter(c)) return POCS_E_ARG;
   if (!(hx > 0) || !(hy > 0)) return fail(c, POCS_E_ARG, "footprint half extents must be > 0");
   c->fp.dx = dx; c->fp.dy = dy; c->fp.hx = hx; c->fp.hy = hy;
   c->env_dirty = true;
@@ -121,82 +208,38 @@ int pocs_set_footprint(pocs_ctx* c, double dx, double dy, double hx, double hy) 
 }
 
 int pocs_set_obstacles(pocs_ctx* c, const double* boxes, int M) {
-  if (c) touch(c);
-  if (!c) return POCS_E_ARG;
+  if (!setter(c)) return POCS_E_ARG;
   if (M < 0 || M > POCS_MAX_OBSTACLES || (M > 0 && !boxes))
     return fail(c, POCS_E_ARG, "obstacle count %d outside 0..%d", M, POCS_MAX_OBSTACLES);
-  for (int m = 0; m < M; ++m)
-    if (!(boxes[5 * m + 2] > 0) || !(boxes[5 * m + 3] > 0))
-      return fail(c, POCS_E_ARG, "obstacle %d: half extents must be > 0", m);
-  c->boxes.assign(boxes, boxes + (size_t)M * 5);
-  c->world_S = 1;                                    // (a schedule gives way to the static world)
-  c->world.clear();                                  // (and so does a large world)
-  c->have_obstacles = true;
-  c->env_dirty = true;
-  return POCS_OK;
+  if (int r = check_boxes(c, "obstacles", boxes, (size_t)M, (size_t)M, false)) return r;
+  return install_world(c, boxes, (size_t)M, 1, 0);
 }
 
 // The obstacle schedule: S worlds of M boxes each, world s the collision world at waypoint s (upload_world prepares one
 // record per step; every launch takes the record of its waypoint: world_at).  S = 1 is pocs_set_obstacles.
 int pocs_set_obstacle_schedule(pocs_ctx* c, const double* boxes, int M, int S) {
-  if (c) touch(c);
-  if (!c) return POCS_E_ARG;
+  if (!setter(c)) return POCS_E_ARG;
   if (M < 0 || M > POCS_MAX_OBSTACLES) return fail(c, POCS_E_ARG, "obstacle count %d outside 0..%d", M, POCS_MAX_OBSTACLES);
   if (S == 0 && M == 0) return pocs_set_obstacles(c, nullptr, 0);      // no schedule, an explicitly empty world
   if (S < 1 || S > POCS_MAX_WORLD_STEPS) return fail(c, POCS_E_ARG, "obstacle schedule of %d steps outside 1..%d", S, POCS_MAX_WORLD_STEPS);
   if (M > 0 && !boxes) return fail(c, POCS_E_ARG, "obstacle schedule: null boxes");
-  for (int s = 0; s < S; ++s)
-    for (int m = 0; m < M; ++m) {
-      const double* b = boxes + ((size_t)s * (size_t)M + (size_t)m) * 5;
-      for (int j = 0; j < 5; ++j)
-        if (!std::isfinite(b[j])) return fail(c, POCS_E_ARG, "obstacle schedule: step %d, obstacle %d: value %d is not finite", s, m, j);
-      if (!(b[2] > 0) || !(b[3] > 0)) return fail(c, POCS_E_ARG, "obstacle schedule: step %d, obstacle %d: half extents must be > 0", s, m);
-    }
-  c->boxes.assign(boxes, boxes + (size_t)S * (size_t)M * 5);
-  c->world_S = S;
-  c->world.clear();                                  // (a large world gives way to the schedule)
-  c->have_obstacles = true;
-  c->env_dirty = true;
-  return POCS_OK;
+  if (int r = check_boxes(c, "obstacle schedule", boxes, (size_t)S * (size_t)M, (size_t)M, true)) return r;
+  return install_world(c, boxes, (size_t)M, S, 0);
 }
 
 int pocs_get_world_steps(const pocs_ctx* c) { return (c && c->have_obstacles) ? c->world_S : 0; }
-
-// What a large world does not serve, checked where the world or the other half of the combination is set: the context keeps what
-// it had.  `what`: the caller's name for the message.
-static int refuse_with_large_world(pocs_ctx* c, const char* what) {
-  if (c->opt_obs_counts) return fail(c, POCS_E_STATE, "%s: POCS_OPT_OBSTACLE_COUNTS is on; the per-box counts serve worlds of at most %d boxes", what, POCS_MAX_OBSTACLES);
-  if (c->opt_fused) return fail(c, POCS_E_STATE, "%s: POCS_OPT_MC_FUSED is on; the fused roll-out serves worlds of at most %d boxes", what, POCS_MAX_OBSTACLES);
-  if (c->tree.n) return fail(c, POCS_E_STATE, "%s: a tree of plans is set; trees serve worlds of at most %d boxes", what, POCS_MAX_OBSTACLES);
-  if (c->shard_first >= 0) return fail(c, POCS_E_STATE, "%s: a shard is set; sharded runs serve worlds of at most %d boxes", what, POCS_MAX_OBSTACLES);
-  if (c->xchg_own || c->xchg_connected) return fail(c, POCS_E_STATE, "%s: the context takes part in the in-library exchange, which serves worlds of at most %d boxes", what, POCS_MAX_OBSTACLES);
-  if (c->ext_moments) return fail(c, POCS_E_STATE, "%s: a caller-owned moments buffer is bound (the step API), which serves worlds of at most %d boxes", what, POCS_MAX_OBSTACLES);
-  if (c->gmm_open) return fail(c, POCS_E_ORDER, "%s inside a begin/end sequence", what);
-  return POCS_OK;
-}
 
 // A static world of up to POCS_MAX_WORLD_BOXES boxes.  Up to POCS_MAX_OBSTACLES it IS pocs_set_obstacles; above, the boxes are kept
 // apart from the staged table (which is then empty): upload_world prepares their records, the GMM launches get a cull launch in
 // front of each waypoint and the _world forms of the sampling kernel, the MC launches the _world forms of theirs.
 int pocs_set_world(pocs_ctx* c, const double* boxes, int M) {
-  if (c) touch(c);
-  if (!c) return POCS_E_ARG;
+  if (!setter(c)) return POCS_E_ARG;
   if (M < 0 || M > POCS_MAX_WORLD_BOXES || (M > 0 && !boxes))
     return fail(c, POCS_E_ARG, "world of %d boxes outside 0..%d (or null boxes)", M, POCS_MAX_WORLD_BOXES);
   if (M <= POCS_MAX_OBSTACLES) return pocs_set_obstacles(c, boxes, M);
-  for (int m = 0; m < M; ++m) {
-    for (int j = 0; j < 5; ++j)
-      if (!std::isfinite(boxes[5 * (size_t)m + j])) return fail(c, POCS_E_ARG, "world: box %d: value %d is not finite", m, j);
-    if (!(boxes[5 * (size_t)m + 2] > 0) || !(boxes[5 * (size_t)m + 3] > 0))
-      return fail(c, POCS_E_ARG, "world: box %d: half extents must be > 0", m);
-  }
-  if (int r = refuse_with_large_world(c, "pocs_set_world with more than 64 boxes")) return r;
-  c->world.assign(boxes, boxes + (size_t)M * 5);
-  c->boxes.clear();                                  // (the staged table holds nothing; a schedule gives way)
-  c->world_S = 1;
-  c->have_obstacles = true;
-  c->env_dirty = true;
-  return POCS_OK;
+  if (int r = check_boxes(c, "world", boxes, (size_t)M, (size_t)M, true)) return r;
+  if (int r = may_enter(c, "pocs_set_world with more than 64 boxes", pocs_modes::kLargeWorld)) return r;
+  return install_world(c, boxes, 0, 1, (size_t)M);
 }
 
 int pocs_get_world_boxes(const pocs_ctx* c) {
@@ -208,16 +251,12 @@ int pocs_get_world_reach(pocs_ctx* c, int* out, int cap) {
   if (!c || !out) return POCS_E_ARG;
   if (c->reach_R < 1 || c->reach.empty())
     return fail(c, POCS_E_STATE, "pocs_get_world_reach: the last GMM call did not run under a large world (pocs_set_world with more than %d boxes)", POCS_MAX_OBSTACLES);
-  const int r = c->res.view >= 0 && c->res.view < c->reach_R ? c->res.view : 0;
-  const int n = c->reach_len[(size_t)r];
-  if (n > cap) return fail(c, POCS_E_BUFFER, "need %d ints", n);
-  memcpy(out, &c->reach[(size_t)r * (size_t)c->reach_W], (size_t)n * sizeof(int));
-  return n;
+  const size_t r = c->res.view >= 0 && c->res.view < c->reach_R ? (size_t)c->res.view : 0;
+  return copy_out(c, out, cap, &c->reach[r * (size_t)c->reach_W], (size_t)c->reach_len[r], "ints");
 }
 
 int pocs_set_alphas(pocs_ctx* c, const double* a, int n) {
-  if (c) touch(c);
-  if (!c) return POCS_E_ARG;
+  if (!setter(c)) return POCS_E_ARG;
   if (n < 1 || n > 4 || !a) return fail(c, POCS_E_ARG, "setAlphas takes 1..4 values (got %d)", n);
   for (int i = 0; i < n; ++i) c->alphas[i] = a[i];
   c->have_alphas = true;
@@ -225,24 +264,21 @@ int pocs_set_alphas(pocs_ctx* c, const double* a, int n) {
 }
 
 int pocs_set_q(pocs_ctx* c, double q) {
-  if (c) touch(c);
-  if (!c) return POCS_E_ARG;
+  if (!setter(c)) return POCS_E_ARG;
   if (!(q >= 0)) return fail(c, POCS_E_ARG, "Q must be >= 0");
   c->sensor.Q = q; c->have_q = true; c->sensor_dirty = true;
   return POCS_OK;
 }
 
 int pocs_set_num_landmarks(pocs_ctx* c, int n) {
-  if (c) touch(c);
-  if (!c) return POCS_E_ARG;
+  if (!setter(c)) return POCS_E_ARG;
   if (n < 0 || n > POCS_MAX_LANDMARKS) return fail(c, POCS_E_ARG, "numLandmarks %d outside 0..%d", n, POCS_MAX_LANDMARKS);
   c->num_landmarks = n; c->have_landmarks = false;
   return POCS_OK;
 }
 
 int pocs_set_landmarks(pocs_ctx* c, const double* xy, int n) {
-  if (c) touch(c);
-  if (!c) return POCS_E_ARG;
+  if (!setter(c)) return POCS_E_ARG;
   if (c->num_landmarks < 0) return fail(c, POCS_E_ORDER, "setLandmarks before setNumLandmarks");
   if (n != c->num_landmarks || (n > 0 && !xy)) return fail(c, POCS_E_ARG, "setLandmarks needs 2*%d values", c->num_landmarks);
   c->sensor.L = n;
@@ -252,26 +288,22 @@ int pocs_set_landmarks(pocs_ctx* c, const double* xy, int n) {
 }
 
 int pocs_set_num_particles(pocs_ctx* c, long long n) {
-  if (c) touch(c);
-  if (!c) return POCS_E_ARG;
+  if (!setter(c)) return POCS_E_ARG;
   if (n < 1) return fail(c, POCS_E_ARG, "numParticles must be >= 1");
   c->num_particles = n;
   return POCS_OK;
 }
 
 int pocs_set_initial_covariance(pocs_ctx* c, const double* m9) {
-  if (c) touch(c);
-  if (!c || !m9) return POCS_E_ARG;
+  if (!setter(c) || !m9) return POCS_E_ARG;
   memcpy(c->cov0, m9, 9 * sizeof(double));
   c->have_cov0 = true;
   return POCS_OK;
 }
 
 int pocs_set_path_length(pocs_ctx* c, int W) {
-  if (c) touch(c);
-  if (!c) return POCS_E_ARG;
-  if (c->plans.n) return fail(c, POCS_E_ORDER, "pocs_set_path_length while plans are set: clear them first with pocs_set_plans(ctx, 0, ...)");
-  if (c->tree.n) return fail(c, POCS_E_ORDER, "pocs_set_path_length while a tree of plans is set: clear it first with pocs_set_plan_tree(ctx, 0, ...)");
+  if (!setter(c)) return POCS_E_ARG;
+  if (int r = may_enter(c, "pocs_set_path_length", pocs_modes::kSinglePlan)) return r;
   if (W < 1) return fail(c, POCS_E_ARG, "pathLength must be >= 1");
   if (W != c->W) { c->have_traj = false; c->have_odom = false; }
   c->W = W;
@@ -279,10 +311,8 @@ int pocs_set_path_length(pocs_ctx* c, int W) {
 }
 
 int pocs_set_trajectory(pocs_ctx* c, const double* v, int W) {
-  if (c) touch(c);
-  if (!c) return POCS_E_ARG;
-  if (c->plans.n) return fail(c, POCS_E_ORDER, "pocs_set_trajectory while plans are set: clear them first with pocs_set_plans(ctx, 0, ...)");
-  if (c->tree.n) return fail(c, POCS_E_ORDER, "pocs_set_trajectory while a tree of plans is set: clear it first with pocs_set_plan_tree(ctx, 0, ...)");
+  if (!setter(c)) return POCS_E_ARG;
+  if (int r = may_enter(c, "pocs_set_trajectory", pocs_modes::kSinglePlan)) return r;
   if (c->W < 1) return fail(c, POCS_E_ORDER, "setTrajectory before setPathLength");
   if (W != c->W || !v) return fail(c, POCS_E_ARG, "setTrajectory needs 3*%d values", c->W);
   c->traj.assign(v, v + (size_t)3 * W);
@@ -291,10 +321,8 @@ int pocs_set_trajectory(pocs_ctx* c, const double* v, int W) {
 }
 
 int pocs_set_odometry(pocs_ctx* c, const double* v, int Wm1) {
-  if (c) touch(c);
-  if (!c) return POCS_E_ARG;
-  if (c->plans.n) return fail(c, POCS_E_ORDER, "pocs_set_odometry while plans are set: clear them first with pocs_set_plans(ctx, 0, ...)");
-  if (c->tree.n) return fail(c, POCS_E_ORDER, "pocs_set_odometry while a tree of plans is set: clear it first with pocs_set_plan_tree(ctx, 0, ...)");
+  if (!setter(c)) return POCS_E_ARG;
+  if (int r = may_enter(c, "pocs_set_odometry", pocs_modes::kSinglePlan)) return r;
   if (c->W < 1) return fail(c, POCS_E_ORDER, "setOdometry before setPathLength");
   if (Wm1 != c->W - 1 || (Wm1 > 0 && !v)) return fail(c, POCS_E_ARG, "setOdometry needs 3*%d values", c->W - 1);
   c->odom.assign(v, v + (size_t)3 * Wm1);
@@ -303,35 +331,31 @@ int pocs_set_odometry(pocs_ctx* c, const double* v, int Wm1) {
 }
 
 int pocs_set_num_gaussians(pocs_ctx* c, int K) {
-  if (c) touch(c);
-  if (!c) return POCS_E_ARG;
+  if (!setter(c)) return POCS_E_ARG;
   if (K < 1 || K > POCS_MAX_GAUSSIANS) return fail(c, POCS_E_ARG, "numGaussians %d outside 1..%d", K, POCS_MAX_GAUSSIANS);
   c->K = K;
   return POCS_OK;
 }
 
 int pocs_set_num_gmm_samples(pocs_ctx* c, long long n) {
-  if (c) touch(c);
-  if (!c) return POCS_E_ARG;
+  if (!setter(c)) return POCS_E_ARG;
   if (n < 1) return fail(c, POCS_E_ARG, "numGMMSamples must be >= 1");
   c->num_gmm = n;
   return POCS_OK;
 }
 
 int pocs_set_seed(pocs_ctx* c, uint64_t seed) {
-  if (c) touch(c);
-  if (!c) return POCS_E_ARG;
+  if (!setter(c)) return POCS_E_ARG;
   c->seed = seed; c->run_index = 0;
   return POCS_OK;
 }
 
 int pocs_set_option(pocs_ctx* c, int option, long long value) {
-  if (c) touch(c);
-  if (!c) return POCS_E_ARG;
+  if (!setter(c)) return POCS_E_ARG;
   switch (option) {
     case POCS_OPT_STORE_SAMPLES: c->opt_store = value ? 1 : 0; break;
     case POCS_OPT_MC_FUSED:
-      if (value && large_world(c)) return fail(c, POCS_E_STATE, "POCS_OPT_MC_FUSED = 1 under a large world of %d boxes (pocs_set_world): the fused roll-out serves worlds of at most %d boxes", large_boxes(c), POCS_MAX_OBSTACLES);
+      if (value) if (int r = may_enter(c, "POCS_OPT_MC_FUSED = 1", pocs_modes::kFused)) return r;
       c->opt_fused = value ? 1 : 0;
       break;
     case POCS_OPT_USE_GRAPH: c->opt_graph = value ? 1 : 0; break;
@@ -367,10 +391,10 @@ int pocs_set_option(pocs_ctx* c, int option, long long value) {
       break;
     case POCS_OPT_OBSTACLE_COUNTS:
       if (value < 0 || value > 1) return fail(c, POCS_E_ARG, "POCS_OPT_OBSTACLE_COUNTS takes 0 or 1");
-      if (c->gmm_open) return fail(c, POCS_E_ORDER, "POCS_OPT_OBSTACLE_COUNTS inside a begin/end sequence");
-      if (value && large_world(c)) return fail(c, POCS_E_STATE, "POCS_OPT_OBSTACLE_COUNTS = 1 under a large world of %d boxes (pocs_set_world): the per-box counts serve worlds of at most %d boxes", large_boxes(c), POCS_MAX_OBSTACLES);
+      // (inside a sequence the option is not touched at all, whatever the value)
+      if (int r = may_enter(c, "POCS_OPT_OBSTACLE_COUNTS", pocs_modes::kObsCounts, value ? pocs_modes::kAll : pocs_modes::kSequence)) return r;
       c->opt_obs_counts = value;
-      c->res.oc_kind = 0;                            // (a table is served until the option is touched or the next call)
+      c->res.oc_kind = Kind::None;                           // (a table is served until the option is touched or the next call)
       break;
     case POCS_OPT_RUN_AHEAD:
       if (value < 0 || value > 256) return fail(c, POCS_E_ARG, "run-ahead %lld outside 0..256", value);
@@ -382,12 +406,10 @@ int pocs_set_option(pocs_ctx* c, int option, long long value) {
 }
 
 int pocs_set_batch(pocs_ctx* c, int runs) {
-  if (!c) return POCS_E_ARG;
-  touch(c);
-  if (c->plans.n) return fail(c, POCS_E_ORDER, "pocs_set_batch while plans are set (the batch is the plans): clear them first with pocs_set_plans(ctx, 0, ...)");
-  if (c->tree.n) return fail(c, POCS_E_ORDER, "pocs_set_batch while a tree of plans is set: clear it first with pocs_set_plan_tree(ctx, 0, ...)");
+  if (!setter(c)) return POCS_E_ARG;
+  if (int r = may_enter(c, "pocs_set_batch", pocs_modes::kSinglePlan)) return r;
   if (runs < 1 || runs > 256) return fail(c, POCS_E_ARG, "batch %d outside 1..256", runs);
-  if (c->gmm_open) return fail(c, POCS_E_ORDER, "pocs_set_batch inside a begin/end sequence");
+  if (int r = may_enter(c, "pocs_set_batch", pocs_modes::kBatch)) return r;
   c->batch = runs;
   return POCS_OK;
 }
@@ -396,7 +418,7 @@ int pocs_set_batch(pocs_ctx* c, int runs) {
 // the nodes); the single plan's wait for leave_multi.  The results of the last launch refer to the plans (or the plan) it
 // evaluated: entering and leaving drop them.
 static void enter_multi(pocs_ctx* c, int W, int batch) {
-  if (!c->plans.n && !c->tree.n) { c->single_W = c->W; c->single_batch = c->batch; }
+  if (!in_mode(c, pocs_modes::kPlans | pocs_modes::kTree)) { c->single_W = c->W; c->single_batch = c->batch; }
   c->W = W; c->batch = batch;
   reset_results(c);
 }
@@ -406,15 +428,14 @@ static void leave_multi(pocs_ctx* c) {
 }
 
 int pocs_set_plans(pocs_ctx* c, int P, const int* W, const double* trajs, const double* odoms) {
-  if (!c) return POCS_E_ARG;
-  touch(c);
-  if (c->gmm_open) return fail(c, POCS_E_ORDER, "pocs_set_plans inside a begin/end sequence");
+  if (!setter(c)) return POCS_E_ARG;
+  if (int r = may_enter(c, "pocs_set_plans", pocs_modes::kPlans, pocs_modes::kSequence)) return r;      // (P = 0 too)
   if (P < 0 || P > 256) return fail(c, POCS_E_ARG, "plans: P = %d outside 0..256", P);
   if (P == 0) {                                      // back to the single plan
     if (c->plans.n) { c->plans = PlanSet{}; leave_multi(c); }
     return POCS_OK;
   }
-  if (c->tree.n) return fail(c, POCS_E_ORDER, "pocs_set_plans while a tree of plans is set: clear it first with pocs_set_plan_tree(ctx, 0, ...)");
+  if (int r = may_enter(c, "pocs_set_plans", pocs_modes::kPlans, pocs_modes::kTree)) return r;
   if (!W || !trajs) return fail(c, POCS_E_ARG, "plans: null lengths or trajectories");
   size_t nt = 0, no = 0;
   int Wmax = 0;
@@ -424,8 +445,7 @@ int pocs_set_plans(pocs_ctx* c, int P, const int* W, const double* trajs, const 
     Wmax = W[p] > Wmax ? W[p] : Wmax;
   }
   if (no > 0 && !odoms) return fail(c, POCS_E_ARG, "plans: null odometry");
-  if (c->shard_first >= 0) return fail(c, POCS_E_STATE, "plans: not with a shard (pocs_set_shard(ctx, -1, -1) first): multi-GPU plan batches are not supported");
-  if (c->xchg_connected) return fail(c, POCS_E_STATE, "plans: not on a context connected to the in-library exchange");
+  if (int r = may_enter(c, "pocs_set_plans", pocs_modes::kPlans)) return r;
   c->plans.W.assign(W, W + P);
   c->plans.toff.assign((size_t)P, 0); c->plans.ooff.assign((size_t)P, 0);
   for (int p = 1; p < P; ++p) {
@@ -441,43 +461,36 @@ int pocs_set_plans(pocs_ctx* c, int P, const int* W, const double* trajs, const 
 }
 
 int pocs_set_plan_risk_bound(pocs_ctx* c, double bound) {
-  if (!c) return POCS_E_ARG;
-  touch(c);
+  if (!setter(c)) return POCS_E_ARG;
   if (!(bound > 0.0)) return fail(c, POCS_E_ARG, "risk bound %g: a probability in (0, 1), or >= 1 for none", bound);     // (NaN too)
-  if (c->gmm_open) return fail(c, POCS_E_ORDER, "pocs_set_plan_risk_bound inside a begin/end sequence");
+  if (int r = may_enter(c, "pocs_set_plan_risk_bound", pocs_modes::kRiskBound)) return r;
   c->risk_bound = bound < 1.0 ? bound : 1.0;
   return POCS_OK;
 }
 
 int pocs_get_plan_evaluated(pocs_ctx* c, int* out, int cap) {
   if (!c || !out) return POCS_E_ARG;
-  const int kind = c->res.last_kind;                     // 1 GMM, 2 MC -- which by default ignores the bound: every plan is driven to its end
-  if (!c->plans.n || kind == 0 || c->res.plan_slot[kind - 1].empty() || (kind == 1 && c->res.plan_E.empty()))
+  const Kind kind = c->res.last_kind;                    // (an MC call by default ignores the bound: every plan is driven to its end)
+  if (!c->plans.n || kind == Kind::None || c->res.plan_slot(kind).empty() || (kind == Kind::Gmm && c->res.plan_E.empty()))
     return fail(c, POCS_E_STATE, "pocs_get_plan_evaluated: the last call was not a call of plans");
-  const std::vector<int>& E = kind == 1 ? c->res.plan_E : c->res.plan_E_mc.empty() ? c->plans.W : c->res.plan_E_mc;
-  if ((int)E.size() > cap) return fail(c, POCS_E_BUFFER, "need %zu ints", E.size());
-  memcpy(out, E.data(), E.size() * sizeof(int));
-  return (int)E.size();
+  return copy_out(c, out, cap, kind == Kind::Gmm ? c->res.plan_E : c->res.plan_E_mc.empty() ? c->plans.W : c->res.plan_E_mc, "ints");
 }
 
 int pocs_set_plan_tree(pocs_ctx* c, int nodes, const int* parent, const double* poses, const double* odoms) {
-  if (!c) return POCS_E_ARG;
-  touch(c);
-  if (c->gmm_open) return fail(c, POCS_E_ORDER, "pocs_set_plan_tree inside a begin/end sequence");
+  if (!setter(c)) return POCS_E_ARG;
+  if (int r = may_enter(c, "pocs_set_plan_tree", pocs_modes::kTree, pocs_modes::kSequence)) return r;      // (nodes = 0 too)
   if (nodes < 0 || nodes > POCS_MAX_TREE_NODES) return fail(c, POCS_E_ARG, "tree: %d nodes outside 0..%d", nodes, POCS_MAX_TREE_NODES);
   if (nodes == 0) {                                  // back to the single plan
     if (c->tree.n) { c->tree = PlanTree{}; leave_multi(c); }
     return POCS_OK;
   }
-  if (c->plans.n) return fail(c, POCS_E_ORDER, "pocs_set_plan_tree while plans are set: clear them first with pocs_set_plans(ctx, 0, ...)");
-  if (large_world(c)) return fail(c, POCS_E_STATE, "pocs_set_plan_tree under a large world of %d boxes (pocs_set_world): trees serve worlds of at most %d boxes", large_boxes(c), POCS_MAX_OBSTACLES);
+  if (int r = may_enter(c, "pocs_set_plan_tree", pocs_modes::kTree, pocs_modes::kPlans | pocs_modes::kLargeWorld)) return r;
   if (!parent || !poses || (nodes > 1 && !odoms)) return fail(c, POCS_E_ARG, "tree: null parents, poses or controls");
   if (parent[0] != -1) return fail(c, POCS_E_ARG, "tree: node 0 is the root, its parent must be -1 (got %d)", parent[0]);
   for (int n = 1; n < nodes; ++n)
     if (parent[n] < 0 || parent[n] >= n)
       return fail(c, POCS_E_ARG, "tree: parent[%d] = %d; one root, and every other node's parent comes before it (0 <= parent[n] < n)", n, parent[n]);
-  if (c->shard_first >= 0) return fail(c, POCS_E_STATE, "tree: not with a shard (pocs_set_shard(ctx, -1, -1) first): trees run on one GPU");
-  if (c->xchg_connected) return fail(c, POCS_E_STATE, "tree: not on a context connected to the in-library exchange");
+  if (int r = may_enter(c, "pocs_set_plan_tree", pocs_modes::kTree)) return r;
   const size_t T = (size_t)nodes;
   std::vector<int> depth(T, 0);
   int D = 0;
@@ -502,193 +515,112 @@ int pocs_set_plan_tree(pocs_ctx* c, int nodes, const int* parent, const double* 
 
 int pocs_get_tree_probabilities(pocs_ctx* c, double* out, int cap) {
   if (!c || !out) return POCS_E_ARG;
-  if (!c->tree.n || !c->res.tree_last || c->res.tree_probs.empty()) return fail(c, POCS_E_STATE, "pocs_get_tree_probabilities: the last call was not a call on a tree of plans");
-  if ((int)c->res.tree_probs.size() > cap) return fail(c, POCS_E_BUFFER, "need %zu doubles", c->res.tree_probs.size());
-  memcpy(out, c->res.tree_probs.data(), c->res.tree_probs.size() * sizeof(double));
-  return (int)c->res.tree_probs.size();
+  if (tree_last(c) == Kind::None || c->res.tree_probs.empty()) return fail(c, POCS_E_STATE, "pocs_get_tree_probabilities: the last call was not a call on a tree of plans");
+  return copy_out(c, out, cap, c->res.tree_probs, "doubles");
 }
 
 int pocs_get_tree_evaluated(pocs_ctx* c, unsigned char* out, int cap) {
   if (!c || !out) return POCS_E_ARG;
-  if (!c->tree.n || !c->res.tree_last || c->res.tree_eval.empty()) return fail(c, POCS_E_STATE, "pocs_get_tree_evaluated: the last call was not a call on a tree of plans");
-  if ((int)c->res.tree_eval.size() > cap) return fail(c, POCS_E_BUFFER, "need %zu bytes", c->res.tree_eval.size());
-  memcpy(out, c->res.tree_eval.data(), c->res.tree_eval.size());
-  return (int)c->res.tree_eval.size();
+  if (tree_last(c) == Kind::None || c->res.tree_eval.empty()) return fail(c, POCS_E_STATE, "pocs_get_tree_evaluated: the last call was not a call on a tree of plans");
+  return copy_out(c, out, cap, c->res.tree_eval, "bytes");
 }
 
 int pocs_mc_get_tree_counts(pocs_ctx* c, unsigned long long* out, int cap) {
   if (!c || !out) return POCS_E_ARG;
-  if (!c->tree.n || c->res.tree_last != 2 || c->res.tree_C.empty()) return fail(c, POCS_E_STATE, "pocs_mc_get_tree_counts: the last call was not an MC call on a tree of plans");
-  if ((int)c->res.tree_C.size() > cap) return fail(c, POCS_E_BUFFER, "need %zu counters", c->res.tree_C.size());
-  memcpy(out, c->res.tree_C.data(), c->res.tree_C.size() * sizeof(unsigned long long));
-  return (int)c->res.tree_C.size();
+  if (tree_last(c) != Kind::Mc || c->res.tree_C.empty()) return fail(c, POCS_E_STATE, "pocs_mc_get_tree_counts: the last call was not an MC call on a tree of plans");
+  return copy_out(c, out, cap, c->res.tree_C, "counters");
 }
 
 int pocs_select_tree_node(pocs_ctx* c, int node) {
   if (!c) return POCS_E_ARG;
-  if (!c->tree.n || !c->res.tree_last) return fail(c, POCS_E_STATE, "pocs_select_tree_node: the last call was not a call on a tree of plans");
+  if (tree_last(c) == Kind::None) return fail(c, POCS_E_STATE, "pocs_select_tree_node: the last call was not a call on a tree of plans");
   if (node < 0 || node >= c->tree.n) return fail(c, POCS_E_ARG, "node %d outside the tree (0..%d)", node, c->tree.n - 1);
-  if (c->res.tree_last == 1) tree_select_gmm(c, node);
+  if (tree_last(c) == Kind::Gmm) tree_select_gmm(c, node);
   c->res.tree_sel = node;
   return POCS_OK;
 }
 
 int pocs_get_batch_probabilities(pocs_ctx* c, double* out, int cap) {
   if (!c || !out) return POCS_E_ARG;
-  if (c->ra_internal) {                       // the caller asked for one run at a time
-    if (cap < 1 || c->res.batch_probs.empty()) return fail(c, POCS_E_BUFFER, "need 1 double");
-    out[0] = c->res.batch_probs[(size_t)c->res.view];
-    return 1;
-  }
-  if ((int)c->res.batch_probs.size() > cap) return fail(c, POCS_E_BUFFER, "need %zu doubles", c->res.batch_probs.size());
-  memcpy(out, c->res.batch_probs.data(), c->res.batch_probs.size() * sizeof(double));
-  return (int)c->res.batch_probs.size();
+  return batch_out(c, out, cap, c->res.batch_probs, "doubles");
 }
 
 int pocs_select_batch_run(pocs_ctx* c, int run) {
   if (!c) return POCS_E_ARG;
   if (c->ra_internal) return fail(c, POCS_E_ORDER, "pocs_select_batch_run: the last launch was a run-ahead batch (one run per command)");
-  if (c->tree.n) return fail(c, POCS_E_ORDER, "pocs_select_batch_run: a tree of plans is set (pocs_select_tree_node selects a node)");
+  if (int r = may_enter(c, "pocs_select_batch_run", pocs_modes::kSelectRun)) return r;
   if (run < 0 || run >= c->res.batch_R || c->res.batch_probs.empty()) return fail(c, POCS_E_ARG, "run %d outside the last batch (0..%d)", run, c->res.batch_R - 1);
-  if (c->res.last_kind == 1) gmm_select_view(c, run);       // per-waypoint probabilities and moments of that run
+  if (c->res.last_kind == Kind::Gmm) gmm_select_view(c, run);       // per-waypoint probabilities and moments of that run
   c->res.view = run;
   return POCS_OK;
 }
 
 int pocs_set_shard(pocs_ctx* c, long long first, long long count) {
-  if (c) touch(c);
-  if (!c) return POCS_E_ARG;
+  if (!setter(c)) return POCS_E_ARG;
   if (first == -1 && count == -1) { c->shard_first = -1; c->shard_count = -1; return POCS_OK; }   // whole range
-  if (c->plans.n) return fail(c, POCS_E_STATE, "pocs_set_shard: plans are set (multi-GPU plan batches are not supported)");
-  if (c->tree.n) return fail(c, POCS_E_STATE, "pocs_set_shard: a tree of plans is set (trees run on one GPU)");
-  if (large_world(c)) return fail(c, POCS_E_STATE, "pocs_set_shard under a large world of %d boxes (pocs_set_world): sharded runs serve worlds of at most %d boxes", large_boxes(c), POCS_MAX_OBSTACLES);
+  if (int r = may_enter(c, "pocs_set_shard", pocs_modes::kShard)) return r;
   if (first < 0 || count < 0) return fail(c, POCS_E_ARG, "negative shard");
   c->shard_first = first; c->shard_count = count;
   return POCS_OK;
 }
 
 int pocs_set_stream(pocs_ctx* c, void* s) {
-  if (c) touch(c);
-  if (!c) return POCS_E_ARG;
+  if (!setter(c)) return POCS_E_ARG;
   c->stream = s ? (hipStream_t)s : c->own_stream;
   return POCS_OK;
 }
 
 int pocs_gmm_bind_moments(pocs_ctx* c, void* dptr, long long len) {
-  if (c) touch(c);
-  if (!c) return POCS_E_ARG;
-  if (dptr && large_world(c)) return fail(c, POCS_E_STATE, "pocs_gmm_bind_moments under a large world of %d boxes (pocs_set_world): the step API serves worlds of at most %d boxes", large_boxes(c), POCS_MAX_OBSTACLES);
+  if (!setter(c)) return POCS_E_ARG;
+  if (dptr) if (int r = may_enter(c, "pocs_gmm_bind_moments", pocs_modes::kMoments)) return r;
   c->ext_moments = (double*)dptr; c->ext_moments_len = dptr ? len : 0;
   return POCS_OK;
-}
-
-// run* with run-ahead: serve the next cached run, or evaluate the next `run_ahead` runs at once.
-static bool ra_can_serve(const pocs_ctx* c, int kind) {
-  return c->ra_have > 0 && c->ra_kind == kind && c->batch == 1 && c->res.view + 1 < c->ra_have;
-}
-// Runs evaluated per launch when run-ahead is on.  0 (automatic): enough runs to keep the chip busy for the
-// launch's fixed cost to fade -- 1.6 x 10^7 mixture samples or 8 x 10^6 particles (what stays in the
-// Infinity Cache between two waypoint launches) per launch, at least 8, at most 64: the reference's
-// own 200 runs of 10^4 samples go 64 at a time, a 10^6-sample estimation 16 at a time.
-static int ra_depth(const pocs_ctx* c, int kind) {
-  if (c->run_ahead != 0) return c->run_ahead;
-  const long long n = kind == 1 ? c->num_gmm : c->num_particles;
-  const long long want = (kind == 1 ? 16000000LL : 8000000LL) / (n > 0 ? n : 1);
-  return (int)(want < 8 ? 8 : want > 64 ? 64 : want);
-}
-static bool ra_wanted(const pocs_ctx* c, int kind) {
-  return ra_depth(c, kind) > 1 && c->batch == 1 && !c->plans.n && !c->tree.n && c->shard_first < 0 && !c->opt_profile && !c->ext_moments && !c->gmm_open;
-}
-static void mc_fill_probs(pocs_ctx* c) {
-  // getCollisionProportion, MCSimulator.h:324-330 (of the particles this context evaluated)
-  const double den = (double)(c->res.last_mc_count > 0 ? c->res.last_mc_count : 1);
-  c->res.batch_probs.assign(c->res.mc_counts.size(), 0.0);
-  for (size_t r = 0; r < c->res.mc_counts.size(); ++r) c->res.batch_probs[r] = (double)c->res.mc_counts[r] / den;
 }
 
 int pocs_run_gmm_estimation(pocs_ctx* c, double* probability) {
   if (!c) return POCS_E_ARG;
   if (!probability) return fail(c, POCS_E_ARG, "null output");
-  HIPCHK(c, hipSetDevice(c->device));
-  if (ra_can_serve(c, 1)) {
-    gmm_select_view(c, c->res.view + 1);
-    *probability = c->res.batch_probs[(size_t)c->res.view];
-    return POCS_OK;
-  }
-  ra_drop(c);
-  c->ra_internal = false;
-  if (!ra_wanted(c, 1)) return run_gmm_full(c, probability);
-  const int depth = ra_depth(c, 1);
-  c->batch = depth;
-  const int rc = run_gmm_full(c, probability);
-  c->batch = 1;
-  if (rc == POCS_OK) { c->ra_have = depth; c->ra_kind = 1; c->ra_internal = true; }
-  return rc;
+  if (int r = ra_front(c, Kind::Gmm, true, [&] { return run_gmm_full(c, probability); })) return r;
+  *probability = c->res.batch_probs[(size_t)c->res.view];
+  return POCS_OK;
 }
 
 int pocs_run_simulation(pocs_ctx* c, double* probability) {
   if (!c) return POCS_E_ARG;
   if (!probability) return fail(c, POCS_E_ARG, "null output");
-  HIPCHK(c, hipSetDevice(c->device));
-  if (ra_can_serve(c, 2)) {
-    c->res.view += 1;
-    *probability = c->res.batch_probs[(size_t)c->res.view];
-    return POCS_OK;
-  }
-  ra_drop(c);
-  c->ra_internal = false;
-  const bool ra = ra_wanted(c, 2);
-  const int depth = ra_depth(c, 2);
-  if (ra) c->batch = depth;
-  const int rc = run_mc_local(c);
-  c->batch = ra ? 1 : c->batch;
-  if (rc) return rc;
-  mc_fill_probs(c);
-  if (ra) { c->ra_have = depth; c->ra_kind = 2; c->ra_internal = true; }
-  *probability = c->res.batch_probs[0];
+  if (int r = ra_front(c, Kind::Mc, true, [&] { const int rc = run_mc_local(c); if (rc == POCS_OK) mc_fill_probs(c); return rc; })) return r;
+  *probability = c->res.batch_probs[(size_t)c->res.view];
   return POCS_OK;
 }
 
 int pocs_mc_run_local(pocs_ctx* c, unsigned long long* collided) {
   if (!c) return POCS_E_ARG;
   if (!collided) return fail(c, POCS_E_ARG, "null output");
-  HIPCHK(c, hipSetDevice(c->device));
-  ra_drop(c);
-  c->ra_internal = false;
-  if (int r = run_mc_local(c)) return r;
+  if (int r = ra_front(c, Kind::Mc, false, [&] { return run_mc_local(c); })) return r;
   *collided = c->res.mc_counts[0];
   return POCS_OK;
 }
 
 int pocs_mc_get_batch_counts(pocs_ctx* c, unsigned long long* out, int cap) {
   if (!c || !out) return POCS_E_ARG;
-  if (c->ra_internal) {                       // the caller asked for one run at a time
-    if (cap < 1 || c->res.mc_counts.empty()) return fail(c, POCS_E_BUFFER, "need 1 counter");
-    out[0] = c->res.mc_counts[(size_t)c->res.view];
-    return 1;
-  }
-  if ((int)c->res.mc_counts.size() > cap) return fail(c, POCS_E_BUFFER, "need %zu counters", c->res.mc_counts.size());
-  memcpy(out, c->res.mc_counts.data(), c->res.mc_counts.size() * sizeof(unsigned long long));
-  return (int)c->res.mc_counts.size();
+  return batch_out(c, out, cap, c->res.mc_counts, "counters");
 }
 
 int pocs_mc_get_waypoint_counts(pocs_ctx* c, unsigned long long* out, int cap) {
   if (!c || !out) return POCS_E_ARG;
   const size_t W = (size_t)(c->res.mc_wp_W > 0 ? c->res.mc_wp_W : 1), r = (size_t)c->res.view;
   if (c->tree.n) {                                   // the selected node's path: the first collisions at each of its nodes
-    if (c->res.tree_last != 2 || c->res.tree_F.empty()) return fail(c, POCS_E_STATE, "pocs_mc_get_waypoint_counts: the last call was not an MC call on the tree");
+    if (tree_last(c) != Kind::Mc || c->res.tree_F.empty()) return fail(c, POCS_E_STATE, "pocs_mc_get_waypoint_counts: the last call was not an MC call on the tree");
     const int n = c->tree.depth[(size_t)c->res.tree_sel] + 1;
     if (n > cap) return fail(c, POCS_E_BUFFER, "need %d counters", n);
     for (int v = c->res.tree_sel, w = n - 1; v >= 0; v = c->tree.parent[(size_t)v], --w) out[w] = c->res.tree_F[(size_t)v];
     return n;
   }
-  if (c->res.last_kind != 2 || c->res.mc_wp.empty() || (r + 1) * W > c->res.mc_wp.size())
+  if (c->res.last_kind != Kind::Mc || c->res.mc_wp.empty() || (r + 1) * W > c->res.mc_wp.size())
     return fail(c, POCS_E_STATE, "pocs_mc_get_waypoint_counts: the last call was not an MC call under POCS_OPT_MC_WAYPOINT_COUNTS (or POCS_OPT_MC_RISK_BOUND with a bound)");
   int n = (int)W;                                    // the selected run's waypoints; a plan's own, or those before its stop
-  if (c->plans.n && r < c->res.plan_slot[1].size()) n = c->res.plan_E_mc.empty() ? c->plans.W[r] : c->res.plan_E_mc[r];
-  if (n > cap) return fail(c, POCS_E_BUFFER, "need %d counters", n);
-  memcpy(out, &c->res.mc_wp[r * W], (size_t)n * sizeof(unsigned long long));
-  return n;
+  if (c->plans.n && r < c->res.plan_slot(Kind::Mc).size()) n = c->res.plan_E_mc.empty() ? c->plans.W[r] : c->res.plan_E_mc[r];
+  return copy_out(c, out, cap, &c->res.mc_wp[r * W], (size_t)n, "counters");
 }
 
 int pocs_xchg_create(pocs_ctx* c, int world, int rank, void* handle64) {
@@ -696,9 +628,7 @@ int pocs_xchg_create(pocs_ctx* c, int world, int rank, void* handle64) {
   if (world < 1 || world > POCS_XCHG_MAX_WORLD || rank < 0 || rank >= world)
     return fail(c, POCS_E_ARG, "exchange: world %d / rank %d outside 1..%d", world, rank, POCS_XCHG_MAX_WORLD);
   static_assert(sizeof(hipIpcMemHandle_t) == 64, "pocs.h promises a 64-byte handle");
-  if (c->plans.n) return fail(c, POCS_E_STATE, "pocs_xchg_create: plans are set (multi-GPU plan batches are not supported)");
-  if (c->tree.n) return fail(c, POCS_E_STATE, "pocs_xchg_create: a tree of plans is set (trees run on one GPU)");
-  if (large_world(c)) return fail(c, POCS_E_STATE, "pocs_xchg_create under a large world of %d boxes (pocs_set_world): the exchange serves worlds of at most %d boxes", large_boxes(c), POCS_MAX_OBSTACLES);
+  if (int r = may_enter(c, "pocs_xchg_create", pocs_modes::kXchgCreated)) return r;
   HIPCHK(c, hipSetDevice(c->device));
   if (!c->xchg_own) {
     // FINE-GRAINED device memory: other GPUs write into it and this GPU polls it inside a running kernel.
@@ -717,9 +647,7 @@ int pocs_xchg_create(pocs_ctx* c, int world, int rank, void* handle64) {
 
 int pocs_xchg_connect(pocs_ctx* c, const void* handles, int world) {
   if (!c || !handles) return POCS_E_ARG;
-  if (c->plans.n) return fail(c, POCS_E_STATE, "pocs_xchg_connect: plans are set (multi-GPU plan batches are not supported)");
-  if (c->tree.n) return fail(c, POCS_E_STATE, "pocs_xchg_connect: a tree of plans is set (trees run on one GPU)");
-  if (large_world(c)) return fail(c, POCS_E_STATE, "pocs_xchg_connect under a large world of %d boxes (pocs_set_world): the exchange serves worlds of at most %d boxes", large_boxes(c), POCS_MAX_OBSTACLES);
+  if (int r = may_enter(c, "pocs_xchg_connect", pocs_modes::kXchgConnected)) return r;
   if (!c->xchg_own || world != c->xchg_world) return fail(c, POCS_E_ORDER, "pocs_xchg_connect before pocs_xchg_create (or another world size)");
   HIPCHK(c, hipSetDevice(c->device));
   for (int q = 0; q < world; ++q) {
@@ -742,18 +670,14 @@ int pocs_get_path_length(const pocs_ctx* c) {
 
 int pocs_get_waypoint_probabilities(pocs_ctx* c, double* out, int cap) {
   if (!c || !out) return POCS_E_ARG;
-  if ((int)c->res.probs.size() > cap) return fail(c, POCS_E_BUFFER, "need %zu doubles", c->res.probs.size());
-  memcpy(out, c->res.probs.data(), c->res.probs.size() * sizeof(double));
-  return (int)c->res.probs.size();
+  return copy_out(c, out, cap, c->res.probs, "doubles");
 }
 
 int pocs_get_moments(pocs_ctx* c, int w, double* out, int cap) {
   if (!c || !out) return POCS_E_ARG;
   const int n = c->K * POCS_NMOM;
   if (w < 0 || (size_t)(w + 1) * n > c->res.last_moments.size()) return fail(c, POCS_E_ARG, "no moments for waypoint %d", w);
-  if (cap < n) return fail(c, POCS_E_BUFFER, "need %d doubles", n);
-  memcpy(out, &c->res.last_moments[(size_t)w * n], (size_t)n * sizeof(double));
-  return n;
+  return copy_out(c, out, cap, &c->res.last_moments[(size_t)w * n], (size_t)n, "doubles");
 }
 
 // The text channel: the grammar (names, token counts, order rules) lives in pocs_command.hpp -- host only, fuzzed
@@ -783,7 +707,7 @@ int pocs_send_command(pocs_ctx* c, const char* line, char* out, size_t cap) {
     case pocs_cmd::kSetSeed: return pocs_set_seed(c, (uint64_t)p.seed);
     case pocs_cmd::kSetFootprint: return pocs_set_footprint(c, v[0], v[1], v[2], v[3]);
     case pocs_cmd::kAddObstacle: {
-      if (large_world(c)) return fail(c, POCS_E_ARG, "addObstacle: the world holds %d boxes (pocs_set_world); the text channel serves worlds of at most %d", large_boxes(c), POCS_MAX_OBSTACLES);
+      if (int r = may_enter(c, "addObstacle", pocs_modes::kAddObstacle)) return r;
       std::vector<double> b(c->boxes.begin(), c->boxes.begin() + (size_t)world_boxes(c) * 5);   // (under a schedule: world 0)
       b.insert(b.end(), v.begin(), v.end());
       return pocs_set_obstacles(c, b.data(), (int)(b.size() / 5));

@@ -5,9 +5,9 @@
 using namespace pocs_rt;
 
 // The batch slot that holds the selected run's data in the device buffers: the run itself, or -- the last launch of that
-// kind (0 GMM, 1 MC) was a call of plans -- the selected plan's slot.
-static size_t view_slot(const pocs_ctx* c, int kind) {
-  const std::vector<int>& ps = c->res.plan_slot[kind];
+// kind was a call of plans -- the selected plan's slot.
+static size_t view_slot(const pocs_ctx* c, Kind kind) {
+  const std::vector<int>& ps = c->res.plan_slot(kind);
   return (c->plans.n && (size_t)c->res.view < ps.size()) ? (size_t)ps[(size_t)c->res.view] : (size_t)c->res.view;
 }
 
@@ -43,7 +43,7 @@ int pocs_get_gmm_state(pocs_ctx* c, int w, double* means3, double* covs9, double
   const size_t row = (size_t)c->K * POCS_STATE_STRIDE;
   const double* src = nullptr;                       // the mixture's K rows on the device
   if (c->tree.n) {                                   // the mixture of the selected node's ancestor of depth w
-    if (c->res.tree_last != 1 || !c->d_state.p) return fail(c, POCS_E_ARG, "no mixture for waypoint %d: the last call was not a GMM call on the tree", w);
+    if (tree_last(c) != Kind::Gmm || !c->d_state.p) return fail(c, POCS_E_ARG, "no mixture for waypoint %d: the last call was not a GMM call on the tree", w);
     const int depth = c->tree.depth[(size_t)c->res.tree_sel];
     if (w < 0 || w > depth) return fail(c, POCS_E_ARG, "no mixture for waypoint %d: node %d has depth %d", w, c->res.tree_sel, depth);
     int v = c->res.tree_sel;
@@ -55,7 +55,7 @@ int pocs_get_gmm_state(pocs_ctx* c, int w, double* means3, double* covs9, double
     if (c->plans.n && w >= pocs_get_path_length(c)) return fail(c, POCS_E_ARG, "no mixture for waypoint %d: plan %d has %d waypoints", w, c->res.view, pocs_get_path_length(c));
     if (c->plans.n && (size_t)c->res.view < c->res.plan_E.size() && w >= c->res.plan_E[(size_t)c->res.view])
       return fail(c, POCS_E_ARG, "no mixture for waypoint %d: plan %d was stopped by the risk bound after %d waypoints", w, c->res.view, c->res.plan_E[(size_t)c->res.view]);
-    src = (double*)c->d_state.p + (view_slot(c, 0) * c->W + (size_t)w) * row;               // [run][W][K*16]
+    src = (double*)c->d_state.p + (view_slot(c, Kind::Gmm) * c->W + (size_t)w) * row;               // [run][W][K*16]
   }
   HIPCHK(c, hipSetDevice(c->device));
   std::vector<double> s(row);
@@ -74,7 +74,7 @@ int pocs_get_host_chain(pocs_ctx* c, double* applied3, double* noisy3, double* z
   if (!c) return POCS_E_ARG;
   const int steps = pocs_get_path_length(c) - 1, L = c->sensor.L;
   if (c->tree.n) {                                   // the chain of the path root -> the selected node, as a plan's
-    if (!c->res.tree_last) return fail(c, POCS_E_STATE, "no run yet");
+    if (tree_last(c) == Kind::None) return fail(c, POCS_E_STATE, "no run yet");
     const size_t W = (size_t)steps + 1, T = (size_t)c->tree.n;
     std::vector<double> traj(3 * W), odom(3 * (W > 1 ? W - 1 : 1));
     for (int v = c->res.tree_sel, w = steps; v >= 0; v = c->tree.parent[(size_t)v], --w)
@@ -110,7 +110,7 @@ long long pocs_copy_gmm_samples(pocs_ctx* c, double* aos, int16_t* flags, long l
   if (cap < n) return fail(c, POCS_E_BUFFER, "need room for %lld samples", n);
   if (hipSetDevice(c->device) != hipSuccess || hipStreamSynchronize(c->stream) != hipSuccess)
     return fail(c, POCS_E_DEVICE, "sync failed");
-  const size_t off = view_slot(c, 0) * (size_t)sample_stride_of(n);          // this run's slice
+  const size_t off = view_slot(c, Kind::Gmm) * (size_t)sample_stride_of(n);          // this run's slice
   if (aos && copy_soa_as_aos(c, c->d_sx, c->d_sy, c->d_st, off, n, aos) < 0) return fail(c, POCS_E_DEVICE, "copy failed");
   if (flags && copy_out(c, flags, (const int16_t*)c->d_flags.p + off, (size_t)n * sizeof(int16_t), 1, 0) != POCS_OK)
     return fail(c, POCS_E_DEVICE, "copy failed");
@@ -124,10 +124,10 @@ long long pocs_copy_particles(pocs_ctx* c, double* aos, uint32_t* hits, long lon
   if (cap < n) return fail(c, POCS_E_BUFFER, "need room for %lld particles", n);
   if (hipSetDevice(c->device) != hipSuccess || hipStreamSynchronize(c->stream) != hipSuccess)
     return fail(c, POCS_E_DEVICE, "sync failed");
-  size_t off = view_slot(c, 1) * (size_t)sample_stride_of(n);                // this run's slice
+  size_t off = view_slot(c, Kind::Mc) * (size_t)sample_stride_of(n);                // this run's slice
   if (c->tree.n) {                                   // a tree: the last two levels' clouds are still there; the deepest level's are served
     const int D = (int)c->tree.level.size() - 2;
-    if (c->res.tree_last != 2) return fail(c, POCS_E_STATE, "no particles: the last call was not an MC call on the tree");
+    if (tree_last(c) != Kind::Mc) return fail(c, POCS_E_STATE, "no particles: the last call was not an MC call on the tree");
     if (c->tree.depth[(size_t)c->res.tree_sel] != D)
       return fail(c, POCS_E_STATE, "particles of node %d (depth %d) are gone: an MC call on a tree keeps the clouds of its deepest level (%d)", c->res.tree_sel, c->tree.depth[(size_t)c->res.tree_sel], D);
     off = (size_t)(D & 1) * c->res.tree_mc_half + (size_t)(c->tree.slot[(size_t)c->res.tree_sel] - c->tree.level[(size_t)D]) * (size_t)sample_stride_of(n);
@@ -144,25 +144,25 @@ long long pocs_copy_particles(pocs_ctx* c, double* aos, uint32_t* hits, long lon
 int pocs_get_obstacle_counts(pocs_ctx* c, unsigned long long* out, int cap, int* boxes) {
   if (!c) return POCS_E_ARG;
   if (!out || !boxes) return fail(c, POCS_E_ARG, "pocs_get_obstacle_counts: null output");
-  const int kind = c->res.oc_kind;
-  if (!kind || kind != c->res.last_kind || !c->d_obsct.p)
+  const Kind kind = c->res.oc_kind;
+  if (kind == Kind::None || kind != c->res.last_kind || !c->d_obsct.p)
     return fail(c, POCS_E_STATE, "pocs_get_obstacle_counts: the last call ran without POCS_OPT_OBSTACLE_COUNTS (or there was none)");
   const size_t M = (size_t)c->res.oc_M, Wr = (size_t)c->res.oc_W, row = POCS_MAX_OBSTACLES;
   std::vector<size_t> rows;                          // the device rows ([slot * oc_W + w]) of the view's waypoints, in order
   if (c->tree.n) {
-    if (c->res.tree_last != kind) return fail(c, POCS_E_STATE, "pocs_get_obstacle_counts: the last call was not a call on the tree");
+    if (tree_last(c) != kind) return fail(c, POCS_E_STATE, "pocs_get_obstacle_counts: the last call was not a call on the tree");
     for (int v = c->res.tree_sel; v >= 0; v = c->tree.parent[(size_t)v])
-      if (kind == 2 || c->res.tree_eval[(size_t)v]) rows.push_back((size_t)c->tree.slot[(size_t)v]);      // (GMM under a bound: the evaluated part)
+      if (kind == Kind::Mc || c->res.tree_eval[(size_t)v]) rows.push_back((size_t)c->tree.slot[(size_t)v]);      // (GMM under a bound: the evaluated part)
     std::reverse(rows.begin(), rows.end());
   } else {
     const size_t r = (size_t)c->res.view;
     int E = (int)Wr;                                   // a plan's own length, or the waypoints before its stop
-    if (c->plans.n && r < c->res.plan_slot[kind - 1].size()) {
-      if (kind == 1) E = r < c->res.plan_E.size() ? c->res.plan_E[r] : c->plans.W[r];
+    if (c->plans.n && r < c->res.plan_slot(kind).size()) {
+      if (kind == Kind::Gmm) E = r < c->res.plan_E.size() ? c->res.plan_E[r] : c->plans.W[r];
       else E = c->res.plan_E_mc.empty() ? c->plans.W[r] : c->res.plan_E_mc[r];
     }
-    if (r >= (size_t)c->res.batch_R && kind == 1) return fail(c, POCS_E_STATE, "pocs_get_obstacle_counts: no run %zu in the last call", r);
-    const size_t slot = view_slot(c, kind - 1);
+    if (r >= (size_t)c->res.batch_R && kind == Kind::Gmm) return fail(c, POCS_E_STATE, "pocs_get_obstacle_counts: no run %zu in the last call", r);
+    const size_t slot = view_slot(c, kind);
     for (int w = 0; w < E; ++w) rows.push_back(slot * Wr + (size_t)w);
   }
   *boxes = (int)M;
@@ -253,8 +253,7 @@ int pocs_probe_device_collide(pocs_ctx* c, int K, const double* params, int n, c
     return fail(c, POCS_E_ARG, "pocs_probe_device_collide: 1 <= n <= 2^20, 1 <= K <= %d, no null pointers", POCS_MAX_GAUSSIANS);
   if (!c->have_obstacles)
     return fail(c, POCS_E_STATE, "no collision world: pocs_set_obstacles / addObstacle / clearObstacles missing");
-  if (large_world(c))
-    return fail(c, POCS_E_STATE, "pocs_probe_device_collide under a large world of %d boxes (pocs_set_world): the probe stages worlds of at most %d boxes", large_boxes(c), POCS_MAX_OBSTACLES);
+  if (int r = may_enter(c, "pocs_probe_device_collide", pocs_modes::kProbe)) return r;
   // (a heading that is not a number has no sector: nothing of the kind reaches the device)
   const size_t PS = (size_t)K * POCS_PARAM_STRIDE;
   for (size_t j = 0; j < PS; ++j)

@@ -5,6 +5,7 @@
 //   pocs_host.hip    the run paths: GMM and MC whole calls, their tree forms, the step and exchange API
 //   pocs_api.hip     context life cycle, setters, getters, run-ahead front, text dispatcher
 //   pocs_audit.hip   read-backs of device state for tests and audits, bandwidth and device-math probes, timing getters
+//   pocs_modes.hpp   the modes a context can be in and the table of the pairs that exclude each other (no HIP type)
 //
 // Host only: none of these units holds a kernel (pocs_kernels.hip does, with its parts pocs_dev_*.hpp).
 #pragma once
@@ -22,16 +23,24 @@
 
 #include "../../include/pocs.h"
 #include "pocs_kernels.h"
+#include "pocs_modes.hpp"
 
 // Everything internal to the host runtime lives in this namespace and stays out of the library's dynamic symbols.
 #define POCS_HIDDEN __attribute__((visibility("hidden")))
 
 namespace pocs_rt POCS_HIDDEN {
 
+// A device buffer the context owns: freed with the context (pocs_destroy selects the device first), grown by `ensure`.
 struct DevBuf {
   void* p = nullptr;
   size_t cap = 0;
+  DevBuf() = default;
+  DevBuf(const DevBuf&) = delete;
+  DevBuf& operator=(const DevBuf&) = delete;
+  ~DevBuf() { if (p) (void)hipFree(p); }
 };
+
+enum class Kind { None, Gmm, Mc };      // the estimator a call ran, a result belongs to, a cached run-ahead batch serves
 
 // candidate plans (pocs_set_plans): n > 0 = every run* call evaluates n plans, one run each, in one batch.  The context's W is
 // then the longest plan's length (the stride of every [run][W] array) and its batch = n; the single plan's length and
@@ -60,7 +69,7 @@ struct PlanTree {
 // Everything that describes the last call: what the getters serve.  A new set of plans and a call that fails after its launches
 // leave none of it (reset_results).
 struct Results {
-  int last_kind = 0;                     // what the last launch was: 1 GMM, 2 MC
+  Kind last_kind = Kind::None;           // what the last launch was (on a tree: what the last call on the tree was, tree_last)
   uint64_t batch_base = 0;               // run_index of run 0 of the last launch
   int batch_R = 1;                       // runs in the last launch
   int view = 0;                          // the run of the last launch the getters expose
@@ -73,12 +82,13 @@ struct Results {
   std::vector<double> batch_moments;     // [W][R][K*11] of the last GMM launch
   long long last_gmm_count = 0, last_mc_count = 0;
   int last_gmm_wp = -1;
-  std::vector<int> plan_slot[2];         // the batch slot of plan p in the last call of plans: [0] GMM, [1] MC
+  std::vector<int> plan_slot_[2];        // the batch slot of plan p in the last GMM / MC call of plans: through plan_slot(kind)
+  std::vector<int>& plan_slot(Kind k) { return plan_slot_[k == Kind::Mc]; }
+  const std::vector<int>& plan_slot(Kind k) const { return plan_slot_[k == Kind::Mc]; }
   std::vector<int> plan_E;               // [P] waypoints evaluated per plan in the last GMM call of plans (empty: there was none)
   std::vector<unsigned long long> mc_wp; // [R][mc_wp_W] first collisions per waypoint of the last MC call, in run / plan order (empty: the call ran without)
   int mc_wp_W = 0;
   std::vector<int> plan_E_mc;            // [P] waypoints evaluated per plan in the last MC call of plans under the bound (empty: every plan to its end)
-  int tree_last = 0;                     // what the last call on the tree was: 0 none, 1 GMM, 2 MC
   int tree_sel = 0;                      // the node the getters show (pocs_select_tree_node)
   std::vector<double> tree_probs;                 // [T] node order: running probability of the path root -> n
   std::vector<unsigned char> tree_eval;           // [T] 1 evaluated, 0 cut off below a stopped ancestor
@@ -86,7 +96,7 @@ struct Results {
   size_t tree_mc_half = 0;                        // MC: elements of one level's half of the particle buffers
   // per-obstacle collision counts (POCS_OPT_OBSTACLE_COUNTS): the table stays on the device ([slot][oc_W][POCS_MAX_OBSTACLES], d_obsct)
   // and pocs_get_obstacle_counts reads the selected run's rows; this is what the last call left there
-  int oc_kind = 0;                                // 0: the last call ran with the option off (or there was none); 1 GMM, 2 MC
+  Kind oc_kind = Kind::None;                      // None: the last call ran with the option off (or there was none)
   int oc_M = 0, oc_W = 0;                         // boxes of the call's world, rows per slot
 };
 
@@ -154,7 +164,7 @@ struct pocs_ctx {
   // of the context in one launch and the following calls are served from it (res.view: the one served last).
   int run_ahead = 1;
   int ra_have = 0;                       // runs of the last launch that may still be served (0: none)
-  int ra_kind = 0;                       // 1 GMM, 2 MC
+  pocs_rt::Kind ra_kind = pocs_rt::Kind::None;
   bool ra_internal = false;              // the last launch was an internal run-ahead batch
 
   pocs_rt::PlanSet plans;
@@ -253,7 +263,9 @@ inline int ensure(pocs_ctx* c, DevBuf& b, size_t bytes) {
   if (b.cap >= bytes) return POCS_OK;
   if (b.p) {
     HIPCHK(c, hipStreamSynchronize(c->stream));      // nothing queued may still use the old buffer
-    HIPCHK(c, hipFree(b.p)); b.p = nullptr; b.cap = 0;
+    void* old = b.p;
+    b.p = nullptr; b.cap = 0;                        // (before the free is checked: a DevBuf never keeps a pointer it does not own)
+    HIPCHK(c, hipFree(old));
   }
   HIPCHK(c, hipMalloc(&b.p, bytes));
   b.cap = bytes;
@@ -273,15 +285,15 @@ inline void touch(pocs_ctx* c) { ra_drop(c); c->epoch++; }
 // the calls' assign / resize then find their buffers still allocated.
 inline void reset_results(pocs_ctx* c) {
   Results& r = c->res;
-  r.last_kind = 0; r.batch_base = 0; r.batch_R = c->batch; r.view = 0;
+  r.last_kind = Kind::None; r.batch_base = 0; r.batch_R = c->batch; r.view = 0;
   r.h_chain.clear(); r.h_mu.clear(); r.h_cov.clear();
   r.probs.clear(); r.batch_probs.clear(); r.mc_counts.clear(); r.last_moments.clear(); r.batch_moments.clear();
   r.last_gmm_count = 0; r.last_mc_count = 0; r.last_gmm_wp = -1;
-  r.plan_slot[0].clear(); r.plan_slot[1].clear(); r.plan_E.clear();
+  r.plan_slot(Kind::Gmm).clear(); r.plan_slot(Kind::Mc).clear(); r.plan_E.clear();
   r.mc_wp.clear(); r.mc_wp_W = 0; r.plan_E_mc.clear();
-  r.tree_last = 0; r.tree_sel = 0; r.tree_mc_half = 0;
+  r.tree_sel = 0; r.tree_mc_half = 0;
   r.tree_probs.clear(); r.tree_eval.clear(); r.tree_F.clear(); r.tree_C.clear();
-  r.oc_kind = 0; r.oc_M = 0; r.oc_W = 0;
+  r.oc_kind = Kind::None; r.oc_M = 0; r.oc_W = 0;
 }
 
 // The collision world: M boxes per step, and the record of the device's env array ([world_S] pocs_env_dev) that waypoint w --
@@ -293,8 +305,30 @@ inline const pocs_env_dev* world_at(const pocs_ctx* c, int w) {
 
 // A large world is in force (pocs_set_world with more than POCS_MAX_OBSTACLES boxes), and its number of boxes.
 static_assert(POCS_MAX_WORLD_RECORDS == POCS_MAX_WORLD_BOXES, "pocs_kernels.h restates the public limit");
-inline bool large_world(const pocs_ctx* c) { return !c->world.empty(); }
 inline int large_boxes(const pocs_ctx* c) { return (int)(c->world.size() / 5); }
+
+// The modes a context is in (pocs_modes.hpp), as a bit word: the one place that says what "plans are set" and the others mean.
+inline unsigned modes_of(const pocs_ctx* c) {
+  using namespace pocs_modes;
+  return (c->plans.n > 0 ? kPlans : 0u) | (c->tree.n > 0 ? kTree : 0u) | (c->shard_first >= 0 ? kShard : 0u) |
+         (c->xchg_own ? kXchgCreated : 0u) | (c->xchg_connected ? kXchgConnected : 0u) | (c->ext_moments ? kMoments : 0u) |
+         (!c->world.empty() ? kLargeWorld : 0u) | (c->opt_obs_counts ? kObsCounts : 0u) | (c->opt_fused ? kFused : 0u) |
+         (c->gmm_open ? kSequence : 0u);
+}
+inline bool in_mode(const pocs_ctx* c, unsigned any_of) { return (modes_of(c) & any_of) != 0; }
+inline bool large_world(const pocs_ctx* c) { return in_mode(c, pocs_modes::kLargeWorld); }
+
+// May the context enter `enter`, as asked by the call `what`?  The one place that refuses a combination (pocs_modes.hpp).
+inline int may_enter(pocs_ctx* c, const char* what, pocs_modes::Mode enter, unsigned among = pocs_modes::kAll) {
+  const pocs_modes::Refusal r = pocs_modes::refusal(modes_of(c), enter, among);
+  if (r.code == POCS_OK) return POCS_OK;
+  char clause[200];
+  snprintf(clause, sizeof clause, r.clause, POCS_MAX_OBSTACLES);
+  return fail(c, r.code, "%s: %s; %s", what, pocs_modes::name(r.by), clause);
+}
+
+// What the last call on the tree was: last_kind (a failed call, entering and leaving a tree all go through reset_results).
+inline Kind tree_last(const pocs_ctx* c) { return c->tree.n ? c->res.last_kind : Kind::None; }
 
 inline double* moments_dev(pocs_ctx* c) { return c->ext_moments ? c->ext_moments : (double*)c->d_moments.p; }
 inline long long sample_stride_of(long long count) { return count > 0 ? ((count + 1) & ~1LL) : 2; }   // even
@@ -315,7 +349,7 @@ std::vector<int> slot_lengths(const pocs_ctx* c, const std::vector<int>& slot_pl
 int live_runs(const std::vector<int>& Ws, int lo, int hi, int w);
 uint64_t plan_run(const pocs_ctx* c, int p);
 void prefetch_next_batch(pocs_ctx* c, int groups);
-int stage_and_upload_runs(pocs_ctx* c, int groups, int kind);
+int stage_and_upload_runs(pocs_ctx* c, int groups, Kind kind);
 
 // ---- pocs_host.hip ----
 int upload_tables(pocs_ctx* c);

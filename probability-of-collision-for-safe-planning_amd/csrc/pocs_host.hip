@@ -236,9 +236,9 @@ int enqueue_obs_counts_reset(Issuer is) {
   if (!c->opt_obs_counts) return POCS_OK;
   return is.launch(pocs_launch_zero_counts, 0, (unsigned long long*)c->d_obsct.p, obs_count_words(c));
 }
-// what the getter needs to know of the call that has just filled the table (kind: 1 GMM, 2 MC; 0 with the option off)
-void note_obs_counts(pocs_ctx* c, int kind) {
-  c->res.oc_kind = c->opt_obs_counts ? kind : 0;
+// what the getter needs to know of the call that has just filled the table (None with the option off)
+void note_obs_counts(pocs_ctx* c, Kind kind) {
+  c->res.oc_kind = c->opt_obs_counts ? kind : Kind::None;
   c->res.oc_M = world_boxes(c);
   c->res.oc_W = c->W > 0 ? c->W : 1;
 }
@@ -325,7 +325,7 @@ int gmm_groups(const pocs_ctx* c) {
 }
 
 int gmm_upload_run(pocs_ctx* c) {
-  if (int r = stage_and_upload_runs(c, gmm_groups(c), 0)) return r;
+  if (int r = stage_and_upload_runs(c, gmm_groups(c), Kind::Gmm)) return r;
   const PinLayout pl = pin_layout(c);
   double* pin = (double*)c->h_pin;
   const int W = c->W, R = c->batch;
@@ -575,13 +575,13 @@ int gmm_check_gave_up(pocs_ctx* c, const char* what) {
 // it leaves stays readable.
 int gmm_read_reach(pocs_ctx* c) {
   const int R = c->batch, W = c->W;
-  const bool plans = c->plans.n && !c->res.plan_slot[0].empty();
+  const bool plans = c->plans.n && !c->res.plan_slot(Kind::Gmm).empty();
   const std::vector<int> by_slot = c->reach;
   c->reach_R = R; c->reach_W = W;
   c->reach_len.assign((size_t)R, W);
   int bad_w = -1, bad_n = 0, bad_r = 0;
   for (int r = 0; r < R; ++r) {
-    const int slot = plans ? c->res.plan_slot[0][(size_t)r] : r;
+    const int slot = plans ? c->res.plan_slot(Kind::Gmm)[(size_t)r] : r;
     if (plans) c->reach_len[(size_t)r] = c->plans.W[(size_t)r];
     for (int w = 0; w < W; ++w) {
       const int n = by_slot[(size_t)slot * W + w];
@@ -607,10 +607,10 @@ double waypoint_probability(const double* row, int K, long long n) {
 // The getters' view of the last GMM launch: per-waypoint probabilities and moments of run v.
 // (a call of plans: v is the plan, which the moments hold in its batch slot, over its own W_p waypoints)
 void gmm_select_view(pocs_ctx* c, int v) {
-  const bool plans = c->plans.n && !c->res.plan_slot[0].empty();
+  const bool plans = c->plans.n && !c->res.plan_slot(Kind::Gmm).empty();
   // (a plan stopped by the risk bound: its E[v] evaluated waypoints -- what lies behind them is whatever an earlier call left)
   const int W = plans ? ((size_t)v < c->res.plan_E.size() ? c->res.plan_E[(size_t)v] : c->plans.W[(size_t)v]) : c->W, K = c->K, R = c->res.batch_R;
-  const int slot = plans ? c->res.plan_slot[0][(size_t)v] : v;
+  const int slot = plans ? c->res.plan_slot(Kind::Gmm)[(size_t)v] : v;
   c->res.view = v;
   c->res.probs.assign(W, 0.0);
   c->res.last_moments.assign((size_t)W * K * POCS_NMOM, 0.0);
@@ -651,7 +651,7 @@ void tree_select_gmm(pocs_ctx* c, int n) {
 int gmm_combine_tree(pocs_ctx* c, const double* moments, double* probability, const unsigned* stop) {
   const int T = c->tree.n, K = c->K;
   c->res.batch_R = T;
-  c->res.last_kind = 1;
+  c->res.last_kind = Kind::Gmm;
   c->res.batch_moments.assign(moments, moments + (size_t)T * K * POCS_NMOM);
   c->res.plan_E.clear();
   c->res.tree_probs.assign((size_t)T, 0.0);
@@ -681,7 +681,6 @@ int gmm_combine_tree(pocs_ctx* c, const double* moments, double* probability, co
     c->res.tree_probs[(size_t)n] = 1.0 - pr;
   }
   c->res.batch_probs.assign(1, c->res.tree_probs[0]);
-  c->res.tree_last = 1;
   c->res.view = 0;
   tree_select_gmm(c, 0);
   *probability = c->res.tree_probs[0];
@@ -692,13 +691,13 @@ int gmm_combine(pocs_ctx* c, const double* moments, double* probability, const u
   if (c->tree.n) return gmm_combine_tree(c, moments, probability, stop);
   const int W = c->W, K = c->K, R = c->batch;          // moments: [W][R][K*11]
   c->res.batch_R = R;
-  c->res.last_kind = 1;
+  c->res.last_kind = Kind::Gmm;
   c->res.batch_moments.assign(moments, moments + (size_t)W * R * K * POCS_NMOM);
   c->res.batch_probs.assign(R, 0.0);
-  const bool plans = c->plans.n && !c->res.plan_slot[0].empty();
+  const bool plans = c->plans.n && !c->res.plan_slot(Kind::Gmm).empty();
   if (plans) c->res.plan_E = c->plans.W; else c->res.plan_E.clear();
   for (int r = 0; r < R; ++r) {                        // (a call of plans: r is the plan, in its slot, over its W_p waypoints)
-    const int slot = plans ? c->res.plan_slot[0][(size_t)r] : r, Wr = plans ? c->plans.W[(size_t)r] : W;
+    const int slot = plans ? c->res.plan_slot(Kind::Gmm)[(size_t)r] : r, Wr = plans ? c->plans.W[(size_t)r] : W;
     const int dev = stop ? (int)stop[(size_t)slot] : 0;
     if (dev < 0 || dev > Wr) return fail(c, POCS_E_DEVICE, "risk bound: the device stopped plan %d at waypoint %d of %d; results discarded", r, dev - 1, Wr);
     const int Er = dev ? dev : Wr;
@@ -729,7 +728,7 @@ int run_gmm_full(pocs_ctx* c, double* probability) {
 #else
   auto lap = [](const char*) {};
 #endif
-  c->res.oc_kind = 0;                                  // (the per-obstacle table is rewritten from here on; noted again behind the combine)
+  c->res.oc_kind = Kind::None;                                  // (the per-obstacle table is rewritten from here on; noted again behind the combine)
   c->reach.clear(); c->reach_len.clear(); c->reach_R = 0; c->reach_W = 0;      // (pocs_get_world_reach covers the last GMM call)
   if (int r = gmm_prepare(c)) return r;
   long long first, count;
@@ -767,7 +766,7 @@ int run_gmm_full(pocs_ctx* c, double* probability) {
   const unsigned* stop = risk_active(c) ? (const unsigned*)((double*)c->h_pin + c->sync.pin) + (c->sync.stop - POCS_SYNC_ABORT) : nullptr;
   if (large_world(c)) if (int r = gmm_read_reach(c)) { reset_results(c); return r; }
   if (int r = gmm_combine(c, (double*)c->h_pin + pin_layout(c).moments, probability, stop)) { reset_results(c); return r; }
-  note_obs_counts(c, 1);
+  note_obs_counts(c, Kind::Gmm);
   c->res.last_gmm_count = count;
   c->res.last_gmm_wp = c->W - 1;
   lap("combined");
@@ -889,7 +888,7 @@ int mc_read_waypoint_counts(pocs_ctx* c, const unsigned long long* words) {
   if (stop) c->res.plan_E_mc = c->plans.W;
   const double n = (double)c->num_particles;
   for (size_t r = 0; r < R; ++r) {                     // (a call of plans: r is the plan, in its slot, over its W_p waypoints)
-    const size_t slot = plans ? (size_t)c->res.plan_slot[1][r] : r, Wr = plans ? (size_t)c->plans.W[r] : W;
+    const size_t slot = plans ? (size_t)c->res.plan_slot(Kind::Mc)[r] : r, Wr = plans ? (size_t)c->plans.W[r] : W;
     const unsigned long long* f = F + slot * W;
     unsigned long long C = 0;
     int host = 0;                                      // the host's stop word
@@ -973,7 +972,7 @@ int mc_prepare(pocs_ctx* c, size_t runs, size_t chain_rows, size_t elems, size_t
   if (int r = ensure(c, c->d_total, total_bytes + 16)) return r;
   if (int r = ensure_obs_counts(c)) return r;
   if (int r = ensure_pin(c)) return r;
-  return stage_and_upload_runs(c, 1, 1);
+  return stage_and_upload_runs(c, 1, Kind::Mc);
 }
 template <class Enqueue>
 int mc_run(pocs_ctx* c, size_t total_bytes, bool span, const unsigned long long** tot, Enqueue enqueue) {
@@ -1019,16 +1018,15 @@ int run_mc_tree(pocs_ctx* c) {                      // (behind run_mc_local's ch
   }
   c->res.mc_counts.assign(1, c->res.tree_C[0]);
   c->res.last_mc_count = count;
-  c->res.last_kind = 2;
-  c->res.tree_last = 2;
+  c->res.last_kind = Kind::Mc;
   c->res.tree_sel = 0;
-  note_obs_counts(c, 2);
+  note_obs_counts(c, Kind::Mc);
   return POCS_OK;
 }
 
 // One batch of MC roll-outs (runSimulation x batch) over this context's shard; fills c->res.mc_counts.
 int run_mc_local(pocs_ctx* c) {
-  c->res.oc_kind = 0;
+  c->res.oc_kind = Kind::None;
   if (int r = check_common(c)) return r;
   if (c->num_particles < 1) return fail(c, POCS_E_STATE, "setNumParticles missing");
   if (int r = upload_static(c)) return r;
@@ -1055,14 +1053,14 @@ int run_mc_local(pocs_ctx* c) {
   memcpy(c->res.mc_counts.data(), tot, R * sizeof(unsigned long long));
   if (c->plans.n) {                                     // slot order -> the caller's plan order
     const std::vector<unsigned long long> by_slot = c->res.mc_counts;
-    for (size_t p = 0; p < R; ++p) c->res.mc_counts[p] = by_slot[(size_t)c->res.plan_slot[1][p]];
+    for (size_t p = 0; p < R; ++p) c->res.mc_counts[p] = by_slot[(size_t)c->res.plan_slot(Kind::Mc)[p]];
   }
   c->res.last_mc_count = count;
-  c->res.last_kind = 2;
+  c->res.last_kind = Kind::Mc;
   c->res.mc_wp.clear(); c->res.plan_E_mc.clear();
   if (mc_counts_active(c))
     if (int r = mc_read_waypoint_counts(c, tot)) { reset_results(c); return r; }
-  note_obs_counts(c, 2);
+  note_obs_counts(c, Kind::Mc);
   return POCS_OK;
 }
 
@@ -1090,9 +1088,7 @@ static int step_api_sample(pocs_ctx* c, int w, bool exchange) {
 
 int pocs_gmm_begin(pocs_ctx* c) {
   if (!c) return POCS_E_ARG;
-  if (c->plans.n) return fail(c, POCS_E_STATE, "pocs_gmm_begin: plans are set (the step API serves a single plan)");
-  if (c->tree.n) return fail(c, POCS_E_STATE, "pocs_gmm_begin: a tree of plans is set (the step API serves a single plan)");
-  if (large_world(c)) return fail(c, POCS_E_STATE, "pocs_gmm_begin: a large world of %d boxes is set (pocs_set_world): the step API serves worlds of at most %d boxes", large_boxes(c), POCS_MAX_OBSTACLES);
+  if (int r = may_enter(c, "pocs_gmm_begin", pocs_modes::kSequence)) return r;
   HIPCHK(c, hipSetDevice(c->device));
   ra_drop(c);
   c->ra_internal = false;
@@ -1101,7 +1097,7 @@ int pocs_gmm_begin(pocs_ctx* c) {
   if (int r = prof_begin(c, (size_t)c->W)) return r;
   if (int r = enqueue_ticket_reset(c)) return r;
   if (int r = enqueue_obs_counts_reset({c, nullptr})) return r;
-  c->res.oc_kind = 0;                                 // (the table is this sequence's from here on; served once pocs_gmm_end has closed it)
+  c->res.oc_kind = Kind::None;                                 // (the table is this sequence's from here on; served once pocs_gmm_end has closed it)
   c->xchg_calls += 1;
   c->gmm_open = true;
   c->res.last_gmm_wp = -1;
@@ -1180,7 +1176,7 @@ int pocs_gmm_end(pocs_ctx* c, double* probability) {
   if (int r = gmm_check_gave_up(c, "a bounded wait expired on the device (code %u: 4 = a peer's moments never arrived); results discarded")) { c->gmm_open = false; return r; }
   if (int r = prof_collect(c, (size_t)c->W)) return r;
   (void)gmm_combine(c, (double*)c->h_pin + pin_layout(c).moments, probability);      // (no risk bound in the step API: cannot fail)
-  note_obs_counts(c, 1);
+  note_obs_counts(c, Kind::Gmm);
   c->gmm_open = false;
   return POCS_OK;
 }

@@ -272,8 +272,8 @@ void prefetch_next_batch(pocs_ctx* c, int groups) {
 
 // Host image of this call's batch into the pinned staging area (from the look-ahead cache when it
 // matches), run counter advanced; then the uploads every path needs: headers and chains (and, for a call of
-// plans, the runs' start rows).  `groups`: the call's sub-batches; `kind`: 0 GMM, 1 MC (whose plan layout it records).
-int stage_and_upload_runs(pocs_ctx* c, int groups, int kind) {
+// plans, the runs' start rows).  `groups`: the call's sub-batches; `kind`: the estimator whose plan layout it records.
+int stage_and_upload_runs(pocs_ctx* c, int groups, Kind kind) {
   const PinLayout pl = pin_layout(c);
   double* pin = (double*)c->h_pin;
   const int W = c->W, R = c->batch;
@@ -294,7 +294,7 @@ int stage_and_upload_runs(pocs_ctx* c, int groups, int kind) {
   c->res.view = 0;
   c->run_index += (c->plans.n && c->opt_plan_seeds) || c->tree.n ? 1 : (uint64_t)R;      // (a tree: one stream for all its nodes)
   if (c->plans.n) {
-    std::vector<int>& ps = c->res.plan_slot[kind];
+    std::vector<int>& ps = c->res.plan_slot(kind);
     ps.assign((size_t)R, 0);
     for (int r = 0; r < R; ++r) ps[(size_t)slot_plan[(size_t)r]] = r;
     HIPCHK(c, hipMemcpyAsync(c->d_runplan.p, pin + pl.runplan, (size_t)R * 4 * sizeof(double), hipMemcpyHostToDevice, c->stream));
