@@ -408,6 +408,50 @@ int pocs_mc_get_waypoint_counts(pocs_ctx* ctx, unsigned long long* out, int cap)
  * touched since, or there was no call); POCS_E_ARG for null pointers.  Every call shape serves it: none is refused. */
 int pocs_get_obstacle_counts(pocs_ctx* ctx, unsigned long long* out, int cap, int* boxes);
 
+/* ---- clearance levels: near-miss counts per waypoint, for both estimators (ours) ----------------
+ * How CLOSE a plan comes, out of the samples a call draws anyway.  For clearances 0 < d_0 < d_1 < ... (at most
+ * POCS_MAX_CLEARANCE_LEVELS of them):
+ *   grown footprint     the footprint grown by d is {dx, dy, half_x + d, half_y + d}: one IEEE addition per half extent;
+ *   within clearance d  a pose is within clearance d of a world exactly when the collision test answers "touches" for the grown
+ *                       footprint against that world, touching included.  (The grown box is the definition: no Euclidean distance.)
+ *   nesting             every margin of the test is a monotone function of the half extents: a pose within d is within every
+ *                       larger d, and a pose that collides is within every clearance.
+ * pocs_set_clearance_levels: 0 <= L <= POCS_MAX_CLEARANCE_LEVELS finite distances, 0 < d[0] < d[1] < ...; L = 0 (the default) is
+ * off.  POCS_E_ARG otherwise, and the levels in force stay.  The levels belong to the context: they survive pocs_set_plans and
+ * pocs_set_footprint (which re-prepares what depends on the footprint).  Like every setter it ends run-ahead serving.  The text
+ * channel has no command for it.
+ *
+ * Where the levels are APPLIED: whole calls on one GPU -- pocs_run_gmm_estimation, pocs_run_simulation (pocs_mc_run_local) -- as
+ * single runs, batches in both sub-batch forms, run-ahead, calls of plans with and without the risk bound, over static worlds of up
+ * to 64 boxes and obstacle schedules.  A GMM call of one run then takes the ticket form (POCS_OPT_LONE_CALL has no effect, as
+ * under a large world), an MC call the per-step form whatever POCS_OPT_MC_FUSED says (as under the MC risk bound).  No other
+ * result of any call changes by a bit.  NOT applied -- never refused: a tree of plans, a large world (pocs_set_world with more than
+ * 64 boxes), POCS_OPT_OBSTACLE_COUNTS = 1, a shard (with it a bound moments buffer and the exchange) and the step API: there the call
+ * is launch for launch and bit for bit the call it is with L = 0, and the two getters below answer POCS_E_STATE.
+ *
+ * pocs_get_clearance_counts serves the selected run (pocs_select_batch_run; plan p while plans are set; the run served last under
+ * run-ahead): writes the table A, E x L row-major, sets *levels = L and returns E, the waypoints covered -- a plan's own length, or
+ * the waypoints before its stop under a risk bound (GMM, or MC with POCS_OPT_MC_RISK_BOUND).
+ *   GMM  A[w][l] = the samples drawn at waypoint w that are within clearance d_l of the world at w (world min(w, S - 1) under a
+ *        schedule).  The colliding samples are included: collisions at w <= A[w][0] <= ... <= A[w][L-1] <= N.
+ *   MC   A[w][l] = the particles that are within clearance d_l at waypoint w and at no waypoint before it: the first-collision
+ *        profile of pocs_mc_get_waypoint_counts as it would be for the grown footprint on the same cloud.
+ * POCS_E_BUFFER for cap < E * L, POCS_E_ARG for null pointers, POCS_E_STATE -- the message says which -- when there was no call, L
+ * was 0, a setter touched the levels since, or the last call is one the levels are not applied to.
+ * pocs_get_batch_clearance_probabilities(level): per run / plan of the last call, in run / plan order (after a run-ahead batch:
+ * the run served last),
+ *   GMM  1 - prod_w (1 - A[w][level] / N), formed exactly as the final probability is formed from the collision counts: the
+ *        division, the product in waypoint order, IEEE double.  NOTE what this number is: the samples of waypoint w are drawn
+ *        from the mixture truncated by COLLISIONS before w, not by near misses -- it is the probability of the same estimator with
+ *        "within d_level" counted in place of "collides" at every waypoint on the belief the collision estimate propagates, NOT
+ *        the collision probability of the grown footprint (whose belief would be truncated differently);
+ *   MC   (sum_w A[w][level]) / N, one IEEE division: exactly the collision probability of the grown footprint on this cloud. */
+#define POCS_MAX_CLEARANCE_LEVELS 4
+int pocs_set_clearance_levels(pocs_ctx* ctx, const double* d, int L);
+int pocs_get_clearance_levels(const pocs_ctx* ctx, double* d, int cap);     /* writes and returns L */
+int pocs_get_clearance_counts(pocs_ctx* ctx, unsigned long long* out, int cap, int* levels);
+int pocs_get_batch_clearance_probabilities(pocs_ctx* ctx, int level, double* out, int cap);
+
 /* ---- results of the last run, for audits and parity tests ------------------------------- */
 int pocs_get_path_length(const pocs_ctx* ctx);
 int pocs_get_waypoint_probabilities(pocs_ctx* ctx, double* out, int cap);         /* `probabilities`, MCSimulator.h:660,678,817 */
@@ -452,6 +496,16 @@ int pocs_probe_device_collide(pocs_ctx* ctx, int K, const double* params, int n,
    free-running launch never draws -- a few ulps from touching, at the edge of the mixture's reach -- in front of the oracle
    (tests/test_collision_probe.py).  POCS_E_ARG for a null pointer, n or K out of range and ANY input that is not finite;
    POCS_E_STATE for a context without a collision world. */
+int pocs_probe_device_clearance(pocs_ctx* ctx, const double* fp4, const double* d, int L, const double* boxes, int M,
+                                int n, const double* poses_xyt, int* level_out);
+/* TEST HOOK beside pocs_probe_device_collide: the DEVICE's clearance level of poses the caller picks, for the caller's own footprint
+   fp4 = {dx, dy, half_x, half_y}, distances d[0 .. L) (0 <= L <= POCS_MAX_CLEARANCE_LEVELS, as pocs_set_clearance_levels takes them)
+   and table of M <= 64 boxes {cx, cy, half_x, half_y, yaw_rad}, prepared as the library prepares the context's.  One small launch
+   stages them; per pose i < n it writes the smallest l whose grown footprint touches: -1 for the footprint itself, L for none --
+   through the inline functions the kernels use (the single-pose form of the MC kernels, and the two-pose lane-mask form of the GMM
+   sampling kernel on poses 2 j, 2 j + 1: 100 is added should the two ever disagree).  It reads nothing of the context's world,
+   plans or modes, so it is never refused.  POCS_E_ARG for a null pointer, n outside 1 .. 2^20, bad distances or boxes and ANY
+   input that is not finite. */
 int pocs_get_sequence_time(pocs_ctx* ctx, double* ms, int* concurrent);  /* POCS_OPT_PROFILE=1, whole-run GMM calls: first sampling launch -> end of the last one, and how many
                                                                             sub-batches of the call were in flight side by side (their launches overlap: DESIGN.md section 5) */
 

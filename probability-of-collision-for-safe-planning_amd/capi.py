@@ -22,6 +22,7 @@ MAX_PLANS = 256
 MAX_TREE_NODES = 4096
 MAX_WORLD_STEPS = 4096
 MAX_WORLD_BOXES = 4096             # POCS_MAX_WORLD_BOXES: the largest table pocs_set_world takes
+MAX_CLEARANCE_LEVELS = 4           # POCS_MAX_CLEARANCE_LEVELS: the most distances pocs_set_clearance_levels takes
 
 _dp = C.POINTER(C.c_double)
 _vp = C.c_void_p
@@ -80,6 +81,11 @@ SIGNATURES = {
     "pocs_mc_get_batch_counts": (C.c_int, [_vp, C.POINTER(C.c_ulonglong), C.c_int]),
     "pocs_mc_get_waypoint_counts": (C.c_int, [_vp, C.POINTER(C.c_ulonglong), C.c_int]),
     "pocs_get_obstacle_counts": (C.c_int, [_vp, C.POINTER(C.c_ulonglong), C.c_int, C.POINTER(C.c_int)]),
+    "pocs_set_clearance_levels": (C.c_int, [_vp, _dp, C.c_int]),
+    "pocs_get_clearance_levels": (C.c_int, [_vp, _dp, C.c_int]),
+    "pocs_get_clearance_counts": (C.c_int, [_vp, C.POINTER(C.c_ulonglong), C.c_int, C.POINTER(C.c_int)]),
+    "pocs_get_batch_clearance_probabilities": (C.c_int, [_vp, C.c_int, _dp, C.c_int]),
+    "pocs_probe_device_clearance": (C.c_int, [_vp, _dp, _dp, C.c_int, _dp, C.c_int, C.c_int, _dp, C.POINTER(C.c_int)]),
     "pocs_xchg_create": (C.c_int, [_vp, C.c_int, C.c_int, C.c_void_p]),
     "pocs_xchg_connect": (C.c_int, [_vp, C.c_void_p, C.c_int]),
     "pocs_gmm_exchange_local": (C.c_int, [_vp, C.c_int]),
@@ -462,6 +468,49 @@ class Context:
         M = C.c_int(0)
         got = self._chk(self.lib.pocs_get_obstacle_counts(self.h, out.ctypes.data_as(C.POINTER(C.c_ulonglong)), out.size, C.byref(M)))
         return out[:got * M.value].reshape(got, M.value)
+
+    def set_clearance_levels(self, d):
+        """Clearance levels 0 < d[0] < d[1] < ... (at most MAX_CLEARANCE_LEVELS; an empty list turns them off): whole calls on one
+        GPU then also count, per waypoint and level, the poses that pass within d of an obstacle (include/pocs.h)."""
+        d = _arr(d).ravel()
+        self._chk(self.lib.pocs_set_clearance_levels(self.h, d.ctypes.data_as(_dp) if d.size else None, d.size))
+
+    def clearance_levels(self):
+        """The distances in force (float64 array; empty: off)."""
+        out = np.zeros(MAX_CLEARANCE_LEVELS)
+        got = self._chk(self.lib.pocs_get_clearance_levels(self.h, out.ctypes.data_as(_dp), out.size))
+        return out[:got]
+
+    def clearance_counts(self):
+        """Near-miss counts of the current selection (run or plan) of the last call under clearance levels: an (E, L) uint64
+        array, entry [w, l] = samples at waypoint w within clearance d_l (GMM), or particles within d_l at w and at no waypoint
+        before (MC); include/pocs.h."""
+        E = max(self.path_length(), 1)
+        out = np.zeros(E * MAX_CLEARANCE_LEVELS, dtype=np.uint64)
+        L = C.c_int(0)
+        got = self._chk(self.lib.pocs_get_clearance_counts(self.h, out.ctypes.data_as(C.POINTER(C.c_ulonglong)), out.size, C.byref(L)))
+        return out[:got * L.value].reshape(got, L.value)
+
+    def clearance_probabilities(self, level):
+        """Per run / plan of the last call: the estimator's probability with "within d_level" in place of "collides"."""
+        n = getattr(self, "_batch", 1)
+        out = np.zeros(n)
+        got = self._chk(self.lib.pocs_get_batch_clearance_probabilities(self.h, int(level), out.ctypes.data_as(_dp), n))
+        return out[:got]
+
+    def probe_device_clearance(self, footprint, d, boxes, poses):
+        """Test hook: the device's clearance level of poses (n x 3) for a footprint (dx, dy, hx, hy), distances d and boxes (M x 5) of
+        the caller's own: int32[n], -1 the footprint itself touches, else the smallest level whose grown footprint does, len(d) for none."""
+        fp = _arr(footprint).ravel()
+        d = _arr(d).ravel()
+        b = _arr(boxes).reshape(-1, 5)
+        xyt = _arr(poses).reshape(-1, 3)
+        assert fp.size == 4
+        out = np.full(xyt.shape[0], -99, dtype=np.int32)
+        self._chk(self.lib.pocs_probe_device_clearance(self.h, fp.ctypes.data_as(_dp), d.ctypes.data_as(_dp) if d.size else None, d.size,
+                                                       b.ctypes.data_as(_dp) if b.size else None, b.shape[0], xyt.shape[0],
+                                                       xyt.ctypes.data_as(_dp), out.ctypes.data_as(C.POINTER(C.c_int))))
+        return out
 
     def gmm_begin(self):
         self._chk(self.lib.pocs_gmm_begin(self.h))

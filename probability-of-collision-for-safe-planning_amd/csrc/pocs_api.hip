@@ -540,6 +540,98 @@ int pocs_select_tree_node(pocs_ctx* c, int node) {
   return POCS_OK;
 }
 
+// ---- clearance levels (include/pocs.h) ----
+static int check_clearance_levels(pocs_ctx* c, const char* what, const double* d, int L) {
+  if (L < 0 || L > POCS_MAX_CLEARANCE_LEVELS || (L > 0 && !d)) return fail(c, POCS_E_ARG, "%s: %d levels outside 0..%d (or null distances)", what, L, POCS_MAX_CLEARANCE_LEVELS);
+  for (int l = 0; l < L; ++l)
+    if (!std::isfinite(d[l]) || !(d[l] > (l ? d[l - 1] : 0.0)))
+      return fail(c, POCS_E_ARG, "%s: distance %d (%g): finite distances with 0 < d[0] < d[1] < ... are needed", what, l, d[l]);
+  return POCS_OK;
+}
+
+int pocs_set_clearance_levels(pocs_ctx* c, const double* d, int L) {
+  if (!setter(c)) return POCS_E_ARG;
+  if (int r = check_clearance_levels(c, "pocs_set_clearance_levels", d, L)) return r;
+  c->clr_L = L;
+  for (int l = 0; l < POCS_MAX_CLEARANCE_LEVELS; ++l) c->clr_d[l] = l < L ? d[l] : 0.0;
+  c->env_dirty = true;                               // (the second record set and the distances live beside the world on the device)
+  if (c->res.cl_state != Results::ClNoCall) c->res.cl_state = Results::ClTouched;      // (a table is served until the levels are touched or the next call)
+  return POCS_OK;
+}
+
+int pocs_get_clearance_levels(const pocs_ctx* c, double* d, int cap) {
+  if (!c) return POCS_E_ARG;
+  if (c->clr_L > 0 && (!d || cap < c->clr_L)) return POCS_E_BUFFER;
+  for (int l = 0; l < c->clr_L; ++l) d[l] = c->clr_d[l];
+  return c->clr_L;
+}
+
+// The table of the last call serves `what`?  POCS_E_STATE with the reason otherwise.
+static int clearance_served(pocs_ctx* c, const char* what) {
+  const Results& r = c->res;
+  switch (r.cl_state) {
+    case Results::ClServed: break;
+    case Results::ClNoCall: return fail(c, POCS_E_STATE, "%s: there was no call yet", what);
+    case Results::ClOff: return fail(c, POCS_E_STATE, "%s: the last call ran without clearance levels (L was 0)", what);
+    case Results::ClTouched: return fail(c, POCS_E_STATE, "%s: pocs_set_clearance_levels touched the levels since the last call", what);
+    default: return fail(c, POCS_E_STATE, "%s: the levels are not applied to the last call (a tree of plans, a large world, POCS_OPT_OBSTACLE_COUNTS, a shard, the step API -- or it failed)", what);
+  }
+  if (r.cl_kind == Kind::None || r.cl_kind != r.last_kind || r.cl_counts.empty()) return fail(c, POCS_E_STATE, "%s: there was no call yet", what);
+  return POCS_OK;
+}
+// run / plan r of the last call: its batch slot and the waypoints its rows cover
+static void clearance_rows(const pocs_ctx* c, size_t r, size_t* slot, int* E) {
+  const Kind kind = c->res.cl_kind;
+  *slot = r; *E = c->res.cl_W;
+  if (c->plans.n && r < c->res.plan_slot(kind).size()) {
+    *slot = (size_t)c->res.plan_slot(kind)[r];
+    if (kind == Kind::Gmm) *E = r < c->res.plan_E.size() ? c->res.plan_E[r] : c->plans.W[r];
+    else *E = c->res.plan_E_mc.empty() ? c->plans.W[r] : c->res.plan_E_mc[r];
+  }
+}
+
+int pocs_get_clearance_counts(pocs_ctx* c, unsigned long long* out, int cap, int* levels) {
+  if (!c) return POCS_E_ARG;
+  if (!out || !levels) return fail(c, POCS_E_ARG, "pocs_get_clearance_counts: null output");
+  if (int r = clearance_served(c, "pocs_get_clearance_counts")) return r;
+  size_t slot; int E;
+  clearance_rows(c, (size_t)c->res.view, &slot, &E);
+  const size_t L = (size_t)c->res.cl_L, W = (size_t)c->res.cl_W;
+  if ((slot + 1) * W * POCS_MAX_CLEARANCE_LEVELS > c->res.cl_counts.size() || (size_t)E > W)
+    return fail(c, POCS_E_STATE, "pocs_get_clearance_counts: the table does not cover the selection");
+  *levels = (int)L;
+  if ((size_t)(cap < 0 ? 0 : cap) < (size_t)E * L) return fail(c, POCS_E_BUFFER, "need %zu counters", (size_t)E * L);
+  for (size_t w = 0; w < (size_t)E; ++w)
+    for (size_t l = 0; l < L; ++l) out[w * L + l] = c->res.cl_counts[(slot * W + w) * POCS_MAX_CLEARANCE_LEVELS + l];
+  return E;
+}
+
+int pocs_get_batch_clearance_probabilities(pocs_ctx* c, int level, double* out, int cap) {
+  if (!c) return POCS_E_ARG;
+  if (!out) return fail(c, POCS_E_ARG, "pocs_get_batch_clearance_probabilities: null output");
+  if (int r = clearance_served(c, "pocs_get_batch_clearance_probabilities")) return r;
+  if (level < 0 || level >= c->res.cl_L) return fail(c, POCS_E_ARG, "pocs_get_batch_clearance_probabilities: level %d outside 0..%d", level, c->res.cl_L - 1);
+  const size_t W = (size_t)c->res.cl_W, R = c->res.cl_counts.size() / (W * POCS_MAX_CLEARANCE_LEVELS);
+  const size_t lo = c->ra_internal ? (size_t)c->res.view : 0, hi = c->ra_internal ? lo + 1 : R;
+  if ((long long)(hi - lo) > (long long)cap) return fail(c, POCS_E_BUFFER, "need %zu doubles", hi - lo);
+  const double n = (double)c->res.cl_N;
+  for (size_t r = lo; r < hi; ++r) {
+    size_t slot; int E;
+    clearance_rows(c, r, &slot, &E);
+    const unsigned long long* A = &c->res.cl_counts[slot * W * POCS_MAX_CLEARANCE_LEVELS + (size_t)level];
+    if (c->res.cl_kind == Kind::Gmm) {               // as gmm_combine forms the final probability from the collision counts
+      double prod = 1.0;
+      for (int w = 0; w < E; ++w) prod *= (1.0 - (double)A[(size_t)w * POCS_MAX_CLEARANCE_LEVELS] / (1.0 * n));
+      out[r - lo] = 1.0 - prod;
+    } else {
+      unsigned long long sum = 0;
+      for (int w = 0; w < E; ++w) sum += A[(size_t)w * POCS_MAX_CLEARANCE_LEVELS];
+      out[r - lo] = (double)sum / n;
+    }
+  }
+  return (int)(hi - lo);
+}
+
 int pocs_get_batch_probabilities(pocs_ctx* c, double* out, int cap) {
   if (!c || !out) return POCS_E_ARG;
   return batch_out(c, out, cap, c->res.batch_probs, "doubles");

@@ -360,3 +360,55 @@ POCS_HD double pocs_footprint_extent_pre(double rx, double ry, double rr, double
 POCS_HD double pocs_footprint_extent(double rx, double ry, double lo, double hi) {
   return pocs_footprint_extent_pre(rx, ry, sqrt(rx * rx + ry * ry), atan2(ry, rx), lo, hi);
 }
+
+// ---- clearance levels (pocs_set_clearance_levels) -------------------------------------------------------------------
+// For clearances d_0 < d_1 < ... < d_{L-1} a pose is WITHIN clearance d of the world exactly when the collision test above
+// answers "touches" for the footprint grown by d -- {dx, dy, hx + d, hy + d}, one addition per half extent -- touching
+// included.  Every margin of the narrow phase is a monotone function of the half extents, so a pose within d is within every
+// larger d: the largest level is tested first and a smaller one only for a pose that touched.  The records are those prepared
+// (pocs_prepare_obstacle) for the footprint grown by d_{L-1}: fields 0 .. 5 do not depend on the footprint, and a broad phase
+// sized for the largest level is conservative for the smaller ones.  The functions above stay what they are.
+#define POCS_MAX_CLEARANCE_LEVELS 4
+
+POCS_HD pocs_footprint pocs_grown_footprint(const pocs_footprint* fp, double d) {
+  pocs_footprint g = {fp->dx, fp->dy, fp->hx + d, fp->hy + d};
+  return g;
+}
+
+// The smallest level l with the pose within clearance d[l]; L: within none.  (The footprint itself is not looked at: a caller
+// that wants to know whether the pose collides asks pocs_pose_collides with the records of the footprint as it is.)
+POCS_HD int pocs_pose_clearance_level(double x, double y, double th, const pocs_footprint* fp, const double* d, int L,
+                                      const double* obs, int M, const pocs_tables* T, const pocs_vconst* V = nullptr) {
+  int level = L;
+  for (int l = L - 1; l >= 0; --l) {
+    const pocs_footprint g = pocs_grown_footprint(fp, d[l]);
+    if (!pocs_pose_collides(x, y, th, &g, obs, M, T, V)) break;
+    level = l;
+  }
+  return level;
+}
+
+#if defined(__HIPCC__)
+// The same for the pair of poses a thread of k_gmm_step draws, as lane masks per level in the manner of
+// pocs_pair_collides_masks: each(l, m0, m1) is called once per level, from L - 1 down to 0, with the lanes whose pose 0 / pose 1
+// is within d[l].  A level below one that no lane of either pose touched is not computed (both masks zero), and a lane counts
+// for a level only if it counted for the one above: per lane the answer of pocs_pose_clearance_level, whatever the other lanes
+// of its wave hold.  `obs` and `d` lie in LDS (the kept records of the grown footprint, the distances).
+template <class Each>
+__device__ __forceinline__ void pocs_pair_clearance_masks(const double x[2], const double y[2], const double th[2], const pocs_footprint* fp,
+                                                          const double* d, int L, const double* obs, int M, const pocs_tables* T,
+                                                          const pocs_vconst* V, Each each) {
+  unsigned long long up0 = ~0ull, up1 = ~0ull;
+#pragma unroll 1
+  for (int l = L - 1; l >= 0; --l) {
+    unsigned long long m[2] = {0ull, 0ull};
+    if ((up0 | up1) != 0ull) {                                      // (scalar)
+      const pocs_footprint g = pocs_grown_footprint(fp, d[l]);
+      pocs_pair_collides_masks<false>(x, y, th, &g, obs, M, T, V, m);
+      m[0] &= up0; m[1] &= up1;
+    }
+    each(l, m[0], m[1]);
+    up0 = m[0]; up1 = m[1];
+  }
+}
+#endif

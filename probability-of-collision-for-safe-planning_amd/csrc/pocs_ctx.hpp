@@ -98,6 +98,14 @@ struct Results {
   // and pocs_get_obstacle_counts reads the selected run's rows; this is what the last call left there
   Kind oc_kind = Kind::None;                      // None: the last call ran with the option off (or there was none)
   int oc_M = 0, oc_W = 0;                         // boxes of the call's world, rows per slot
+  // clearance levels (pocs_set_clearance_levels): the table of the last call, read back with its results ([slot][cl_W][cl_L]), and
+  // why there is none to serve (pocs_get_clearance_counts names it)
+  enum ClearState { ClNoCall, ClOff, ClTouched, ClNotApplied, ClServed };
+  ClearState cl_state = ClNoCall;
+  Kind cl_kind = Kind::None;
+  int cl_L = 0, cl_W = 0;
+  long long cl_N = 0;                             // samples / particles per waypoint of the call: the probabilities' divisor
+  std::vector<unsigned long long> cl_counts;
 };
 
 // One cached graph and its signature: the bytes of its launches in issue order (Issuer, pocs_host.hip), compared before a replay.
@@ -180,6 +188,10 @@ struct pocs_ctx {
   long long opt_mc_wp = 0, opt_mc_rb = 0;
   // per-obstacle collision counts (POCS_OPT_OBSTACLE_COUNTS): the launches are the kernels' _boxes / MC_BOXES forms
   long long opt_obs_counts = 0;
+  // clearance levels (pocs_set_clearance_levels): L = 0 is off.  Applied to whole calls on one GPU over a small world (clearance_applied,
+  // pocs_host.hip); everywhere else a call is the call it is with L = 0
+  int clr_L = 0;
+  double clr_d[POCS_MAX_CLEARANCE_LEVELS] = {0.0, 0.0, 0.0, 0.0};
 
   // host image (headers | chains | initial mixtures) of the NEXT batch, computed while the GPU
   // works on the current one
@@ -202,6 +214,9 @@ struct pocs_ctx {
   // sampled [slots][POCS_MAX_OBSTACLES][POCS_OBS_STRIDE], their indices in the caller's table [slots][POCS_MAX_OBSTACLES] int, and the
   // kept counts [slots][W] int, zeroed at the head of every call
   pocs_rt::DevBuf d_world, d_kept, d_keptidx, d_reach;
+  // clearance levels: [world_S] pocs_clear_dev beside d_env (upload_world), the counters [slots][W][POCS_MAX_CLEARANCE_LEVELS] u64 zeroed
+  // by a kernel at the head of every call's launches, and the MC particles' smallest level so far [slots][stride] u8
+  pocs_rt::DevBuf d_clr, d_clrct, d_clrlv;
   pocs_rt::DevBuf d_obsct;               // POCS_OPT_OBSTACLE_COUNTS: [slots][W][POCS_MAX_OBSTACLES] u64, zeroed by a kernel at the head of every call's launches
   // one-hop exchange (pocs_xchg_*): this rank's buffer, the peers' buffers as mapped here
   void* xchg_own = nullptr;
@@ -294,6 +309,7 @@ inline void reset_results(pocs_ctx* c) {
   r.tree_sel = 0; r.tree_mc_half = 0;
   r.tree_probs.clear(); r.tree_eval.clear(); r.tree_F.clear(); r.tree_C.clear();
   r.oc_kind = Kind::None; r.oc_M = 0; r.oc_W = 0;
+  r.cl_state = Results::ClNoCall; r.cl_kind = Kind::None; r.cl_L = 0; r.cl_W = 0; r.cl_N = 0; r.cl_counts.clear();
 }
 
 // The collision world: M boxes per step, and the record of the device's env array ([world_S] pocs_env_dev) that waypoint w --
@@ -301,6 +317,10 @@ inline void reset_results(pocs_ctx* c) {
 inline int world_boxes(const pocs_ctx* c) { return (int)(c->boxes.size() / 5 / (size_t)c->world_S); }
 inline const pocs_env_dev* world_at(const pocs_ctx* c, int w) {
   return (const pocs_env_dev*)c->d_env.p + (w < 0 ? 0 : w < c->world_S ? w : c->world_S - 1);
+}
+
+inline const pocs_clear_dev* clear_at(const pocs_ctx* c, int w) {
+  return (const pocs_clear_dev*)c->d_clr.p + (w < 0 ? 0 : w < c->world_S ? w : c->world_S - 1);
 }
 
 // A large world is in force (pocs_set_world with more than POCS_MAX_OBSTACLES boxes), and its number of boxes.
@@ -356,6 +376,8 @@ int upload_tables(pocs_ctx* c);
 int upload_world(pocs_ctx* c);
 void fill_gmm_world(const pocs_ctx* c, pocs_gmm_launch* a, int w);
 size_t obs_count_words(const pocs_ctx* c);
+bool clearance_applied(const pocs_ctx* c);
+void prepare_clearance(const pocs_footprint& fp, const double* d, int L, const double* boxes, int M, pocs_clear_dev* out);
 void gmm_select_view(pocs_ctx* c, int v);
 void tree_select_gmm(pocs_ctx* c, int n);
 int run_gmm_full(pocs_ctx* c, double* probability);

@@ -47,11 +47,25 @@ template <> struct gmm_oc_smem<true> {
   unsigned occ[2][POCS_MAX_OBSTACLES];
   int oci[2][POCS_MAX_OBSTACLES];
 };
-template <int K, int TB, bool OC = false>
-struct gmm_smem : gmm_oc_smem<OC> {
+//   keep2 / clh / clc  (the clearance form only, pocs_set_clearance_levels: an empty base otherwise again) per run buffer the obstacle
+//          table culled against the footprint grown by the largest clearance (8 KB), the head of the waypoint's pocs_clear_dev
+//          (grown footprint, its radius and corner angle, the distances) and per run buffer and level the block's samples within it
+template <bool CL> struct gmm_cl_smem {};
+template <> struct gmm_cl_smem<true> {
+  alignas(16) double keep2[2][POCS_MAX_OBSTACLES * POCS_OBS_STRIDE];
+  double clh[6 + POCS_MAX_CLEARANCE_LEVELS];
+  unsigned clc[2][POCS_MAX_CLEARANCE_LEVELS];
+  int nkeep2[2];
+};
+static_assert(offsetof(pocs_clear_dev, fp_rr) == 32 && offsetof(pocs_clear_dev, d) == 48 && offsetof(pocs_clear_dev, obs) == 48 + 8 * POCS_MAX_CLEARANCE_LEVELS,
+              "clh: the record's first doubles are footprint (4), radius, corner angle, distances");
+template <int K, int TB, bool OC = false, bool CL = false>
+struct gmm_smem : gmm_oc_smem<OC>, gmm_cl_smem<CL> {
   static constexpr int NC = K * POCS_NMOM;
   static constexpr int NW = TB / 64;
-  static constexpr int SUB = POCS_GMM_SUB;
+  // (the clearance form holds 24 units at a time, not 32: with its second kept table K = 7 and K = 8 would otherwise pass the 80 KB
+  // that let two blocks share a CU's 160 KB; the sums are defined per unit, so how many a block holds at a time changes no bit)
+  static constexpr int SUB = CL ? 24 : POCS_GMM_SUB;
   alignas(16) pocs_tables tab;                                       // 12 KB log / sector tables, staged once per block
   alignas(16) double keep[2][POCS_MAX_OBSTACLES * POCS_OBS_STRIDE];  // obstacle table culled for the block's (up to) two runs
   alignas(16) double par[2][K * POCS_PARAM_STRIDE];                  // sampler parameters of (run, waypoint)
@@ -68,6 +82,8 @@ struct gmm_smem : gmm_oc_smem<OC> {
   static_assert(NW * POCS_FLUSH_ROWS * POCS_FLUSH_PITCH >= 16 * NC, "the closer's staging rows live in the transpose scratch");
   static_assert(SUB * NW * POCS_UNIT_SUMS >= POCS_ADV_SCRATCH(K) + POCS_SPEC_SCRATCH(K), "the advance's scratch lives in the slots");
   __device__ __forceinline__ double* obs() { return &tr[0][0][0]; }
+  static_assert(!CL || NW * POCS_FLUSH_ROWS * POCS_FLUSH_PITCH >= 2 * POCS_MAX_OBSTACLES * POCS_OBS_STRIDE, "... and the grown footprint's table behind it");
+  __device__ __forceinline__ double* obs2() { return &tr[0][0][0] + POCS_MAX_OBSTACLES * POCS_OBS_STRIDE; }
   __device__ __forceinline__ double* stage() { return &tr[0][0][0]; }
   __device__ __forceinline__ double* adv() { return &slot[0][0][0]; }
   __device__ __forceinline__ double* spec() { return &slot[0][0][0] + POCS_ADV_SCRATCH(K); }
@@ -99,8 +115,8 @@ __device__ __forceinline__ double oct_sum(double s) {     // lanes 8 j .. 8 j + 
 // wave's xtra entry of k), and the chains restart.  By LDS transposition, five then four sums at a
 // time: every lane writes its values, lane 8 j + q adds lanes 8 q .. 8 q + 7 of sum j, oct_sum adds the
 // eight q.  One wave: the LDS executes a wave's instructions in order, nothing else synchronises.
-template <int K, int TB, bool OC>
-__device__ __forceinline__ void flush_unit(gmm_smem<K, TB, OC>& sm, const int wave, const int lane, const int rb, const int tl,
+template <int K, int TB, bool OC, bool CL>
+__device__ __forceinline__ void flush_unit(gmm_smem<K, TB, OC, CL>& sm, const int wave, const int lane, const int rb, const int tl,
                                            const int k, bool& first, double (&acc)[9], int& nfree) {
   double* const T = &sm.tr[wave][0][0];
   double* const dst = first ? &sm.slot[tl][wave][0] : &sm.xtra[rb][wave][k][0];
@@ -166,8 +182,8 @@ __device__ __forceinline__ void gmm_reach(const pocs_footprint& fp, const double
   ext_y = pocs_footprint_extent_is_radius(fp_phi, tlo - HALF_PI, thi - HALF_PI) ? fp_rr
         : pocs_footprint_extent_of_ends(fp_rr, lane_value(end_f, 2), lane_value(end_f, 3));
 }
-template <int K, int TB, bool OC>
-__device__ __forceinline__ void gmm_cull(const pocs_gmm_launch& a, gmm_smem<K, TB, OC>& sm, const int rb, const int lane, const double* par) {
+template <int K, int TB, bool OC, bool CL>
+__device__ __forceinline__ void gmm_cull(const pocs_gmm_launch& a, gmm_smem<K, TB, OC, CL>& sm, const int rb, const int lane, const double* par) {
   const pocs_footprint fp = a.fp;
   const int M = a.M;
   const double* const obs = sm.obs();
@@ -215,6 +231,55 @@ __device__ __forceinline__ void gmm_cull(const pocs_gmm_launch& a, gmm_smem<K, T
   if (lane == 0) sm.nkeep[rb] = __popcll(mask);
 }
 
+// The clearance form's second list (one wave, all 64 lanes, beside the wave that runs gmm_cull for the same run buffer): the table
+// prepared for the footprint grown by the largest clearance (sm.obs2()) culled against the same mixture with that footprint's
+// extents -- gmm_cull's arithmetic with clh's footprint, radius and corner angle in place of the launch's -- into keep2[rb]; the
+// level counters of the buffer start at zero.  Conservative for every smaller level: their footprints lie inside this one.
+template <int K, int TB, bool OC>
+__device__ __forceinline__ void gmm_cull_clear(const pocs_gmm_launch& a, gmm_smem<K, TB, OC, true>& sm, const int rb, const int lane, const double* par) {
+  const pocs_footprint fp = {sm.clh[0], sm.clh[1], sm.clh[2], sm.clh[3]};
+  const double fp_rr = sm.clh[4], fp_phi = sm.clh[5];
+  const int M = a.M;
+  const double* const obs = sm.obs2();
+  double xlo = 1e300, xhi = -1e300, ylo = 1e300, yhi = -1e300, tlo = 1e300, thi = -1e300;
+#pragma unroll
+  for (int k = 0; k < K; ++k) {
+    const double* p = &par[k * POCS_PARAM_STRIDE];
+    const double ex = 6.67 * fabs(p[3]), ey = 6.67 * (fabs(p[4]) + fabs(p[5])), et = 6.67 * (fabs(p[6]) + fabs(p[7]) + fabs(p[8]));
+    xlo = fmin(xlo, p[0] - ex); xhi = fmax(xhi, p[0] + ex);
+    ylo = fmin(ylo, p[1] - ey); yhi = fmax(yhi, p[1] + ey);
+    tlo = fmin(tlo, p[2] - et); thi = fmax(thi, p[2] + et);
+  }
+  const double pad = sqrt(fp.dx * fp.dx + fp.dy * fp.dy) + 1e-6;
+  xlo -= pad; xhi += pad; ylo -= pad; yhi += pad;
+  tlo -= 1e-9 * (1.0 + fabs(tlo)); thi += 1e-9 * (1.0 + fabs(thi));
+  const double HALF_PI = 1.57079632679489661923;
+  const double end_t = ((lane & 1) ? thi : tlo) - ((lane & 2) ? HALF_PI : 0.0);
+  const double end_f = pocs_footprint_extent_end(fp.hx, fp.hy, end_t);
+  const double ext_x = pocs_footprint_extent_is_radius(fp_phi, tlo, thi) ? fp_rr
+                     : pocs_footprint_extent_of_ends(fp_rr, lane_value(end_f, 0), lane_value(end_f, 1));
+  const double ext_y = pocs_footprint_extent_is_radius(fp_phi, tlo - HALF_PI, thi - HALF_PI) ? fp_rr
+                     : pocs_footprint_extent_of_ends(fp_rr, lane_value(end_f, 2), lane_value(end_f, 3));
+  bool keep = false;
+  double bx = 0.0, by = 0.0;
+  if (lane < M) {
+    const double* o = &obs[lane * POCS_OBS_STRIDE];
+    bx = fmin(o[6], fma(o[4], fabs(o[2]), o[5] * fabs(o[3])) * (1.0 + 1e-12) + ext_x);
+    by = fmin(o[7], fma(o[4], fabs(o[3]), o[5] * fabs(o[2])) * (1.0 + 1e-12) + ext_y);
+    keep = !(o[0] - bx > xhi || o[0] + bx < xlo || o[1] - by > yhi || o[1] + by < ylo);
+  }
+  const unsigned long long mask = __ballot(keep);
+  if (keep) {
+    const int pos = __popcll(mask & ((1ull << lane) - 1ull));
+#pragma unroll
+    for (int j = 0; j < 6; ++j) sm.keep2[rb][pos * POCS_OBS_STRIDE + j] = obs[lane * POCS_OBS_STRIDE + j];
+    sm.keep2[rb][pos * POCS_OBS_STRIDE + 6] = bx;
+    sm.keep2[rb][pos * POCS_OBS_STRIDE + 7] = by;
+  }
+  if (lane < POCS_MAX_CLEARANCE_LEVELS) sm.clc[rb][lane] = 0u;
+  if (lane == 0) sm.nkeep2[rb] = __popcll(mask);
+}
+
 // ---------------------------------------------------------------------------------------------
 // THE BODY: units [ta, tb) of the launch (unit t = virtual slice t mod VS of run t / VS; at most
 // POCS_GMM_SUB of them, of at most two runs r0 and r0 + 1 whose parameters and culled tables are staged
@@ -231,8 +296,11 @@ __device__ __forceinline__ void gmm_cull(const pocs_gmm_launch& a, gmm_smem<K, T
 //   balloted; hits are rare, so a zero ballot -- nearly all of them -- is skipped by a scalar branch, and otherwise one lane
 //   adds the population count to the block's LDS counter of (run buffer, kept slot).  Nothing else differs: the same
 //   pocs_pair_collides_masks, with every record's answer handed out.
-template <int K, bool STORE, int TB, bool LONE_PRE = false, bool OC = false>
-__device__ __forceinline__ void gmm_units(const pocs_gmm_launch& a, gmm_smem<K, TB, OC>& sm, const int w, const int r0,
+//   CL (pocs_set_clearance_levels): behind the unchanged base test the level test runs on the second kept list
+//   (pocs_pair_clearance_masks); per level the lanes whose sample exists are picked by scalar ands of the masks and one lane adds
+//   the population count to the block's LDS counter of (run buffer, level).  The odd shard's unused twin does not count.
+template <int K, bool STORE, int TB, bool LONE_PRE = false, bool OC = false, bool CL = false>
+__device__ __forceinline__ void gmm_units(const pocs_gmm_launch& a, gmm_smem<K, TB, OC, CL>& sm, const int w, const int r0,
                                           const int ta, const int tb, const double* zpre = nullptr, const int npre = 0) {
   const pocs_tables* const s_tab = &sm.tab;
   const int tid = threadIdx.x, lane = tid & 63;
@@ -265,6 +333,8 @@ __device__ __forceinline__ void gmm_units(const pocs_gmm_launch& a, gmm_smem<K, 
   int rb = -1, nkeep = 0, kcur = 0, kw = 0;
   const double* s_par = nullptr;
   const double* s_keep = nullptr;
+  [[maybe_unused]] const double* s_keep2 = nullptr;       // CL: the second kept list and its length
+  [[maybe_unused]] int nkeep2 = 0;
   uint64_t seed = 0;
   double cumn[K > 1 ? K - 1 : 1];                   // cumulative component counts
   double *xr = nullptr, *yr = nullptr, *tr = nullptr;
@@ -344,6 +414,15 @@ __device__ __forceinline__ void gmm_units(const pocs_gmm_launch& a, gmm_smem<K, 
     } else {
     POCS_TUNE_COLLIDE(pocs_pair_collides_masks<LONE_PRE>(xs, ys, ts, &fp, s_keep, nkeep, s_tab, vc, hits));
     }
+    if constexpr (CL) {
+      const unsigned long long lm = WHOLE ? ~0ull : __ballot(live), tm = WHOLE ? ~0ull : __ballot(two);
+      unsigned* const clc = sm.clc[rb];
+      pocs_pair_clearance_masks(xs, ys, ts, &fp, &sm.clh[6], a.clr_L, s_keep2, nkeep2, s_tab, vc,
+                                [&](const int l, const unsigned long long m0, const unsigned long long m1) {
+        const unsigned n = (unsigned)__popcll(m0 & lm) + (unsigned)__popcll(m1 & tm);      // (scalar)
+        if (n != 0u && lane == 0) __hip_atomic_fetch_add(&clc[l], n, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+      });
+    }
     if constexpr (POCS_TUNE_SKIP_MOMENTS) { POCS_TUNE_MOMENTS_ALT(); } else {
     // T1 sums over the collision-free samples of the component being accumulated:
     //   (x, y, t, x x, x y, x t, y y, y t, t t) with the products inside the fma; survivors by population count.
@@ -419,6 +498,7 @@ __device__ __forceinline__ void gmm_units(const pocs_gmm_launch& a, gmm_smem<K, 
       rb = r - r0;
       s_par = sm.par[rb]; s_keep = sm.keep[rb];
       nkeep = __builtin_amdgcn_readfirstlane(sm.nkeep[rb]);
+      if constexpr (CL) { s_keep2 = sm.keep2[rb]; nkeep2 = __builtin_amdgcn_readfirstlane(sm.nkeep2[rb]); }
       seed = (uint64_t)uniform64((long long)sm.seed[rb]);         // scalar registers, provably
 #pragma unroll
       for (int q = 0; q < K - 1; ++q) cumn[q] = s_par[q * POCS_PARAM_STRIDE + 9];
@@ -469,8 +549,8 @@ __device__ __forceinline__ void gmm_units(const pocs_gmm_launch& a, gmm_smem<K, 
 // order -- whichever of them the unit has: slot if the component was the wave's first there, xtra if it
 // started inside the wave's share, +0 otherwise -- stored write-through to the run's partial rows.
 // Column 1 (collisions) stays 0: a component's collisions are what is left of its block (gmm_close_sums).
-template <int K, int TB, bool OC>
-__device__ __forceinline__ void gmm_emit_rows(const pocs_gmm_launch& a, gmm_smem<K, TB, OC>& sm, const int r0, const int ta, const int tb) {
+template <int K, int TB, bool OC, bool CL>
+__device__ __forceinline__ void gmm_emit_rows(const pocs_gmm_launch& a, gmm_smem<K, TB, OC, CL>& sm, const int r0, const int ta, const int tb) {
   constexpr int NC = K * POCS_NMOM, NW = TB / 64;
   for (int i = threadIdx.x; i < (tb - ta) * NC; i += TB) {
     const int tl = i / NC, c = i - tl * NC, k = c / POCS_NMOM, col = c - k * POCS_NMOM;
@@ -642,9 +722,18 @@ __device__ __forceinline__ void gmm_close_sums(const pocs_gmm_launch& a, const i
 // every run of the launch in a.kept and their number in a.reach.  The head asks for the (up to) two runs' records and counts with
 // its other requests, the same single round trip, and commits min(reach, POCS_MAX_OBSTACLES) records to sm.keep[rb] -- what gmm_cull
 // leaves there otherwise.  The body does not know the difference.
-template <int K, bool STORE, int TB, bool LONE, bool RISK, bool TREE = false, bool OC = false, bool WORLD = false>
+//
+// CL (clearance levels, pocs_set_clearance_levels; the kernels k_gmm_step_clear, k_gmm_step_risk_clear: ticket form, never LONE, TREE,
+// OC or WORLD): the head also stages the table prepared for the footprint grown by the largest clearance (behind the base table in
+// the transpose scratch) and the head of the waypoint's pocs_clear_dev, with its other requests; waves 2 and 3 cull that table
+// beside waves 0 and 1 (gmm_cull_clear); the body counts per level (gmm_units); behind the units the nonzero counters leave with
+// one integer atomic each to clr_counts[run][waypoint][level], as occ does.  The base test, the moment sums, the tickets and the
+// closers are what they are.  LDS: + 8 KB for the second kept table, + 0.1 KB, and 24 instead of 32 held units (- 5.25 KB): K = 3 holds
+// 70 688 B against the twin's 67 744, K = 8 78 368 B against 75 424 -- two blocks per CU (160 KB) in every instantiation, as the twins.
+template <int K, bool STORE, int TB, bool LONE, bool RISK, bool TREE = false, bool OC = false, bool WORLD = false, bool CL = false>
 __device__ __forceinline__ void gmm_step_block(const pocs_gmm_launch a) {      // (by value, as a kernel holds its argument)
-  typedef gmm_smem<K, TB, OC> smem_t;
+  typedef gmm_smem<K, TB, OC, CL> smem_t;
+  static_assert(!(CL && (LONE || TREE || OC || WORLD)), "clearance levels: the ticket form of a batch or of plans on a small world, no per-box counts");
   static_assert(!(WORLD && (LONE || TREE || OC)), "a large world: the ticket form of a batch or of plans, no per-box counts");
   static_assert(!WORLD || TB == POCS_MAX_OBSTACLES * POCS_OBS_STRIDE, "one element of a run's kept records per thread");
   static_assert(!(LONE && RISK), "the lone form closes in its heads: a call under a risk bound takes the ticket form");
@@ -677,6 +766,11 @@ __device__ __forceinline__ void gmm_step_block(const pocs_gmm_launch a) {      /
   request_tables<TB>(a.tables, tid, tabv);
   double obs_elem = 0.0;
   if constexpr (!WORLD) obs_elem = tid < a.M * POCS_OBS_STRIDE ? a.env->obs[tid] : 0.0;
+  [[maybe_unused]] double obs2_elem = 0.0, clh_elem = 0.0;      // CL: the grown footprint's table, the head of the clearance record
+  if constexpr (CL) {
+    obs2_elem = tid < a.M * POCS_OBS_STRIDE ? a.clr->obs[tid] : 0.0;
+    clh_elem = tid < 6 + POCS_MAX_CLEARANCE_LEVELS ? reinterpret_cast<const double*>(a.clr)[tid] : 0.0;
+  }
   if (LONE && w > 0) {
     // close waypoint w - 1 and advance to w, here (r0 is the call's one run)
     const bool out = blockIdx.x == 0;
@@ -773,6 +867,7 @@ __device__ __forceinline__ void gmm_step_block(const pocs_gmm_launch a) {      /
       else if (dead1) { r1 = r0_all; t1 = r1_all << a.vs_shift; }
       commit_tables<TB>(&sm.tab, tid, tabv);
       if (tid < a.M * POCS_OBS_STRIDE) sm.obs()[tid] = obs_elem;
+      if constexpr (CL) { if (tid < a.M * POCS_OBS_STRIDE) sm.obs2()[tid] = obs2_elem; if (tid < 6 + POCS_MAX_CLEARANCE_LEVELS) sm.clh[tid] = clh_elem; }
       if (tid < (r1_all - r0_all + 1) * PS && rp >= shift && rp - shift <= r1 - r0) sm.par[rp - shift][jp] = parv;
       for (int j = tid; j < 2 * NW * K; j += TB) (&sm.xj[0][0][0])[j] = -1;
       if (tid <= r1_all - r0_all && tid >= shift && tid - shift <= r1 - r0) sm.seed[tid - shift] = seedv;
@@ -781,6 +876,7 @@ __device__ __forceinline__ void gmm_step_block(const pocs_gmm_launch a) {      /
     requests_issued();
     commit_tables<TB>(&sm.tab, tid, tabv);
     if (tid < a.M * POCS_OBS_STRIDE) sm.obs()[tid] = obs_elem;
+    if constexpr (CL) { if (tid < a.M * POCS_OBS_STRIDE) sm.obs2()[tid] = obs2_elem; if (tid < 6 + POCS_MAX_CLEARANCE_LEVELS) sm.clh[tid] = clh_elem; }
     if (tid < (r1 - r0 + 1) * PS) sm.par[rp][jp] = parv;
     for (int j = tid; j < 2 * NW * K; j += TB) (&sm.xj[0][0][0])[j] = -1;
     if (tid <= r1 - r0) sm.seed[tid] = seedv;
@@ -790,6 +886,10 @@ __device__ __forceinline__ void gmm_step_block(const pocs_gmm_launch a) {      /
   __syncthreads();
   if constexpr (!WORLD) {
   if (!(LONE && w > 0)) {                            // (scalar; the lone form's heads have culled already, above)
+    if constexpr (CL) {
+      if (tid >= 128 && tid < 192) gmm_cull_clear(a, sm, 0, tid - 128, sm.par[0]);
+      else if (tid >= 192 && tid < 256 && r1 > r0) gmm_cull_clear(a, sm, 1, tid - 192, sm.par[1]);
+    }
     if (tid < 64) gmm_cull(a, sm, 0, tid, sm.par[0]);
     else if (tid < 128 && r1 > r0) gmm_cull(a, sm, 1, tid - 64, sm.par[1]);
     __syncthreads();
@@ -798,7 +898,7 @@ __device__ __forceinline__ void gmm_step_block(const pocs_gmm_launch a) {      /
   POCS_STAMP(0);
   for (int ta = t0; ta < t1; ta += SUB) {
     const int tb = (ta + SUB < t1) ? ta + SUB : t1;
-    gmm_units<K, STORE, TB, LONE, OC>(a, sm, w, r0, ta, tb, s_zpre, ta == t0 ? npre : 0);
+    gmm_units<K, STORE, TB, LONE, OC, CL>(a, sm, w, r0, ta, tb, s_zpre, ta == t0 ? npre : 0);
     POCS_STAMP(1);
     __syncthreads();
     POCS_STAMP(2);
@@ -816,6 +916,15 @@ __device__ __forceinline__ void gmm_step_block(const pocs_gmm_launch a) {      /
     if (rb <= r1 - r0 && j < sm.nkeep[rb]) {
       const unsigned n = sm.occ[rb][j];
       if (n) atomicAdd(&a.obs_counts[((size_t)(r0 + rb) * a.W + wr) * POCS_MAX_OBSTACLES + sm.oci[rb][j]], (unsigned long long)n);
+    }
+  }
+  if constexpr (CL) {
+    // (as occ above: every wave's LDS additions lie in front of the barrier behind the last gmm_units)
+    const int rb = tid >> 2, l = tid & 3;
+    static_assert(POCS_MAX_CLEARANCE_LEVELS == 4, "thread 4 rb + l");
+    if (tid < 8 && rb <= r1 - r0 && l < a.clr_L) {
+      const unsigned n = sm.clc[rb][l];
+      if (n) atomicAdd(&a.clr_counts[((size_t)(r0 + rb) * a.W + wr) * POCS_MAX_CLEARANCE_LEVELS + l], (unsigned long long)n);
     }
   }
   if (LONE) return;                                  // the rows leave through the kernel boundary; the next launch's heads add them
@@ -931,6 +1040,16 @@ __global__ __launch_bounds__(TB, POCS_GMM_BLOCKS_PER_CU * TB / 256) void k_gmm_s
 template <int K, int TB, bool RISK>
 __global__ __launch_bounds__(TB, POCS_GMM_BLOCKS_PER_CU * TB / 256) void k_gmm_step_tree_boxes(pocs_gmm_launch a) {
   gmm_step_block<K, false, TB, false, RISK, true, true>(a);
+}
+
+// The clearance forms (CL above): kernels of their own names again.
+template <int K, bool STORE, int TB>
+__global__ __launch_bounds__(TB, POCS_GMM_BLOCKS_PER_CU * TB / 256) void k_gmm_step_clear(pocs_gmm_launch a) {
+  gmm_step_block<K, STORE, TB, false, false, false, false, false, true>(a);
+}
+template <int K, bool STORE, int TB>
+__global__ __launch_bounds__(TB, POCS_GMM_BLOCKS_PER_CU * TB / 256) void k_gmm_step_risk_clear(pocs_gmm_launch a) {
+  gmm_step_block<K, STORE, TB, false, true, false, false, false, true>(a);
 }
 
 // The forms under a large collision world (WORLD above): kernels of their own names again.

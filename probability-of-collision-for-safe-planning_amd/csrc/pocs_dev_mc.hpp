@@ -113,7 +113,14 @@ __device__ __forceinline__ mc_run_start mc_start(const pocs_mc_launch& a) {
 // that touches two boxes counts for both).  The collision test is then pocs_pose_collides_each, which hands out every record's
 // answer; a thread keeps them as a 64-bit mask (POCS_MAX_OBSTACLES = 64: box 63 is bit 63), and the mask matters only for a
 // particle with old == 0 && hit.  The forms without the flag are the kernels as they are.
-enum { MC_PLAIN = 0, MC_COUNTS = 1, MC_STOP = 2, MC_BOXES = 4 };
+//
+// MC_CLEAR (pocs_set_clearance_levels), a flag on top of MC_PLAIN, MC_COUNTS or MC_STOP, on k_mc_init and the per-step kernel: every
+// particle keeps one byte, the smallest clearance level it has been within so far (L: none yet), and a particle counts for every
+// level between its new smallest level and its old one -- clr_counts[run][w][l], the particles within clearance d_l at waypoint w and
+// at no waypoint before: the first-collision profile as it would be for the grown footprint on the same cloud.  The level comes
+// from pocs_pose_clearance_level on the table prepared for the footprint grown by the largest clearance, staged beside the world's;
+// the collision test itself, the hit counters and the other counts are what they are without the flag.
+enum { MC_PLAIN = 0, MC_COUNTS = 1, MC_STOP = 2, MC_BOXES = 4, MC_CLEAR = 8 };
 static_assert(POCS_MAX_OBSTACLES <= 64, "a particle's touched boxes are a 64-bit mask");
 
 // pocs_pose_collides with the touched boxes as a mask (the flag: mask != 0, as the plain form's).
@@ -171,6 +178,38 @@ __device__ __forceinline__ void mc_block_add(unsigned c, unsigned long long* dst
 __device__ __forceinline__ void mc_wave_first_hits(bool first, unsigned long long* dst) {
   const unsigned long long m = __ballot(first);
   if (m != 0ull && (threadIdx.x & 63) == (unsigned)__builtin_ctzll(m)) atomicAdd(dst, (unsigned long long)__popcll(m));
+}
+
+// MC_CLEAR: what a thread keeps of the clearance record behind the head's barrier, and its staging (in front of that barrier).
+struct mc_clear {
+  const double* obs;               // LDS: the table prepared for the footprint grown by d[L - 1]
+  const double* d;                 // LDS: the distances
+  int L;
+};
+__device__ __forceinline__ mc_clear stage_mc_clear(const pocs_mc_launch& a) {
+  __shared__ double s_obs2[POCS_MAX_OBSTACLES * POCS_OBS_STRIDE];
+  __shared__ double s_d[POCS_MAX_CLEARANCE_LEVELS];
+  constexpr int NO = POCS_MAX_OBSTACLES * POCS_OBS_STRIDE, UO = (NO + POCS_BLOCK - 1) / POCS_BLOCK;
+  const int tid = threadIdx.x;
+  double vo[UO];
+#pragma unroll
+  for (int u = 0; u < UO; ++u) { const int i = tid + u * POCS_BLOCK; vo[u] = i < NO ? a.clr->obs[i] : 0.0; }
+  const double dv = tid < POCS_MAX_CLEARANCE_LEVELS ? a.clr->d[tid] : 0.0;
+  requests_issued();
+#pragma unroll
+  for (int u = 0; u < UO; ++u) { const int i = tid + u * POCS_BLOCK; if (i < NO) s_obs2[i] = vo[u]; }
+  if (tid < POCS_MAX_CLEARANCE_LEVELS) s_d[tid] = dv;
+  return {s_obs2, s_d, a.clr_L};
+}
+// The lanes of a wave that are in the particle loop together, each with its particle's level at this waypoint and its smallest
+// level before: per level that some particle reaches for the first time one ballot, and the first lane of the ballot adds the
+// population count to the level's counter of (run, waypoint), as mc_wave_first_hits does.
+__device__ __forceinline__ void mc_wave_level_hits(int now, int before, int L, unsigned long long* dst) {
+  if (__ballot(now < before) == 0ull) return;
+  for (int l = 0; l < L; ++l) {
+    const unsigned long long b = __ballot(now <= l && l < before);
+    if (b != 0ull && (threadIdx.x & 63) == (unsigned)__builtin_ctzll(b)) atomicAdd(&dst[l], (unsigned long long)__popcll(b));
+  }
 }
 
 // MC_STOP, the head of every block of the launch of control s: is the run stopped?  The run stops at the FIRST waypoint s
@@ -320,6 +359,8 @@ template <int MODE>
 __global__ __launch_bounds__(POCS_BLOCK) void k_mc_init(pocs_mc_launch a) {
   mc_box_counters box = {nullptr};
   if constexpr ((MODE & MC_BOXES) != 0) box = mc_box_counters_zeroed();      // (in front of the head's barrier)
+  mc_clear cl = {nullptr, nullptr, 0};
+  if constexpr ((MODE & MC_CLEAR) != 0) cl = stage_mc_clear(a);              // (in front of the head's barrier)
   const mc_head hd = stage_mc_head(a.env, a.tables);
   const mc_run_view v = mc_view(a);
   const mc_world wd = hd.world();
@@ -340,8 +381,13 @@ __global__ __launch_bounds__(POCS_BLOCK) void k_mc_init(pocs_mc_launch a) {
     }
     v.hits[i] = h;
     first += h;
+    if constexpr ((MODE & MC_CLEAR) != 0) {
+      const int lv = pocs_pose_clearance_level(x, y, t, &wd.fp, cl.d, cl.L, cl.obs, wd.M, wd.tab);
+      a.clr_level[(size_t)blockIdx.y * (size_t)a.stride + (size_t)i] = (unsigned char)lv;
+      mc_wave_level_hits(lv, cl.L, cl.L, a.clr_counts + (size_t)blockIdx.y * (size_t)a.W * POCS_MAX_CLEARANCE_LEVELS);
+    }
   }
-  if (MODE != MC_PLAIN) mc_block_add(first, a.wp_counts + (size_t)blockIdx.y * (size_t)a.W);      // waypoint 0
+  if ((MODE & 3) != MC_PLAIN) mc_block_add(first, a.wp_counts + (size_t)blockIdx.y * (size_t)a.W);      // waypoint 0
   if constexpr ((MODE & MC_BOXES) != 0) box.out(wd.M, a.obs_counts + (size_t)blockIdx.y * (size_t)a.W * POCS_MAX_OBSTACLES);
 }
 
@@ -387,6 +433,8 @@ __device__ __forceinline__ void mc_step_body(const pocs_mc_launch& a) {
   }
   mc_box_counters box = {nullptr};
   if constexpr ((MODE & MC_BOXES) != 0) box = mc_box_counters_zeroed();      // (in front of the head's barrier)
+  mc_clear cl = {nullptr, nullptr, 0};
+  if constexpr ((MODE & MC_CLEAR) != 0) cl = stage_mc_clear(a);              // (in front of the head's barrier)
   const mc_head hd = stage_mc_head(a.env, a.tables);
   const mc_run_view v = mc_view(a);
   const mc_world wd = hd.world();
@@ -416,8 +464,15 @@ __device__ __forceinline__ void mc_step_body(const pocs_mc_launch& a) {
       first += old == 0u ? 1u : 0u;
     }
     }
+    if constexpr ((MODE & MC_CLEAR) != 0) {
+      unsigned char* const lp = a.clr_level + (size_t)blockIdx.y * (size_t)a.stride + (size_t)i;
+      const int before = (int)*lp;
+      const int lv = pocs_pose_clearance_level(nx, ny, nt, &wd.fp, cl.d, cl.L, cl.obs, wd.M, wd.tab);
+      if (lv < before) *lp = (unsigned char)lv;
+      mc_wave_level_hits(lv, before, cl.L, a.clr_counts + ((size_t)blockIdx.y * (size_t)a.W + (size_t)a.step + 1) * POCS_MAX_CLEARANCE_LEVELS);
+    }
   }
-  if (MODE != MC_PLAIN) mc_block_add(first, a.wp_counts + (size_t)blockIdx.y * (size_t)a.W + (size_t)a.step + 1);   // control s -> waypoint s + 1
+  if ((MODE & 3) != MC_PLAIN) mc_block_add(first, a.wp_counts + (size_t)blockIdx.y * (size_t)a.W + (size_t)a.step + 1);   // control s -> waypoint s + 1
   if constexpr ((MODE & MC_BOXES) != 0) box.out(wd.M, a.obs_counts + ((size_t)blockIdx.y * (size_t)a.W + (size_t)a.step + 1) * POCS_MAX_OBSTACLES);
 }
 template <bool NT>

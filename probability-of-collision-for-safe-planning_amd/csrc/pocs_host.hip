@@ -73,6 +73,26 @@ int upload_tables(pocs_ctx* c) {               // log / sector tables of the num
   HIPCHK(c, hipMemcpy(c->d_tables.p, &T, sizeof T, hipMemcpyHostToDevice));
   return POCS_OK;
 }
+// Clearance levels: the record of one world step as the kernels read it (pocs_clear_dev) -- the footprint grown by the largest
+// distance, its radius and corner angle, the distances, and the step's boxes prepared for that footprint exactly as upload_world
+// prepares them for the footprint itself.  (pocs_probe_device_clearance prepares its own table through this function too.)
+void prepare_clearance(const pocs_footprint& fp, const double* d, int L, const double* boxes, int M, pocs_clear_dev* out) {
+  memset(out, 0, sizeof *out);
+  out->fp = L > 0 ? pocs_grown_footprint(&fp, d[L - 1]) : fp;
+  out->fp_rr = sqrt(out->fp.hx * out->fp.hx + out->fp.hy * out->fp.hy);
+  out->fp_phi = atan2(out->fp.hy, out->fp.hx);
+  for (int l = 0; l < L; ++l) out->d[l] = d[l];
+  for (int m = 0; m < M; ++m) pocs_prepare_obstacle(boxes + (size_t)m * 5, &out->fp, &out->obs[(size_t)m * POCS_OBS_STRIDE]);
+}
+
+// Where the levels are applied: whole calls on one GPU over a small world, static or scheduled -- single runs, batches, run-ahead,
+// calls of plans with and without the risk bound, GMM and MC.  A tree of plans, a large world, per-box counts, a shard (and with it
+// the exchange and a bound moments buffer) are the calls they are with L = 0; the step API never asks.
+bool clearance_applied(const pocs_ctx* c) {
+  using namespace pocs_modes;
+  return c->clr_L > 0 && !in_mode(c, kTree | kLargeWorld | kObsCounts | kShard | kMoments);
+}
+
 int upload_world(pocs_ctx* c) {                // tables + the collision world: one record (obstacle records, footprint) per step of the schedule
   if (int r = upload_tables(c)) return r;
   if (c->env_dirty) {
@@ -89,6 +109,12 @@ int upload_world(pocs_ctx* c) {                // tables + the collision world: 
     if (int r = ensure(c, c->d_env, S * sizeof(pocs_env_dev))) return r;      // (a schedule that grows: the graphs go with the old table)
     HIPCHK(c, hipStreamSynchronize(c->stream));      // (nothing queued may still read the last world's)
     HIPCHK(c, hipMemcpy(c->d_env.p, env.data(), S * sizeof(pocs_env_dev), hipMemcpyHostToDevice));
+    if (c->clr_L > 0 && !large_world(c)) {           // the second record set, next to the first: the footprint grown by d_L
+      std::vector<pocs_clear_dev> clr(S);
+      for (size_t s = 0; s < S; ++s) prepare_clearance(c->fp, c->clr_d, c->clr_L, c->boxes.data() + s * (size_t)M * 5, M, &clr[s]);
+      if (int r = ensure(c, c->d_clr, S * sizeof(pocs_clear_dev))) return r;
+      HIPCHK(c, hipMemcpy(c->d_clr.p, clr.data(), S * sizeof(pocs_clear_dev), hipMemcpyHostToDevice));
+    }
     if (large_world(c)) {                            // the large world's records (the env record above then holds the footprint and M = 0)
       const size_t LM = (size_t)large_boxes(c);
       std::vector<double> rec(LM * POCS_OBS_STRIDE);
@@ -243,6 +269,34 @@ void note_obs_counts(pocs_ctx* c, Kind kind) {
   c->res.oc_W = c->W > 0 ? c->W : 1;
 }
 
+// Clearance levels: d_clrct holds [batch][W][POCS_MAX_CLEARANCE_LEVELS] u64, zeroed by the first launch of every call they are applied
+// to (a kernel, inside the replayed graph, as d_obsct) and read back behind the call (read_clearance).  Not applied: no buffer, no
+// launch, and every launch is the kernel it is with L = 0.
+size_t clear_count_words(const pocs_ctx* c) { return (size_t)c->batch * (size_t)(c->W > 0 ? c->W : 1) * POCS_MAX_CLEARANCE_LEVELS; }
+int ensure_clearance(pocs_ctx* c) {
+  return clearance_applied(c) ? ensure(c, c->d_clrct, clear_count_words(c) * sizeof(unsigned long long)) : POCS_OK;
+}
+int enqueue_clearance_reset(Issuer is) {
+  pocs_ctx* c = is.c;
+  if (!clearance_applied(c)) return POCS_OK;
+  return is.launch(pocs_launch_zero_counts, 0, (unsigned long long*)c->d_clrct.p, clear_count_words(c));
+}
+// the state a call leaves for pocs_get_clearance_counts while it runs (or fails) ...
+void open_clearance(pocs_ctx* c) {
+  Results& r = c->res;
+  r.cl_state = c->clr_L == 0 ? Results::ClOff : Results::ClNotApplied;
+  r.cl_kind = Kind::None; r.cl_L = 0; r.cl_W = 0; r.cl_N = 0; r.cl_counts.clear();
+}
+// ... and behind its results: the table in slot order, as the device holds it (the stream is idle)
+int read_clearance(pocs_ctx* c, Kind kind, long long n) {
+  if (!clearance_applied(c)) return POCS_OK;
+  Results& r = c->res;
+  r.cl_counts.assign(clear_count_words(c), 0ull);
+  HIPCHK(c, hipMemcpy(r.cl_counts.data(), c->d_clrct.p, r.cl_counts.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+  r.cl_state = Results::ClServed; r.cl_kind = kind; r.cl_L = c->clr_L; r.cl_W = c->W > 0 ? c->W : 1; r.cl_N = n;
+  return POCS_OK;
+}
+
 // The call's synchronisation words (SyncLayout, pocs_ctx.hpp); the copy behind the launches starts at the give-up word and,
 // under a risk bound, runs on through the pad and the stop words.
 SyncLayout sync_layout(const pocs_ctx* c) {
@@ -286,6 +340,7 @@ int gmm_prepare(pocs_ctx* c) {
   if (c->tree.n)
     if (int r = upload_tree(c)) return r;
   if (int r = ensure_obs_counts(c)) return r;
+  if (int r = ensure_clearance(c)) return r;
   if (large_world(c)) {
     if (int r = ensure(c, c->d_kept, R * POCS_MAX_OBSTACLES * POCS_OBS_STRIDE * sizeof(double))) return r;
     if (int r = ensure(c, c->d_keptidx, R * POCS_MAX_OBSTACLES * sizeof(int))) return r;
@@ -385,6 +440,7 @@ void fill_gmm_launch(pocs_ctx* c, pocs_gmm_launch* a, long long first, long long
 void aim_gmm_launch(const pocs_ctx* c, pocs_gmm_launch* a, int w, int run_lo = 0, int run_cnt = -1, int groups = 1) {
   if (run_cnt < 0) run_cnt = c->batch;
   a->env = world_at(c, w); a->waypoint = w;
+  if (a->clr) a->clr = clear_at(c, w);               // (the clearance form: the record of the same step)
   const GmmGeometry geo = gmm_geometry(a->count, run_cnt, c->K, groups);
   a->chunks = geo.chunks; a->vs_shift = geo.vs_shift; a->upb = geo.upb; a->blocks = geo.blocks;
   a->run_lo = run_lo; a->run_cnt = run_cnt;
@@ -415,7 +471,8 @@ int enqueue_advance(Issuer is, int w) {
 // keeps the ticket-and-closer form; the results are the same bits.
 // (Under a large world the cull of waypoint w reads param[w] ahead of the sampling launch; the lone form builds param[w] in its own
 // heads, so a call of one run takes the ticket form there: the same bits.)
-bool lone_call(const pocs_ctx* c) { return c->opt_lone && !large_world(c) && c->batch == 1 && !c->tree.n && !c->ext_moments && !(c->xchg_connected && c->shard_first >= 0) && !risk_active(c); }
+// (Under clearance levels too: the counting form exists as the ticket form only.)
+bool lone_call(const pocs_ctx* c) { return c->opt_lone && !large_world(c) && !clearance_applied(c) && c->batch == 1 && !c->tree.n && !c->ext_moments && !(c->xchg_connected && c->shard_first >= 0) && !risk_active(c); }
 void set_risk(pocs_ctx* c, pocs_gmm_launch* a) {      // under a risk bound the launch is k_gmm_step_risk (whole calls of plans or on a tree only)
   a->risk = 1;
   a->stop = a->sync + c->sync.stop;
@@ -513,11 +570,15 @@ int enqueue_gmm_all(Issuer is, long long first, long long count, bool prof) {
   if (c->tree.n) return enqueue_gmm_tree(is, count);
   const int W = c->W, R = c->batch, G = gmm_groups(c);
   if (int r = enqueue_obs_counts_reset(is)) return r;    // (ahead of the fork: every sub-batch's launches lie behind it)
+  if (int r = enqueue_clearance_reset(is)) return r;
   if (int r = enqueue_advance(is, 0)) return r;
   if (prof) if (int r = is.mark(c->ev_seq[0])) return r;
   for (int g = 1; g < G; ++g) if (int r = is.order(0, g, c->ev_fork, g == 1)) return r;
   pocs_gmm_launch base;
   fill_gmm_launch(c, &base, first, count);
+  if (clearance_applied(c)) {                        // (the whole call only: the step API's launches never carry the levels)
+    base.clr = clear_at(c, 0); base.clr_counts = (unsigned long long*)c->d_clrct.p; base.clr_L = c->clr_L;
+  }
   StepLaunch s;
   s.groups = G; s.advance = true; s.lone = lone_call(c); s.risk = risk_active(c);
   if (whole_call_exchanges(c)) s.exchange = StepLaunch::FROM_HEADERS;
@@ -729,6 +790,7 @@ int run_gmm_full(pocs_ctx* c, double* probability) {
   auto lap = [](const char*) {};
 #endif
   c->res.oc_kind = Kind::None;                                  // (the per-obstacle table is rewritten from here on; noted again behind the combine)
+  open_clearance(c);
   c->reach.clear(); c->reach_len.clear(); c->reach_R = 0; c->reach_W = 0;      // (pocs_get_world_reach covers the last GMM call)
   if (int r = gmm_prepare(c)) return r;
   long long first, count;
@@ -767,6 +829,7 @@ int run_gmm_full(pocs_ctx* c, double* probability) {
   if (large_world(c)) if (int r = gmm_read_reach(c)) { reset_results(c); return r; }
   if (int r = gmm_combine(c, (double*)c->h_pin + pin_layout(c).moments, probability, stop)) { reset_results(c); return r; }
   note_obs_counts(c, Kind::Gmm);
+  if (int r = read_clearance(c, Kind::Gmm, c->num_gmm)) return r;
   c->res.last_gmm_count = count;
   c->res.last_gmm_wp = c->W - 1;
   lap("combined");
@@ -791,7 +854,8 @@ bool mc_stop_active(const pocs_ctx* c) { return c->opt_mc_rb && risk_active(c) &
 bool mc_counts_active(const pocs_ctx* c) { return c->opt_mc_wp || c->opt_obs_counts || mc_stop_active(c); }      // (the per-box counts split the per-waypoint ones)
 // The fused kernel carries a particle through all its steps and meets no other block on the way: a call that stops on a count
 // takes the per-step form.
-bool mc_fused_form(const pocs_ctx* c) { return c->opt_fused && !mc_stop_active(c); }
+// So does a call that counts clearance levels: the levels live in the per-step kernels (MC_CLEAR).
+bool mc_fused_form(const pocs_ctx* c) { return c->opt_fused && !mc_stop_active(c) && !clearance_applied(c); }
 // d_total, u64 words: [R] collided particles per run | counts active: [R][W] first collisions | [R] u32 stop words
 size_t mc_total_words(const pocs_ctx* c) {
   const size_t R = (size_t)c->batch, W = (size_t)c->W;
@@ -838,6 +902,10 @@ int enqueue_mc_all(Issuer is, long long first, long long count, bool prof) {
     a.obs_counts = (unsigned long long*)c->d_obsct.p;
     if (int r = enqueue_obs_counts_reset(is)) return r;
   }
+  if (clearance_applied(c)) {
+    a.clr = clear_at(c, 0); a.clr_counts = (unsigned long long*)c->d_clrct.p; a.clr_level = (unsigned char*)c->d_clrlv.p; a.clr_L = c->clr_L;
+    if (int r = enqueue_clearance_reset(is)) return r;
+  }
   if (c->plans.n) {
     a.run_plan = (const double*)c->d_runplan.p;      // every run its own start mean and steps
   } else {
@@ -860,6 +928,7 @@ int enqueue_mc_all(Issuer is, long long first, long long count, bool prof) {
       pocs_mc_launch as;
       memcpy(&as, &a, sizeof as);
       as.env = world_at(c, s + 1);                   // control s produces waypoint s + 1
+      if (as.clr) as.clr = clear_at(c, s + 1);
       int nb = nblk;
       if (c->plans.n) {
         as.nruns = live_runs(Ws, 0, R, s + 1);       // plans with a control at step s: W_p - 1 > s
@@ -971,6 +1040,8 @@ int mc_prepare(pocs_ctx* c, size_t runs, size_t chain_rows, size_t elems, size_t
   if (int r = ensure(c, c->d_hits, elems * sizeof(uint32_t))) return r;
   if (int r = ensure(c, c->d_total, total_bytes + 16)) return r;
   if (int r = ensure_obs_counts(c)) return r;
+  if (int r = ensure_clearance(c)) return r;
+  if (clearance_applied(c)) if (int r = ensure(c, c->d_clrlv, elems)) return r;
   if (int r = ensure_pin(c)) return r;
   return stage_and_upload_runs(c, 1, Kind::Mc);
 }
@@ -1027,6 +1098,7 @@ int run_mc_tree(pocs_ctx* c) {                      // (behind run_mc_local's ch
 // One batch of MC roll-outs (runSimulation x batch) over this context's shard; fills c->res.mc_counts.
 int run_mc_local(pocs_ctx* c) {
   c->res.oc_kind = Kind::None;
+  open_clearance(c);
   if (int r = check_common(c)) return r;
   if (c->num_particles < 1) return fail(c, POCS_E_STATE, "setNumParticles missing");
   if (int r = upload_static(c)) return r;
@@ -1061,7 +1133,7 @@ int run_mc_local(pocs_ctx* c) {
   if (mc_counts_active(c))
     if (int r = mc_read_waypoint_counts(c, tot)) { reset_results(c); return r; }
   note_obs_counts(c, Kind::Mc);
-  return POCS_OK;
+  return read_clearance(c, Kind::Mc, count);
 }
 
 }  // namespace pocs_rt
@@ -1098,6 +1170,7 @@ int pocs_gmm_begin(pocs_ctx* c) {
   if (int r = enqueue_ticket_reset(c)) return r;
   if (int r = enqueue_obs_counts_reset({c, nullptr})) return r;
   c->res.oc_kind = Kind::None;                                 // (the table is this sequence's from here on; served once pocs_gmm_end has closed it)
+  open_clearance(c);                                           // (the step API: the levels are not applied)
   c->xchg_calls += 1;
   c->gmm_open = true;
   c->res.last_gmm_wp = -1;

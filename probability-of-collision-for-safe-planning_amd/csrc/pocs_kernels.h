@@ -49,6 +49,16 @@ struct pocs_env_dev {            // collision world as the kernels see it (in HB
   double obs[POCS_MAX_OBSTACLES * POCS_OBS_STRIDE];
 };
 
+// Clearance levels (pocs_set_clearance_levels) as the kernels see them, in HBM beside the collision world: one record per step of
+// the obstacle schedule.  The distances and everything derived from them live HERE, not in launch arguments: a call's launches
+// carry the array's address and L, so other distances with the same L replay the cached graph.
+struct pocs_clear_dev {
+  pocs_footprint fp;             // the footprint grown by d[L - 1]
+  double fp_rr, fp_phi;          // its bounding radius and corner angle (pocs_footprint_extent_pre), for the cull
+  double d[POCS_MAX_CLEARANCE_LEVELS];
+  double obs[POCS_MAX_OBSTACLES * POCS_OBS_STRIDE];   // the step's boxes prepared (pocs_prepare_obstacle) for that footprint
+};
+
 struct pocs_run_header {         // per-run scalars read by every kernel (so a captured graph stays valid)
   uint64_t seed;
   uint64_t pad;                  // sharded whole calls: the context's count of exchange sequences (pocs_gmm_launch::xchg_epoch_from_header)
@@ -142,6 +152,13 @@ struct pocs_gmm_launch {
                                  // the caller's order, fields 6 and 7 tightened to the run's headings
   int* kept_idx;                 // [nruns][POCS_MAX_OBSTACLES] their indices in the caller's table
   int* reach;                    // [nruns][W] how many records the cull kept at (run, waypoint), the overflow included; zeroed per call
+  // clearance levels (pocs_set_clearance_levels; behind everything else again): non-null = the launch is the kernel's _clear form
+  // (ticket form, with or without the risk bound; never LONE, TREE, OC or WORLD), which also counts per level the samples drawn at
+  // (run, waypoint) that are within the level's clearance of the waypoint's world
+  const pocs_clear_dev* clr;     // the record of the launch's waypoint (aimed with `env`)
+  unsigned long long* clr_counts; // [nruns][W][POCS_MAX_CLEARANCE_LEVELS]; zeroed by pocs_launch_zero_counts at the head of the call's launches
+  int clr_L;                     // 1 .. POCS_MAX_CLEARANCE_LEVELS
+  int clr_pad;
 };
 #define POCS_MAX_WORLD_RECORDS 4096   // = POCS_MAX_WORLD_BOXES (include/pocs.h; pocs_ctx.hpp checks)
 #define POCS_CULL_BLOCK 256           // k_world_cull
@@ -195,6 +212,14 @@ struct pocs_mc_launch {               // blockIdx.y = run of the batch, like poc
   const double* world;                 // [world_M][POCS_OBS_STRIDE]; non-null: a large world
   int world_M;
   int world_pad;
+  // clearance levels (pocs_set_clearance_levels; behind everything else again): non-null = the MC_CLEAR forms of k_mc_init /
+  // k_mc_step_counts (per-step launches only), which keep per particle the smallest level it has been within so far and count per
+  // level the particles that are within it at waypoint w and at no waypoint before
+  const pocs_clear_dev* clr;           // the record of the launch's waypoint (aimed with `env`)
+  unsigned long long* clr_counts;      // [nruns][W][POCS_MAX_CLEARANCE_LEVELS]; zeroed inside the graph like obs_counts
+  unsigned char* clr_level;            // [nruns][stride] the particle's smallest level so far (clr_L: none); written by k_mc_init
+  int clr_L;
+  int clr_pad;
 };
 
 
@@ -213,6 +238,10 @@ hipError_t pocs_launch_probe_math(const pocs_tables* tables, int n, const uint32
 // x / y / th: n poses; flags: 3 x n (full table, pair, pair EAGER); nkeep: 1; kept: POCS_MAX_OBSTACLES records
 hipError_t pocs_launch_probe_collide(int K, const pocs_gmm_launch& a, int n, const double* x, const double* y, const double* th,
                                      int* flags, int* nkeep, double* kept, hipStream_t s);
+// one block; poses n x (x, y, th) by component; level_out[i]: -1 the footprint itself touches, else the smallest level, L for none
+// (+100 should the pair form ever disagree with the single-pose form).  env: base records of M boxes; clr: the grown ones
+hipError_t pocs_launch_probe_clearance(const pocs_env_dev* env, const pocs_clear_dev* clr, int L, const pocs_tables* tables, int n,
+                                       const double* x, const double* y, const double* th, int* level_out, hipStream_t s);
 hipError_t pocs_launch_mc_init(int nblk, const pocs_mc_launch& a, hipStream_t s);
 hipError_t pocs_launch_mc_step(int nblk, const pocs_mc_launch& a, hipStream_t s);
 hipError_t pocs_launch_mc_fused(int nblk, const pocs_mc_launch& a, hipStream_t s);

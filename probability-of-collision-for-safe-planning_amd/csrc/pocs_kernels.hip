@@ -54,6 +54,18 @@ hipError_t with_K(const int K, F f) {
 hipError_t pocs_launch_gmm_step(int K, const pocs_gmm_launch& a, hipStream_t s) {
   return with_K(K, [&](auto k) {
     constexpr int KK = decltype(k)::value, TB = POCS_GMM_BLOCK_OF(KK);
+    if (a.clr) {                                       // clearance levels: the ticket forms that also count per level
+      if (a.lone || a.obs_counts || a.world || a.tree_parent || a.exchange_in_tail || !a.clr_counts || a.clr_L < 1 || a.clr_L > POCS_MAX_CLEARANCE_LEVELS ||
+          a.M > POCS_MAX_OBSTACLES || (a.risk && (!a.stop || !a.surv)))
+        return hipErrorInvalidValue;
+      if (a.risk) {
+        if (a.store) hipLaunchKernelGGL((k_gmm_step_risk_clear<KK, true, TB>), dim3(a.blocks), dim3(TB), 0, s, a);
+        else         hipLaunchKernelGGL((k_gmm_step_risk_clear<KK, false, TB>), dim3(a.blocks), dim3(TB), 0, s, a);
+      } else {
+        if (a.store) hipLaunchKernelGGL((k_gmm_step_clear<KK, true, TB>), dim3(a.blocks), dim3(TB), 0, s, a);
+        else         hipLaunchKernelGGL((k_gmm_step_clear<KK, false, TB>), dim3(a.blocks), dim3(TB), 0, s, a);
+      }
+    } else
     if (a.world) {                                     // a large world: the ticket forms that fetch what k_world_cull has left
       if (a.lone || a.obs_counts || a.exchange_in_tail || a.tree_parent || !a.kept || !a.reach || a.M != 0 ||
           (a.risk && (!a.stop || !a.surv)))
@@ -163,6 +175,11 @@ hipError_t pocs_launch_mc_tree_step(int nblk, const pocs_mc_launch& a, hipStream
 
 hipError_t pocs_launch_mc_init(int nblk, const pocs_mc_launch& a, hipStream_t s) {
   if ((a.wp_mode != 0 && !a.wp_counts) || (a.obs_counts && !a.wp_mode)) return hipErrorInvalidValue;
+  if (a.clr) {                                        // clearance levels: the MC_CLEAR forms (a small world, no per-box counts)
+    if (a.world || a.obs_counts || !a.clr_counts || !a.clr_level || a.clr_L < 1 || a.clr_L > POCS_MAX_CLEARANCE_LEVELS) return hipErrorInvalidValue;
+    if (a.wp_mode) hipLaunchKernelGGL(k_mc_init<MC_COUNTS | MC_CLEAR>, dim3(nblk, a.nruns), dim3(POCS_BLOCK), 0, s, a);
+    else           hipLaunchKernelGGL(k_mc_init<MC_PLAIN | MC_CLEAR>, dim3(nblk, a.nruns), dim3(POCS_BLOCK), 0, s, a);
+  } else
   if (a.world) {                                      // a large world (no per-box counts there)
     if (a.obs_counts || a.world_M < 1 || a.world_M > POCS_MAX_WORLD_RECORDS) return hipErrorInvalidValue;
     if (a.wp_mode) hipLaunchKernelGGL(k_mc_init_world<MC_COUNTS>, dim3(nblk, a.nruns), dim3(POCS_BLOCK), 0, s, a);
@@ -176,6 +193,21 @@ hipError_t pocs_launch_mc_init(int nblk, const pocs_mc_launch& a, hipStream_t s)
 hipError_t pocs_launch_mc_step(int nblk, const pocs_mc_launch& a, hipStream_t s) {
   const dim3 grid(nblk, a.nruns), block(POCS_BLOCK);
   if ((a.wp_mode != 0 && !a.wp_counts) || (a.obs_counts && !a.wp_mode)) return hipErrorInvalidValue;
+  if (a.clr) {                                        // clearance levels: the MC_CLEAR forms of the three modes
+    if (a.world || a.obs_counts || !a.clr_counts || !a.clr_level || a.clr_L < 1 || a.clr_L > POCS_MAX_CLEARANCE_LEVELS || a.step < 0 || a.step + 1 >= a.W ||
+        (a.wp_mode == 2 && (!a.wp_stop || a.wp_n < 1)))
+      return hipErrorInvalidValue;
+    if (a.wp_mode == 2) {
+      if (a.nontemporal) hipLaunchKernelGGL((k_mc_step_counts<true, MC_STOP | MC_CLEAR>), grid, block, 0, s, a);
+      else               hipLaunchKernelGGL((k_mc_step_counts<false, MC_STOP | MC_CLEAR>), grid, block, 0, s, a);
+    } else if (a.wp_mode == 1) {
+      if (a.nontemporal) hipLaunchKernelGGL((k_mc_step_counts<true, MC_COUNTS | MC_CLEAR>), grid, block, 0, s, a);
+      else               hipLaunchKernelGGL((k_mc_step_counts<false, MC_COUNTS | MC_CLEAR>), grid, block, 0, s, a);
+    } else {
+      if (a.nontemporal) hipLaunchKernelGGL((k_mc_step_counts<true, MC_PLAIN | MC_CLEAR>), grid, block, 0, s, a);
+      else               hipLaunchKernelGGL((k_mc_step_counts<false, MC_PLAIN | MC_CLEAR>), grid, block, 0, s, a);
+    }
+  } else
   if (a.world) {                                      // a large world: the same three modes, no per-box counts
     if (a.obs_counts || a.world_M < 1 || a.world_M > POCS_MAX_WORLD_RECORDS) return hipErrorInvalidValue;
     if (a.wp_mode != 0 && (a.step < 0 || a.step + 1 >= a.W || (a.wp_mode == 2 && (!a.wp_stop || a.wp_n < 1)))) return hipErrorInvalidValue;
@@ -213,6 +245,7 @@ hipError_t pocs_launch_mc_step(int nblk, const pocs_mc_launch& a, hipStream_t s)
 }
 hipError_t pocs_launch_mc_fused(int nblk, const pocs_mc_launch& a, hipStream_t s) {
   if (a.wp_mode == 2 || (a.wp_mode != 0 && !a.wp_counts) || (a.obs_counts && !a.wp_mode)) return hipErrorInvalidValue;      // (no stop without a launch boundary per step)
+  if (a.clr) return hipErrorInvalidValue;             // (clearance levels: the per-step form)
   if (a.world) return hipErrorInvalidValue;           // (a large world is not staged: no fused form)
   if (a.obs_counts) {
     if (a.env_steps > 1) hipLaunchKernelGGL(k_mc_fused_sched<MC_COUNTS | MC_BOXES>, dim3(nblk, a.nruns), dim3(POCS_BLOCK), 0, s, a);
@@ -354,6 +387,53 @@ hipError_t pocs_launch_probe_collide(int K, const pocs_gmm_launch& a, int n, con
     hipLaunchKernelGGL((k_probe_collide<KK, TB>), dim3(1), dim3(TB), 0, s, a, n, x, y, th, flags, nkeep, kept);
     return hipGetLastError();
   });
+}
+// The clearance level of poses, a footprint, distances and a world the caller picks (pocs_probe_device_clearance: a test hook beside
+// k_probe_collide): ONE block stages the tables, the base records and the records of the footprint grown by the largest distance as
+// the kernels' heads do and asks, per pose, the functions the kernels ask: pocs_pose_collides for the footprint itself (-1), then
+// pocs_pose_clearance_level as the MC kernels call it; and pocs_pair_clearance_masks as k_gmm_step's clearance form calls it, pose
+// 2 p with pose 2 p + 1 (an odd last pose with itself) -- 100 is added to a pose's answer should the two forms ever disagree.
+__global__ __launch_bounds__(POCS_BLOCK) void k_probe_clearance(const pocs_env_dev* __restrict__ env, const pocs_clear_dev* __restrict__ clr, int L,
+                                                                const pocs_tables* __restrict__ tables, int n, const double* __restrict__ x,
+                                                                const double* __restrict__ y, const double* __restrict__ th, int* __restrict__ out) {
+  __shared__ pocs_tables s_tab;
+  __shared__ __attribute__((aligned(16))) double s_obs[POCS_MAX_OBSTACLES * POCS_OBS_STRIDE];
+  __shared__ __attribute__((aligned(16))) double s_obs2[POCS_MAX_OBSTACLES * POCS_OBS_STRIDE];
+  __shared__ double s_d[POCS_MAX_CLEARANCE_LEVELS];
+  stage_tables(tables, &s_tab);
+  for (int j = threadIdx.x; j < POCS_MAX_OBSTACLES * POCS_OBS_STRIDE; j += POCS_BLOCK) { s_obs[j] = env->obs[j]; s_obs2[j] = clr->obs[j]; }
+  if (threadIdx.x < POCS_MAX_CLEARANCE_LEVELS) s_d[threadIdx.x] = clr->d[threadIdx.x];
+  __syncthreads();
+  const pocs_footprint fp = env->fp;
+  const int M = env->M;
+  POCS_VCONST(vc_);
+  const int npairs = (n + 1) / 2;
+  // (every lane of a wave makes every trip: the pair form ballots)
+  for (int p0 = (int)threadIdx.x - (int)(threadIdx.x & 63); p0 < npairs; p0 += POCS_BLOCK) {
+    const int p = p0 + (int)(threadIdx.x & 63);
+    const bool live = p < npairs;
+    const int i0 = live ? 2 * p : 0, i1 = live && i0 + 1 < n ? i0 + 1 : i0;
+    const double xs[2] = {x[i0], x[i1]}, ys[2] = {y[i0], y[i1]}, ts[2] = {th[i0], th[i1]};
+    int single[2], pair[2] = {L, L};
+#pragma unroll
+    for (int h = 0; h < 2; ++h)
+      single[h] = pocs_pose_collides(xs[h], ys[h], ts[h], &fp, s_obs, M, &s_tab) ? -1
+                : pocs_pose_clearance_level(xs[h], ys[h], ts[h], &fp, s_d, L, s_obs2, M, &s_tab);
+    pocs_pair_clearance_masks(xs, ys, ts, &fp, s_d, L, s_obs2, M, &s_tab, &vc_, [&](const int l, const unsigned long long m0, const unsigned long long m1) {
+      if (__builtin_amdgcn_inverse_ballot_w64(m0)) pair[0] = l;
+      if (__builtin_amdgcn_inverse_ballot_w64(m1)) pair[1] = l;
+    });
+    if (live) {
+      out[i0] = single[0] + ((single[0] >= 0 && pair[0] != single[0]) || (i1 == i0 && single[1] != single[0]) ? 100 : 0);
+      if (i1 != i0) out[i1] = single[1] + (single[1] >= 0 && pair[1] != single[1] ? 100 : 0);
+    }
+  }
+}
+hipError_t pocs_launch_probe_clearance(const pocs_env_dev* env, const pocs_clear_dev* clr, int L, const pocs_tables* tables, int n,
+                                       const double* x, const double* y, const double* th, int* level_out, hipStream_t s) {
+  if (!env || !clr || !tables || n < 1 || L < 0 || L > POCS_MAX_CLEARANCE_LEVELS || !x || !y || !th || !level_out) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(k_probe_clearance, dim3(1), dim3(POCS_BLOCK), 0, s, env, clr, L, tables, n, x, y, th, level_out);
+  return hipGetLastError();
 }
 hipError_t pocs_launch_fill(void* dst, long long bytes, hipStream_t s) {
   hipLaunchKernelGGL(k_fill, dim3(8192), dim3(POCS_BLOCK), 0, s, (double2*)dst, bytes / 16, 1.5);
