@@ -427,7 +427,8 @@ int pocs_get_obstacle_counts(pocs_ctx* ctx, unsigned long long* out, int cap, in
  * under a large world), an MC call the per-step form whatever POCS_OPT_MC_FUSED says (as under the MC risk bound).  No other
  * result of any call changes by a bit.  NOT applied -- never refused: a tree of plans, a large world (pocs_set_world with more than
  * 64 boxes), POCS_OPT_OBSTACLE_COUNTS = 1, a shard (with it a bound moments buffer and the exchange) and the step API: there the call
- * is launch for launch and bit for bit the call it is with L = 0, and the two getters below answer POCS_E_STATE.
+ * is launch for launch and bit for bit the call it is with L = 0, and the two getters below answer POCS_E_STATE.  The same holds
+ * while a compound footprint is set (pocs_set_footprint_parts with F > 1): the call is the call with L = 0 under that footprint.
  *
  * pocs_get_clearance_counts serves the selected run (pocs_select_batch_run; plan p while plans are set; the run served last under
  * run-ahead): writes the table A, E x L row-major, sets *levels = L and returns E, the waypoints covered -- a plan's own length, or
@@ -451,6 +452,38 @@ int pocs_set_clearance_levels(pocs_ctx* ctx, const double* d, int L);
 int pocs_get_clearance_levels(const pocs_ctx* ctx, double* d, int cap);     /* writes and returns L */
 int pocs_get_clearance_counts(pocs_ctx* ctx, unsigned long long* out, int cap, int* levels);
 int pocs_get_batch_clearance_probabilities(pocs_ctx* ctx, int level, double* out, int cap);
+
+/* ---- compound footprints: a robot of up to four boxes, for both estimators (ours) ----------------
+ * A compound footprint is F parts, 1 <= F <= POCS_MAX_FOOTPRINT_PARTS.  Part f is {dx, dy, half_x, half_y}, exactly a
+ * pocs_set_footprint footprint: an offset in the base frame and half extents, with no yaw of its own.
+ *   touches   a pose touches a world exactly when the collision test (pocs_pose_collides) answers "touches" for at least one part
+ *             taken alone as the footprint.  Per part the same operations run in the same order, so the flag is the OR of the parts'
+ *             flags, touching included.
+ * Everything downstream is what it is today, formed from that flag: the truncation, moment sums, nColl, probabilities and risk
+ * bound on the GMM path; hit counters, first-collision profile, counts and the MC risk bound on the MC path.
+ *
+ * pocs_set_footprint_parts: F = 1 IS pocs_set_footprint(parts[0..3]) -- the same device state, the same kernels, the same bits (as
+ * pocs_set_world with at most 64 boxes is pocs_set_obstacles).  POCS_E_ARG, with the footprint in force kept: F out of range, a null
+ * pointer, a value that is not finite, a half extent <= 0.  pocs_set_footprint and the text channel's setFootprint replace a
+ * compound footprint with the single box.  Like every setter it ends run-ahead serving; it re-prepares the records of every world
+ * step, as pocs_set_footprint does.  The text channel has no command for it.  pocs_get_footprint_parts writes the parts in force and
+ * returns F (1 after pocs_set_footprint); POCS_E_BUFFER for cap < F.
+ *
+ * SERVED (F > 1): whole calls on one GPU -- pocs_run_gmm_estimation, pocs_run_simulation, pocs_mc_run_local -- as single runs,
+ * batches in both sub-batch forms, run-ahead, calls of plans with and without the risk bound (GMM, and MC with
+ * POCS_OPT_MC_RISK_BOUND), POCS_OPT_MC_WAYPOINT_COUNTS, POCS_OPT_STORE_SAMPLES (stored flags are the compound flags), over static
+ * worlds of up to 64 boxes and obstacle schedules.  A GMM call of one run takes the ticket form (POCS_OPT_LONE_CALL has no effect,
+ * as under a large world), an MC call the per-step form whatever POCS_OPT_MC_FUSED says (as under the MC risk bound).  New values
+ * with the same F replay the cached graph (the values live in device memory); a change of F may capture again.
+ * REFUSED, never silently served with one box -- a compound footprint changes results: a tree of plans, a large world (more than
+ * 64 boxes), a shard, the exchange (created or connected), a bound moments buffer, an open begin/end sequence and pocs_gmm_begin,
+ * POCS_OPT_OBSTACLE_COUNTS = 1, pocs_probe_device_collide.  In both directions, with the context left as it was:
+ * pocs_set_footprint_parts(F > 1) under any of these answers POCS_E_STATE (POCS_E_ORDER inside a begin/end sequence) and names what
+ * is in the way; entering any of them while F > 1 answers POCS_E_STATE, and the message names the call and "a compound footprint
+ * is set (pocs_set_footprint_parts)".  Clearance levels are not applied while F > 1 (see there). */
+#define POCS_MAX_FOOTPRINT_PARTS 4
+int pocs_set_footprint_parts(pocs_ctx* ctx, const double* parts /* F x {dx, dy, half_x, half_y} */, int F);
+int pocs_get_footprint_parts(const pocs_ctx* ctx, double* parts, int cap /* in parts */);   /* writes and returns F (1 after pocs_set_footprint) */
 
 /* ---- results of the last run, for audits and parity tests ------------------------------- */
 int pocs_get_path_length(const pocs_ctx* ctx);
@@ -506,6 +539,15 @@ int pocs_probe_device_clearance(pocs_ctx* ctx, const double* fp4, const double* 
    sampling kernel on poses 2 j, 2 j + 1: 100 is added should the two ever disagree).  It reads nothing of the context's world,
    plans or modes, so it is never refused.  POCS_E_ARG for a null pointer, n outside 1 .. 2^20, bad distances or boxes and ANY
    input that is not finite. */
+int pocs_probe_device_footprint_parts(pocs_ctx* ctx, const double* parts, int F, const double* boxes, int M,
+                                      int n, const double* poses_xyt, int* touched_out);
+/* TEST HOOK beside pocs_probe_device_clearance, equally self-contained: which parts of the caller's own compound footprint (F parts
+   as pocs_set_footprint_parts takes them, 1 <= F <= POCS_MAX_FOOTPRINT_PARTS) touch the caller's own table of M <= 64 boxes {cx, cy,
+   half_x, half_y, yaw_rad}, prepared as the library prepares the context's.  One small launch stages them; per pose i < n
+   touched_out[i] is a bit mask, bit f set when part f touches -- through the inline functions the kernels use (the single-pose form
+   of the MC kernels, and the two-pose lane-mask form of the GMM sampling kernel on poses 2 j, 2 j + 1: bit 8 is set should the two
+   ever disagree).  It reads nothing of the context's world or modes, so it is never refused.  POCS_E_ARG for a null pointer, n
+   outside 1 .. 2^20, bad parts or boxes and ANY input that is not finite. */
 int pocs_get_sequence_time(pocs_ctx* ctx, double* ms, int* concurrent);  /* POCS_OPT_PROFILE=1, whole-run GMM calls: first sampling launch -> end of the last one, and how many
                                                                             sub-batches of the call were in flight side by side (their launches overlap: DESIGN.md section 5) */
 

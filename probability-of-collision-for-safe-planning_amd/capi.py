@@ -23,6 +23,7 @@ MAX_TREE_NODES = 4096
 MAX_WORLD_STEPS = 4096
 MAX_WORLD_BOXES = 4096             # POCS_MAX_WORLD_BOXES: the largest table pocs_set_world takes
 MAX_CLEARANCE_LEVELS = 4           # POCS_MAX_CLEARANCE_LEVELS: the most distances pocs_set_clearance_levels takes
+MAX_FOOTPRINT_PARTS = 4            # POCS_MAX_FOOTPRINT_PARTS: the most parts pocs_set_footprint_parts takes
 
 _dp = C.POINTER(C.c_double)
 _vp = C.c_void_p
@@ -86,6 +87,9 @@ SIGNATURES = {
     "pocs_get_clearance_counts": (C.c_int, [_vp, C.POINTER(C.c_ulonglong), C.c_int, C.POINTER(C.c_int)]),
     "pocs_get_batch_clearance_probabilities": (C.c_int, [_vp, C.c_int, _dp, C.c_int]),
     "pocs_probe_device_clearance": (C.c_int, [_vp, _dp, _dp, C.c_int, _dp, C.c_int, C.c_int, _dp, C.POINTER(C.c_int)]),
+    "pocs_set_footprint_parts": (C.c_int, [_vp, _dp, C.c_int]),
+    "pocs_get_footprint_parts": (C.c_int, [_vp, _dp, C.c_int]),
+    "pocs_probe_device_footprint_parts": (C.c_int, [_vp, _dp, C.c_int, _dp, C.c_int, C.c_int, _dp, C.POINTER(C.c_int)]),
     "pocs_xchg_create": (C.c_int, [_vp, C.c_int, C.c_int, C.c_void_p]),
     "pocs_xchg_connect": (C.c_int, [_vp, C.c_void_p, C.c_int]),
     "pocs_gmm_exchange_local": (C.c_int, [_vp, C.c_int]),
@@ -242,8 +246,11 @@ class Context:
 
     # ---- typed setters ----------------------------------------------------------------
     def set_env(self, env):
-        fp = env["footprint"]
-        self._chk(self.lib.pocs_set_footprint(self.h, fp[0], fp[1], fp[2], fp[3]))
+        if "footprint_parts" in env:        # a compound footprint (set_footprint_parts) in place of the single box
+            self.set_footprint_parts(env["footprint_parts"])
+        else:
+            fp = env["footprint"]
+            self._chk(self.lib.pocs_set_footprint(self.h, fp[0], fp[1], fp[2], fp[3]))
         if env.get("boxes") is None:        # footprint only: the world itself is left as it is
             return
         b = _arr(env["boxes"]).reshape(-1, 5)
@@ -510,6 +517,30 @@ class Context:
         self._chk(self.lib.pocs_probe_device_clearance(self.h, fp.ctypes.data_as(_dp), d.ctypes.data_as(_dp) if d.size else None, d.size,
                                                        b.ctypes.data_as(_dp) if b.size else None, b.shape[0], xyt.shape[0],
                                                        xyt.ctypes.data_as(_dp), out.ctypes.data_as(C.POINTER(C.c_int))))
+        return out
+
+    def set_footprint_parts(self, parts):
+        """A compound footprint: F x (dx, dy, half_x, half_y), 1 <= F <= MAX_FOOTPRINT_PARTS; a pose touches when one of the parts
+        does.  One part is set_footprint (include/pocs.h)."""
+        q = _arr(parts).reshape(-1, 4)
+        self._chk(self.lib.pocs_set_footprint_parts(self.h, q.ctypes.data_as(_dp) if q.size else None, q.shape[0]))
+
+    def footprint_parts(self):
+        """The parts in force: an (F, 4) float64 array (F = 1 after set_footprint)."""
+        out = np.zeros((MAX_FOOTPRINT_PARTS, 4))
+        got = self._chk(self.lib.pocs_get_footprint_parts(self.h, out.ctypes.data_as(_dp), MAX_FOOTPRINT_PARTS))
+        return out[:got]
+
+    def probe_footprint_parts(self, parts, boxes, poses):
+        """Test hook: per pose (n x 3) the parts (F x 4) of the caller's own compound footprint that touch the caller's own boxes
+        (M x 5) on the device: int32[n], bit f = part f touches, bit 8 = the kernels' two forms disagree (never)."""
+        q = _arr(parts).reshape(-1, 4)
+        b = _arr(boxes).reshape(-1, 5)
+        xyt = _arr(poses).reshape(-1, 3)
+        out = np.full(xyt.shape[0], -1, dtype=np.int32)
+        self._chk(self.lib.pocs_probe_device_footprint_parts(self.h, q.ctypes.data_as(_dp) if q.size else None, q.shape[0],
+                                                             b.ctypes.data_as(_dp) if b.size else None, b.shape[0], xyt.shape[0],
+                                                             xyt.ctypes.data_as(_dp), out.ctypes.data_as(C.POINTER(C.c_int))))
         return out
 
     def gmm_begin(self):

@@ -203,8 +203,45 @@ int pocs_set_footprint(pocs_ctx* c, double dx, double dy, double hx, double hy) 
   if (!setter(c)) return POCS_E_ARG;
   if (!(hx > 0) || !(hy > 0)) return fail(c, POCS_E_ARG, "footprint half extents must be > 0");
   c->fp.dx = dx; c->fp.dy = dy; c->fp.hx = hx; c->fp.hy = hy;
+  c->fp_F = 1; c->fp_parts[0] = c->fp;               // (a compound footprint is replaced by the single box)
   c->env_dirty = true;
   return POCS_OK;
+}
+
+// ---- compound footprints (include/pocs.h) ----
+int pocs_set_footprint_parts(pocs_ctx* c, const double* parts, int F) {
+  if (!setter(c)) return POCS_E_ARG;
+  if (!parts || F < 1 || F > POCS_MAX_FOOTPRINT_PARTS)
+    return fail(c, POCS_E_ARG, "pocs_set_footprint_parts: %d parts outside 1..%d (or null parts)", F, POCS_MAX_FOOTPRINT_PARTS);
+  for (int j = 0; j < 4 * F; ++j)
+    if (!std::isfinite(parts[j])) return fail(c, POCS_E_ARG, "pocs_set_footprint_parts: part %d: value %d is not finite", j / 4, j % 4);
+  for (int f = 0; f < F; ++f)
+    if (!(parts[4 * f + 2] > 0) || !(parts[4 * f + 3] > 0)) return fail(c, POCS_E_ARG, "pocs_set_footprint_parts: part %d: half extents must be > 0", f);
+  if (F == 1) return pocs_set_footprint(c, parts[0], parts[1], parts[2], parts[3]);
+  // (not a mode of the table: the one mask of what a compound footprint excludes, pocs_modes.hpp)
+  unsigned in_the_way = modes_of(c) & pocs_modes::kPartsExcluded;
+  if (in_the_way) {                                  // names ONE mode: the open sequence before all others, a connected exchange before its buffer
+    const bool open = (in_the_way & pocs_modes::kSequence) != 0;
+    if (open) in_the_way = pocs_modes::kSequence;
+    if (in_the_way & pocs_modes::kXchgConnected) in_the_way &= ~(unsigned)pocs_modes::kXchgCreated;
+    return fail(c, open ? POCS_E_ORDER : POCS_E_STATE, "pocs_set_footprint_parts: %s; %s",
+                pocs_modes::name((pocs_modes::Mode)(in_the_way & (0u - in_the_way))), pocs_modes::kPartsClause);
+  }
+  for (int f = 0; f < F; ++f) c->fp_parts[f] = pocs_footprint{parts[4 * f], parts[4 * f + 1], parts[4 * f + 2], parts[4 * f + 3]};
+  c->fp_F = F;
+  c->fp = c->fp_parts[0];
+  c->env_dirty = true;
+  return POCS_OK;
+}
+
+int pocs_get_footprint_parts(const pocs_ctx* c, double* parts, int cap) {
+  if (!c || !parts) return POCS_E_ARG;
+  if (cap < c->fp_F) return POCS_E_BUFFER;
+  for (int f = 0; f < c->fp_F; ++f) {
+    const pocs_footprint& q = c->fp_F > 1 ? c->fp_parts[f] : c->fp;
+    parts[4 * f] = q.dx; parts[4 * f + 1] = q.dy; parts[4 * f + 2] = q.hx; parts[4 * f + 3] = q.hy;
+  }
+  return c->fp_F;
 }
 
 int pocs_set_obstacles(pocs_ctx* c, const double* boxes, int M) {

@@ -349,6 +349,55 @@ int pocs_probe_device_clearance(pocs_ctx* c, const double* fp4, const double* d,
   return rc;
 }
 
+// Test hook: which parts of a compound footprint touch, on the device, for chosen poses, parts and boxes (include/pocs.h).  Nothing of
+// the context's world, plans or modes is read: the records and the parts are prepared here, as upload_world prepares the context's.
+int pocs_probe_device_footprint_parts(pocs_ctx* c, const double* parts, int F, const double* boxes, int M, int n,
+                                      const double* poses, int* touched_out) {
+  if (!c) return POCS_E_ARG;
+  if (!parts || !poses || !touched_out || n < 1 || n > (1 << 20) || F < 1 || F > POCS_MAX_FOOTPRINT_PARTS || M < 0 || M > POCS_MAX_OBSTACLES || (M > 0 && !boxes))
+    return fail(c, POCS_E_ARG, "pocs_probe_device_footprint_parts: 1 <= n <= 2^20, 1 <= F <= %d, 0 <= M <= %d, no null pointers", POCS_MAX_FOOTPRINT_PARTS, POCS_MAX_OBSTACLES);
+  for (int j = 0; j < 4 * F; ++j)
+    if (!std::isfinite(parts[j])) return fail(c, POCS_E_ARG, "pocs_probe_device_footprint_parts: part %d: value %d is not finite", j / 4, j % 4);
+  for (int f = 0; f < F; ++f)
+    if (!(parts[4 * f + 2] > 0) || !(parts[4 * f + 3] > 0)) return fail(c, POCS_E_ARG, "pocs_probe_device_footprint_parts: part %d: half extents must be > 0", f);
+  for (size_t j = 0; j < 5 * (size_t)M; ++j)
+    if (!std::isfinite(boxes[j])) return fail(c, POCS_E_ARG, "pocs_probe_device_footprint_parts: box %zu: value %zu is not finite", j / 5, j % 5);
+  for (int m = 0; m < M; ++m)
+    if (!(boxes[5 * (size_t)m + 2] > 0) || !(boxes[5 * (size_t)m + 3] > 0)) return fail(c, POCS_E_ARG, "pocs_probe_device_footprint_parts: box %d: half extents must be > 0", m);
+  for (size_t j = 0; j < 3 * (size_t)n; ++j)
+    if (!std::isfinite(poses[j])) return fail(c, POCS_E_ARG, "pocs_probe_device_footprint_parts: pose %zu is not finite", j / 3);
+  HIPCHK(c, hipSetDevice(c->device));
+  if (int r = upload_tables(c)) return r;
+  pocs_footprint fps[POCS_MAX_FOOTPRINT_PARTS];
+  for (int f = 0; f < F; ++f) fps[f] = pocs_footprint{parts[4 * f], parts[4 * f + 1], parts[4 * f + 2], parts[4 * f + 3]};
+  std::vector<pocs_env_dev> env(1);
+  pocs_parts_dev pd;
+  prepare_parts(fps, F, boxes, M, env.data(), &pd);
+  std::vector<double> h(3 * (size_t)n);
+  for (int i = 0; i < n; ++i)
+    for (int j = 0; j < 3; ++j) h[(size_t)j * n + i] = poses[3 * (size_t)i + j];
+  // [env | parts | x | y | th] then [touched n] ints
+  const size_t off_parts = sizeof(pocs_env_dev), off_x = off_parts + sizeof(pocs_parts_dev), off_out = off_x + 3 * (size_t)n * sizeof(double);
+  static_assert(sizeof(pocs_env_dev) % 8 == 0 && sizeof(pocs_parts_dev) % 8 == 0, "the probe's buffer keeps its parts aligned");
+  char* buf = nullptr;
+  HIPCHK(c, hipMalloc((void**)&buf, off_out + (size_t)n * sizeof(int)));
+  int rc = POCS_OK;
+  if (hipMemcpy(buf, env.data(), sizeof(pocs_env_dev), hipMemcpyHostToDevice) != hipSuccess ||
+      hipMemcpy(buf + off_parts, &pd, sizeof(pocs_parts_dev), hipMemcpyHostToDevice) != hipSuccess ||
+      hipMemcpy(buf + off_x, h.data(), h.size() * sizeof(double), hipMemcpyHostToDevice) != hipSuccess ||
+      hipMemset(buf + off_out, 0, (size_t)n * sizeof(int)) != hipSuccess)
+    rc = fail(c, POCS_E_DEVICE, "probe upload failed");
+  const double* d_x = (const double*)(buf + off_x);
+  if (rc == POCS_OK && pocs_launch_probe_parts((const pocs_env_dev*)buf, (const pocs_parts_dev*)(buf + off_parts), F, (const pocs_tables*)c->d_tables.p, n,
+                                               d_x, d_x + n, d_x + 2 * (size_t)n, (int*)(buf + off_out), c->stream) != hipSuccess)
+    rc = fail(c, POCS_E_DEVICE, "probe launch failed");
+  if (rc == POCS_OK && hipStreamSynchronize(c->stream) != hipSuccess) rc = fail(c, POCS_E_DEVICE, "probe kernel failed");
+  if (rc == POCS_OK && hipMemcpy(touched_out, buf + off_out, (size_t)n * sizeof(int), hipMemcpyDeviceToHost) != hipSuccess)
+    rc = fail(c, POCS_E_DEVICE, "probe download failed");
+  (void)hipFree(buf);
+  return rc;
+}
+
 int pocs_get_sequence_time(pocs_ctx* c, double* ms, int* concurrent) {
   if (!c) return POCS_E_ARG;
   if (ms) *ms = c->seq_ms;

@@ -412,3 +412,131 @@ __device__ __forceinline__ void pocs_pair_clearance_masks(const double x[2], con
   }
 }
 #endif
+
+// ---- compound footprints (pocs_set_footprint_parts) ------------------------------------------------------------------
+// A compound footprint is F parts, each {dx, dy, hx, hy} exactly a pocs_footprint: an offset in the base frame and half
+// extents, no yaw of its own.  A pose touches a world exactly when pocs_pose_collides answers "touches" for at least one
+// part taken alone as the footprint: per part the same operations in the same order, the flag the OR of the parts' flags.
+// A part as the kernels hold it is POCS_PART_STRIDE doubles: dx dy hx hy, then its bounding radius sqrt(hx^2 + hy^2) and
+// corner angle atan2(hy, hx) (pocs_footprint_extent_pre), which only the GMM cull reads.  The records are those prepared
+// (pocs_prepare_obstacle) for the part with the largest bounding radius: fields 0 .. 5 do not depend on the footprint, and
+// a broad phase sized for the largest part is conservative for the others.  The functions above stay what they are.
+#define POCS_MAX_FOOTPRINT_PARTS 4
+#define POCS_PART_STRIDE 6
+
+// Which of the parts (each a pocs_footprint) has the largest bounding radius: the one the records are prepared for.
+POCS_HD int pocs_parts_cover(const pocs_footprint* parts, int F) {
+  int best = 0;
+  double rbest = -1.0;
+  for (int f = 0; f < F; ++f) {
+    const double rr = sqrt(parts[f].hx * parts[f].hx + parts[f].hy * parts[f].hy);
+    if (rr > rbest) { rbest = rr; best = f; }
+  }
+  return best;
+}
+POCS_HD void pocs_prepare_part(const pocs_footprint* fp, double* rec) {
+  rec[0] = fp->dx; rec[1] = fp->dy; rec[2] = fp->hx; rec[3] = fp->hy;
+  rec[4] = sqrt(fp->hx * fp->hx + fp->hy * fp->hy);
+  rec[5] = atan2(fp->hy, fp->hx);
+}
+
+// One pose: bit f of the answer is set when part f touches some record.  The heading's sine and cosine once per pose;
+// (px, py) per part as pocs_pose_collides forms it, pocs_box_hit per part and record as there.
+POCS_HD unsigned pocs_pose_parts_touched(double x, double y, double th, const double* parts, int F,
+                                         const double* obs, int M, const pocs_tables* T, const pocs_vconst* V = nullptr) {
+  if (M <= 0) return 0u;
+  double sn, cs;
+  pocs_sincos_tab(th, T, &sn, &cs, V);
+  unsigned touched = 0u;
+  for (int f = 0; f < F; ++f) {
+    const double* q = parts + f * POCS_PART_STRIDE;
+    const double dx = q[0], dy = q[1], rx = q[2], ry = q[3];
+    double px = x, py = y;
+    if (!(dx == 0.0 && dy == 0.0)) {
+      px = x + fma(cs, dx, -(sn * dy));
+      py = y + fma(sn, dx, cs * dy);
+    }
+    bool hit = false;
+    for (int m = 0; m < M; ++m)
+      if (pocs_box_hit(px, py, sn, cs, rx, ry, obs + m * POCS_OBS_STRIDE)) hit = true;
+    if (hit) touched |= 1u << f;
+  }
+  return touched;
+}
+POCS_HD bool pocs_pose_collides_parts(double x, double y, double th, const double* parts, int F,
+                                      const double* obs, int M, const pocs_tables* T, const pocs_vconst* V = nullptr) {
+  return pocs_pose_parts_touched(x, y, th, parts, F, obs, M, T, V) != 0u;
+}
+
+#if defined(__HIPCC__)
+// The same for the pair of poses a thread of k_gmm_step draws, as lane masks in the manner of pocs_pair_collides_masks:
+// mask[h] bit l = lane l's pose h touches with some part; each(f, m0, m1) is called once per part with the part's own two
+// masks.  The two headings' sines and cosines are computed once per call; per part the loop of pocs_pair_loop over the
+// records -- one fetch per record for both poses, the narrow phase behind wave-uniform branches, every answer balloted.
+// `parts` and `obs` lie in LDS.  F and M are wave-uniform.
+struct pocs_each_part_none { __device__ __forceinline__ void operator()(int, unsigned long long, unsigned long long) const {} };
+
+template <class Each = pocs_each_part_none>
+__device__ __forceinline__ void pocs_pair_parts_masks(const double x[2], const double y[2], const double th[2], const double* parts, int F,
+                                                      const double* obs, int M, const pocs_tables* T, const pocs_vconst* V,
+                                                      unsigned long long mask[2], Each each = Each()) {
+  unsigned long long all0 = 0ull, all1 = 0ull;
+  double sn[2] = {0.0, 0.0}, cs[2] = {1.0, 1.0};
+  if (M > 0) {                                                       // (scalar)
+#pragma unroll
+    for (int h = 0; h < 2; ++h) pocs_sincos_tab(th[h], T, &sn[h], &cs[h], V);
+  }
+#pragma unroll 1
+  for (int f = 0; f < F; ++f) {
+    unsigned long long m0 = 0ull, m1 = 0ull;
+    if (M > 0) {
+      const double* q = parts + f * POCS_PART_STRIDE;
+      const double fdx = q[0], fdy = q[1], rx = q[2], ry = q[3];
+      const bool offset = __builtin_amdgcn_ballot_w64(!(fdx == 0.0 && fdy == 0.0)) != 0ull;      // (scalar: every lane reads the same part)
+      double px[2], py[2], ex[2], ey[2];
+#pragma unroll
+      for (int h = 0; h < 2; ++h) {
+        px[h] = x[h]; py[h] = y[h];
+        if (offset) {
+          px[h] = x[h] + fma(cs[h], fdx, -(sn[h] * fdy));
+          py[h] = y[h] + fma(sn[h], fdx, cs[h] * fdy);
+        }
+        ex[h] = fma(rx, fabs(cs[h]), ry * fabs(sn[h]));
+        ey[h] = fma(rx, fabs(sn[h]), ry * fabs(cs[h]));
+      }
+      const __attribute__((address_space(3))) pocs_v2d* o = (const __attribute__((address_space(3))) pocs_v2d*)obs;
+      asm volatile("" : "+v"(o));
+      for (int m = 0; m < M; ++m, o += POCS_OBS_STRIDE / 2) {
+        const pocs_v2d c = o[0], b = o[3], a = o[1], e = o[2];       // (cx, cy) (bx, by) | (ax, ay) (hx, hy)
+        double dx[2], dy[2];
+        unsigned long long pm[2], bt[2] = {0ull, 0ull};
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {                                // pocs_box_hit's broad phase
+          dx[h] = c.x - px[h];
+          dy[h] = c.y - py[h];
+          pm[h] = __builtin_amdgcn_ballot_w64(!(fabs(dx[h]) > b.x)) & __builtin_amdgcn_ballot_w64(!(fabs(dy[h]) > b.y));
+        }
+        if ((pm[0] | pm[1]) != 0ull) {                               // pocs_box_narrow for the lanes inside the box
+          const bool turned = (__builtin_amdgcn_ballot_w64(a.x != 1.0) | __builtin_amdgcn_ballot_w64(a.y != 0.0)) != 0ull;
+#pragma unroll
+          for (int h = 0; h < 2; ++h) {
+            if (pm[h] == 0ull) continue;
+            if (!turned)
+              bt[h] = pocs_box_margins_mask(pm[h], dx[h], dy[h], sn[h], cs[h], rx, ry, e.x, e.y, cs[h], sn[h], dx[h], dy[h], ex[h], ey[h]);
+            else {
+              const double cr = fma(cs[h], a.x, sn[h] * a.y), sr = fma(sn[h], a.x, -(cs[h] * a.y));      // the relative yaw
+              bt[h] = pocs_box_margins_mask(pm[h], dx[h], dy[h], sn[h], cs[h], rx, ry, e.x, e.y, cr, sr,
+                                            fma(dx[h], a.x, dy[h] * a.y), fma(dy[h], a.x, -(dx[h] * a.y)),
+                                            fma(rx, fabs(cr), ry * fabs(sr)), fma(rx, fabs(sr), ry * fabs(cr)));
+            }
+          }
+          m0 |= bt[0]; m1 |= bt[1];
+        }
+      }
+    }
+    each(f, m0, m1);
+    all0 |= m0; all1 |= m1;
+  }
+  mask[0] = all0; mask[1] = all1;
+}
+#endif

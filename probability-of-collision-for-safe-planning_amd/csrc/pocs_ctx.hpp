@@ -192,6 +192,10 @@ struct pocs_ctx {
   // pocs_host.hip); everywhere else a call is the call it is with L = 0
   int clr_L = 0;
   double clr_d[POCS_MAX_CLEARANCE_LEVELS] = {0.0, 0.0, 0.0, 0.0};
+  // a compound footprint (pocs_set_footprint_parts): F = 1 is the single box `fp`.  F > 1: `fp` is part 0, every call is served by the
+  // kernels' _parts / MC_PARTS forms (parts_applied, pocs_host.hip) and the modes of pocs_modes::kPartsExcluded are refused
+  int fp_F = 1;
+  pocs_footprint fp_parts[POCS_MAX_FOOTPRINT_PARTS] = {};
 
   // host image (headers | chains | initial mixtures) of the NEXT batch, computed while the GPU
   // works on the current one
@@ -217,6 +221,7 @@ struct pocs_ctx {
   // clearance levels: [world_S] pocs_clear_dev beside d_env (upload_world), the counters [slots][W][POCS_MAX_CLEARANCE_LEVELS] u64 zeroed
   // by a kernel at the head of every call's launches, and the MC particles' smallest level so far [slots][stride] u8
   pocs_rt::DevBuf d_clr, d_clrct, d_clrlv;
+  pocs_rt::DevBuf d_parts;               // a compound footprint: one pocs_parts_dev beside d_env (upload_world)
   pocs_rt::DevBuf d_obsct;               // POCS_OPT_OBSTACLE_COUNTS: [slots][W][POCS_MAX_OBSTACLES] u64, zeroed by a kernel at the head of every call's launches
   // one-hop exchange (pocs_xchg_*): this rank's buffer, the peers' buffers as mapped here
   void* xchg_own = nullptr;
@@ -338,8 +343,18 @@ inline unsigned modes_of(const pocs_ctx* c) {
 inline bool in_mode(const pocs_ctx* c, unsigned any_of) { return (modes_of(c) & any_of) != 0; }
 inline bool large_world(const pocs_ctx* c) { return in_mode(c, pocs_modes::kLargeWorld); }
 
+// A compound footprint is set (pocs_set_footprint_parts with F > 1): not a mode of the table -- one mask of the modes it excludes
+// (pocs_modes::kPartsExcluded), asked here in front of the table and by the setter itself.
+inline bool parts_applied(const pocs_ctx* c) { return c->fp_F > 1; }
+inline int parts_refuse(pocs_ctx* c, const char* what, pocs_modes::Mode enter) {
+  if (!parts_applied(c) || !(enter & pocs_modes::kPartsExcluded)) return POCS_OK;
+  return fail(c, POCS_E_STATE, "%s: a compound footprint is set (pocs_set_footprint_parts); %s", what, pocs_modes::kPartsClause);
+}
+
 // May the context enter `enter`, as asked by the call `what`?  The one place that refuses a combination (pocs_modes.hpp).
 inline int may_enter(pocs_ctx* c, const char* what, pocs_modes::Mode enter, unsigned among = pocs_modes::kAll) {
+  if (among == pocs_modes::kAll)                     // (a setter's staged asks in front of its argument checks enter nothing yet)
+    if (int r = parts_refuse(c, what, enter)) return r;
   const pocs_modes::Refusal r = pocs_modes::refusal(modes_of(c), enter, among);
   if (r.code == POCS_OK) return POCS_OK;
   char clause[200];
@@ -377,6 +392,7 @@ int upload_world(pocs_ctx* c);
 void fill_gmm_world(const pocs_ctx* c, pocs_gmm_launch* a, int w);
 size_t obs_count_words(const pocs_ctx* c);
 bool clearance_applied(const pocs_ctx* c);
+void prepare_parts(const pocs_footprint* parts, int F, const double* boxes, int M, pocs_env_dev* env, pocs_parts_dev* out);
 void prepare_clearance(const pocs_footprint& fp, const double* d, int L, const double* boxes, int M, pocs_clear_dev* out);
 void gmm_select_view(pocs_ctx* c, int v);
 void tree_select_gmm(pocs_ctx* c, int n);

@@ -59,8 +59,13 @@ template <> struct gmm_cl_smem<true> {
 };
 static_assert(offsetof(pocs_clear_dev, fp_rr) == 32 && offsetof(pocs_clear_dev, d) == 48 && offsetof(pocs_clear_dev, obs) == 48 + 8 * POCS_MAX_CLEARANCE_LEVELS,
               "clh: the record's first doubles are footprint (4), radius, corner angle, distances");
-template <int K, int TB, bool OC = false, bool CL = false>
-struct gmm_smem : gmm_oc_smem<OC>, gmm_cl_smem<CL> {
+//   fpp    (the parts form only, pocs_set_footprint_parts: an empty base otherwise again) the parts of the compound footprint, 192 B
+template <bool FPN> struct gmm_fp_smem {};
+template <> struct gmm_fp_smem<true> {
+  double fpp[POCS_MAX_FOOTPRINT_PARTS * POCS_PART_STRIDE];
+};
+template <int K, int TB, bool OC = false, bool CL = false, bool FPN = false>
+struct gmm_smem : gmm_oc_smem<OC>, gmm_cl_smem<CL>, gmm_fp_smem<FPN> {
   static constexpr int NC = K * POCS_NMOM;
   static constexpr int NW = TB / 64;
   // (the clearance form holds 24 units at a time, not 32: with its second kept table K = 7 and K = 8 would otherwise pass the 80 KB
@@ -115,8 +120,8 @@ __device__ __forceinline__ double oct_sum(double s) {     // lanes 8 j .. 8 j + 
 // wave's xtra entry of k), and the chains restart.  By LDS transposition, five then four sums at a
 // time: every lane writes its values, lane 8 j + q adds lanes 8 q .. 8 q + 7 of sum j, oct_sum adds the
 // eight q.  One wave: the LDS executes a wave's instructions in order, nothing else synchronises.
-template <int K, int TB, bool OC, bool CL>
-__device__ __forceinline__ void flush_unit(gmm_smem<K, TB, OC, CL>& sm, const int wave, const int lane, const int rb, const int tl,
+template <int K, int TB, bool OC, bool CL, bool FPN>
+__device__ __forceinline__ void flush_unit(gmm_smem<K, TB, OC, CL, FPN>& sm, const int wave, const int lane, const int rb, const int tl,
                                            const int k, bool& first, double (&acc)[9], int& nfree) {
   double* const T = &sm.tr[wave][0][0];
   double* const dst = first ? &sm.slot[tl][wave][0] : &sm.xtra[rb][wave][k][0];
@@ -182,8 +187,8 @@ __device__ __forceinline__ void gmm_reach(const pocs_footprint& fp, const double
   ext_y = pocs_footprint_extent_is_radius(fp_phi, tlo - HALF_PI, thi - HALF_PI) ? fp_rr
         : pocs_footprint_extent_of_ends(fp_rr, lane_value(end_f, 2), lane_value(end_f, 3));
 }
-template <int K, int TB, bool OC, bool CL>
-__device__ __forceinline__ void gmm_cull(const pocs_gmm_launch& a, gmm_smem<K, TB, OC, CL>& sm, const int rb, const int lane, const double* par) {
+template <int K, int TB, bool OC, bool CL, bool FPN>
+__device__ __forceinline__ void gmm_cull(const pocs_gmm_launch& a, gmm_smem<K, TB, OC, CL, FPN>& sm, const int rb, const int lane, const double* par) {
   const pocs_footprint fp = a.fp;
   const int M = a.M;
   const double* const obs = sm.obs();
@@ -280,6 +285,60 @@ __device__ __forceinline__ void gmm_cull_clear(const pocs_gmm_launch& a, gmm_sme
   if (lane == 0) sm.nkeep2[rb] = __popcll(mask);
 }
 
+// The parts form's cull (one wave, all 64 lanes, in place of gmm_cull): ONE kept list per run buffer for the compound footprint
+// staged in sm.fpp.  Per part f gmm_cull's arithmetic with the part's offset, half extents, bounding radius and corner angle: the
+// mixture's box padded by the part's own offset, the part's extents over the run's headings (the four end values of part f side
+// by side in lanes 4 f .. 4 f + 3), the record's broad-phase box for that part (never more than the table's, which is sized for the
+// largest part).  A record is kept if the keep test passes for ANY part; its fields 6 and 7 are the largest of the parts' boxes, so
+// the broad phase of the sampling loop -- against each part's own centre -- is conservative for every part: no flag changes.
+template <int K, int TB>
+__device__ __forceinline__ void gmm_cull_parts(const pocs_gmm_launch& a, gmm_smem<K, TB, false, false, true>& sm, const int rb, const int lane, const double* par) {
+  const int M = a.M, F = a.parts_F;
+  const double* const obs = sm.obs();
+  double xlo = 1e300, xhi = -1e300, ylo = 1e300, yhi = -1e300, tlo = 1e300, thi = -1e300;
+#pragma unroll
+  for (int k = 0; k < K; ++k) {
+    const double* p = &par[k * POCS_PARAM_STRIDE];
+    const double ex = 6.67 * fabs(p[3]), ey = 6.67 * (fabs(p[4]) + fabs(p[5])), et = 6.67 * (fabs(p[6]) + fabs(p[7]) + fabs(p[8]));
+    xlo = fmin(xlo, p[0] - ex); xhi = fmax(xhi, p[0] + ex);
+    ylo = fmin(ylo, p[1] - ey); yhi = fmax(yhi, p[1] + ey);
+    tlo = fmin(tlo, p[2] - et); thi = fmax(thi, p[2] + et);
+  }
+  tlo -= 1e-9 * (1.0 + fabs(tlo)); thi += 1e-9 * (1.0 + fabs(thi));
+  const double HALF_PI = 1.57079632679489661923;
+  static_assert(POCS_MAX_FOOTPRINT_PARTS == 4, "lanes 4 f + e");
+  const int pf = ((lane >> 2) & 3) < F ? ((lane >> 2) & 3) : 0;      // (the lanes past 4 F repeat a part: their values are not read)
+  const double end_t = ((lane & 1) ? thi : tlo) - ((lane & 2) ? HALF_PI : 0.0);      // tlo, thi, tlo - pi/2, thi - pi/2
+  const double end_f = pocs_footprint_extent_end(sm.fpp[pf * POCS_PART_STRIDE + 2], sm.fpp[pf * POCS_PART_STRIDE + 3], end_t);
+  const bool in = lane < M;
+  const double* const o = &obs[(in ? lane : 0) * POCS_OBS_STRIDE];
+  const double o0 = o[0], o1 = o[1], o6 = o[6], o7 = o[7];
+  const double ax = fma(o[4], fabs(o[2]), o[5] * fabs(o[3])) * (1.0 + 1e-12), ay = fma(o[4], fabs(o[3]), o[5] * fabs(o[2])) * (1.0 + 1e-12);
+  bool keep = false;
+  double bx = 0.0, by = 0.0;
+#pragma unroll 1
+  for (int f = 0; f < F; ++f) {                      // (scalar)
+    const double* q = &sm.fpp[f * POCS_PART_STRIDE];
+    const double rr = q[4], phi = q[5];
+    const double e0 = lane_value(end_f, 4 * f), e1 = lane_value(end_f, 4 * f + 1), e2 = lane_value(end_f, 4 * f + 2), e3 = lane_value(end_f, 4 * f + 3);
+    const double ext_x = pocs_footprint_extent_is_radius(phi, tlo, thi) ? rr : pocs_footprint_extent_of_ends(rr, e0, e1);
+    const double ext_y = pocs_footprint_extent_is_radius(phi, tlo - HALF_PI, thi - HALF_PI) ? rr : pocs_footprint_extent_of_ends(rr, e2, e3);
+    const double pad = sqrt(q[0] * q[0] + q[1] * q[1]) + 1e-6;       // the part's centre vs the base
+    const double bxf = fmin(o6, ax + ext_x), byf = fmin(o7, ay + ext_y);
+    if (in && !(o0 - bxf > xhi + pad || o0 + bxf < xlo - pad || o1 - byf > yhi + pad || o1 + byf < ylo - pad)) keep = true;
+    bx = fmax(bx, bxf); by = fmax(by, byf);
+  }
+  const unsigned long long mask = __ballot(keep);
+  if (keep) {
+    const int pos = __popcll(mask & ((1ull << lane) - 1ull));
+#pragma unroll
+    for (int j = 0; j < 6; ++j) sm.keep[rb][pos * POCS_OBS_STRIDE + j] = obs[lane * POCS_OBS_STRIDE + j];
+    sm.keep[rb][pos * POCS_OBS_STRIDE + 6] = bx;
+    sm.keep[rb][pos * POCS_OBS_STRIDE + 7] = by;
+  }
+  if (lane == 0) sm.nkeep[rb] = __popcll(mask);
+}
+
 // ---------------------------------------------------------------------------------------------
 // THE BODY: units [ta, tb) of the launch (unit t = virtual slice t mod VS of run t / VS; at most
 // POCS_GMM_SUB of them, of at most two runs r0 and r0 + 1 whose parameters and culled tables are staged
@@ -299,8 +358,10 @@ __device__ __forceinline__ void gmm_cull_clear(const pocs_gmm_launch& a, gmm_sme
 //   CL (pocs_set_clearance_levels): behind the unchanged base test the level test runs on the second kept list
 //   (pocs_pair_clearance_masks); per level the lanes whose sample exists are picked by scalar ands of the masks and one lane adds
 //   the population count to the block's LDS counter of (run buffer, level).  The odd shard's unused twin does not count.
-template <int K, bool STORE, int TB, bool LONE_PRE = false, bool OC = false, bool CL = false>
-__device__ __forceinline__ void gmm_units(const pocs_gmm_launch& a, gmm_smem<K, TB, OC, CL>& sm, const int w, const int r0,
+//   FPN (pocs_set_footprint_parts, F > 1): the collision test is pocs_pair_parts_masks over the parts staged in sm.fpp, on the one
+//   kept list (gmm_cull_parts); the flag is the OR of the parts' flags and everything behind it is what it is.
+template <int K, bool STORE, int TB, bool LONE_PRE = false, bool OC = false, bool CL = false, bool FPN = false>
+__device__ __forceinline__ void gmm_units(const pocs_gmm_launch& a, gmm_smem<K, TB, OC, CL, FPN>& sm, const int w, const int r0,
                                           const int ta, const int tb, const double* zpre = nullptr, const int npre = 0) {
   const pocs_tables* const s_tab = &sm.tab;
   const int tid = threadIdx.x, lane = tid & 63;
@@ -404,6 +465,9 @@ __device__ __forceinline__ void gmm_units(const pocs_gmm_launch& a, gmm_smem<K, 
       ks[h] = k;
     }
     POCS_TUNE_COLLIDE_STATS();
+    if constexpr (FPN) {
+      pocs_pair_parts_masks(xs, ys, ts, sm.fpp, a.parts_F, s_keep, nkeep, s_tab, vc, hits);
+    } else
     if constexpr (OC) {
       unsigned* const occ = sm.occ[rb];
       pocs_pair_collides_masks<LONE_PRE>(xs, ys, ts, &fp, s_keep, nkeep, s_tab, vc, hits, [&](const int m, const int h, const bool t) {
@@ -549,8 +613,8 @@ __device__ __forceinline__ void gmm_units(const pocs_gmm_launch& a, gmm_smem<K, 
 // order -- whichever of them the unit has: slot if the component was the wave's first there, xtra if it
 // started inside the wave's share, +0 otherwise -- stored write-through to the run's partial rows.
 // Column 1 (collisions) stays 0: a component's collisions are what is left of its block (gmm_close_sums).
-template <int K, int TB, bool OC, bool CL>
-__device__ __forceinline__ void gmm_emit_rows(const pocs_gmm_launch& a, gmm_smem<K, TB, OC, CL>& sm, const int r0, const int ta, const int tb) {
+template <int K, int TB, bool OC, bool CL, bool FPN>
+__device__ __forceinline__ void gmm_emit_rows(const pocs_gmm_launch& a, gmm_smem<K, TB, OC, CL, FPN>& sm, const int r0, const int ta, const int tb) {
   constexpr int NC = K * POCS_NMOM, NW = TB / 64;
   for (int i = threadIdx.x; i < (tb - ta) * NC; i += TB) {
     const int tl = i / NC, c = i - tl * NC, k = c / POCS_NMOM, col = c - k * POCS_NMOM;
@@ -730,9 +794,16 @@ __device__ __forceinline__ void gmm_close_sums(const pocs_gmm_launch& a, const i
 // one integer atomic each to clr_counts[run][waypoint][level], as occ does.  The base test, the moment sums, the tickets and the
 // closers are what they are.  LDS: + 8 KB for the second kept table, + 0.1 KB, and 24 instead of 32 held units (- 5.25 KB): K = 3 holds
 // 70 688 B against the twin's 67 744, K = 8 78 368 B against 75 424 -- two blocks per CU (160 KB) in every instantiation, as the twins.
-template <int K, bool STORE, int TB, bool LONE, bool RISK, bool TREE = false, bool OC = false, bool WORLD = false, bool CL = false>
+//
+// FPN (a compound footprint, pocs_set_footprint_parts with F > 1; the kernels k_gmm_step_parts, k_gmm_step_risk_parts: ticket form,
+// never LONE, TREE, OC, WORLD or CL): the head also stages the parts (pocs_parts_dev) with its other requests; waves 0 and 1 cull with
+// gmm_cull_parts in place of gmm_cull -- ONE kept list per run buffer, a record kept if any part's keep test passes, its broad-phase
+// fields the largest of the parts' -- and the body asks pocs_pair_parts_masks.  The moment sums, the tickets and the closers are what
+// they are.  LDS: + 192 B for the parts (K = 8: 75 616 B against the twin's 75 424): two blocks per CU in every instantiation.
+template <int K, bool STORE, int TB, bool LONE, bool RISK, bool TREE = false, bool OC = false, bool WORLD = false, bool CL = false, bool FPN = false>
 __device__ __forceinline__ void gmm_step_block(const pocs_gmm_launch a) {      // (by value, as a kernel holds its argument)
-  typedef gmm_smem<K, TB, OC, CL> smem_t;
+  typedef gmm_smem<K, TB, OC, CL, FPN> smem_t;
+  static_assert(!(FPN && (LONE || TREE || OC || WORLD || CL)), "a compound footprint: the ticket form of a batch or of plans on a small world, no counts per box or level");
   static_assert(!(CL && (LONE || TREE || OC || WORLD)), "clearance levels: the ticket form of a batch or of plans on a small world, no per-box counts");
   static_assert(!(WORLD && (LONE || TREE || OC)), "a large world: the ticket form of a batch or of plans, no per-box counts");
   static_assert(!WORLD || TB == POCS_MAX_OBSTACLES * POCS_OBS_STRIDE, "one element of a run's kept records per thread");
@@ -766,6 +837,8 @@ __device__ __forceinline__ void gmm_step_block(const pocs_gmm_launch a) {      /
   request_tables<TB>(a.tables, tid, tabv);
   double obs_elem = 0.0;
   if constexpr (!WORLD) obs_elem = tid < a.M * POCS_OBS_STRIDE ? a.env->obs[tid] : 0.0;
+  [[maybe_unused]] double fpp_elem = 0.0;                       // FPN: the parts
+  if constexpr (FPN) fpp_elem = tid < POCS_MAX_FOOTPRINT_PARTS * POCS_PART_STRIDE ? a.parts->part[tid] : 0.0;
   [[maybe_unused]] double obs2_elem = 0.0, clh_elem = 0.0;      // CL: the grown footprint's table, the head of the clearance record
   if constexpr (CL) {
     obs2_elem = tid < a.M * POCS_OBS_STRIDE ? a.clr->obs[tid] : 0.0;
@@ -868,6 +941,7 @@ __device__ __forceinline__ void gmm_step_block(const pocs_gmm_launch a) {      /
       commit_tables<TB>(&sm.tab, tid, tabv);
       if (tid < a.M * POCS_OBS_STRIDE) sm.obs()[tid] = obs_elem;
       if constexpr (CL) { if (tid < a.M * POCS_OBS_STRIDE) sm.obs2()[tid] = obs2_elem; if (tid < 6 + POCS_MAX_CLEARANCE_LEVELS) sm.clh[tid] = clh_elem; }
+      if constexpr (FPN) { if (tid < POCS_MAX_FOOTPRINT_PARTS * POCS_PART_STRIDE) sm.fpp[tid] = fpp_elem; }
       if (tid < (r1_all - r0_all + 1) * PS && rp >= shift && rp - shift <= r1 - r0) sm.par[rp - shift][jp] = parv;
       for (int j = tid; j < 2 * NW * K; j += TB) (&sm.xj[0][0][0])[j] = -1;
       if (tid <= r1_all - r0_all && tid >= shift && tid - shift <= r1 - r0) sm.seed[tid - shift] = seedv;
@@ -877,6 +951,7 @@ __device__ __forceinline__ void gmm_step_block(const pocs_gmm_launch a) {      /
     commit_tables<TB>(&sm.tab, tid, tabv);
     if (tid < a.M * POCS_OBS_STRIDE) sm.obs()[tid] = obs_elem;
     if constexpr (CL) { if (tid < a.M * POCS_OBS_STRIDE) sm.obs2()[tid] = obs2_elem; if (tid < 6 + POCS_MAX_CLEARANCE_LEVELS) sm.clh[tid] = clh_elem; }
+      if constexpr (FPN) { if (tid < POCS_MAX_FOOTPRINT_PARTS * POCS_PART_STRIDE) sm.fpp[tid] = fpp_elem; }
     if (tid < (r1 - r0 + 1) * PS) sm.par[rp][jp] = parv;
     for (int j = tid; j < 2 * NW * K; j += TB) (&sm.xj[0][0][0])[j] = -1;
     if (tid <= r1 - r0) sm.seed[tid] = seedv;
@@ -890,15 +965,20 @@ __device__ __forceinline__ void gmm_step_block(const pocs_gmm_launch a) {      /
       if (tid >= 128 && tid < 192) gmm_cull_clear(a, sm, 0, tid - 128, sm.par[0]);
       else if (tid >= 192 && tid < 256 && r1 > r0) gmm_cull_clear(a, sm, 1, tid - 192, sm.par[1]);
     }
+    if constexpr (FPN) {
+      if (tid < 64) gmm_cull_parts(a, sm, 0, tid, sm.par[0]);
+      else if (tid < 128 && r1 > r0) gmm_cull_parts(a, sm, 1, tid - 64, sm.par[1]);
+    } else {
     if (tid < 64) gmm_cull(a, sm, 0, tid, sm.par[0]);
     else if (tid < 128 && r1 > r0) gmm_cull(a, sm, 1, tid - 64, sm.par[1]);
+    }
     __syncthreads();
   }                                                  // from here on the transpose scratch is the waves'
   }
   POCS_STAMP(0);
   for (int ta = t0; ta < t1; ta += SUB) {
     const int tb = (ta + SUB < t1) ? ta + SUB : t1;
-    gmm_units<K, STORE, TB, LONE, OC, CL>(a, sm, w, r0, ta, tb, s_zpre, ta == t0 ? npre : 0);
+    gmm_units<K, STORE, TB, LONE, OC, CL, FPN>(a, sm, w, r0, ta, tb, s_zpre, ta == t0 ? npre : 0);
     POCS_STAMP(1);
     __syncthreads();
     POCS_STAMP(2);
@@ -1050,6 +1130,16 @@ __global__ __launch_bounds__(TB, POCS_GMM_BLOCKS_PER_CU * TB / 256) void k_gmm_s
 template <int K, bool STORE, int TB>
 __global__ __launch_bounds__(TB, POCS_GMM_BLOCKS_PER_CU * TB / 256) void k_gmm_step_risk_clear(pocs_gmm_launch a) {
   gmm_step_block<K, STORE, TB, false, true, false, false, false, true>(a);
+}
+
+// The forms under a compound footprint (FPN above): kernels of their own names again.
+template <int K, bool STORE, int TB>
+__global__ __launch_bounds__(TB, POCS_GMM_BLOCKS_PER_CU * TB / 256) void k_gmm_step_parts(pocs_gmm_launch a) {
+  gmm_step_block<K, STORE, TB, false, false, false, false, false, false, true>(a);
+}
+template <int K, bool STORE, int TB>
+__global__ __launch_bounds__(TB, POCS_GMM_BLOCKS_PER_CU * TB / 256) void k_gmm_step_risk_parts(pocs_gmm_launch a) {
+  gmm_step_block<K, STORE, TB, false, true, false, false, false, false, true>(a);
 }
 
 // The forms under a large collision world (WORLD above): kernels of their own names again.

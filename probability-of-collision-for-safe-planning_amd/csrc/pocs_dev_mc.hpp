@@ -120,7 +120,11 @@ __device__ __forceinline__ mc_run_start mc_start(const pocs_mc_launch& a) {
 // at no waypoint before: the first-collision profile as it would be for the grown footprint on the same cloud.  The level comes
 // from pocs_pose_clearance_level on the table prepared for the footprint grown by the largest clearance, staged beside the world's;
 // the collision test itself, the hit counters and the other counts are what they are without the flag.
-enum { MC_PLAIN = 0, MC_COUNTS = 1, MC_STOP = 2, MC_BOXES = 4, MC_CLEAR = 8 };
+//
+// MC_PARTS (pocs_set_footprint_parts with F > 1), a flag on top of MC_PLAIN, MC_COUNTS or MC_STOP, on k_mc_init and the per-step
+// kernel: the collision test is pocs_pose_collides_parts over the parts staged beside the world's records (which are prepared for
+// the largest part); the hit counters and the counts are formed from that flag as they are from the single footprint's.
+enum { MC_PLAIN = 0, MC_COUNTS = 1, MC_STOP = 2, MC_BOXES = 4, MC_CLEAR = 8, MC_PARTS = 16 };
 static_assert(POCS_MAX_OBSTACLES <= 64, "a particle's touched boxes are a 64-bit mask");
 
 // pocs_pose_collides with the touched boxes as a mask (the flag: mask != 0, as the plain form's).
@@ -200,6 +204,19 @@ __device__ __forceinline__ mc_clear stage_mc_clear(const pocs_mc_launch& a) {
   for (int u = 0; u < UO; ++u) { const int i = tid + u * POCS_BLOCK; if (i < NO) s_obs2[i] = vo[u]; }
   if (tid < POCS_MAX_CLEARANCE_LEVELS) s_d[tid] = dv;
   return {s_obs2, s_d, a.clr_L};
+}
+// MC_PARTS: the parts of the compound footprint in LDS, staged in front of the head's barrier.
+struct mc_parts {
+  const double* p;                 // LDS: F x POCS_PART_STRIDE
+  int F;
+};
+__device__ __forceinline__ mc_parts stage_mc_parts(const pocs_mc_launch& a) {
+  __shared__ double s_parts[POCS_MAX_FOOTPRINT_PARTS * POCS_PART_STRIDE];
+  const int tid = threadIdx.x;
+  const double v = tid < POCS_MAX_FOOTPRINT_PARTS * POCS_PART_STRIDE ? a.parts->part[tid] : 0.0;
+  requests_issued();
+  if (tid < POCS_MAX_FOOTPRINT_PARTS * POCS_PART_STRIDE) s_parts[tid] = v;
+  return {s_parts, a.parts_F};
 }
 // The lanes of a wave that are in the particle loop together, each with its particle's level at this waypoint and its smallest
 // level before: per level that some particle reaches for the first time one ballot, and the first lane of the ballot adds the
@@ -361,6 +378,8 @@ __global__ __launch_bounds__(POCS_BLOCK) void k_mc_init(pocs_mc_launch a) {
   if constexpr ((MODE & MC_BOXES) != 0) box = mc_box_counters_zeroed();      // (in front of the head's barrier)
   mc_clear cl = {nullptr, nullptr, 0};
   if constexpr ((MODE & MC_CLEAR) != 0) cl = stage_mc_clear(a);              // (in front of the head's barrier)
+  mc_parts pt = {nullptr, 0};
+  if constexpr ((MODE & MC_PARTS) != 0) pt = stage_mc_parts(a);              // (in front of the head's barrier)
   const mc_head hd = stage_mc_head(a.env, a.tables);
   const mc_run_view v = mc_view(a);
   const mc_world wd = hd.world();
@@ -376,6 +395,8 @@ __global__ __launch_bounds__(POCS_BLOCK) void k_mc_init(pocs_mc_launch a) {
       unsigned long long mask;
       h = mc_collides_mask(x, y, t, &wd.fp, wd.obs, wd.M, wd.tab, mask) ? 1u : 0u;
       mc_wave_box_hits(h != 0u, mask, wd.M, box.c);
+    } else if constexpr ((MODE & MC_PARTS) != 0) {
+      h = pocs_pose_collides_parts(x, y, t, pt.p, pt.F, wd.obs, wd.M, wd.tab) ? 1u : 0u;
     } else {
       h = pocs_pose_collides(x, y, t, &wd.fp, wd.obs, wd.M, wd.tab) ? 1u : 0u;
     }
@@ -435,6 +456,8 @@ __device__ __forceinline__ void mc_step_body(const pocs_mc_launch& a) {
   if constexpr ((MODE & MC_BOXES) != 0) box = mc_box_counters_zeroed();      // (in front of the head's barrier)
   mc_clear cl = {nullptr, nullptr, 0};
   if constexpr ((MODE & MC_CLEAR) != 0) cl = stage_mc_clear(a);              // (in front of the head's barrier)
+  mc_parts pt = {nullptr, 0};
+  if constexpr ((MODE & MC_PARTS) != 0) pt = stage_mc_parts(a);              // (in front of the head's barrier)
   const mc_head hd = stage_mc_head(a.env, a.tables);
   const mc_run_view v = mc_view(a);
   const mc_world wd = hd.world();
@@ -457,6 +480,12 @@ __device__ __forceinline__ void mc_step_body(const pocs_mc_launch& a) {
         first += fresh ? 1u : 0u;
       }
       mc_wave_box_hits(fresh, mask, wd.M, box.c);
+    } else if constexpr ((MODE & MC_PARTS) != 0) {
+      if (pocs_pose_collides_parts(nx, ny, nt, pt.p, pt.F, wd.obs, wd.M, wd.tab)) {
+        const uint32_t old = v.hits[i];
+        v.hits[i] = old + 1u;
+        first += old == 0u ? 1u : 0u;
+      }
     } else {
     if (pocs_pose_collides(nx, ny, nt, &wd.fp, wd.obs, wd.M, wd.tab)) {
       const uint32_t old = v.hits[i];                // the counter is in hand exactly when the particle collides

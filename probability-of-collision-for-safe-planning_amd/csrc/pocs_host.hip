@@ -85,12 +85,28 @@ void prepare_clearance(const pocs_footprint& fp, const double* d, int L, const d
   for (int m = 0; m < M; ++m) pocs_prepare_obstacle(boxes + (size_t)m * 5, &out->fp, &out->obs[(size_t)m * POCS_OBS_STRIDE]);
 }
 
+// A compound footprint (F > 1) as the kernels read it: the parts (pocs_prepare_part), and one world step's record with the boxes
+// prepared for the part with the largest bounding radius -- a broad phase that is conservative for every part -- and part 0 as its
+// footprint.  (pocs_probe_device_footprint_parts prepares its own through this function too; env may be null.)
+void prepare_parts(const pocs_footprint* parts, int F, const double* boxes, int M, pocs_env_dev* env, pocs_parts_dev* out) {
+  if (out) {
+    memset(out, 0, sizeof *out);
+    for (int f = 0; f < F; ++f) pocs_prepare_part(&parts[f], &out->part[(size_t)f * POCS_PART_STRIDE]);
+  }
+  if (env) {
+    const pocs_footprint* cover = &parts[pocs_parts_cover(parts, F)];
+    memset(env, 0, sizeof *env);
+    env->fp = parts[0]; env->M = M;
+    for (int m = 0; m < M; ++m) pocs_prepare_obstacle(boxes + (size_t)m * 5, cover, &env->obs[(size_t)m * POCS_OBS_STRIDE]);
+  }
+}
+
 // Where the levels are applied: whole calls on one GPU over a small world, static or scheduled -- single runs, batches, run-ahead,
 // calls of plans with and without the risk bound, GMM and MC.  A tree of plans, a large world, per-box counts, a shard (and with it
 // the exchange and a bound moments buffer) are the calls they are with L = 0; the step API never asks.
 bool clearance_applied(const pocs_ctx* c) {
   using namespace pocs_modes;
-  return c->clr_L > 0 && !in_mode(c, kTree | kLargeWorld | kObsCounts | kShard | kMoments);
+  return c->clr_L > 0 && !parts_applied(c) && !in_mode(c, kTree | kLargeWorld | kObsCounts | kShard | kMoments);
 }
 
 int upload_world(pocs_ctx* c) {                // tables + the collision world: one record (obstacle records, footprint) per step of the schedule
@@ -100,7 +116,12 @@ int upload_world(pocs_ctx* c) {                // tables + the collision world: 
     const int M = world_boxes(c);
     std::vector<pocs_env_dev> env(S);
     memset(env.data(), 0, S * sizeof(pocs_env_dev));
+    pocs_parts_dev parts;
     for (size_t s = 0; s < S; ++s) {
+      if (parts_applied(c)) {                        // (a compound footprint: the records of the covering part; no large world then)
+        prepare_parts(c->fp_parts, c->fp_F, c->boxes.data() + s * (size_t)M * 5, M, &env[s], s == 0 ? &parts : nullptr);
+        continue;
+      }
       env[s].fp = c->fp;
       env[s].M = M;
       for (int m = 0; m < M; ++m)
@@ -109,6 +130,10 @@ int upload_world(pocs_ctx* c) {                // tables + the collision world: 
     if (int r = ensure(c, c->d_env, S * sizeof(pocs_env_dev))) return r;      // (a schedule that grows: the graphs go with the old table)
     HIPCHK(c, hipStreamSynchronize(c->stream));      // (nothing queued may still read the last world's)
     HIPCHK(c, hipMemcpy(c->d_env.p, env.data(), S * sizeof(pocs_env_dev), hipMemcpyHostToDevice));
+    if (parts_applied(c)) {
+      if (int r = ensure(c, c->d_parts, sizeof(pocs_parts_dev))) return r;
+      HIPCHK(c, hipMemcpy(c->d_parts.p, &parts, sizeof parts, hipMemcpyHostToDevice));
+    }
     if (c->clr_L > 0 && !large_world(c)) {           // the second record set, next to the first: the footprint grown by d_L
       std::vector<pocs_clear_dev> clr(S);
       for (size_t s = 0; s < S; ++s) prepare_clearance(c->fp, c->clr_d, c->clr_L, c->boxes.data() + s * (size_t)M * 5, M, &clr[s]);
@@ -404,8 +429,11 @@ bool whole_call_exchanges(const pocs_ctx* c) { return c->xchg_connected && c->sh
 void fill_gmm_world(const pocs_ctx* c, pocs_gmm_launch* a, int w) {
   a->env = world_at(c, w);
   a->tables = (const pocs_tables*)c->d_tables.p;
-  a->fp = c->fp; a->M = world_boxes(c);
-  a->fp_rr = sqrt(c->fp.hx * c->fp.hx + c->fp.hy * c->fp.hy); a->fp_phi = atan2(c->fp.hy, c->fp.hx);
+  a->M = world_boxes(c);
+  if (!parts_applied(c)) {                           // (a compound footprint's values live in device memory: the launch carries none)
+    a->fp = c->fp;
+    a->fp_rr = sqrt(c->fp.hx * c->fp.hx + c->fp.hy * c->fp.hy); a->fp_phi = atan2(c->fp.hy, c->fp.hx);
+  }
   if (large_world(c)) {                              // (M above is 0 then: the staged table is empty)
     a->world = (const double*)c->d_world.p; a->world_M = large_boxes(c);
     a->kept = (double*)c->d_kept.p; a->kept_idx = (int*)c->d_keptidx.p; a->reach = (int*)c->d_reach.p;
@@ -472,7 +500,8 @@ int enqueue_advance(Issuer is, int w) {
 // (Under a large world the cull of waypoint w reads param[w] ahead of the sampling launch; the lone form builds param[w] in its own
 // heads, so a call of one run takes the ticket form there: the same bits.)
 // (Under clearance levels too: the counting form exists as the ticket form only.)
-bool lone_call(const pocs_ctx* c) { return c->opt_lone && !large_world(c) && !clearance_applied(c) && c->batch == 1 && !c->tree.n && !c->ext_moments && !(c->xchg_connected && c->shard_first >= 0) && !risk_active(c); }
+// (And under a compound footprint: the parts form exists as the ticket form only.)
+bool lone_call(const pocs_ctx* c) { return c->opt_lone && !large_world(c) && !clearance_applied(c) && !parts_applied(c) && c->batch == 1 && !c->tree.n && !c->ext_moments && !(c->xchg_connected && c->shard_first >= 0) && !risk_active(c); }
 void set_risk(pocs_ctx* c, pocs_gmm_launch* a) {      // under a risk bound the launch is k_gmm_step_risk (whole calls of plans or on a tree only)
   a->risk = 1;
   a->stop = a->sync + c->sync.stop;
@@ -576,6 +605,7 @@ int enqueue_gmm_all(Issuer is, long long first, long long count, bool prof) {
   for (int g = 1; g < G; ++g) if (int r = is.order(0, g, c->ev_fork, g == 1)) return r;
   pocs_gmm_launch base;
   fill_gmm_launch(c, &base, first, count);
+  if (parts_applied(c)) { base.parts = (const pocs_parts_dev*)c->d_parts.p; base.parts_F = c->fp_F; }
   if (clearance_applied(c)) {                        // (the whole call only: the step API's launches never carry the levels)
     base.clr = clear_at(c, 0); base.clr_counts = (unsigned long long*)c->d_clrct.p; base.clr_L = c->clr_L;
   }
@@ -855,7 +885,8 @@ bool mc_counts_active(const pocs_ctx* c) { return c->opt_mc_wp || c->opt_obs_cou
 // The fused kernel carries a particle through all its steps and meets no other block on the way: a call that stops on a count
 // takes the per-step form.
 // So does a call that counts clearance levels: the levels live in the per-step kernels (MC_CLEAR).
-bool mc_fused_form(const pocs_ctx* c) { return c->opt_fused && !mc_stop_active(c) && !clearance_applied(c); }
+// And a call under a compound footprint: the parts live in the per-step kernels too (MC_PARTS).
+bool mc_fused_form(const pocs_ctx* c) { return c->opt_fused && !mc_stop_active(c) && !clearance_applied(c) && !parts_applied(c); }
 // d_total, u64 words: [R] collided particles per run | counts active: [R][W] first collisions | [R] u32 stop words
 size_t mc_total_words(const pocs_ctx* c) {
   const size_t R = (size_t)c->batch, W = (size_t)c->W;
@@ -902,6 +933,7 @@ int enqueue_mc_all(Issuer is, long long first, long long count, bool prof) {
     a.obs_counts = (unsigned long long*)c->d_obsct.p;
     if (int r = enqueue_obs_counts_reset(is)) return r;
   }
+  if (parts_applied(c)) { a.parts = (const pocs_parts_dev*)c->d_parts.p; a.parts_F = c->fp_F; }
   if (clearance_applied(c)) {
     a.clr = clear_at(c, 0); a.clr_counts = (unsigned long long*)c->d_clrct.p; a.clr_level = (unsigned char*)c->d_clrlv.p; a.clr_L = c->clr_L;
     if (int r = enqueue_clearance_reset(is)) return r;

@@ -59,6 +59,14 @@ struct pocs_clear_dev {
   double obs[POCS_MAX_OBSTACLES * POCS_OBS_STRIDE];   // the step's boxes prepared (pocs_prepare_obstacle) for that footprint
 };
 
+// A compound footprint (pocs_set_footprint_parts, F > 1) as the kernels see it, in HBM beside the collision world: the parts'
+// values live HERE, not in launch arguments -- a call's launches carry the address and F, so other values with the same F replay the
+// cached graph.  Under a compound footprint the world's records (pocs_env_dev::obs) are prepared for the part with the largest
+// bounding radius (pocs_parts_cover), and pocs_env_dev::fp is part 0.
+struct pocs_parts_dev {
+  double part[POCS_MAX_FOOTPRINT_PARTS * POCS_PART_STRIDE];   // per part dx dy hx hy, bounding radius, corner angle (pocs_prepare_part)
+};
+
 struct pocs_run_header {         // per-run scalars read by every kernel (so a captured graph stays valid)
   uint64_t seed;
   uint64_t pad;                  // sharded whole calls: the context's count of exchange sequences (pocs_gmm_launch::xchg_epoch_from_header)
@@ -159,6 +167,12 @@ struct pocs_gmm_launch {
   unsigned long long* clr_counts; // [nruns][W][POCS_MAX_CLEARANCE_LEVELS]; zeroed by pocs_launch_zero_counts at the head of the call's launches
   int clr_L;                     // 1 .. POCS_MAX_CLEARANCE_LEVELS
   int clr_pad;
+  // a compound footprint (pocs_set_footprint_parts with F > 1; behind everything else again): non-null = the launch is the kernel's
+  // _parts form (ticket form, with or without the risk bound; never LONE, TREE, OC, WORLD or CL), whose cull and collision test run
+  // over the parts; `fp`, `fp_rr` and `fp_phi` above are zero then
+  const pocs_parts_dev* parts;
+  int parts_F;                   // 2 .. POCS_MAX_FOOTPRINT_PARTS
+  int parts_pad;
 };
 #define POCS_MAX_WORLD_RECORDS 4096   // = POCS_MAX_WORLD_BOXES (include/pocs.h; pocs_ctx.hpp checks)
 #define POCS_CULL_BLOCK 256           // k_world_cull
@@ -220,6 +234,10 @@ struct pocs_mc_launch {               // blockIdx.y = run of the batch, like poc
   unsigned char* clr_level;            // [nruns][stride] the particle's smallest level so far (clr_L: none); written by k_mc_init
   int clr_L;
   int clr_pad;
+  // a compound footprint (pocs_set_footprint_parts with F > 1): non-null = the MC_PARTS forms of k_mc_init and the per-step kernels
+  const pocs_parts_dev* parts;
+  int parts_F;
+  int parts_pad;
 };
 
 
@@ -242,6 +260,10 @@ hipError_t pocs_launch_probe_collide(int K, const pocs_gmm_launch& a, int n, con
 // (+100 should the pair form ever disagree with the single-pose form).  env: base records of M boxes; clr: the grown ones
 hipError_t pocs_launch_probe_clearance(const pocs_env_dev* env, const pocs_clear_dev* clr, int L, const pocs_tables* tables, int n,
                                        const double* x, const double* y, const double* th, int* level_out, hipStream_t s);
+// one block; poses n x (x, y, th) by component; touched_out[i]: bit f = part f touches (bit 8 should the pair form ever disagree with
+// the single-pose form).  env: records of M boxes prepared for the covering part; parts: F parts
+hipError_t pocs_launch_probe_parts(const pocs_env_dev* env, const pocs_parts_dev* parts, int F, const pocs_tables* tables, int n,
+                                   const double* x, const double* y, const double* th, int* touched_out, hipStream_t s);
 hipError_t pocs_launch_mc_init(int nblk, const pocs_mc_launch& a, hipStream_t s);
 hipError_t pocs_launch_mc_step(int nblk, const pocs_mc_launch& a, hipStream_t s);
 hipError_t pocs_launch_mc_fused(int nblk, const pocs_mc_launch& a, hipStream_t s);

@@ -54,6 +54,18 @@ hipError_t with_K(const int K, F f) {
 hipError_t pocs_launch_gmm_step(int K, const pocs_gmm_launch& a, hipStream_t s) {
   return with_K(K, [&](auto k) {
     constexpr int KK = decltype(k)::value, TB = POCS_GMM_BLOCK_OF(KK);
+    if (a.parts) {                                     // a compound footprint: the ticket forms that test every part
+      if (a.lone || a.obs_counts || a.world || a.tree_parent || a.exchange_in_tail || a.clr || a.parts_F < 2 || a.parts_F > POCS_MAX_FOOTPRINT_PARTS ||
+          a.M > POCS_MAX_OBSTACLES || (a.risk && (!a.stop || !a.surv)))
+        return hipErrorInvalidValue;
+      if (a.risk) {
+        if (a.store) hipLaunchKernelGGL((k_gmm_step_risk_parts<KK, true, TB>), dim3(a.blocks), dim3(TB), 0, s, a);
+        else         hipLaunchKernelGGL((k_gmm_step_risk_parts<KK, false, TB>), dim3(a.blocks), dim3(TB), 0, s, a);
+      } else {
+        if (a.store) hipLaunchKernelGGL((k_gmm_step_parts<KK, true, TB>), dim3(a.blocks), dim3(TB), 0, s, a);
+        else         hipLaunchKernelGGL((k_gmm_step_parts<KK, false, TB>), dim3(a.blocks), dim3(TB), 0, s, a);
+      }
+    } else
     if (a.clr) {                                       // clearance levels: the ticket forms that also count per level
       if (a.lone || a.obs_counts || a.world || a.tree_parent || a.exchange_in_tail || !a.clr_counts || a.clr_L < 1 || a.clr_L > POCS_MAX_CLEARANCE_LEVELS ||
           a.M > POCS_MAX_OBSTACLES || (a.risk && (!a.stop || !a.surv)))
@@ -175,6 +187,11 @@ hipError_t pocs_launch_mc_tree_step(int nblk, const pocs_mc_launch& a, hipStream
 
 hipError_t pocs_launch_mc_init(int nblk, const pocs_mc_launch& a, hipStream_t s) {
   if ((a.wp_mode != 0 && !a.wp_counts) || (a.obs_counts && !a.wp_mode)) return hipErrorInvalidValue;
+  if (a.parts) {                                      // a compound footprint: the MC_PARTS forms (a small world, no per-box counts, no levels)
+    if (a.world || a.obs_counts || a.clr || a.parts_F < 2 || a.parts_F > POCS_MAX_FOOTPRINT_PARTS) return hipErrorInvalidValue;
+    if (a.wp_mode) hipLaunchKernelGGL(k_mc_init<MC_COUNTS | MC_PARTS>, dim3(nblk, a.nruns), dim3(POCS_BLOCK), 0, s, a);
+    else           hipLaunchKernelGGL(k_mc_init<MC_PLAIN | MC_PARTS>, dim3(nblk, a.nruns), dim3(POCS_BLOCK), 0, s, a);
+  } else
   if (a.clr) {                                        // clearance levels: the MC_CLEAR forms (a small world, no per-box counts)
     if (a.world || a.obs_counts || !a.clr_counts || !a.clr_level || a.clr_L < 1 || a.clr_L > POCS_MAX_CLEARANCE_LEVELS) return hipErrorInvalidValue;
     if (a.wp_mode) hipLaunchKernelGGL(k_mc_init<MC_COUNTS | MC_CLEAR>, dim3(nblk, a.nruns), dim3(POCS_BLOCK), 0, s, a);
@@ -193,6 +210,21 @@ hipError_t pocs_launch_mc_init(int nblk, const pocs_mc_launch& a, hipStream_t s)
 hipError_t pocs_launch_mc_step(int nblk, const pocs_mc_launch& a, hipStream_t s) {
   const dim3 grid(nblk, a.nruns), block(POCS_BLOCK);
   if ((a.wp_mode != 0 && !a.wp_counts) || (a.obs_counts && !a.wp_mode)) return hipErrorInvalidValue;
+  if (a.parts) {                                      // a compound footprint: the MC_PARTS forms of the three modes
+    if (a.world || a.obs_counts || a.clr || a.parts_F < 2 || a.parts_F > POCS_MAX_FOOTPRINT_PARTS || a.step < 0 || a.step + 1 >= a.W ||
+        (a.wp_mode == 2 && (!a.wp_stop || a.wp_n < 1)))
+      return hipErrorInvalidValue;
+    if (a.wp_mode == 2) {
+      if (a.nontemporal) hipLaunchKernelGGL((k_mc_step_counts<true, MC_STOP | MC_PARTS>), grid, block, 0, s, a);
+      else               hipLaunchKernelGGL((k_mc_step_counts<false, MC_STOP | MC_PARTS>), grid, block, 0, s, a);
+    } else if (a.wp_mode == 1) {
+      if (a.nontemporal) hipLaunchKernelGGL((k_mc_step_counts<true, MC_COUNTS | MC_PARTS>), grid, block, 0, s, a);
+      else               hipLaunchKernelGGL((k_mc_step_counts<false, MC_COUNTS | MC_PARTS>), grid, block, 0, s, a);
+    } else {
+      if (a.nontemporal) hipLaunchKernelGGL((k_mc_step_counts<true, MC_PLAIN | MC_PARTS>), grid, block, 0, s, a);
+      else               hipLaunchKernelGGL((k_mc_step_counts<false, MC_PLAIN | MC_PARTS>), grid, block, 0, s, a);
+    }
+  } else
   if (a.clr) {                                        // clearance levels: the MC_CLEAR forms of the three modes
     if (a.world || a.obs_counts || !a.clr_counts || !a.clr_level || a.clr_L < 1 || a.clr_L > POCS_MAX_CLEARANCE_LEVELS || a.step < 0 || a.step + 1 >= a.W ||
         (a.wp_mode == 2 && (!a.wp_stop || a.wp_n < 1)))
@@ -246,6 +278,7 @@ hipError_t pocs_launch_mc_step(int nblk, const pocs_mc_launch& a, hipStream_t s)
 hipError_t pocs_launch_mc_fused(int nblk, const pocs_mc_launch& a, hipStream_t s) {
   if (a.wp_mode == 2 || (a.wp_mode != 0 && !a.wp_counts) || (a.obs_counts && !a.wp_mode)) return hipErrorInvalidValue;      // (no stop without a launch boundary per step)
   if (a.clr) return hipErrorInvalidValue;             // (clearance levels: the per-step form)
+  if (a.parts) return hipErrorInvalidValue;           // (a compound footprint: the per-step form)
   if (a.world) return hipErrorInvalidValue;           // (a large world is not staged: no fused form)
   if (a.obs_counts) {
     if (a.env_steps > 1) hipLaunchKernelGGL(k_mc_fused_sched<MC_COUNTS | MC_BOXES>, dim3(nblk, a.nruns), dim3(POCS_BLOCK), 0, s, a);
@@ -433,6 +466,51 @@ hipError_t pocs_launch_probe_clearance(const pocs_env_dev* env, const pocs_clear
                                        const double* x, const double* y, const double* th, int* level_out, hipStream_t s) {
   if (!env || !clr || !tables || n < 1 || L < 0 || L > POCS_MAX_CLEARANCE_LEVELS || !x || !y || !th || !level_out) return hipErrorInvalidValue;
   hipLaunchKernelGGL(k_probe_clearance, dim3(1), dim3(POCS_BLOCK), 0, s, env, clr, L, tables, n, x, y, th, level_out);
+  return hipGetLastError();
+}
+// Which parts of a compound footprint touch, on poses, parts and a world the caller picks (pocs_probe_device_footprint_parts: a test
+// hook beside k_probe_clearance): ONE block stages the tables, the records (prepared for the covering part) and the parts as the
+// kernels' heads do and asks, per pose, the functions the kernels ask: pocs_pose_parts_touched as the MC kernels' predicate forms
+// its flag; and pocs_pair_parts_masks as k_gmm_step's parts form calls it, pose 2 p with pose 2 p + 1 (an odd last pose with
+// itself) -- bit 8 is set in a pose's answer should the two forms ever disagree.
+__global__ __launch_bounds__(POCS_BLOCK) void k_probe_parts(const pocs_env_dev* __restrict__ env, const pocs_parts_dev* __restrict__ parts, int F,
+                                                            const pocs_tables* __restrict__ tables, int n, const double* __restrict__ x,
+                                                            const double* __restrict__ y, const double* __restrict__ th, int* __restrict__ out) {
+  __shared__ pocs_tables s_tab;
+  __shared__ __attribute__((aligned(16))) double s_obs[POCS_MAX_OBSTACLES * POCS_OBS_STRIDE];
+  __shared__ double s_parts[POCS_MAX_FOOTPRINT_PARTS * POCS_PART_STRIDE];
+  stage_tables(tables, &s_tab);
+  for (int j = threadIdx.x; j < POCS_MAX_OBSTACLES * POCS_OBS_STRIDE; j += POCS_BLOCK) s_obs[j] = env->obs[j];
+  if (threadIdx.x < POCS_MAX_FOOTPRINT_PARTS * POCS_PART_STRIDE) s_parts[threadIdx.x] = parts->part[threadIdx.x];
+  __syncthreads();
+  const int M = env->M;
+  POCS_VCONST(vc_);
+  const int npairs = (n + 1) / 2;
+  // (every lane of a wave makes every trip: the pair form ballots)
+  for (int p0 = (int)threadIdx.x - (int)(threadIdx.x & 63); p0 < npairs; p0 += POCS_BLOCK) {
+    const int p = p0 + (int)(threadIdx.x & 63);
+    const bool live = p < npairs;
+    const int i0 = live ? 2 * p : 0, i1 = live && i0 + 1 < n ? i0 + 1 : i0;
+    const double xs[2] = {x[i0], x[i1]}, ys[2] = {y[i0], y[i1]}, ts[2] = {th[i0], th[i1]};
+    unsigned single[2], pair[2] = {0u, 0u};
+#pragma unroll
+    for (int h = 0; h < 2; ++h) single[h] = pocs_pose_parts_touched(xs[h], ys[h], ts[h], s_parts, F, s_obs, M, &s_tab);
+    unsigned long long all[2];
+    pocs_pair_parts_masks(xs, ys, ts, s_parts, F, s_obs, M, &s_tab, &vc_, all, [&](const int f, const unsigned long long m0, const unsigned long long m1) {
+      if (__builtin_amdgcn_inverse_ballot_w64(m0)) pair[0] |= 1u << f;
+      if (__builtin_amdgcn_inverse_ballot_w64(m1)) pair[1] |= 1u << f;
+    });
+    const bool any0 = __builtin_amdgcn_inverse_ballot_w64(all[0]), any1 = __builtin_amdgcn_inverse_ballot_w64(all[1]);
+    if (live) {
+      out[i0] = (int)(single[0] | ((pair[0] != single[0] || any0 != (single[0] != 0u) || (i1 == i0 && single[1] != single[0])) ? 256u : 0u));
+      if (i1 != i0) out[i1] = (int)(single[1] | ((pair[1] != single[1] || any1 != (single[1] != 0u)) ? 256u : 0u));
+    }
+  }
+}
+hipError_t pocs_launch_probe_parts(const pocs_env_dev* env, const pocs_parts_dev* parts, int F, const pocs_tables* tables, int n,
+                                   const double* x, const double* y, const double* th, int* touched_out, hipStream_t s) {
+  if (!env || !parts || !tables || n < 1 || F < 1 || F > POCS_MAX_FOOTPRINT_PARTS || !x || !y || !th || !touched_out) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(k_probe_parts, dim3(1), dim3(POCS_BLOCK), 0, s, env, parts, F, tables, n, x, y, th, touched_out);
   return hipGetLastError();
 }
 hipError_t pocs_launch_fill(void* dst, long long bytes, hipStream_t s) {

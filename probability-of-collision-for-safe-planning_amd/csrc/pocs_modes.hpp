@@ -75,6 +75,12 @@ static const Row kRows[] = {
     {kAddObstacle, kLargeWorld, POCS_E_ARG, POCS_OK, "the text channel serves worlds of at most %d boxes"},
 };
 
+// A compound footprint (pocs_set_footprint_parts with F > 1) is not a mode of the table: it changes results, so what it is not
+// built for is refused in both directions -- entering any of these while it is set (may_enter asks in front of the table), and
+// setting it under any of these (the setter asks) -- with POCS_E_STATE (the setter inside a begin/end sequence: POCS_E_ORDER).
+constexpr unsigned kPartsExcluded = kTree | kShard | kXchgCreated | kXchgConnected | kMoments | kLargeWorld | kObsCounts | kSequence | kProbe;
+static const char* const kPartsClause = "a compound footprint is served by whole calls on one GPU over worlds of at most 64 boxes, without per-box counts";
+
 // May a context whose active modes are `active` enter `enter`?  `among`: the modes asked about now -- a setter whose argument
 // checks stand between two of its combination checks asks in stages, so that a call with two faults keeps its code.
 struct Refusal { int code; Mode by; const char* clause; };
