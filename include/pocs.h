@@ -485,6 +485,51 @@ int pocs_get_batch_clearance_probabilities(pocs_ctx* ctx, int level, double* out
 int pocs_set_footprint_parts(pocs_ctx* ctx, const double* parts /* F x {dx, dy, half_x, half_y} */, int F);
 int pocs_get_footprint_parts(const pocs_ctx* ctx, double* parts, int cap /* in parts */);   /* writes and returns F (1 after pocs_set_footprint) */
 
+/* ---- watched regions: arrival and pass-through counts per waypoint (ours) ------------------------
+ * Whether a plan ARRIVES, out of the samples and particles a call draws anyway.  A region is a box {cx, cy, half_x, half_y, yaw_rad} in the
+ * layout of pocs_set_obstacles plus a kind; at most POCS_MAX_REGIONS of them.  Regions truncate nothing, are static (they follow no
+ * obstacle schedule) and change no other result of any call by a bit.
+ *   POCS_REGION_TOUCH  a pose is IN the region exactly when pocs_pose_collides answers "touches" for the robot's footprint in force
+ *                      against the one-box table holding the region: the same operations in the same order, touching counts;
+ *   POCS_REGION_POINT  the same predicate with the footprint {0, 0, 0, 0}: the pose's reference point lies in the box or on its
+ *                      boundary.  (pocs_set_footprint still refuses half extents <= 0: the point is internal to the regions.)
+ * pocs_set_regions: 0 <= G <= POCS_MAX_REGIONS boxes and kinds; G = 0 (the default) clears.  POCS_E_ARG for G out of range, a null
+ * pointer, a value that is not finite, a half extent <= 0 or a kind other than 0 or 1, and the table in force stays.  The regions
+ * belong to the context: they survive pocs_set_plans and pocs_set_footprint (which re-prepares the TOUCH regions).  Like every
+ * setter it ends run-ahead serving.  The text channel has no command for it.  pocs_get_regions writes and returns G.
+ *
+ * Where the regions are APPLIED: whole calls on one GPU -- pocs_run_gmm_estimation, pocs_run_simulation (pocs_mc_run_local) -- as
+ * single runs, batches in both sub-batch forms, run-ahead, calls of plans with and without the risk bounds, over static worlds of up
+ * to 64 boxes and obstacle schedules.  A GMM call of one run then takes the ticket form (POCS_OPT_LONE_CALL has no effect, as under
+ * clearance levels), an MC call the per-step form whatever POCS_OPT_MC_FUSED says (as under the MC risk bound).  NOT applied --
+ * never refused: a tree of plans, a large world, POCS_OPT_OBSTACLE_COUNTS = 1, a shard (with it a bound moments buffer and the
+ * exchange), the step API, a compound footprint (F > 1) and clearance levels with L > 0 (the levels keep applying): there the call
+ * is launch for launch and bit for bit the call it is with G = 0, and the two getters below answer POCS_E_STATE.
+ *
+ * pocs_get_region_counts serves the selected run (pocs_select_batch_run; plan p while plans are set; the run served last under
+ * run-ahead): writes the table, E x G row-major, sets *regions = G and returns E, the waypoints covered -- a plan's own length, or
+ * the waypoints before its stop under a risk bound (GMM, or MC with POCS_OPT_MC_RISK_BOUND).
+ *   GMM  G[w][g] = the samples drawn at waypoint w whose collision flag is 0 and which are in region g: G[w][g] <= the waypoint's
+ *        collision-free samples.  The unused twin of an odd shard's last pair does not count.
+ *   MC   G[w][g] = the particles that have collided at no waypoint <= w and are in region g at w.
+ * POCS_E_BUFFER for cap < E * G, POCS_E_ARG for null pointers, POCS_E_STATE -- the message says which -- when there was no call, G
+ * was 0, a setter touched the regions since, or the last call is one the regions are not applied to.
+ * pocs_get_batch_region_probabilities(region, waypoint): per run / plan of the last call, in run / plan order (after a run-ahead
+ * batch: the run served last); waypoint -1 means each plan's own last waypoint.  Formed on the host:
+ *   GMM  (prod_{v < w} (1 - p_v)) * (G[w][region] / N): p_v as the final probability's p_v is formed, the product in waypoint order
+ *        from 1.0, the quotient one IEEE division.  NOTE what this number is: the estimator's independence product for "free up to
+ *        w", times the share of waypoint w's samples that are free and in the region -- samples drawn from the belief truncated by
+ *        the collisions before w;
+ *   MC   G[w][region] / N, one IEEE division: exactly the cloud's joint share "never collided and in the region at w";
+ *   -1.0 for a waypoint the run / plan was not evaluated at: behind a stop, or w >= W_p. */
+#define POCS_MAX_REGIONS 4
+#define POCS_REGION_TOUCH 0
+#define POCS_REGION_POINT 1
+int pocs_set_regions(pocs_ctx* ctx, const double* boxes, const int* kinds, int G);
+int pocs_get_regions(const pocs_ctx* ctx, double* boxes, int* kinds, int cap);     /* writes and returns G */
+int pocs_get_region_counts(pocs_ctx* ctx, unsigned long long* out, int cap, int* regions);
+int pocs_get_batch_region_probabilities(pocs_ctx* ctx, int region, int waypoint, double* out, int cap);
+
 /* ---- results of the last run, for audits and parity tests ------------------------------- */
 int pocs_get_path_length(const pocs_ctx* ctx);
 int pocs_get_waypoint_probabilities(pocs_ctx* ctx, double* out, int cap);         /* `probabilities`, MCSimulator.h:660,678,817 */
@@ -548,6 +593,14 @@ int pocs_probe_device_footprint_parts(pocs_ctx* ctx, const double* parts, int F,
    of the MC kernels, and the two-pose lane-mask form of the GMM sampling kernel on poses 2 j, 2 j + 1: bit 8 is set should the two
    ever disagree).  It reads nothing of the context's world or modes, so it is never refused.  POCS_E_ARG for a null pointer, n
    outside 1 .. 2^20, bad parts or boxes and ANY input that is not finite. */
+int pocs_probe_device_regions(pocs_ctx* ctx, const double* fp4, const double* boxes, const int* kinds, int G,
+                              int n, const double* poses_xyt, int* mask_out);
+/* TEST HOOK beside pocs_probe_device_clearance: which watched regions the DEVICE finds poses of the caller's in, for the caller's own
+   footprint fp4 = {dx, dy, half_x, half_y} and G <= POCS_MAX_REGIONS boxes and kinds (as pocs_set_regions takes them), prepared as the
+   library prepares the context's.  One small launch stages them; per pose i < n bit g of mask_out[i] means "in region g" through the
+   single-pose function of the MC kernels, and bit 8 + g is set should the two-pose lane-mask form ever disagree.  It reads nothing of
+   the context's world, plans, modes or regions, so it is never refused.  POCS_E_ARG for a null pointer, n outside 1 .. 2^20, bad
+   boxes or kinds and ANY input that is not finite. */
 int pocs_get_sequence_time(pocs_ctx* ctx, double* ms, int* concurrent);  /* POCS_OPT_PROFILE=1, whole-run GMM calls: first sampling launch -> end of the last one, and how many
                                                                             sub-batches of the call were in flight side by side (their launches overlap: DESIGN.md section 5) */
 

@@ -23,6 +23,8 @@ MAX_TREE_NODES = 4096
 MAX_WORLD_STEPS = 4096
 MAX_WORLD_BOXES = 4096             # POCS_MAX_WORLD_BOXES: the largest table pocs_set_world takes
 MAX_CLEARANCE_LEVELS = 4           # POCS_MAX_CLEARANCE_LEVELS: the most distances pocs_set_clearance_levels takes
+MAX_REGIONS = 4                    # POCS_MAX_REGIONS: the most boxes pocs_set_regions takes
+REGION_TOUCH, REGION_POINT = 0, 1  # POCS_REGION_*: the robot's footprint touches the box / the pose's reference point lies in it
 MAX_FOOTPRINT_PARTS = 4            # POCS_MAX_FOOTPRINT_PARTS: the most parts pocs_set_footprint_parts takes
 
 _dp = C.POINTER(C.c_double)
@@ -89,6 +91,11 @@ SIGNATURES = {
     "pocs_probe_device_clearance": (C.c_int, [_vp, _dp, _dp, C.c_int, _dp, C.c_int, C.c_int, _dp, C.POINTER(C.c_int)]),
     "pocs_set_footprint_parts": (C.c_int, [_vp, _dp, C.c_int]),
     "pocs_get_footprint_parts": (C.c_int, [_vp, _dp, C.c_int]),
+    "pocs_set_regions": (C.c_int, [_vp, _dp, C.POINTER(C.c_int), C.c_int]),
+    "pocs_get_regions": (C.c_int, [_vp, _dp, C.POINTER(C.c_int), C.c_int]),
+    "pocs_get_region_counts": (C.c_int, [_vp, C.POINTER(C.c_ulonglong), C.c_int, C.POINTER(C.c_int)]),
+    "pocs_get_batch_region_probabilities": (C.c_int, [_vp, C.c_int, C.c_int, _dp, C.c_int]),
+    "pocs_probe_device_regions": (C.c_int, [_vp, _dp, _dp, C.POINTER(C.c_int), C.c_int, C.c_int, _dp, C.POINTER(C.c_int)]),
     "pocs_probe_device_footprint_parts": (C.c_int, [_vp, _dp, C.c_int, _dp, C.c_int, C.c_int, _dp, C.POINTER(C.c_int)]),
     "pocs_xchg_create": (C.c_int, [_vp, C.c_int, C.c_int, C.c_void_p]),
     "pocs_xchg_connect": (C.c_int, [_vp, C.c_void_p, C.c_int]),
@@ -541,6 +548,55 @@ class Context:
         self._chk(self.lib.pocs_probe_device_footprint_parts(self.h, q.ctypes.data_as(_dp) if q.size else None, q.shape[0],
                                                              b.ctypes.data_as(_dp) if b.size else None, b.shape[0], xyt.shape[0],
                                                              xyt.ctypes.data_as(_dp), out.ctypes.data_as(C.POINTER(C.c_int))))
+        return out
+
+    def set_regions(self, boxes, kinds=None):
+        """Watched regions: up to MAX_REGIONS boxes (cx, cy, half_x, half_y, yaw_rad) with a kind each (REGION_TOUCH, the default:
+        the robot's footprint touches the box; REGION_POINT: the pose's reference point lies in it); an empty list clears.  Whole MC
+        calls on one GPU then also count, per waypoint and region, the never-collided particles in it (include/pocs.h)."""
+        b = _arr(boxes).reshape(-1, 5)
+        k = np.ascontiguousarray(np.zeros(b.shape[0]) if kinds is None else kinds, dtype=np.int32).ravel()
+        assert k.size == b.shape[0]
+        ip = C.POINTER(C.c_int)
+        self._chk(self.lib.pocs_set_regions(self.h, b.ctypes.data_as(_dp) if b.size else None, k.ctypes.data_as(ip) if k.size else None, b.shape[0]))
+
+    def regions(self):
+        """The regions in force: (boxes (G, 5) float64, kinds int32[G]); G = 0: off."""
+        b = np.zeros((MAX_REGIONS, 5))
+        k = np.zeros(MAX_REGIONS, dtype=np.int32)
+        got = self._chk(self.lib.pocs_get_regions(self.h, b.ctypes.data_as(_dp), k.ctypes.data_as(C.POINTER(C.c_int)), MAX_REGIONS))
+        return b[:got], k[:got]
+
+    def region_counts(self):
+        """Region counts of the current selection (run or plan) of the last call under watched regions: an (E, G) uint64 array,
+        entry [w, g] = the particles that have collided at no waypoint <= w and are in region g at w; include/pocs.h."""
+        E = max(self.path_length(), 1)
+        out = np.zeros(E * MAX_REGIONS, dtype=np.uint64)
+        G = C.c_int(0)
+        got = self._chk(self.lib.pocs_get_region_counts(self.h, out.ctypes.data_as(C.POINTER(C.c_ulonglong)), out.size, C.byref(G)))
+        return out[:got * G.value].reshape(got, G.value)
+
+    def region_probabilities(self, region, waypoint=-1):
+        """Per run / plan of the last call: the share of the cloud that never collided and is in `region` at `waypoint` (-1: each
+        plan's own last waypoint); -1.0 where the run / plan was not evaluated at that waypoint."""
+        n = getattr(self, "_batch", 1)
+        out = np.zeros(n)
+        got = self._chk(self.lib.pocs_get_batch_region_probabilities(self.h, int(region), int(waypoint), out.ctypes.data_as(_dp), n))
+        return out[:got]
+
+    def probe_device_regions(self, footprint, boxes, kinds, poses):
+        """Test hook: per pose (n x 3) the regions (G x 5, kinds[G]) of the caller's own that the device finds it in, for a footprint
+        (dx, dy, hx, hy): int32[n], bit g = in region g, bit 8 + g = the kernels' two forms disagree on region g (never)."""
+        fp = _arr(footprint).ravel()
+        b = _arr(boxes).reshape(-1, 5)
+        k = np.ascontiguousarray(kinds, dtype=np.int32).ravel()
+        xyt = _arr(poses).reshape(-1, 3)
+        assert fp.size == 4 and k.size == b.shape[0]
+        ip = C.POINTER(C.c_int)
+        out = np.full(xyt.shape[0], -1, dtype=np.int32)
+        self._chk(self.lib.pocs_probe_device_regions(self.h, fp.ctypes.data_as(_dp), b.ctypes.data_as(_dp) if b.size else None,
+                                                     k.ctypes.data_as(ip) if k.size else None, b.shape[0], xyt.shape[0],
+                                                     xyt.ctypes.data_as(_dp), out.ctypes.data_as(ip)))
         return out
 
     def gmm_begin(self):

@@ -669,6 +669,103 @@ int pocs_get_batch_clearance_probabilities(pocs_ctx* c, int level, double* out, 
   return (int)(hi - lo);
 }
 
+// ---- watched regions (include/pocs.h) ----
+int pocs_set_regions(pocs_ctx* c, const double* boxes, const int* kinds, int G) {
+  if (!setter(c)) return POCS_E_ARG;
+  if (G < 0 || G > POCS_MAX_REGIONS || (G > 0 && (!boxes || !kinds)))
+    return fail(c, POCS_E_ARG, "pocs_set_regions: %d regions outside 0..%d (or a null pointer)", G, POCS_MAX_REGIONS);
+  if (int r = check_boxes(c, "pocs_set_regions", boxes, (size_t)G, (size_t)(G > 0 ? G : 1), true)) return r;
+  for (int g = 0; g < G; ++g)
+    if (kinds[g] != POCS_REGION_TOUCH && kinds[g] != POCS_REGION_POINT)
+      return fail(c, POCS_E_ARG, "pocs_set_regions: region %d: kind %d is neither POCS_REGION_TOUCH (0) nor POCS_REGION_POINT (1)", g, kinds[g]);
+  c->reg_G = G;
+  for (int g = 0; g < POCS_MAX_REGIONS; ++g) {
+    for (int j = 0; j < 5; ++j) c->reg_box[5 * g + j] = g < G ? boxes[5 * g + j] : 0.0;
+    c->reg_kind[g] = g < G ? kinds[g] : 0;
+  }
+  c->env_dirty = true;                               // (the regions' record lives beside the world on the device)
+  if (c->res.rg_state != Results::RgNoCall) c->res.rg_state = Results::RgTouched;      // (a table is served until the regions are touched or the next call)
+  return POCS_OK;
+}
+
+int pocs_get_regions(const pocs_ctx* c, double* boxes, int* kinds, int cap) {
+  if (!c) return POCS_E_ARG;
+  if (c->reg_G > 0 && (!boxes || !kinds || cap < c->reg_G)) return POCS_E_BUFFER;
+  for (int g = 0; g < c->reg_G; ++g) {
+    for (int j = 0; j < 5; ++j) boxes[5 * g + j] = c->reg_box[5 * g + j];
+    kinds[g] = c->reg_kind[g];
+  }
+  return c->reg_G;
+}
+
+// The table of the last call serves `what`?  POCS_E_STATE with the reason otherwise.
+static int regions_served(pocs_ctx* c, const char* what) {
+  const Results& r = c->res;
+  switch (r.rg_state) {
+    case Results::RgServed: break;
+    case Results::RgNoCall: return fail(c, POCS_E_STATE, "%s: there was no call yet", what);
+    case Results::RgOff: return fail(c, POCS_E_STATE, "%s: the last call ran without watched regions (G was 0)", what);
+    case Results::RgTouched: return fail(c, POCS_E_STATE, "%s: pocs_set_regions touched the regions since the last call", what);
+    default: return fail(c, POCS_E_STATE, "%s: the regions are not applied to the last call (a tree of plans, a large world, POCS_OPT_OBSTACLE_COUNTS, a shard, the step API, a compound footprint, clearance levels -- or it failed)", what);
+  }
+  if (r.rg_kind == Kind::None || r.rg_kind != r.last_kind || r.rg_counts.empty()) return fail(c, POCS_E_STATE, "%s: there was no call yet", what);
+  return POCS_OK;
+}
+// run / plan r of the last call: its batch slot and the waypoints its rows cover
+static void region_rows(const pocs_ctx* c, size_t r, size_t* slot, int* E) {
+  const Kind kind = c->res.rg_kind;
+  *slot = r; *E = c->res.rg_W;
+  if (c->plans.n && r < c->res.plan_slot(kind).size()) {
+    *slot = (size_t)c->res.plan_slot(kind)[r];
+    if (kind == Kind::Gmm) *E = r < c->res.plan_E.size() ? c->res.plan_E[r] : c->plans.W[r];
+    else *E = c->res.plan_E_mc.empty() ? c->plans.W[r] : c->res.plan_E_mc[r];
+  }
+}
+
+int pocs_get_region_counts(pocs_ctx* c, unsigned long long* out, int cap, int* regions) {
+  if (!c) return POCS_E_ARG;
+  if (!out || !regions) return fail(c, POCS_E_ARG, "pocs_get_region_counts: null output");
+  if (int r = regions_served(c, "pocs_get_region_counts")) return r;
+  size_t slot; int E;
+  region_rows(c, (size_t)c->res.view, &slot, &E);
+  const size_t G = (size_t)c->res.rg_G, W = (size_t)c->res.rg_W;
+  if ((slot + 1) * W * POCS_MAX_REGIONS > c->res.rg_counts.size() || (size_t)E > W)
+    return fail(c, POCS_E_STATE, "pocs_get_region_counts: the table does not cover the selection");
+  *regions = (int)G;
+  if ((size_t)(cap < 0 ? 0 : cap) < (size_t)E * G) return fail(c, POCS_E_BUFFER, "need %zu counters", (size_t)E * G);
+  for (size_t w = 0; w < (size_t)E; ++w)
+    for (size_t g = 0; g < G; ++g) out[w * G + g] = c->res.rg_counts[(slot * W + w) * POCS_MAX_REGIONS + g];
+  return E;
+}
+
+int pocs_get_batch_region_probabilities(pocs_ctx* c, int region, int waypoint, double* out, int cap) {
+  if (!c) return POCS_E_ARG;
+  if (!out) return fail(c, POCS_E_ARG, "pocs_get_batch_region_probabilities: null output");
+  if (int r = regions_served(c, "pocs_get_batch_region_probabilities")) return r;
+  if (region < 0 || region >= c->res.rg_G) return fail(c, POCS_E_ARG, "pocs_get_batch_region_probabilities: region %d outside 0..%d", region, c->res.rg_G - 1);
+  if (waypoint < -1) return fail(c, POCS_E_ARG, "pocs_get_batch_region_probabilities: waypoint %d (-1: each plan's own last waypoint)", waypoint);
+  const size_t W = (size_t)c->res.rg_W, R = c->res.rg_counts.size() / (W * POCS_MAX_REGIONS);
+  const size_t lo = c->ra_internal ? (size_t)c->res.view : 0, hi = c->ra_internal ? lo + 1 : R;
+  if ((long long)(hi - lo) > (long long)cap) return fail(c, POCS_E_BUFFER, "need %zu doubles", hi - lo);
+  const double n = (double)c->res.rg_N;
+  for (size_t r = lo; r < hi; ++r) {
+    size_t slot; int E;
+    region_rows(c, r, &slot, &E);
+    // the run's / plan's own length (a stop shortens E, not the plan): -1 asks for its last waypoint
+    const int Wr = c->plans.n && r < c->plans.W.size() ? c->plans.W[r] : (int)W;
+    const int w = waypoint < 0 ? Wr - 1 : waypoint;
+    if (w >= E || w >= Wr) { out[r - lo] = -1.0; continue; }      // (not evaluated there: behind a stop, or past the plan's end)
+    const double share = (double)c->res.rg_counts[(slot * W + (size_t)w) * POCS_MAX_REGIONS + (size_t)region] / n;      // one division
+    if (c->res.rg_kind == Kind::Mc) { out[r - lo] = share; continue; }      // the cloud's joint share "never collided and in the region at w"
+    // GMM: the estimator's independence product for "free up to w", p_v formed as gmm_combine forms it, in waypoint order from 1.0
+    const size_t Rb = (size_t)c->res.batch_R, NC = (size_t)c->K * POCS_NMOM;
+    double prod = 1.0;
+    for (int v = 0; v < w; ++v) prod *= (1.0 - waypoint_probability(&c->res.batch_moments[((size_t)v * Rb + slot) * NC], c->K, (long long)c->res.rg_N));
+    out[r - lo] = prod * share;
+  }
+  return (int)(hi - lo);
+}
+
 int pocs_get_batch_probabilities(pocs_ctx* c, double* out, int cap) {
   if (!c || !out) return POCS_E_ARG;
   return batch_out(c, out, cap, c->res.batch_probs, "doubles");

@@ -398,6 +398,54 @@ int pocs_probe_device_footprint_parts(pocs_ctx* c, const double* parts, int F, c
   return rc;
 }
 
+// Test hook: which watched regions the device finds chosen poses in, for a footprint and regions of the caller's own
+// (include/pocs.h).  Nothing of the context's world, plans, modes or regions is read: the record is prepared here, as upload_world
+// prepares the context's.
+int pocs_probe_device_regions(pocs_ctx* c, const double* fp4, const double* boxes, const int* kinds, int G, int n,
+                              const double* poses, int* mask_out) {
+  if (!c) return POCS_E_ARG;
+  if (!fp4 || !poses || !mask_out || n < 1 || n > (1 << 20) || G < 0 || G > POCS_MAX_REGIONS || (G > 0 && (!boxes || !kinds)))
+    return fail(c, POCS_E_ARG, "pocs_probe_device_regions: 1 <= n <= 2^20, 0 <= G <= %d, no null pointers", POCS_MAX_REGIONS);
+  for (int j = 0; j < 4; ++j)
+    if (!std::isfinite(fp4[j])) return fail(c, POCS_E_ARG, "pocs_probe_device_regions: footprint value %d is not finite", j);
+  if (!(fp4[2] > 0) || !(fp4[3] > 0)) return fail(c, POCS_E_ARG, "pocs_probe_device_regions: footprint half extents must be > 0");
+  for (size_t j = 0; j < 5 * (size_t)G; ++j)
+    if (!std::isfinite(boxes[j])) return fail(c, POCS_E_ARG, "pocs_probe_device_regions: region %zu: value %zu is not finite", j / 5, j % 5);
+  for (int g = 0; g < G; ++g) {
+    if (!(boxes[5 * (size_t)g + 2] > 0) || !(boxes[5 * (size_t)g + 3] > 0)) return fail(c, POCS_E_ARG, "pocs_probe_device_regions: region %d: half extents must be > 0", g);
+    if (kinds[g] != POCS_REGION_TOUCH && kinds[g] != POCS_REGION_POINT) return fail(c, POCS_E_ARG, "pocs_probe_device_regions: region %d: kind %d", g, kinds[g]);
+  }
+  for (size_t j = 0; j < 3 * (size_t)n; ++j)
+    if (!std::isfinite(poses[j])) return fail(c, POCS_E_ARG, "pocs_probe_device_regions: pose %zu is not finite", j / 3);
+  HIPCHK(c, hipSetDevice(c->device));
+  if (int r = upload_tables(c)) return r;
+  const pocs_footprint fp = {fp4[0], fp4[1], fp4[2], fp4[3]};
+  pocs_regions_dev reg;
+  prepare_regions(fp, boxes, kinds, G, &reg);
+  std::vector<double> h(3 * (size_t)n);
+  for (int i = 0; i < n; ++i)
+    for (int j = 0; j < 3; ++j) h[(size_t)j * n + i] = poses[3 * (size_t)i + j];
+  // [regions | x | y | th] then [masks n] ints
+  const size_t off_x = sizeof(pocs_regions_dev), off_out = off_x + 3 * (size_t)n * sizeof(double);
+  static_assert(sizeof(pocs_regions_dev) % 8 == 0, "the probe's buffer keeps its parts aligned");
+  char* buf = nullptr;
+  HIPCHK(c, hipMalloc((void**)&buf, off_out + (size_t)n * sizeof(int)));
+  int rc = POCS_OK;
+  if (hipMemcpy(buf, &reg, sizeof reg, hipMemcpyHostToDevice) != hipSuccess ||
+      hipMemcpy(buf + off_x, h.data(), h.size() * sizeof(double), hipMemcpyHostToDevice) != hipSuccess ||
+      hipMemset(buf + off_out, 0, (size_t)n * sizeof(int)) != hipSuccess)
+    rc = fail(c, POCS_E_DEVICE, "probe upload failed");
+  const double* d_x = (const double*)(buf + off_x);
+  if (rc == POCS_OK && pocs_launch_probe_regions((const pocs_regions_dev*)buf, G, (const pocs_tables*)c->d_tables.p, n,
+                                                 d_x, d_x + n, d_x + 2 * (size_t)n, (int*)(buf + off_out), c->stream) != hipSuccess)
+    rc = fail(c, POCS_E_DEVICE, "probe launch failed");
+  if (rc == POCS_OK && hipStreamSynchronize(c->stream) != hipSuccess) rc = fail(c, POCS_E_DEVICE, "probe kernel failed");
+  if (rc == POCS_OK && hipMemcpy(mask_out, buf + off_out, (size_t)n * sizeof(int), hipMemcpyDeviceToHost) != hipSuccess)
+    rc = fail(c, POCS_E_DEVICE, "probe download failed");
+  (void)hipFree(buf);
+  return rc;
+}
+
 int pocs_get_sequence_time(pocs_ctx* c, double* ms, int* concurrent) {
   if (!c) return POCS_E_ARG;
   if (ms) *ms = c->seq_ms;

@@ -540,3 +540,61 @@ __device__ __forceinline__ void pocs_pair_parts_masks(const double x[2], const d
   mask[0] = all0; mask[1] = all1;
 }
 #endif
+
+// ---- watched regions (pocs_set_regions) -----------------------------------------------------------------------------
+// A region is a box of the obstacle layout that truncates nothing: a call counts the surviving poses that are in it.  A pose
+// is IN region g exactly when pocs_pose_collides answers "touches" against the one-box table holding the region, for the
+// region's own footprint -- the robot's (POCS_REGION_TOUCH) or the point {0, 0, 0, 0} (POCS_REGION_POINT: the pose's
+// reference point lies in the box or on its boundary).  Record g (POCS_OBS_STRIDE doubles) is prepared by
+// pocs_prepare_obstacle for footprint g (four doubles: dx dy hx hy).  The same operations in the same order as
+// pocs_pose_collides, touching included; the functions above stay what they are.
+#define POCS_MAX_REGIONS 4
+#define POCS_REGION_TOUCH 0
+#define POCS_REGION_POINT 1
+
+// One pose: bit g of the answer = the pose is in region g.  The heading's sine and cosine are formed once.
+POCS_HD unsigned pocs_pose_regions_mask(double x, double y, double th, const double* rec, const double* fps, int G,
+                                        const pocs_tables* T, const pocs_vconst* V = nullptr) {
+  if (G <= 0) return 0u;
+  double sn, cs;
+  pocs_sincos_tab(th, T, &sn, &cs, V);
+  unsigned in = 0u;
+  for (int g = 0; g < G; ++g) {
+    const double* f = fps + 4 * g;
+    double px = x, py = y;
+    if (!(f[0] == 0.0 && f[1] == 0.0)) {          // (pocs_pose_collides: a centred footprint skips x + (c*0 - s*0) == x)
+      px = x + fma(cs, f[0], -(sn * f[1]));
+      py = y + fma(sn, f[0], cs * f[1]);
+    }
+    if (pocs_box_hit(px, py, sn, cs, f[2], f[3], rec + g * POCS_OBS_STRIDE)) in |= 1u << g;
+  }
+  return in;
+}
+
+#if defined(__HIPCC__)
+// The same for the pair of poses a sampling thread holds, as lane masks per region: each(g, m0, m1) is called once per region
+// of `keep` with the lanes whose pose 0 / pose 1 is in it.  Per region the one-record loop of pocs_pair_collides_masks with the region's
+// footprint: every branch is wave-uniform, and a region whose broad phase no lane of either pose passes costs two ballots.
+// `rec` and `fps` lie in LDS; a footprint's four values are the same in every lane and are moved to scalar registers, so
+// that the centred / offset choice of pocs_pair_collides_masks stays a scalar branch.
+__device__ __forceinline__ double pocs_wave_uniform_f64(double v) {
+  const unsigned long long u = __builtin_bit_cast(unsigned long long, v);
+  const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)u), hi = __builtin_amdgcn_readfirstlane((unsigned)(u >> 32));
+  return __builtin_bit_cast(double, ((unsigned long long)hi << 32) | (unsigned long long)lo);
+}
+template <class Each>
+__device__ __forceinline__ void pocs_pair_regions_masks(const double x[2], const double y[2], const double th[2], const double* rec,
+                                                        const double* fps, int G, unsigned keep, const pocs_tables* T, const pocs_vconst* V,
+                                                        Each each) {
+  // keep (wave-uniform): bit g clear = the caller knows that no pose of the wave can be in region g; it is not looked at
+#pragma unroll 1
+  for (int g = 0; g < G; ++g) {
+    if (((keep >> g) & 1u) == 0u) continue;
+    const pocs_footprint f = {pocs_wave_uniform_f64(fps[4 * g]), pocs_wave_uniform_f64(fps[4 * g + 1]),
+                              pocs_wave_uniform_f64(fps[4 * g + 2]), pocs_wave_uniform_f64(fps[4 * g + 3])};
+    unsigned long long m[2];
+    pocs_pair_collides_masks<false>(x, y, th, &f, rec + g * POCS_OBS_STRIDE, 1, T, V, m);
+    each(g, m[0], m[1]);
+  }
+}
+#endif

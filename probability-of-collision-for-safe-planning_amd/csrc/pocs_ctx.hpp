@@ -106,6 +106,14 @@ struct Results {
   int cl_L = 0, cl_W = 0;
   long long cl_N = 0;                             // samples / particles per waypoint of the call: the probabilities' divisor
   std::vector<unsigned long long> cl_counts;
+  // watched regions (pocs_set_regions): the table of the last call, read back with its results in slot order
+  // ([slot][rg_W][POCS_MAX_REGIONS]), and why there is none to serve (pocs_get_region_counts names it)
+  enum RegionState { RgNoCall, RgOff, RgTouched, RgNotApplied, RgServed };
+  RegionState rg_state = RgNoCall;
+  Kind rg_kind = Kind::None;
+  int rg_G = 0, rg_W = 0;
+  long long rg_N = 0;                             // samples / particles per waypoint of the call: the probabilities' divisor
+  std::vector<unsigned long long> rg_counts;
 };
 
 // One cached graph and its signature: the bytes of its launches in issue order (Issuer, pocs_host.hip), compared before a replay.
@@ -192,6 +200,11 @@ struct pocs_ctx {
   // pocs_host.hip); everywhere else a call is the call it is with L = 0
   int clr_L = 0;
   double clr_d[POCS_MAX_CLEARANCE_LEVELS] = {0.0, 0.0, 0.0, 0.0};
+  // watched regions (pocs_set_regions): G = 0 is off.  Applied where regions_applied (pocs_host.hip) says; everywhere else a call is
+  // the call it is with G = 0
+  int reg_G = 0;
+  double reg_box[POCS_MAX_REGIONS * 5] = {};
+  int reg_kind[POCS_MAX_REGIONS] = {};
   // a compound footprint (pocs_set_footprint_parts): F = 1 is the single box `fp`.  F > 1: `fp` is part 0, every call is served by the
   // kernels' _parts / MC_PARTS forms (parts_applied, pocs_host.hip) and the modes of pocs_modes::kPartsExcluded are refused
   int fp_F = 1;
@@ -221,6 +234,9 @@ struct pocs_ctx {
   // clearance levels: [world_S] pocs_clear_dev beside d_env (upload_world), the counters [slots][W][POCS_MAX_CLEARANCE_LEVELS] u64 zeroed
   // by a kernel at the head of every call's launches, and the MC particles' smallest level so far [slots][stride] u8
   pocs_rt::DevBuf d_clr, d_clrct, d_clrlv;
+  // watched regions: one pocs_regions_dev beside d_env (upload_world) and the counters [slots][W][POCS_MAX_REGIONS] u64, zeroed by a
+  // kernel at the head of every call's launches
+  pocs_rt::DevBuf d_reg, d_regct;
   pocs_rt::DevBuf d_parts;               // a compound footprint: one pocs_parts_dev beside d_env (upload_world)
   pocs_rt::DevBuf d_obsct;               // POCS_OPT_OBSTACLE_COUNTS: [slots][W][POCS_MAX_OBSTACLES] u64, zeroed by a kernel at the head of every call's launches
   // one-hop exchange (pocs_xchg_*): this rank's buffer, the peers' buffers as mapped here
@@ -315,6 +331,7 @@ inline void reset_results(pocs_ctx* c) {
   r.tree_probs.clear(); r.tree_eval.clear(); r.tree_F.clear(); r.tree_C.clear();
   r.oc_kind = Kind::None; r.oc_M = 0; r.oc_W = 0;
   r.cl_state = Results::ClNoCall; r.cl_kind = Kind::None; r.cl_L = 0; r.cl_W = 0; r.cl_N = 0; r.cl_counts.clear();
+  r.rg_state = Results::RgNoCall; r.rg_kind = Kind::None; r.rg_G = 0; r.rg_W = 0; r.rg_N = 0; r.rg_counts.clear();
 }
 
 // The collision world: M boxes per step, and the record of the device's env array ([world_S] pocs_env_dev) that waypoint w --
@@ -392,6 +409,9 @@ int upload_world(pocs_ctx* c);
 void fill_gmm_world(const pocs_ctx* c, pocs_gmm_launch* a, int w);
 size_t obs_count_words(const pocs_ctx* c);
 bool clearance_applied(const pocs_ctx* c);
+bool regions_applied(const pocs_ctx* c);
+double waypoint_probability(const double* row, int K, long long n);
+void prepare_regions(const pocs_footprint& fp, const double* boxes, const int* kinds, int G, pocs_regions_dev* out);
 void prepare_parts(const pocs_footprint* parts, int F, const double* boxes, int M, pocs_env_dev* env, pocs_parts_dev* out);
 void prepare_clearance(const pocs_footprint& fp, const double* d, int L, const double* boxes, int M, pocs_clear_dev* out);
 void gmm_select_view(pocs_ctx* c, int v);

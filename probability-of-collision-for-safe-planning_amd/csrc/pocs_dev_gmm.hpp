@@ -64,8 +64,17 @@ template <bool FPN> struct gmm_fp_smem {};
 template <> struct gmm_fp_smem<true> {
   double fpp[POCS_MAX_FOOTPRINT_PARTS * POCS_PART_STRIDE];
 };
-template <int K, int TB, bool OC = false, bool CL = false, bool FPN = false>
-struct gmm_smem : gmm_oc_smem<OC>, gmm_cl_smem<CL>, gmm_fp_smem<FPN> {
+//   rgh / rgk / rgc  (the regions form only, pocs_set_regions: an empty base otherwise again) the regions' records and footprints
+//          (pocs_regions_dev's head, 384 B), per run buffer the regions the run's mixture can reach (a bit each) and per run buffer and
+//          region the block's collision-free samples in it: 432 B, so K = 8 holds 75 856 B against the twin's 75 424
+template <bool RG> struct gmm_rg_smem {};
+template <> struct gmm_rg_smem<true> {
+  alignas(16) double rgh[POCS_REGIONS_HEAD];
+  unsigned rgc[2][POCS_MAX_REGIONS];
+  unsigned rgk[2];
+};
+template <int K, int TB, bool OC = false, bool CL = false, bool FPN = false, bool RG = false>
+struct gmm_smem : gmm_oc_smem<OC>, gmm_cl_smem<CL>, gmm_fp_smem<FPN>, gmm_rg_smem<RG> {
   static constexpr int NC = K * POCS_NMOM;
   static constexpr int NW = TB / 64;
   // (the clearance form holds 24 units at a time, not 32: with its second kept table K = 7 and K = 8 would otherwise pass the 80 KB
@@ -120,8 +129,8 @@ __device__ __forceinline__ double oct_sum(double s) {     // lanes 8 j .. 8 j + 
 // wave's xtra entry of k), and the chains restart.  By LDS transposition, five then four sums at a
 // time: every lane writes its values, lane 8 j + q adds lanes 8 q .. 8 q + 7 of sum j, oct_sum adds the
 // eight q.  One wave: the LDS executes a wave's instructions in order, nothing else synchronises.
-template <int K, int TB, bool OC, bool CL, bool FPN>
-__device__ __forceinline__ void flush_unit(gmm_smem<K, TB, OC, CL, FPN>& sm, const int wave, const int lane, const int rb, const int tl,
+template <int K, int TB, bool OC, bool CL, bool FPN, bool RG>
+__device__ __forceinline__ void flush_unit(gmm_smem<K, TB, OC, CL, FPN, RG>& sm, const int wave, const int lane, const int rb, const int tl,
                                            const int k, bool& first, double (&acc)[9], int& nfree) {
   double* const T = &sm.tr[wave][0][0];
   double* const dst = first ? &sm.slot[tl][wave][0] : &sm.xtra[rb][wave][k][0];
@@ -187,8 +196,8 @@ __device__ __forceinline__ void gmm_reach(const pocs_footprint& fp, const double
   ext_y = pocs_footprint_extent_is_radius(fp_phi, tlo - HALF_PI, thi - HALF_PI) ? fp_rr
         : pocs_footprint_extent_of_ends(fp_rr, lane_value(end_f, 2), lane_value(end_f, 3));
 }
-template <int K, int TB, bool OC, bool CL, bool FPN>
-__device__ __forceinline__ void gmm_cull(const pocs_gmm_launch& a, gmm_smem<K, TB, OC, CL, FPN>& sm, const int rb, const int lane, const double* par) {
+template <int K, int TB, bool OC, bool CL, bool FPN, bool RG>
+__device__ __forceinline__ void gmm_cull(const pocs_gmm_launch& a, gmm_smem<K, TB, OC, CL, FPN, RG>& sm, const int rb, const int lane, const double* par) {
   const pocs_footprint fp = a.fp;
   const int M = a.M;
   const double* const obs = sm.obs();
@@ -339,6 +348,34 @@ __device__ __forceinline__ void gmm_cull_parts(const pocs_gmm_launch& a, gmm_sme
   if (lane == 0) sm.nkeep[rb] = __popcll(mask);
 }
 
+// The regions form's reach (one wave, all 64 lanes, beside the wave that runs gmm_cull for the same run buffer): lane g decides
+// whether the run's mixture can reach region g at all -- gmm_cull's conservative keep test against the mixture's bounding box (the
+// same 6.67 sigma box, padded by the footprint's offset), with the region's own footprint: the record's broad-phase half extents
+// are its AABB grown by that footprint's bounding radius (pocs_prepare_obstacle), which bounds the footprint's extent at every
+// heading.  A region that fails it fails pocs_box_hit's broad phase for every sample of the run.  The answers are a bit each in
+// rgk[rb]; the region counters of the buffer start at zero.
+template <int K, int TB, bool OC, bool CL, bool FPN>
+__device__ __forceinline__ void gmm_cull_regions(const pocs_gmm_launch& a, gmm_smem<K, TB, OC, CL, FPN, true>& sm, const int rb, const int lane, const double* par) {
+  double xlo = 1e300, xhi = -1e300, ylo = 1e300, yhi = -1e300;
+#pragma unroll
+  for (int k = 0; k < K; ++k) {
+    const double* p = &par[k * POCS_PARAM_STRIDE];
+    const double ex = 6.67 * fabs(p[3]), ey = 6.67 * (fabs(p[4]) + fabs(p[5]));
+    xlo = fmin(xlo, p[0] - ex); xhi = fmax(xhi, p[0] + ex);
+    ylo = fmin(ylo, p[1] - ey); yhi = fmax(yhi, p[1] + ey);
+  }
+  bool keep = false;
+  if (lane < a.reg_G) {
+    const double* o = &sm.rgh[lane * POCS_OBS_STRIDE];
+    const double* f = &sm.rgh[POCS_MAX_REGIONS * POCS_OBS_STRIDE + 4 * lane];
+    const double pad = sqrt(f[0] * f[0] + f[1] * f[1]) + 1e-6;
+    keep = !(o[0] - o[6] > xhi + pad || o[0] + o[6] < xlo - pad || o[1] - o[7] > yhi + pad || o[1] + o[7] < ylo - pad);
+  }
+  const unsigned long long mask = __ballot(keep);
+  if (lane < POCS_MAX_REGIONS) sm.rgc[rb][lane] = 0u;
+  if (lane == 0) sm.rgk[rb] = (unsigned)mask;
+}
+
 // ---------------------------------------------------------------------------------------------
 // THE BODY: units [ta, tb) of the launch (unit t = virtual slice t mod VS of run t / VS; at most
 // POCS_GMM_SUB of them, of at most two runs r0 and r0 + 1 whose parameters and culled tables are staged
@@ -360,8 +397,12 @@ __device__ __forceinline__ void gmm_cull_parts(const pocs_gmm_launch& a, gmm_sme
 //   the population count to the block's LDS counter of (run buffer, level).  The odd shard's unused twin does not count.
 //   FPN (pocs_set_footprint_parts, F > 1): the collision test is pocs_pair_parts_masks over the parts staged in sm.fpp, on the one
 //   kept list (gmm_cull_parts); the flag is the OR of the parts' flags and everything behind it is what it is.
-template <int K, bool STORE, int TB, bool LONE_PRE = false, bool OC = false, bool CL = false, bool FPN = false>
-__device__ __forceinline__ void gmm_units(const pocs_gmm_launch& a, gmm_smem<K, TB, OC, CL, FPN>& sm, const int w, const int r0,
+//   RG (pocs_set_regions): behind the unchanged collision test the region test runs over the regions the run's mixture can reach
+//   (sm.rgk[rb]: usually none, one scalar branch); per region the lanes whose sample exists, whose flag is 0 and which are in the
+//   region are picked by scalar ands of the masks and lane 0 adds the population count to the block's LDS counter of (run buffer,
+//   region).  The odd shard's unused twin does not count.
+template <int K, bool STORE, int TB, bool LONE_PRE = false, bool OC = false, bool CL = false, bool FPN = false, bool RG = false>
+__device__ __forceinline__ void gmm_units(const pocs_gmm_launch& a, gmm_smem<K, TB, OC, CL, FPN, RG>& sm, const int w, const int r0,
                                           const int ta, const int tb, const double* zpre = nullptr, const int npre = 0) {
   const pocs_tables* const s_tab = &sm.tab;
   const int tid = threadIdx.x, lane = tid & 63;
@@ -396,6 +437,7 @@ __device__ __forceinline__ void gmm_units(const pocs_gmm_launch& a, gmm_smem<K, 
   const double* s_keep = nullptr;
   [[maybe_unused]] const double* s_keep2 = nullptr;       // CL: the second kept list and its length
   [[maybe_unused]] int nkeep2 = 0;
+  [[maybe_unused]] unsigned rgkeep = 0u;                  // RG: the regions in the run's reach, a bit each
   uint64_t seed = 0;
   double cumn[K > 1 ? K - 1 : 1];                   // cumulative component counts
   double *xr = nullptr, *yr = nullptr, *tr = nullptr;
@@ -487,6 +529,17 @@ __device__ __forceinline__ void gmm_units(const pocs_gmm_launch& a, gmm_smem<K, 
         if (n != 0u && lane == 0) __hip_atomic_fetch_add(&clc[l], n, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
       });
     }
+    if constexpr (RG) {
+      if (rgkeep != 0u) {                                            // (scalar: nearly every waypoint's belief is near no region)
+        const unsigned long long f0 = (WHOLE ? ~0ull : __ballot(live)) & ~hits[0], f1 = (WHOLE ? ~0ull : __ballot(two)) & ~hits[1];
+        unsigned* const rgc = sm.rgc[rb];
+        pocs_pair_regions_masks(xs, ys, ts, &sm.rgh[0], &sm.rgh[POCS_MAX_REGIONS * POCS_OBS_STRIDE], a.reg_G, rgkeep, s_tab, vc,
+                                [&](const int g, const unsigned long long m0, const unsigned long long m1) {
+          const unsigned n = (unsigned)__popcll(m0 & f0) + (unsigned)__popcll(m1 & f1);      // (scalar)
+          if (n != 0u && lane == 0) __hip_atomic_fetch_add(&rgc[g], n, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+        });
+      }
+    }
     if constexpr (POCS_TUNE_SKIP_MOMENTS) { POCS_TUNE_MOMENTS_ALT(); } else {
     // T1 sums over the collision-free samples of the component being accumulated:
     //   (x, y, t, x x, x y, x t, y y, y t, t t) with the products inside the fma; survivors by population count.
@@ -563,6 +616,7 @@ __device__ __forceinline__ void gmm_units(const pocs_gmm_launch& a, gmm_smem<K, 
       s_par = sm.par[rb]; s_keep = sm.keep[rb];
       nkeep = __builtin_amdgcn_readfirstlane(sm.nkeep[rb]);
       if constexpr (CL) { s_keep2 = sm.keep2[rb]; nkeep2 = __builtin_amdgcn_readfirstlane(sm.nkeep2[rb]); }
+      if constexpr (RG) rgkeep = (unsigned)__builtin_amdgcn_readfirstlane((int)sm.rgk[rb]);
       seed = (uint64_t)uniform64((long long)sm.seed[rb]);         // scalar registers, provably
 #pragma unroll
       for (int q = 0; q < K - 1; ++q) cumn[q] = s_par[q * POCS_PARAM_STRIDE + 9];
@@ -613,8 +667,8 @@ __device__ __forceinline__ void gmm_units(const pocs_gmm_launch& a, gmm_smem<K, 
 // order -- whichever of them the unit has: slot if the component was the wave's first there, xtra if it
 // started inside the wave's share, +0 otherwise -- stored write-through to the run's partial rows.
 // Column 1 (collisions) stays 0: a component's collisions are what is left of its block (gmm_close_sums).
-template <int K, int TB, bool OC, bool CL, bool FPN>
-__device__ __forceinline__ void gmm_emit_rows(const pocs_gmm_launch& a, gmm_smem<K, TB, OC, CL, FPN>& sm, const int r0, const int ta, const int tb) {
+template <int K, int TB, bool OC, bool CL, bool FPN, bool RG>
+__device__ __forceinline__ void gmm_emit_rows(const pocs_gmm_launch& a, gmm_smem<K, TB, OC, CL, FPN, RG>& sm, const int r0, const int ta, const int tb) {
   constexpr int NC = K * POCS_NMOM, NW = TB / 64;
   for (int i = threadIdx.x; i < (tb - ta) * NC; i += TB) {
     const int tl = i / NC, c = i - tl * NC, k = c / POCS_NMOM, col = c - k * POCS_NMOM;
@@ -800,9 +854,19 @@ __device__ __forceinline__ void gmm_close_sums(const pocs_gmm_launch& a, const i
 // gmm_cull_parts in place of gmm_cull -- ONE kept list per run buffer, a record kept if any part's keep test passes, its broad-phase
 // fields the largest of the parts' -- and the body asks pocs_pair_parts_masks.  The moment sums, the tickets and the closers are what
 // they are.  LDS: + 192 B for the parts (K = 8: 75 616 B against the twin's 75 424): two blocks per CU in every instantiation.
-template <int K, bool STORE, int TB, bool LONE, bool RISK, bool TREE = false, bool OC = false, bool WORLD = false, bool CL = false, bool FPN = false>
+//
+// RG (watched regions, pocs_set_regions; the kernels k_gmm_step_regions, k_gmm_step_risk_regions: ticket form, never LONE, TREE, OC,
+// WORLD, CL or FPN): the head also stages the regions' records and footprints (the head of pocs_regions_dev) with its other requests;
+// waves 2 and 3 decide per run buffer which regions the run's mixture can reach (gmm_cull_regions) beside waves 0 and 1; the body
+// counts per kept region the collision-free samples in it (gmm_units); behind the units the nonzero counters leave with one integer
+// atomic each to reg_counts[run][waypoint][region], as clc does.  The collision test, the moment sums, the tickets and the closers
+// are what they are.  LDS: + 432 B (K = 8: 75 856 B against the twin's 75 424): two blocks per CU in every instantiation.
+template <int K, bool STORE, int TB, bool LONE, bool RISK, bool TREE = false, bool OC = false, bool WORLD = false, bool CL = false, bool FPN = false,
+          bool RG = false>
 __device__ __forceinline__ void gmm_step_block(const pocs_gmm_launch a) {      // (by value, as a kernel holds its argument)
-  typedef gmm_smem<K, TB, OC, CL, FPN> smem_t;
+  typedef gmm_smem<K, TB, OC, CL, FPN, RG> smem_t;
+  static_assert(!(RG && (LONE || TREE || OC || WORLD || CL || FPN)), "watched regions: the ticket form of a batch or of plans on a small world, no other counts");
+  static_assert(!RG || TB >= 256, "waves 2 and 3 decide the regions in reach");
   static_assert(!(FPN && (LONE || TREE || OC || WORLD || CL)), "a compound footprint: the ticket form of a batch or of plans on a small world, no counts per box or level");
   static_assert(!(CL && (LONE || TREE || OC || WORLD)), "clearance levels: the ticket form of a batch or of plans on a small world, no per-box counts");
   static_assert(!(WORLD && (LONE || TREE || OC)), "a large world: the ticket form of a batch or of plans, no per-box counts");
@@ -844,6 +908,8 @@ __device__ __forceinline__ void gmm_step_block(const pocs_gmm_launch a) {      /
     obs2_elem = tid < a.M * POCS_OBS_STRIDE ? a.clr->obs[tid] : 0.0;
     clh_elem = tid < 6 + POCS_MAX_CLEARANCE_LEVELS ? reinterpret_cast<const double*>(a.clr)[tid] : 0.0;
   }
+  [[maybe_unused]] double rgh_elem = 0.0;                       // RG: the regions' records and footprints
+  if constexpr (RG) rgh_elem = tid < POCS_REGIONS_HEAD ? reinterpret_cast<const double*>(a.regions)[tid] : 0.0;
   if (LONE && w > 0) {
     // close waypoint w - 1 and advance to w, here (r0 is the call's one run)
     const bool out = blockIdx.x == 0;
@@ -942,6 +1008,7 @@ __device__ __forceinline__ void gmm_step_block(const pocs_gmm_launch a) {      /
       if (tid < a.M * POCS_OBS_STRIDE) sm.obs()[tid] = obs_elem;
       if constexpr (CL) { if (tid < a.M * POCS_OBS_STRIDE) sm.obs2()[tid] = obs2_elem; if (tid < 6 + POCS_MAX_CLEARANCE_LEVELS) sm.clh[tid] = clh_elem; }
       if constexpr (FPN) { if (tid < POCS_MAX_FOOTPRINT_PARTS * POCS_PART_STRIDE) sm.fpp[tid] = fpp_elem; }
+      if constexpr (RG) { if (tid < POCS_REGIONS_HEAD) sm.rgh[tid] = rgh_elem; }
       if (tid < (r1_all - r0_all + 1) * PS && rp >= shift && rp - shift <= r1 - r0) sm.par[rp - shift][jp] = parv;
       for (int j = tid; j < 2 * NW * K; j += TB) (&sm.xj[0][0][0])[j] = -1;
       if (tid <= r1_all - r0_all && tid >= shift && tid - shift <= r1 - r0) sm.seed[tid - shift] = seedv;
@@ -952,6 +1019,7 @@ __device__ __forceinline__ void gmm_step_block(const pocs_gmm_launch a) {      /
     if (tid < a.M * POCS_OBS_STRIDE) sm.obs()[tid] = obs_elem;
     if constexpr (CL) { if (tid < a.M * POCS_OBS_STRIDE) sm.obs2()[tid] = obs2_elem; if (tid < 6 + POCS_MAX_CLEARANCE_LEVELS) sm.clh[tid] = clh_elem; }
       if constexpr (FPN) { if (tid < POCS_MAX_FOOTPRINT_PARTS * POCS_PART_STRIDE) sm.fpp[tid] = fpp_elem; }
+    if constexpr (RG) { if (tid < POCS_REGIONS_HEAD) sm.rgh[tid] = rgh_elem; }
     if (tid < (r1 - r0 + 1) * PS) sm.par[rp][jp] = parv;
     for (int j = tid; j < 2 * NW * K; j += TB) (&sm.xj[0][0][0])[j] = -1;
     if (tid <= r1 - r0) sm.seed[tid] = seedv;
@@ -964,6 +1032,10 @@ __device__ __forceinline__ void gmm_step_block(const pocs_gmm_launch a) {      /
     if constexpr (CL) {
       if (tid >= 128 && tid < 192) gmm_cull_clear(a, sm, 0, tid - 128, sm.par[0]);
       else if (tid >= 192 && tid < 256 && r1 > r0) gmm_cull_clear(a, sm, 1, tid - 192, sm.par[1]);
+    }
+    if constexpr (RG) {
+      if (tid >= 128 && tid < 192) gmm_cull_regions(a, sm, 0, tid - 128, sm.par[0]);
+      else if (tid >= 192 && tid < 256 && r1 > r0) gmm_cull_regions(a, sm, 1, tid - 192, sm.par[1]);
     }
     if constexpr (FPN) {
       if (tid < 64) gmm_cull_parts(a, sm, 0, tid, sm.par[0]);
@@ -978,7 +1050,7 @@ __device__ __forceinline__ void gmm_step_block(const pocs_gmm_launch a) {      /
   POCS_STAMP(0);
   for (int ta = t0; ta < t1; ta += SUB) {
     const int tb = (ta + SUB < t1) ? ta + SUB : t1;
-    gmm_units<K, STORE, TB, LONE, OC, CL, FPN>(a, sm, w, r0, ta, tb, s_zpre, ta == t0 ? npre : 0);
+    gmm_units<K, STORE, TB, LONE, OC, CL, FPN, RG>(a, sm, w, r0, ta, tb, s_zpre, ta == t0 ? npre : 0);
     POCS_STAMP(1);
     __syncthreads();
     POCS_STAMP(2);
@@ -1005,6 +1077,15 @@ __device__ __forceinline__ void gmm_step_block(const pocs_gmm_launch a) {      /
     if (tid < 8 && rb <= r1 - r0 && l < a.clr_L) {
       const unsigned n = sm.clc[rb][l];
       if (n) atomicAdd(&a.clr_counts[((size_t)(r0 + rb) * a.W + wr) * POCS_MAX_CLEARANCE_LEVELS + l], (unsigned long long)n);
+    }
+  }
+  if constexpr (RG) {
+    // (as clc above: every wave's LDS additions lie in front of the barrier behind the last gmm_units)
+    const int rb = tid >> 2, g = tid & 3;
+    static_assert(POCS_MAX_REGIONS == 4, "thread 4 rb + g");
+    if (tid < 8 && rb <= r1 - r0 && g < a.reg_G) {
+      const unsigned n = sm.rgc[rb][g];
+      if (n) atomicAdd(&a.reg_counts[((size_t)(r0 + rb) * a.W + wr) * POCS_MAX_REGIONS + g], (unsigned long long)n);
     }
   }
   if (LONE) return;                                  // the rows leave through the kernel boundary; the next launch's heads add them
@@ -1140,6 +1221,16 @@ __global__ __launch_bounds__(TB, POCS_GMM_BLOCKS_PER_CU * TB / 256) void k_gmm_s
 template <int K, bool STORE, int TB>
 __global__ __launch_bounds__(TB, POCS_GMM_BLOCKS_PER_CU * TB / 256) void k_gmm_step_risk_parts(pocs_gmm_launch a) {
   gmm_step_block<K, STORE, TB, false, true, false, false, false, false, true>(a);
+}
+
+// The forms that count watched regions (RG above): kernels of their own names again.
+template <int K, bool STORE, int TB>
+__global__ __launch_bounds__(TB, POCS_GMM_BLOCKS_PER_CU * TB / 256) void k_gmm_step_regions(pocs_gmm_launch a) {
+  gmm_step_block<K, STORE, TB, false, false, false, false, false, false, false, true>(a);
+}
+template <int K, bool STORE, int TB>
+__global__ __launch_bounds__(TB, POCS_GMM_BLOCKS_PER_CU * TB / 256) void k_gmm_step_risk_regions(pocs_gmm_launch a) {
+  gmm_step_block<K, STORE, TB, false, true, false, false, false, false, false, true>(a);
 }
 
 // The forms under a large collision world (WORLD above): kernels of their own names again.

@@ -124,7 +124,14 @@ __device__ __forceinline__ mc_run_start mc_start(const pocs_mc_launch& a) {
 // MC_PARTS (pocs_set_footprint_parts with F > 1), a flag on top of MC_PLAIN, MC_COUNTS or MC_STOP, on k_mc_init and the per-step
 // kernel: the collision test is pocs_pose_collides_parts over the parts staged beside the world's records (which are prepared for
 // the largest part); the hit counters and the counts are formed from that flag as they are from the single footprint's.
-enum { MC_PLAIN = 0, MC_COUNTS = 1, MC_STOP = 2, MC_BOXES = 4, MC_CLEAR = 8, MC_PARTS = 16 };
+//
+// MC_REGIONS (pocs_set_regions), a flag on top of MC_PLAIN, MC_COUNTS or MC_STOP, on k_mc_init and the per-step kernel, never with
+// MC_BOXES, MC_CLEAR or MC_PARTS: reg_counts[run][w][g] also counts the particles that have collided at no waypoint <= w and are in
+// region g at w (pocs_pose_regions_mask on the regions staged beside the world's records).  No per-particle state: "never
+// collided" is the hit counter the kernel holds anyway -- !hit in k_mc_init, old == 0 && !hit in the per-step kernel, which reads the
+// counter of a particle that does not collide only when the particle is in some region.  The collision test, the hit counters
+// and the other counts are what they are without the flag.
+enum { MC_PLAIN = 0, MC_COUNTS = 1, MC_STOP = 2, MC_BOXES = 4, MC_CLEAR = 8, MC_PARTS = 16, MC_REGIONS = 32 };
 static_assert(POCS_MAX_OBSTACLES <= 64, "a particle's touched boxes are a 64-bit mask");
 
 // pocs_pose_collides with the touched boxes as a mask (the flag: mask != 0, as the plain form's).
@@ -226,6 +233,33 @@ __device__ __forceinline__ void mc_wave_level_hits(int now, int before, int L, u
   for (int l = 0; l < L; ++l) {
     const unsigned long long b = __ballot(now <= l && l < before);
     if (b != 0ull && (threadIdx.x & 63) == (unsigned)__builtin_ctzll(b)) atomicAdd(&dst[l], (unsigned long long)__popcll(b));
+  }
+}
+
+// MC_REGIONS: the regions' records and footprints in LDS, staged in front of the head's barrier.
+struct mc_regions {
+  const double* rec;               // LDS: G x POCS_OBS_STRIDE
+  const double* fp;                // LDS: G x 4
+  int G;
+};
+__device__ __forceinline__ mc_regions stage_mc_regions(const pocs_mc_launch& a) {
+  __shared__ double s_reg[POCS_REGIONS_HEAD];
+  static_assert(POCS_REGIONS_HEAD <= POCS_BLOCK && offsetof(pocs_regions_dev, fp) == POCS_MAX_REGIONS * POCS_OBS_STRIDE * sizeof(double),
+                "one double of rec | fp per thread");
+  const int tid = threadIdx.x;
+  const double v = tid < POCS_REGIONS_HEAD ? reinterpret_cast<const double*>(a.regions)[tid] : 0.0;
+  requests_issued();
+  if (tid < POCS_REGIONS_HEAD) s_reg[tid] = v;
+  return {s_reg, s_reg + POCS_MAX_REGIONS * POCS_OBS_STRIDE, a.reg_G};
+}
+// The lanes of a wave that are in the particle loop together, each with the regions its never-collided particle is in (0: none,
+// or collided): per region one ballot, and the first lane of the ballot adds the population count to the region's counter of
+// (run, waypoint), as mc_wave_level_hits does.  No such particle in the wave: one ballot and a scalar branch.
+__device__ __forceinline__ void mc_wave_region_hits(unsigned in, int G, unsigned long long* dst) {
+  if (__ballot(in != 0u) == 0ull) return;
+  for (int g = 0; g < G; ++g) {
+    const unsigned long long b = __ballot(((in >> g) & 1u) != 0u);
+    if (b != 0ull && (threadIdx.x & 63) == (unsigned)__builtin_ctzll(b)) atomicAdd(&dst[g], (unsigned long long)__popcll(b));
   }
 }
 
@@ -380,6 +414,8 @@ __global__ __launch_bounds__(POCS_BLOCK) void k_mc_init(pocs_mc_launch a) {
   if constexpr ((MODE & MC_CLEAR) != 0) cl = stage_mc_clear(a);              // (in front of the head's barrier)
   mc_parts pt = {nullptr, 0};
   if constexpr ((MODE & MC_PARTS) != 0) pt = stage_mc_parts(a);              // (in front of the head's barrier)
+  mc_regions rg = {nullptr, nullptr, 0};
+  if constexpr ((MODE & MC_REGIONS) != 0) rg = stage_mc_regions(a);          // (in front of the head's barrier)
   const mc_head hd = stage_mc_head(a.env, a.tables);
   const mc_run_view v = mc_view(a);
   const mc_world wd = hd.world();
@@ -406,6 +442,10 @@ __global__ __launch_bounds__(POCS_BLOCK) void k_mc_init(pocs_mc_launch a) {
       const int lv = pocs_pose_clearance_level(x, y, t, &wd.fp, cl.d, cl.L, cl.obs, wd.M, wd.tab);
       a.clr_level[(size_t)blockIdx.y * (size_t)a.stride + (size_t)i] = (unsigned char)lv;
       mc_wave_level_hits(lv, cl.L, cl.L, a.clr_counts + (size_t)blockIdx.y * (size_t)a.W * POCS_MAX_CLEARANCE_LEVELS);
+    }
+    if constexpr ((MODE & MC_REGIONS) != 0) {
+      const unsigned in = h != 0u ? 0u : pocs_pose_regions_mask(x, y, t, rg.rec, rg.fp, rg.G, wd.tab);
+      mc_wave_region_hits(in, rg.G, a.reg_counts + (size_t)blockIdx.y * (size_t)a.W * POCS_MAX_REGIONS);
     }
   }
   if ((MODE & 3) != MC_PLAIN) mc_block_add(first, a.wp_counts + (size_t)blockIdx.y * (size_t)a.W);      // waypoint 0
@@ -458,6 +498,8 @@ __device__ __forceinline__ void mc_step_body(const pocs_mc_launch& a) {
   if constexpr ((MODE & MC_CLEAR) != 0) cl = stage_mc_clear(a);              // (in front of the head's barrier)
   mc_parts pt = {nullptr, 0};
   if constexpr ((MODE & MC_PARTS) != 0) pt = stage_mc_parts(a);              // (in front of the head's barrier)
+  mc_regions rg = {nullptr, nullptr, 0};
+  if constexpr ((MODE & MC_REGIONS) != 0) rg = stage_mc_regions(a);          // (in front of the head's barrier)
   const mc_head hd = stage_mc_head(a.env, a.tables);
   const mc_run_view v = mc_view(a);
   const mc_world wd = hd.world();
@@ -486,6 +528,17 @@ __device__ __forceinline__ void mc_step_body(const pocs_mc_launch& a) {
         v.hits[i] = old + 1u;
         first += old == 0u ? 1u : 0u;
       }
+    } else if constexpr ((MODE & MC_REGIONS) != 0) {
+      unsigned in = 0u;
+      if (pocs_pose_collides(nx, ny, nt, &wd.fp, wd.obs, wd.M, wd.tab)) {
+        const uint32_t old = v.hits[i];
+        v.hits[i] = old + 1u;
+        first += old == 0u ? 1u : 0u;
+      } else {
+        in = pocs_pose_regions_mask(nx, ny, nt, rg.rec, rg.fp, rg.G, wd.tab);
+        if (in != 0u && v.hits[i] != 0u) in = 0u;      // (in a region, but collided at an earlier waypoint)
+      }
+      mc_wave_region_hits(in, rg.G, a.reg_counts + ((size_t)blockIdx.y * (size_t)a.W + (size_t)a.step + 1) * POCS_MAX_REGIONS);
     } else {
     if (pocs_pose_collides(nx, ny, nt, &wd.fp, wd.obs, wd.M, wd.tab)) {
       const uint32_t old = v.hits[i];                // the counter is in hand exactly when the particle collides

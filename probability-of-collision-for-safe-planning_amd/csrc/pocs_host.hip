@@ -109,6 +109,30 @@ bool clearance_applied(const pocs_ctx* c) {
   return c->clr_L > 0 && !parts_applied(c) && !in_mode(c, kTree | kLargeWorld | kObsCounts | kShard | kMoments);
 }
 
+// Watched regions: the record the kernels read (pocs_regions_dev) -- region g prepared as upload_world prepares an obstacle, for
+// the region's own footprint: the robot's (POCS_REGION_TOUCH) or the point {0, 0, 0, 0} (POCS_REGION_POINT).
+// (pocs_probe_device_regions prepares its own record through this function too.)
+void prepare_regions(const pocs_footprint& fp, const double* boxes, const int* kinds, int G, pocs_regions_dev* out) {
+  memset(out, 0, sizeof *out);
+  for (int g = 0; g < G; ++g) {
+    const pocs_footprint f = kinds[g] == POCS_REGION_POINT ? pocs_footprint{0.0, 0.0, 0.0, 0.0} : fp;
+    out->kind[g] = kinds[g];
+    out->fp[4 * g] = f.dx; out->fp[4 * g + 1] = f.dy; out->fp[4 * g + 2] = f.hx; out->fp[4 * g + 3] = f.hy;
+    out->fp_rr[g] = sqrt(f.hx * f.hx + f.hy * f.hy);
+    out->fp_phi[g] = atan2(f.hy, f.hx);
+    pocs_prepare_obstacle(boxes + (size_t)g * 5, &f, &out->rec[(size_t)g * POCS_OBS_STRIDE]);
+  }
+}
+
+// Where the regions are applied -- the ONE place that says so: whole calls on one GPU over a small world, static or scheduled --
+// single runs, batches in both sub-batch forms, run-ahead, calls of plans with and without the risk bounds, GMM and MC.  A tree of
+// plans, a large world, per-box counts, a shard (and with it the exchange and a bound moments buffer), a compound footprint and clearance levels with
+// L > 0 are the calls they are with G = 0; the step API never asks.
+bool regions_applied(const pocs_ctx* c) {
+  using namespace pocs_modes;
+  return c->reg_G > 0 && c->clr_L == 0 && !parts_applied(c) && !in_mode(c, kTree | kLargeWorld | kObsCounts | kShard | kMoments);
+}
+
 int upload_world(pocs_ctx* c) {                // tables + the collision world: one record (obstacle records, footprint) per step of the schedule
   if (int r = upload_tables(c)) return r;
   if (c->env_dirty) {
@@ -139,6 +163,12 @@ int upload_world(pocs_ctx* c) {                // tables + the collision world: 
       for (size_t s = 0; s < S; ++s) prepare_clearance(c->fp, c->clr_d, c->clr_L, c->boxes.data() + s * (size_t)M * 5, M, &clr[s]);
       if (int r = ensure(c, c->d_clr, S * sizeof(pocs_clear_dev))) return r;
       HIPCHK(c, hipMemcpy(c->d_clr.p, clr.data(), S * sizeof(pocs_clear_dev), hipMemcpyHostToDevice));
+    }
+    if (c->reg_G > 0 && !parts_applied(c)) {         // the watched regions, next to the world: TOUCH regions follow the footprint
+      pocs_regions_dev reg;
+      prepare_regions(c->fp, c->reg_box, c->reg_kind, c->reg_G, &reg);
+      if (int r = ensure(c, c->d_reg, sizeof reg)) return r;
+      HIPCHK(c, hipMemcpy(c->d_reg.p, &reg, sizeof reg, hipMemcpyHostToDevice));
     }
     if (large_world(c)) {                            // the large world's records (the env record above then holds the footprint and M = 0)
       const size_t LM = (size_t)large_boxes(c);
@@ -322,6 +352,29 @@ int read_clearance(pocs_ctx* c, Kind kind, long long n) {
   return POCS_OK;
 }
 
+// Watched regions: d_regct holds [batch][W][POCS_MAX_REGIONS] u64, zeroed by the first launch of every call they are applied to (a
+// kernel, inside the replayed graph, as d_clrct) and read back behind the call (read_regions).  Not applied: no buffer, no launch,
+// and every launch is the kernel it is with G = 0.
+size_t region_count_words(const pocs_ctx* c) { return (size_t)c->batch * (size_t)(c->W > 0 ? c->W : 1) * POCS_MAX_REGIONS; }
+int ensure_regions(pocs_ctx* c) {
+  return regions_applied(c) ? ensure(c, c->d_regct, region_count_words(c) * sizeof(unsigned long long)) : POCS_OK;
+}
+// the state a call leaves for pocs_get_region_counts while it runs (or fails) ...
+void open_regions(pocs_ctx* c) {
+  Results& r = c->res;
+  r.rg_state = c->reg_G == 0 ? Results::RgOff : Results::RgNotApplied;
+  r.rg_kind = Kind::None; r.rg_G = 0; r.rg_W = 0; r.rg_N = 0; r.rg_counts.clear();
+}
+// ... and behind its results: the table in slot order, as the device holds it (the stream is idle)
+int read_regions(pocs_ctx* c, Kind kind, long long n) {
+  if (!regions_applied(c)) return POCS_OK;
+  Results& r = c->res;
+  r.rg_counts.assign(region_count_words(c), 0ull);
+  HIPCHK(c, hipMemcpy(r.rg_counts.data(), c->d_regct.p, r.rg_counts.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+  r.rg_state = Results::RgServed; r.rg_kind = kind; r.rg_G = c->reg_G; r.rg_W = c->W > 0 ? c->W : 1; r.rg_N = n;
+  return POCS_OK;
+}
+
 // The call's synchronisation words (SyncLayout, pocs_ctx.hpp); the copy behind the launches starts at the give-up word and,
 // under a risk bound, runs on through the pad and the stop words.
 SyncLayout sync_layout(const pocs_ctx* c) {
@@ -366,6 +419,7 @@ int gmm_prepare(pocs_ctx* c) {
     if (int r = upload_tree(c)) return r;
   if (int r = ensure_obs_counts(c)) return r;
   if (int r = ensure_clearance(c)) return r;
+  if (int r = ensure_regions(c)) return r;
   if (large_world(c)) {
     if (int r = ensure(c, c->d_kept, R * POCS_MAX_OBSTACLES * POCS_OBS_STRIDE * sizeof(double))) return r;
     if (int r = ensure(c, c->d_keptidx, R * POCS_MAX_OBSTACLES * sizeof(int))) return r;
@@ -499,9 +553,9 @@ int enqueue_advance(Issuer is, int w) {
 // keeps the ticket-and-closer form; the results are the same bits.
 // (Under a large world the cull of waypoint w reads param[w] ahead of the sampling launch; the lone form builds param[w] in its own
 // heads, so a call of one run takes the ticket form there: the same bits.)
-// (Under clearance levels too: the counting form exists as the ticket form only.)
+// (Under clearance levels and watched regions too: the counting forms exist as the ticket form only.)
 // (And under a compound footprint: the parts form exists as the ticket form only.)
-bool lone_call(const pocs_ctx* c) { return c->opt_lone && !large_world(c) && !clearance_applied(c) && !parts_applied(c) && c->batch == 1 && !c->tree.n && !c->ext_moments && !(c->xchg_connected && c->shard_first >= 0) && !risk_active(c); }
+bool lone_call(const pocs_ctx* c) { return c->opt_lone && !large_world(c) && !clearance_applied(c) && !regions_applied(c) && !parts_applied(c) && c->batch == 1 && !c->tree.n && !c->ext_moments && !(c->xchg_connected && c->shard_first >= 0) && !risk_active(c); }
 void set_risk(pocs_ctx* c, pocs_gmm_launch* a) {      // under a risk bound the launch is k_gmm_step_risk (whole calls of plans or on a tree only)
   a->risk = 1;
   a->stop = a->sync + c->sync.stop;
@@ -600,6 +654,7 @@ int enqueue_gmm_all(Issuer is, long long first, long long count, bool prof) {
   const int W = c->W, R = c->batch, G = gmm_groups(c);
   if (int r = enqueue_obs_counts_reset(is)) return r;    // (ahead of the fork: every sub-batch's launches lie behind it)
   if (int r = enqueue_clearance_reset(is)) return r;
+  if (regions_applied(c)) if (int r = is.launch(pocs_launch_zero_counts, 0, (unsigned long long*)c->d_regct.p, region_count_words(c))) return r;
   if (int r = enqueue_advance(is, 0)) return r;
   if (prof) if (int r = is.mark(c->ev_seq[0])) return r;
   for (int g = 1; g < G; ++g) if (int r = is.order(0, g, c->ev_fork, g == 1)) return r;
@@ -608,6 +663,9 @@ int enqueue_gmm_all(Issuer is, long long first, long long count, bool prof) {
   if (parts_applied(c)) { base.parts = (const pocs_parts_dev*)c->d_parts.p; base.parts_F = c->fp_F; }
   if (clearance_applied(c)) {                        // (the whole call only: the step API's launches never carry the levels)
     base.clr = clear_at(c, 0); base.clr_counts = (unsigned long long*)c->d_clrct.p; base.clr_L = c->clr_L;
+  }
+  if (regions_applied(c)) {                          // (the whole call only, as the levels)
+    base.regions = (const pocs_regions_dev*)c->d_reg.p; base.reg_counts = (unsigned long long*)c->d_regct.p; base.reg_G = c->reg_G;
   }
   StepLaunch s;
   s.groups = G; s.advance = true; s.lone = lone_call(c); s.risk = risk_active(c);
@@ -821,6 +879,7 @@ int run_gmm_full(pocs_ctx* c, double* probability) {
 #endif
   c->res.oc_kind = Kind::None;                                  // (the per-obstacle table is rewritten from here on; noted again behind the combine)
   open_clearance(c);
+  open_regions(c);
   c->reach.clear(); c->reach_len.clear(); c->reach_R = 0; c->reach_W = 0;      // (pocs_get_world_reach covers the last GMM call)
   if (int r = gmm_prepare(c)) return r;
   long long first, count;
@@ -860,6 +919,7 @@ int run_gmm_full(pocs_ctx* c, double* probability) {
   if (int r = gmm_combine(c, (double*)c->h_pin + pin_layout(c).moments, probability, stop)) { reset_results(c); return r; }
   note_obs_counts(c, Kind::Gmm);
   if (int r = read_clearance(c, Kind::Gmm, c->num_gmm)) return r;
+  if (int r = read_regions(c, Kind::Gmm, c->num_gmm)) return r;
   c->res.last_gmm_count = count;
   c->res.last_gmm_wp = c->W - 1;
   lap("combined");
@@ -886,7 +946,8 @@ bool mc_counts_active(const pocs_ctx* c) { return c->opt_mc_wp || c->opt_obs_cou
 // takes the per-step form.
 // So does a call that counts clearance levels: the levels live in the per-step kernels (MC_CLEAR).
 // And a call under a compound footprint: the parts live in the per-step kernels too (MC_PARTS).
-bool mc_fused_form(const pocs_ctx* c) { return c->opt_fused && !mc_stop_active(c) && !clearance_applied(c) && !parts_applied(c); }
+// And a call that counts watched regions: they live in the per-step kernels as well (MC_REGIONS).
+bool mc_fused_form(const pocs_ctx* c) { return c->opt_fused && !mc_stop_active(c) && !clearance_applied(c) && !parts_applied(c) && !regions_applied(c); }
 // d_total, u64 words: [R] collided particles per run | counts active: [R][W] first collisions | [R] u32 stop words
 size_t mc_total_words(const pocs_ctx* c) {
   const size_t R = (size_t)c->batch, W = (size_t)c->W;
@@ -937,6 +998,10 @@ int enqueue_mc_all(Issuer is, long long first, long long count, bool prof) {
   if (clearance_applied(c)) {
     a.clr = clear_at(c, 0); a.clr_counts = (unsigned long long*)c->d_clrct.p; a.clr_level = (unsigned char*)c->d_clrlv.p; a.clr_L = c->clr_L;
     if (int r = enqueue_clearance_reset(is)) return r;
+  }
+  if (regions_applied(c)) {
+    a.regions = (const pocs_regions_dev*)c->d_reg.p; a.reg_counts = (unsigned long long*)c->d_regct.p; a.reg_G = c->reg_G;
+    if (int r = is.launch(pocs_launch_zero_counts, 0, a.reg_counts, region_count_words(c))) return r;
   }
   if (c->plans.n) {
     a.run_plan = (const double*)c->d_runplan.p;      // every run its own start mean and steps
@@ -1074,6 +1139,7 @@ int mc_prepare(pocs_ctx* c, size_t runs, size_t chain_rows, size_t elems, size_t
   if (int r = ensure_obs_counts(c)) return r;
   if (int r = ensure_clearance(c)) return r;
   if (clearance_applied(c)) if (int r = ensure(c, c->d_clrlv, elems)) return r;
+  if (int r = ensure_regions(c)) return r;
   if (int r = ensure_pin(c)) return r;
   return stage_and_upload_runs(c, 1, Kind::Mc);
 }
@@ -1131,6 +1197,7 @@ int run_mc_tree(pocs_ctx* c) {                      // (behind run_mc_local's ch
 int run_mc_local(pocs_ctx* c) {
   c->res.oc_kind = Kind::None;
   open_clearance(c);
+  open_regions(c);
   if (int r = check_common(c)) return r;
   if (c->num_particles < 1) return fail(c, POCS_E_STATE, "setNumParticles missing");
   if (int r = upload_static(c)) return r;
@@ -1165,7 +1232,8 @@ int run_mc_local(pocs_ctx* c) {
   if (mc_counts_active(c))
     if (int r = mc_read_waypoint_counts(c, tot)) { reset_results(c); return r; }
   note_obs_counts(c, Kind::Mc);
-  return read_clearance(c, Kind::Mc, count);
+  if (int r = read_clearance(c, Kind::Mc, count)) return r;
+  return read_regions(c, Kind::Mc, count);
 }
 
 }  // namespace pocs_rt
@@ -1203,6 +1271,7 @@ int pocs_gmm_begin(pocs_ctx* c) {
   if (int r = enqueue_obs_counts_reset({c, nullptr})) return r;
   c->res.oc_kind = Kind::None;                                 // (the table is this sequence's from here on; served once pocs_gmm_end has closed it)
   open_clearance(c);                                           // (the step API: the levels are not applied)
+  open_regions(c);                                             // (nor the watched regions)
   c->xchg_calls += 1;
   c->gmm_open = true;
   c->res.last_gmm_wp = -1;

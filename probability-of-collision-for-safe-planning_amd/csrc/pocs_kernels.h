@@ -67,6 +67,17 @@ struct pocs_parts_dev {
   double part[POCS_MAX_FOOTPRINT_PARTS * POCS_PART_STRIDE];   // per part dx dy hx hy, bounding radius, corner angle (pocs_prepare_part)
 };
 
+// Watched regions (pocs_set_regions) as the kernels see them, in HBM beside the collision world: ONE record, the regions are
+// static.  The boxes and everything derived from them live HERE, not in launch arguments: a call's launches carry the address
+// and G, so other boxes with the same G and kinds replay the cached graph.
+struct pocs_regions_dev {
+  double rec[POCS_MAX_REGIONS * POCS_OBS_STRIDE];   // region g prepared (pocs_prepare_obstacle) for ITS footprint
+  double fp[POCS_MAX_REGIONS * 4];                  // that footprint, dx dy hx hy: the robot's (TOUCH) or {0, 0, 0, 0} (POINT)
+  double fp_rr[POCS_MAX_REGIONS], fp_phi[POCS_MAX_REGIONS];   // its bounding radius and corner angle (pocs_footprint_extent_pre)
+  int kind[POCS_MAX_REGIONS];
+};
+#define POCS_REGIONS_HEAD (POCS_MAX_REGIONS * (POCS_OBS_STRIDE + 4))   // the doubles a kernel's head stages: rec | fp
+
 struct pocs_run_header {         // per-run scalars read by every kernel (so a captured graph stays valid)
   uint64_t seed;
   uint64_t pad;                  // sharded whole calls: the context's count of exchange sequences (pocs_gmm_launch::xchg_epoch_from_header)
@@ -173,6 +184,13 @@ struct pocs_gmm_launch {
   const pocs_parts_dev* parts;
   int parts_F;                   // 2 .. POCS_MAX_FOOTPRINT_PARTS
   int parts_pad;
+  // watched regions (pocs_set_regions; behind everything else again): non-null = the launch is the kernel's _regions form (ticket
+  // form, with or without the risk bound; never LONE, TREE, OC, WORLD, CL or parts), which also counts per region the samples drawn
+  // at (run, waypoint) whose collision flag is 0 and which are in the region
+  const pocs_regions_dev* regions;
+  unsigned long long* reg_counts; // [nruns][W][POCS_MAX_REGIONS]; zeroed by pocs_launch_zero_counts at the head of the call's launches
+  int reg_G;                     // 1 .. POCS_MAX_REGIONS
+  int reg_pad;
 };
 #define POCS_MAX_WORLD_RECORDS 4096   // = POCS_MAX_WORLD_BOXES (include/pocs.h; pocs_ctx.hpp checks)
 #define POCS_CULL_BLOCK 256           // k_world_cull
@@ -238,6 +256,13 @@ struct pocs_mc_launch {               // blockIdx.y = run of the batch, like poc
   const pocs_parts_dev* parts;
   int parts_F;
   int parts_pad;
+  // watched regions (pocs_set_regions; behind everything else again): non-null = the MC_REGIONS forms of k_mc_init /
+  // k_mc_step_counts (per-step launches only; never with a large world, per-box counts, levels or parts), which also count per
+  // region the particles that have collided at no waypoint so far and are in the region at the launch's waypoint
+  const pocs_regions_dev* regions;
+  unsigned long long* reg_counts;      // [nruns][W][POCS_MAX_REGIONS]; zeroed inside the graph like obs_counts
+  int reg_G;                           // 1 .. POCS_MAX_REGIONS
+  int reg_pad;
 };
 
 
@@ -264,6 +289,10 @@ hipError_t pocs_launch_probe_clearance(const pocs_env_dev* env, const pocs_clear
 // the single-pose form).  env: records of M boxes prepared for the covering part; parts: F parts
 hipError_t pocs_launch_probe_parts(const pocs_env_dev* env, const pocs_parts_dev* parts, int F, const pocs_tables* tables, int n,
                                    const double* x, const double* y, const double* th, int* touched_out, hipStream_t s);
+// one block; poses n x (x, y, th) by component; mask_out[i]: bit g = pose i is in region g by the single-pose form (bit 8 + g should
+// the pair form ever disagree with it)
+hipError_t pocs_launch_probe_regions(const pocs_regions_dev* regions, int G, const pocs_tables* tables, int n,
+                                     const double* x, const double* y, const double* th, int* mask_out, hipStream_t s);
 hipError_t pocs_launch_mc_init(int nblk, const pocs_mc_launch& a, hipStream_t s);
 hipError_t pocs_launch_mc_step(int nblk, const pocs_mc_launch& a, hipStream_t s);
 hipError_t pocs_launch_mc_fused(int nblk, const pocs_mc_launch& a, hipStream_t s);

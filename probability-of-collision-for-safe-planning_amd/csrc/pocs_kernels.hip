@@ -66,6 +66,18 @@ hipError_t pocs_launch_gmm_step(int K, const pocs_gmm_launch& a, hipStream_t s) 
         else         hipLaunchKernelGGL((k_gmm_step_parts<KK, false, TB>), dim3(a.blocks), dim3(TB), 0, s, a);
       }
     } else
+    if (a.regions) {                                   // watched regions: the ticket forms that also count per region
+      if (a.lone || a.obs_counts || a.world || a.tree_parent || a.exchange_in_tail || a.clr || !a.reg_counts || a.reg_G < 1 || a.reg_G > POCS_MAX_REGIONS ||
+          a.M > POCS_MAX_OBSTACLES || (a.risk && (!a.stop || !a.surv)))
+        return hipErrorInvalidValue;
+      if (a.risk) {
+        if (a.store) hipLaunchKernelGGL((k_gmm_step_risk_regions<KK, true, TB>), dim3(a.blocks), dim3(TB), 0, s, a);
+        else         hipLaunchKernelGGL((k_gmm_step_risk_regions<KK, false, TB>), dim3(a.blocks), dim3(TB), 0, s, a);
+      } else {
+        if (a.store) hipLaunchKernelGGL((k_gmm_step_regions<KK, true, TB>), dim3(a.blocks), dim3(TB), 0, s, a);
+        else         hipLaunchKernelGGL((k_gmm_step_regions<KK, false, TB>), dim3(a.blocks), dim3(TB), 0, s, a);
+      }
+    } else
     if (a.clr) {                                       // clearance levels: the ticket forms that also count per level
       if (a.lone || a.obs_counts || a.world || a.tree_parent || a.exchange_in_tail || !a.clr_counts || a.clr_L < 1 || a.clr_L > POCS_MAX_CLEARANCE_LEVELS ||
           a.M > POCS_MAX_OBSTACLES || (a.risk && (!a.stop || !a.surv)))
@@ -192,6 +204,11 @@ hipError_t pocs_launch_mc_init(int nblk, const pocs_mc_launch& a, hipStream_t s)
     if (a.wp_mode) hipLaunchKernelGGL(k_mc_init<MC_COUNTS | MC_PARTS>, dim3(nblk, a.nruns), dim3(POCS_BLOCK), 0, s, a);
     else           hipLaunchKernelGGL(k_mc_init<MC_PLAIN | MC_PARTS>, dim3(nblk, a.nruns), dim3(POCS_BLOCK), 0, s, a);
   } else
+  if (a.regions) {                                    // watched regions: the MC_REGIONS forms (a small world, no per-box counts, levels or parts)
+    if (a.world || a.obs_counts || a.clr || !a.reg_counts || a.reg_G < 1 || a.reg_G > POCS_MAX_REGIONS) return hipErrorInvalidValue;
+    if (a.wp_mode) hipLaunchKernelGGL(k_mc_init<MC_COUNTS | MC_REGIONS>, dim3(nblk, a.nruns), dim3(POCS_BLOCK), 0, s, a);
+    else           hipLaunchKernelGGL(k_mc_init<MC_PLAIN | MC_REGIONS>, dim3(nblk, a.nruns), dim3(POCS_BLOCK), 0, s, a);
+  } else
   if (a.clr) {                                        // clearance levels: the MC_CLEAR forms (a small world, no per-box counts)
     if (a.world || a.obs_counts || !a.clr_counts || !a.clr_level || a.clr_L < 1 || a.clr_L > POCS_MAX_CLEARANCE_LEVELS) return hipErrorInvalidValue;
     if (a.wp_mode) hipLaunchKernelGGL(k_mc_init<MC_COUNTS | MC_CLEAR>, dim3(nblk, a.nruns), dim3(POCS_BLOCK), 0, s, a);
@@ -223,6 +240,21 @@ hipError_t pocs_launch_mc_step(int nblk, const pocs_mc_launch& a, hipStream_t s)
     } else {
       if (a.nontemporal) hipLaunchKernelGGL((k_mc_step_counts<true, MC_PLAIN | MC_PARTS>), grid, block, 0, s, a);
       else               hipLaunchKernelGGL((k_mc_step_counts<false, MC_PLAIN | MC_PARTS>), grid, block, 0, s, a);
+    }
+  } else
+  if (a.regions) {                                    // watched regions: the MC_REGIONS forms of the three modes
+    if (a.world || a.obs_counts || a.clr || !a.reg_counts || a.reg_G < 1 || a.reg_G > POCS_MAX_REGIONS || a.step < 0 || a.step + 1 >= a.W ||
+        (a.wp_mode == 2 && (!a.wp_stop || a.wp_n < 1)))
+      return hipErrorInvalidValue;
+    if (a.wp_mode == 2) {
+      if (a.nontemporal) hipLaunchKernelGGL((k_mc_step_counts<true, MC_STOP | MC_REGIONS>), grid, block, 0, s, a);
+      else               hipLaunchKernelGGL((k_mc_step_counts<false, MC_STOP | MC_REGIONS>), grid, block, 0, s, a);
+    } else if (a.wp_mode == 1) {
+      if (a.nontemporal) hipLaunchKernelGGL((k_mc_step_counts<true, MC_COUNTS | MC_REGIONS>), grid, block, 0, s, a);
+      else               hipLaunchKernelGGL((k_mc_step_counts<false, MC_COUNTS | MC_REGIONS>), grid, block, 0, s, a);
+    } else {
+      if (a.nontemporal) hipLaunchKernelGGL((k_mc_step_counts<true, MC_PLAIN | MC_REGIONS>), grid, block, 0, s, a);
+      else               hipLaunchKernelGGL((k_mc_step_counts<false, MC_PLAIN | MC_REGIONS>), grid, block, 0, s, a);
     }
   } else
   if (a.clr) {                                        // clearance levels: the MC_CLEAR forms of the three modes
@@ -279,6 +311,7 @@ hipError_t pocs_launch_mc_fused(int nblk, const pocs_mc_launch& a, hipStream_t s
   if (a.wp_mode == 2 || (a.wp_mode != 0 && !a.wp_counts) || (a.obs_counts && !a.wp_mode)) return hipErrorInvalidValue;      // (no stop without a launch boundary per step)
   if (a.clr) return hipErrorInvalidValue;             // (clearance levels: the per-step form)
   if (a.parts) return hipErrorInvalidValue;           // (a compound footprint: the per-step form)
+  if (a.regions) return hipErrorInvalidValue;         // (watched regions: the per-step form)
   if (a.world) return hipErrorInvalidValue;           // (a large world is not staged: no fused form)
   if (a.obs_counts) {
     if (a.env_steps > 1) hipLaunchKernelGGL(k_mc_fused_sched<MC_COUNTS | MC_BOXES>, dim3(nblk, a.nruns), dim3(POCS_BLOCK), 0, s, a);
@@ -511,6 +544,47 @@ hipError_t pocs_launch_probe_parts(const pocs_env_dev* env, const pocs_parts_dev
                                    const double* x, const double* y, const double* th, int* touched_out, hipStream_t s) {
   if (!env || !parts || !tables || n < 1 || F < 1 || F > POCS_MAX_FOOTPRINT_PARTS || !x || !y || !th || !touched_out) return hipErrorInvalidValue;
   hipLaunchKernelGGL(k_probe_parts, dim3(1), dim3(POCS_BLOCK), 0, s, env, parts, F, tables, n, x, y, th, touched_out);
+  return hipGetLastError();
+}
+// Which watched regions poses are in, on poses and regions the caller picks (pocs_probe_device_regions: a test hook beside
+// k_probe_parts): ONE block stages the tables and the regions' records and footprints as the kernels' heads do and asks, per pose,
+// pocs_pose_regions_mask as the MC kernels call it, and pocs_pair_regions_masks, the sampling thread's pair form, pose 2 p with pose
+// 2 p + 1 (an odd last pose with itself) -- bit 8 + g is set in a pose's answer should the two forms ever disagree on region g.
+__global__ __launch_bounds__(POCS_BLOCK) void k_probe_regions(const pocs_regions_dev* __restrict__ regions, int G,
+                                                              const pocs_tables* __restrict__ tables, int n, const double* __restrict__ x,
+                                                              const double* __restrict__ y, const double* __restrict__ th, int* __restrict__ out) {
+  __shared__ pocs_tables s_tab;
+  __shared__ __attribute__((aligned(16))) double s_reg[POCS_REGIONS_HEAD];
+  stage_tables(tables, &s_tab);
+  if (threadIdx.x < POCS_REGIONS_HEAD) s_reg[threadIdx.x] = reinterpret_cast<const double*>(regions)[threadIdx.x];
+  __syncthreads();
+  const double* const s_rec = s_reg;
+  const double* const s_fp = s_reg + POCS_MAX_REGIONS * POCS_OBS_STRIDE;
+  POCS_VCONST(vc_);
+  const int npairs = (n + 1) / 2;
+  // (every lane of a wave makes every trip: the pair form ballots)
+  for (int p0 = (int)threadIdx.x - (int)(threadIdx.x & 63); p0 < npairs; p0 += POCS_BLOCK) {
+    const int p = p0 + (int)(threadIdx.x & 63);
+    const bool live = p < npairs;
+    const int i0 = live ? 2 * p : 0, i1 = live && i0 + 1 < n ? i0 + 1 : i0;
+    const double xs[2] = {x[i0], x[i1]}, ys[2] = {y[i0], y[i1]}, ts[2] = {th[i0], th[i1]};
+    unsigned single[2], pair[2] = {0u, 0u};
+#pragma unroll
+    for (int h = 0; h < 2; ++h) single[h] = pocs_pose_regions_mask(xs[h], ys[h], ts[h], s_rec, s_fp, G, &s_tab);
+    pocs_pair_regions_masks(xs, ys, ts, s_rec, s_fp, G, ~0u, &s_tab, &vc_, [&](const int g, const unsigned long long m0, const unsigned long long m1) {
+      if (__builtin_amdgcn_inverse_ballot_w64(m0)) pair[0] |= 1u << g;
+      if (__builtin_amdgcn_inverse_ballot_w64(m1)) pair[1] |= 1u << g;
+    });
+    if (live) {
+      out[i0] = (int)(single[0] | ((pair[0] ^ single[0]) << 8) | (i1 == i0 ? (single[1] ^ single[0]) << 8 : 0u));
+      if (i1 != i0) out[i1] = (int)(single[1] | ((pair[1] ^ single[1]) << 8));
+    }
+  }
+}
+hipError_t pocs_launch_probe_regions(const pocs_regions_dev* regions, int G, const pocs_tables* tables, int n,
+                                     const double* x, const double* y, const double* th, int* mask_out, hipStream_t s) {
+  if (!regions || !tables || n < 1 || G < 0 || G > POCS_MAX_REGIONS || !x || !y || !th || !mask_out) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(k_probe_regions, dim3(1), dim3(POCS_BLOCK), 0, s, regions, G, tables, n, x, y, th, mask_out);
   return hipGetLastError();
 }
 hipError_t pocs_launch_fill(void* dst, long long bytes, hipStream_t s) {

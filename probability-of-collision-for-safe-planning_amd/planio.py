@@ -183,6 +183,20 @@ def moving_boxes(boxes0, velocity, S):
     return out
 
 
+def goal_region(plan, half_x, half_y):
+    """The goal tolerance of a plan as a watched region (Context.set_regions): the box (cx, cy, half_x, half_y, yaw) centred at
+    the plan's last waypoint and turned to its heading.  `plan` is a dict with `traj` (W x 3) or the W x 3 array itself.
+    ValueError for an empty plan or a half extent that is not positive and finite."""
+    traj = np.asarray(plan["traj"] if isinstance(plan, dict) else plan, dtype=np.float64).reshape(-1, 3)
+    hx, hy = float(half_x), float(half_y)
+    if traj.shape[0] < 1:
+        raise ValueError("a plan has at least one waypoint")
+    if not (math.isfinite(hx) and math.isfinite(hy) and hx > 0.0 and hy > 0.0):
+        raise ValueError("half extents must be positive and finite, got %r, %r" % (half_x, half_y))
+    x, y, th = traj[-1]
+    return np.array([x, y, hx, hy, th], dtype=np.float64)
+
+
 MAX_WORLD_BOXES = 4096
 
 
