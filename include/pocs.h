@@ -530,6 +530,61 @@ int pocs_get_regions(const pocs_ctx* ctx, double* boxes, int* kinds, int cap);  
 int pocs_get_region_counts(pocs_ctx* ctx, unsigned long long* out, int cap, int* regions);
 int pocs_get_batch_region_probabilities(pocs_ctx* ctx, int region, int waypoint, double* out, int cap);
 
+/* ---- segment checks: collisions between waypoints, for both estimators (ours) ---------------------
+ * Both estimators test poses at waypoints only: a particle or sample that is free at waypoint w and free at w + 1 counts as safe,
+ * whatever stands between the two.  For a plan whose waypoints lie a robot length or more apart (RRT edges, lattice primitives)
+ * that is a risk that is too low.  With J >= 2 checks per segment (at most POCS_MAX_SEGMENT_CHECKS):
+ *   fraction   f_j = (double)j / (double)J, one IEEE division;
+ *   sub-pose   an output of the motion model as it is (pocs_motion, csrc/pocs_model.h, its angle wrap included) on a control whose
+ *              third entry is 0.0;
+ *   touches    a pose "touches" at a waypoint when the pose itself or one of J - 1 sub-poses on the way into that waypoint touches
+ *              (pocs_pose_collides, touching included).  Every result of both estimators is formed from that flag.
+ * J = 1 (the default) is every call as it has always been, bit for bit and launch for launch.
+ *   MC   a particle with pose p at waypoint s is driven by the step's noisy control u (the one the particle moves with):
+ *        q_j = pocs_motion(p, {u[0], f_j * u[1], 0.0}) for 1 <= j <= J - 1, one IEEE multiplication.  The particle touches at
+ *        waypoint s + 1 when its end pose (unchanged) or any q_j touches the world of waypoint s + 1 (world min(s + 1, S - 1) under a
+ *        schedule).  Waypoint 0 is the initial cloud alone.  The hit counters (+1 per waypoint at which the particle touches), the
+ *        first-collision profile, the counts and the MC risk bound are what they are, formed from that flag.
+ *   GMM  a sample p drawn at waypoint w >= 1 has no history: its way in is restated backwards with u = the applied control of step
+ *        w - 1 (the control the EKF carried the mixture with): q_j = pocs_motion(p, {-u[2], -(f_{J-j} * u[1]), 0.0}).  The sample's
+ *        flag is: its own pose or any q_j touches the world of waypoint w.  The truncation, nFree / nColl, the moment sums, the
+ *        per-waypoint and final probabilities, the risk bound and the stored flags follow from that flag.
+ *        NOTE what this number is: the estimator with "collides on the way into w" in place of "collides at w".  The way in is
+ *        approximated by the nominal control applied backwards from the sample: it is not a propagated sample path.
+ * Segment counts B[w], how many collisions were found only BETWEEN waypoints -- a planner reads from them that its waypoint spacing
+ * is too coarse for the world:
+ *   GMM  the samples of waypoint w whose own pose is free and some sub-pose touches (the odd shard's unused twin does not count):
+ *        B[w] <= the collisions at w;
+ *   MC   the particles whose first touching waypoint is w and whose end pose at w is free: B[w] <= F[w]
+ *        (pocs_mc_get_waypoint_counts);
+ *   B[0] = 0 always.
+ * pocs_set_segment_checks takes 1 <= J <= POCS_MAX_SEGMENT_CHECKS; anything else is POCS_E_ARG and the value in force stays.  Like
+ * every setter it ends run-ahead serving.  J belongs to the context: it survives pocs_set_plans and pocs_set_footprint.  The text
+ * channel has no command for it.  pocs_get_segment_checks returns the value in force.
+ *
+ * SERVED (J > 1), as a compound footprint is: whole calls on one GPU -- pocs_run_gmm_estimation, pocs_run_simulation,
+ * pocs_mc_run_local -- as single runs, batches in both sub-batch forms, run-ahead, calls of plans with and without both risk bounds
+ * (each plan on its own chain and clock), POCS_OPT_MC_WAYPOINT_COUNTS, POCS_OPT_STORE_SAMPLES (stored flags are the segment flags), over
+ * static worlds of up to 64 boxes and obstacle schedules.  A GMM call of one run takes the ticket form (POCS_OPT_LONE_CALL has no
+ * effect), an MC call the per-step form whatever POCS_OPT_MC_FUSED says, and counts as under POCS_OPT_MC_WAYPOINT_COUNTS.  J and the
+ * fractions live in device memory and the controls in the runs' chain records: another J > 1 replays the cached graph.
+ * REFUSED in both directions with POCS_E_STATE (POCS_E_ORDER for the setter inside a begin/end sequence), the context left as it
+ * was -- segment checks change results: a tree of plans, a large world (more than 64 boxes), a shard, the exchange (created or
+ * connected), a bound moments buffer, an open begin/end sequence and pocs_gmm_begin, POCS_OPT_OBSTACLE_COUNTS = 1, a compound
+ * footprint with F > 1.  pocs_set_segment_checks(J > 1) under any of these names what is in the way; entering any of them while
+ * J > 1 names the call and "segment checks are set (pocs_set_segment_checks)".
+ * NOT applied while J > 1, never refused: clearance levels and watched regions, as under a compound footprint -- their getters
+ * answer POCS_E_STATE and the call is the J > 1 call without them.
+ *
+ * pocs_get_segment_counts serves the selected run (pocs_select_batch_run; plan p while plans are set; the run served last under
+ * run-ahead): writes B[0 .. E) and returns E, the waypoints evaluated -- a plan's own length, or the waypoints before its stop under
+ * a risk bound.  POCS_E_BUFFER for cap < E, POCS_E_ARG for a null pointer, POCS_E_STATE -- the message says which -- when there was
+ * no call, J was 1, the setter was touched since, or the last call is not a served shape. */
+#define POCS_MAX_SEGMENT_CHECKS 8
+int pocs_set_segment_checks(pocs_ctx* ctx, int J);
+int pocs_get_segment_checks(const pocs_ctx* ctx);
+int pocs_get_segment_counts(pocs_ctx* ctx, unsigned long long* out, int cap);
+
 /* ---- results of the last run, for audits and parity tests ------------------------------- */
 int pocs_get_path_length(const pocs_ctx* ctx);
 int pocs_get_waypoint_probabilities(pocs_ctx* ctx, double* out, int cap);         /* `probabilities`, MCSimulator.h:660,678,817 */
@@ -601,6 +656,17 @@ int pocs_probe_device_regions(pocs_ctx* ctx, const double* fp4, const double* bo
    single-pose function of the MC kernels, and bit 8 + g is set should the two-pose lane-mask form ever disagree.  It reads nothing of
    the context's world, plans, modes or regions, so it is never refused.  POCS_E_ARG for a null pointer, n outside 1 .. 2^20, bad
    boxes or kinds and ANY input that is not finite. */
+int pocs_probe_device_segment(pocs_ctx* ctx, const double* fp4, const double* boxes, int M, const double* u3, int J, int backward,
+                              int n, const double* poses_xyt, int* mask_out);
+/* TEST HOOK beside pocs_probe_device_footprint_parts, equally self-contained: which of the segment checks' sub-poses the DEVICE finds
+   touching, for the caller's own footprint fp4 = {dx, dy, half_x, half_y}, table of M <= 64 boxes {cx, cy, half_x, half_y, yaw_rad},
+   control u3 and 1 <= J <= POCS_MAX_SEGMENT_CHECKS, prepared as the library prepares the context's.  backward 0 is the MC form: pose
+   i is a particle at the segment's start, driven by u3 as a noisy control; backward 1 is the GMM form: pose i is a sample at the
+   segment's end, u3 the applied control.  One small launch stages them; bit j of mask_out[i], 1 <= j <= J - 1, means sub-pose j
+   touches, bit J that the end pose touches (the moved particle, or the sample itself) -- through the inline functions the kernels
+   use (the single-pose form of the MC kernels, and the two-pose lane-mask form of the GMM sampling kernel on poses 2 j, 2 j + 1: bit
+   16 is set should the two ever disagree).  It reads nothing of the context's world or modes, so it is never refused.  POCS_E_ARG for
+   a null pointer, n outside 1 .. 2^20, J, M or backward out of range, a bad footprint or box and ANY input that is not finite. */
 int pocs_get_sequence_time(pocs_ctx* ctx, double* ms, int* concurrent);  /* POCS_OPT_PROFILE=1, whole-run GMM calls: first sampling launch -> end of the last one, and how many
                                                                             sub-batches of the call were in flight side by side (their launches overlap: DESIGN.md section 5) */
 

@@ -24,6 +24,7 @@ MAX_WORLD_STEPS = 4096
 MAX_WORLD_BOXES = 4096             # POCS_MAX_WORLD_BOXES: the largest table pocs_set_world takes
 MAX_CLEARANCE_LEVELS = 4           # POCS_MAX_CLEARANCE_LEVELS: the most distances pocs_set_clearance_levels takes
 MAX_REGIONS = 4                    # POCS_MAX_REGIONS: the most boxes pocs_set_regions takes
+MAX_SEGMENT_CHECKS = 8             # POCS_MAX_SEGMENT_CHECKS: the most checks per segment pocs_set_segment_checks takes
 REGION_TOUCH, REGION_POINT = 0, 1  # POCS_REGION_*: the robot's footprint touches the box / the pose's reference point lies in it
 MAX_FOOTPRINT_PARTS = 4            # POCS_MAX_FOOTPRINT_PARTS: the most parts pocs_set_footprint_parts takes
 
@@ -96,6 +97,10 @@ SIGNATURES = {
     "pocs_get_region_counts": (C.c_int, [_vp, C.POINTER(C.c_ulonglong), C.c_int, C.POINTER(C.c_int)]),
     "pocs_get_batch_region_probabilities": (C.c_int, [_vp, C.c_int, C.c_int, _dp, C.c_int]),
     "pocs_probe_device_regions": (C.c_int, [_vp, _dp, _dp, C.POINTER(C.c_int), C.c_int, C.c_int, _dp, C.POINTER(C.c_int)]),
+    "pocs_set_segment_checks": (C.c_int, [_vp, C.c_int]),
+    "pocs_get_segment_checks": (C.c_int, [_vp]),
+    "pocs_get_segment_counts": (C.c_int, [_vp, C.POINTER(C.c_ulonglong), C.c_int]),
+    "pocs_probe_device_segment": (C.c_int, [_vp, _dp, _dp, C.c_int, _dp, C.c_int, C.c_int, C.c_int, _dp, C.POINTER(C.c_int)]),
     "pocs_probe_device_footprint_parts": (C.c_int, [_vp, _dp, C.c_int, _dp, C.c_int, C.c_int, _dp, C.POINTER(C.c_int)]),
     "pocs_xchg_create": (C.c_int, [_vp, C.c_int, C.c_int, C.c_void_p]),
     "pocs_xchg_connect": (C.c_int, [_vp, C.c_void_p, C.c_int]),
@@ -597,6 +602,39 @@ class Context:
         self._chk(self.lib.pocs_probe_device_regions(self.h, fp.ctypes.data_as(_dp), b.ctypes.data_as(_dp) if b.size else None,
                                                      k.ctypes.data_as(ip) if k.size else None, b.shape[0], xyt.shape[0],
                                                      xyt.ctypes.data_as(_dp), out.ctypes.data_as(ip)))
+        return out
+
+    def set_segment_checks(self, J):
+        """J checks per segment, 1 <= J <= MAX_SEGMENT_CHECKS: with J >= 2 a pose also touches at a waypoint when one of J - 1 sub-poses
+        on the way into it touches.  1 (the default) is every call as it has always been (include/pocs.h)."""
+        self._chk(self.lib.pocs_set_segment_checks(self.h, int(J)))
+
+    def segment_checks(self):
+        """The number of checks per segment in force."""
+        return self._chk(self.lib.pocs_get_segment_checks(self.h))
+
+    def segment_counts(self):
+        """Segment counts of the current selection (run or plan) of the last call under segment checks: uint64[E], entry w = the
+        collisions at waypoint w that were found only between waypoints; include/pocs.h."""
+        E = max(self.path_length(), 1)
+        out = np.zeros(E, dtype=np.uint64)
+        got = self._chk(self.lib.pocs_get_segment_counts(self.h, out.ctypes.data_as(C.POINTER(C.c_ulonglong)), out.size))
+        return out[:got]
+
+    def probe_segment(self, footprint, boxes, u, J, backward, poses):
+        """Test hook: per pose (n x 3) the sub-poses of its segment that touch the caller's own boxes (M x 5) on the device, for a
+        footprint (dx, dy, hx, hy), a control u (3) and J checks; backward 0: the MC form from the start pose, 1: the GMM form from the
+        sample.  int32[n]: bit j (1 <= j < J) = sub-pose j touches, bit J = the end pose touches, bit 16 = the kernels' two forms
+        disagree (never)."""
+        fp = _arr(footprint).ravel()
+        b = _arr(boxes).reshape(-1, 5)
+        u3 = _arr(u).ravel()
+        xyt = _arr(poses).reshape(-1, 3)
+        assert fp.size == 4 and u3.size == 3
+        out = np.full(xyt.shape[0], -1, dtype=np.int32)
+        self._chk(self.lib.pocs_probe_device_segment(self.h, fp.ctypes.data_as(_dp), b.ctypes.data_as(_dp) if b.size else None, b.shape[0],
+                                                     u3.ctypes.data_as(_dp), int(J), int(backward), xyt.shape[0],
+                                                     xyt.ctypes.data_as(_dp), out.ctypes.data_as(C.POINTER(C.c_int))))
         return out
 
     def gmm_begin(self):

@@ -227,6 +227,8 @@ int pocs_set_footprint_parts(pocs_ctx* c, const double* parts, int F) {
     return fail(c, open ? POCS_E_ORDER : POCS_E_STATE, "pocs_set_footprint_parts: %s; %s",
                 pocs_modes::name((pocs_modes::Mode)(in_the_way & (0u - in_the_way))), pocs_modes::kPartsClause);
   }
+  if (seg_applied(c))                                // (the segment forms test a single box: refused in both directions)
+    return fail(c, POCS_E_STATE, "pocs_set_footprint_parts: segment checks are set (pocs_set_segment_checks); %s", pocs_modes::kSegClause);
   for (int f = 0; f < F; ++f) c->fp_parts[f] = pocs_footprint{parts[4 * f], parts[4 * f + 1], parts[4 * f + 2], parts[4 * f + 3]};
   c->fp_F = F;
   c->fp = c->fp_parts[0];
@@ -611,7 +613,7 @@ static int clearance_served(pocs_ctx* c, const char* what) {
     case Results::ClNoCall: return fail(c, POCS_E_STATE, "%s: there was no call yet", what);
     case Results::ClOff: return fail(c, POCS_E_STATE, "%s: the last call ran without clearance levels (L was 0)", what);
     case Results::ClTouched: return fail(c, POCS_E_STATE, "%s: pocs_set_clearance_levels touched the levels since the last call", what);
-    default: return fail(c, POCS_E_STATE, "%s: the levels are not applied to the last call (a tree of plans, a large world, POCS_OPT_OBSTACLE_COUNTS, a shard, the step API -- or it failed)", what);
+    default: return fail(c, POCS_E_STATE, "%s: the levels are not applied to the last call (a tree of plans, a large world, POCS_OPT_OBSTACLE_COUNTS, a shard, the step API, segment checks -- or it failed)", what);
   }
   if (r.cl_kind == Kind::None || r.cl_kind != r.last_kind || r.cl_counts.empty()) return fail(c, POCS_E_STATE, "%s: there was no call yet", what);
   return POCS_OK;
@@ -706,7 +708,7 @@ static int regions_served(pocs_ctx* c, const char* what) {
     case Results::RgNoCall: return fail(c, POCS_E_STATE, "%s: there was no call yet", what);
     case Results::RgOff: return fail(c, POCS_E_STATE, "%s: the last call ran without watched regions (G was 0)", what);
     case Results::RgTouched: return fail(c, POCS_E_STATE, "%s: pocs_set_regions touched the regions since the last call", what);
-    default: return fail(c, POCS_E_STATE, "%s: the regions are not applied to the last call (a tree of plans, a large world, POCS_OPT_OBSTACLE_COUNTS, a shard, the step API, a compound footprint, clearance levels -- or it failed)", what);
+    default: return fail(c, POCS_E_STATE, "%s: the regions are not applied to the last call (a tree of plans, a large world, POCS_OPT_OBSTACLE_COUNTS, a shard, the step API, a compound footprint, clearance levels, segment checks -- or it failed)", what);
   }
   if (r.rg_kind == Kind::None || r.rg_kind != r.last_kind || r.rg_counts.empty()) return fail(c, POCS_E_STATE, "%s: there was no call yet", what);
   return POCS_OK;
@@ -764,6 +766,61 @@ int pocs_get_batch_region_probabilities(pocs_ctx* c, int region, int waypoint, d
     out[r - lo] = prod * share;
   }
   return (int)(hi - lo);
+}
+
+// ---- segment checks (include/pocs.h) ----
+int pocs_set_segment_checks(pocs_ctx* c, int J) {
+  if (!setter(c)) return POCS_E_ARG;
+  if (J < 1 || J > POCS_MAX_SEGMENT_CHECKS)
+    return fail(c, POCS_E_ARG, "pocs_set_segment_checks: %d checks per segment outside 1..%d", J, POCS_MAX_SEGMENT_CHECKS);
+  if (J > 1) {
+    // (not a mode of the table: the one mask of what segment checks exclude, pocs_modes.hpp, and a compound footprint beside it)
+    unsigned in_the_way = modes_of(c) & pocs_modes::kSegExcluded;
+    if (in_the_way) {                                // names ONE mode: the open sequence before all others, a connected exchange before its buffer
+      const bool open = (in_the_way & pocs_modes::kSequence) != 0;
+      if (open) in_the_way = pocs_modes::kSequence;
+      if (in_the_way & pocs_modes::kXchgConnected) in_the_way &= ~(unsigned)pocs_modes::kXchgCreated;
+      return fail(c, open ? POCS_E_ORDER : POCS_E_STATE, "pocs_set_segment_checks: %s; %s",
+                  pocs_modes::name((pocs_modes::Mode)(in_the_way & (0u - in_the_way))), pocs_modes::kSegClause);
+    }
+    if (parts_applied(c))
+      return fail(c, POCS_E_STATE, "pocs_set_segment_checks: a compound footprint is set (pocs_set_footprint_parts); %s", pocs_modes::kSegClause);
+  }
+  c->seg_J = J;
+  c->env_dirty = true;                               // (J and the fractions live beside the world on the device)
+  if (c->res.sg_state != Results::SgNoCall) c->res.sg_state = Results::SgTouched;      // (a table is served until the setter is touched or the next call)
+  return POCS_OK;
+}
+
+int pocs_get_segment_checks(const pocs_ctx* c) { return c ? c->seg_J : POCS_E_ARG; }
+
+int pocs_get_segment_counts(pocs_ctx* c, unsigned long long* out, int cap) {
+  if (!c) return POCS_E_ARG;
+  if (!out) return fail(c, POCS_E_ARG, "pocs_get_segment_counts: null output");
+  const Results& r = c->res;
+  const char* const what = "pocs_get_segment_counts";
+  switch (r.sg_state) {
+    case Results::SgServed: break;
+    case Results::SgNoCall: return fail(c, POCS_E_STATE, "%s: there was no call yet", what);
+    case Results::SgOff: return fail(c, POCS_E_STATE, "%s: the last call ran without segment checks (J was 1)", what);
+    case Results::SgTouched: return fail(c, POCS_E_STATE, "%s: pocs_set_segment_checks was called since the last call", what);
+    default: return fail(c, POCS_E_STATE, "%s: the last call is not a served shape (it failed, or was refused)", what);
+  }
+  if (r.sg_kind == Kind::None || r.sg_kind != r.last_kind || r.sg_counts.empty()) return fail(c, POCS_E_STATE, "%s: there was no call yet", what);
+  // run / plan `view` of the last call: its batch slot and the waypoints its row covers
+  size_t slot = (size_t)r.view;
+  int E = r.sg_W;
+  if (c->plans.n && (size_t)r.view < r.plan_slot(r.sg_kind).size()) {
+    const size_t p = (size_t)r.view;
+    slot = (size_t)r.plan_slot(r.sg_kind)[p];
+    if (r.sg_kind == Kind::Gmm) E = p < r.plan_E.size() ? r.plan_E[p] : c->plans.W[p];
+    else E = r.plan_E_mc.empty() ? c->plans.W[p] : r.plan_E_mc[p];
+  }
+  const size_t W = (size_t)r.sg_W;
+  if ((slot + 1) * W > r.sg_counts.size() || (size_t)E > W) return fail(c, POCS_E_STATE, "%s: the table does not cover the selection", what);
+  if (cap < E) return fail(c, POCS_E_BUFFER, "need %d counters", E);
+  for (int w = 0; w < E; ++w) out[w] = r.sg_counts[slot * W + (size_t)w];
+  return E;
 }
 
 int pocs_get_batch_probabilities(pocs_ctx* c, double* out, int cap) {

@@ -446,6 +446,61 @@ int pocs_probe_device_regions(pocs_ctx* c, const double* fp4, const double* boxe
   return rc;
 }
 
+// Test hook: which sub-poses of a segment touch, on the device, for chosen poses, footprint, boxes, control and J (include/pocs.h).
+// Nothing of the context's world, plans or modes is read: the records and the segment record are prepared here, as upload_world
+// prepares the context's.
+int pocs_probe_device_segment(pocs_ctx* c, const double* fp4, const double* boxes, int M, const double* u3, int J, int backward, int n,
+                              const double* poses, int* mask_out) {
+  if (!c) return POCS_E_ARG;
+  if (!fp4 || !u3 || !poses || !mask_out || n < 1 || n > (1 << 20) || J < 1 || J > POCS_MAX_SEGMENT_CHECKS || M < 0 || M > POCS_MAX_OBSTACLES ||
+      (M > 0 && !boxes) || (backward != 0 && backward != 1))
+    return fail(c, POCS_E_ARG, "pocs_probe_device_segment: 1 <= n <= 2^20, 1 <= J <= %d, 0 <= M <= %d, backward 0 or 1, no null pointers", POCS_MAX_SEGMENT_CHECKS, POCS_MAX_OBSTACLES);
+  for (int j = 0; j < 4; ++j)
+    if (!std::isfinite(fp4[j])) return fail(c, POCS_E_ARG, "pocs_probe_device_segment: footprint value %d is not finite", j);
+  if (!(fp4[2] > 0) || !(fp4[3] > 0)) return fail(c, POCS_E_ARG, "pocs_probe_device_segment: footprint half extents must be > 0");
+  for (int j = 0; j < 3; ++j)
+    if (!std::isfinite(u3[j])) return fail(c, POCS_E_ARG, "pocs_probe_device_segment: control value %d is not finite", j);
+  for (size_t j = 0; j < 5 * (size_t)M; ++j)
+    if (!std::isfinite(boxes[j])) return fail(c, POCS_E_ARG, "pocs_probe_device_segment: box %zu: value %zu is not finite", j / 5, j % 5);
+  for (int m = 0; m < M; ++m)
+    if (!(boxes[5 * (size_t)m + 2] > 0) || !(boxes[5 * (size_t)m + 3] > 0)) return fail(c, POCS_E_ARG, "pocs_probe_device_segment: box %d: half extents must be > 0", m);
+  for (size_t j = 0; j < 3 * (size_t)n; ++j)
+    if (!std::isfinite(poses[j])) return fail(c, POCS_E_ARG, "pocs_probe_device_segment: pose %zu is not finite", j / 3);
+  HIPCHK(c, hipSetDevice(c->device));
+  if (int r = upload_tables(c)) return r;
+  const pocs_footprint fp = {fp4[0], fp4[1], fp4[2], fp4[3]};
+  std::vector<pocs_env_dev> env(1);
+  memset(env.data(), 0, sizeof(pocs_env_dev));
+  env[0].fp = fp; env[0].M = M;
+  for (int m = 0; m < M; ++m) pocs_prepare_obstacle(boxes + (size_t)m * 5, &fp, &env[0].obs[(size_t)m * POCS_OBS_STRIDE]);
+  pocs_seg_dev sg;
+  prepare_segment(J, &sg);
+  std::vector<double> h(3 * (size_t)n);
+  for (int i = 0; i < n; ++i)
+    for (int j = 0; j < 3; ++j) h[(size_t)j * n + i] = poses[3 * (size_t)i + j];
+  // [env | seg | x | y | th] then [masks n] ints
+  const size_t off_seg = sizeof(pocs_env_dev), off_x = off_seg + sizeof(pocs_seg_dev), off_out = off_x + 3 * (size_t)n * sizeof(double);
+  static_assert(sizeof(pocs_env_dev) % 8 == 0 && sizeof(pocs_seg_dev) % 8 == 0, "the probe's buffer keeps its parts aligned");
+  char* buf = nullptr;
+  HIPCHK(c, hipMalloc((void**)&buf, off_out + (size_t)n * sizeof(int)));
+  int rc = POCS_OK;
+  if (hipMemcpy(buf, env.data(), sizeof(pocs_env_dev), hipMemcpyHostToDevice) != hipSuccess ||
+      hipMemcpy(buf + off_seg, &sg, sizeof sg, hipMemcpyHostToDevice) != hipSuccess ||
+      hipMemcpy(buf + off_x, h.data(), h.size() * sizeof(double), hipMemcpyHostToDevice) != hipSuccess ||
+      hipMemset(buf + off_out, 0, (size_t)n * sizeof(int)) != hipSuccess)
+    rc = fail(c, POCS_E_DEVICE, "probe upload failed");
+  const double* d_x = (const double*)(buf + off_x);
+  if (rc == POCS_OK && pocs_launch_probe_segment((const pocs_env_dev*)buf, (const pocs_seg_dev*)(buf + off_seg), (const pocs_tables*)c->d_tables.p,
+                                                 u3[0], u3[1], u3[2], backward, n, d_x, d_x + n, d_x + 2 * (size_t)n, (int*)(buf + off_out),
+                                                 c->stream) != hipSuccess)
+    rc = fail(c, POCS_E_DEVICE, "probe launch failed");
+  if (rc == POCS_OK && hipStreamSynchronize(c->stream) != hipSuccess) rc = fail(c, POCS_E_DEVICE, "probe kernel failed");
+  if (rc == POCS_OK && hipMemcpy(mask_out, buf + off_out, (size_t)n * sizeof(int), hipMemcpyDeviceToHost) != hipSuccess)
+    rc = fail(c, POCS_E_DEVICE, "probe download failed");
+  (void)hipFree(buf);
+  return rc;
+}
+
 int pocs_get_sequence_time(pocs_ctx* c, double* ms, int* concurrent) {
   if (!c) return POCS_E_ARG;
   if (ms) *ms = c->seq_ms;

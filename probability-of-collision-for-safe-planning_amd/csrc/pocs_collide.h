@@ -12,6 +12,7 @@
 //                                     bounding radius (broad phase; purely conservative)
 #pragma once
 #include "pocs_math.h"
+#include "pocs_model.h"      // pocs_wrap_angle: the segment checks' sub-poses are outputs of pocs_motion
 
 #define POCS_OBS_STRIDE 8
 #define POCS_MAX_OBSTACLES 64
@@ -596,5 +597,168 @@ __device__ __forceinline__ void pocs_pair_regions_masks(const double x[2], const
     pocs_pair_collides_masks<false>(x, y, th, &f, rec + g * POCS_OBS_STRIDE, 1, T, V, m);
     each(g, m[0], m[1]);
   }
+}
+#endif
+
+// ---- segment checks (pocs_set_segment_checks) ------------------------------------------------------------------------
+// With J >= 2 checks per segment a pose also "touches" at a waypoint when one of J - 1 sub-poses on the way into that waypoint
+// touches.  The sub-poses are outputs of pocs_motion (pocs_model.h) as it is, on a control whose third entry is 0.0:
+//   q_j = pocs_motion(p, {a0, d_j, 0.0}),  1 <= j <= J - 1,
+//   forwards  (MC, from the particle at the segment's start, the step's noisy control u):   a0 = u[0],  d_j = f_j * u[1];
+//   backwards (GMM, from the sample at the segment's end, the step's applied control u):    a0 = -u[2], d_j = -(f_{J-j} * u[1]);
+//   f_j = (double)j / (double)J, one IEEE division (pocs_segment_fractions: formed once on the host, read by the kernels).
+// The J - 1 sub-poses of a pose share one heading: one sine and cosine of the drive direction p.theta + a0 (pocs_sincos, as
+// pocs_motion forms them -- the MC step holds them already), one of the wrapped heading as the collision test evaluates it
+// (pocs_sincos_tab), and the rotated footprint offset once; only the centre moves, along a line.  Per sub-pose and record the
+// operations of pocs_pose_collides in its order (pocs_box_hit): the flags are those of pocs_pose_collides(q_j).
+//   The broad phase over the whole segment (single-pose form): fma(d, cs, x) is a monotone function of d, and so is the sum
+//   with the offset and the difference to a record's centre, each being one rounded monotone operation; every d_j lies between
+//   0 and d_end = +-u[1] (f < 1, a rounded product never passes its factor).  So per axis every sub-pose's offset to a record
+//   lies between the offsets of the two ends d = 0 and d = d_end, and a record whose broad-phase box neither end's interval
+//   reaches is failed by pocs_box_hit's broad phase for every sub-pose: it is skipped for all of them.  Exact, no margin.
+#define POCS_MAX_SEGMENT_CHECKS 8
+
+POCS_HD void pocs_segment_fractions(int J, double* f) {            // f[j] = j / J for j < J, 0 behind (f[0] = 0)
+  for (int j = 0; j < POCS_MAX_SEGMENT_CHECKS; ++j) f[j] = j < J ? (double)j / (double)J : 0.0;
+}
+// the drive of sub-pose j
+POCS_HD double pocs_segment_drive(const double* f, int J, int j, int backward, double u1) {
+  return backward ? -(f[J - j] * u1) : f[j] * u1;
+}
+
+// One pose: bit j (1 <= j <= J - 1) of the answer is set when sub-pose j touches some record.  hd = p.theta + a0, the drive
+// direction as pocs_motion forms it, (sn, cs) its sine and cosine by pocs_sincos.
+POCS_HD unsigned pocs_segment_touched_dir(double x, double y, double hd, double sn, double cs, double u1, const double* f, int J, int backward,
+                                          const pocs_footprint* fp, const double* obs, int M, const pocs_tables* T,
+                                          const pocs_vconst* V = nullptr) {
+  if (M <= 0 || J < 2) return 0u;
+  const double qt = pocs_wrap_angle(hd + 0.0);                     // pocs_motion: x[2] + u[0] + u[2] with u[2] = 0.0
+  double sh, ch;
+  pocs_sincos_tab(qt, T, &sh, &ch, V);
+  const bool offset = !(fp->dx == 0.0 && fp->dy == 0.0);
+  double ox = 0.0, oy = 0.0;
+  if (offset) {
+    ox = fma(ch, fp->dx, -(sh * fp->dy));
+    oy = fma(sh, fp->dx, ch * fp->dy);
+  }
+  // the two ends of the line the footprint's centre moves on
+  const double dend = backward ? -u1 : u1;
+  double ax = x, ay = y, bx = fma(dend, cs, x), by = fma(dend, sn, y);
+  if (offset) { ax = x + ox; ay = y + oy; bx = bx + ox; by = by + oy; }
+  const double xlo = fmin(ax, bx), xhi = fmax(ax, bx), ylo = fmin(ay, by), yhi = fmax(ay, by);
+  static_assert(POCS_MAX_OBSTACLES <= 64, "the records in the segment's reach are a 64-bit mask");
+  unsigned long long cand = 0ull;
+  for (int m = 0; m < M; ++m) {
+    const double* o = obs + m * POCS_OBS_STRIDE;
+    // o[0] - px over px in [xlo, xhi] lies in [o[0] - xhi, o[0] - xlo]: all |.| > o[6] exactly when the interval misses [-o[6], o[6]]
+    if (o[0] - xhi > o[6] || o[0] - xlo < -o[6] || o[1] - yhi > o[7] || o[1] - ylo < -o[7]) continue;
+    cand |= 1ull << m;
+  }
+  if (cand == 0ull) return 0u;
+  unsigned touched = 0u;
+  for (int j = 1; j < J; ++j) {
+    const double d = pocs_segment_drive(f, J, j, backward, u1);
+    const double qx = fma(d, cs, x), qy = fma(d, sn, y);
+    double px = qx, py = qy;
+    if (offset) { px = qx + ox; py = qy + oy; }
+    bool hit = false;
+    for (unsigned long long b = cand; b != 0ull; b &= b - 1ull) {
+      const int m = __builtin_ctzll(b);
+      if (pocs_box_hit(px, py, sh, ch, fp->hx, fp->hy, obs + m * POCS_OBS_STRIDE)) hit = true;
+    }
+    if (hit) touched |= 1u << j;
+  }
+  return touched;
+}
+// ... with the drive direction's sine and cosine formed here (the GMM form's way in, the probe, the host harness)
+POCS_HD unsigned pocs_segment_touched(double x, double y, double th, double a0, double u1, const double* f, int J, int backward,
+                                      const pocs_footprint* fp, const double* obs, int M, const pocs_tables* T,
+                                      const pocs_vconst* V = nullptr) {
+  if (M <= 0 || J < 2) return 0u;
+  double sn, cs;
+  pocs_sincos(th + a0, &sn, &cs);
+  return pocs_segment_touched_dir(x, y, th + a0, sn, cs, u1, f, J, backward, fp, obs, M, T, V);
+}
+
+#if defined(__HIPCC__)
+// The same for the pair of poses a sampling thread holds, as lane masks in the manner of pocs_pair_parts_masks: mask[h] bit l =
+// some sub-pose of lane l's pose h touches; each(j, m0, m1) is called once per sub-pose with its own two masks.  The two drive
+// directions' and wrapped headings' sines and cosines and the rotated offsets once per call; per sub-pose the record loop of
+// pocs_pair_parts_masks -- one fetch per record for both poses, the narrow phase behind wave-uniform branches, every answer
+// balloted.  `obs` lies in LDS (the caller's kept list, culled for the whole segment); f, J, backward, a0, u1 and M are
+// wave-uniform.
+struct pocs_each_sub_none { __device__ __forceinline__ void operator()(int, unsigned long long, unsigned long long) const {} };
+
+template <class Each = pocs_each_sub_none>
+__device__ __forceinline__ void pocs_pair_segment_masks(const double x[2], const double y[2], const double th[2], double a0, double u1,
+                                                        const double* f, int J, int backward, const pocs_footprint* fp,
+                                                        const double* obs, int M, const pocs_tables* T, const pocs_vconst* V,
+                                                        unsigned long long mask[2], Each each = Each()) {
+  unsigned long long all0 = 0ull, all1 = 0ull;
+  const double rx = fp->hx, ry = fp->hy;
+  double sn[2] = {0.0, 0.0}, cs[2] = {1.0, 1.0}, sh[2] = {0.0, 0.0}, ch[2] = {1.0, 1.0}, ox[2] = {0.0, 0.0}, oy[2] = {0.0, 0.0}, ex[2], ey[2];
+  const bool offset = __builtin_amdgcn_ballot_w64(!(fp->dx == 0.0 && fp->dy == 0.0)) != 0ull;      // (scalar: every lane reads the same footprint)
+  if (M > 0) {                                                       // (scalar)
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+      const double hd = th[h] + a0;
+      pocs_sincos(hd, &sn[h], &cs[h]);
+      pocs_sincos_tab(pocs_wrap_angle(hd + 0.0), T, &sh[h], &ch[h], V);
+      if (offset) {
+        ox[h] = fma(ch[h], fp->dx, -(sh[h] * fp->dy));
+        oy[h] = fma(sh[h], fp->dx, ch[h] * fp->dy);
+      }
+    }
+  }
+#pragma unroll
+  for (int h = 0; h < 2; ++h) {
+    ex[h] = fma(rx, fabs(ch[h]), ry * fabs(sh[h]));
+    ey[h] = fma(rx, fabs(sh[h]), ry * fabs(ch[h]));
+  }
+#pragma unroll 1
+  for (int j = 1; j < J; ++j) {
+    unsigned long long m0 = 0ull, m1 = 0ull;
+    if (M > 0) {
+      const double d = pocs_segment_drive(f, J, j, backward, u1);
+      double px[2], py[2];
+#pragma unroll
+      for (int h = 0; h < 2; ++h) {
+        px[h] = fma(d, cs[h], x[h]); py[h] = fma(d, sn[h], y[h]);
+        if (offset) { px[h] = px[h] + ox[h]; py[h] = py[h] + oy[h]; }
+      }
+      const __attribute__((address_space(3))) pocs_v2d* o = (const __attribute__((address_space(3))) pocs_v2d*)obs;
+      asm volatile("" : "+v"(o));
+      for (int m = 0; m < M; ++m, o += POCS_OBS_STRIDE / 2) {
+        const pocs_v2d c = o[0], b = o[3], a = o[1], e = o[2];       // (cx, cy) (bx, by) | (ax, ay) (hx, hy)
+        double dx[2], dy[2];
+        unsigned long long pm[2], bt[2] = {0ull, 0ull};
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {                                // pocs_box_hit's broad phase
+          dx[h] = c.x - px[h];
+          dy[h] = c.y - py[h];
+          pm[h] = __builtin_amdgcn_ballot_w64(!(fabs(dx[h]) > b.x)) & __builtin_amdgcn_ballot_w64(!(fabs(dy[h]) > b.y));
+        }
+        if ((pm[0] | pm[1]) != 0ull) {                               // pocs_box_narrow for the lanes inside the box
+          const bool turned = (__builtin_amdgcn_ballot_w64(a.x != 1.0) | __builtin_amdgcn_ballot_w64(a.y != 0.0)) != 0ull;
+#pragma unroll
+          for (int h = 0; h < 2; ++h) {
+            if (pm[h] == 0ull) continue;
+            if (!turned)
+              bt[h] = pocs_box_margins_mask(pm[h], dx[h], dy[h], sh[h], ch[h], rx, ry, e.x, e.y, ch[h], sh[h], dx[h], dy[h], ex[h], ey[h]);
+            else {
+              const double cr = fma(ch[h], a.x, sh[h] * a.y), sr = fma(sh[h], a.x, -(ch[h] * a.y));      // the relative yaw
+              bt[h] = pocs_box_margins_mask(pm[h], dx[h], dy[h], sh[h], ch[h], rx, ry, e.x, e.y, cr, sr,
+                                            fma(dx[h], a.x, dy[h] * a.y), fma(dy[h], a.x, -(dx[h] * a.y)),
+                                            fma(rx, fabs(cr), ry * fabs(sr)), fma(rx, fabs(sr), ry * fabs(cr)));
+            }
+          }
+          m0 |= bt[0]; m1 |= bt[1];
+        }
+      }
+    }
+    each(j, m0, m1);
+    all0 |= m0; all1 |= m1;
+  }
+  mask[0] = all0; mask[1] = all1;
 }
 #endif

@@ -114,6 +114,13 @@ struct Results {
   int rg_G = 0, rg_W = 0;
   long long rg_N = 0;                             // samples / particles per waypoint of the call: the probabilities' divisor
   std::vector<unsigned long long> rg_counts;
+  // segment checks (pocs_set_segment_checks): the segment counts B of the last call, read back with its results in slot order
+  // ([slot][sg_W]), and why there are none to serve (pocs_get_segment_counts names it)
+  enum SegState { SgNoCall, SgOff, SgTouched, SgNotServed, SgServed };
+  SegState sg_state = SgNoCall;
+  Kind sg_kind = Kind::None;
+  int sg_J = 1, sg_W = 0;
+  std::vector<unsigned long long> sg_counts;
 };
 
 // One cached graph and its signature: the bytes of its launches in issue order (Issuer, pocs_host.hip), compared before a replay.
@@ -209,6 +216,10 @@ struct pocs_ctx {
   // kernels' _parts / MC_PARTS forms (parts_applied, pocs_host.hip) and the modes of pocs_modes::kPartsExcluded are refused
   int fp_F = 1;
   pocs_footprint fp_parts[POCS_MAX_FOOTPRINT_PARTS] = {};
+  // segment checks (pocs_set_segment_checks): J = 1 is off -- every call is, launch for launch, what it is without this.  J > 1: every
+  // call is served by the kernels' _seg / MC_SEG forms (seg_applied) and the modes of pocs_modes::kSegExcluded and a compound
+  // footprint are refused
+  int seg_J = 1;
 
   // host image (headers | chains | initial mixtures) of the NEXT batch, computed while the GPU
   // works on the current one
@@ -238,6 +249,9 @@ struct pocs_ctx {
   // kernel at the head of every call's launches
   pocs_rt::DevBuf d_reg, d_regct;
   pocs_rt::DevBuf d_parts;               // a compound footprint: one pocs_parts_dev beside d_env (upload_world)
+  // segment checks: one pocs_seg_dev beside d_env (upload_world: J and the fractions live in device memory, so another J > 1 replays
+  // the cached graph) and the segment counts [slots][W] u64, zeroed by a kernel at the head of every call's launches
+  pocs_rt::DevBuf d_seg, d_segct;
   pocs_rt::DevBuf d_obsct;               // POCS_OPT_OBSTACLE_COUNTS: [slots][W][POCS_MAX_OBSTACLES] u64, zeroed by a kernel at the head of every call's launches
   // one-hop exchange (pocs_xchg_*): this rank's buffer, the peers' buffers as mapped here
   void* xchg_own = nullptr;
@@ -332,6 +346,7 @@ inline void reset_results(pocs_ctx* c) {
   r.oc_kind = Kind::None; r.oc_M = 0; r.oc_W = 0;
   r.cl_state = Results::ClNoCall; r.cl_kind = Kind::None; r.cl_L = 0; r.cl_W = 0; r.cl_N = 0; r.cl_counts.clear();
   r.rg_state = Results::RgNoCall; r.rg_kind = Kind::None; r.rg_G = 0; r.rg_W = 0; r.rg_N = 0; r.rg_counts.clear();
+  r.sg_state = Results::SgNoCall; r.sg_kind = Kind::None; r.sg_J = 1; r.sg_W = 0; r.sg_counts.clear();
 }
 
 // The collision world: M boxes per step, and the record of the device's env array ([world_S] pocs_env_dev) that waypoint w --
@@ -368,10 +383,20 @@ inline int parts_refuse(pocs_ctx* c, const char* what, pocs_modes::Mode enter) {
   return fail(c, POCS_E_STATE, "%s: a compound footprint is set (pocs_set_footprint_parts); %s", what, pocs_modes::kPartsClause);
 }
 
+// Segment checks are set (pocs_set_segment_checks with J > 1): as a compound footprint, one mask (pocs_modes::kSegExcluded) asked in
+// front of the table and by the setter itself.
+inline bool seg_applied(const pocs_ctx* c) { return c->seg_J > 1; }
+inline int seg_refuse(pocs_ctx* c, const char* what, pocs_modes::Mode enter) {
+  if (!seg_applied(c) || !(enter & pocs_modes::kSegExcluded)) return POCS_OK;
+  return fail(c, POCS_E_STATE, "%s: segment checks are set (pocs_set_segment_checks); %s", what, pocs_modes::kSegClause);
+}
+
 // May the context enter `enter`, as asked by the call `what`?  The one place that refuses a combination (pocs_modes.hpp).
 inline int may_enter(pocs_ctx* c, const char* what, pocs_modes::Mode enter, unsigned among = pocs_modes::kAll) {
-  if (among == pocs_modes::kAll)                     // (a setter's staged asks in front of its argument checks enter nothing yet)
+  if (among == pocs_modes::kAll) {                   // (a setter's staged asks in front of its argument checks enter nothing yet)
     if (int r = parts_refuse(c, what, enter)) return r;
+    if (int r = seg_refuse(c, what, enter)) return r;
+  }
   const pocs_modes::Refusal r = pocs_modes::refusal(modes_of(c), enter, among);
   if (r.code == POCS_OK) return POCS_OK;
   char clause[200];
@@ -412,6 +437,7 @@ bool clearance_applied(const pocs_ctx* c);
 bool regions_applied(const pocs_ctx* c);
 double waypoint_probability(const double* row, int K, long long n);
 void prepare_regions(const pocs_footprint& fp, const double* boxes, const int* kinds, int G, pocs_regions_dev* out);
+void prepare_segment(int J, pocs_seg_dev* out);
 void prepare_parts(const pocs_footprint* parts, int F, const double* boxes, int M, pocs_env_dev* env, pocs_parts_dev* out);
 void prepare_clearance(const pocs_footprint& fp, const double* d, int L, const double* boxes, int M, pocs_clear_dev* out);
 void gmm_select_view(pocs_ctx* c, int v);

@@ -73,13 +73,25 @@ template <> struct gmm_rg_smem<true> {
   unsigned rgc[2][POCS_MAX_REGIONS];
   unsigned rgk[2];
 };
-template <int K, int TB, bool OC = false, bool CL = false, bool FPN = false, bool RG = false>
-struct gmm_smem : gmm_oc_smem<OC>, gmm_cl_smem<CL>, gmm_fp_smem<FPN>, gmm_rg_smem<RG> {
+//   keeps / sgf / sgu / sgc  (the segment form only, pocs_set_segment_checks: an empty base otherwise again) per run buffer the obstacle
+//          table culled for the run's whole way in (8 KB), the fractions f_j, the run's applied control of step w - 1, the block's
+//          samples whose own pose is free and some sub-pose touches, and J
+template <bool SG> struct gmm_sg_smem {};
+template <> struct gmm_sg_smem<true> {
+  alignas(16) double keeps[2][POCS_MAX_OBSTACLES * POCS_OBS_STRIDE];
+  double sgf[2][POCS_MAX_SEGMENT_CHECKS];
+  double sgu[2][4];
+  unsigned sgc[2];
+  int nkeeps[2];
+  int sgJ[2];
+};
+template <int K, int TB, bool OC = false, bool CL = false, bool FPN = false, bool RG = false, bool SG = false>
+struct gmm_smem : gmm_oc_smem<OC>, gmm_cl_smem<CL>, gmm_fp_smem<FPN>, gmm_rg_smem<RG>, gmm_sg_smem<SG> {
   static constexpr int NC = K * POCS_NMOM;
   static constexpr int NW = TB / 64;
   // (the clearance form holds 24 units at a time, not 32: with its second kept table K = 7 and K = 8 would otherwise pass the 80 KB
   // that let two blocks share a CU's 160 KB; the sums are defined per unit, so how many a block holds at a time changes no bit)
-  static constexpr int SUB = CL ? 24 : POCS_GMM_SUB;
+  static constexpr int SUB = (CL || SG) ? 24 : POCS_GMM_SUB;      // (the segment form's second kept table: as the clearance form)
   alignas(16) pocs_tables tab;                                       // 12 KB log / sector tables, staged once per block
   alignas(16) double keep[2][POCS_MAX_OBSTACLES * POCS_OBS_STRIDE];  // obstacle table culled for the block's (up to) two runs
   alignas(16) double par[2][K * POCS_PARAM_STRIDE];                  // sampler parameters of (run, waypoint)
@@ -129,8 +141,8 @@ __device__ __forceinline__ double oct_sum(double s) {     // lanes 8 j .. 8 j + 
 // wave's xtra entry of k), and the chains restart.  By LDS transposition, five then four sums at a
 // time: every lane writes its values, lane 8 j + q adds lanes 8 q .. 8 q + 7 of sum j, oct_sum adds the
 // eight q.  One wave: the LDS executes a wave's instructions in order, nothing else synchronises.
-template <int K, int TB, bool OC, bool CL, bool FPN, bool RG>
-__device__ __forceinline__ void flush_unit(gmm_smem<K, TB, OC, CL, FPN, RG>& sm, const int wave, const int lane, const int rb, const int tl,
+template <int K, int TB, bool OC, bool CL, bool FPN, bool RG, bool SG>
+__device__ __forceinline__ void flush_unit(gmm_smem<K, TB, OC, CL, FPN, RG, SG>& sm, const int wave, const int lane, const int rb, const int tl,
                                            const int k, bool& first, double (&acc)[9], int& nfree) {
   double* const T = &sm.tr[wave][0][0];
   double* const dst = first ? &sm.slot[tl][wave][0] : &sm.xtra[rb][wave][k][0];
@@ -196,8 +208,8 @@ __device__ __forceinline__ void gmm_reach(const pocs_footprint& fp, const double
   ext_y = pocs_footprint_extent_is_radius(fp_phi, tlo - HALF_PI, thi - HALF_PI) ? fp_rr
         : pocs_footprint_extent_of_ends(fp_rr, lane_value(end_f, 2), lane_value(end_f, 3));
 }
-template <int K, int TB, bool OC, bool CL, bool FPN, bool RG>
-__device__ __forceinline__ void gmm_cull(const pocs_gmm_launch& a, gmm_smem<K, TB, OC, CL, FPN, RG>& sm, const int rb, const int lane, const double* par) {
+template <int K, int TB, bool OC, bool CL, bool FPN, bool RG, bool SG>
+__device__ __forceinline__ void gmm_cull(const pocs_gmm_launch& a, gmm_smem<K, TB, OC, CL, FPN, RG, SG>& sm, const int rb, const int lane, const double* par) {
   const pocs_footprint fp = a.fp;
   const int M = a.M;
   const double* const obs = sm.obs();
@@ -376,6 +388,51 @@ __device__ __forceinline__ void gmm_cull_regions(const pocs_gmm_launch& a, gmm_s
   if (lane == 0) sm.rgk[rb] = (unsigned)mask;
 }
 
+// The segment form's second list (one wave, all 64 lanes, beside the wave that runs gmm_cull for the same run buffer; `r` is the run):
+// the records some SUB-POSE of some sample of the run can touch.  A sub-pose's centre lies up to |u[1]| from its sample's (the drive
+// of sub-pose j is a rounded fraction of u[1], and the drive direction is a unit vector up to rounding), and its heading is the
+// sample's shifted by -u[2]: so the mixture's 6.67 sigma box is grown by |u[1]| (and the footprint's offset, and a margin for the
+// rounding), and a record is tested with the table's own broad-phase box -- its AABB grown by the footprint's bounding radius, which
+// bounds the footprint's extent at EVERY heading: no range of headings is assumed for the sub-poses.  A record that fails this is
+// failed by pocs_box_hit's broad phase for every sub-pose of the run, so dropping it changes no flag; the kept records keep the
+// table's fields 6 and 7.  At waypoint 0 there is no way in: the list is empty.  An empty list skips all sub-pose work of the run
+// buffer by one scalar branch (gmm_units).  The wave also stages J, the fractions and the run's applied control of step w - 1 (chain
+// record [0..2]), and zeroes the buffer's counter.
+template <int K, int TB>
+__device__ __forceinline__ void gmm_cull_seg(const pocs_gmm_launch& a, gmm_smem<K, TB, false, false, false, false, true>& sm, const int rb, const int lane,
+                                             const double* par, const int r) {
+  const int w = a.waypoint, M = a.M;
+  const int J = a.seg->J;
+  const double* const ch = a.chain + ((size_t)r * (a.W > 1 ? a.W - 1 : 1) + (w > 0 ? w - 1 : 0)) * POCS_CHAIN_STRIDE;
+  const double u1 = w > 0 ? ch[1] : 0.0;
+  if (lane < POCS_MAX_SEGMENT_CHECKS) sm.sgf[rb][lane] = a.seg->f[lane];
+  if (lane < 3) sm.sgu[rb][lane] = w > 0 ? ch[lane] : 0.0;
+  const pocs_footprint fp = a.fp;
+  const double* const obs = sm.obs();
+  double xlo = 1e300, xhi = -1e300, ylo = 1e300, yhi = -1e300;
+#pragma unroll
+  for (int k = 0; k < K; ++k) {
+    const double* p = &par[k * POCS_PARAM_STRIDE];
+    const double ex = 6.67 * fabs(p[3]), ey = 6.67 * (fabs(p[4]) + fabs(p[5]));
+    xlo = fmin(xlo, p[0] - ex); xhi = fmax(xhi, p[0] + ex);
+    ylo = fmin(ylo, p[1] - ey); yhi = fmax(yhi, p[1] + ey);
+  }
+  const double pad = sqrt(fp.dx * fp.dx + fp.dy * fp.dy) + fabs(u1) * (1.0 + 1e-9) + 1e-6;   // footprint centre vs base, the drive
+  xlo -= pad; xhi += pad; ylo -= pad; yhi += pad;
+  bool keep = false;
+  if (lane < M && w > 0 && J > 1) {
+    const double* o = &obs[lane * POCS_OBS_STRIDE];
+    keep = !(o[0] - o[6] > xhi || o[0] + o[6] < xlo || o[1] - o[7] > yhi || o[1] + o[7] < ylo);
+  }
+  const unsigned long long mask = __ballot(keep);
+  if (keep) {
+    const int pos = __popcll(mask & ((1ull << lane) - 1ull));
+#pragma unroll
+    for (int j = 0; j < POCS_OBS_STRIDE; ++j) sm.keeps[rb][pos * POCS_OBS_STRIDE + j] = obs[lane * POCS_OBS_STRIDE + j];
+  }
+  if (lane == 0) { sm.nkeeps[rb] = __popcll(mask); sm.sgc[rb] = 0u; sm.sgJ[rb] = J; }
+}
+
 // ---------------------------------------------------------------------------------------------
 // THE BODY: units [ta, tb) of the launch (unit t = virtual slice t mod VS of run t / VS; at most
 // POCS_GMM_SUB of them, of at most two runs r0 and r0 + 1 whose parameters and culled tables are staged
@@ -401,8 +458,13 @@ __device__ __forceinline__ void gmm_cull_regions(const pocs_gmm_launch& a, gmm_s
 //   (sm.rgk[rb]: usually none, one scalar branch); per region the lanes whose sample exists, whose flag is 0 and which are in the
 //   region are picked by scalar ands of the masks and lane 0 adds the population count to the block's LDS counter of (run buffer,
 //   region).  The odd shard's unused twin does not count.
-template <int K, bool STORE, int TB, bool LONE_PRE = false, bool OC = false, bool CL = false, bool FPN = false, bool RG = false>
-__device__ __forceinline__ void gmm_units(const pocs_gmm_launch& a, gmm_smem<K, TB, OC, CL, FPN, RG>& sm, const int w, const int r0,
+//   SG (pocs_set_segment_checks, J > 1): behind the unchanged collision test of the samples themselves, where the run's second kept list
+//   is not empty (usually it is: one scalar branch), the J - 1 sub-poses on each sample's way in are tested on that list
+//   (pocs_pair_segment_masks, backwards along the run's applied control); lane 0 adds the population count of the lanes whose sample
+//   exists, whose own flag is 0 and some sub-pose of which touches to the block's LDS counter of the run buffer, and the sub-poses'
+//   masks are or-ed into the flags: everything behind is formed from those.  The odd shard's unused twin does not count.
+template <int K, bool STORE, int TB, bool LONE_PRE = false, bool OC = false, bool CL = false, bool FPN = false, bool RG = false, bool SG = false>
+__device__ __forceinline__ void gmm_units(const pocs_gmm_launch& a, gmm_smem<K, TB, OC, CL, FPN, RG, SG>& sm, const int w, const int r0,
                                           const int ta, const int tb, const double* zpre = nullptr, const int npre = 0) {
   const pocs_tables* const s_tab = &sm.tab;
   const int tid = threadIdx.x, lane = tid & 63;
@@ -438,6 +500,10 @@ __device__ __forceinline__ void gmm_units(const pocs_gmm_launch& a, gmm_smem<K, 
   [[maybe_unused]] const double* s_keep2 = nullptr;       // CL: the second kept list and its length
   [[maybe_unused]] int nkeep2 = 0;
   [[maybe_unused]] unsigned rgkeep = 0u;                  // RG: the regions in the run's reach, a bit each
+  [[maybe_unused]] const double* s_keeps = nullptr;       // SG: the second kept list, its length, J, the fractions, the applied control
+  [[maybe_unused]] int nkeeps = 0, sgJ = 1;
+  [[maybe_unused]] const double* s_sgf = nullptr;
+  [[maybe_unused]] double sg_u1 = 0.0, sg_u2 = 0.0;
   uint64_t seed = 0;
   double cumn[K > 1 ? K - 1 : 1];                   // cumulative component counts
   double *xr = nullptr, *yr = nullptr, *tr = nullptr;
@@ -540,6 +606,16 @@ __device__ __forceinline__ void gmm_units(const pocs_gmm_launch& a, gmm_smem<K, 
         });
       }
     }
+    if constexpr (SG) {
+      if (nkeeps != 0) {                                             // (scalar: at most waypoints of a plan nothing is near the way in)
+        unsigned long long sub[2];
+        pocs_pair_segment_masks(xs, ys, ts, -sg_u2, sg_u1, s_sgf, sgJ, 1, &fp, s_keeps, nkeeps, s_tab, vc, sub);
+        const unsigned long long lm = WHOLE ? ~0ull : __ballot(live), tm = WHOLE ? ~0ull : __ballot(two);
+        const unsigned n = (unsigned)__popcll(sub[0] & ~hits[0] & lm) + (unsigned)__popcll(sub[1] & ~hits[1] & tm);      // (scalar)
+        if (n != 0u && lane == 0) __hip_atomic_fetch_add(&sm.sgc[rb], n, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+        hits[0] |= sub[0]; hits[1] |= sub[1];
+      }
+    }
     if constexpr (POCS_TUNE_SKIP_MOMENTS) { POCS_TUNE_MOMENTS_ALT(); } else {
     // T1 sums over the collision-free samples of the component being accumulated:
     //   (x, y, t, x x, x y, x t, y y, y t, t t) with the products inside the fma; survivors by population count.
@@ -617,6 +693,11 @@ __device__ __forceinline__ void gmm_units(const pocs_gmm_launch& a, gmm_smem<K, 
       nkeep = __builtin_amdgcn_readfirstlane(sm.nkeep[rb]);
       if constexpr (CL) { s_keep2 = sm.keep2[rb]; nkeep2 = __builtin_amdgcn_readfirstlane(sm.nkeep2[rb]); }
       if constexpr (RG) rgkeep = (unsigned)__builtin_amdgcn_readfirstlane((int)sm.rgk[rb]);
+      if constexpr (SG) {
+        s_keeps = sm.keeps[rb]; s_sgf = sm.sgf[rb];
+        nkeeps = __builtin_amdgcn_readfirstlane(sm.nkeeps[rb]); sgJ = __builtin_amdgcn_readfirstlane(sm.sgJ[rb]);
+        sg_u1 = pocs_wave_uniform_f64(sm.sgu[rb][1]); sg_u2 = pocs_wave_uniform_f64(sm.sgu[rb][2]);
+      }
       seed = (uint64_t)uniform64((long long)sm.seed[rb]);         // scalar registers, provably
 #pragma unroll
       for (int q = 0; q < K - 1; ++q) cumn[q] = s_par[q * POCS_PARAM_STRIDE + 9];
@@ -667,8 +748,8 @@ __device__ __forceinline__ void gmm_units(const pocs_gmm_launch& a, gmm_smem<K, 
 // order -- whichever of them the unit has: slot if the component was the wave's first there, xtra if it
 // started inside the wave's share, +0 otherwise -- stored write-through to the run's partial rows.
 // Column 1 (collisions) stays 0: a component's collisions are what is left of its block (gmm_close_sums).
-template <int K, int TB, bool OC, bool CL, bool FPN, bool RG>
-__device__ __forceinline__ void gmm_emit_rows(const pocs_gmm_launch& a, gmm_smem<K, TB, OC, CL, FPN, RG>& sm, const int r0, const int ta, const int tb) {
+template <int K, int TB, bool OC, bool CL, bool FPN, bool RG, bool SG>
+__device__ __forceinline__ void gmm_emit_rows(const pocs_gmm_launch& a, gmm_smem<K, TB, OC, CL, FPN, RG, SG>& sm, const int r0, const int ta, const int tb) {
   constexpr int NC = K * POCS_NMOM, NW = TB / 64;
   for (int i = threadIdx.x; i < (tb - ta) * NC; i += TB) {
     const int tl = i / NC, c = i - tl * NC, k = c / POCS_NMOM, col = c - k * POCS_NMOM;
@@ -861,10 +942,20 @@ __device__ __forceinline__ void gmm_close_sums(const pocs_gmm_launch& a, const i
 // counts per kept region the collision-free samples in it (gmm_units); behind the units the nonzero counters leave with one integer
 // atomic each to reg_counts[run][waypoint][region], as clc does.  The collision test, the moment sums, the tickets and the closers
 // are what they are.  LDS: + 432 B (K = 8: 75 856 B against the twin's 75 424): two blocks per CU in every instantiation.
+//
+// SG (segment checks, pocs_set_segment_checks with J > 1; the kernels k_gmm_step_seg, k_gmm_step_risk_seg: ticket form, never LONE, TREE,
+// OC, WORLD, CL, FPN or RG): waves 2 and 3 build per run buffer the second kept list -- the records in reach of the run's whole way
+// in (gmm_cull_seg, which also stages J, the fractions and the run's applied control) -- beside waves 0 and 1; the body tests the
+// sub-poses of the samples where that list is not empty and ors their flags in (gmm_units); behind the units the nonzero counters
+// leave with one integer atomic each to seg_counts[run][waypoint], as clc does.  The samples' own test, the moment sums (formed from
+// the or-ed flags), the tickets and the closers are what they are.  LDS: + 8 KB for the second kept table, + 0.3 KB, and 24 instead of
+// 32 held units, as the clearance form: two blocks per CU in every instantiation.
 template <int K, bool STORE, int TB, bool LONE, bool RISK, bool TREE = false, bool OC = false, bool WORLD = false, bool CL = false, bool FPN = false,
-          bool RG = false>
+          bool RG = false, bool SG = false>
 __device__ __forceinline__ void gmm_step_block(const pocs_gmm_launch a) {      // (by value, as a kernel holds its argument)
-  typedef gmm_smem<K, TB, OC, CL, FPN, RG> smem_t;
+  typedef gmm_smem<K, TB, OC, CL, FPN, RG, SG> smem_t;
+  static_assert(!(SG && (LONE || TREE || OC || WORLD || CL || FPN || RG)), "segment checks: the ticket form of a batch or of plans on a small world, a single footprint box, no other counts");
+  static_assert(!SG || TB >= 256, "waves 2 and 3 build the second kept list");
   static_assert(!(RG && (LONE || TREE || OC || WORLD || CL || FPN)), "watched regions: the ticket form of a batch or of plans on a small world, no other counts");
   static_assert(!RG || TB >= 256, "waves 2 and 3 decide the regions in reach");
   static_assert(!(FPN && (LONE || TREE || OC || WORLD || CL)), "a compound footprint: the ticket form of a batch or of plans on a small world, no counts per box or level");
@@ -1037,6 +1128,10 @@ __device__ __forceinline__ void gmm_step_block(const pocs_gmm_launch a) {      /
       if (tid >= 128 && tid < 192) gmm_cull_regions(a, sm, 0, tid - 128, sm.par[0]);
       else if (tid >= 192 && tid < 256 && r1 > r0) gmm_cull_regions(a, sm, 1, tid - 192, sm.par[1]);
     }
+    if constexpr (SG) {
+      if (tid >= 128 && tid < 192) gmm_cull_seg(a, sm, 0, tid - 128, sm.par[0], r0);
+      else if (tid >= 192 && tid < 256 && r1 > r0) gmm_cull_seg(a, sm, 1, tid - 192, sm.par[1], r0 + 1);
+    }
     if constexpr (FPN) {
       if (tid < 64) gmm_cull_parts(a, sm, 0, tid, sm.par[0]);
       else if (tid < 128 && r1 > r0) gmm_cull_parts(a, sm, 1, tid - 64, sm.par[1]);
@@ -1050,7 +1145,7 @@ __device__ __forceinline__ void gmm_step_block(const pocs_gmm_launch a) {      /
   POCS_STAMP(0);
   for (int ta = t0; ta < t1; ta += SUB) {
     const int tb = (ta + SUB < t1) ? ta + SUB : t1;
-    gmm_units<K, STORE, TB, LONE, OC, CL, FPN, RG>(a, sm, w, r0, ta, tb, s_zpre, ta == t0 ? npre : 0);
+    gmm_units<K, STORE, TB, LONE, OC, CL, FPN, RG, SG>(a, sm, w, r0, ta, tb, s_zpre, ta == t0 ? npre : 0);
     POCS_STAMP(1);
     __syncthreads();
     POCS_STAMP(2);
@@ -1086,6 +1181,13 @@ __device__ __forceinline__ void gmm_step_block(const pocs_gmm_launch a) {      /
     if (tid < 8 && rb <= r1 - r0 && g < a.reg_G) {
       const unsigned n = sm.rgc[rb][g];
       if (n) atomicAdd(&a.reg_counts[((size_t)(r0 + rb) * a.W + wr) * POCS_MAX_REGIONS + g], (unsigned long long)n);
+    }
+  }
+  if constexpr (SG) {
+    // (as clc above: every wave's LDS additions lie in front of the barrier behind the last gmm_units)
+    if (tid < 2 && tid <= r1 - r0) {
+      const unsigned n = sm.sgc[tid];
+      if (n) atomicAdd(&a.seg_counts[(size_t)(r0 + tid) * a.W + wr], (unsigned long long)n);
     }
   }
   if (LONE) return;                                  // the rows leave through the kernel boundary; the next launch's heads add them
@@ -1231,6 +1333,16 @@ __global__ __launch_bounds__(TB, POCS_GMM_BLOCKS_PER_CU * TB / 256) void k_gmm_s
 template <int K, bool STORE, int TB>
 __global__ __launch_bounds__(TB, POCS_GMM_BLOCKS_PER_CU * TB / 256) void k_gmm_step_risk_regions(pocs_gmm_launch a) {
   gmm_step_block<K, STORE, TB, false, true, false, false, false, false, false, true>(a);
+}
+
+// The forms under segment checks (SG above): kernels of their own names again.
+template <int K, bool STORE, int TB>
+__global__ __launch_bounds__(TB, POCS_GMM_BLOCKS_PER_CU * TB / 256) void k_gmm_step_seg(pocs_gmm_launch a) {
+  gmm_step_block<K, STORE, TB, false, false, false, false, false, false, false, false, true>(a);
+}
+template <int K, bool STORE, int TB>
+__global__ __launch_bounds__(TB, POCS_GMM_BLOCKS_PER_CU * TB / 256) void k_gmm_step_risk_seg(pocs_gmm_launch a) {
+  gmm_step_block<K, STORE, TB, false, true, false, false, false, false, false, false, true>(a);
 }
 
 // The forms under a large collision world (WORLD above): kernels of their own names again.

@@ -131,7 +131,15 @@ __device__ __forceinline__ mc_run_start mc_start(const pocs_mc_launch& a) {
 // collided" is the hit counter the kernel holds anyway -- !hit in k_mc_init, old == 0 && !hit in the per-step kernel, which reads the
 // counter of a particle that does not collide only when the particle is in some region.  The collision test, the hit counters
 // and the other counts are what they are without the flag.
-enum { MC_PLAIN = 0, MC_COUNTS = 1, MC_STOP = 2, MC_BOXES = 4, MC_CLEAR = 8, MC_PARTS = 16, MC_REGIONS = 32 };
+//
+// MC_SEG (pocs_set_segment_checks with J > 1), a flag on top of MC_COUNTS or MC_STOP on the per-step kernel alone (waypoint 0 is the
+// initial cloud: k_mc_init is what it is), never with MC_BOXES, MC_CLEAR, MC_PARTS or MC_REGIONS: a particle touches at waypoint
+// s + 1 when its end pose (mc_move, unchanged) or one of the J - 1 sub-poses q_j = pocs_motion(p, {u[0], f_j u[1], 0.0}) on the way
+// there touches the world of waypoint s + 1.  The end pose is tested first and the sub-poses only for a particle whose end pose is
+// free: the OR needs nothing more, and seg_counts[run][s + 1] counts exactly that case -- the particles whose first touching
+// waypoint this is and whose end pose is free.  The sine and cosine of the drive direction are mc_move's own (mc_move_dir).  J and
+// the fractions are read from pocs_seg_dev in device memory (wave-uniform loads); hit counters and counts are formed from the flag.
+enum { MC_PLAIN = 0, MC_COUNTS = 1, MC_STOP = 2, MC_BOXES = 4, MC_CLEAR = 8, MC_PARTS = 16, MC_REGIONS = 32, MC_SEG = 64 };
 static_assert(POCS_MAX_OBSTACLES <= 64, "a particle's touched boxes are a 64-bit mask");
 
 // pocs_pose_collides with the touched boxes as a mask (the flag: mask != 0, as the plain form's).
@@ -310,6 +318,14 @@ __device__ __forceinline__ void mc_initial(const pocs_mc_launch& a, uint64_t see
 __device__ __forceinline__ void mc_move(const double x, const double y, const double t, const double u0, const double u1,
                                         const double u2, double& nx, double& ny, double& nt) {
   double sn, cs;
+  pocs_sincos(t + u0, &sn, &cs);
+  nx = fma(u1, cs, x);
+  ny = fma(u1, sn, y);
+  nt = pocs_wrap_angle(t + u0 + u2);
+}
+// MC_SEG: mc_move with the drive direction's sine and cosine handed out (the same operations: the same pose).
+__device__ __forceinline__ void mc_move_dir(const double x, const double y, const double t, const double u0, const double u1,
+                                            const double u2, double& nx, double& ny, double& nt, double& sn, double& cs) {
   pocs_sincos(t + u0, &sn, &cs);
   nx = fma(u1, cs, x);
   ny = fma(u1, sn, y);
@@ -507,6 +523,32 @@ __device__ __forceinline__ void mc_step_body(const pocs_mc_launch& a) {
   const double u0 = u[0], u1 = u[1], u2 = u[2];
   unsigned first = 0;                              // this thread's particles whose first collision is this waypoint (unused: MC_PLAIN)
   const long long stride = (long long)gridDim.x * POCS_BLOCK;
+  if constexpr ((MODE & MC_SEG) != 0) {
+    static_assert((MODE & MC_SEG) == 0 || ((MODE & (MC_BOXES | MC_CLEAR | MC_PARTS | MC_REGIONS)) == 0 && (MODE & 3) != MC_PLAIN),
+                  "segment checks: on top of MC_COUNTS or MC_STOP alone");
+    const double* const sf = a.seg->f;             // (wave-uniform: J and the fractions come through the scalar cache)
+    const int J = a.seg->J;
+    unsigned between = 0;                          // ... whose first touching waypoint this is and whose end pose is free
+    for (long long i = (long long)blockIdx.x * POCS_BLOCK + threadIdx.x; i < a.count; i += stride) {
+      const double x = mc_load<NT>(v.x + i), y = mc_load<NT>(v.y + i), t = mc_load<NT>(v.th + i);
+      double nx, ny, nt, sn, cs;
+      mc_move_dir(x, y, t, u0, u1, u2, nx, ny, nt, sn, cs);
+      mc_store<NT>(nx, v.x + i); mc_store<NT>(ny, v.y + i); mc_store<NT>(nt, v.th + i);
+      const bool end = pocs_pose_collides(nx, ny, nt, &wd.fp, wd.obs, wd.M, wd.tab);
+      bool sub = false;
+      if (!end) sub = pocs_segment_touched_dir(x, y, t + u0, sn, cs, u1, sf, J, 0, &wd.fp, wd.obs, wd.M, wd.tab) != 0u;
+      if (end || sub) {
+        const uint32_t old = v.hits[i];
+        v.hits[i] = old + 1u;
+        first += old == 0u ? 1u : 0u;
+        between += (old == 0u && sub) ? 1u : 0u;
+      }
+    }
+    mc_block_add(first, a.wp_counts + (size_t)blockIdx.y * (size_t)a.W + (size_t)a.step + 1);
+    __syncthreads();                                 // (mc_block_add's scratch is read by thread 0 of the call above)
+    mc_block_add(between, a.seg_counts + (size_t)blockIdx.y * (size_t)a.W + (size_t)a.step + 1);
+    return;
+  }
   for (long long i = (long long)blockIdx.x * POCS_BLOCK + threadIdx.x; i < a.count; i += stride) {
     const double x = mc_load<NT>(v.x + i), y = mc_load<NT>(v.y + i), t = mc_load<NT>(v.th + i);
     double nx, ny, nt;

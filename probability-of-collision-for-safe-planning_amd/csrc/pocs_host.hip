@@ -106,7 +106,7 @@ void prepare_parts(const pocs_footprint* parts, int F, const double* boxes, int 
 // the exchange and a bound moments buffer) are the calls they are with L = 0; the step API never asks.
 bool clearance_applied(const pocs_ctx* c) {
   using namespace pocs_modes;
-  return c->clr_L > 0 && !parts_applied(c) && !in_mode(c, kTree | kLargeWorld | kObsCounts | kShard | kMoments);
+  return c->clr_L > 0 && !parts_applied(c) && !seg_applied(c) && !in_mode(c, kTree | kLargeWorld | kObsCounts | kShard | kMoments);
 }
 
 // Watched regions: the record the kernels read (pocs_regions_dev) -- region g prepared as upload_world prepares an obstacle, for
@@ -130,7 +130,16 @@ void prepare_regions(const pocs_footprint& fp, const double* boxes, const int* k
 // L > 0 are the calls they are with G = 0; the step API never asks.
 bool regions_applied(const pocs_ctx* c) {
   using namespace pocs_modes;
-  return c->reg_G > 0 && c->clr_L == 0 && !parts_applied(c) && !in_mode(c, kTree | kLargeWorld | kObsCounts | kShard | kMoments);
+  return c->reg_G > 0 && c->clr_L == 0 && !parts_applied(c) && !seg_applied(c) && !in_mode(c, kTree | kLargeWorld | kObsCounts | kShard | kMoments);
+}
+
+// Segment checks (J > 1) as the kernels read them (pocs_seg_dev): J and the fractions f_j = j / J.  (pocs_probe_device_segment
+// prepares its own record through this function too.)  Clearance levels and watched regions are not applied while J > 1 (above):
+// the call is the J > 1 call without them.
+void prepare_segment(int J, pocs_seg_dev* out) {
+  memset(out, 0, sizeof *out);
+  out->J = J;
+  pocs_segment_fractions(J, out->f);
 }
 
 int upload_world(pocs_ctx* c) {                // tables + the collision world: one record (obstacle records, footprint) per step of the schedule
@@ -163,6 +172,12 @@ int upload_world(pocs_ctx* c) {                // tables + the collision world: 
       for (size_t s = 0; s < S; ++s) prepare_clearance(c->fp, c->clr_d, c->clr_L, c->boxes.data() + s * (size_t)M * 5, M, &clr[s]);
       if (int r = ensure(c, c->d_clr, S * sizeof(pocs_clear_dev))) return r;
       HIPCHK(c, hipMemcpy(c->d_clr.p, clr.data(), S * sizeof(pocs_clear_dev), hipMemcpyHostToDevice));
+    }
+    if (seg_applied(c)) {                            // the segment checks' record, next to the world
+      pocs_seg_dev sg;
+      prepare_segment(c->seg_J, &sg);
+      if (int r = ensure(c, c->d_seg, sizeof sg)) return r;
+      HIPCHK(c, hipMemcpy(c->d_seg.p, &sg, sizeof sg, hipMemcpyHostToDevice));
     }
     if (c->reg_G > 0 && !parts_applied(c)) {         // the watched regions, next to the world: TOUCH regions follow the footprint
       pocs_regions_dev reg;
@@ -375,6 +390,29 @@ int read_regions(pocs_ctx* c, Kind kind, long long n) {
   return POCS_OK;
 }
 
+// Segment checks: d_segct holds the segment counts [batch][W] u64, zeroed by the first launch of every call under J > 1 (a kernel,
+// inside the replayed graph, as d_regct) and read back behind the call (read_segment).  J = 1: no buffer, no launch, and every
+// launch is the kernel it has always been.
+size_t seg_count_words(const pocs_ctx* c) { return (size_t)c->batch * (size_t)(c->W > 0 ? c->W : 1); }
+int ensure_segment(pocs_ctx* c) {
+  return seg_applied(c) ? ensure(c, c->d_segct, seg_count_words(c) * sizeof(unsigned long long)) : POCS_OK;
+}
+// the state a call leaves for pocs_get_segment_counts while it runs (or fails) ...
+void open_segment(pocs_ctx* c) {
+  Results& r = c->res;
+  r.sg_state = seg_applied(c) ? Results::SgNotServed : Results::SgOff;
+  r.sg_kind = Kind::None; r.sg_J = c->seg_J; r.sg_W = 0; r.sg_counts.clear();
+}
+// ... and behind its results: the table in slot order, as the device holds it (the stream is idle)
+int read_segment(pocs_ctx* c, Kind kind) {
+  if (!seg_applied(c)) return POCS_OK;
+  Results& r = c->res;
+  r.sg_counts.assign(seg_count_words(c), 0ull);
+  HIPCHK(c, hipMemcpy(r.sg_counts.data(), c->d_segct.p, r.sg_counts.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+  r.sg_state = Results::SgServed; r.sg_kind = kind; r.sg_J = c->seg_J; r.sg_W = c->W > 0 ? c->W : 1;
+  return POCS_OK;
+}
+
 // The call's synchronisation words (SyncLayout, pocs_ctx.hpp); the copy behind the launches starts at the give-up word and,
 // under a risk bound, runs on through the pad and the stop words.
 SyncLayout sync_layout(const pocs_ctx* c) {
@@ -420,6 +458,7 @@ int gmm_prepare(pocs_ctx* c) {
   if (int r = ensure_obs_counts(c)) return r;
   if (int r = ensure_clearance(c)) return r;
   if (int r = ensure_regions(c)) return r;
+  if (int r = ensure_segment(c)) return r;
   if (large_world(c)) {
     if (int r = ensure(c, c->d_kept, R * POCS_MAX_OBSTACLES * POCS_OBS_STRIDE * sizeof(double))) return r;
     if (int r = ensure(c, c->d_keptidx, R * POCS_MAX_OBSTACLES * sizeof(int))) return r;
@@ -554,8 +593,8 @@ int enqueue_advance(Issuer is, int w) {
 // (Under a large world the cull of waypoint w reads param[w] ahead of the sampling launch; the lone form builds param[w] in its own
 // heads, so a call of one run takes the ticket form there: the same bits.)
 // (Under clearance levels and watched regions too: the counting forms exist as the ticket form only.)
-// (And under a compound footprint: the parts form exists as the ticket form only.)
-bool lone_call(const pocs_ctx* c) { return c->opt_lone && !large_world(c) && !clearance_applied(c) && !regions_applied(c) && !parts_applied(c) && c->batch == 1 && !c->tree.n && !c->ext_moments && !(c->xchg_connected && c->shard_first >= 0) && !risk_active(c); }
+// (And under a compound footprint: the parts form exists as the ticket form only.  And under segment checks: the same.)
+bool lone_call(const pocs_ctx* c) { return c->opt_lone && !large_world(c) && !clearance_applied(c) && !regions_applied(c) && !parts_applied(c) && !seg_applied(c) && c->batch == 1 && !c->tree.n && !c->ext_moments && !(c->xchg_connected && c->shard_first >= 0) && !risk_active(c); }
 void set_risk(pocs_ctx* c, pocs_gmm_launch* a) {      // under a risk bound the launch is k_gmm_step_risk (whole calls of plans or on a tree only)
   a->risk = 1;
   a->stop = a->sync + c->sync.stop;
@@ -655,6 +694,7 @@ int enqueue_gmm_all(Issuer is, long long first, long long count, bool prof) {
   if (int r = enqueue_obs_counts_reset(is)) return r;    // (ahead of the fork: every sub-batch's launches lie behind it)
   if (int r = enqueue_clearance_reset(is)) return r;
   if (regions_applied(c)) if (int r = is.launch(pocs_launch_zero_counts, 0, (unsigned long long*)c->d_regct.p, region_count_words(c))) return r;
+  if (seg_applied(c)) if (int r = is.launch(pocs_launch_zero_counts, 0, (unsigned long long*)c->d_segct.p, seg_count_words(c))) return r;
   if (int r = enqueue_advance(is, 0)) return r;
   if (prof) if (int r = is.mark(c->ev_seq[0])) return r;
   for (int g = 1; g < G; ++g) if (int r = is.order(0, g, c->ev_fork, g == 1)) return r;
@@ -663,6 +703,9 @@ int enqueue_gmm_all(Issuer is, long long first, long long count, bool prof) {
   if (parts_applied(c)) { base.parts = (const pocs_parts_dev*)c->d_parts.p; base.parts_F = c->fp_F; }
   if (clearance_applied(c)) {                        // (the whole call only: the step API's launches never carry the levels)
     base.clr = clear_at(c, 0); base.clr_counts = (unsigned long long*)c->d_clrct.p; base.clr_L = c->clr_L;
+  }
+  if (seg_applied(c)) {                              // (the whole call only: the step API is refused under J > 1)
+    base.seg = (const pocs_seg_dev*)c->d_seg.p; base.seg_counts = (unsigned long long*)c->d_segct.p;
   }
   if (regions_applied(c)) {                          // (the whole call only, as the levels)
     base.regions = (const pocs_regions_dev*)c->d_reg.p; base.reg_counts = (unsigned long long*)c->d_regct.p; base.reg_G = c->reg_G;
@@ -880,6 +923,7 @@ int run_gmm_full(pocs_ctx* c, double* probability) {
   c->res.oc_kind = Kind::None;                                  // (the per-obstacle table is rewritten from here on; noted again behind the combine)
   open_clearance(c);
   open_regions(c);
+  open_segment(c);
   c->reach.clear(); c->reach_len.clear(); c->reach_R = 0; c->reach_W = 0;      // (pocs_get_world_reach covers the last GMM call)
   if (int r = gmm_prepare(c)) return r;
   long long first, count;
@@ -920,6 +964,7 @@ int run_gmm_full(pocs_ctx* c, double* probability) {
   note_obs_counts(c, Kind::Gmm);
   if (int r = read_clearance(c, Kind::Gmm, c->num_gmm)) return r;
   if (int r = read_regions(c, Kind::Gmm, c->num_gmm)) return r;
+  if (int r = read_segment(c, Kind::Gmm)) return r;
   c->res.last_gmm_count = count;
   c->res.last_gmm_wp = c->W - 1;
   lap("combined");
@@ -941,13 +986,14 @@ int mc_shard(pocs_ctx* c, long long* first, long long* count) {
 // call, or any MC call under POCS_OPT_MC_WAYPOINT_COUNTS, counts the first collisions per waypoint.  Both off: the launches,
 // the memset and the copies of an MC call are what they have always been.
 bool mc_stop_active(const pocs_ctx* c) { return c->opt_mc_rb && risk_active(c) && !c->tree.n; }     // (an MC call on a tree ignores the bound)
-bool mc_counts_active(const pocs_ctx* c) { return c->opt_mc_wp || c->opt_obs_counts || mc_stop_active(c); }      // (the per-box counts split the per-waypoint ones)
+bool mc_counts_active(const pocs_ctx* c) { return c->opt_mc_wp || c->opt_obs_counts || seg_applied(c) || mc_stop_active(c); }      // (the per-box counts split the per-waypoint ones; an MC call under segment checks counts as under POCS_OPT_MC_WAYPOINT_COUNTS)
 // The fused kernel carries a particle through all its steps and meets no other block on the way: a call that stops on a count
 // takes the per-step form.
 // So does a call that counts clearance levels: the levels live in the per-step kernels (MC_CLEAR).
 // And a call under a compound footprint: the parts live in the per-step kernels too (MC_PARTS).
 // And a call that counts watched regions: they live in the per-step kernels as well (MC_REGIONS).
-bool mc_fused_form(const pocs_ctx* c) { return c->opt_fused && !mc_stop_active(c) && !clearance_applied(c) && !parts_applied(c) && !regions_applied(c); }
+// And a call under segment checks: the sub-poses live in the per-step kernels (MC_SEG).
+bool mc_fused_form(const pocs_ctx* c) { return c->opt_fused && !mc_stop_active(c) && !clearance_applied(c) && !parts_applied(c) && !regions_applied(c) && !seg_applied(c); }
 // d_total, u64 words: [R] collided particles per run | counts active: [R][W] first collisions | [R] u32 stop words
 size_t mc_total_words(const pocs_ctx* c) {
   const size_t R = (size_t)c->batch, W = (size_t)c->W;
@@ -1002,6 +1048,10 @@ int enqueue_mc_all(Issuer is, long long first, long long count, bool prof) {
   if (regions_applied(c)) {
     a.regions = (const pocs_regions_dev*)c->d_reg.p; a.reg_counts = (unsigned long long*)c->d_regct.p; a.reg_G = c->reg_G;
     if (int r = is.launch(pocs_launch_zero_counts, 0, a.reg_counts, region_count_words(c))) return r;
+  }
+  if (seg_applied(c)) {
+    a.seg = (const pocs_seg_dev*)c->d_seg.p; a.seg_counts = (unsigned long long*)c->d_segct.p;
+    if (int r = is.launch(pocs_launch_zero_counts, 0, a.seg_counts, seg_count_words(c))) return r;
   }
   if (c->plans.n) {
     a.run_plan = (const double*)c->d_runplan.p;      // every run its own start mean and steps
@@ -1140,6 +1190,7 @@ int mc_prepare(pocs_ctx* c, size_t runs, size_t chain_rows, size_t elems, size_t
   if (int r = ensure_clearance(c)) return r;
   if (clearance_applied(c)) if (int r = ensure(c, c->d_clrlv, elems)) return r;
   if (int r = ensure_regions(c)) return r;
+  if (int r = ensure_segment(c)) return r;
   if (int r = ensure_pin(c)) return r;
   return stage_and_upload_runs(c, 1, Kind::Mc);
 }
@@ -1198,6 +1249,7 @@ int run_mc_local(pocs_ctx* c) {
   c->res.oc_kind = Kind::None;
   open_clearance(c);
   open_regions(c);
+  open_segment(c);
   if (int r = check_common(c)) return r;
   if (c->num_particles < 1) return fail(c, POCS_E_STATE, "setNumParticles missing");
   if (int r = upload_static(c)) return r;
@@ -1233,7 +1285,8 @@ int run_mc_local(pocs_ctx* c) {
     if (int r = mc_read_waypoint_counts(c, tot)) { reset_results(c); return r; }
   note_obs_counts(c, Kind::Mc);
   if (int r = read_clearance(c, Kind::Mc, count)) return r;
-  return read_regions(c, Kind::Mc, count);
+  if (int r = read_regions(c, Kind::Mc, count)) return r;
+  return read_segment(c, Kind::Mc);
 }
 
 }  // namespace pocs_rt
@@ -1272,6 +1325,7 @@ int pocs_gmm_begin(pocs_ctx* c) {
   c->res.oc_kind = Kind::None;                                 // (the table is this sequence's from here on; served once pocs_gmm_end has closed it)
   open_clearance(c);                                           // (the step API: the levels are not applied)
   open_regions(c);                                             // (nor the watched regions)
+  open_segment(c);                                             // (segment checks refuse the sequence: J is 1 here)
   c->xchg_calls += 1;
   c->gmm_open = true;
   c->res.last_gmm_wp = -1;

@@ -78,6 +78,15 @@ struct pocs_regions_dev {
 };
 #define POCS_REGIONS_HEAD (POCS_MAX_REGIONS * (POCS_OBS_STRIDE + 4))   // the doubles a kernel's head stages: rec | fp
 
+// Segment checks (pocs_set_segment_checks, J > 1) as the kernels see them, in HBM beside the collision world: J and the fractions
+// f_j = j / J (pocs_segment_fractions) live HERE, not in launch arguments -- a call's launches carry the address, so another J > 1
+// replays the cached graph.  The controls come from the run's chain record, which is on the device anyway.
+struct pocs_seg_dev {
+  double f[POCS_MAX_SEGMENT_CHECKS];
+  int J;                         // 2 .. POCS_MAX_SEGMENT_CHECKS
+  int pad;
+};
+
 struct pocs_run_header {         // per-run scalars read by every kernel (so a captured graph stays valid)
   uint64_t seed;
   uint64_t pad;                  // sharded whole calls: the context's count of exchange sequences (pocs_gmm_launch::xchg_epoch_from_header)
@@ -191,6 +200,12 @@ struct pocs_gmm_launch {
   unsigned long long* reg_counts; // [nruns][W][POCS_MAX_REGIONS]; zeroed by pocs_launch_zero_counts at the head of the call's launches
   int reg_G;                     // 1 .. POCS_MAX_REGIONS
   int reg_pad;
+  // segment checks (pocs_set_segment_checks with J > 1; behind everything else again): non-null = the launch is the kernel's _seg form
+  // (ticket form, with or without the risk bound; never LONE, TREE, OC, WORLD, CL, parts or regions): a sample drawn at waypoint w >= 1
+  // also touches when one of its J - 1 sub-poses on the way in does -- backwards along the applied control of step w - 1, chain record
+  // [0..2] of the run -- and the samples whose own pose is free and some sub-pose touches are counted
+  const pocs_seg_dev* seg;
+  unsigned long long* seg_counts; // [nruns][W]; zeroed by pocs_launch_zero_counts at the head of the call's launches
 };
 #define POCS_MAX_WORLD_RECORDS 4096   // = POCS_MAX_WORLD_BOXES (include/pocs.h; pocs_ctx.hpp checks)
 #define POCS_CULL_BLOCK 256           // k_world_cull
@@ -263,6 +278,12 @@ struct pocs_mc_launch {               // blockIdx.y = run of the batch, like poc
   unsigned long long* reg_counts;      // [nruns][W][POCS_MAX_REGIONS]; zeroed inside the graph like obs_counts
   int reg_G;                           // 1 .. POCS_MAX_REGIONS
   int reg_pad;
+  // segment checks (pocs_set_segment_checks with J > 1; behind everything else again): non-null = the MC_SEG forms of
+  // k_mc_step_counts (per-step launches only, wp_mode 1 or 2; never with a large world, per-box counts, levels, parts or regions): a
+  // particle also touches at waypoint step + 1 when one of its J - 1 sub-poses on the way there does, and the particles whose first
+  // touching waypoint this is and whose end pose is free are counted
+  const pocs_seg_dev* seg;
+  unsigned long long* seg_counts;      // [nruns][W]; zeroed inside the graph like obs_counts
 };
 
 
@@ -293,6 +314,12 @@ hipError_t pocs_launch_probe_parts(const pocs_env_dev* env, const pocs_parts_dev
 // the pair form ever disagree with it)
 hipError_t pocs_launch_probe_regions(const pocs_regions_dev* regions, int G, const pocs_tables* tables, int n,
                                      const double* x, const double* y, const double* th, int* mask_out, hipStream_t s);
+// one block; poses n x (x, y, th) by component; env: records of M boxes and the footprint; seg: J and the fractions; u: the control;
+// backward 0: the MC form from the start pose, 1: the GMM form from the sample.  mask_out[i]: bit j (1 <= j < J) = sub-pose j touches,
+// bit J = the end pose (mc_move's, or the sample itself) touches, bit 16 should the pair form ever disagree with the single-pose form
+hipError_t pocs_launch_probe_segment(const pocs_env_dev* env, const pocs_seg_dev* seg, const pocs_tables* tables, double u0, double u1,
+                                     double u2, int backward, int n, const double* x, const double* y, const double* th, int* mask_out,
+                                     hipStream_t s);
 hipError_t pocs_launch_mc_init(int nblk, const pocs_mc_launch& a, hipStream_t s);
 hipError_t pocs_launch_mc_step(int nblk, const pocs_mc_launch& a, hipStream_t s);
 hipError_t pocs_launch_mc_fused(int nblk, const pocs_mc_launch& a, hipStream_t s);

@@ -54,6 +54,18 @@ hipError_t with_K(const int K, F f) {
 hipError_t pocs_launch_gmm_step(int K, const pocs_gmm_launch& a, hipStream_t s) {
   return with_K(K, [&](auto k) {
     constexpr int KK = decltype(k)::value, TB = POCS_GMM_BLOCK_OF(KK);
+    if (a.seg) {                                       // segment checks: the ticket forms that also test the sub-poses on the way in
+      if (a.lone || a.obs_counts || a.world || a.tree_parent || a.exchange_in_tail || a.clr || a.parts || a.regions || !a.seg_counts || !a.chain ||
+          a.M > POCS_MAX_OBSTACLES || (a.risk && (!a.stop || !a.surv)))
+        return hipErrorInvalidValue;
+      if (a.risk) {
+        if (a.store) hipLaunchKernelGGL((k_gmm_step_risk_seg<KK, true, TB>), dim3(a.blocks), dim3(TB), 0, s, a);
+        else         hipLaunchKernelGGL((k_gmm_step_risk_seg<KK, false, TB>), dim3(a.blocks), dim3(TB), 0, s, a);
+      } else {
+        if (a.store) hipLaunchKernelGGL((k_gmm_step_seg<KK, true, TB>), dim3(a.blocks), dim3(TB), 0, s, a);
+        else         hipLaunchKernelGGL((k_gmm_step_seg<KK, false, TB>), dim3(a.blocks), dim3(TB), 0, s, a);
+      }
+    } else
     if (a.parts) {                                     // a compound footprint: the ticket forms that test every part
       if (a.lone || a.obs_counts || a.world || a.tree_parent || a.exchange_in_tail || a.clr || a.parts_F < 2 || a.parts_F > POCS_MAX_FOOTPRINT_PARTS ||
           a.M > POCS_MAX_OBSTACLES || (a.risk && (!a.stop || !a.surv)))
@@ -227,6 +239,18 @@ hipError_t pocs_launch_mc_init(int nblk, const pocs_mc_launch& a, hipStream_t s)
 hipError_t pocs_launch_mc_step(int nblk, const pocs_mc_launch& a, hipStream_t s) {
   const dim3 grid(nblk, a.nruns), block(POCS_BLOCK);
   if ((a.wp_mode != 0 && !a.wp_counts) || (a.obs_counts && !a.wp_mode)) return hipErrorInvalidValue;
+  if (a.seg) {                                        // segment checks: the MC_SEG forms of the two counting modes
+    if (a.world || a.obs_counts || a.clr || a.parts || a.regions || !a.seg_counts || a.wp_mode == 0 || a.step < 0 || a.step + 1 >= a.W ||
+        (a.wp_mode == 2 && (!a.wp_stop || a.wp_n < 1)))
+      return hipErrorInvalidValue;
+    if (a.wp_mode == 2) {
+      if (a.nontemporal) hipLaunchKernelGGL((k_mc_step_counts<true, MC_STOP | MC_SEG>), grid, block, 0, s, a);
+      else               hipLaunchKernelGGL((k_mc_step_counts<false, MC_STOP | MC_SEG>), grid, block, 0, s, a);
+    } else {
+      if (a.nontemporal) hipLaunchKernelGGL((k_mc_step_counts<true, MC_COUNTS | MC_SEG>), grid, block, 0, s, a);
+      else               hipLaunchKernelGGL((k_mc_step_counts<false, MC_COUNTS | MC_SEG>), grid, block, 0, s, a);
+    }
+  } else
   if (a.parts) {                                      // a compound footprint: the MC_PARTS forms of the three modes
     if (a.world || a.obs_counts || a.clr || a.parts_F < 2 || a.parts_F > POCS_MAX_FOOTPRINT_PARTS || a.step < 0 || a.step + 1 >= a.W ||
         (a.wp_mode == 2 && (!a.wp_stop || a.wp_n < 1)))
@@ -312,6 +336,7 @@ hipError_t pocs_launch_mc_fused(int nblk, const pocs_mc_launch& a, hipStream_t s
   if (a.clr) return hipErrorInvalidValue;             // (clearance levels: the per-step form)
   if (a.parts) return hipErrorInvalidValue;           // (a compound footprint: the per-step form)
   if (a.regions) return hipErrorInvalidValue;         // (watched regions: the per-step form)
+  if (a.seg) return hipErrorInvalidValue;             // (segment checks: the per-step form)
   if (a.world) return hipErrorInvalidValue;           // (a large world is not staged: no fused form)
   if (a.obs_counts) {
     if (a.env_steps > 1) hipLaunchKernelGGL(k_mc_fused_sched<MC_COUNTS | MC_BOXES>, dim3(nblk, a.nruns), dim3(POCS_BLOCK), 0, s, a);
@@ -585,6 +610,68 @@ hipError_t pocs_launch_probe_regions(const pocs_regions_dev* regions, int G, con
                                      const double* x, const double* y, const double* th, int* mask_out, hipStream_t s) {
   if (!regions || !tables || n < 1 || G < 0 || G > POCS_MAX_REGIONS || !x || !y || !th || !mask_out) return hipErrorInvalidValue;
   hipLaunchKernelGGL(k_probe_regions, dim3(1), dim3(POCS_BLOCK), 0, s, regions, G, tables, n, x, y, th, mask_out);
+  return hipGetLastError();
+}
+// The segment checks' sub-poses on poses, a footprint, a world and a control the caller picks (pocs_probe_device_segment: a test hook
+// beside k_probe_parts): ONE block stages the tables and the records as the kernels' heads do and asks, per pose, the functions the
+// kernels ask.  backward 0, the MC form: the pose is a particle at the segment's start, the end pose is mc_move's (bit J: it touches,
+// by pocs_pose_collides), the sub-poses pocs_segment_touched_dir with mc_move_dir's sine and cosine, as mc_step_body calls it.
+// backward 1, the GMM form: the pose is a sample at the segment's end (bit J: it touches), the sub-poses pocs_segment_touched.  And
+// both ways pocs_pair_segment_masks as k_gmm_step's segment form calls it, pose 2 p with pose 2 p + 1 (an odd last pose with itself):
+// bit 16 is set in a pose's answer should the two forms ever disagree.
+__global__ __launch_bounds__(POCS_BLOCK) void k_probe_segment(const pocs_env_dev* __restrict__ env, const pocs_seg_dev* __restrict__ seg,
+                                                              const pocs_tables* __restrict__ tables, double u0, double u1, double u2, int backward, int n,
+                                                              const double* __restrict__ x, const double* __restrict__ y, const double* __restrict__ th,
+                                                              int* __restrict__ out) {
+  __shared__ pocs_tables s_tab;
+  __shared__ __attribute__((aligned(16))) double s_obs[POCS_MAX_OBSTACLES * POCS_OBS_STRIDE];
+  __shared__ double s_f[POCS_MAX_SEGMENT_CHECKS];
+  stage_tables(tables, &s_tab);
+  for (int j = threadIdx.x; j < POCS_MAX_OBSTACLES * POCS_OBS_STRIDE; j += POCS_BLOCK) s_obs[j] = env->obs[j];
+  if (threadIdx.x < POCS_MAX_SEGMENT_CHECKS) s_f[threadIdx.x] = seg->f[threadIdx.x];
+  __syncthreads();
+  const int M = env->M, J = seg->J;
+  const pocs_footprint fp = env->fp;
+  POCS_VCONST(vc_);
+  const double a0 = backward ? -u2 : u0;
+  const int npairs = (n + 1) / 2;
+  // (every lane of a wave makes every trip: the pair form ballots)
+  for (int p0 = (int)threadIdx.x - (int)(threadIdx.x & 63); p0 < npairs; p0 += POCS_BLOCK) {
+    const int p = p0 + (int)(threadIdx.x & 63);
+    const bool live = p < npairs;
+    const int i0 = live ? 2 * p : 0, i1 = live && i0 + 1 < n ? i0 + 1 : i0;
+    const double xs[2] = {x[i0], x[i1]}, ys[2] = {y[i0], y[i1]}, ts[2] = {th[i0], th[i1]};
+    unsigned single[2], pair[2] = {0u, 0u};
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+      if (backward) {
+        single[h] = pocs_segment_touched(xs[h], ys[h], ts[h], a0, u1, s_f, J, 1, &fp, s_obs, M, &s_tab);
+        if (pocs_pose_collides(xs[h], ys[h], ts[h], &fp, s_obs, M, &s_tab)) single[h] |= 1u << J;
+      } else {
+        double nx, ny, nt, sn, cs;
+        mc_move_dir(xs[h], ys[h], ts[h], u0, u1, u2, nx, ny, nt, sn, cs);
+        single[h] = pocs_segment_touched_dir(xs[h], ys[h], ts[h] + u0, sn, cs, u1, s_f, J, 0, &fp, s_obs, M, &s_tab);
+        if (pocs_pose_collides(nx, ny, nt, &fp, s_obs, M, &s_tab)) single[h] |= 1u << J;
+      }
+    }
+    unsigned long long all[2];
+    pocs_pair_segment_masks(xs, ys, ts, a0, u1, s_f, J, backward, &fp, s_obs, M, &s_tab, &vc_, all, [&](const int j, const unsigned long long m0, const unsigned long long m1) {
+      if (__builtin_amdgcn_inverse_ballot_w64(m0)) pair[0] |= 1u << j;
+      if (__builtin_amdgcn_inverse_ballot_w64(m1)) pair[1] |= 1u << j;
+    });
+    const bool any0 = __builtin_amdgcn_inverse_ballot_w64(all[0]), any1 = __builtin_amdgcn_inverse_ballot_w64(all[1]);
+    const unsigned subs = (1u << J) - 1u;
+    if (live) {
+      out[i0] = (int)(single[0] | ((pair[0] != (single[0] & subs) || any0 != ((single[0] & subs) != 0u) || (i1 == i0 && single[1] != single[0])) ? 65536u : 0u));
+      if (i1 != i0) out[i1] = (int)(single[1] | ((pair[1] != (single[1] & subs) || any1 != ((single[1] & subs) != 0u)) ? 65536u : 0u));
+    }
+  }
+}
+hipError_t pocs_launch_probe_segment(const pocs_env_dev* env, const pocs_seg_dev* seg, const pocs_tables* tables, double u0, double u1,
+                                     double u2, int backward, int n, const double* x, const double* y, const double* th, int* mask_out,
+                                     hipStream_t s) {
+  if (!env || !seg || !tables || n < 1 || !x || !y || !th || !mask_out) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(k_probe_segment, dim3(1), dim3(POCS_BLOCK), 0, s, env, seg, tables, u0, u1, u2, backward ? 1 : 0, n, x, y, th, mask_out);
   return hipGetLastError();
 }
 hipError_t pocs_launch_fill(void* dst, long long bytes, hipStream_t s) {

@@ -81,6 +81,12 @@ static const Row kRows[] = {
 constexpr unsigned kPartsExcluded = kTree | kShard | kXchgCreated | kXchgConnected | kMoments | kLargeWorld | kObsCounts | kSequence | kProbe;
 static const char* const kPartsClause = "a compound footprint is served by whole calls on one GPU over worlds of at most 64 boxes, without per-box counts";
 
+// Segment checks (pocs_set_segment_checks with J > 1) are no mode of the table either, for the same reason: they change results, so
+// what they are not built for is refused in both directions, as under a compound footprint -- and a compound footprint itself, which
+// is no bit of a mode word, is asked about beside this mask (seg_refuse, pocs_ctx.hpp; the two setters).
+constexpr unsigned kSegExcluded = kTree | kShard | kXchgCreated | kXchgConnected | kMoments | kLargeWorld | kObsCounts | kSequence;
+static const char* const kSegClause = "segment checks are served by whole calls on one GPU over worlds of at most 64 boxes, with a single footprint box and without per-box counts";
+
 // May a context whose active modes are `active` enter `enter`?  `among`: the modes asked about now -- a setter whose argument
 // checks stand between two of its combination checks asks in stages, so that a call with two faults keeps its code.
 struct Refusal { int code; Mode by; const char* clause; };

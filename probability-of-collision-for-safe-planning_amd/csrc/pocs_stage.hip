@@ -116,7 +116,7 @@ PinLayout pin_layout(const pocs_ctx* c) {
   p.moments = p.runplan + (c->plans.n ? 4 * R : 0);
   p.total = p.moments + W * R * K * POCS_NMOM;
   p.end = p.total + R + 2 + (R + 4) / 2 + 1;   // one u64 per run: MC totals; the call's give-up word and -- under a risk bound -- the R stop words behind it
-  if (c->opt_mc_wp || c->opt_mc_rb || c->opt_obs_counts) p.end += R * W + (R + 1) / 2;      // (mc_counts_active: the per-box counts bring the per-waypoint ones along)
+  if (c->opt_mc_wp || c->opt_mc_rb || c->opt_obs_counts || seg_applied(c)) p.end += R * W + (R + 1) / 2;      // (mc_counts_active: the per-box counts bring the per-waypoint ones along)
   if (c->tree.n) p.end += R;                          // an MC call on a tree: [T] collided at or before the node, [T] first collisions   // MC calls with first collisions per waypoint: behind the totals, [R][W] u64 and the R stop words
   return p;
 }
