@@ -611,6 +611,15 @@ int pocs_probe_device_math(pocs_ctx* ctx, int n, const uint32_t* radius_words, c
    and sin / cos of headings[i] as the footprint test evaluates them -- through the same inline functions, tables and pinned
    constants as k_gmm_step.  A free-running launch meets a given word once in 2^32 draws; this puts the edge words (0, the
    cells' boundaries, 2^32 - 1, a heading on a sector's tie) in front of the oracle directly (tests/test_gpu_parity.py). */
+int pocs_probe_device_radius_roots(pocs_ctx* ctx, uint32_t first_word, unsigned long long count, unsigned long long* mismatches,
+                                   uint32_t* first_bad);
+/* TEST HOOK beside pocs_probe_device_math: the mixture sampler takes the square root of its Box-Muller radius with one residual
+   correction less than the correctly rounded sequence has; the radius' argument takes one value per
+   32-bit word, so the two are compared on the DEVICE word by word.  For the words first_word .. first_word + count - 1
+   (count >= 1, first_word + count <= 2^32) the device forms the argument through the staged tables as the sampling kernel
+   does and takes both roots; mismatches: the number of words whose two roots differ in any bit; first_bad: the smallest such
+   word (0 where there is none).  Sixteen calls of 2^28 words cover every argument (tests/test_radius_root_sweep.py).  POCS_E_ARG
+   for a null pointer or a range outside the words. */
 int pocs_probe_device_collide(pocs_ctx* ctx, int K, const double* params, int n, const double* poses_xyt, int* flag_full, int* flag_pair,
                               int* flag_pair_eager, int* nkeep, double* kept);
 /* TEST HOOK, no counterpart in the reference: the DEVICE's collision test and the obstacle cull of the GMM sampling kernel on

@@ -120,6 +120,7 @@ SIGNATURES = {
     "pocs_get_exchange_wait": (C.c_int, [_vp, _dp]),
     "pocs_get_graph_captures": (C.c_int, [_vp, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong)]),
     "pocs_probe_device_math": (C.c_int, [_vp, C.c_int, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), _dp, _dp, _dp, _dp, _dp, _dp]),
+    "pocs_probe_device_radius_roots": (C.c_int, [_vp, C.c_uint32, C.c_ulonglong, C.POINTER(C.c_ulonglong), C.POINTER(C.c_uint32)]),
     "pocs_probe_device_collide": (C.c_int, [_vp, C.c_int, _dp, C.c_int, _dp, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int),
                                             C.POINTER(C.c_int), _dp]),
 }
@@ -769,6 +770,16 @@ class Context:
         self._chk(self.lib.pocs_probe_device_math(self.h, n, wr.ctypes.data_as(u32), wa.ctypes.data_as(u32), x.ctypes.data_as(_dp),
                                                   *[o.ctypes.data_as(_dp) for o in out]))
         return tuple(out)
+
+    def probe_device_radius_roots(self, first_word, count):
+        """Test hook: the sampler's short square root of the Box-Muller radius against the correctly rounded one on the device,
+        for the words first_word .. first_word + count - 1 -> (words whose roots differ, the smallest of them or 0)."""
+        first, count = int(first_word), int(count)
+        if not (0 <= first < 1 << 32 and 0 <= count <= 1 << 32):      # (ctypes would wrap them silently)
+            raise PocsError(-1, "probe_device_radius_roots: a range outside the 32-bit words")
+        bad, word = C.c_ulonglong(0), C.c_uint32(0)
+        self._chk(self.lib.pocs_probe_device_radius_roots(self.h, first, count, C.byref(bad), C.byref(word)))
+        return bad.value, word.value
 
     def probe_device_collide(self, params, poses):
         """Test hook: the device's collision test and the sampling kernel's obstacle cull on chosen inputs, against the

@@ -245,6 +245,29 @@ int pocs_probe_device_math(pocs_ctx* c, int n, const uint32_t* radius_words, con
   return rc;
 }
 
+// Test hook: the two square roots of the Box-Muller radius on a range of words (include/pocs.h).
+int pocs_probe_device_radius_roots(pocs_ctx* c, uint32_t first_word, unsigned long long count, unsigned long long* mismatches, uint32_t* first_bad) {
+  if (!c) return POCS_E_ARG;
+  if (!mismatches || !first_bad || count < 1 || (unsigned long long)first_word + count > (1ull << 32))
+    return fail(c, POCS_E_ARG, "pocs_probe_device_radius_roots: count >= 1, first_word + count <= 2^32, no null pointers");
+  HIPCHK(c, hipSetDevice(c->device));
+  if (int r = upload_tables(c)) return r;
+  unsigned long long* d_out = nullptr;               // [mismatches | smallest mismatching word]
+  HIPCHK(c, hipMalloc((void**)&d_out, 2 * sizeof(unsigned long long)));
+  unsigned long long h[2] = {0ull, ~0ull};
+  int rc = POCS_OK;
+  if (hipMemcpy(d_out, h, sizeof h, hipMemcpyHostToDevice) != hipSuccess) rc = fail(c, POCS_E_DEVICE, "probe upload failed");
+  if (rc == POCS_OK && pocs_launch_probe_radius_roots((const pocs_tables*)c->d_tables.p, first_word, count, d_out, c->stream) != hipSuccess)
+    rc = fail(c, POCS_E_DEVICE, "probe launch failed");
+  if (rc == POCS_OK && hipStreamSynchronize(c->stream) != hipSuccess) rc = fail(c, POCS_E_DEVICE, "probe kernel failed");
+  if (rc == POCS_OK && hipMemcpy(h, d_out, sizeof h, hipMemcpyDeviceToHost) != hipSuccess) rc = fail(c, POCS_E_DEVICE, "probe download failed");
+  (void)hipFree(d_out);
+  if (rc != POCS_OK) return rc;
+  *mismatches = h[0];
+  *first_bad = h[0] ? (uint32_t)h[1] : 0u;
+  return POCS_OK;
+}
+
 // Test hook: the device's collision test and obstacle cull on chosen poses and a chosen mixture (include/pocs.h).
 int pocs_probe_device_collide(pocs_ctx* c, int K, const double* params, int n, const double* poses, int* flag_full, int* flag_pair,
                               int* flag_pair_eager, int* nkeep, double* kept) {

@@ -298,6 +298,8 @@ hipError_t pocs_launch_zero_counts(unsigned long long* p, size_t words, hipStrea
 hipError_t pocs_launch_copy(const void* src, void* dst, long long bytes, hipStream_t s);
 hipError_t pocs_launch_fill(void* dst, long long bytes, hipStream_t s);
 hipError_t pocs_launch_probe_math(const pocs_tables* tables, int n, const uint32_t* wr, const uint32_t* wa, const double* x, double* out, hipStream_t s);   // out: 5 x n
+// words first .. first + count - 1 (inside 0 .. 2^32 - 1); out[0] += the words whose two radius roots differ, out[1] = min(out[1], the smallest)
+hipError_t pocs_launch_probe_radius_roots(const pocs_tables* tables, uint32_t first, unsigned long long count, unsigned long long* out, hipStream_t s);
 // one block; a: env, tables, param (the K records of ONE mixture: W = 1), fp, fp_rr, fp_phi, M -- nothing else is read.
 // x / y / th: n poses; flags: 3 x n (full table, pair, pair EAGER); nkeep: 1; kept: POCS_MAX_OBSTACLES records
 hipError_t pocs_launch_probe_collide(int K, const pocs_gmm_launch& a, int n, const double* x, const double* y, const double* th,

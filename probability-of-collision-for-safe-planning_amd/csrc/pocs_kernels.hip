@@ -418,6 +418,39 @@ hipError_t pocs_launch_probe_math(const pocs_tables* tables, int n, const uint32
   hipLaunchKernelGGL(k_probe_math, dim3(1), dim3(POCS_BLOCK), 0, s, tables, n, wr, wa, x, out);
   return hipGetLastError();
 }
+// The Box-Muller radius' two square roots on a range of words (pocs_probe_device_radius_roots: a test hook -- the sweep over
+// all 2^32 words that pocs_sqrt_radius rests on): per word the argument t = |pocs_radius2_unit32(w)| through the tables
+// staged in LDS as k_gmm_step stages them, the correctly rounded root and the short one; a wave adds the number of its lanes
+// whose two roots differ in any bit to out[0], and the smallest such word goes to out[1].
+__global__ __launch_bounds__(POCS_BLOCK) void k_probe_radius_roots(const pocs_tables* __restrict__ tables, uint32_t first, unsigned long long count,
+                                                                  unsigned long long* __restrict__ out) {
+  __shared__ pocs_tables s_tab;
+  stage_tables(tables, &s_tab);
+  __syncthreads();
+  const unsigned long long stride = (unsigned long long)gridDim.x * POCS_BLOCK;
+  // (every lane of a wave makes every trip: the count is balloted)
+  for (unsigned long long i0 = (unsigned long long)blockIdx.x * POCS_BLOCK + (threadIdx.x & ~63u); i0 < count; i0 += stride) {
+    const unsigned long long i = i0 + (threadIdx.x & 63u);
+    const bool live = i < count;
+    const uint32_t w = first + (uint32_t)(live ? i : 0ull);
+    const double t = fabs(pocs_radius2_unit32(w, &s_tab));
+    const double full = pocs_sqrt_normal(t), brief = pocs_sqrt_radius(t);
+    const bool bad = live && __builtin_bit_cast(unsigned long long, full) != __builtin_bit_cast(unsigned long long, brief);
+    const unsigned long long b = __ballot(bad);
+    if (b != 0ull) {                                                 // (scalar)
+      if ((threadIdx.x & 63u) == (unsigned)__builtin_ctzll(b)) {    // the wave's first such lane: its lowest such word
+        atomicAdd(&out[0], (unsigned long long)__popcll(b));
+        atomicMin(&out[1], (unsigned long long)w);
+      }
+    }
+  }
+}
+hipError_t pocs_launch_probe_radius_roots(const pocs_tables* tables, uint32_t first, unsigned long long count, unsigned long long* out, hipStream_t s) {
+  if (!tables || !out || count < 1 || (unsigned long long)first + count > (1ull << 32)) return hipErrorInvalidValue;
+  const unsigned long long nb = (count + POCS_BLOCK - 1) / POCS_BLOCK;
+  hipLaunchKernelGGL(k_probe_radius_roots, dim3((unsigned)(nb < POCS_MAX_BLOCKS ? nb : POCS_MAX_BLOCKS)), dim3(POCS_BLOCK), 0, s, tables, first, count, out);
+  return hipGetLastError();
+}
 // The hot paths' collision test and k_gmm_step's obstacle cull on poses, a mixture and a world the caller picks
 // (pocs_probe_device_collide: a test hook -- a pose a few ulps from touching, a pose at the edge of what the mixture can
 // draw, which no free-running launch meets): ONE block that does what the kernels' blocks do, through the same inline

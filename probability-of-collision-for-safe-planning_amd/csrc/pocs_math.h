@@ -342,8 +342,8 @@ POCS_HD void pocs_normal3(uint64_t seed, uint64_t index, uint32_t waypoint, uint
   *spare = a.w;
 }
 
-// sqrt for positive t in the normal range -- the squared Box-Muller radius (0 < t <= 64), and the distances and pivots
-// of pocs_model.h --, correctly rounded like sqrt().  On the
+// sqrt for positive t in the normal range -- the distances and pivots of pocs_model.h; the squared Box-Muller radius
+// (0 < t <= 64) has the shorter pocs_sqrt_radius below --, correctly rounded like sqrt().  On the
 // device: the compiler's own f64 expansion (v_rsq_f64 seed, one coupled Goldschmidt step, two
 // residual corrections) without the 2^+-256 range scaling it wraps around it for arguments below
 // 2^-767 and without its select for +-0 / inf: t = |-2 log u| is never 0 (the smallest value, at
@@ -362,6 +362,26 @@ POCS_HD double pocs_sqrt_normal(double t) {
   d = fma(-g, g, t);
   g = fma(d, h, g);
   return g;
+#else
+  return sqrt(t);
+#endif
+}
+
+// sqrt for the squared Box-Muller radius alone: t = |pocs_radius2_unit32(w)|, one of 2^32 values.  On the device the
+// sequence above WITHOUT its second residual correction: for every one of those arguments the first correction already
+// lands on the correctly rounded root (pocs_probe_device_radius_roots takes both roots of all 2^32 words on the GPU and
+// counts the words whose bits differ: tests/test_radius_root_sweep.py asserts none).  That is a property of this finite
+// set with the hardware's v_rsq_f64 seed, not of the sequence: every other caller keeps pocs_sqrt_normal.
+POCS_HD double pocs_sqrt_radius(double t) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  const double y = __builtin_amdgcn_rsq(t);
+  double g = t * y;
+  double h = 0.5 * y;
+  const double r = fma(-h, g, 0.5);
+  g = fma(g, r, g);
+  h = fma(h, r, h);
+  const double d = fma(-g, g, t);
+  return fma(d, h, g);
 #else
   return sqrt(t);
 #endif
@@ -403,7 +423,7 @@ POCS_HD double pocs_div(double a, double b) { return pocs_div_by(a, b, pocs_reci
 // k_gmm_step relies on; the level u = 0: pocs_radius2_unit32), one word for the angle.
 POCS_HD void pocs_normal_pair_w2(uint32_t wr, uint32_t wa, const pocs_tables* T, double* n0, double* n1, const pocs_vconst* V = nullptr) {
   // (|.|: free on the device, and the root's argument is then non-negative by construction, not by an error bound)
-  const double rad = pocs_sqrt_normal(fabs(pocs_radius2_unit32(wr, T)));
+  const double rad = pocs_sqrt_radius(fabs(pocs_radius2_unit32(wr, T)));
   double sn, cs;
   pocs_sincos_2pi_u32_tab(wa, T, &sn, &cs, V);
   *n0 = rad * cs;
