@@ -676,6 +676,21 @@ int pocs_probe_device_segment(pocs_ctx* ctx, const double* fp4, const double* bo
    use (the single-pose form of the MC kernels, and the two-pose lane-mask form of the GMM sampling kernel on poses 2 j, 2 j + 1: bit
    16 is set should the two ever disagree).  It reads nothing of the context's world or modes, so it is never refused.  POCS_E_ARG for
    a null pointer, n outside 1 .. 2^20, J, M or backward out of range, a bad footprint or box and ANY input that is not finite. */
+int pocs_probe_device_counts(pocs_ctx* ctx, int n, const int* K, const double* weights, const double* alive, const uint64_t* seeds,
+                             const uint32_t* waypoints, const long long* n_total, double* counts_out);
+/* TEST HOOK beside pocs_probe_device_math, equally self-contained: the DEVICE's component counts of a waypoint (DESIGN.md section 4,
+   "degenerate cases") on inputs the caller picks.  n cases; case i is a mixture of K[i] components (1 <= K[i] <= 8): weights and
+   alive are n rows of 8 doubles, of which case i reads the first K[i] -- the raw weights (survivor counts, or any finite numbers
+   >= 0) and the alive flags (0 = retired) as the advance leaves them before it normalises; seeds[i] and waypoints[i] key the case's
+   draws, and n_total[i] (1 .. 2^53: a count is exact in a double) is the number of samples its components share.  One small launch,
+   one thread per case, divides the weights by their sum and draws the conditional binomials -- waiting times below
+   n min(p, 1 - p) = 10, BTPE from there on -- through the inline functions the mixture advance calls on both of its paths (the
+   speculated counts and their fallback); counts_out is n rows of 8, row i the CUMULATIVE counts n_0, n_0 + n_1, ... of case i (the
+   last live component's entry is n_total[i]; all retired: component 0 gets everything), zeros behind its K[i].  A free-running call
+   meets only the (n, p, seed) its own mixtures produce; this puts the switch between the two samplers, weights next to 0 and 1 and
+   retired components in every position in front of the oracle (tests/test_degenerate_forms.py).  It reads nothing of the context's
+   world, plans or modes, so it is never refused.  POCS_E_ARG for a null pointer, n outside 1 .. 2^20, a K or n_total out of range,
+   a negative weight and ANY input that is not finite. */
 int pocs_get_sequence_time(pocs_ctx* ctx, double* ms, int* concurrent);  /* POCS_OPT_PROFILE=1, whole-run GMM calls: first sampling launch -> end of the last one, and how many
                                                                             sub-batches of the call were in flight side by side (their launches overlap: DESIGN.md section 5) */
 

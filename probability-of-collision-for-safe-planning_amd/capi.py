@@ -123,6 +123,8 @@ SIGNATURES = {
     "pocs_probe_device_radius_roots": (C.c_int, [_vp, C.c_uint32, C.c_ulonglong, C.POINTER(C.c_ulonglong), C.POINTER(C.c_uint32)]),
     "pocs_probe_device_collide": (C.c_int, [_vp, C.c_int, _dp, C.c_int, _dp, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int),
                                             C.POINTER(C.c_int), _dp]),
+    "pocs_probe_device_counts": (C.c_int, [_vp, C.c_int, C.POINTER(C.c_int), _dp, _dp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint32),
+                                           C.POINTER(C.c_longlong), _dp]),
 }
 
 _lib = None
@@ -795,6 +797,24 @@ class Context:
         self._chk(self.lib.pocs_probe_device_collide(self.h, K, par.ctypes.data_as(_dp), n, xyt.ctypes.data_as(_dp),
                                                      *[f.ctypes.data_as(ip) for f in flags], C.byref(nkeep), kept.ctypes.data_as(_dp)))
         return flags[0], flags[1], flags[2], kept[:nkeep.value].copy()
+
+    def probe_device_counts(self, K, weights, alive, seeds, waypoints, n_total):
+        """Test hook: the device's component counts of a waypoint on chosen inputs, n cases in one launch.  K: int[n], the components
+        of each case (1 .. 8); weights, alive: n x 8 (raw weights >= 0 and alive flags, case i uses the first K[i]); seeds (uint64),
+        waypoints (uint32), n_total (int64, 1 .. 2^53): n each.  -> n x 8 cumulative counts (float64), zeros behind a case's K."""
+        k = np.ascontiguousarray(K, dtype=np.int32).ravel()
+        n = len(k)
+        w, a = _arr(weights), _arr(alive)
+        s = np.ascontiguousarray(seeds, dtype=np.uint64).ravel()
+        wp = np.ascontiguousarray(waypoints, dtype=np.uint32).ravel()
+        nt = np.ascontiguousarray(n_total, dtype=np.int64).ravel()
+        if w.shape != (n, 8) or a.shape != (n, 8) or not (len(s) == len(wp) == len(nt) == n):
+            raise ValueError("%d cases: weights and alive are n x 8, seeds, waypoints and n_total have n entries" % n)
+        out = np.full((n, 8), -1.0)
+        self._chk(self.lib.pocs_probe_device_counts(self.h, n, k.ctypes.data_as(C.POINTER(C.c_int)), w.ctypes.data_as(_dp), a.ctypes.data_as(_dp),
+                                                    s.ctypes.data_as(C.POINTER(C.c_uint64)), wp.ctypes.data_as(C.POINTER(C.c_uint32)),
+                                                    nt.ctypes.data_as(C.POINTER(C.c_longlong)), out.ctypes.data_as(_dp)))
+        return out
 
     def graph_captures(self):
         """(gmm, mc): how often the whole GMM call's and the MC call's launches have been captured into a graph so far."""

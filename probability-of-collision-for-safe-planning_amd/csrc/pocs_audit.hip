@@ -524,6 +524,55 @@ int pocs_probe_device_segment(pocs_ctx* c, const double* fp4, const double* boxe
   return rc;
 }
 
+// Test hook: the device's component counts on chosen weights, alive flags, seeds, waypoints and sample totals (include/pocs.h).
+// Nothing of the context's world, plans or modes is read.
+int pocs_probe_device_counts(pocs_ctx* c, int n, const int* K, const double* weights, const double* alive, const uint64_t* seeds,
+                             const uint32_t* waypoints, const long long* n_total, double* counts_out) {
+  if (!c) return POCS_E_ARG;
+  if (!K || !weights || !alive || !seeds || !waypoints || !n_total || !counts_out || n < 1 || n > (1 << 20))
+    return fail(c, POCS_E_ARG, "pocs_probe_device_counts: 1 <= n <= 2^20, no null pointers");
+  constexpr size_t KM = POCS_MAX_GAUSSIANS;
+  for (int i = 0; i < n; ++i) {
+    if (K[i] < 1 || K[i] > POCS_MAX_GAUSSIANS) return fail(c, POCS_E_ARG, "pocs_probe_device_counts: case %d: 1 <= K <= %d", i, POCS_MAX_GAUSSIANS);
+    if (n_total[i] < 1 || n_total[i] > (1LL << 53)) return fail(c, POCS_E_ARG, "pocs_probe_device_counts: case %d: 1 <= n_total <= 2^53", i);
+    for (int k = 0; k < K[i]; ++k) {
+      const double w = weights[(size_t)i * KM + k], a = alive[(size_t)i * KM + k];
+      if (!std::isfinite(w) || w < 0.0) return fail(c, POCS_E_ARG, "pocs_probe_device_counts: case %d: weight %d is not a finite number >= 0", i, k);
+      if (!std::isfinite(a)) return fail(c, POCS_E_ARG, "pocs_probe_device_counts: case %d: alive flag %d is not finite", i, k);
+    }
+  }
+  HIPCHK(c, hipSetDevice(c->device));
+  // [w | alive] n x KM doubles each, [n_total] n doubles, [out] n x KM doubles, [seeds] n 64-bit words, [waypoints | K] n 32-bit words each
+  const size_t nk = (size_t)n * KM;
+  std::vector<double> h(2 * nk + (size_t)n, 0.0);
+  for (int i = 0; i < n; ++i) {
+    for (int k = 0; k < K[i]; ++k) {                       // (what lies behind a case's K is not read, here or on the device)
+      h[(size_t)i * KM + k] = weights[(size_t)i * KM + k];
+      h[nk + (size_t)i * KM + k] = alive[(size_t)i * KM + k];
+    }
+    h[2 * nk + (size_t)i] = (double)n_total[i];
+  }
+  const size_t off_out = h.size() * sizeof(double), off_seed = off_out + nk * sizeof(double), off_wp = off_seed + (size_t)n * sizeof(uint64_t),
+               off_k = off_wp + (size_t)n * sizeof(uint32_t);
+  char* buf = nullptr;
+  HIPCHK(c, hipMalloc((void**)&buf, off_k + (size_t)n * sizeof(int)));
+  int rc = POCS_OK;
+  if (hipMemcpy(buf, h.data(), off_out, hipMemcpyHostToDevice) != hipSuccess || hipMemset(buf + off_out, 0, nk * sizeof(double)) != hipSuccess ||
+      hipMemcpy(buf + off_seed, seeds, (size_t)n * sizeof(uint64_t), hipMemcpyHostToDevice) != hipSuccess ||
+      hipMemcpy(buf + off_wp, waypoints, (size_t)n * sizeof(uint32_t), hipMemcpyHostToDevice) != hipSuccess ||
+      hipMemcpy(buf + off_k, K, (size_t)n * sizeof(int), hipMemcpyHostToDevice) != hipSuccess)
+    rc = fail(c, POCS_E_DEVICE, "probe upload failed");
+  const double* d_w = (const double*)buf;
+  if (rc == POCS_OK && pocs_launch_probe_counts(n, (const int*)(buf + off_k), d_w, d_w + nk, (const unsigned long long*)(buf + off_seed),
+                                                (const uint32_t*)(buf + off_wp), d_w + 2 * nk, (double*)(buf + off_out), c->stream) != hipSuccess)
+    rc = fail(c, POCS_E_DEVICE, "probe launch failed");
+  if (rc == POCS_OK && hipStreamSynchronize(c->stream) != hipSuccess) rc = fail(c, POCS_E_DEVICE, "probe kernel failed");
+  if (rc == POCS_OK && hipMemcpy(counts_out, buf + off_out, nk * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess)
+    rc = fail(c, POCS_E_DEVICE, "probe download failed");
+  (void)hipFree(buf);
+  return rc;
+}
+
 int pocs_get_sequence_time(pocs_ctx* c, double* ms, int* concurrent) {
   if (!c) return POCS_E_ARG;
   if (ms) *ms = c->seq_ms;

@@ -322,6 +322,11 @@ hipError_t pocs_launch_probe_regions(const pocs_regions_dev* regions, int G, con
 hipError_t pocs_launch_probe_segment(const pocs_env_dev* env, const pocs_seg_dev* seg, const pocs_tables* tables, double u0, double u1,
                                      double u2, int backward, int n, const double* x, const double* y, const double* th, int* mask_out,
                                      hipStream_t s);
+// one thread per case; K / seeds / wp / n_total: n; w / alive / out: n rows of POCS_MAX_GAUSSIANS (case i uses the first K[i]): raw weights
+// and alive flags in, cumulative component counts out (pocs_normalise_weights + pocs_component_counts, as advance_finish and
+// speculate_counts call them)
+hipError_t pocs_launch_probe_counts(int n, const int* K, const double* w, const double* alive, const unsigned long long* seeds, const uint32_t* wp,
+                                    const double* n_total, double* out, hipStream_t s);
 hipError_t pocs_launch_mc_init(int nblk, const pocs_mc_launch& a, hipStream_t s);
 hipError_t pocs_launch_mc_step(int nblk, const pocs_mc_launch& a, hipStream_t s);
 hipError_t pocs_launch_mc_fused(int nblk, const pocs_mc_launch& a, hipStream_t s);

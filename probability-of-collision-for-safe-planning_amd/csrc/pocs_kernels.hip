@@ -707,6 +707,35 @@ hipError_t pocs_launch_probe_segment(const pocs_env_dev* env, const pocs_seg_dev
   hipLaunchKernelGGL(k_probe_segment, dim3(1), dim3(POCS_BLOCK), 0, s, env, seg, tables, u0, u1, u2, backward ? 1 : 0, n, x, y, th, mask_out);
   return hipGetLastError();
 }
+// The component counts of a waypoint on weights, alive flags, seeds, waypoints and sample totals the caller picks
+// (pocs_probe_device_counts: a test hook -- a free-running call meets only the (n, p, seed) its own mixtures produce): one thread
+// per case builds the K x POCS_STATE_STRIDE image of which only [12] (weight) and [13] (alive) matter, as speculate_counts does,
+// and runs pocs_normalise_weights + pocs_component_counts -- the inline functions of advance_finish and speculate_counts.
+// Kc / seeds / wp / n_total: n; w / alive / out: n rows of POCS_MAX_GAUSSIANS, of which case i uses the first Kc[i].
+__global__ __launch_bounds__(POCS_BLOCK) void k_probe_counts(int n, const int* __restrict__ Kc, const double* __restrict__ w,
+                                                            const double* __restrict__ alive, const unsigned long long* __restrict__ seeds,
+                                                            const uint32_t* __restrict__ wp, const double* __restrict__ n_total,
+                                                            double* __restrict__ out) {
+  const int i = (int)blockIdx.x * POCS_BLOCK + (int)threadIdx.x;
+  if (i >= n) return;
+  const int K = min(max(Kc[i], 1), POCS_MAX_GAUSSIANS);              // (the host has checked the range)
+  const size_t row = (size_t)i * POCS_MAX_GAUSSIANS;
+  double st[POCS_MAX_GAUSSIANS * POCS_STATE_STRIDE];
+  for (int k = 0; k < K; ++k) {
+    st[k * POCS_STATE_STRIDE + 12] = w[row + k];
+    st[k * POCS_STATE_STRIDE + 13] = alive[row + k];
+  }
+  const int last_alive = pocs_normalise_weights(K, 1, st);
+  double cum[POCS_MAX_GAUSSIANS];
+  pocs_component_counts(K, st, last_alive, (uint64_t)seeds[i], wp[i], n_total[i], cum, 1);
+  for (int k = 0; k < POCS_MAX_GAUSSIANS; ++k) out[row + k] = k < K ? cum[k] : 0.0;
+}
+hipError_t pocs_launch_probe_counts(int n, const int* K, const double* w, const double* alive, const unsigned long long* seeds, const uint32_t* wp,
+                                    const double* n_total, double* out, hipStream_t s) {
+  if (n < 1 || n > (1 << 20) || !K || !w || !alive || !seeds || !wp || !n_total || !out) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(k_probe_counts, dim3((unsigned)((n + POCS_BLOCK - 1) / POCS_BLOCK)), dim3(POCS_BLOCK), 0, s, n, K, w, alive, seeds, wp, n_total, out);
+  return hipGetLastError();
+}
 hipError_t pocs_launch_fill(void* dst, long long bytes, hipStream_t s) {
   hipLaunchKernelGGL(k_fill, dim3(8192), dim3(POCS_BLOCK), 0, s, (double2*)dst, bytes / 16, 1.5);
   return hipGetLastError();
