@@ -585,6 +585,43 @@ int pocs_set_segment_checks(pocs_ctx* ctx, int J);
 int pocs_get_segment_checks(const pocs_ctx* ctx);
 int pocs_get_segment_counts(pocs_ctx* ctx, unsigned long long* out, int cap);
 
+/* ---- round obstacles: discs beside the boxes, for both estimators (ours) ----------------------------
+ * What moves in a mobile robot's world -- people, other robots -- reaches a planner as a centre and a radius per time step, and
+ * pillars, table legs and lidar returns are the same shape.  A disc is {cx, cy, r}, r > 0, all finite.
+ *   world     the collision world at waypoint w is the boxes in force at w together with the discs in force at w;
+ *   touches   a pose touches when it touches a box, as ever, or a disc: with the footprint's centre (px, py), heading (sn, cs) and half
+ *             extents (rx, ry) as the box test forms them, d = (cx - px, cy - py) turned into the footprint's frame (the box test's own
+ *             d1, d2), q_i = max(|d_i| - r_i, 0), the pose touches the disc exactly when NOT fma(q1, q1, q2 q2) > r r -- the exact
+ *             distance from the disc's centre to the footprint, touching included (csrc/pocs_collide.h: pocs_disc_narrow).
+ * Every result of both estimators is formed from that flag.
+ *   schedule  S tables of D discs, table min(w, S - 1) in force at waypoint w -- independent of the boxes' own schedule: a static room
+ *             with moving pedestrians is pocs_set_obstacles plus pocs_set_discs(.., D, W);
+ *   bound     boxes and discs share the table of POCS_MAX_OBSTACLES records: M + D <= 64.  pocs_set_discs, pocs_set_obstacles and
+ *             pocs_set_obstacle_schedule refuse a combination above it with POCS_E_ARG and leave the context as it was.  The discs lie
+ *             behind the boxes: the caller's box indices do not move.
+ * pocs_set_discs: discs = S x D x {cx, cy, r}, 1 <= S <= POCS_MAX_WORLD_STEPS.  D = 0, or S = 0 with a null pointer, clears: every call is
+ * again, launch for launch, what it is without discs.  POCS_E_ARG, the discs in force kept: a null pointer with D > 0, D or S out of
+ * range, a value that is not finite, r <= 0.  Like every setter it ends run-ahead serving.  The discs belong to the context: they survive
+ * pocs_set_plans, pocs_set_footprint (the records are re-prepared), pocs_set_obstacles and pocs_set_obstacle_schedule (re-composed).  A
+ * context given discs and never boxes has a world (M = 0) and may run.  pocs_get_discs writes D and S (0 and 0 without discs);
+ * pocs_get_world_steps answers max(Sb, Sd).  The text channel has no command for discs; its clearObstacles leaves them.
+ * Discs of the same D and S with other numbers are overwritten in place and the cached graph is replayed (pocs_get_graph_captures does
+ * not move): the planning cycle, where new predictions arrive with every call.
+ *
+ * SERVED (D > 0), as a compound footprint is: whole calls on one GPU -- pocs_run_gmm_estimation, pocs_run_simulation, pocs_mc_run_local
+ * -- over at most 64 records, static or scheduled, as single runs, batches in both sub-batch forms, run-ahead, calls of plans with and
+ * without both risk bounds, POCS_OPT_MC_WAYPOINT_COUNTS, POCS_OPT_STORE_SAMPLES (stored flags are the world's flags).  A GMM call of one
+ * run takes the ticket form (POCS_OPT_LONE_CALL has no effect), an MC call the per-step form whatever POCS_OPT_MC_FUSED says.
+ * REFUSED in both directions with POCS_E_STATE (POCS_E_ORDER for the setter inside a begin/end sequence), the context left as it was --
+ * discs change results: a tree of plans, a large world (more than 64 boxes), a shard, the exchange (created or connected), a bound
+ * moments buffer, an open begin/end sequence and pocs_gmm_begin, POCS_OPT_OBSTACLE_COUNTS = 1, a compound footprint with F > 1, segment
+ * checks with J > 1.  pocs_set_discs under any of these names what is in the way; entering any of them while D > 0 names the call and
+ * "discs are set (pocs_set_discs)".  pocs_probe_device_collide, which tests boxes, answers POCS_E_STATE while D > 0.
+ * NOT applied while D > 0, never refused: clearance levels and watched regions -- their getters answer POCS_E_STATE and the call is the
+ * call with discs and without them. */
+int pocs_set_discs(pocs_ctx* ctx, const double* discs /* S x D x {cx, cy, r} */, int D, int S);
+int pocs_get_discs(const pocs_ctx* ctx, int* D, int* S);
+
 /* ---- results of the last run, for audits and parity tests ------------------------------- */
 int pocs_get_path_length(const pocs_ctx* ctx);
 int pocs_get_waypoint_probabilities(pocs_ctx* ctx, double* out, int cap);         /* `probabilities`, MCSimulator.h:660,678,817 */
@@ -691,6 +728,14 @@ int pocs_probe_device_counts(pocs_ctx* ctx, int n, const int* K, const double* w
    retired components in every position in front of the oracle (tests/test_degenerate_forms.py).  It reads nothing of the context's
    world, plans or modes, so it is never refused.  POCS_E_ARG for a null pointer, n outside 1 .. 2^20, a K or n_total out of range,
    a negative weight and ANY input that is not finite. */
+int pocs_probe_device_discs(pocs_ctx* ctx, const double* fp4, const double* boxes, int M, const double* discs, int D,
+                            int n, const double* poses_xyt, int* out);
+/* TEST HOOK beside pocs_probe_device_segment, equally self-contained: which kinds of obstacle the DEVICE finds a pose touching, for the
+   caller's own footprint fp4 = {dx, dy, half_x, half_y}, M boxes {cx, cy, half_x, half_y, yaw_rad} and D discs {cx, cy, r}, M + D <= 64,
+   prepared and composed as the library prepares the context's.  One small launch stages them; out[i] bit 0: pose i touches some box,
+   bit 1: some disc -- through the MC kernels' single-pose form on the full table --, bit 8 should the sampling kernel's two-pose
+   lane-mask form (poses 2 j, 2 j + 1) ever disagree.  It reads nothing of the context's world or modes, so it is never refused.
+   POCS_E_ARG for a null pointer, n outside 1 .. 2^20, M + D out of range, a bad footprint, box or disc and ANY input that is not finite. */
 int pocs_get_sequence_time(pocs_ctx* ctx, double* ms, int* concurrent);  /* POCS_OPT_PROFILE=1, whole-run GMM calls: first sampling launch -> end of the last one, and how many
                                                                             sub-batches of the call were in flight side by side (their launches overlap: DESIGN.md section 5) */
 

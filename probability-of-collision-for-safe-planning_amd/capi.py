@@ -97,6 +97,9 @@ SIGNATURES = {
     "pocs_get_region_counts": (C.c_int, [_vp, C.POINTER(C.c_ulonglong), C.c_int, C.POINTER(C.c_int)]),
     "pocs_get_batch_region_probabilities": (C.c_int, [_vp, C.c_int, C.c_int, _dp, C.c_int]),
     "pocs_probe_device_regions": (C.c_int, [_vp, _dp, _dp, C.POINTER(C.c_int), C.c_int, C.c_int, _dp, C.POINTER(C.c_int)]),
+    "pocs_set_discs": (C.c_int, [_vp, _dp, C.c_int, C.c_int]),
+    "pocs_get_discs": (C.c_int, [_vp, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "pocs_probe_device_discs": (C.c_int, [_vp, _dp, _dp, C.c_int, _dp, C.c_int, C.c_int, _dp, C.POINTER(C.c_int)]),
     "pocs_set_segment_checks": (C.c_int, [_vp, C.c_int]),
     "pocs_get_segment_checks": (C.c_int, [_vp]),
     "pocs_get_segment_counts": (C.c_int, [_vp, C.POINTER(C.c_ulonglong), C.c_int]),
@@ -280,8 +283,48 @@ class Context:
         self._chk(self.lib.pocs_set_obstacle_schedule(self.h, b.ctypes.data_as(_dp) if b.size else None, b.shape[1], b.shape[0]))
 
     def world_steps(self):
-        """S of the obstacle schedule in force; 1 for a static world; 0 for a context without a collision world."""
+        """S of the obstacle schedule in force (under discs: the larger of the boxes' and the discs' steps); 1 for a static world; 0
+        for a context without a collision world."""
         return self.lib.pocs_get_world_steps(self.h)
+
+    def set_discs(self, discs):
+        """Round obstacles beside the boxes: discs of shape (D, 3) = {cx, cy, r} for a static table, or (S, D, 3) for a schedule of
+        their own -- table min(w, S - 1) is in force at waypoint w, whatever the boxes' schedule (include/pocs.h).  An empty array or
+        None clears.  planio.moving_discs builds a schedule from per-waypoint centres."""
+        if discs is None:
+            self._chk(self.lib.pocs_set_discs(self.h, None, 0, 0))
+            return
+        d = _arr(discs)
+        if d.size == 0:
+            self._chk(self.lib.pocs_set_discs(self.h, None, 0, 0))
+            return
+        if d.ndim == 2:
+            d = d.reshape((1,) + d.shape)
+        if d.ndim != 3 or d.shape[2] != 3:
+            raise ValueError("discs of shape %s, (D, 3) or (S, D, 3) expected" % (d.shape,))
+        d = np.ascontiguousarray(d)
+        self._chk(self.lib.pocs_set_discs(self.h, d.ctypes.data_as(_dp), d.shape[1], d.shape[0]))
+
+    def discs(self):
+        """(D, S) of the discs in force; (0, 0) without discs."""
+        D, S = C.c_int(0), C.c_int(0)
+        self._chk(self.lib.pocs_get_discs(self.h, C.byref(D), C.byref(S)))
+        return D.value, S.value
+
+    def probe_device_discs(self, footprint, boxes, discs, poses):
+        """Test hook: per pose (n x 3) the kinds of obstacle it touches on the device, for the caller's own footprint (dx, dy, hx, hy),
+        boxes (M x 5) and discs (D x 3).  int32[n]: bit 0 = touches some box, bit 1 = touches some disc, bit 8 = the kernels' two forms
+        disagree (never)."""
+        fp = _arr(footprint).ravel()
+        b = _arr(boxes if boxes is not None else []).reshape(-1, 5)
+        d = _arr(discs if discs is not None else []).reshape(-1, 3)
+        xyt = _arr(poses).reshape(-1, 3)
+        assert fp.size == 4
+        out = np.full(xyt.shape[0], -1, dtype=np.int32)
+        self._chk(self.lib.pocs_probe_device_discs(self.h, fp.ctypes.data_as(_dp), b.ctypes.data_as(_dp) if b.size else None, b.shape[0],
+                                                   d.ctypes.data_as(_dp) if d.size else None, d.shape[0], xyt.shape[0],
+                                                   xyt.ctypes.data_as(_dp), out.ctypes.data_as(C.POINTER(C.c_int))))
+        return out
 
     def set_world(self, boxes):
         """A static world of up to MAX_WORLD_BOXES boxes, shape (M, 5) = {cx, cy, half_x, half_y, yaw}; the footprint stays as set
@@ -439,6 +482,8 @@ class Context:
         p = dict(DEFAULTS)
         p.update(params or {})
         self.set_env(env)
+        if env.get("discs") is not None:   # round obstacles beside the boxes (set_discs)
+            self.set_discs(env["discs"])
         self.set_alphas(p["alphas"])
         self.set_q(p["Q"])
         self.set_landmarks(p["landmarks"])

@@ -229,6 +229,8 @@ int pocs_set_footprint_parts(pocs_ctx* c, const double* parts, int F) {
   }
   if (seg_applied(c))                                // (the segment forms test a single box: refused in both directions)
     return fail(c, POCS_E_STATE, "pocs_set_footprint_parts: segment checks are set (pocs_set_segment_checks); %s", pocs_modes::kSegClause);
+  if (discs_applied(c))                              // (so do the round forms)
+    return fail(c, POCS_E_STATE, "pocs_set_footprint_parts: discs are set (pocs_set_discs); %s", pocs_modes::kDiscClause);
   for (int f = 0; f < F; ++f) c->fp_parts[f] = pocs_footprint{parts[4 * f], parts[4 * f + 1], parts[4 * f + 2], parts[4 * f + 3]};
   c->fp_F = F;
   c->fp = c->fp_parts[0];
@@ -250,6 +252,8 @@ int pocs_set_obstacles(pocs_ctx* c, const double* boxes, int M) {
   if (!setter(c)) return POCS_E_ARG;
   if (M < 0 || M > POCS_MAX_OBSTACLES || (M > 0 && !boxes))
     return fail(c, POCS_E_ARG, "obstacle count %d outside 0..%d", M, POCS_MAX_OBSTACLES);
+  if (M + c->disc_D > POCS_MAX_OBSTACLES)            // (boxes and discs share the table of POCS_MAX_OBSTACLES records)
+    return fail(c, POCS_E_ARG, "%d boxes beside %d discs (pocs_set_discs): more than %d records", M, c->disc_D, POCS_MAX_OBSTACLES);
   if (int r = check_boxes(c, "obstacles", boxes, (size_t)M, (size_t)M, false)) return r;
   return install_world(c, boxes, (size_t)M, 1, 0);
 }
@@ -262,11 +266,60 @@ int pocs_set_obstacle_schedule(pocs_ctx* c, const double* boxes, int M, int S) {
   if (S == 0 && M == 0) return pocs_set_obstacles(c, nullptr, 0);      // no schedule, an explicitly empty world
   if (S < 1 || S > POCS_MAX_WORLD_STEPS) return fail(c, POCS_E_ARG, "obstacle schedule of %d steps outside 1..%d", S, POCS_MAX_WORLD_STEPS);
   if (M > 0 && !boxes) return fail(c, POCS_E_ARG, "obstacle schedule: null boxes");
+  if (M + c->disc_D > POCS_MAX_OBSTACLES)
+    return fail(c, POCS_E_ARG, "obstacle schedule: %d boxes beside %d discs (pocs_set_discs): more than %d records", M, c->disc_D, POCS_MAX_OBSTACLES);
   if (int r = check_boxes(c, "obstacle schedule", boxes, (size_t)S * (size_t)M, (size_t)M, true)) return r;
   return install_world(c, boxes, (size_t)M, S, 0);
 }
 
-int pocs_get_world_steps(const pocs_ctx* c) { return (c && c->have_obstacles) ? c->world_S : 0; }
+int pocs_get_world_steps(const pocs_ctx* c) { return (c && (c->have_obstacles || discs_applied(c))) ? env_steps(c) : 0; }      // (max(Sb, Sd) under discs)
+
+// ---- round obstacles (include/pocs.h) ----
+// S tables of D discs {cx, cy, r}; upload_world composes them with the boxes' steps into the env records.  D = 0 clears.
+int pocs_set_discs(pocs_ctx* c, const double* discs, int D, int S) {
+  if (!setter(c)) return POCS_E_ARG;
+  if (D < 0 || D > POCS_MAX_OBSTACLES) return fail(c, POCS_E_ARG, "pocs_set_discs: %d discs outside 0..%d", D, POCS_MAX_OBSTACLES);
+  if (D == 0 || (S == 0 && !discs)) {                // clears: every call is again what it is without discs
+    if (c->disc_D > 0) c->env_dirty = true;
+    c->discs.clear(); c->disc_D = 0; c->disc_S = 1;
+    return POCS_OK;
+  }
+  if (S < 1 || S > POCS_MAX_WORLD_STEPS) return fail(c, POCS_E_ARG, "pocs_set_discs: %d steps outside 1..%d", S, POCS_MAX_WORLD_STEPS);
+  if (!discs) return fail(c, POCS_E_ARG, "pocs_set_discs: null discs");
+  const int M = large_world(c) ? 0 : world_boxes(c);
+  if (M + D > POCS_MAX_OBSTACLES)
+    return fail(c, POCS_E_ARG, "pocs_set_discs: %d discs beside %d boxes: more than %d records", D, M, POCS_MAX_OBSTACLES);
+  for (size_t i = 0; i < (size_t)S * (size_t)D; ++i) {
+    const double* d = discs + 3 * i;
+    for (int j = 0; j < 3; ++j)
+      if (!std::isfinite(d[j])) return fail(c, POCS_E_ARG, "pocs_set_discs: step %d, disc %d: value %d is not finite", (int)(i / (size_t)D), (int)(i % (size_t)D), j);
+    if (!(d[2] > 0)) return fail(c, POCS_E_ARG, "pocs_set_discs: step %d, disc %d: the radius must be > 0", (int)(i / (size_t)D), (int)(i % (size_t)D));
+  }
+  // (not a mode of the table: the one mask of what discs exclude, pocs_modes.hpp, and a compound footprint and segment checks beside it)
+  unsigned in_the_way = modes_of(c) & pocs_modes::kDiscExcluded;
+  if (in_the_way) {                                  // names ONE mode: the open sequence before all others, a connected exchange before its buffer
+    const bool open = (in_the_way & pocs_modes::kSequence) != 0;
+    if (open) in_the_way = pocs_modes::kSequence;
+    if (in_the_way & pocs_modes::kXchgConnected) in_the_way &= ~(unsigned)pocs_modes::kXchgCreated;
+    return fail(c, open ? POCS_E_ORDER : POCS_E_STATE, "pocs_set_discs: %s; %s",
+                pocs_modes::name((pocs_modes::Mode)(in_the_way & (0u - in_the_way))), pocs_modes::kDiscClause);
+  }
+  if (parts_applied(c))
+    return fail(c, POCS_E_STATE, "pocs_set_discs: a compound footprint is set (pocs_set_footprint_parts); %s", pocs_modes::kDiscClause);
+  if (seg_applied(c))
+    return fail(c, POCS_E_STATE, "pocs_set_discs: segment checks are set (pocs_set_segment_checks); %s", pocs_modes::kDiscClause);
+  c->discs.assign(discs, discs + (size_t)S * (size_t)D * 3);
+  c->disc_D = D; c->disc_S = S;
+  c->env_dirty = true;                               // (same D and S: the records are overwritten in place and the cached graph replays)
+  return POCS_OK;
+}
+
+int pocs_get_discs(const pocs_ctx* c, int* D, int* S) {
+  if (!c) return POCS_E_ARG;
+  if (D) *D = c->disc_D;
+  if (S) *S = c->disc_D > 0 ? c->disc_S : 0;
+  return POCS_OK;
+}
 
 // A static world of up to POCS_MAX_WORLD_BOXES boxes.  Up to POCS_MAX_OBSTACLES it IS pocs_set_obstacles; above, the boxes are kept
 // apart from the staged table (which is then empty): upload_world prepares their records, the GMM launches get a cull launch in
@@ -613,7 +666,7 @@ static int clearance_served(pocs_ctx* c, const char* what) {
     case Results::ClNoCall: return fail(c, POCS_E_STATE, "%s: there was no call yet", what);
     case Results::ClOff: return fail(c, POCS_E_STATE, "%s: the last call ran without clearance levels (L was 0)", what);
     case Results::ClTouched: return fail(c, POCS_E_STATE, "%s: pocs_set_clearance_levels touched the levels since the last call", what);
-    default: return fail(c, POCS_E_STATE, "%s: the levels are not applied to the last call (a tree of plans, a large world, POCS_OPT_OBSTACLE_COUNTS, a shard, the step API, segment checks -- or it failed)", what);
+    default: return fail(c, POCS_E_STATE, "%s: the levels are not applied to the last call (a tree of plans, a large world, POCS_OPT_OBSTACLE_COUNTS, a shard, the step API, segment checks, discs -- or it failed)", what);
   }
   if (r.cl_kind == Kind::None || r.cl_kind != r.last_kind || r.cl_counts.empty()) return fail(c, POCS_E_STATE, "%s: there was no call yet", what);
   return POCS_OK;
@@ -708,7 +761,7 @@ static int regions_served(pocs_ctx* c, const char* what) {
     case Results::RgNoCall: return fail(c, POCS_E_STATE, "%s: there was no call yet", what);
     case Results::RgOff: return fail(c, POCS_E_STATE, "%s: the last call ran without watched regions (G was 0)", what);
     case Results::RgTouched: return fail(c, POCS_E_STATE, "%s: pocs_set_regions touched the regions since the last call", what);
-    default: return fail(c, POCS_E_STATE, "%s: the regions are not applied to the last call (a tree of plans, a large world, POCS_OPT_OBSTACLE_COUNTS, a shard, the step API, a compound footprint, clearance levels, segment checks -- or it failed)", what);
+    default: return fail(c, POCS_E_STATE, "%s: the regions are not applied to the last call (a tree of plans, a large world, POCS_OPT_OBSTACLE_COUNTS, a shard, the step API, a compound footprint, clearance levels, segment checks, discs -- or it failed)", what);
   }
   if (r.rg_kind == Kind::None || r.rg_kind != r.last_kind || r.rg_counts.empty()) return fail(c, POCS_E_STATE, "%s: there was no call yet", what);
   return POCS_OK;
@@ -785,6 +838,8 @@ int pocs_set_segment_checks(pocs_ctx* c, int J) {
     }
     if (parts_applied(c))
       return fail(c, POCS_E_STATE, "pocs_set_segment_checks: a compound footprint is set (pocs_set_footprint_parts); %s", pocs_modes::kSegClause);
+    if (discs_applied(c))
+      return fail(c, POCS_E_STATE, "pocs_set_segment_checks: discs are set (pocs_set_discs); %s", pocs_modes::kDiscClause);
   }
   c->seg_J = J;
   c->env_dirty = true;                               // (J and the fractions live beside the world on the device)

@@ -277,6 +277,8 @@ int pocs_probe_device_collide(pocs_ctx* c, int K, const double* params, int n, c
   if (!c->have_obstacles)
     return fail(c, POCS_E_STATE, "no collision world: pocs_set_obstacles / addObstacle / clearObstacles missing");
   if (int r = may_enter(c, "pocs_probe_device_collide", pocs_modes::kProbe)) return r;
+  if (discs_applied(c))                              // (this probe's three forms test boxes: a world with discs is probed by pocs_probe_device_discs)
+    return fail(c, POCS_E_STATE, "pocs_probe_device_collide: discs are set (pocs_set_discs); the probe tests boxes only, pocs_probe_device_discs probes a world with discs");
   // (a heading that is not a number has no sector: nothing of the kind reaches the device)
   const size_t PS = (size_t)K * POCS_PARAM_STRIDE;
   for (size_t j = 0; j < PS; ++j)
@@ -568,6 +570,59 @@ int pocs_probe_device_counts(pocs_ctx* c, int n, const int* K, const double* wei
     rc = fail(c, POCS_E_DEVICE, "probe launch failed");
   if (rc == POCS_OK && hipStreamSynchronize(c->stream) != hipSuccess) rc = fail(c, POCS_E_DEVICE, "probe kernel failed");
   if (rc == POCS_OK && hipMemcpy(counts_out, buf + off_out, nk * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess)
+    rc = fail(c, POCS_E_DEVICE, "probe download failed");
+  (void)hipFree(buf);
+  return rc;
+}
+
+// Test hook: which kinds of obstacle a pose touches, on the device, for chosen poses, footprint, boxes and discs (include/pocs.h).
+// Nothing of the context's world, plans or modes is read: the composed record (boxes, then discs) is prepared here, as upload_world
+// prepares the context's.
+int pocs_probe_device_discs(pocs_ctx* c, const double* fp4, const double* boxes, int M, const double* discs, int D, int n,
+                            const double* poses, int* out) {
+  if (!c) return POCS_E_ARG;
+  if (!fp4 || !poses || !out || n < 1 || n > (1 << 20) || M < 0 || D < 0 || M + D > POCS_MAX_OBSTACLES || (M > 0 && !boxes) || (D > 0 && !discs))
+    return fail(c, POCS_E_ARG, "pocs_probe_device_discs: 1 <= n <= 2^20, 0 <= M, 0 <= D, M + D <= %d, no null pointers", POCS_MAX_OBSTACLES);
+  for (int j = 0; j < 4; ++j)
+    if (!std::isfinite(fp4[j])) return fail(c, POCS_E_ARG, "pocs_probe_device_discs: footprint value %d is not finite", j);
+  if (!(fp4[2] > 0) || !(fp4[3] > 0)) return fail(c, POCS_E_ARG, "pocs_probe_device_discs: footprint half extents must be > 0");
+  for (size_t j = 0; j < 5 * (size_t)M; ++j)
+    if (!std::isfinite(boxes[j])) return fail(c, POCS_E_ARG, "pocs_probe_device_discs: box %zu: value %zu is not finite", j / 5, j % 5);
+  for (int m = 0; m < M; ++m)
+    if (!(boxes[5 * (size_t)m + 2] > 0) || !(boxes[5 * (size_t)m + 3] > 0)) return fail(c, POCS_E_ARG, "pocs_probe_device_discs: box %d: half extents must be > 0", m);
+  for (size_t j = 0; j < 3 * (size_t)D; ++j)
+    if (!std::isfinite(discs[j])) return fail(c, POCS_E_ARG, "pocs_probe_device_discs: disc %zu: value %zu is not finite", j / 3, j % 3);
+  for (int d = 0; d < D; ++d)
+    if (!(discs[3 * (size_t)d + 2] > 0)) return fail(c, POCS_E_ARG, "pocs_probe_device_discs: disc %d: the radius must be > 0", d);
+  for (size_t j = 0; j < 3 * (size_t)n; ++j)
+    if (!std::isfinite(poses[j])) return fail(c, POCS_E_ARG, "pocs_probe_device_discs: pose %zu is not finite", j / 3);
+  HIPCHK(c, hipSetDevice(c->device));
+  if (int r = upload_tables(c)) return r;
+  const pocs_footprint fp = {fp4[0], fp4[1], fp4[2], fp4[3]};
+  std::vector<pocs_env_dev> env(1);
+  memset(env.data(), 0, sizeof(pocs_env_dev));
+  env[0].fp = fp; env[0].M = M + D;
+  for (int m = 0; m < M; ++m) pocs_prepare_box_beside_discs(boxes + (size_t)m * 5, &fp, &env[0].obs[(size_t)m * POCS_OBS_STRIDE]);
+  for (int d = 0; d < D; ++d) pocs_prepare_disc(discs + (size_t)d * 3, &fp, &env[0].obs[(size_t)(M + d) * POCS_OBS_STRIDE]);
+  std::vector<double> h(3 * (size_t)n);
+  for (int i = 0; i < n; ++i)
+    for (int j = 0; j < 3; ++j) h[(size_t)j * n + i] = poses[3 * (size_t)i + j];
+  // [env | x | y | th] then [out n] ints
+  const size_t off_x = sizeof(pocs_env_dev), off_out = off_x + 3 * (size_t)n * sizeof(double);
+  static_assert(sizeof(pocs_env_dev) % 8 == 0, "the probe's buffer keeps its parts aligned");
+  char* buf = nullptr;
+  HIPCHK(c, hipMalloc((void**)&buf, off_out + (size_t)n * sizeof(int)));
+  int rc = POCS_OK;
+  if (hipMemcpy(buf, env.data(), sizeof(pocs_env_dev), hipMemcpyHostToDevice) != hipSuccess ||
+      hipMemcpy(buf + off_x, h.data(), h.size() * sizeof(double), hipMemcpyHostToDevice) != hipSuccess ||
+      hipMemset(buf + off_out, 0, (size_t)n * sizeof(int)) != hipSuccess)
+    rc = fail(c, POCS_E_DEVICE, "probe upload failed");
+  const double* d_x = (const double*)(buf + off_x);
+  if (rc == POCS_OK && pocs_launch_probe_discs((const pocs_env_dev*)buf, (const pocs_tables*)c->d_tables.p, n, d_x, d_x + n, d_x + 2 * (size_t)n,
+                                               (int*)(buf + off_out), c->stream) != hipSuccess)
+    rc = fail(c, POCS_E_DEVICE, "probe launch failed");
+  if (rc == POCS_OK && hipStreamSynchronize(c->stream) != hipSuccess) rc = fail(c, POCS_E_DEVICE, "probe kernel failed");
+  if (rc == POCS_OK && hipMemcpy(out, buf + off_out, (size_t)n * sizeof(int), hipMemcpyDeviceToHost) != hipSuccess)
     rc = fail(c, POCS_E_DEVICE, "probe download failed");
   (void)hipFree(buf);
   return rc;

@@ -78,7 +78,52 @@ POCS_HD bool pocs_box_hit(double px, double py, double sn, double cs, double rx,
   return pocs_box_narrow(px, py, sn, cs, rx, ry, o);
 }
 
+// ---- round obstacles (pocs_set_discs) ---------------------------------------------------------------------------------
+// A disc {cx, cy, r} occupies one record of the table, behind the boxes, prepared as its bounding square -- centre, axis (1, 0),
+// hx = hy = r, fields 6 and 7 exactly as pocs_prepare_obstacle forms them for that square -- with ONE difference: ay is -0.0, the
+// marker.  -0.0 is arithmetic-neutral wherever a record is read (|ay| = 0, ay == 0.0, products with it are zeros), so the broad
+// phase, gmm_cull's keep test and its heading-tightened box read the record as the square's and stay conservative (a disc lies
+// inside its square), and the culls' copies of fields 0 .. 5 carry the marker into the kept lists.  A BOX record never holds
+// ay = -0.0 in a table that may hold discs: pocs_prepare_box_beside_discs writes +0.0 for a zero sine (no result of the box test
+// depends on the sign of a zero ay: it is read through ax == 1.0 && ay == 0.0, products and fabs).
+// The test below is exact: the squared distance from the disc's centre to the footprint's box, in the footprint's frame, against
+// r^2, touching included.  The flag is broad phase AND narrow phase, as pocs_box_hit is.
+POCS_HD void pocs_prepare_disc(const double disc3[3], const pocs_footprint* fp, double* rec) {
+  const double sq[5] = {disc3[0], disc3[1], disc3[2], disc3[2], 0.0};
+  pocs_prepare_obstacle(sq, fp, rec);
+  rec[2] = 1.0; rec[3] = -0.0;
+}
+POCS_HD void pocs_prepare_box_beside_discs(const double box5[5], const pocs_footprint* fp, double* rec) {
+  pocs_prepare_obstacle(box5, fp, rec);
+  // a yaw of -0.0 gives ay = -0.0: written as +0.0, so that the marker means a disc.  (fabs of a zero is +0.0 under any
+  // floating-point flags; the nonzero values are kept as they are)
+  rec[3] = rec[3] == 0.0 ? fabs(rec[3]) : rec[3];
+}
+POCS_HD bool pocs_record_is_disc(double ay) { return ay == 0.0 && __builtin_signbit(ay); }
+
+// Narrow phase for a disc record that has passed the broad phase: the operations of the specification, in its order.
+POCS_HD bool pocs_disc_narrow(double px, double py, double sn, double cs, double rx, double ry, const double* o) {
+  const double dx = o[0] - px;
+  const double dy = o[1] - py;
+  const double r = o[4];
+  const double d1 = fma(dx, cs, dy * sn);                         // d in the footprint frame (the box test's own d1, d2)
+  const double d2 = fma(dy, cs, -(dx * sn));
+  const double q1 = fmax(fabs(d1) - rx, 0.0);
+  const double q2 = fmax(fabs(d2) - ry, 0.0);
+  return !(fma(q1, q1, q2 * q2) > r * r);
+}
+// pocs_box_hit for a table that may hold discs: the record's kind is the same in every lane (a wave-uniform branch, as the
+// ax == 1.0 && ay == 0.0 test of pocs_box_narrow is).
+POCS_HD bool pocs_world_hit(double px, double py, double sn, double cs, double rx, double ry, const double* o) {
+  if (fabs(o[0] - px) > o[6] || fabs(o[1] - py) > o[7]) return false;
+  if (pocs_record_is_disc(o[3])) return pocs_disc_narrow(px, py, sn, cs, rx, ry, o);
+  return pocs_box_narrow(px, py, sn, cs, rx, ry, o);
+}
+
 // checkCollision for one pose: true if the footprint touches any of the M obstacles.
+// ROUND (pocs_set_discs with D > 0): the table may hold disc records (pocs_world_hit); ROUND = false is the function as it has
+// always been.
+template <bool ROUND = false>
 POCS_HD bool pocs_pose_collides(double x, double y, double th, const pocs_footprint* fp,
                                 const double* obs, int M, const pocs_tables* T, const pocs_vconst* V = nullptr) {
   if (M <= 0) return false;                     // nothing in reach (k_gmm_step: every obstacle culled): no heading needed
@@ -95,9 +140,33 @@ POCS_HD bool pocs_pose_collides(double x, double y, double th, const pocs_footpr
     py = y + fma(sn, fp->dx, cs * fp->dy);
   }
   bool hit = false;                             // (set under a condition, not or-ed in: see pocs_pair_collides)
-  for (int m = 0; m < M; ++m)
-    if (pocs_box_hit(px, py, sn, cs, fp->hx, fp->hy, obs + m * POCS_OBS_STRIDE)) hit = true;
+  if constexpr (ROUND) {
+    for (int m = 0; m < M; ++m)
+      if (pocs_world_hit(px, py, sn, cs, fp->hx, fp->hy, obs + m * POCS_OBS_STRIDE)) hit = true;
+  } else {
+    for (int m = 0; m < M; ++m)
+      if (pocs_box_hit(px, py, sn, cs, fp->hx, fp->hy, obs + m * POCS_OBS_STRIDE)) hit = true;
+  }
   return hit;
+}
+// One pose against a table that may hold discs, the two kinds apart: bit 0 = touches some box, bit 1 = touches some disc (the
+// flag of pocs_pose_collides<true> is kinds != 0).  The probe's and the host harness' way in.
+POCS_HD unsigned pocs_pose_kinds_touched(double x, double y, double th, const pocs_footprint* fp,
+                                         const double* obs, int M, const pocs_tables* T, const pocs_vconst* V = nullptr) {
+  if (M <= 0) return 0u;
+  double sn, cs;
+  pocs_sincos_tab(th, T, &sn, &cs, V);
+  double px = x, py = y;
+  if (!(fp->dx == 0.0 && fp->dy == 0.0)) {
+    px = x + fma(cs, fp->dx, -(sn * fp->dy));
+    py = y + fma(sn, fp->dx, cs * fp->dy);
+  }
+  unsigned kinds = 0u;
+  for (int m = 0; m < M; ++m) {
+    const double* o = obs + m * POCS_OBS_STRIDE;
+    if (pocs_world_hit(px, py, sn, cs, fp->hx, fp->hy, o)) kinds |= pocs_record_is_disc(o[3]) ? 2u : 1u;
+  }
+  return kinds;
 }
 
 // The same predicate for the two poses a thread of k_gmm_step draws per iteration, with ONE pass over the obstacle
@@ -140,12 +209,26 @@ __device__ __forceinline__ unsigned long long pocs_box_margins_mask(unsigned lon
   return near & __builtin_amdgcn_ballot_w64(!(fmax(m1, m2) > 0.0));
 }
 
-template <bool EAGER, bool CENTRED, class Each>
+// pocs_disc_narrow for the lanes of `pm`, the answer as a lane mask: per lane its operations in its order, balloted.
+__device__ __forceinline__ unsigned long long pocs_disc_narrow_mask(unsigned long long pm, double dx, double dy, double sn, double cs,
+                                                                    double rx, double ry, double r) {
+  const double d1 = fma(dx, cs, dy * sn);
+  const double d2 = fma(dy, cs, -(dx * sn));
+  const double q1 = fmax(fabs(d1) - rx, 0.0);
+  const double q2 = fmax(fabs(d2) - ry, 0.0);
+  return pm & __builtin_amdgcn_ballot_w64(!(fma(q1, q1, q2 * q2) > r * r));
+}
+
+// ROUND: the table may hold disc records; a record's kind is decided by a scalar branch on a ballot of its marker (every lane
+// reads the same record), and `kinds`, where given, receives the two poses' masks for the disc records apart: kinds[h] is the part
+// of mask[h] that discs contributed.
+template <bool EAGER, bool CENTRED, class Each, bool ROUND = false>
 __device__ __forceinline__ void pocs_pair_loop(const double x[2], const double y[2], const double th[2], const pocs_footprint* fp,
                                                const double* obs, int M, const pocs_tables* T, const pocs_vconst* V,
-                                               unsigned long long mask[2], Each each) {
+                                               unsigned long long mask[2], Each each, unsigned long long* kinds = nullptr) {
   const double rx = fp->hx, ry = fp->hy;
   double sn[2], cs[2], px[2], py[2];
+  [[maybe_unused]] unsigned long long k0 = 0ull, k1 = 0ull;
   double ex[2], ey[2];                                             // the footprint's extents along world x and y at the two headings
   bool heading = false;                                            // (wave-uniform) sn, cs, ex, ey hold the two headings' values
   // (until then they hold nothing: said to the compiler, which otherwise zeroes them in front of the loop)
@@ -190,6 +273,19 @@ __device__ __forceinline__ void pocs_pair_loop(const double x[2], const double y
         heading = true;
       }
       // an axis-aligned record (every lane reads the same one): the relative yaw IS the heading, the offset as it is
+      bool disc = false;                                             // (scalar) the record is a disc: ay is -0.0
+      if constexpr (ROUND) {
+        const double ay = a.y;                                       // (a copy: the bits of THIS element are compared)
+        disc = __builtin_amdgcn_ballot_w64(__builtin_bit_cast(unsigned long long, ay) == 0x8000000000000000ull) != 0ull;
+      }
+      if (ROUND && disc) {
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+          if (pm[h] == 0ull) continue;
+          bt[h] = pocs_disc_narrow_mask(pm[h], dx[h], dy[h], sn[h], cs[h], rx, ry, e.x);
+        }
+        if constexpr (ROUND) { k0 |= bt[0]; k1 |= bt[1]; }
+      } else {
       const bool turned = (__builtin_amdgcn_ballot_w64(a.x != 1.0) | __builtin_amdgcn_ballot_w64(a.y != 0.0)) != 0ull;
 #pragma unroll
       for (int h = 0; h < 2; ++h) {
@@ -203,28 +299,39 @@ __device__ __forceinline__ void pocs_pair_loop(const double x[2], const double y
                                         fma(rx, fabs(cr), ry * fabs(sr)), fma(rx, fabs(sr), ry * fabs(cr)));
         }
       }
+      }
       m0 |= bt[0]; m1 |= bt[1];
     }
 #pragma unroll
     for (int h = 0; h < 2; ++h) each(m, h, __builtin_amdgcn_inverse_ballot_w64(bt[h]));
   }
   mask[0] = m0; mask[1] = m1;
+  if constexpr (ROUND) { if (kinds) { kinds[0] = k0; kinds[1] = k1; } }
 }
 
 // The pair's flags as lane masks (bit l: lane l's pose h touches some record; lanes that do not run the call stay 0).
-template <bool EAGER = false, class Each = pocs_each_none>
+template <bool EAGER = false, class Each = pocs_each_none, bool ROUND = false>
 __device__ __forceinline__ void pocs_pair_collides_masks(const double x[2], const double y[2], const double th[2], const pocs_footprint* fp,
                                                          const double* obs, int M, const pocs_tables* T, const pocs_vconst* V,
-                                                         unsigned long long mask[2], Each each = Each()) {
+                                                         unsigned long long mask[2], Each each = Each(), unsigned long long* kinds = nullptr) {
   mask[0] = 0ull; mask[1] = 0ull;
+  if constexpr (ROUND) { if (kinds) { kinds[0] = 0ull; kinds[1] = 0ull; } }
   if (M <= 0) return;
   // (scalar) the loop twice, not one loop behind a merge of (x, y) with (px, py): merged, the centred footprint pays four
   // 64-bit register copies per call for values it already holds
   if (fp->dx == 0.0 && fp->dy == 0.0) {
-    pocs_pair_loop<EAGER, true>(x, y, th, fp, obs, M, T, V, mask, each);
+    if constexpr (ROUND) {
+      pocs_pair_loop<EAGER, true, Each, true>(x, y, th, fp, obs, M, T, V, mask, each, kinds);
+    } else {
+      pocs_pair_loop<EAGER, true>(x, y, th, fp, obs, M, T, V, mask, each);
+    }
   } else {
     asm volatile("; offset footprint");
-    pocs_pair_loop<EAGER, false>(x, y, th, fp, obs, M, T, V, mask, each);
+    if constexpr (ROUND) {
+      pocs_pair_loop<EAGER, false, Each, true>(x, y, th, fp, obs, M, T, V, mask, each, kinds);
+    } else {
+      pocs_pair_loop<EAGER, false>(x, y, th, fp, obs, M, T, V, mask, each);
+    }
   }
 }
 #endif

@@ -220,6 +220,12 @@ struct pocs_ctx {
   // call is served by the kernels' _seg / MC_SEG forms (seg_applied) and the modes of pocs_modes::kSegExcluded and a compound
   // footprint are refused
   int seg_J = 1;
+  // round obstacles (pocs_set_discs): disc_D = 0 is off -- every call is, launch for launch, what it is without this.  D > 0: disc_S
+  // tables of D discs {cx, cy, r}, table min(w, disc_S - 1) in force at waypoint w beside box step min(w, world_S - 1); upload_world
+  // composes the two into the env records (boxes, then discs), every call is served by the kernels' _round / MC_ROUND forms
+  // (discs_applied) and the modes of pocs_modes::kDiscExcluded, a compound footprint and segment checks are refused
+  std::vector<double> discs;             // disc_S x disc_D x 3
+  int disc_D = 0, disc_S = 1;
 
   // host image (headers | chains | initial mixtures) of the NEXT batch, computed while the GPU
   // works on the current one
@@ -352,8 +358,14 @@ inline void reset_results(pocs_ctx* c) {
 // The collision world: M boxes per step, and the record of the device's env array ([world_S] pocs_env_dev) that waypoint w --
 // a launch's waypoint, a tree level's depth -- is tested against.
 inline int world_boxes(const pocs_ctx* c) { return (int)(c->boxes.size() / 5 / (size_t)c->world_S); }
+// Round obstacles are set (pocs_set_discs with D > 0).  The env array then holds max(world_S, disc_S) composed records of
+// world_boxes + disc_D obstacle records each; without discs both are what they have always been.
+inline bool discs_applied(const pocs_ctx* c) { return c->disc_D > 0; }
+inline int env_steps(const pocs_ctx* c) { return discs_applied(c) && c->disc_S > c->world_S ? c->disc_S : c->world_S; }
+inline int env_records(const pocs_ctx* c) { return world_boxes(c) + c->disc_D; }
 inline const pocs_env_dev* world_at(const pocs_ctx* c, int w) {
-  return (const pocs_env_dev*)c->d_env.p + (w < 0 ? 0 : w < c->world_S ? w : c->world_S - 1);
+  const int S = env_steps(c);
+  return (const pocs_env_dev*)c->d_env.p + (w < 0 ? 0 : w < S ? w : S - 1);
 }
 
 inline const pocs_clear_dev* clear_at(const pocs_ctx* c, int w) {
@@ -391,11 +403,18 @@ inline int seg_refuse(pocs_ctx* c, const char* what, pocs_modes::Mode enter) {
   return fail(c, POCS_E_STATE, "%s: segment checks are set (pocs_set_segment_checks); %s", what, pocs_modes::kSegClause);
 }
 
+// Round obstacles are set: as segment checks, one mask (pocs_modes::kDiscExcluded) asked in front of the table and by the setter.
+inline int discs_refuse(pocs_ctx* c, const char* what, pocs_modes::Mode enter) {
+  if (!discs_applied(c) || !(enter & pocs_modes::kDiscExcluded)) return POCS_OK;
+  return fail(c, POCS_E_STATE, "%s: discs are set (pocs_set_discs); %s", what, pocs_modes::kDiscClause);
+}
+
 // May the context enter `enter`, as asked by the call `what`?  The one place that refuses a combination (pocs_modes.hpp).
 inline int may_enter(pocs_ctx* c, const char* what, pocs_modes::Mode enter, unsigned among = pocs_modes::kAll) {
   if (among == pocs_modes::kAll) {                   // (a setter's staged asks in front of its argument checks enter nothing yet)
     if (int r = parts_refuse(c, what, enter)) return r;
     if (int r = seg_refuse(c, what, enter)) return r;
+    if (int r = discs_refuse(c, what, enter)) return r;
   }
   const pocs_modes::Refusal r = pocs_modes::refusal(modes_of(c), enter, among);
   if (r.code == POCS_OK) return POCS_OK;

@@ -463,7 +463,10 @@ __device__ __forceinline__ void gmm_cull_seg(const pocs_gmm_launch& a, gmm_smem<
 //   (pocs_pair_segment_masks, backwards along the run's applied control); lane 0 adds the population count of the lanes whose sample
 //   exists, whose own flag is 0 and some sub-pose of which touches to the block's LDS counter of the run buffer, and the sub-poses'
 //   masks are or-ed into the flags: everything behind is formed from those.  The odd shard's unused twin does not count.
-template <int K, bool STORE, int TB, bool LONE_PRE = false, bool OC = false, bool CL = false, bool FPN = false, bool RG = false, bool SG = false>
+//   RD (pocs_set_discs, D > 0): the kept list may hold disc records; the collision test is pocs_pair_collides_masks' ROUND form, which
+//   decides a record's kind by a scalar branch and ballots the disc's answer into the same masks.  Nothing else differs.
+template <int K, bool STORE, int TB, bool LONE_PRE = false, bool OC = false, bool CL = false, bool FPN = false, bool RG = false, bool SG = false,
+          bool RD = false>
 __device__ __forceinline__ void gmm_units(const pocs_gmm_launch& a, gmm_smem<K, TB, OC, CL, FPN, RG, SG>& sm, const int w, const int r0,
                                           const int ta, const int tb, const double* zpre = nullptr, const int npre = 0) {
   const pocs_tables* const s_tab = &sm.tab;
@@ -583,6 +586,9 @@ __device__ __forceinline__ void gmm_units(const pocs_gmm_launch& a, gmm_smem<K, 
         if (b != 0ull && lane == (int)__builtin_ctzll(b))
           __hip_atomic_fetch_add(&occ[m], (unsigned)__popcll(b), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
       });
+    } else
+    if constexpr (RD) {
+      pocs_pair_collides_masks<false, pocs_each_none, true>(xs, ys, ts, &fp, s_keep, nkeep, s_tab, vc, hits);
     } else {
     POCS_TUNE_COLLIDE(pocs_pair_collides_masks<LONE_PRE>(xs, ys, ts, &fp, s_keep, nkeep, s_tab, vc, hits));
     }
@@ -951,9 +957,10 @@ __device__ __forceinline__ void gmm_close_sums(const pocs_gmm_launch& a, const i
 // the or-ed flags), the tickets and the closers are what they are.  LDS: + 8 KB for the second kept table, + 0.3 KB, and 24 instead of
 // 32 held units, as the clearance form: two blocks per CU in every instantiation.
 template <int K, bool STORE, int TB, bool LONE, bool RISK, bool TREE = false, bool OC = false, bool WORLD = false, bool CL = false, bool FPN = false,
-          bool RG = false, bool SG = false>
+          bool RG = false, bool SG = false, bool RD = false>
 __device__ __forceinline__ void gmm_step_block(const pocs_gmm_launch a) {      // (by value, as a kernel holds its argument)
   typedef gmm_smem<K, TB, OC, CL, FPN, RG, SG> smem_t;
+  static_assert(!(RD && (LONE || TREE || OC || WORLD || CL || FPN || RG || SG)), "round obstacles: the ticket form of a batch or of plans on a small world, a single footprint box, no counts, no segment checks");
   static_assert(!(SG && (LONE || TREE || OC || WORLD || CL || FPN || RG)), "segment checks: the ticket form of a batch or of plans on a small world, a single footprint box, no other counts");
   static_assert(!SG || TB >= 256, "waves 2 and 3 build the second kept list");
   static_assert(!(RG && (LONE || TREE || OC || WORLD || CL || FPN)), "watched regions: the ticket form of a batch or of plans on a small world, no other counts");
@@ -1145,7 +1152,7 @@ __device__ __forceinline__ void gmm_step_block(const pocs_gmm_launch a) {      /
   POCS_STAMP(0);
   for (int ta = t0; ta < t1; ta += SUB) {
     const int tb = (ta + SUB < t1) ? ta + SUB : t1;
-    gmm_units<K, STORE, TB, LONE, OC, CL, FPN, RG, SG>(a, sm, w, r0, ta, tb, s_zpre, ta == t0 ? npre : 0);
+    gmm_units<K, STORE, TB, LONE, OC, CL, FPN, RG, SG, RD>(a, sm, w, r0, ta, tb, s_zpre, ta == t0 ? npre : 0);
     POCS_STAMP(1);
     __syncthreads();
     POCS_STAMP(2);
@@ -1343,6 +1350,18 @@ __global__ __launch_bounds__(TB, POCS_GMM_BLOCKS_PER_CU * TB / 256) void k_gmm_s
 template <int K, bool STORE, int TB>
 __global__ __launch_bounds__(TB, POCS_GMM_BLOCKS_PER_CU * TB / 256) void k_gmm_step_risk_seg(pocs_gmm_launch a) {
   gmm_step_block<K, STORE, TB, false, true, false, false, false, false, false, false, true>(a);
+}
+
+// The forms under round obstacles (RD above; pocs_set_discs with D > 0): kernels of their own names again.  The head stages and culls
+// the composed table with gmm_cull as it is -- a disc record reads as its bounding square there, marker copied -- and the shared memory
+// is the twin's: the same LDS, two blocks per CU in every instantiation.
+template <int K, bool STORE, int TB>
+__global__ __launch_bounds__(TB, POCS_GMM_BLOCKS_PER_CU * TB / 256) void k_gmm_step_round(pocs_gmm_launch a) {
+  gmm_step_block<K, STORE, TB, false, false, false, false, false, false, false, false, false, true>(a);
+}
+template <int K, bool STORE, int TB>
+__global__ __launch_bounds__(TB, POCS_GMM_BLOCKS_PER_CU * TB / 256) void k_gmm_step_risk_round(pocs_gmm_launch a) {
+  gmm_step_block<K, STORE, TB, false, true, false, false, false, false, false, false, false, true>(a);
 }
 
 // The forms under a large collision world (WORLD above): kernels of their own names again.

@@ -139,7 +139,11 @@ __device__ __forceinline__ mc_run_start mc_start(const pocs_mc_launch& a) {
 // free: the OR needs nothing more, and seg_counts[run][s + 1] counts exactly that case -- the particles whose first touching
 // waypoint this is and whose end pose is free.  The sine and cosine of the drive direction are mc_move's own (mc_move_dir).  J and
 // the fractions are read from pocs_seg_dev in device memory (wave-uniform loads); hit counters and counts are formed from the flag.
-enum { MC_PLAIN = 0, MC_COUNTS = 1, MC_STOP = 2, MC_BOXES = 4, MC_CLEAR = 8, MC_PARTS = 16, MC_REGIONS = 32, MC_SEG = 64 };
+//
+// MC_ROUND (pocs_set_discs with D > 0), a flag on top of MC_PLAIN, MC_COUNTS or MC_STOP on k_mc_init and the per-step kernel, never
+// with MC_BOXES, MC_CLEAR, MC_PARTS, MC_REGIONS or MC_SEG: the staged table may hold disc records behind its boxes, and the
+// collision test is pocs_pose_collides<true>, which decides a record's kind by a wave-uniform branch.  Nothing else differs.
+enum { MC_PLAIN = 0, MC_COUNTS = 1, MC_STOP = 2, MC_BOXES = 4, MC_CLEAR = 8, MC_PARTS = 16, MC_REGIONS = 32, MC_SEG = 64, MC_ROUND = 128 };
 static_assert(POCS_MAX_OBSTACLES <= 64, "a particle's touched boxes are a 64-bit mask");
 
 // pocs_pose_collides with the touched boxes as a mask (the flag: mask != 0, as the plain form's).
@@ -449,6 +453,9 @@ __global__ __launch_bounds__(POCS_BLOCK) void k_mc_init(pocs_mc_launch a) {
       mc_wave_box_hits(h != 0u, mask, wd.M, box.c);
     } else if constexpr ((MODE & MC_PARTS) != 0) {
       h = pocs_pose_collides_parts(x, y, t, pt.p, pt.F, wd.obs, wd.M, wd.tab) ? 1u : 0u;
+    } else if constexpr ((MODE & MC_ROUND) != 0) {
+      static_assert((MODE & MC_ROUND) == 0 || (MODE & (MC_BOXES | MC_CLEAR | MC_PARTS | MC_REGIONS | MC_SEG)) == 0, "round obstacles: on top of the three plain modes alone");
+      h = pocs_pose_collides<true>(x, y, t, &wd.fp, wd.obs, wd.M, wd.tab) ? 1u : 0u;
     } else {
       h = pocs_pose_collides(x, y, t, &wd.fp, wd.obs, wd.M, wd.tab) ? 1u : 0u;
     }
@@ -581,6 +588,13 @@ __device__ __forceinline__ void mc_step_body(const pocs_mc_launch& a) {
         if (in != 0u && v.hits[i] != 0u) in = 0u;      // (in a region, but collided at an earlier waypoint)
       }
       mc_wave_region_hits(in, rg.G, a.reg_counts + ((size_t)blockIdx.y * (size_t)a.W + (size_t)a.step + 1) * POCS_MAX_REGIONS);
+    } else if constexpr ((MODE & MC_ROUND) != 0) {
+      static_assert((MODE & MC_ROUND) == 0 || (MODE & (MC_BOXES | MC_CLEAR | MC_PARTS | MC_REGIONS | MC_SEG)) == 0, "round obstacles: on top of the three plain modes alone");
+      if (pocs_pose_collides<true>(nx, ny, nt, &wd.fp, wd.obs, wd.M, wd.tab)) {
+        const uint32_t old = v.hits[i];
+        v.hits[i] = old + 1u;
+        first += old == 0u ? 1u : 0u;
+      }
     } else {
     if (pocs_pose_collides(nx, ny, nt, &wd.fp, wd.obs, wd.M, wd.tab)) {
       const uint32_t old = v.hits[i];                // the counter is in hand exactly when the particle collides

@@ -60,7 +60,7 @@ int check_common(pocs_ctx* c) {
   // The reference receives its collision world through the module constructor (sim(penv),
   // mcsimplugin.cpp:12 -> MCSimulator.h:139-156).  A context that was never given one would answer
   // 0.0 for every run: refuse instead.  An explicitly empty world (clearObstacles) is allowed.
-  if (!c->have_obstacles)
+  if (!c->have_obstacles && !discs_applied(c))       // (a context given discs and never boxes has a world: M = 0)
     return fail(c, POCS_E_STATE, "no collision world: pocs_set_obstacles / addObstacle / clearObstacles missing");
   return POCS_OK;
 }
@@ -106,7 +106,7 @@ void prepare_parts(const pocs_footprint* parts, int F, const double* boxes, int 
 // the exchange and a bound moments buffer) are the calls they are with L = 0; the step API never asks.
 bool clearance_applied(const pocs_ctx* c) {
   using namespace pocs_modes;
-  return c->clr_L > 0 && !parts_applied(c) && !seg_applied(c) && !in_mode(c, kTree | kLargeWorld | kObsCounts | kShard | kMoments);
+  return c->clr_L > 0 && !parts_applied(c) && !seg_applied(c) && !discs_applied(c) && !in_mode(c, kTree | kLargeWorld | kObsCounts | kShard | kMoments);
 }
 
 // Watched regions: the record the kernels read (pocs_regions_dev) -- region g prepared as upload_world prepares an obstacle, for
@@ -130,7 +130,7 @@ void prepare_regions(const pocs_footprint& fp, const double* boxes, const int* k
 // L > 0 are the calls they are with G = 0; the step API never asks.
 bool regions_applied(const pocs_ctx* c) {
   using namespace pocs_modes;
-  return c->reg_G > 0 && c->clr_L == 0 && !parts_applied(c) && !seg_applied(c) && !in_mode(c, kTree | kLargeWorld | kObsCounts | kShard | kMoments);
+  return c->reg_G > 0 && c->clr_L == 0 && !parts_applied(c) && !seg_applied(c) && !discs_applied(c) && !in_mode(c, kTree | kLargeWorld | kObsCounts | kShard | kMoments);
 }
 
 // Segment checks (J > 1) as the kernels read them (pocs_seg_dev): J and the fractions f_j = j / J.  (pocs_probe_device_segment
@@ -145,12 +145,23 @@ void prepare_segment(int J, pocs_seg_dev* out) {
 int upload_world(pocs_ctx* c) {                // tables + the collision world: one record (obstacle records, footprint) per step of the schedule
   if (int r = upload_tables(c)) return r;
   if (c->env_dirty) {
-    const size_t S = (size_t)c->world_S;
+    const size_t Sb = (size_t)c->world_S, S = (size_t)env_steps(c);
     const int M = world_boxes(c);
     std::vector<pocs_env_dev> env(S);
     memset(env.data(), 0, S * sizeof(pocs_env_dev));
     pocs_parts_dev parts;
     for (size_t s = 0; s < S; ++s) {
+      if (discs_applied(c)) {                        // round obstacles: record s is box step min(s, Sb - 1), then disc step min(s, Sd - 1)
+        const size_t sb = s < Sb ? s : Sb - 1, sd = s < (size_t)c->disc_S ? s : (size_t)c->disc_S - 1;
+        const int D = c->disc_D;
+        env[s].fp = c->fp;
+        env[s].M = M + D;
+        for (int m = 0; m < M; ++m)
+          pocs_prepare_box_beside_discs(&c->boxes[(sb * (size_t)M + (size_t)m) * 5], &c->fp, &env[s].obs[(size_t)m * POCS_OBS_STRIDE]);
+        for (int d = 0; d < D; ++d)
+          pocs_prepare_disc(&c->discs[(sd * (size_t)D + (size_t)d) * 3], &c->fp, &env[s].obs[(size_t)(M + d) * POCS_OBS_STRIDE]);
+        continue;
+      }
       if (parts_applied(c)) {                        // (a compound footprint: the records of the covering part; no large world then)
         prepare_parts(c->fp_parts, c->fp_F, c->boxes.data() + s * (size_t)M * 5, M, &env[s], s == 0 ? &parts : nullptr);
         continue;
@@ -168,10 +179,10 @@ int upload_world(pocs_ctx* c) {                // tables + the collision world: 
       HIPCHK(c, hipMemcpy(c->d_parts.p, &parts, sizeof parts, hipMemcpyHostToDevice));
     }
     if (c->clr_L > 0 && !large_world(c)) {           // the second record set, next to the first: the footprint grown by d_L
-      std::vector<pocs_clear_dev> clr(S);
-      for (size_t s = 0; s < S; ++s) prepare_clearance(c->fp, c->clr_d, c->clr_L, c->boxes.data() + s * (size_t)M * 5, M, &clr[s]);
-      if (int r = ensure(c, c->d_clr, S * sizeof(pocs_clear_dev))) return r;
-      HIPCHK(c, hipMemcpy(c->d_clr.p, clr.data(), S * sizeof(pocs_clear_dev), hipMemcpyHostToDevice));
+      std::vector<pocs_clear_dev> clr(Sb);             // (per step of the BOXES' schedule: the levels are not applied under discs)
+      for (size_t s = 0; s < Sb; ++s) prepare_clearance(c->fp, c->clr_d, c->clr_L, c->boxes.data() + s * (size_t)M * 5, M, &clr[s]);
+      if (int r = ensure(c, c->d_clr, Sb * sizeof(pocs_clear_dev))) return r;
+      HIPCHK(c, hipMemcpy(c->d_clr.p, clr.data(), Sb * sizeof(pocs_clear_dev), hipMemcpyHostToDevice));
     }
     if (seg_applied(c)) {                            // the segment checks' record, next to the world
       pocs_seg_dev sg;
@@ -522,7 +533,8 @@ bool whole_call_exchanges(const pocs_ctx* c) { return c->xchg_connected && c->sh
 void fill_gmm_world(const pocs_ctx* c, pocs_gmm_launch* a, int w) {
   a->env = world_at(c, w);
   a->tables = (const pocs_tables*)c->d_tables.p;
-  a->M = world_boxes(c);
+  a->M = env_records(c);                             // (the boxes, and behind them the discs in force)
+  a->round = discs_applied(c) ? 1 : 0;               // (nonzero: the sampling launch is the _round form)
   if (!parts_applied(c)) {                           // (a compound footprint's values live in device memory: the launch carries none)
     a->fp = c->fp;
     a->fp_rr = sqrt(c->fp.hx * c->fp.hx + c->fp.hy * c->fp.hy); a->fp_phi = atan2(c->fp.hy, c->fp.hx);
@@ -593,8 +605,8 @@ int enqueue_advance(Issuer is, int w) {
 // (Under a large world the cull of waypoint w reads param[w] ahead of the sampling launch; the lone form builds param[w] in its own
 // heads, so a call of one run takes the ticket form there: the same bits.)
 // (Under clearance levels and watched regions too: the counting forms exist as the ticket form only.)
-// (And under a compound footprint: the parts form exists as the ticket form only.  And under segment checks: the same.)
-bool lone_call(const pocs_ctx* c) { return c->opt_lone && !large_world(c) && !clearance_applied(c) && !regions_applied(c) && !parts_applied(c) && !seg_applied(c) && c->batch == 1 && !c->tree.n && !c->ext_moments && !(c->xchg_connected && c->shard_first >= 0) && !risk_active(c); }
+// (And under a compound footprint: the parts form exists as the ticket form only.  And under segment checks and discs: the same.)
+bool lone_call(const pocs_ctx* c) { return c->opt_lone && !large_world(c) && !clearance_applied(c) && !regions_applied(c) && !parts_applied(c) && !seg_applied(c) && !discs_applied(c) && c->batch == 1 && !c->tree.n && !c->ext_moments && !(c->xchg_connected && c->shard_first >= 0) && !risk_active(c); }
 void set_risk(pocs_ctx* c, pocs_gmm_launch* a) {      // under a risk bound the launch is k_gmm_step_risk (whole calls of plans or on a tree only)
   a->risk = 1;
   a->stop = a->sync + c->sync.stop;
@@ -993,7 +1005,7 @@ bool mc_counts_active(const pocs_ctx* c) { return c->opt_mc_wp || c->opt_obs_cou
 // And a call under a compound footprint: the parts live in the per-step kernels too (MC_PARTS).
 // And a call that counts watched regions: they live in the per-step kernels as well (MC_REGIONS).
 // And a call under segment checks: the sub-poses live in the per-step kernels (MC_SEG).
-bool mc_fused_form(const pocs_ctx* c) { return c->opt_fused && !mc_stop_active(c) && !clearance_applied(c) && !parts_applied(c) && !regions_applied(c) && !seg_applied(c); }
+bool mc_fused_form(const pocs_ctx* c) { return c->opt_fused && !mc_stop_active(c) && !clearance_applied(c) && !parts_applied(c) && !regions_applied(c) && !seg_applied(c) && !discs_applied(c); }      // (and under discs: MC_ROUND lives in the per-step kernels)
 // d_total, u64 words: [R] collided particles per run | counts active: [R][W] first collisions | [R] u32 stop words
 size_t mc_total_words(const pocs_ctx* c) {
   const size_t R = (size_t)c->batch, W = (size_t)c->W;
@@ -1053,6 +1065,7 @@ int enqueue_mc_all(Issuer is, long long first, long long count, bool prof) {
     a.seg = (const pocs_seg_dev*)c->d_seg.p; a.seg_counts = (unsigned long long*)c->d_segct.p;
     if (int r = is.launch(pocs_launch_zero_counts, 0, a.seg_counts, seg_count_words(c))) return r;
   }
+  if (discs_applied(c)) a.round = 1;                 // (round obstacles: the MC_ROUND forms of k_mc_init and the per-step kernel)
   if (c->plans.n) {
     a.run_plan = (const double*)c->d_runplan.p;      // every run its own start mean and steps
   } else {

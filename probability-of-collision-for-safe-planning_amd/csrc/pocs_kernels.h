@@ -206,6 +206,11 @@ struct pocs_gmm_launch {
   // [0..2] of the run -- and the samples whose own pose is free and some sub-pose touches are counted
   const pocs_seg_dev* seg;
   unsigned long long* seg_counts; // [nruns][W]; zeroed by pocs_launch_zero_counts at the head of the call's launches
+  // round obstacles (pocs_set_discs with D > 0; behind everything else again): nonzero = the launch is the kernel's _round form (ticket
+  // form, with or without the risk bound; never LONE, TREE, OC, WORLD, CL, parts, regions or segment checks): the table in `env` may
+  // hold disc records behind its boxes (pocs_collide.h), M counts both
+  int round;
+  int round_pad;
 };
 #define POCS_MAX_WORLD_RECORDS 4096   // = POCS_MAX_WORLD_BOXES (include/pocs.h; pocs_ctx.hpp checks)
 #define POCS_CULL_BLOCK 256           // k_world_cull
@@ -284,6 +289,11 @@ struct pocs_mc_launch {               // blockIdx.y = run of the batch, like poc
   // touching waypoint this is and whose end pose is free are counted
   const pocs_seg_dev* seg;
   unsigned long long* seg_counts;      // [nruns][W]; zeroed inside the graph like obs_counts
+  // round obstacles (pocs_set_discs with D > 0; behind everything else again): nonzero = the MC_ROUND forms of k_mc_init and
+  // k_mc_step_counts (per-step launches only, every wp_mode; never with a large world, per-box counts, levels, parts, regions or
+  // segment checks): the table in `env` may hold disc records behind its boxes
+  int round;
+  int round_pad;
 };
 
 
@@ -322,6 +332,10 @@ hipError_t pocs_launch_probe_regions(const pocs_regions_dev* regions, int G, con
 hipError_t pocs_launch_probe_segment(const pocs_env_dev* env, const pocs_seg_dev* seg, const pocs_tables* tables, double u0, double u1,
                                      double u2, int backward, int n, const double* x, const double* y, const double* th, int* mask_out,
                                      hipStream_t s);
+// one block; poses n x (x, y, th) by component; env: the composed records (boxes, then discs) and the footprint.  out[i]: bit 0 = pose
+// i touches some box, bit 1 = some disc (the single-pose form on the full table), bit 8 should the pair form ever disagree with it
+hipError_t pocs_launch_probe_discs(const pocs_env_dev* env, const pocs_tables* tables, int n, const double* x, const double* y,
+                                   const double* th, int* out, hipStream_t s);
 // one thread per case; K / seeds / wp / n_total: n; w / alive / out: n rows of POCS_MAX_GAUSSIANS (case i uses the first K[i]): raw weights
 // and alive flags in, cumulative component counts out (pocs_normalise_weights + pocs_component_counts, as advance_finish and
 // speculate_counts call them)

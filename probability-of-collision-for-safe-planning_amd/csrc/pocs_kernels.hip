@@ -54,6 +54,18 @@ hipError_t with_K(const int K, F f) {
 hipError_t pocs_launch_gmm_step(int K, const pocs_gmm_launch& a, hipStream_t s) {
   return with_K(K, [&](auto k) {
     constexpr int KK = decltype(k)::value, TB = POCS_GMM_BLOCK_OF(KK);
+    if (a.round) {                                     // round obstacles: the ticket forms whose table may hold disc records
+      if (a.lone || a.obs_counts || a.world || a.tree_parent || a.exchange_in_tail || a.clr || a.parts || a.regions || a.seg ||
+          a.M > POCS_MAX_OBSTACLES || (a.risk && (!a.stop || !a.surv)))
+        return hipErrorInvalidValue;
+      if (a.risk) {
+        if (a.store) hipLaunchKernelGGL((k_gmm_step_risk_round<KK, true, TB>), dim3(a.blocks), dim3(TB), 0, s, a);
+        else         hipLaunchKernelGGL((k_gmm_step_risk_round<KK, false, TB>), dim3(a.blocks), dim3(TB), 0, s, a);
+      } else {
+        if (a.store) hipLaunchKernelGGL((k_gmm_step_round<KK, true, TB>), dim3(a.blocks), dim3(TB), 0, s, a);
+        else         hipLaunchKernelGGL((k_gmm_step_round<KK, false, TB>), dim3(a.blocks), dim3(TB), 0, s, a);
+      }
+    } else
     if (a.seg) {                                       // segment checks: the ticket forms that also test the sub-poses on the way in
       if (a.lone || a.obs_counts || a.world || a.tree_parent || a.exchange_in_tail || a.clr || a.parts || a.regions || !a.seg_counts || !a.chain ||
           a.M > POCS_MAX_OBSTACLES || (a.risk && (!a.stop || !a.surv)))
@@ -211,6 +223,11 @@ hipError_t pocs_launch_mc_tree_step(int nblk, const pocs_mc_launch& a, hipStream
 
 hipError_t pocs_launch_mc_init(int nblk, const pocs_mc_launch& a, hipStream_t s) {
   if ((a.wp_mode != 0 && !a.wp_counts) || (a.obs_counts && !a.wp_mode)) return hipErrorInvalidValue;
+  if (a.round) {                                      // round obstacles: the MC_ROUND forms (a small world, no counts per box, level or region, one footprint box)
+    if (a.world || a.obs_counts || a.clr || a.parts || a.regions || a.seg) return hipErrorInvalidValue;
+    if (a.wp_mode) hipLaunchKernelGGL(k_mc_init<MC_COUNTS | MC_ROUND>, dim3(nblk, a.nruns), dim3(POCS_BLOCK), 0, s, a);
+    else           hipLaunchKernelGGL(k_mc_init<MC_PLAIN | MC_ROUND>, dim3(nblk, a.nruns), dim3(POCS_BLOCK), 0, s, a);
+  } else
   if (a.parts) {                                      // a compound footprint: the MC_PARTS forms (a small world, no per-box counts, no levels)
     if (a.world || a.obs_counts || a.clr || a.parts_F < 2 || a.parts_F > POCS_MAX_FOOTPRINT_PARTS) return hipErrorInvalidValue;
     if (a.wp_mode) hipLaunchKernelGGL(k_mc_init<MC_COUNTS | MC_PARTS>, dim3(nblk, a.nruns), dim3(POCS_BLOCK), 0, s, a);
@@ -239,6 +256,21 @@ hipError_t pocs_launch_mc_init(int nblk, const pocs_mc_launch& a, hipStream_t s)
 hipError_t pocs_launch_mc_step(int nblk, const pocs_mc_launch& a, hipStream_t s) {
   const dim3 grid(nblk, a.nruns), block(POCS_BLOCK);
   if ((a.wp_mode != 0 && !a.wp_counts) || (a.obs_counts && !a.wp_mode)) return hipErrorInvalidValue;
+  if (a.round) {                                      // round obstacles: the MC_ROUND forms of the three modes
+    if (a.world || a.obs_counts || a.clr || a.parts || a.regions || a.seg || a.step < 0 || a.step + 1 >= a.W ||
+        (a.wp_mode == 2 && (!a.wp_stop || a.wp_n < 1)))
+      return hipErrorInvalidValue;
+    if (a.wp_mode == 2) {
+      if (a.nontemporal) hipLaunchKernelGGL((k_mc_step_counts<true, MC_STOP | MC_ROUND>), grid, block, 0, s, a);
+      else               hipLaunchKernelGGL((k_mc_step_counts<false, MC_STOP | MC_ROUND>), grid, block, 0, s, a);
+    } else if (a.wp_mode == 1) {
+      if (a.nontemporal) hipLaunchKernelGGL((k_mc_step_counts<true, MC_COUNTS | MC_ROUND>), grid, block, 0, s, a);
+      else               hipLaunchKernelGGL((k_mc_step_counts<false, MC_COUNTS | MC_ROUND>), grid, block, 0, s, a);
+    } else {
+      if (a.nontemporal) hipLaunchKernelGGL((k_mc_step_counts<true, MC_PLAIN | MC_ROUND>), grid, block, 0, s, a);
+      else               hipLaunchKernelGGL((k_mc_step_counts<false, MC_PLAIN | MC_ROUND>), grid, block, 0, s, a);
+    }
+  } else
   if (a.seg) {                                        // segment checks: the MC_SEG forms of the two counting modes
     if (a.world || a.obs_counts || a.clr || a.parts || a.regions || !a.seg_counts || a.wp_mode == 0 || a.step < 0 || a.step + 1 >= a.W ||
         (a.wp_mode == 2 && (!a.wp_stop || a.wp_n < 1)))
@@ -337,6 +369,7 @@ hipError_t pocs_launch_mc_fused(int nblk, const pocs_mc_launch& a, hipStream_t s
   if (a.parts) return hipErrorInvalidValue;           // (a compound footprint: the per-step form)
   if (a.regions) return hipErrorInvalidValue;         // (watched regions: the per-step form)
   if (a.seg) return hipErrorInvalidValue;             // (segment checks: the per-step form)
+  if (a.round) return hipErrorInvalidValue;           // (round obstacles: the per-step form)
   if (a.world) return hipErrorInvalidValue;           // (a large world is not staged: no fused form)
   if (a.obs_counts) {
     if (a.env_steps > 1) hipLaunchKernelGGL(k_mc_fused_sched<MC_COUNTS | MC_BOXES>, dim3(nblk, a.nruns), dim3(POCS_BLOCK), 0, s, a);
@@ -734,6 +767,57 @@ hipError_t pocs_launch_probe_counts(int n, const int* K, const double* w, const 
                                     const double* n_total, double* out, hipStream_t s) {
   if (n < 1 || n > (1 << 20) || !K || !w || !alive || !seeds || !wp || !n_total || !out) return hipErrorInvalidValue;
   hipLaunchKernelGGL(k_probe_counts, dim3((unsigned)((n + POCS_BLOCK - 1) / POCS_BLOCK)), dim3(POCS_BLOCK), 0, s, n, K, w, alive, seeds, wp, n_total, out);
+  return hipGetLastError();
+}
+// The footprint-against-world test on poses, a footprint, boxes and discs the caller picks (pocs_probe_device_discs: a test hook beside
+// k_probe_segment): ONE block stages the tables and the composed records as the kernels' heads do and asks, per pose, the functions
+// the kernels ask.  Bit 0: the pose touches some box, bit 1: some disc -- pocs_pose_kinds_touched, the single-pose form's operations
+// with the two kinds apart -- and pocs_pose_collides<true> as the MC kernels call it must say (bits != 0).  Then
+// pocs_pair_collides_masks' ROUND form as k_gmm_step_round calls it, pose 2 p with pose 2 p + 1 (an odd last pose with itself), its
+// disc masks handed out: bit 8 is set in a pose's answer should the two forms ever disagree.
+__global__ __launch_bounds__(POCS_BLOCK) void k_probe_discs(const pocs_env_dev* __restrict__ env, const pocs_tables* __restrict__ tables, int n,
+                                                            const double* __restrict__ x, const double* __restrict__ y, const double* __restrict__ th,
+                                                            int* __restrict__ out) {
+  __shared__ pocs_tables s_tab;
+  __shared__ __attribute__((aligned(16))) double s_obs[POCS_MAX_OBSTACLES * POCS_OBS_STRIDE];
+  stage_tables(tables, &s_tab);
+  for (int j = threadIdx.x; j < POCS_MAX_OBSTACLES * POCS_OBS_STRIDE; j += POCS_BLOCK) s_obs[j] = env->obs[j];
+  __syncthreads();
+  const int M = env->M < POCS_MAX_OBSTACLES ? env->M : POCS_MAX_OBSTACLES;
+  const pocs_footprint fp = env->fp;
+  POCS_VCONST(vc_);
+  const int npairs = (n + 1) / 2;
+  // (every lane of a wave makes every trip: the pair form ballots)
+  for (int p0 = (int)threadIdx.x - (int)(threadIdx.x & 63); p0 < npairs; p0 += POCS_BLOCK) {
+    const int p = p0 + (int)(threadIdx.x & 63);
+    const bool live = p < npairs;
+    const int i0 = live ? 2 * p : 0, i1 = live && i0 + 1 < n ? i0 + 1 : i0;
+    const double xs[2] = {x[i0], x[i1]}, ys[2] = {y[i0], y[i1]}, ts[2] = {th[i0], th[i1]};
+    unsigned single[2];
+    bool bad[2];
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+      single[h] = pocs_pose_kinds_touched(xs[h], ys[h], ts[h], &fp, s_obs, M, &s_tab);
+      bad[h] = pocs_pose_collides<true>(xs[h], ys[h], ts[h], &fp, s_obs, M, &s_tab) != (single[h] != 0u);
+    }
+    unsigned long long all[2], disc[2];
+    pocs_pair_collides_masks<false, pocs_each_none, true>(xs, ys, ts, &fp, s_obs, M, &s_tab, &vc_, all, pocs_each_none(), disc);
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+      const bool any = __builtin_amdgcn_inverse_ballot_w64(all[h]), round = __builtin_amdgcn_inverse_ballot_w64(disc[h]);
+      // (a pose that touches a box AND a disc: the pair form says "any" and "disc"; the box bit is not handed out apart)
+      if (any != (single[h] != 0u) || round != ((single[h] & 2u) != 0u)) bad[h] = true;
+    }
+    if (live) {
+      out[i0] = (int)(single[0] | ((bad[0] || (i1 == i0 && single[1] != single[0])) ? 256u : 0u));
+      if (i1 != i0) out[i1] = (int)(single[1] | (bad[1] ? 256u : 0u));
+    }
+  }
+}
+hipError_t pocs_launch_probe_discs(const pocs_env_dev* env, const pocs_tables* tables, int n, const double* x, const double* y,
+                                   const double* th, int* out, hipStream_t s) {
+  if (!env || !tables || n < 1 || !x || !y || !th || !out) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(k_probe_discs, dim3(1), dim3(POCS_BLOCK), 0, s, env, tables, n, x, y, th, out);
   return hipGetLastError();
 }
 hipError_t pocs_launch_fill(void* dst, long long bytes, hipStream_t s) {

@@ -87,6 +87,12 @@ static const char* const kPartsClause = "a compound footprint is served by whole
 constexpr unsigned kSegExcluded = kTree | kShard | kXchgCreated | kXchgConnected | kMoments | kLargeWorld | kObsCounts | kSequence;
 static const char* const kSegClause = "segment checks are served by whole calls on one GPU over worlds of at most 64 boxes, with a single footprint box and without per-box counts";
 
+// Round obstacles (pocs_set_discs with D > 0) are no mode of the table either: they change results, so what they are not built for
+// is refused in both directions -- and a compound footprint and segment checks, which are no bits of a mode word, are asked about
+// beside this mask (discs_refuse, pocs_ctx.hpp; the three setters).
+constexpr unsigned kDiscExcluded = kTree | kShard | kXchgCreated | kXchgConnected | kMoments | kLargeWorld | kObsCounts | kSequence;
+static const char* const kDiscClause = "discs are served by whole calls on one GPU over worlds of at most 64 records, with a single footprint box, without per-box counts and segment checks";
+
 // May a context whose active modes are `active` enter `enter`?  `among`: the modes asked about now -- a setter whose argument
 // checks stand between two of its combination checks asks in stages, so that a call with two faults keeps its code.
 struct Refusal { int code; Mode by; const char* clause; };

@@ -183,6 +183,29 @@ def moving_boxes(boxes0, velocity, S):
     return out
 
 
+def moving_discs(tracks, r):
+    """A disc schedule (Context.set_discs) from per-waypoint centres, the counterpart of moving_boxes: tracks of shape (S, D, 2) --
+    tracks[s, d] the centre of disc d at waypoint s, as a predictor hands it over -- or (S, 2) for a single disc; r a radius for
+    all discs or one per disc (D).  Returns S x D x 3 = (cx, cy, r): the values as they are, no arithmetic.  ValueError for a
+    shape that is neither, an empty track, or a radius that is not positive and finite."""
+    t = np.asarray(tracks, dtype=np.float64)
+    if t.ndim == 2 and t.shape[1] == 2:
+        t = t.reshape(t.shape[0], 1, 2)
+    if t.ndim != 3 or t.shape[2] != 2 or t.shape[0] < 1 or t.shape[1] < 1:
+        raise ValueError("tracks of shape %s, (S, D, 2) with S, D >= 1 expected" % (t.shape,))
+    rr = np.asarray(r, dtype=np.float64).ravel()
+    if rr.size == 1:
+        rr = np.repeat(rr, t.shape[1])
+    if rr.size != t.shape[1]:
+        raise ValueError("%d radii for %d discs" % (rr.size, t.shape[1]))
+    if not (np.all(np.isfinite(rr)) and np.all(rr > 0.0)):
+        raise ValueError("a disc's radius is positive and finite")
+    out = np.empty((t.shape[0], t.shape[1], 3))
+    out[:, :, :2] = t
+    out[:, :, 2] = rr[None, :]
+    return out
+
+
 def goal_region(plan, half_x, half_y):
     """The goal tolerance of a plan as a watched region (Context.set_regions): the box (cx, cy, half_x, half_y, yaw) centred at
     the plan's last waypoint and turned to its heading.  `plan` is a dict with `traj` (W x 3) or the W x 3 array itself.
