@@ -622,6 +622,41 @@ int pocs_get_segment_counts(pocs_ctx* ctx, unsigned long long* out, int cap);
 int pocs_set_discs(pocs_ctx* ctx, const double* discs /* S x D x {cx, cy, r} */, int D, int S);
 int pocs_get_discs(const pocs_ctx* ctx, int* D, int* S);
 
+/* ---- uncertain discs: a position covariance per disc and step, for both estimators (ours) -----------
+ * A disc's centre is a prediction: a pedestrian two seconds ahead is known to decimetres.  For every disc d and disc step s the caller
+ * may give a position covariance {sxx, sxy, syy} (m^2); table min(w, Sd - 1) is in force at waypoint w, like the discs' own.
+ *   factor    the host factorises a row as the initial covariance is factorised, in double arithmetic and this order:
+ *             l00 = sqrt(sxx), l10 = sxy / l00, l11 = sqrt(syy - l10 l10).  A row of three zeros is a certain disc: it draws nothing.
+ *   draw      a pose is one possible world.  For pose index i (the global sample index of a GMM call, the global particle index
+ *             first + i of an MC call), the run's effective seed, disc index d in the caller's table and waypoint word v:
+ *             words = Philox4x32-7(ctr = (lo32(i >> 1), hi32(i >> 1), v, 5 << 16 | d), key = seed) -- stream 5 --, h = i & 1,
+ *             (z0, z1) = the table-form Box-Muller pair of (words[2 h], words[2 h + 1]); |z| < 6.661.
+ *   displace  cx' = fma(l00, z0, cx), cy' = fma(l11, z1, fma(l10, z0, cy)).
+ *   word      GMM calls: v = w, a fresh deviation per waypoint, as the samples themselves are fresh.  The GMM estimator carries only the
+ *             robot's mixture across waypoints, so it treats the deviations as INDEPENDENT IN TIME; against a persistent truth that errs
+ *             to the high side.  MC calls: persistent = POCS_DISC_NOISE_PERSISTENT gives v = 0, a particle's world keeps its deviation z,
+ *             the obstacle's track is c_s + L_s z and a covariance that grows with s is a prediction that fans out;
+ *             POCS_DISC_NOISE_PER_WAYPOINT gives v = w.  Under plans every plan runs on its own clock from 0, as everywhere.
+ *   flag      broad phase AND narrow phase, as for every record: the broad phase on the NOMINAL centre with the record's fields 6 and 7
+ *             grown by 6.67 |l00| and 6.67 (|l10| + |l11|) (conservative: |z| < 6.661), the narrow phase the disc test above on
+ *             (cx', cy').  A certain disc, a box and every call without covariances are what they are without this; a pose touches
+ *             the world when it touches a box or a disc, certain or displaced, and every result is formed from that flag.
+ * pocs_set_disc_covariances: cov = S x D x {sxx, sxy, syy}; D and S must equal those of the discs in force (POCS_E_ARG otherwise;
+ * POCS_E_STATE without discs).  A null pointer with D = 0 clears; all rows zero is the same as cleared: every call is then, launch for
+ * launch, the discs call it is without this.  POCS_E_ARG, what was in force kept: a value that is not finite, a row that is neither
+ * zeros nor has sxx > 0 and syy - l10 l10 > 0, a persistent other than 0 or 1.  POCS_E_ORDER inside a begin/end sequence.  Like every
+ * setter it ends run-ahead serving.  pocs_set_discs with the same D and S keeps the covariances; another D or S, or clearing, drops
+ * them.  They survive pocs_set_footprint, pocs_set_obstacles, pocs_set_obstacle_schedule and pocs_set_plans (re-composed).  Covariances
+ * of the same shape with other numbers are overwritten in place and the cached graph is replayed (pocs_get_graph_captures does not
+ * move): the planning cycle.  pocs_get_disc_covariances writes the table and the setting and returns S * D * 3 (0 when none,
+ * POCS_E_BUFFER for a short buffer).
+ * SERVED, REFUSED and NOT applied: exactly what discs serve, refuse and do not apply (the block above); covariances need discs, so
+ * there is no refusal of their own. */
+#define POCS_DISC_NOISE_PER_WAYPOINT 0
+#define POCS_DISC_NOISE_PERSISTENT   1
+int pocs_set_disc_covariances(pocs_ctx* ctx, const double* cov /* S x D x {sxx, sxy, syy} */, int D, int S, int persistent);
+int pocs_get_disc_covariances(const pocs_ctx* ctx, double* out, int cap, int* persistent);   /* returns S*D*3, 0 when none */
+
 /* ---- results of the last run, for audits and parity tests ------------------------------- */
 int pocs_get_path_length(const pocs_ctx* ctx);
 int pocs_get_waypoint_probabilities(pocs_ctx* ctx, double* out, int cap);         /* `probabilities`, MCSimulator.h:660,678,817 */
@@ -736,6 +771,15 @@ int pocs_probe_device_discs(pocs_ctx* ctx, const double* fp4, const double* boxe
    bit 1: some disc -- through the MC kernels' single-pose form on the full table --, bit 8 should the sampling kernel's two-pose
    lane-mask form (poses 2 j, 2 j + 1) ever disagree.  It reads nothing of the context's world or modes, so it is never refused.
    POCS_E_ARG for a null pointer, n outside 1 .. 2^20, M + D out of range, a bad footprint, box or disc and ANY input that is not finite. */
+int pocs_probe_device_disc_noise(pocs_ctx* ctx, const double* fp4, const double* discs /* D x 3 */, const double* cov /* D x 3 */, int D,
+                                 uint64_t seed, uint32_t waypoint_word, unsigned long long first /* even */, int n /* even */,
+                                 const double* poses_xyt, double* centres_out /* n x D x 2 */, unsigned* flags_out /* n */);
+/* TEST HOOK beside pocs_probe_device_discs, equally self-contained: uncertain discs on the DEVICE for the caller's own footprint, D <= 16
+   discs {cx, cy, r} and covariances {sxx, sxy, syy} (zeros: a certain disc), prepared as the library prepares the context's.  Pose i has
+   index first + i, the seed and the waypoint word are the caller's.  centres_out: the device's displaced centres; bit d of flags_out[i]:
+   pose i touches displaced disc d -- through the MC kernels' single-pose form --, bit 31 should the sampling kernel's two-pose lane-mask
+   form (poses 2 j, 2 j + 1) ever disagree.  Never refused.  POCS_E_ARG for a null pointer, D outside 1 .. 16, n outside 2 .. 2^20 or odd,
+   an odd first, a bad footprint, disc or covariance and ANY input that is not finite. */
 int pocs_get_sequence_time(pocs_ctx* ctx, double* ms, int* concurrent);  /* POCS_OPT_PROFILE=1, whole-run GMM calls: first sampling launch -> end of the last one, and how many
                                                                             sub-batches of the call were in flight side by side (their launches overlap: DESIGN.md section 5) */
 

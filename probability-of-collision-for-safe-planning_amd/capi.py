@@ -100,6 +100,9 @@ SIGNATURES = {
     "pocs_set_discs": (C.c_int, [_vp, _dp, C.c_int, C.c_int]),
     "pocs_get_discs": (C.c_int, [_vp, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "pocs_probe_device_discs": (C.c_int, [_vp, _dp, _dp, C.c_int, _dp, C.c_int, C.c_int, _dp, C.POINTER(C.c_int)]),
+    "pocs_set_disc_covariances": (C.c_int, [_vp, _dp, C.c_int, C.c_int, C.c_int]),
+    "pocs_get_disc_covariances": (C.c_int, [_vp, _dp, C.c_int, C.POINTER(C.c_int)]),
+    "pocs_probe_device_disc_noise": (C.c_int, [_vp, _dp, _dp, _dp, C.c_int, C.c_uint64, C.c_uint32, C.c_ulonglong, C.c_int, _dp, _dp, C.POINTER(C.c_uint)]),
     "pocs_set_segment_checks": (C.c_int, [_vp, C.c_int]),
     "pocs_get_segment_checks": (C.c_int, [_vp]),
     "pocs_get_segment_counts": (C.c_int, [_vp, C.POINTER(C.c_ulonglong), C.c_int]),
@@ -311,6 +314,52 @@ class Context:
         self._chk(self.lib.pocs_get_discs(self.h, C.byref(D), C.byref(S)))
         return D.value, S.value
 
+    def set_disc_covariances(self, cov, persistent=False):
+        """Uncertain discs: a position covariance {sxx, sxy, syy} (m^2) per disc, of shape (D, 3) for a static table or (S, D, 3) for a
+        schedule; D and S are those of the discs in force (set_discs).  A row of zeros is a certain disc; None, an empty array or all
+        zeros clears.  `persistent` (the MC path): True, a particle's world keeps its deviation from waypoint to waypoint, so a
+        covariance that grows is a prediction that fans out; False, the deviations are independent per waypoint -- as the GMM path
+        always treats them (include/pocs.h).  planio.prediction_covariances builds a constant-velocity predictor's fan."""
+        if cov is None or _arr(cov).size == 0:
+            self._chk(self.lib.pocs_set_disc_covariances(self.h, None, 0, 0, 0))
+            return
+        v = _arr(cov)
+        if v.ndim == 2:
+            v = v.reshape((1,) + v.shape)
+        if v.ndim != 3 or v.shape[2] != 3:
+            raise ValueError("covariances of shape %s, (D, 3) or (S, D, 3) expected" % (v.shape,))
+        v = np.ascontiguousarray(v)
+        self._chk(self.lib.pocs_set_disc_covariances(self.h, v.ctypes.data_as(_dp), v.shape[1], v.shape[0], 1 if persistent else 0))
+
+    def disc_covariances(self):
+        """(covariances of shape (S, D, 3), persistent) as in force; (None, False) when none are set."""
+        D, S = self.discs()
+        out = np.zeros(max(S * D * 3, 1))
+        per = C.c_int(0)
+        n = self.lib.pocs_get_disc_covariances(self.h, out.ctypes.data_as(_dp), S * D * 3, C.byref(per))
+        if n < 0:
+            self._chk(n)
+        if n == 0:
+            return None, False
+        return out[:n].reshape(S, D, 3), bool(per.value)
+
+    def probe_device_disc_noise(self, footprint, discs, cov, seed, waypoint_word, first, poses):
+        """Test hook: uncertain discs on the device for the caller's own footprint (dx, dy, hx, hy), discs (D x 3, D <= 16) and
+        covariances (D x 3).  Pose i of `poses` (n x 3, n even) has index first + i (first even).  Returns (centres float64[n, D, 2],
+        flags uint32[n]): the displaced centres, bit d = pose i touches displaced disc d, bit 31 = the kernels' two forms disagree
+        (never)."""
+        fp = _arr(footprint).ravel()
+        d = np.ascontiguousarray(_arr(discs).reshape(-1, 3))
+        v = np.ascontiguousarray(_arr(cov).reshape(-1, 3))
+        xyt = np.ascontiguousarray(_arr(poses).reshape(-1, 3))
+        assert fp.size == 4 and v.shape == d.shape
+        centres = np.full((xyt.shape[0], d.shape[0], 2), np.nan)
+        flags = np.full(xyt.shape[0], 0xFFFFFFFF, dtype=np.uint32)
+        self._chk(self.lib.pocs_probe_device_disc_noise(self.h, fp.ctypes.data_as(_dp), d.ctypes.data_as(_dp), v.ctypes.data_as(_dp), d.shape[0],
+                                                        C.c_uint64(int(seed)), C.c_uint32(int(waypoint_word)), C.c_ulonglong(int(first)), xyt.shape[0],
+                                                        xyt.ctypes.data_as(_dp), centres.ctypes.data_as(_dp), flags.ctypes.data_as(C.POINTER(C.c_uint))))
+        return centres, flags
+
     def probe_device_discs(self, footprint, boxes, discs, poses):
         """Test hook: per pose (n x 3) the kinds of obstacle it touches on the device, for the caller's own footprint (dx, dy, hx, hy),
         boxes (M x 5) and discs (D x 3).  int32[n]: bit 0 = touches some box, bit 1 = touches some disc, bit 8 = the kernels' two forms
@@ -484,6 +533,8 @@ class Context:
         self.set_env(env)
         if env.get("discs") is not None:   # round obstacles beside the boxes (set_discs)
             self.set_discs(env["discs"])
+        if env.get("disc_covariances") is not None:   # uncertain discs (set_disc_covariances)
+            self.set_disc_covariances(env["disc_covariances"], bool(env.get("disc_noise_persistent", False)))
         self.set_alphas(p["alphas"])
         self.set_q(p["Q"])
         self.set_landmarks(p["landmarks"])

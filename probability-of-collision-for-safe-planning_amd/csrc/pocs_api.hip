@@ -282,6 +282,7 @@ int pocs_set_discs(pocs_ctx* c, const double* discs, int D, int S) {
   if (D == 0 || (S == 0 && !discs)) {                // clears: every call is again what it is without discs
     if (c->disc_D > 0) c->env_dirty = true;
     c->discs.clear(); c->disc_D = 0; c->disc_S = 1;
+    c->disc_cov.clear(); c->disc_noise_persistent = 0;      // (covariances need discs)
     return POCS_OK;
   }
   if (S < 1 || S > POCS_MAX_WORLD_STEPS) return fail(c, POCS_E_ARG, "pocs_set_discs: %d steps outside 1..%d", S, POCS_MAX_WORLD_STEPS);
@@ -309,9 +310,53 @@ int pocs_set_discs(pocs_ctx* c, const double* discs, int D, int S) {
   if (seg_applied(c))
     return fail(c, POCS_E_STATE, "pocs_set_discs: segment checks are set (pocs_set_segment_checks); %s", pocs_modes::kDiscClause);
   c->discs.assign(discs, discs + (size_t)S * (size_t)D * 3);
+  if (D != c->disc_D || S != c->disc_S) { c->disc_cov.clear(); c->disc_noise_persistent = 0; }      // (the same D and S keep the covariances: new predictions, the same fan)
   c->disc_D = D; c->disc_S = S;
   c->env_dirty = true;                               // (same D and S: the records are overwritten in place and the cached graph replays)
   return POCS_OK;
+}
+
+// ---- uncertain discs (include/pocs.h) ----
+// S x D covariances {sxx, sxy, syy} for the discs in force; upload_world factorises them into the noise rows and grows the records.
+int pocs_set_disc_covariances(pocs_ctx* c, const double* cov, int D, int S, int persistent) {
+  if (!setter(c)) return POCS_E_ARG;
+  if (modes_of(c) & pocs_modes::kSequence)
+    return fail(c, POCS_E_ORDER, "pocs_set_disc_covariances: %s; %s", pocs_modes::name(pocs_modes::kSequence), pocs_modes::kDiscClause);
+  if (!cov && D == 0) {                              // clears: every call is again the discs call it is without covariances
+    if (!c->disc_cov.empty()) c->env_dirty = true;
+    c->disc_cov.clear(); c->disc_noise_persistent = 0;
+    return POCS_OK;
+  }
+  if (!discs_applied(c)) return fail(c, POCS_E_STATE, "pocs_set_disc_covariances: no discs are set (pocs_set_discs): covariances belong to discs");
+  if (!cov) return fail(c, POCS_E_ARG, "pocs_set_disc_covariances: null covariances");
+  if (D != c->disc_D || S != c->disc_S)
+    return fail(c, POCS_E_ARG, "pocs_set_disc_covariances: %d discs over %d steps, the discs in force are %d over %d", D, S, c->disc_D, c->disc_S);
+  if (persistent != POCS_DISC_NOISE_PER_WAYPOINT && persistent != POCS_DISC_NOISE_PERSISTENT)
+    return fail(c, POCS_E_ARG, "pocs_set_disc_covariances: persistent is %d, POCS_DISC_NOISE_PER_WAYPOINT (0) or POCS_DISC_NOISE_PERSISTENT (1)", persistent);
+  bool any = false;
+  for (size_t i = 0; i < (size_t)S * (size_t)D; ++i) {
+    double row[3];
+    const int k = pocs_disc_noise_factor(cov + 3 * i, row);
+    if (k < 0)
+      return fail(c, POCS_E_ARG, "pocs_set_disc_covariances: step %d, disc %d: {%g, %g, %g} is neither zeros nor a finite covariance with sxx > 0 and syy - sxy^2 / sxx > 0",
+                  (int)(i / (size_t)D), (int)(i % (size_t)D), cov[3 * i], cov[3 * i + 1], cov[3 * i + 2]);
+    any = any || k == 0;
+  }
+  if (any) c->disc_cov.assign(cov, cov + (size_t)S * (size_t)D * 3);      // (all rows zero is the same as cleared)
+  else c->disc_cov.clear();
+  c->disc_noise_persistent = any ? persistent : 0;
+  c->env_dirty = true;                               // (the same shape: rows and records are overwritten in place and the cached graph replays)
+  return POCS_OK;
+}
+
+int pocs_get_disc_covariances(const pocs_ctx* c, double* out, int cap, int* persistent) {
+  if (!c) return POCS_E_ARG;
+  if (persistent) *persistent = c->disc_noise_persistent;
+  const size_t n = noise_applied(c) ? c->disc_cov.size() : 0;
+  if (n == 0) return 0;
+  if (!out || (long long)n > (long long)cap) return POCS_E_BUFFER;
+  memcpy(out, c->disc_cov.data(), n * sizeof(double));
+  return (int)n;
 }
 
 int pocs_get_discs(const pocs_ctx* c, int* D, int* S) {

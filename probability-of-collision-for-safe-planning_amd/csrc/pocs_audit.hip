@@ -628,6 +628,68 @@ int pocs_probe_device_discs(pocs_ctx* c, const double* fp4, const double* boxes,
   return rc;
 }
 
+// Test hook: the displaced centres and the touched displaced discs, on the device, for chosen poses, pose indices, footprint, discs and
+// covariances (include/pocs.h).  Nothing of the context's world, plans or modes is read: records and rows are prepared here, as
+// upload_world prepares the context's.
+int pocs_probe_device_disc_noise(pocs_ctx* c, const double* fp4, const double* discs, const double* cov, int D, uint64_t seed,
+                                 uint32_t waypoint_word, unsigned long long first, int n, const double* poses, double* centres_out,
+                                 unsigned* flags_out) {
+  if (!c) return POCS_E_ARG;
+  if (!fp4 || !discs || !cov || !poses || !centres_out || !flags_out || D < 1 || D > 16 || n < 2 || n > (1 << 20) || (n & 1) || (first & 1ull) ||
+      first > (1ull << 62))
+    return fail(c, POCS_E_ARG, "pocs_probe_device_disc_noise: 1 <= D <= 16, 2 <= n <= 2^20 and even, first even and at most 2^62, no null pointers");
+  for (int j = 0; j < 4; ++j)
+    if (!std::isfinite(fp4[j])) return fail(c, POCS_E_ARG, "pocs_probe_device_disc_noise: footprint value %d is not finite", j);
+  if (!(fp4[2] > 0) || !(fp4[3] > 0)) return fail(c, POCS_E_ARG, "pocs_probe_device_disc_noise: footprint half extents must be > 0");
+  for (size_t j = 0; j < 3 * (size_t)D; ++j)
+    if (!std::isfinite(discs[j])) return fail(c, POCS_E_ARG, "pocs_probe_device_disc_noise: disc %zu: value %zu is not finite", j / 3, j % 3);
+  for (int d = 0; d < D; ++d)
+    if (!(discs[3 * (size_t)d + 2] > 0)) return fail(c, POCS_E_ARG, "pocs_probe_device_disc_noise: disc %d: the radius must be > 0", d);
+  for (size_t j = 0; j < 3 * (size_t)n; ++j)
+    if (!std::isfinite(poses[j])) return fail(c, POCS_E_ARG, "pocs_probe_device_disc_noise: pose %zu is not finite", j / 3);
+  const pocs_footprint fp = {fp4[0], fp4[1], fp4[2], fp4[3]};
+  std::vector<pocs_env_dev> env(1);
+  memset(env.data(), 0, sizeof(pocs_env_dev));
+  env[0].fp = fp; env[0].M = D;
+  std::vector<double> rows(POCS_MAX_OBSTACLES * POCS_NOISE_STRIDE, 0.0);
+  for (int d = 0; d < D; ++d) {
+    double* const rec = &env[0].obs[(size_t)d * POCS_OBS_STRIDE];
+    pocs_prepare_disc(discs + (size_t)d * 3, &fp, rec);
+    if (pocs_disc_noise_factor(cov + (size_t)d * 3, &rows[(size_t)d * POCS_NOISE_STRIDE]) < 0)
+      return fail(c, POCS_E_ARG, "pocs_probe_device_disc_noise: disc %d: neither zeros nor a finite covariance with sxx > 0 and syy - sxy^2 / sxx > 0", d);
+    rows[(size_t)d * POCS_NOISE_STRIDE + 3] = (double)d;
+    pocs_disc_noise_grow(&rows[(size_t)d * POCS_NOISE_STRIDE], rec);
+  }
+  HIPCHK(c, hipSetDevice(c->device));
+  if (int r = upload_tables(c)) return r;
+  std::vector<double> h(3 * (size_t)n);
+  for (int i = 0; i < n; ++i)
+    for (int j = 0; j < 3; ++j) h[(size_t)j * n + i] = poses[3 * (size_t)i + j];
+  // [env | rows | x | y | th | centres n x D x 2] then [flags n] words
+  static_assert(sizeof(pocs_env_dev) % 8 == 0, "the probe's buffer keeps its parts aligned");
+  const size_t off_rows = sizeof(pocs_env_dev), off_x = off_rows + rows.size() * sizeof(double), off_c = off_x + 3 * (size_t)n * sizeof(double),
+               nc = (size_t)n * (size_t)D * 2, off_f = off_c + nc * sizeof(double);
+  char* buf = nullptr;
+  HIPCHK(c, hipMalloc((void**)&buf, off_f + (size_t)n * sizeof(unsigned)));
+  int rc = POCS_OK;
+  if (hipMemcpy(buf, env.data(), sizeof(pocs_env_dev), hipMemcpyHostToDevice) != hipSuccess ||
+      hipMemcpy(buf + off_rows, rows.data(), rows.size() * sizeof(double), hipMemcpyHostToDevice) != hipSuccess ||
+      hipMemcpy(buf + off_x, h.data(), h.size() * sizeof(double), hipMemcpyHostToDevice) != hipSuccess ||
+      hipMemset(buf + off_c, 0, nc * sizeof(double) + (size_t)n * sizeof(unsigned)) != hipSuccess)
+    rc = fail(c, POCS_E_DEVICE, "probe upload failed");
+  const double* d_x = (const double*)(buf + off_x);
+  if (rc == POCS_OK && pocs_launch_probe_disc_noise((const pocs_env_dev*)buf, (const double*)(buf + off_rows), (const pocs_tables*)c->d_tables.p, seed,
+                                                    waypoint_word, first, n, d_x, d_x + n, d_x + 2 * (size_t)n, (double*)(buf + off_c),
+                                                    (unsigned*)(buf + off_f), c->stream) != hipSuccess)
+    rc = fail(c, POCS_E_DEVICE, "probe launch failed");
+  if (rc == POCS_OK && hipStreamSynchronize(c->stream) != hipSuccess) rc = fail(c, POCS_E_DEVICE, "probe kernel failed");
+  if (rc == POCS_OK && (hipMemcpy(centres_out, buf + off_c, nc * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess ||
+                        hipMemcpy(flags_out, buf + off_f, (size_t)n * sizeof(unsigned), hipMemcpyDeviceToHost) != hipSuccess))
+    rc = fail(c, POCS_E_DEVICE, "probe download failed");
+  (void)hipFree(buf);
+  return rc;
+}
+
 int pocs_get_sequence_time(pocs_ctx* c, double* ms, int* concurrent) {
   if (!c) return POCS_E_ARG;
   if (ms) *ms = c->seq_ms;

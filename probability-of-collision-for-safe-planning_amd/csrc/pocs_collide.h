@@ -169,6 +169,95 @@ POCS_HD unsigned pocs_pose_kinds_touched(double x, double y, double th, const po
   return kinds;
 }
 
+// ---- uncertain discs (pocs_set_disc_covariances) ----------------------------------------------------------------------
+// A disc's centre may carry a position covariance {sxx, sxy, syy}.  The host factorises it as the initial covariance is
+// factorised (pocs_disc_noise_factor: l00 = sqrt(sxx), l10 = sxy / l00, l11 = sqrt(syy - l10 l10), double arithmetic in that
+// order) into the record's ROW of the noise table, {l00, l10, l11, d} with d the disc's index in the caller's table; a row of
+// zeros is a certain disc or a box and draws nothing (an uncertain row has l00 > 0).  A pose is one possible world: for pose
+// index i, the run's seed, disc d and waypoint word v
+//   words = Philox4x32-7((lo32(i >> 1), hi32(i >> 1), v, 5 << 16 | d), seed)        (pocs_draw, POCS_STREAM_DISC)
+//   (z0, z1) = pocs_normal_pair_w2(words[2 h], words[2 h + 1]),  h = i & 1          (one draw serves poses 2 j and 2 j + 1)
+//   cx' = fma(l00, z0, cx)     cy' = fma(l11, z1, fma(l10, z0, cy))
+// and the flag is the broad phase on the NOMINAL centre AND pocs_disc_narrow's operations on (cx', cy').
+// Why the culls stay exact: |z| <= sqrt(64 ln 2) < 6.661 (pocs_normal_pair_w2), so |cx' - cx| <= 6.661 |l00| and
+// |cy' - cy| <= 6.661 (|l10| + |l11|) up to the rounding of two fmas (relative 2^-52, far inside the 0.1 % that 6.67 leaves).
+// The record's fields 6 and 7 are grown on the host by gx = 6.67 |l00| and gy = 6.67 (|l10| + |l11|) (pocs_disc_noise_grow):
+// the displaced disc lies inside the nominal bounding square moved by at most (gx, gy), so a pose that the grown broad phase
+// rejects is further than the footprint's bounding radius from every displaced square and cannot touch.  gmm_cull tightens a
+// kept record's box to the record's own extents plus the footprint's extents over the run's headings; with + gx, + gy
+// (gmm_cull<.., RN>) the same argument holds for the tightened box, and its keep test reads the grown fields: no flag changes.
+#define POCS_NOISE_STRIDE 4
+// 0: a row was written (uncertain, l00 > 0), 1: all zeros, a certain disc (the row is zeros), -1: not a covariance
+POCS_HD int pocs_disc_noise_factor(const double cov3[3], double row3[3]) {
+  row3[0] = row3[1] = row3[2] = 0.0;
+  for (int j = 0; j < 3; ++j)
+    if (!__builtin_isfinite(cov3[j])) return -1;
+  if (cov3[0] == 0.0 && cov3[1] == 0.0 && cov3[2] == 0.0) return 1;
+  if (!(cov3[0] > 0.0)) return -1;
+  const double l00 = sqrt(cov3[0]);
+  const double l10 = cov3[1] / l00;
+  const double t = cov3[2] - l10 * l10;
+  if (!(t > 0.0) || !__builtin_isfinite(l10)) return -1;
+  row3[0] = l00; row3[1] = l10; row3[2] = sqrt(t);
+  return 0;
+}
+// the growth of a prepared disc record's fields 6 and 7 (pocs_prepare_disc forms them first, unchanged)
+POCS_HD void pocs_disc_noise_grow(const double row3[3], double* rec) {
+  rec[6] += 6.67 * fabs(row3[0]);
+  rec[7] += 6.67 * (fabs(row3[1]) + fabs(row3[2]));
+}
+// the displaced centre of the disc of row `row` (l00 != 0) for pose index `index`
+POCS_HD void pocs_disc_displaced(double cx, double cy, const double* row, uint64_t seed, uint64_t index, uint32_t v,
+                                 const pocs_tables* T, double* cxp, double* cyp, const pocs_vconst* V = nullptr) {
+  const pocs_u32x4 w = pocs_draw(seed, index >> 1, v, POCS_STREAM_DISC, (uint32_t)row[3]);
+  double z0, z1;
+  if (index & 1ull) pocs_normal_pair_w2(w.z, w.w, T, &z0, &z1, V);
+  else              pocs_normal_pair_w2(w.x, w.y, T, &z0, &z1, V);
+  *cxp = fma(row[0], z0, cx);
+  *cyp = fma(row[2], z1, fma(row[1], z0, cy));
+}
+// pocs_world_hit for a table whose disc records may be uncertain: `row` is the record's row of the noise table
+POCS_HD bool pocs_world_hit_noisy(double px, double py, double sn, double cs, double rx, double ry, const double* o, const double* row,
+                                  uint64_t seed, uint64_t index, uint32_t v, const pocs_tables* T) {
+  if (fabs(o[0] - px) > o[6] || fabs(o[1] - py) > o[7]) return false;
+  if (pocs_record_is_disc(o[3])) {
+    if (row[0] != 0.0) {                                             // (wave-uniform) an uncertain disc: the test on the displaced centre
+      double d[5];
+      pocs_disc_displaced(o[0], o[1], row, seed, index, v, T, &d[0], &d[1]);
+      d[4] = o[4];
+      return pocs_disc_narrow(px, py, sn, cs, rx, ry, d);
+    }
+    return pocs_disc_narrow(px, py, sn, cs, rx, ry, o);
+  }
+  return pocs_box_narrow(px, py, sn, cs, rx, ry, o);
+}
+// pocs_pose_collides<true> under disc covariances, beside it: `rows` holds POCS_NOISE_STRIDE doubles per record of `obs`.
+// `discs_touched`, where given, receives bit (row[3]) per touched DISC record (the probe's and the harness' way in; D <= 32 there).
+// T: ALL the tables -- the heading reads the sector table, the draw the log tables of the radius too (on the device: the staged
+// copy, whose even log entries stage_tables has doubled).
+POCS_HD bool pocs_pose_collides_noisy(double x, double y, double th, const pocs_footprint* fp, const double* obs, const double* rows, int M,
+                                      uint64_t seed, uint64_t index, uint32_t v, const pocs_tables* T, unsigned* discs_touched = nullptr) {
+  if (discs_touched) *discs_touched = 0u;
+  if (M <= 0) return false;
+  double sn, cs;
+  pocs_sincos_tab(th, T, &sn, &cs);
+  double px = x, py = y;
+  if (!(fp->dx == 0.0 && fp->dy == 0.0)) {
+    px = x + fma(cs, fp->dx, -(sn * fp->dy));
+    py = y + fma(sn, fp->dx, cs * fp->dy);
+  }
+  bool hit = false;
+  for (int m = 0; m < M; ++m) {
+    const double* o = obs + m * POCS_OBS_STRIDE;
+    const double* row = rows + m * POCS_NOISE_STRIDE;
+    if (pocs_world_hit_noisy(px, py, sn, cs, fp->hx, fp->hy, o, row, seed, index, v, T)) {
+      hit = true;
+      if (discs_touched && pocs_record_is_disc(o[3])) *discs_touched |= 1u << ((unsigned)row[3] & 31u);
+    }
+  }
+  return hit;
+}
+
 // The same predicate for the two poses a thread of k_gmm_step draws per iteration, with ONE pass over the obstacle
 // table (it sits in LDS) and the loop's bookkeeping paid once.  Per pose exactly the operations of pocs_pose_collides, in
 // the same order: the same flags.  On the device (pocs_pair_loop) the compiled loop
@@ -219,13 +308,28 @@ __device__ __forceinline__ unsigned long long pocs_disc_narrow_mask(unsigned lon
   return pm & __builtin_amdgcn_ballot_w64(!(fma(q1, q1, q2 * q2) > r * r));
 }
 
+// What the pair loop needs for uncertain discs (pocs_set_disc_covariances; the block above pocs_disc_noise_factor): the rows of the
+// list it runs over (LDS, POCS_NOISE_STRIDE doubles per record, in the list's order), the run's seed, the lane's PAIR index
+// (poses 2 pair and 2 pair + 1) and the waypoint word.  pocs_noise_none: no such thing, and not one instruction of it.
+struct pocs_noise_none { static constexpr bool on = false; };
+struct pocs_noise_pair {
+  static constexpr bool on = true;
+  const double* rows;
+  uint64_t seed, pair;
+  uint32_t v;
+};
+
 // ROUND: the table may hold disc records; a record's kind is decided by a scalar branch on a ballot of its marker (every lane
 // reads the same record), and `kinds`, where given, receives the two poses' masks for the disc records apart: kinds[h] is the part
 // of mask[h] that discs contributed.
-template <bool EAGER, bool CENTRED, class Each, bool ROUND = false>
+// NZ = pocs_noise_pair (ROUND only): behind the disc branch a second scalar branch on the record's row -- every lane reads the same
+// one -- and for an uncertain disc ONE Philox call per pair, a Box-Muller pair per pose whose broad phase some lane passed, and
+// pocs_disc_narrow's operations on the displaced centre.
+template <bool EAGER, bool CENTRED, class Each, bool ROUND = false, class NZ = pocs_noise_none>
 __device__ __forceinline__ void pocs_pair_loop(const double x[2], const double y[2], const double th[2], const pocs_footprint* fp,
                                                const double* obs, int M, const pocs_tables* T, const pocs_vconst* V,
-                                               unsigned long long mask[2], Each each, unsigned long long* kinds = nullptr) {
+                                               unsigned long long mask[2], Each each, unsigned long long* kinds = nullptr, NZ nz = NZ()) {
+  static_assert(!NZ::on || ROUND, "uncertain discs: the ROUND form");
   const double rx = fp->hx, ry = fp->hy;
   double sn[2], cs[2], px[2], py[2];
   [[maybe_unused]] unsigned long long k0 = 0ull, k1 = 0ull;
@@ -279,10 +383,30 @@ __device__ __forceinline__ void pocs_pair_loop(const double x[2], const double y
         disc = __builtin_amdgcn_ballot_w64(__builtin_bit_cast(unsigned long long, ay) == 0x8000000000000000ull) != 0ull;
       }
       if (ROUND && disc) {
+        bool noisy = false;                                          // (scalar) the disc is uncertain: its row's l00 is not zero
+        if constexpr (NZ::on) {
+          const double* const row = nz.rows + m * POCS_NOISE_STRIDE;
+          const double l00 = row[0];
+          noisy = __builtin_amdgcn_ballot_w64(l00 != 0.0) != 0ull;
+          if (noisy) {
+            const pocs_u32x4 wd = pocs_draw(nz.seed, nz.pair, nz.v, POCS_STREAM_DISC, (uint32_t)row[3]);
+            const double l10 = row[1], l11 = row[2];
+#pragma unroll
+            for (int h = 0; h < 2; ++h) {
+              if (pm[h] == 0ull) continue;
+              double z0, z1;
+              pocs_normal_pair_w2(h ? wd.z : wd.x, h ? wd.w : wd.y, T, &z0, &z1, V);
+              const double cxp = fma(l00, z0, c.x), cyp = fma(l11, z1, fma(l10, z0, c.y));
+              bt[h] = pocs_disc_narrow_mask(pm[h], cxp - (CENTRED ? x[h] : px[h]), cyp - (CENTRED ? y[h] : py[h]), sn[h], cs[h], rx, ry, e.x);
+            }
+          }
+        }
+        if (!noisy) {
 #pragma unroll
         for (int h = 0; h < 2; ++h) {
           if (pm[h] == 0ull) continue;
           bt[h] = pocs_disc_narrow_mask(pm[h], dx[h], dy[h], sn[h], cs[h], rx, ry, e.x);
+        }
         }
         if constexpr (ROUND) { k0 |= bt[0]; k1 |= bt[1]; }
       } else {
@@ -310,24 +434,29 @@ __device__ __forceinline__ void pocs_pair_loop(const double x[2], const double y
 }
 
 // The pair's flags as lane masks (bit l: lane l's pose h touches some record; lanes that do not run the call stay 0).
-template <bool EAGER = false, class Each = pocs_each_none, bool ROUND = false>
+template <bool EAGER = false, class Each = pocs_each_none, bool ROUND = false, class NZ = pocs_noise_none>
 __device__ __forceinline__ void pocs_pair_collides_masks(const double x[2], const double y[2], const double th[2], const pocs_footprint* fp,
                                                          const double* obs, int M, const pocs_tables* T, const pocs_vconst* V,
-                                                         unsigned long long mask[2], Each each = Each(), unsigned long long* kinds = nullptr) {
+                                                         unsigned long long mask[2], Each each = Each(), unsigned long long* kinds = nullptr,
+                                                         NZ nz = NZ()) {
   mask[0] = 0ull; mask[1] = 0ull;
   if constexpr (ROUND) { if (kinds) { kinds[0] = 0ull; kinds[1] = 0ull; } }
   if (M <= 0) return;
   // (scalar) the loop twice, not one loop behind a merge of (x, y) with (px, py): merged, the centred footprint pays four
   // 64-bit register copies per call for values it already holds
   if (fp->dx == 0.0 && fp->dy == 0.0) {
-    if constexpr (ROUND) {
+    if constexpr (NZ::on) {
+      pocs_pair_loop<EAGER, true, Each, true, NZ>(x, y, th, fp, obs, M, T, V, mask, each, kinds, nz);
+    } else if constexpr (ROUND) {
       pocs_pair_loop<EAGER, true, Each, true>(x, y, th, fp, obs, M, T, V, mask, each, kinds);
     } else {
       pocs_pair_loop<EAGER, true>(x, y, th, fp, obs, M, T, V, mask, each);
     }
   } else {
     asm volatile("; offset footprint");
-    if constexpr (ROUND) {
+    if constexpr (NZ::on) {
+      pocs_pair_loop<EAGER, false, Each, true, NZ>(x, y, th, fp, obs, M, T, V, mask, each, kinds, nz);
+    } else if constexpr (ROUND) {
       pocs_pair_loop<EAGER, false, Each, true>(x, y, th, fp, obs, M, T, V, mask, each, kinds);
     } else {
       pocs_pair_loop<EAGER, false>(x, y, th, fp, obs, M, T, V, mask, each);

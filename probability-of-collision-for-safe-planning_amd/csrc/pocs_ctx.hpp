@@ -226,6 +226,12 @@ struct pocs_ctx {
   // (discs_applied) and the modes of pocs_modes::kDiscExcluded, a compound footprint and segment checks are refused
   std::vector<double> discs;             // disc_S x disc_D x 3
   int disc_D = 0, disc_S = 1;
+  // uncertain discs (pocs_set_disc_covariances): empty is off -- every call is, launch for launch, the discs call it is without this
+  // (a table of zeros is stored as empty).  Otherwise disc_S x disc_D x {sxx, sxy, syy}, every row zeros or a covariance the setter
+  // has factorised once already; upload_world factorises them again into d_noise ([env_steps][POCS_MAX_OBSTACLES] rows {l00, l10, l11,
+  // disc index}, record by record beside d_env) and grows the disc records, and every call is served by the _noise / MC_NOISE forms
+  std::vector<double> disc_cov;
+  int disc_noise_persistent = 0;         // the MC path's waypoint word: 1 = 0 at every waypoint, 0 = the waypoint
 
   // host image (headers | chains | initial mixtures) of the NEXT batch, computed while the GPU
   // works on the current one
@@ -258,6 +264,7 @@ struct pocs_ctx {
   // segment checks: one pocs_seg_dev beside d_env (upload_world: J and the fractions live in device memory, so another J > 1 replays
   // the cached graph) and the segment counts [slots][W] u64, zeroed by a kernel at the head of every call's launches
   pocs_rt::DevBuf d_seg, d_segct;
+  pocs_rt::DevBuf d_noise;               // uncertain discs: the noise rows, an allocation of its own (pocs_env_dev keeps its layout)
   pocs_rt::DevBuf d_obsct;               // POCS_OPT_OBSTACLE_COUNTS: [slots][W][POCS_MAX_OBSTACLES] u64, zeroed by a kernel at the head of every call's launches
   // one-hop exchange (pocs_xchg_*): this rank's buffer, the peers' buffers as mapped here
   void* xchg_own = nullptr;
@@ -363,6 +370,12 @@ inline int world_boxes(const pocs_ctx* c) { return (int)(c->boxes.size() / 5 / (
 inline bool discs_applied(const pocs_ctx* c) { return c->disc_D > 0; }
 inline int env_steps(const pocs_ctx* c) { return discs_applied(c) && c->disc_S > c->world_S ? c->disc_S : c->world_S; }
 inline int env_records(const pocs_ctx* c) { return world_boxes(c) + c->disc_D; }
+// Disc covariances are set and some row is not zero (pocs_set_disc_covariances): the launches carry the rows of their waypoint.
+inline bool noise_applied(const pocs_ctx* c) { return discs_applied(c) && !c->disc_cov.empty(); }
+inline const double* noise_at(const pocs_ctx* c, int w) {
+  const int S = env_steps(c);
+  return (const double*)c->d_noise.p + (size_t)(w < 0 ? 0 : w < S ? w : S - 1) * (POCS_MAX_OBSTACLES * POCS_NOISE_STRIDE);
+}
 inline const pocs_env_dev* world_at(const pocs_ctx* c, int w) {
   const int S = env_steps(c);
   return (const pocs_env_dev*)c->d_env.p + (w < 0 ? 0 : w < S ? w : S - 1);

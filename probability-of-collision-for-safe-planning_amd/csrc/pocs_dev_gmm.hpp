@@ -85,6 +85,15 @@ template <> struct gmm_sg_smem<true> {
   int nkeeps[2];
   int sgJ[2];
 };
+//   (the noise form only, pocs_set_disc_covariances: LDS of its own beside gmm_smem, whose type and layout stay) per run buffer and KEPT
+//          record its row {l00, l10, l11, disc index} of the noise table, in the kept list's order: 4 KB
+template <bool RN> struct gmm_noise_rows { static __device__ __forceinline__ double* get() { return nullptr; } };
+template <> struct gmm_noise_rows<true> {
+  static __device__ __forceinline__ double* get() {
+    __shared__ alignas(16) double rows[2 * POCS_MAX_OBSTACLES * POCS_NOISE_STRIDE];
+    return rows;
+  }
+};
 template <int K, int TB, bool OC = false, bool CL = false, bool FPN = false, bool RG = false, bool SG = false>
 struct gmm_smem : gmm_oc_smem<OC>, gmm_cl_smem<CL>, gmm_fp_smem<FPN>, gmm_rg_smem<RG>, gmm_sg_smem<SG> {
   static constexpr int NC = K * POCS_NMOM;
@@ -208,8 +217,13 @@ __device__ __forceinline__ void gmm_reach(const pocs_footprint& fp, const double
   ext_y = pocs_footprint_extent_is_radius(fp_phi, tlo - HALF_PI, thi - HALF_PI) ? fp_rr
         : pocs_footprint_extent_of_ends(fp_rr, lane_value(end_f, 2), lane_value(end_f, 3));
 }
-template <int K, int TB, bool OC, bool CL, bool FPN, bool RG, bool SG>
-__device__ __forceinline__ void gmm_cull(const pocs_gmm_launch& a, gmm_smem<K, TB, OC, CL, FPN, RG, SG>& sm, const int rb, const int lane, const double* par) {
+// RN (pocs_set_disc_covariances; `nz`: the block's kept rows, [2][POCS_MAX_OBSTACLES * POCS_NOISE_STRIDE] in LDS): lane m also fetches
+// record m's row of the launch's noise table; the tightened box gains the record's growth gx = 6.67 |l00|, gy = 6.67 (|l10| + |l11|)
+// -- the host's own operations, so that the table's grown fields 6 and 7 and the tightened ones bound the same displaced disc
+// (pocs_collide.h, the block above pocs_disc_noise_factor) -- and a kept record's row is written to the kept list's position.
+template <bool RN = false, int K, int TB, bool OC, bool CL, bool FPN, bool RG, bool SG>
+__device__ __forceinline__ void gmm_cull(const pocs_gmm_launch& a, gmm_smem<K, TB, OC, CL, FPN, RG, SG>& sm, const int rb, const int lane, const double* par,
+                                         [[maybe_unused]] double* nz = nullptr) {
   const pocs_footprint fp = a.fp;
   const int M = a.M;
   const double* const obs = sm.obs();
@@ -237,11 +251,20 @@ __device__ __forceinline__ void gmm_cull(const pocs_gmm_launch& a, gmm_smem<K, T
                      : pocs_footprint_extent_of_ends(a.fp_rr, lane_value(end_f, 2), lane_value(end_f, 3));
   bool keep = false;
   double bx = 0.0, by = 0.0;
+  [[maybe_unused]] double row[POCS_NOISE_STRIDE] = {0.0, 0.0, 0.0, 0.0};
   if (lane < M) {
     const double* o = &obs[lane * POCS_OBS_STRIDE];
+    if constexpr (RN) {
+#pragma unroll
+      for (int j = 0; j < POCS_NOISE_STRIDE; ++j) row[j] = a.noise[lane * POCS_NOISE_STRIDE + j];
+      const double gx = 6.67 * fabs(row[0]), gy = 6.67 * (fabs(row[1]) + fabs(row[2]));
+      bx = fmin(o[6], fma(o[4], fabs(o[2]), o[5] * fabs(o[3])) * (1.0 + 1e-12) + ext_x + gx);
+      by = fmin(o[7], fma(o[4], fabs(o[3]), o[5] * fabs(o[2])) * (1.0 + 1e-12) + ext_y + gy);
+    } else {
     // the obstacle's own world box (as pocs_prepare_obstacle) + the footprint's extents for this run
     bx = fmin(o[6], fma(o[4], fabs(o[2]), o[5] * fabs(o[3])) * (1.0 + 1e-12) + ext_x);
     by = fmin(o[7], fma(o[4], fabs(o[3]), o[5] * fabs(o[2])) * (1.0 + 1e-12) + ext_y);
+    }
     keep = !(o[0] - bx > xhi || o[0] + bx < xlo || o[1] - by > yhi || o[1] + by < ylo);
   }
   const unsigned long long mask = __ballot(keep);
@@ -252,6 +275,10 @@ __device__ __forceinline__ void gmm_cull(const pocs_gmm_launch& a, gmm_smem<K, T
     sm.keep[rb][pos * POCS_OBS_STRIDE + 6] = bx;
     sm.keep[rb][pos * POCS_OBS_STRIDE + 7] = by;
     if constexpr (OC) sm.oci[rb][pos] = lane;      // the kept slot's index in the caller's table: its counter leaves under it
+    if constexpr (RN) {
+#pragma unroll
+      for (int j = 0; j < POCS_NOISE_STRIDE; ++j) nz[(rb * POCS_MAX_OBSTACLES + pos) * POCS_NOISE_STRIDE + j] = row[j];
+    }
   }
   if constexpr (OC) sm.occ[rb][lane] = 0u;           // (one wave, POCS_MAX_OBSTACLES = 64 lanes: every counter of the buffer)
   if (lane == 0) sm.nkeep[rb] = __popcll(mask);
@@ -465,10 +492,14 @@ __device__ __forceinline__ void gmm_cull_seg(const pocs_gmm_launch& a, gmm_smem<
 //   masks are or-ed into the flags: everything behind is formed from those.  The odd shard's unused twin does not count.
 //   RD (pocs_set_discs, D > 0): the kept list may hold disc records; the collision test is pocs_pair_collides_masks' ROUND form, which
 //   decides a record's kind by a scalar branch and ballots the disc's answer into the same masks.  Nothing else differs.
+//   RN (pocs_set_disc_covariances, on top of RD; `nz`: the kept rows gmm_cull<true> left): the ROUND form is handed the run buffer's
+//   rows, the run's seed, the lane's pair index pair0 + lp and the waypoint, and tests an uncertain disc on its displaced centre.
 template <int K, bool STORE, int TB, bool LONE_PRE = false, bool OC = false, bool CL = false, bool FPN = false, bool RG = false, bool SG = false,
-          bool RD = false>
+          bool RD = false, bool RN = false>
 __device__ __forceinline__ void gmm_units(const pocs_gmm_launch& a, gmm_smem<K, TB, OC, CL, FPN, RG, SG>& sm, const int w, const int r0,
-                                          const int ta, const int tb, const double* zpre = nullptr, const int npre = 0) {
+                                          const int ta, const int tb, const double* zpre = nullptr, const int npre = 0,
+                                          [[maybe_unused]] const double* nz = nullptr) {
+  static_assert(!RN || RD, "uncertain discs: on top of the round form");
   const pocs_tables* const s_tab = &sm.tab;
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -586,6 +617,10 @@ __device__ __forceinline__ void gmm_units(const pocs_gmm_launch& a, gmm_smem<K, 
         if (b != 0ull && lane == (int)__builtin_ctzll(b))
           __hip_atomic_fetch_add(&occ[m], (unsigned)__popcll(b), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
       });
+    } else
+    if constexpr (RN) {
+      const pocs_noise_pair np = {nz + rb * (POCS_MAX_OBSTACLES * POCS_NOISE_STRIDE), seed_it, pair0 + (uint64_t)(unsigned)lp, (uint32_t)w};
+      pocs_pair_collides_masks<false, pocs_each_none, true, pocs_noise_pair>(xs, ys, ts, &fp, s_keep, nkeep, s_tab, vc, hits, pocs_each_none(), nullptr, np);
     } else
     if constexpr (RD) {
       pocs_pair_collides_masks<false, pocs_each_none, true>(xs, ys, ts, &fp, s_keep, nkeep, s_tab, vc, hits);
@@ -957,9 +992,10 @@ __device__ __forceinline__ void gmm_close_sums(const pocs_gmm_launch& a, const i
 // the or-ed flags), the tickets and the closers are what they are.  LDS: + 8 KB for the second kept table, + 0.3 KB, and 24 instead of
 // 32 held units, as the clearance form: two blocks per CU in every instantiation.
 template <int K, bool STORE, int TB, bool LONE, bool RISK, bool TREE = false, bool OC = false, bool WORLD = false, bool CL = false, bool FPN = false,
-          bool RG = false, bool SG = false, bool RD = false>
+          bool RG = false, bool SG = false, bool RD = false, bool RN = false>
 __device__ __forceinline__ void gmm_step_block(const pocs_gmm_launch a) {      // (by value, as a kernel holds its argument)
   typedef gmm_smem<K, TB, OC, CL, FPN, RG, SG> smem_t;
+  static_assert(!RN || RD, "uncertain discs: on top of the round form");
   static_assert(!(RD && (LONE || TREE || OC || WORLD || CL || FPN || RG || SG)), "round obstacles: the ticket form of a batch or of plans on a small world, a single footprint box, no counts, no segment checks");
   static_assert(!(SG && (LONE || TREE || OC || WORLD || CL || FPN || RG)), "segment checks: the ticket form of a batch or of plans on a small world, a single footprint box, no other counts");
   static_assert(!SG || TB >= 256, "waves 2 and 3 build the second kept list");
@@ -977,6 +1013,9 @@ __device__ __forceinline__ void gmm_step_block(const pocs_gmm_launch a) {      /
   __shared__ smem_t sm;
   // (lone form: one block per CU, the whole LDS is its own) the normals of the unit's first POCS_LONE_PRE iterations
   __shared__ double s_zpre[LONE ? POCS_LONE_PRE * 6 * TB : 2];
+  // (RN: the kept records' noise rows per run buffer, 4 KB next to the kept lists: with the _round form's 75 424 B, 79 520 B of the
+  // 81 920 B that let two blocks share a CU, for every K.  No other form holds a byte of it.)
+  double* const s_nz = gmm_noise_rows<RN>::get();
   int npre = 0;
   const int tid = threadIdx.x;
   const int w = a.waypoint;
@@ -1142,6 +1181,9 @@ __device__ __forceinline__ void gmm_step_block(const pocs_gmm_launch a) {      /
     if constexpr (FPN) {
       if (tid < 64) gmm_cull_parts(a, sm, 0, tid, sm.par[0]);
       else if (tid < 128 && r1 > r0) gmm_cull_parts(a, sm, 1, tid - 64, sm.par[1]);
+    } else if constexpr (RN) {
+      if (tid < 64) gmm_cull<true>(a, sm, 0, tid, sm.par[0], s_nz);
+      else if (tid < 128 && r1 > r0) gmm_cull<true>(a, sm, 1, tid - 64, sm.par[1], s_nz);
     } else {
     if (tid < 64) gmm_cull(a, sm, 0, tid, sm.par[0]);
     else if (tid < 128 && r1 > r0) gmm_cull(a, sm, 1, tid - 64, sm.par[1]);
@@ -1152,6 +1194,8 @@ __device__ __forceinline__ void gmm_step_block(const pocs_gmm_launch a) {      /
   POCS_STAMP(0);
   for (int ta = t0; ta < t1; ta += SUB) {
     const int tb = (ta + SUB < t1) ? ta + SUB : t1;
+    if constexpr (RN) gmm_units<K, STORE, TB, LONE, OC, CL, FPN, RG, SG, RD, true>(a, sm, w, r0, ta, tb, s_zpre, ta == t0 ? npre : 0, s_nz);
+    else
     gmm_units<K, STORE, TB, LONE, OC, CL, FPN, RG, SG, RD>(a, sm, w, r0, ta, tb, s_zpre, ta == t0 ? npre : 0);
     POCS_STAMP(1);
     __syncthreads();
@@ -1362,6 +1406,18 @@ __global__ __launch_bounds__(TB, POCS_GMM_BLOCKS_PER_CU * TB / 256) void k_gmm_s
 template <int K, bool STORE, int TB>
 __global__ __launch_bounds__(TB, POCS_GMM_BLOCKS_PER_CU * TB / 256) void k_gmm_step_risk_round(pocs_gmm_launch a) {
   gmm_step_block<K, STORE, TB, false, true, false, false, false, false, false, false, false, true>(a);
+}
+
+// The forms under uncertain discs (RN above; pocs_set_disc_covariances with a nonzero row), on top of the _round forms: kernels of their
+// own names again.  The head culls with gmm_cull<true>, which grows the tightened boxes and leaves each kept record's row beside the
+// kept list; the sampling loop draws an uncertain disc's deviation per pair and tests the displaced disc.
+template <int K, bool STORE, int TB>
+__global__ __launch_bounds__(TB, POCS_GMM_BLOCKS_PER_CU * TB / 256) void k_gmm_step_noise(pocs_gmm_launch a) {
+  gmm_step_block<K, STORE, TB, false, false, false, false, false, false, false, false, false, true, true>(a);
+}
+template <int K, bool STORE, int TB>
+__global__ __launch_bounds__(TB, POCS_GMM_BLOCKS_PER_CU * TB / 256) void k_gmm_step_risk_noise(pocs_gmm_launch a) {
+  gmm_step_block<K, STORE, TB, false, true, false, false, false, false, false, false, false, true, true>(a);
 }
 
 // The forms under a large collision world (WORLD above): kernels of their own names again.

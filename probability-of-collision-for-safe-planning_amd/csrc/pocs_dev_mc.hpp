@@ -65,6 +65,16 @@ __device__ __forceinline__ mc_head stage_mc_head(const pocs_env_dev* __restrict_
   return {s_obs, &s_tab, &s_fp, &s_M};
 }
 
+// MC_NOISE: the log tables of the Box-Muller radius into the head's table as well -- stage_tables' copy, the even entries doubled
+// on their way in --, behind the head's barrier and ending in one of its own.  (The head has room for them: its table is whole.)
+__device__ __forceinline__ void stage_mc_log_tables(const pocs_tables* __restrict__ g, const pocs_tables* s_tab) {
+  constexpr int NLG = (int)(sizeof(g->lg) / sizeof(double));
+  const double* src = &g->lg[0][0];
+  double* dst = const_cast<double*>(&s_tab->lg[0][0]);
+  for (int j = threadIdx.x; j < NLG; j += POCS_BLOCK) dst[j] = (j & 1) == 0 ? 2.0 * src[j] : src[j];
+  __syncthreads();
+}
+
 // MC kernels: blockIdx.y = run of the batch (its own seed, its own noisy controls, its own slice
 // of the particle arrays).
 struct mc_run_view {
@@ -143,7 +153,13 @@ __device__ __forceinline__ mc_run_start mc_start(const pocs_mc_launch& a) {
 // MC_ROUND (pocs_set_discs with D > 0), a flag on top of MC_PLAIN, MC_COUNTS or MC_STOP on k_mc_init and the per-step kernel, never
 // with MC_BOXES, MC_CLEAR, MC_PARTS, MC_REGIONS or MC_SEG: the staged table may hold disc records behind its boxes, and the
 // collision test is pocs_pose_collides<true>, which decides a record's kind by a wave-uniform branch.  Nothing else differs.
-enum { MC_PLAIN = 0, MC_COUNTS = 1, MC_STOP = 2, MC_BOXES = 4, MC_CLEAR = 8, MC_PARTS = 16, MC_REGIONS = 32, MC_SEG = 64, MC_ROUND = 128 };
+//
+// MC_NOISE (pocs_set_disc_covariances with a nonzero row), a flag on top of MC_ROUND: a disc record whose row of the launch's noise
+// table is not zero is tested on its displaced centre (pocs_pose_collides_noisy) -- the deviation drawn for (seed, global particle
+// index first + i, disc, waypoint word), the word 0 at every waypoint under POCS_DISC_NOISE_PERSISTENT and the launch's waypoint
+// otherwise.  The rows are read where they lie (wave-uniform addresses).  The head stages the sector table alone and the Box-Muller
+// radius needs the log tables: these forms stage them behind the head (stage_mc_log_tables).  Nothing else differs.
+enum { MC_PLAIN = 0, MC_COUNTS = 1, MC_STOP = 2, MC_BOXES = 4, MC_CLEAR = 8, MC_PARTS = 16, MC_REGIONS = 32, MC_SEG = 64, MC_ROUND = 128, MC_NOISE = 256 };
 static_assert(POCS_MAX_OBSTACLES <= 64, "a particle's touched boxes are a 64-bit mask");
 
 // pocs_pose_collides with the touched boxes as a mask (the flag: mask != 0, as the plain form's).
@@ -437,6 +453,7 @@ __global__ __launch_bounds__(POCS_BLOCK) void k_mc_init(pocs_mc_launch a) {
   mc_regions rg = {nullptr, nullptr, 0};
   if constexpr ((MODE & MC_REGIONS) != 0) rg = stage_mc_regions(a);          // (in front of the head's barrier)
   const mc_head hd = stage_mc_head(a.env, a.tables);
+  if constexpr ((MODE & MC_NOISE) != 0) stage_mc_log_tables(a.tables, hd.tab);
   const mc_run_view v = mc_view(a);
   const mc_world wd = hd.world();
   const mc_run_start st = mc_start(a);
@@ -453,6 +470,9 @@ __global__ __launch_bounds__(POCS_BLOCK) void k_mc_init(pocs_mc_launch a) {
       mc_wave_box_hits(h != 0u, mask, wd.M, box.c);
     } else if constexpr ((MODE & MC_PARTS) != 0) {
       h = pocs_pose_collides_parts(x, y, t, pt.p, pt.F, wd.obs, wd.M, wd.tab) ? 1u : 0u;
+    } else if constexpr ((MODE & MC_NOISE) != 0) {
+      static_assert((MODE & MC_NOISE) == 0 || ((MODE & MC_ROUND) != 0 && (MODE & (MC_BOXES | MC_CLEAR | MC_PARTS | MC_REGIONS | MC_SEG)) == 0), "uncertain discs: on top of MC_ROUND alone");
+      h = pocs_pose_collides_noisy(x, y, t, &wd.fp, wd.obs, a.noise, wd.M, v.seed, (uint64_t)(a.first + i), 0u, wd.tab) ? 1u : 0u;      // waypoint 0
     } else if constexpr ((MODE & MC_ROUND) != 0) {
       static_assert((MODE & MC_ROUND) == 0 || (MODE & (MC_BOXES | MC_CLEAR | MC_PARTS | MC_REGIONS | MC_SEG)) == 0, "round obstacles: on top of the three plain modes alone");
       h = pocs_pose_collides<true>(x, y, t, &wd.fp, wd.obs, wd.M, wd.tab) ? 1u : 0u;
@@ -524,6 +544,7 @@ __device__ __forceinline__ void mc_step_body(const pocs_mc_launch& a) {
   mc_regions rg = {nullptr, nullptr, 0};
   if constexpr ((MODE & MC_REGIONS) != 0) rg = stage_mc_regions(a);          // (in front of the head's barrier)
   const mc_head hd = stage_mc_head(a.env, a.tables);
+  if constexpr ((MODE & MC_NOISE) != 0) stage_mc_log_tables(a.tables, hd.tab);
   const mc_run_view v = mc_view(a);
   const mc_world wd = hd.world();
   const double* u = v.chain + (size_t)a.step * POCS_CHAIN_STRIDE + 6;
@@ -588,6 +609,14 @@ __device__ __forceinline__ void mc_step_body(const pocs_mc_launch& a) {
         if (in != 0u && v.hits[i] != 0u) in = 0u;      // (in a region, but collided at an earlier waypoint)
       }
       mc_wave_region_hits(in, rg.G, a.reg_counts + ((size_t)blockIdx.y * (size_t)a.W + (size_t)a.step + 1) * POCS_MAX_REGIONS);
+    } else if constexpr ((MODE & MC_NOISE) != 0) {
+      static_assert((MODE & MC_NOISE) == 0 || ((MODE & MC_ROUND) != 0 && (MODE & (MC_BOXES | MC_CLEAR | MC_PARTS | MC_REGIONS | MC_SEG)) == 0), "uncertain discs: on top of MC_ROUND alone");
+      const uint32_t vw = a.noise_persistent ? 0u : (uint32_t)(a.step + 1);      // control s produces waypoint s + 1
+      if (pocs_pose_collides_noisy(nx, ny, nt, &wd.fp, wd.obs, a.noise, wd.M, v.seed, (uint64_t)(a.first + i), vw, wd.tab)) {
+        const uint32_t old = v.hits[i];
+        v.hits[i] = old + 1u;
+        first += old == 0u ? 1u : 0u;
+      }
     } else if constexpr ((MODE & MC_ROUND) != 0) {
       static_assert((MODE & MC_ROUND) == 0 || (MODE & (MC_BOXES | MC_CLEAR | MC_PARTS | MC_REGIONS | MC_SEG)) == 0, "round obstacles: on top of the three plain modes alone");
       if (pocs_pose_collides<true>(nx, ny, nt, &wd.fp, wd.obs, wd.M, wd.tab)) {

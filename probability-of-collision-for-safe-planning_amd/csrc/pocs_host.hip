@@ -149,6 +149,7 @@ int upload_world(pocs_ctx* c) {                // tables + the collision world: 
     const int M = world_boxes(c);
     std::vector<pocs_env_dev> env(S);
     memset(env.data(), 0, S * sizeof(pocs_env_dev));
+    std::vector<double> noise(noise_applied(c) ? S * POCS_MAX_OBSTACLES * POCS_NOISE_STRIDE : 0, 0.0);      // uncertain discs: a row per record
     pocs_parts_dev parts;
     for (size_t s = 0; s < S; ++s) {
       if (discs_applied(c)) {                        // round obstacles: record s is box step min(s, Sb - 1), then disc step min(s, Sd - 1)
@@ -158,8 +159,16 @@ int upload_world(pocs_ctx* c) {                // tables + the collision world: 
         env[s].M = M + D;
         for (int m = 0; m < M; ++m)
           pocs_prepare_box_beside_discs(&c->boxes[(sb * (size_t)M + (size_t)m) * 5], &c->fp, &env[s].obs[(size_t)m * POCS_OBS_STRIDE]);
-        for (int d = 0; d < D; ++d)
-          pocs_prepare_disc(&c->discs[(sd * (size_t)D + (size_t)d) * 3], &c->fp, &env[s].obs[(size_t)(M + d) * POCS_OBS_STRIDE]);
+        for (int d = 0; d < D; ++d) {
+          double* const rec = &env[s].obs[(size_t)(M + d) * POCS_OBS_STRIDE];
+          pocs_prepare_disc(&c->discs[(sd * (size_t)D + (size_t)d) * 3], &c->fp, rec);
+          if (noise_applied(c)) {                      // the record's row (zeros: a certain disc) and the growth of its fields 6 and 7
+            double* const row = &noise[(s * POCS_MAX_OBSTACLES + (size_t)(M + d)) * POCS_NOISE_STRIDE];
+            pocs_disc_noise_factor(&c->disc_cov[(sd * (size_t)D + (size_t)d) * 3], row);      // (the setter has checked every row)
+            row[3] = (double)d;
+            pocs_disc_noise_grow(row, rec);
+          }
+        }
         continue;
       }
       if (parts_applied(c)) {                        // (a compound footprint: the records of the covering part; no large world then)
@@ -174,6 +183,10 @@ int upload_world(pocs_ctx* c) {                // tables + the collision world: 
     if (int r = ensure(c, c->d_env, S * sizeof(pocs_env_dev))) return r;      // (a schedule that grows: the graphs go with the old table)
     HIPCHK(c, hipStreamSynchronize(c->stream));      // (nothing queued may still read the last world's)
     HIPCHK(c, hipMemcpy(c->d_env.p, env.data(), S * sizeof(pocs_env_dev), hipMemcpyHostToDevice));
+    if (!noise.empty()) {                            // (the same shape: overwritten in place, the cached graph replays)
+      if (int r = ensure(c, c->d_noise, noise.size() * sizeof(double))) return r;
+      HIPCHK(c, hipMemcpy(c->d_noise.p, noise.data(), noise.size() * sizeof(double), hipMemcpyHostToDevice));
+    }
     if (parts_applied(c)) {
       if (int r = ensure(c, c->d_parts, sizeof(pocs_parts_dev))) return r;
       HIPCHK(c, hipMemcpy(c->d_parts.p, &parts, sizeof parts, hipMemcpyHostToDevice));
@@ -535,6 +548,7 @@ void fill_gmm_world(const pocs_ctx* c, pocs_gmm_launch* a, int w) {
   a->tables = (const pocs_tables*)c->d_tables.p;
   a->M = env_records(c);                             // (the boxes, and behind them the discs in force)
   a->round = discs_applied(c) ? 1 : 0;               // (nonzero: the sampling launch is the _round form)
+  a->noise = noise_applied(c) ? noise_at(c, w) : nullptr;      // (non-null: the _noise form on top of it)
   if (!parts_applied(c)) {                           // (a compound footprint's values live in device memory: the launch carries none)
     a->fp = c->fp;
     a->fp_rr = sqrt(c->fp.hx * c->fp.hx + c->fp.hy * c->fp.hy); a->fp_phi = atan2(c->fp.hy, c->fp.hx);
@@ -573,6 +587,7 @@ void fill_gmm_launch(pocs_ctx* c, pocs_gmm_launch* a, long long first, long long
 void aim_gmm_launch(const pocs_ctx* c, pocs_gmm_launch* a, int w, int run_lo = 0, int run_cnt = -1, int groups = 1) {
   if (run_cnt < 0) run_cnt = c->batch;
   a->env = world_at(c, w); a->waypoint = w;
+  if (a->noise) a->noise = noise_at(c, w);           // (uncertain discs: the rows of the same step)
   if (a->clr) a->clr = clear_at(c, w);               // (the clearance form: the record of the same step)
   const GmmGeometry geo = gmm_geometry(a->count, run_cnt, c->K, groups);
   a->chunks = geo.chunks; a->vs_shift = geo.vs_shift; a->upb = geo.upb; a->blocks = geo.blocks;
@@ -1066,6 +1081,7 @@ int enqueue_mc_all(Issuer is, long long first, long long count, bool prof) {
     if (int r = is.launch(pocs_launch_zero_counts, 0, a.seg_counts, seg_count_words(c))) return r;
   }
   if (discs_applied(c)) a.round = 1;                 // (round obstacles: the MC_ROUND forms of k_mc_init and the per-step kernel)
+  if (noise_applied(c)) { a.noise = noise_at(c, 0); a.noise_persistent = c->disc_noise_persistent ? 1 : 0; }      // (uncertain discs: MC_NOISE on top)
   if (c->plans.n) {
     a.run_plan = (const double*)c->d_runplan.p;      // every run its own start mean and steps
   } else {
@@ -1088,6 +1104,7 @@ int enqueue_mc_all(Issuer is, long long first, long long count, bool prof) {
       pocs_mc_launch as;
       memcpy(&as, &a, sizeof as);
       as.env = world_at(c, s + 1);                   // control s produces waypoint s + 1
+      if (as.noise) as.noise = noise_at(c, s + 1);
       if (as.clr) as.clr = clear_at(c, s + 1);
       int nb = nblk;
       if (c->plans.n) {

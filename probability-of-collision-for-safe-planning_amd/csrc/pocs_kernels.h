@@ -211,6 +211,11 @@ struct pocs_gmm_launch {
   // hold disc records behind its boxes (pocs_collide.h), M counts both
   int round;
   int round_pad;
+  // uncertain discs (pocs_set_disc_covariances with a nonzero row; behind everything else again): non-null = the launch is the _noise
+  // form on top of the _round form (`round` is nonzero too): the rows {l00, l10, l11, disc index} of the records of `env`, record by
+  // record (POCS_NOISE_STRIDE doubles each, zeros for a box), for the launch's waypoint -- aimed with `env`.  The waypoint word of the
+  // deviations is the launch's waypoint
+  const double* noise;
 };
 #define POCS_MAX_WORLD_RECORDS 4096   // = POCS_MAX_WORLD_BOXES (include/pocs.h; pocs_ctx.hpp checks)
 #define POCS_CULL_BLOCK 256           // k_world_cull
@@ -294,6 +299,13 @@ struct pocs_mc_launch {               // blockIdx.y = run of the batch, like poc
   // segment checks): the table in `env` may hold disc records behind its boxes
   int round;
   int round_pad;
+  // uncertain discs (pocs_set_disc_covariances with a nonzero row; behind everything else again): non-null = the MC_NOISE forms on top
+  // of the MC_ROUND forms (`round` is nonzero too): the rows of the records of `env` for the launch's waypoint, aimed with `env`;
+  // noise_persistent nonzero: the deviations' waypoint word is 0 at every waypoint (a particle's world keeps its deviation),
+  // otherwise the launch's waypoint
+  const double* noise;
+  int noise_persistent;
+  int noise_pad;
 };
 
 
@@ -336,6 +348,12 @@ hipError_t pocs_launch_probe_segment(const pocs_env_dev* env, const pocs_seg_dev
 // i touches some box, bit 1 = some disc (the single-pose form on the full table), bit 8 should the pair form ever disagree with it
 hipError_t pocs_launch_probe_discs(const pocs_env_dev* env, const pocs_tables* tables, int n, const double* x, const double* y,
                                    const double* th, int* out, hipStream_t s);
+// one block; poses n x (x, y, th) by component, pose i has index first + i (first even); env: the D disc records alone, grown; rows:
+// their noise rows.  centres[(i * D + d) * 2 ..]: disc d's displaced centre for pose i; flags[i]: bit d = pose i touches displaced disc
+// d (the single-pose form), bit 31 should the pair form ever disagree with it
+hipError_t pocs_launch_probe_disc_noise(const pocs_env_dev* env, const double* rows, const pocs_tables* tables, unsigned long long seed,
+                                        unsigned v, unsigned long long first, int n, const double* x, const double* y, const double* th,
+                                        double* centres, unsigned* flags, hipStream_t s);
 // one thread per case; K / seeds / wp / n_total: n; w / alive / out: n rows of POCS_MAX_GAUSSIANS (case i uses the first K[i]): raw weights
 // and alive flags in, cumulative component counts out (pocs_normalise_weights + pocs_component_counts, as advance_finish and
 // speculate_counts call them)

@@ -54,6 +54,18 @@ hipError_t with_K(const int K, F f) {
 hipError_t pocs_launch_gmm_step(int K, const pocs_gmm_launch& a, hipStream_t s) {
   return with_K(K, [&](auto k) {
     constexpr int KK = decltype(k)::value, TB = POCS_GMM_BLOCK_OF(KK);
+    if (a.noise) {                                     // uncertain discs: the _noise forms on top of the _round forms
+      if (!a.round || a.lone || a.obs_counts || a.world || a.tree_parent || a.exchange_in_tail || a.clr || a.parts || a.regions || a.seg ||
+          a.M > POCS_MAX_OBSTACLES || (a.risk && (!a.stop || !a.surv)))
+        return hipErrorInvalidValue;
+      if (a.risk) {
+        if (a.store) hipLaunchKernelGGL((k_gmm_step_risk_noise<KK, true, TB>), dim3(a.blocks), dim3(TB), 0, s, a);
+        else         hipLaunchKernelGGL((k_gmm_step_risk_noise<KK, false, TB>), dim3(a.blocks), dim3(TB), 0, s, a);
+      } else {
+        if (a.store) hipLaunchKernelGGL((k_gmm_step_noise<KK, true, TB>), dim3(a.blocks), dim3(TB), 0, s, a);
+        else         hipLaunchKernelGGL((k_gmm_step_noise<KK, false, TB>), dim3(a.blocks), dim3(TB), 0, s, a);
+      }
+    } else
     if (a.round) {                                     // round obstacles: the ticket forms whose table may hold disc records
       if (a.lone || a.obs_counts || a.world || a.tree_parent || a.exchange_in_tail || a.clr || a.parts || a.regions || a.seg ||
           a.M > POCS_MAX_OBSTACLES || (a.risk && (!a.stop || !a.surv)))
@@ -223,6 +235,11 @@ hipError_t pocs_launch_mc_tree_step(int nblk, const pocs_mc_launch& a, hipStream
 
 hipError_t pocs_launch_mc_init(int nblk, const pocs_mc_launch& a, hipStream_t s) {
   if ((a.wp_mode != 0 && !a.wp_counts) || (a.obs_counts && !a.wp_mode)) return hipErrorInvalidValue;
+  if (a.noise) {                                      // uncertain discs: the MC_NOISE forms on top of the MC_ROUND forms
+    if (!a.round || a.world || a.obs_counts || a.clr || a.parts || a.regions || a.seg) return hipErrorInvalidValue;
+    if (a.wp_mode) hipLaunchKernelGGL(k_mc_init<MC_COUNTS | MC_ROUND | MC_NOISE>, dim3(nblk, a.nruns), dim3(POCS_BLOCK), 0, s, a);
+    else           hipLaunchKernelGGL(k_mc_init<MC_PLAIN | MC_ROUND | MC_NOISE>, dim3(nblk, a.nruns), dim3(POCS_BLOCK), 0, s, a);
+  } else
   if (a.round) {                                      // round obstacles: the MC_ROUND forms (a small world, no counts per box, level or region, one footprint box)
     if (a.world || a.obs_counts || a.clr || a.parts || a.regions || a.seg) return hipErrorInvalidValue;
     if (a.wp_mode) hipLaunchKernelGGL(k_mc_init<MC_COUNTS | MC_ROUND>, dim3(nblk, a.nruns), dim3(POCS_BLOCK), 0, s, a);
@@ -256,6 +273,21 @@ hipError_t pocs_launch_mc_init(int nblk, const pocs_mc_launch& a, hipStream_t s)
 hipError_t pocs_launch_mc_step(int nblk, const pocs_mc_launch& a, hipStream_t s) {
   const dim3 grid(nblk, a.nruns), block(POCS_BLOCK);
   if ((a.wp_mode != 0 && !a.wp_counts) || (a.obs_counts && !a.wp_mode)) return hipErrorInvalidValue;
+  if (a.noise) {                                      // uncertain discs: the MC_NOISE forms of the three modes
+    if (!a.round || a.world || a.obs_counts || a.clr || a.parts || a.regions || a.seg || a.step < 0 || a.step + 1 >= a.W ||
+        (a.wp_mode == 2 && (!a.wp_stop || a.wp_n < 1)))
+      return hipErrorInvalidValue;
+    if (a.wp_mode == 2) {
+      if (a.nontemporal) hipLaunchKernelGGL((k_mc_step_counts<true, MC_STOP | MC_ROUND | MC_NOISE>), grid, block, 0, s, a);
+      else               hipLaunchKernelGGL((k_mc_step_counts<false, MC_STOP | MC_ROUND | MC_NOISE>), grid, block, 0, s, a);
+    } else if (a.wp_mode == 1) {
+      if (a.nontemporal) hipLaunchKernelGGL((k_mc_step_counts<true, MC_COUNTS | MC_ROUND | MC_NOISE>), grid, block, 0, s, a);
+      else               hipLaunchKernelGGL((k_mc_step_counts<false, MC_COUNTS | MC_ROUND | MC_NOISE>), grid, block, 0, s, a);
+    } else {
+      if (a.nontemporal) hipLaunchKernelGGL((k_mc_step_counts<true, MC_PLAIN | MC_ROUND | MC_NOISE>), grid, block, 0, s, a);
+      else               hipLaunchKernelGGL((k_mc_step_counts<false, MC_PLAIN | MC_ROUND | MC_NOISE>), grid, block, 0, s, a);
+    }
+  } else
   if (a.round) {                                      // round obstacles: the MC_ROUND forms of the three modes
     if (a.world || a.obs_counts || a.clr || a.parts || a.regions || a.seg || a.step < 0 || a.step + 1 >= a.W ||
         (a.wp_mode == 2 && (!a.wp_stop || a.wp_n < 1)))
@@ -818,6 +850,74 @@ hipError_t pocs_launch_probe_discs(const pocs_env_dev* env, const pocs_tables* t
                                    const double* th, int* out, hipStream_t s) {
   if (!env || !tables || n < 1 || !x || !y || !th || !out) return hipErrorInvalidValue;
   hipLaunchKernelGGL(k_probe_discs, dim3(1), dim3(POCS_BLOCK), 0, s, env, tables, n, x, y, th, out);
+  return hipGetLastError();
+}
+// Uncertain discs on poses, a footprint, discs and factor rows the caller picks (pocs_probe_device_disc_noise: a test hook beside
+// k_probe_discs): ONE block stages the tables, the D grown disc records and their rows and asks, per pose of index first + i, the
+// functions the kernels ask.  The displaced centres are pocs_disc_displaced's, disc by disc; bit d of a pose's flags is "touches
+// displaced disc d" by pocs_pose_collides_noisy, the MC kernels' single-pose form, whose own answer must be (bits != 0).  Then
+// pocs_pair_collides_masks' noisy ROUND form as k_gmm_step_noise calls it, disc by disc on poses 2 p, 2 p + 1 of pair
+// (first >> 1) + p (an odd last pose beside its own twin's index, which is then not read): bit 31 should the two forms ever disagree.
+__global__ __launch_bounds__(POCS_BLOCK) void k_probe_disc_noise(const pocs_env_dev* __restrict__ env, const double* __restrict__ rows,
+                                                                 const pocs_tables* __restrict__ tables, unsigned long long seed, unsigned v,
+                                                                 unsigned long long first, int n, const double* __restrict__ x,
+                                                                 const double* __restrict__ y, const double* __restrict__ th,
+                                                                 double* __restrict__ centres, unsigned* __restrict__ flags) {
+  __shared__ pocs_tables s_tab;
+  __shared__ __attribute__((aligned(16))) double s_obs[POCS_MAX_OBSTACLES * POCS_OBS_STRIDE];
+  __shared__ __attribute__((aligned(16))) double s_rows[POCS_MAX_OBSTACLES * POCS_NOISE_STRIDE];
+  stage_tables(tables, &s_tab);
+  for (int j = threadIdx.x; j < POCS_MAX_OBSTACLES * POCS_OBS_STRIDE; j += POCS_BLOCK) s_obs[j] = env->obs[j];
+  for (int j = threadIdx.x; j < POCS_MAX_OBSTACLES * POCS_NOISE_STRIDE; j += POCS_BLOCK) s_rows[j] = rows[j];
+  __syncthreads();
+  const int D = env->M < 16 ? env->M : 16;
+  const pocs_footprint fp = env->fp;
+  POCS_VCONST(vc_);
+  const int npairs = (n + 1) / 2;
+  // (every lane of a wave makes every trip: the pair form ballots)
+  for (int p0 = (int)threadIdx.x - (int)(threadIdx.x & 63); p0 < npairs; p0 += POCS_BLOCK) {
+    const int p = p0 + (int)(threadIdx.x & 63);
+    const bool live = p < npairs;
+    const int i0 = live ? 2 * p : 0;
+    const bool two = live && i0 + 1 < n;
+    const int i1 = two ? i0 + 1 : i0;
+    const double xs[2] = {x[i0], x[i1]}, ys[2] = {y[i0], y[i1]}, ts[2] = {th[i0], th[i1]};
+    const unsigned long long idx[2] = {first + (unsigned long long)i0, first + (unsigned long long)i0 + 1ull};
+    unsigned single[2] = {0u, 0u}, pair[2] = {0u, 0u};
+    bool bad[2] = {false, false};
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+      const bool any = pocs_pose_collides_noisy(xs[h], ys[h], ts[h], &fp, s_obs, s_rows, D, seed, idx[h], v, &s_tab, &single[h]);
+      if (any != (single[h] != 0u)) bad[h] = true;
+      if (live && (h == 0 || two))
+        for (int d = 0; d < D; ++d) {
+          double cx = s_obs[d * POCS_OBS_STRIDE], cy = s_obs[d * POCS_OBS_STRIDE + 1];
+          if (s_rows[d * POCS_NOISE_STRIDE] != 0.0)
+            pocs_disc_displaced(cx, cy, &s_rows[d * POCS_NOISE_STRIDE], seed, idx[h], v, &s_tab, &cx, &cy);
+          double* const out = centres + ((size_t)(h == 0 ? i0 : i1) * (size_t)D + (size_t)d) * 2;
+          out[0] = cx; out[1] = cy;
+        }
+    }
+    for (int d = 0; d < D; ++d) {                                      // (scalar) the pair form, one record at a time: a bit per disc
+      unsigned long long all[2];
+      const pocs_noise_pair np = {&s_rows[d * POCS_NOISE_STRIDE], seed, idx[0] >> 1, v};
+      pocs_pair_collides_masks<false, pocs_each_none, true, pocs_noise_pair>(xs, ys, ts, &fp, &s_obs[d * POCS_OBS_STRIDE], 1, &s_tab, &vc_, all,
+                                                                             pocs_each_none(), nullptr, np);
+#pragma unroll
+      for (int h = 0; h < 2; ++h)
+        if (__builtin_amdgcn_inverse_ballot_w64(all[h])) pair[h] |= 1u << d;
+    }
+    if (live) {
+      flags[i0] = single[0] | ((bad[0] || pair[0] != single[0]) ? 0x80000000u : 0u);
+      if (two) flags[i1] = single[1] | ((bad[1] || pair[1] != single[1]) ? 0x80000000u : 0u);
+    }
+  }
+}
+hipError_t pocs_launch_probe_disc_noise(const pocs_env_dev* env, const double* rows, const pocs_tables* tables, unsigned long long seed,
+                                        unsigned v, unsigned long long first, int n, const double* x, const double* y, const double* th,
+                                        double* centres, unsigned* flags, hipStream_t s) {
+  if (!env || !rows || !tables || n < 1 || (first & 1ull) || !x || !y || !th || !centres || !flags) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(k_probe_disc_noise, dim3(1), dim3(POCS_BLOCK), 0, s, env, rows, tables, seed, v, first, n, x, y, th, centres, flags);
   return hipGetLastError();
 }
 hipError_t pocs_launch_fill(void* dst, long long bytes, hipStream_t s) {

@@ -206,6 +206,22 @@ def moving_discs(tracks, r):
     return out
 
 
+def prediction_covariances(sigma0, rate, S, D):
+    """Disc covariances (Context.set_disc_covariances) of a constant-velocity predictor's fan: isotropic, standard deviation
+    sigma0 + rate * s at disc step s, for S steps of D discs.  Returns S x D x 3 = (sxx, sxy, syy) with (sigma0 + rate s)^2 on the
+    diagonal and sxy = 0.  ValueError for S or D below 1 or a standard deviation that is negative or not finite."""
+    S, D = int(S), int(D)
+    if S < 1 or D < 1:
+        raise ValueError("S and D are at least 1")
+    sig = float(sigma0) + float(rate) * np.arange(S, dtype=np.float64)
+    if not (np.all(np.isfinite(sig)) and np.all(sig >= 0.0)):
+        raise ValueError("a standard deviation is non-negative and finite")
+    out = np.zeros((S, D, 3))
+    out[:, :, 0] = (sig * sig)[:, None]
+    out[:, :, 2] = (sig * sig)[:, None]
+    return out
+
+
 def goal_region(plan, half_x, half_y):
     """The goal tolerance of a plan as a watched region (Context.set_regions): the box (cx, cy, half_x, half_y, yaw) centred at
     the plan's last waypoint and turned to its heading.  `plan` is a dict with `traj` (W x 3) or the W x 3 array itself.
