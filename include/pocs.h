@@ -657,6 +657,34 @@ int pocs_get_discs(const pocs_ctx* ctx, int* D, int* S);
 int pocs_set_disc_covariances(pocs_ctx* ctx, const double* cov /* S x D x {sxx, sxy, syy} */, int D, int S, int persistent);
 int pocs_get_disc_covariances(const pocs_ctx* ctx, double* out, int cap, int* persistent);   /* returns S*D*3, 0 when none */
 
+/* ---- a round footprint: a disc of radius rho centred on the pose, for both estimators (ours) -----------
+ * Most mobile bases are round.  Handed over as its bounding square such a robot is 27 % too large in area, and collisions are decided
+ * at corners it does not have.  pocs_set_footprint_disc makes the footprint the disc of radius rho (finite, >= 0; 0 is a point robot,
+ * for planners that inflate the obstacles themselves) centred on (x, y) of the pose.  The heading is never read by the collision test.
+ *   records   boxes and discs are prepared as under pocs_set_discs, with ONE difference: the footprint's bounding radius in a record's
+ *             fields 6 and 7 is rho, not the square's sqrt(hx^2 + hy^2).  An uncertain disc's growth is added exactly as before.
+ *   flag      broad phase AND narrow phase, touching included.  dx = cx - x, dy = cy - y; |dx| > field 6 or |dy| > field 7: no.
+ *             box:  e1 = fma(dx, ax, dy ay), e2 = fma(dy, ax, -(dx ay)), q_i = fmax(|e_i| - h_i, 0), touches = !(fma(q1, q1, q2 q2) > rho rho).
+ *             disc: R = r + rho, touches = !(fma(dx, dx, dy dy) > R R); an uncertain disc: the broad phase on the nominal centre, this test
+ *             on the displaced centre (stream 5, the keys, the waypoint word and persistence as above).
+ *             A pose touches the world when it touches any record; every result of both estimators is formed from that flag.
+ * REPLACEMENT: a footprint setter replaces the footprint.  pocs_set_footprint, the text channel's setFootprint and
+ * pocs_set_footprint_parts return to boxes; pocs_set_footprint_disc replaces a single box and a compound footprint alike.  While the
+ * disc is in force pocs_get_footprint_parts reports one part, the bounding square {0, 0, rho, rho}; pocs_get_footprint_disc returns 1
+ * and writes rho (0, nothing written, under a box footprint).  POCS_E_ARG for a radius that is not finite or negative, the footprint
+ * in force kept.  Like every setter it ends run-ahead serving.  Obstacles, schedules, discs and covariances set afterwards are prepared
+ * for rho.
+ * SERVED: whole calls on one GPU, GMM and MC -- single runs, batches in both sub-batch forms, run-ahead, plans with and without both
+ * risk bounds, POCS_OPT_MC_WAYPOINT_COUNTS, stored samples -- over static worlds of up to 64 records, obstacle schedules, discs with
+ * their own schedule and disc covariances, persistent and per waypoint.  MC calls take the per-step form whatever POCS_OPT_MC_FUSED says.
+ * REFUSED in both directions (POCS_E_STATE; the setter inside a begin/end sequence: POCS_E_ORDER; the context is left as it was): a
+ * tree of plans, a large world, a shard, the exchange created or connected, bound moments, an open sequence and pocs_gmm_begin,
+ * POCS_OPT_OBSTACLE_COUNTS = 1, segment checks with J > 1, pocs_probe_device_collide.
+ * NOT applied, never refused: clearance levels and watched regions (their getters answer POCS_E_STATE, "not applied"); they apply
+ * again, bit for bit, once a box footprint is back. */
+int pocs_set_footprint_disc(pocs_ctx* ctx, double radius);
+int pocs_get_footprint_disc(const pocs_ctx* ctx, double* radius);   /* 1 and *radius = rho while in force, else 0 */
+
 /* ---- results of the last run, for audits and parity tests ------------------------------- */
 int pocs_get_path_length(const pocs_ctx* ctx);
 int pocs_get_waypoint_probabilities(pocs_ctx* ctx, double* out, int cap);         /* `probabilities`, MCSimulator.h:660,678,817 */
@@ -780,6 +808,16 @@ int pocs_probe_device_disc_noise(pocs_ctx* ctx, const double* fp4, const double*
    pose i touches displaced disc d -- through the MC kernels' single-pose form --, bit 31 should the sampling kernel's two-pose lane-mask
    form (poses 2 j, 2 j + 1) ever disagree.  Never refused.  POCS_E_ARG for a null pointer, D outside 1 .. 16, n outside 2 .. 2^20 or odd,
    an odd first, a bad footprint, disc or covariance and ANY input that is not finite. */
+int pocs_probe_device_footprint_disc(pocs_ctx* ctx, double radius, const double* boxes /* M x 5 */, int M, const double* discs /* D x 3 */, int D,
+                                     const double* cov /* NULL or D x 3 */, uint64_t seed, uint32_t waypoint_word, unsigned long long first /* even */,
+                                     int n, const double* poses_xyt, int* out /* n */);
+/* TEST HOOK beside pocs_probe_device_discs, equally self-contained: the ROUND footprint's test on the DEVICE for the caller's own radius,
+   M boxes and D discs (M + D <= 64) and, where cov is given, the discs' covariances {sxx, sxy, syy} (zeros: a certain disc), prepared as
+   the library prepares the context's.  Pose i has index first + i; the seed and the waypoint word are the caller's (read under cov
+   only).  out[i] bit 0: pose i touches some box, bit 1: some disc, displaced where cov says so -- both through the MC kernels'
+   single-pose form on the full table --, bit 8 should the sampling kernel's two-pose lane-mask form (poses 2 j, 2 j + 1) ever disagree.
+   It reads nothing of the context's world or modes, so it is never refused.  POCS_E_ARG for a null pointer, n outside 1 .. 2^20, M + D
+   out of range, an odd first, a bad radius, box, disc or covariance and ANY input that is not finite. */
 int pocs_get_sequence_time(pocs_ctx* ctx, double* ms, int* concurrent);  /* POCS_OPT_PROFILE=1, whole-run GMM calls: first sampling launch -> end of the last one, and how many
                                                                             sub-batches of the call were in flight side by side (their launches overlap: DESIGN.md section 5) */
 

@@ -100,6 +100,10 @@ SIGNATURES = {
     "pocs_set_discs": (C.c_int, [_vp, _dp, C.c_int, C.c_int]),
     "pocs_get_discs": (C.c_int, [_vp, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "pocs_probe_device_discs": (C.c_int, [_vp, _dp, _dp, C.c_int, _dp, C.c_int, C.c_int, _dp, C.POINTER(C.c_int)]),
+    "pocs_set_footprint_disc": (C.c_int, [_vp, C.c_double]),
+    "pocs_get_footprint_disc": (C.c_int, [_vp, _dp]),
+    "pocs_probe_device_footprint_disc": (C.c_int, [_vp, C.c_double, _dp, C.c_int, _dp, C.c_int, _dp, C.c_uint64, C.c_uint32, C.c_ulonglong, C.c_int, _dp,
+                                                   C.POINTER(C.c_int)]),
     "pocs_set_disc_covariances": (C.c_int, [_vp, _dp, C.c_int, C.c_int, C.c_int]),
     "pocs_get_disc_covariances": (C.c_int, [_vp, _dp, C.c_int, C.POINTER(C.c_int)]),
     "pocs_probe_device_disc_noise": (C.c_int, [_vp, _dp, _dp, _dp, C.c_int, C.c_uint64, C.c_uint32, C.c_ulonglong, C.c_int, _dp, _dp, C.POINTER(C.c_uint)]),
@@ -267,7 +271,9 @@ class Context:
 
     # ---- typed setters ----------------------------------------------------------------
     def set_env(self, env):
-        if "footprint_parts" in env:        # a compound footprint (set_footprint_parts) in place of the single box
+        if env.get("footprint_radius") is not None:      # a round footprint (set_footprint_disc) in place of any box
+            self.set_footprint_disc(env["footprint_radius"])
+        elif "footprint_parts" in env:      # a compound footprint (set_footprint_parts) in place of the single box
             self.set_footprint_parts(env["footprint_parts"])
         else:
             fp = env["footprint"]
@@ -359,6 +365,36 @@ class Context:
                                                         C.c_uint64(int(seed)), C.c_uint32(int(waypoint_word)), C.c_ulonglong(int(first)), xyt.shape[0],
                                                         xyt.ctypes.data_as(_dp), centres.ctypes.data_as(_dp), flags.ctypes.data_as(C.POINTER(C.c_uint))))
         return centres, flags
+
+    def set_footprint_disc(self, radius):
+        """A round footprint: the disc of radius `radius` (finite, >= 0; 0 is a point robot) centred on the pose's reference point,
+        in place of the box or the compound footprint in force.  The heading is never read by the collision test; set_env with
+        "footprint", set_footprint_parts and the text channel's setFootprint return to boxes (include/pocs.h)."""
+        self._chk(self.lib.pocs_set_footprint_disc(self.h, float(radius)))
+
+    def footprint_disc(self):
+        """The radius of the round footprint in force, or None under a box footprint."""
+        r = C.c_double(0.0)
+        got = self._chk(self.lib.pocs_get_footprint_disc(self.h, C.byref(r)))
+        return r.value if got == 1 else None
+
+    def probe_device_footprint_disc(self, radius, boxes, discs, poses, cov=None, seed=0, waypoint_word=0, first=0):
+        """Test hook: per pose (n x 3; the heading is not read) the kinds of obstacle a ROUND footprint of the caller's own radius
+        touches on the device, for the caller's own boxes (M x 5), discs (D x 3) and -- where given -- covariances (D x 3): pose i has
+        index first + i (first even).  int32[n]: bit 0 = touches some box, bit 1 = touches some disc (displaced where cov says so),
+        bit 8 = the kernels' two forms disagree (never)."""
+        b = np.ascontiguousarray(_arr(boxes if boxes is not None else []).reshape(-1, 5))
+        d = np.ascontiguousarray(_arr(discs if discs is not None else []).reshape(-1, 3))
+        v = None if cov is None else np.ascontiguousarray(_arr(cov).reshape(-1, 3))
+        assert v is None or v.shape == d.shape
+        xyt = np.ascontiguousarray(_arr(poses).reshape(-1, 3))
+        out = np.full(xyt.shape[0], -1, dtype=np.int32)
+        self._chk(self.lib.pocs_probe_device_footprint_disc(self.h, float(radius), b.ctypes.data_as(_dp) if b.size else None, b.shape[0],
+                                                            d.ctypes.data_as(_dp) if d.size else None, d.shape[0],
+                                                            v.ctypes.data_as(_dp) if v is not None and v.size else None,
+                                                            C.c_uint64(int(seed)), C.c_uint32(int(waypoint_word)), C.c_ulonglong(int(first)),
+                                                            xyt.shape[0], xyt.ctypes.data_as(_dp), out.ctypes.data_as(C.POINTER(C.c_int))))
+        return out
 
     def probe_device_discs(self, footprint, boxes, discs, poses):
         """Test hook: per pose (n x 3) the kinds of obstacle it touches on the device, for the caller's own footprint (dx, dy, hx, hy),

@@ -204,8 +204,39 @@ int pocs_set_footprint(pocs_ctx* c, double dx, double dy, double hx, double hy) 
   if (!(hx > 0) || !(hy > 0)) return fail(c, POCS_E_ARG, "footprint half extents must be > 0");
   c->fp.dx = dx; c->fp.dy = dy; c->fp.hx = hx; c->fp.hy = hy;
   c->fp_F = 1; c->fp_parts[0] = c->fp;               // (a compound footprint is replaced by the single box)
+  c->fp_round = false; c->fp_rho = 0.0;              // (and so is a round one)
   c->env_dirty = true;
   return POCS_OK;
+}
+
+// ---- a round footprint (include/pocs.h) ----
+int pocs_set_footprint_disc(pocs_ctx* c, double radius) {
+  if (!setter(c)) return POCS_E_ARG;
+  if (!std::isfinite(radius) || radius < 0) return fail(c, POCS_E_ARG, "pocs_set_footprint_disc: the radius must be finite and >= 0");
+  // (not a mode of the table: the one mask of what a round footprint excludes, pocs_modes.hpp, and segment checks beside it)
+  unsigned in_the_way = modes_of(c) & pocs_modes::kRoundFpExcluded;
+  if (in_the_way) {                                  // names ONE mode: the open sequence before all others, a connected exchange before its buffer
+    const bool open = (in_the_way & pocs_modes::kSequence) != 0;
+    if (open) in_the_way = pocs_modes::kSequence;
+    if (in_the_way & pocs_modes::kXchgConnected) in_the_way &= ~(unsigned)pocs_modes::kXchgCreated;
+    return fail(c, open ? POCS_E_ORDER : POCS_E_STATE, "pocs_set_footprint_disc: %s; %s",
+                pocs_modes::name((pocs_modes::Mode)(in_the_way & (0u - in_the_way))), pocs_modes::kRoundFpClause);
+  }
+  if (seg_applied(c))
+    return fail(c, POCS_E_STATE, "pocs_set_footprint_disc: segment checks are set (pocs_set_segment_checks); %s", pocs_modes::kRoundFpClause);
+  const double rho = radius == 0.0 ? 0.0 : radius;   // (a point robot: +0.0)
+  c->fp = pocs_footprint{0.0, 0.0, rho, rho};        // the bounding square: what pocs_get_footprint_parts reports
+  c->fp_F = 1; c->fp_parts[0] = c->fp;               // (a compound footprint is replaced)
+  c->fp_round = true; c->fp_rho = rho;
+  c->env_dirty = true;
+  return POCS_OK;
+}
+
+int pocs_get_footprint_disc(const pocs_ctx* c, double* radius) {
+  if (!c) return POCS_E_ARG;
+  if (!rfoot_applied(c)) return 0;
+  if (radius) *radius = c->fp_rho;
+  return 1;
 }
 
 // ---- compound footprints (include/pocs.h) ----
@@ -233,6 +264,7 @@ int pocs_set_footprint_parts(pocs_ctx* c, const double* parts, int F) {
     return fail(c, POCS_E_STATE, "pocs_set_footprint_parts: discs are set (pocs_set_discs); %s", pocs_modes::kDiscClause);
   for (int f = 0; f < F; ++f) c->fp_parts[f] = pocs_footprint{parts[4 * f], parts[4 * f + 1], parts[4 * f + 2], parts[4 * f + 3]};
   c->fp_F = F;
+  c->fp_round = false; c->fp_rho = 0.0;              // (a round footprint is replaced)
   c->fp = c->fp_parts[0];
   c->env_dirty = true;
   return POCS_OK;
@@ -885,6 +917,8 @@ int pocs_set_segment_checks(pocs_ctx* c, int J) {
       return fail(c, POCS_E_STATE, "pocs_set_segment_checks: a compound footprint is set (pocs_set_footprint_parts); %s", pocs_modes::kSegClause);
     if (discs_applied(c))
       return fail(c, POCS_E_STATE, "pocs_set_segment_checks: discs are set (pocs_set_discs); %s", pocs_modes::kDiscClause);
+    if (rfoot_applied(c))
+      return fail(c, POCS_E_STATE, "pocs_set_segment_checks: a round footprint is set (pocs_set_footprint_disc); %s", pocs_modes::kRoundFpClause);
   }
   c->seg_J = J;
   c->env_dirty = true;                               // (J and the fractions live beside the world on the device)

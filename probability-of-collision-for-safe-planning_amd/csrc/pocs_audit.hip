@@ -628,6 +628,71 @@ int pocs_probe_device_discs(pocs_ctx* c, const double* fp4, const double* boxes,
   return rc;
 }
 
+// Test hook: which kinds of obstacle a pose touches under a ROUND footprint, on the device, for a chosen radius, boxes, discs and --
+// where given -- disc covariances (include/pocs.h).  Nothing of the context's world, plans or modes is read: records and rows are
+// prepared here, as upload_world prepares the context's under pocs_set_footprint_disc.
+int pocs_probe_device_footprint_disc(pocs_ctx* c, double radius, const double* boxes, int M, const double* discs, int D, const double* cov,
+                                     uint64_t seed, uint32_t waypoint_word, unsigned long long first, int n, const double* poses, int* out) {
+  if (!c) return POCS_E_ARG;
+  if (!poses || !out || n < 1 || n > (1 << 20) || M < 0 || D < 0 || M + D > POCS_MAX_OBSTACLES || (M > 0 && !boxes) || (D > 0 && !discs) ||
+      (first & 1ull) || first > (1ull << 62))
+    return fail(c, POCS_E_ARG, "pocs_probe_device_footprint_disc: 1 <= n <= 2^20, 0 <= M, 0 <= D, M + D <= %d, first even and at most 2^62, no null pointers", POCS_MAX_OBSTACLES);
+  if (!std::isfinite(radius) || radius < 0) return fail(c, POCS_E_ARG, "pocs_probe_device_footprint_disc: the radius must be finite and >= 0");
+  for (size_t j = 0; j < 5 * (size_t)M; ++j)
+    if (!std::isfinite(boxes[j])) return fail(c, POCS_E_ARG, "pocs_probe_device_footprint_disc: box %zu: value %zu is not finite", j / 5, j % 5);
+  for (int m = 0; m < M; ++m)
+    if (!(boxes[5 * (size_t)m + 2] > 0) || !(boxes[5 * (size_t)m + 3] > 0)) return fail(c, POCS_E_ARG, "pocs_probe_device_footprint_disc: box %d: half extents must be > 0", m);
+  for (size_t j = 0; j < 3 * (size_t)D; ++j)
+    if (!std::isfinite(discs[j])) return fail(c, POCS_E_ARG, "pocs_probe_device_footprint_disc: disc %zu: value %zu is not finite", j / 3, j % 3);
+  for (int d = 0; d < D; ++d)
+    if (!(discs[3 * (size_t)d + 2] > 0)) return fail(c, POCS_E_ARG, "pocs_probe_device_footprint_disc: disc %d: the radius must be > 0", d);
+  for (size_t j = 0; j < 3 * (size_t)n; ++j)
+    if (!std::isfinite(poses[j])) return fail(c, POCS_E_ARG, "pocs_probe_device_footprint_disc: pose %zu is not finite", j / 3);
+  const double rho = radius == 0.0 ? 0.0 : radius;
+  std::vector<pocs_env_dev> env(1);
+  memset(env.data(), 0, sizeof(pocs_env_dev));
+  env[0].fp = pocs_footprint{0.0, 0.0, rho, rho}; env[0].M = M + D;
+  std::vector<double> rows(POCS_MAX_OBSTACLES * POCS_NOISE_STRIDE, 0.0);
+  for (int m = 0; m < M; ++m) pocs_prepare_obstacle_round(boxes + (size_t)m * 5, rho, &env[0].obs[(size_t)m * POCS_OBS_STRIDE]);
+  for (int d = 0; d < D; ++d) {
+    double* const rec = &env[0].obs[(size_t)(M + d) * POCS_OBS_STRIDE];
+    pocs_prepare_disc_round(discs + (size_t)d * 3, rho, rec);
+    if (cov) {
+      double* const row = &rows[(size_t)(M + d) * POCS_NOISE_STRIDE];
+      if (pocs_disc_noise_factor(cov + (size_t)d * 3, row) < 0)
+        return fail(c, POCS_E_ARG, "pocs_probe_device_footprint_disc: disc %d: neither zeros nor a finite covariance with sxx > 0 and syy - sxy^2 / sxx > 0", d);
+      row[3] = (double)d;
+      pocs_disc_noise_grow(row, rec);
+    }
+  }
+  HIPCHK(c, hipSetDevice(c->device));
+  if (int r = upload_tables(c)) return r;
+  std::vector<double> h(2 * (size_t)n);
+  for (int i = 0; i < n; ++i)
+    for (int j = 0; j < 2; ++j) h[(size_t)j * n + i] = poses[3 * (size_t)i + j];      // (the heading is never read)
+  // [env | rows | x | y] then [out n] ints
+  static_assert(sizeof(pocs_env_dev) % 8 == 0, "the probe's buffer keeps its parts aligned");
+  const size_t off_rows = sizeof(pocs_env_dev), off_x = off_rows + rows.size() * sizeof(double), off_out = off_x + 2 * (size_t)n * sizeof(double);
+  char* buf = nullptr;
+  HIPCHK(c, hipMalloc((void**)&buf, off_out + (size_t)n * sizeof(int)));
+  int rc = POCS_OK;
+  if (hipMemcpy(buf, env.data(), sizeof(pocs_env_dev), hipMemcpyHostToDevice) != hipSuccess ||
+      hipMemcpy(buf + off_rows, rows.data(), rows.size() * sizeof(double), hipMemcpyHostToDevice) != hipSuccess ||
+      hipMemcpy(buf + off_x, h.data(), h.size() * sizeof(double), hipMemcpyHostToDevice) != hipSuccess ||
+      hipMemset(buf + off_out, 0, (size_t)n * sizeof(int)) != hipSuccess)
+    rc = fail(c, POCS_E_DEVICE, "probe upload failed");
+  const double* d_x = (const double*)(buf + off_x);
+  if (rc == POCS_OK && pocs_launch_probe_footprint_disc((const pocs_env_dev*)buf, cov ? (const double*)(buf + off_rows) : nullptr,
+                                                        (const pocs_tables*)c->d_tables.p, seed, waypoint_word, first, n, d_x, d_x + n,
+                                                        (int*)(buf + off_out), c->stream) != hipSuccess)
+    rc = fail(c, POCS_E_DEVICE, "probe launch failed");
+  if (rc == POCS_OK && hipStreamSynchronize(c->stream) != hipSuccess) rc = fail(c, POCS_E_DEVICE, "probe kernel failed");
+  if (rc == POCS_OK && hipMemcpy(out, buf + off_out, (size_t)n * sizeof(int), hipMemcpyDeviceToHost) != hipSuccess)
+    rc = fail(c, POCS_E_DEVICE, "probe download failed");
+  (void)hipFree(buf);
+  return rc;
+}
+
 // Test hook: the displaced centres and the touched displaced discs, on the device, for chosen poses, pose indices, footprint, discs and
 // covariances (include/pocs.h).  Nothing of the context's world, plans or modes is read: records and rows are prepared here, as
 // upload_world prepares the context's.

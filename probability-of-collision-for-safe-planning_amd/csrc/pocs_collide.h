@@ -258,6 +258,95 @@ POCS_HD bool pocs_pose_collides_noisy(double x, double y, double th, const pocs_
   return hit;
 }
 
+// ---- a round footprint (pocs_set_footprint_disc) ------------------------------------------------------------------------
+// The robot is a disc of radius rho >= 0 centred on the pose's reference point (rho = 0: a point).  It has no heading: theta is never
+// read, and no sine or cosine appears anywhere below.  The records are the table's as it is under discs -- boxes by
+// pocs_prepare_box_beside_discs' rule (a zero sine is +0.0), discs as their bounding squares with the ay = -0.0 marker, an uncertain
+// disc's fields 6 and 7 grown by pocs_disc_noise_grow -- with ONE difference: the footprint's bounding radius in fields 6 and 7 is
+// rho itself, pocs_prepare_obstacle's operations in their order with rho in place of sqrt(hx^2 + hy^2).  The flag is broad phase AND
+// narrow phase, touching included:
+//   box record    e = the offset in the obstacle's frame (pocs_box_narrow's e1, e2), q_i = fmax(|e_i| - h_i, 0), the squared distance
+//                 from the pose to the box fma(q1, q1, q2 q2) against rho rho.  An axis-aligned record takes e = (dx, dy): the same bits
+//                 (fma(dx, 1, dy * 0) is dx up to the sign of a zero, which the absolute value drops)
+//   disc record   R = r + rho, fma(dx, dx, dy dy) against R R; an uncertain disc: the same on the displaced centre (pocs_disc_displaced)
+POCS_HD void pocs_prepare_obstacle_round(const double box5[5], double rho, double* rec) {
+  double sn, cs;
+  pocs_sincos(box5[4], &sn, &cs);
+  rec[0] = box5[0]; rec[1] = box5[1];
+  rec[2] = cs; rec[3] = sn == 0.0 ? fabs(sn) : sn;                 // (pocs_prepare_box_beside_discs: the marker means a disc)
+  rec[4] = box5[2]; rec[5] = box5[3];
+  rec[6] = (box5[2] * fabs(cs) + box5[3] * fabs(sn)) + rho;
+  rec[7] = (box5[2] * fabs(sn) + box5[3] * fabs(cs)) + rho;
+}
+POCS_HD void pocs_prepare_disc_round(const double disc3[3], double rho, double* rec) {
+  const double sq[5] = {disc3[0], disc3[1], disc3[2], disc3[2], 0.0};
+  pocs_prepare_obstacle_round(sq, rho, rec);
+  rec[2] = 1.0; rec[3] = -0.0;
+}
+// The two narrow phases, for a record that has passed the broad phase: (dx, dy) = the record's centre minus the pose.
+POCS_HD bool pocs_round_box_narrow(double dx, double dy, double rho, const double* o) {
+  const double ax = o[2], ay = o[3];
+  const double e1 = fma(dx, ax, dy * ay);
+  const double e2 = fma(dy, ax, -(dx * ay));
+  const double q1 = fmax(fabs(e1) - o[4], 0.0);
+  const double q2 = fmax(fabs(e2) - o[5], 0.0);
+  return !(fma(q1, q1, q2 * q2) > rho * rho);
+}
+POCS_HD bool pocs_round_disc_narrow(double dx, double dy, double rho, double r) {
+  const double R = r + rho;
+  return !(fma(dx, dx, dy * dy) > R * R);
+}
+// pocs_world_hit's twin
+POCS_HD bool pocs_round_world_hit(double x, double y, double rho, const double* o) {
+  const double dx = o[0] - x, dy = o[1] - y;
+  if (fabs(dx) > o[6] || fabs(dy) > o[7]) return false;
+  if (pocs_record_is_disc(o[3])) return pocs_round_disc_narrow(dx, dy, rho, o[4]);
+  return pocs_round_box_narrow(dx, dy, rho, o);
+}
+// pocs_world_hit_noisy's twin: the broad phase on the nominal centre, an uncertain disc's narrow phase on the displaced one
+POCS_HD bool pocs_round_world_hit_noisy(double x, double y, double rho, const double* o, const double* row, uint64_t seed, uint64_t index,
+                                        uint32_t v, const pocs_tables* T) {
+  const double dx = o[0] - x, dy = o[1] - y;
+  if (fabs(dx) > o[6] || fabs(dy) > o[7]) return false;
+  if (pocs_record_is_disc(o[3])) {
+    if (row[0] != 0.0) {                                             // (wave-uniform) an uncertain disc
+      double cxp, cyp;
+      pocs_disc_displaced(o[0], o[1], row, seed, index, v, T, &cxp, &cyp);
+      return pocs_round_disc_narrow(cxp - x, cyp - y, rho, o[4]);
+    }
+    return pocs_round_disc_narrow(dx, dy, rho, o[4]);
+  }
+  return pocs_round_box_narrow(dx, dy, rho, o);
+}
+// One pose against the table, the two kinds apart as pocs_pose_kinds_touched gives them: bit 0 = touches some box, bit 1 = touches
+// some disc; the flag is kinds != 0.  `rows` (null: no covariances): POCS_NOISE_STRIDE doubles per record of `obs`, and then the
+// pose's index, the seed, the waypoint word and ALL the tables (pocs_pose_collides_noisy) are read.
+POCS_HD unsigned pocs_round_pose_kinds(double x, double y, double rho, const double* obs, int M, const double* rows = nullptr,
+                                       uint64_t seed = 0, uint64_t index = 0, uint32_t v = 0, const pocs_tables* T = nullptr) {
+  unsigned kinds = 0u;
+  for (int m = 0; m < M; ++m) {
+    const double* o = obs + m * POCS_OBS_STRIDE;
+    const bool t = rows ? pocs_round_world_hit_noisy(x, y, rho, o, rows + m * POCS_NOISE_STRIDE, seed, index, v, T)
+                        : pocs_round_world_hit(x, y, rho, o);
+    if (t) kinds |= pocs_record_is_disc(o[3]) ? 2u : 1u;
+  }
+  return kinds;
+}
+// checkCollision for one pose under a round footprint, and its twin under disc covariances (the MC kernels' forms)
+POCS_HD bool pocs_round_pose_collides(double x, double y, double rho, const double* obs, int M) {
+  bool hit = false;                                                // (set under a condition, not or-ed in: see pocs_pair_collides)
+  for (int m = 0; m < M; ++m)
+    if (pocs_round_world_hit(x, y, rho, obs + m * POCS_OBS_STRIDE)) hit = true;
+  return hit;
+}
+POCS_HD bool pocs_round_pose_collides_noisy(double x, double y, double rho, const double* obs, const double* rows, int M, uint64_t seed,
+                                            uint64_t index, uint32_t v, const pocs_tables* T) {
+  bool hit = false;
+  for (int m = 0; m < M; ++m)
+    if (pocs_round_world_hit_noisy(x, y, rho, obs + m * POCS_OBS_STRIDE, rows + m * POCS_NOISE_STRIDE, seed, index, v, T)) hit = true;
+  return hit;
+}
+
 // The same predicate for the two poses a thread of k_gmm_step draws per iteration, with ONE pass over the obstacle
 // table (it sits in LDS) and the loop's bookkeeping paid once.  Per pose exactly the operations of pocs_pose_collides, in
 // the same order: the same flags.  On the device (pocs_pair_loop) the compiled loop
@@ -462,6 +551,82 @@ __device__ __forceinline__ void pocs_pair_collides_masks(const double x[2], cons
       pocs_pair_loop<EAGER, false>(x, y, th, fp, obs, M, T, V, mask, each);
     }
   }
+}
+
+// The pair form under a round footprint (pocs_set_footprint_disc), in the manner of pocs_pair_loop: one fetch per record serves both
+// poses, the record's kind is decided by the scalar branch on its marker, every answer is balloted and or-ed into the pose's lane
+// mask by a scalar instruction -- no flag lives in a vector register -- and there is no heading: per pose the operations of
+// pocs_round_world_hit (NZ = pocs_noise_pair: of pocs_round_world_hit_noisy, one Philox call per pair and uncertain disc) in their
+// order.  `kinds`, where given: the part of each mask that disc records contributed.  The masks are zero when M <= 0.
+template <class NZ = pocs_noise_none>
+__device__ __forceinline__ void pocs_pair_round_masks(const double x[2], const double y[2], const double rho, const double* obs, int M,
+                                                      [[maybe_unused]] const pocs_tables* T, [[maybe_unused]] const pocs_vconst* V,
+                                                      unsigned long long mask[2], unsigned long long* kinds = nullptr, [[maybe_unused]] NZ nz = NZ()) {
+  unsigned long long m0 = 0ull, m1 = 0ull, k0 = 0ull, k1 = 0ull;
+  const double rho2 = rho * rho;
+  const __attribute__((address_space(3))) pocs_v2d* o = (const __attribute__((address_space(3))) pocs_v2d*)obs;
+  asm volatile("" : "+v"(o));
+  for (int m = 0; m < M; ++m, o += POCS_OBS_STRIDE / 2) {
+    const pocs_v2d c = o[0], b = o[3], a = o[1], e = o[2];           // (cx, cy) (bx, by) | (ax, ay) (hx, hy)
+    double dx[2], dy[2];
+    unsigned long long pm[2], bt[2] = {0ull, 0ull};
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {                                    // the broad phase
+      dx[h] = c.x - x[h];
+      dy[h] = c.y - y[h];
+      pm[h] = __builtin_amdgcn_ballot_w64(!(fabs(dx[h]) > b.x)) & __builtin_amdgcn_ballot_w64(!(fabs(dy[h]) > b.y));
+    }
+    if ((pm[0] | pm[1]) == 0ull) continue;
+    const double ay = a.y;                                           // (a copy: the bits of THIS element are compared)
+    const bool disc = __builtin_amdgcn_ballot_w64(__builtin_bit_cast(unsigned long long, ay) == 0x8000000000000000ull) != 0ull;
+    if (disc) {
+      const double R = e.x + rho, R2 = R * R;
+      bool noisy = false;                                            // (scalar) the disc is uncertain: its row's l00 is not zero
+      if constexpr (NZ::on) {
+        const double* const row = nz.rows + m * POCS_NOISE_STRIDE;
+        const double l00 = row[0];
+        noisy = __builtin_amdgcn_ballot_w64(l00 != 0.0) != 0ull;
+        if (noisy) {
+          const pocs_u32x4 wd = pocs_draw(nz.seed, nz.pair, nz.v, POCS_STREAM_DISC, (uint32_t)row[3]);
+          const double l10 = row[1], l11 = row[2];
+#pragma unroll
+          for (int h = 0; h < 2; ++h) {
+            if (pm[h] == 0ull) continue;
+            double z0, z1;
+            pocs_normal_pair_w2(h ? wd.z : wd.x, h ? wd.w : wd.y, T, &z0, &z1, V);
+            const double ex = fma(l00, z0, c.x) - x[h], ey = fma(l11, z1, fma(l10, z0, c.y)) - y[h];
+            bt[h] = pm[h] & __builtin_amdgcn_ballot_w64(!(fma(ex, ex, ey * ey) > R2));
+          }
+        }
+      }
+      if (!noisy) {
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+          if (pm[h] == 0ull) continue;
+          bt[h] = pm[h] & __builtin_amdgcn_ballot_w64(!(fma(dx[h], dx[h], dy[h] * dy[h]) > R2));
+        }
+      }
+      k0 |= bt[0]; k1 |= bt[1];
+    } else {
+      // an axis-aligned record (every lane reads the same one): the offset as it is
+      const bool turned = (__builtin_amdgcn_ballot_w64(a.x != 1.0) | __builtin_amdgcn_ballot_w64(a.y != 0.0)) != 0ull;
+#pragma unroll
+      for (int h = 0; h < 2; ++h) {
+        if (pm[h] == 0ull) continue;
+        double e1 = dx[h], e2 = dy[h];
+        if (turned) {
+          e1 = fma(dx[h], a.x, dy[h] * a.y);
+          e2 = fma(dy[h], a.x, -(dx[h] * a.y));
+        }
+        const double q1 = fmax(fabs(e1) - e.x, 0.0);
+        const double q2 = fmax(fabs(e2) - e.y, 0.0);
+        bt[h] = pm[h] & __builtin_amdgcn_ballot_w64(!(fma(q1, q1, q2 * q2) > rho2));
+      }
+    }
+    m0 |= bt[0]; m1 |= bt[1];
+  }
+  mask[0] = m0; mask[1] = m1;
+  if (kinds) { kinds[0] = k0; kinds[1] = k1; }
 }
 #endif
 

@@ -232,6 +232,12 @@ struct pocs_ctx {
   // disc index}, record by record beside d_env) and grows the disc records, and every call is served by the _noise / MC_NOISE forms
   std::vector<double> disc_cov;
   int disc_noise_persistent = 0;         // the MC path's waypoint word: 1 = 0 at every waypoint, 0 = the waypoint
+  // a round footprint (pocs_set_footprint_disc): fp_round = false is off -- every call is, launch for launch, what it is without this.
+  // On: the robot is the disc of radius fp_rho centred on the pose; `fp` is its bounding square {0, 0, rho, rho} and fp_F = 1 (what
+  // pocs_get_footprint_parts reports), upload_world prepares every record with rho as the bounding radius, every call is served by
+  // the kernels' _rfoot / MC_RFOOT forms (rfoot_applied) and the modes of pocs_modes::kRoundFpExcluded and segment checks are refused
+  bool fp_round = false;
+  double fp_rho = 0.0;
 
   // host image (headers | chains | initial mixtures) of the NEXT batch, computed while the GPU
   // works on the current one
@@ -422,12 +428,21 @@ inline int discs_refuse(pocs_ctx* c, const char* what, pocs_modes::Mode enter) {
   return fail(c, POCS_E_STATE, "%s: discs are set (pocs_set_discs); %s", what, pocs_modes::kDiscClause);
 }
 
+// A round footprint is in force (pocs_set_footprint_disc): as discs, one mask (pocs_modes::kRoundFpExcluded) asked in front of the
+// table, behind the discs' mask, and by the setter itself.
+inline bool rfoot_applied(const pocs_ctx* c) { return c->fp_round; }
+inline int rfoot_refuse(pocs_ctx* c, const char* what, pocs_modes::Mode enter) {
+  if (!rfoot_applied(c) || !(enter & pocs_modes::kRoundFpExcluded)) return POCS_OK;
+  return fail(c, POCS_E_STATE, "%s: a round footprint is set (pocs_set_footprint_disc); %s", what, pocs_modes::kRoundFpClause);
+}
+
 // May the context enter `enter`, as asked by the call `what`?  The one place that refuses a combination (pocs_modes.hpp).
 inline int may_enter(pocs_ctx* c, const char* what, pocs_modes::Mode enter, unsigned among = pocs_modes::kAll) {
   if (among == pocs_modes::kAll) {                   // (a setter's staged asks in front of its argument checks enter nothing yet)
     if (int r = parts_refuse(c, what, enter)) return r;
     if (int r = seg_refuse(c, what, enter)) return r;
     if (int r = discs_refuse(c, what, enter)) return r;
+    if (int r = rfoot_refuse(c, what, enter)) return r;
   }
   const pocs_modes::Refusal r = pocs_modes::refusal(modes_of(c), enter, among);
   if (r.code == POCS_OK) return POCS_OK;

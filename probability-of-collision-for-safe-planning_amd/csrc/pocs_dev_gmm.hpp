@@ -284,6 +284,45 @@ __device__ __forceinline__ void gmm_cull(const pocs_gmm_launch& a, gmm_smem<K, T
   if (lane == 0) sm.nkeep[rb] = __popcll(mask);
 }
 
+// The cull under a round footprint (pocs_set_footprint_disc; one wave, all 64 lanes): the footprint's extent is rho at every heading,
+// so the table's fields 6 and 7 -- the record's own world box + rho, an uncertain disc's growth included -- are already tight and the
+// kept list carries them as they are; the run's heading range, the four end values and fp_phi are not formed.  The keep test is
+// gmm_cull's on those fields, with pad = 1e-6 (the footprint is centred): a record it drops is rejected by the broad phase for every
+// pose the run can draw, and a kept record keeps its own broad phase, so the kept list's flags are the full table's, bit for bit.
+// RN: a kept record's row of the launch's noise table is written to the kept list's position, as gmm_cull<true> does.
+template <bool RN, int K, int TB, bool OC, bool CL, bool FPN, bool RG, bool SG>
+__device__ __forceinline__ void gmm_cull_rfoot(const pocs_gmm_launch& a, gmm_smem<K, TB, OC, CL, FPN, RG, SG>& sm, const int rb, const int lane, const double* par,
+                                               [[maybe_unused]] double* nz = nullptr) {
+  const int M = a.M;
+  const double* const obs = sm.obs();
+  double xlo = 1e300, xhi = -1e300, ylo = 1e300, yhi = -1e300;
+#pragma unroll
+  for (int k = 0; k < K; ++k) {
+    const double* p = &par[k * POCS_PARAM_STRIDE];
+    const double ex = 6.67 * fabs(p[3]), ey = 6.67 * (fabs(p[4]) + fabs(p[5]));
+    xlo = fmin(xlo, p[0] - ex); xhi = fmax(xhi, p[0] + ex);
+    ylo = fmin(ylo, p[1] - ey); yhi = fmax(yhi, p[1] + ey);
+  }
+  const double pad = 1e-6;
+  xlo -= pad; xhi += pad; ylo -= pad; yhi += pad;
+  bool keep = false;
+  if (lane < M) {
+    const double* o = &obs[lane * POCS_OBS_STRIDE];
+    keep = !(o[0] - o[6] > xhi || o[0] + o[6] < xlo || o[1] - o[7] > yhi || o[1] + o[7] < ylo);
+  }
+  const unsigned long long mask = __ballot(keep);
+  if (keep) {
+    const int pos = __popcll(mask & ((1ull << lane) - 1ull));
+#pragma unroll
+    for (int j = 0; j < POCS_OBS_STRIDE; ++j) sm.keep[rb][pos * POCS_OBS_STRIDE + j] = obs[lane * POCS_OBS_STRIDE + j];
+    if constexpr (RN) {
+#pragma unroll
+      for (int j = 0; j < POCS_NOISE_STRIDE; ++j) nz[(rb * POCS_MAX_OBSTACLES + pos) * POCS_NOISE_STRIDE + j] = a.noise[lane * POCS_NOISE_STRIDE + j];
+    }
+  }
+  if (lane == 0) sm.nkeep[rb] = __popcll(mask);
+}
+
 // The clearance form's second list (one wave, all 64 lanes, beside the wave that runs gmm_cull for the same run buffer): the table
 // prepared for the footprint grown by the largest clearance (sm.obs2()) culled against the same mixture with that footprint's
 // extents -- gmm_cull's arithmetic with clh's footprint, radius and corner angle in place of the launch's -- into keep2[rb]; the
@@ -494,12 +533,15 @@ __device__ __forceinline__ void gmm_cull_seg(const pocs_gmm_launch& a, gmm_smem<
 //   decides a record's kind by a scalar branch and ballots the disc's answer into the same masks.  Nothing else differs.
 //   RN (pocs_set_disc_covariances, on top of RD; `nz`: the kept rows gmm_cull<true> left): the ROUND form is handed the run buffer's
 //   rows, the run's seed, the lane's pair index pair0 + lp and the waypoint, and tests an uncertain disc on its displaced centre.
+//   RF (pocs_set_footprint_disc, with or without RN, never with RD: the form serves worlds with and without discs): the collision test
+//   is pocs_pair_round_masks on the kept list gmm_cull_rfoot left -- the radius is fp.hx, the headings are not looked at.
 template <int K, bool STORE, int TB, bool LONE_PRE = false, bool OC = false, bool CL = false, bool FPN = false, bool RG = false, bool SG = false,
-          bool RD = false, bool RN = false>
+          bool RD = false, bool RN = false, bool RF = false>
 __device__ __forceinline__ void gmm_units(const pocs_gmm_launch& a, gmm_smem<K, TB, OC, CL, FPN, RG, SG>& sm, const int w, const int r0,
                                           const int ta, const int tb, const double* zpre = nullptr, const int npre = 0,
                                           [[maybe_unused]] const double* nz = nullptr) {
-  static_assert(!RN || RD, "uncertain discs: on top of the round form");
+  static_assert(!RN || RD || RF, "uncertain discs: on top of the round form");
+  static_assert(!(RF && (RD || LONE_PRE || OC || CL || FPN || RG || SG)), "a round footprint: a family of its own");
   const pocs_tables* const s_tab = &sm.tab;
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -617,6 +659,14 @@ __device__ __forceinline__ void gmm_units(const pocs_gmm_launch& a, gmm_smem<K, 
         if (b != 0ull && lane == (int)__builtin_ctzll(b))
           __hip_atomic_fetch_add(&occ[m], (unsigned)__popcll(b), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
       });
+    } else
+    if constexpr (RF) {
+      if constexpr (RN) {
+        const pocs_noise_pair np = {nz + rb * (POCS_MAX_OBSTACLES * POCS_NOISE_STRIDE), seed_it, pair0 + (uint64_t)(unsigned)lp, (uint32_t)w};
+        pocs_pair_round_masks<pocs_noise_pair>(xs, ys, fp.hx, s_keep, nkeep, s_tab, vc, hits, nullptr, np);
+      } else {
+        pocs_pair_round_masks(xs, ys, fp.hx, s_keep, nkeep, s_tab, vc, hits);
+      }
     } else
     if constexpr (RN) {
       const pocs_noise_pair np = {nz + rb * (POCS_MAX_OBSTACLES * POCS_NOISE_STRIDE), seed_it, pair0 + (uint64_t)(unsigned)lp, (uint32_t)w};
@@ -992,10 +1042,11 @@ __device__ __forceinline__ void gmm_close_sums(const pocs_gmm_launch& a, const i
 // the or-ed flags), the tickets and the closers are what they are.  LDS: + 8 KB for the second kept table, + 0.3 KB, and 24 instead of
 // 32 held units, as the clearance form: two blocks per CU in every instantiation.
 template <int K, bool STORE, int TB, bool LONE, bool RISK, bool TREE = false, bool OC = false, bool WORLD = false, bool CL = false, bool FPN = false,
-          bool RG = false, bool SG = false, bool RD = false, bool RN = false>
+          bool RG = false, bool SG = false, bool RD = false, bool RN = false, bool RF = false>
 __device__ __forceinline__ void gmm_step_block(const pocs_gmm_launch a) {      // (by value, as a kernel holds its argument)
   typedef gmm_smem<K, TB, OC, CL, FPN, RG, SG> smem_t;
-  static_assert(!RN || RD, "uncertain discs: on top of the round form");
+  static_assert(!RN || RD || RF, "uncertain discs: on top of the round form");
+  static_assert(!(RF && (RD || LONE || TREE || OC || WORLD || CL || FPN || RG || SG)), "a round footprint: the ticket form of a batch or of plans on a small world, no counts, no segment checks");
   static_assert(!(RD && (LONE || TREE || OC || WORLD || CL || FPN || RG || SG)), "round obstacles: the ticket form of a batch or of plans on a small world, a single footprint box, no counts, no segment checks");
   static_assert(!(SG && (LONE || TREE || OC || WORLD || CL || FPN || RG)), "segment checks: the ticket form of a batch or of plans on a small world, a single footprint box, no other counts");
   static_assert(!SG || TB >= 256, "waves 2 and 3 build the second kept list");
@@ -1181,6 +1232,9 @@ __device__ __forceinline__ void gmm_step_block(const pocs_gmm_launch a) {      /
     if constexpr (FPN) {
       if (tid < 64) gmm_cull_parts(a, sm, 0, tid, sm.par[0]);
       else if (tid < 128 && r1 > r0) gmm_cull_parts(a, sm, 1, tid - 64, sm.par[1]);
+    } else if constexpr (RF) {
+      if (tid < 64) gmm_cull_rfoot<RN>(a, sm, 0, tid, sm.par[0], s_nz);
+      else if (tid < 128 && r1 > r0) gmm_cull_rfoot<RN>(a, sm, 1, tid - 64, sm.par[1], s_nz);
     } else if constexpr (RN) {
       if (tid < 64) gmm_cull<true>(a, sm, 0, tid, sm.par[0], s_nz);
       else if (tid < 128 && r1 > r0) gmm_cull<true>(a, sm, 1, tid - 64, sm.par[1], s_nz);
@@ -1194,6 +1248,8 @@ __device__ __forceinline__ void gmm_step_block(const pocs_gmm_launch a) {      /
   POCS_STAMP(0);
   for (int ta = t0; ta < t1; ta += SUB) {
     const int tb = (ta + SUB < t1) ? ta + SUB : t1;
+    if constexpr (RF) gmm_units<K, STORE, TB, LONE, OC, CL, FPN, RG, SG, false, RN, true>(a, sm, w, r0, ta, tb, s_zpre, ta == t0 ? npre : 0, s_nz);
+    else
     if constexpr (RN) gmm_units<K, STORE, TB, LONE, OC, CL, FPN, RG, SG, RD, true>(a, sm, w, r0, ta, tb, s_zpre, ta == t0 ? npre : 0, s_nz);
     else
     gmm_units<K, STORE, TB, LONE, OC, CL, FPN, RG, SG, RD>(a, sm, w, r0, ta, tb, s_zpre, ta == t0 ? npre : 0);
@@ -1418,6 +1474,26 @@ __global__ __launch_bounds__(TB, POCS_GMM_BLOCKS_PER_CU * TB / 256) void k_gmm_s
 template <int K, bool STORE, int TB>
 __global__ __launch_bounds__(TB, POCS_GMM_BLOCKS_PER_CU * TB / 256) void k_gmm_step_risk_noise(pocs_gmm_launch a) {
   gmm_step_block<K, STORE, TB, false, true, false, false, false, false, false, false, false, true, true>(a);
+}
+
+// The forms under a round footprint (RF above; pocs_set_footprint_disc): a family of its own names, for worlds with and without discs,
+// and its noise twins under disc covariances.  The head culls with gmm_cull_rfoot -- no heading range -- and the sampling loop tests
+// with pocs_pair_round_masks, which forms no sine or cosine.  The shared memory is the twin's (the noise twins: + the 4 KB of rows).
+template <int K, bool STORE, int TB>
+__global__ __launch_bounds__(TB, POCS_GMM_BLOCKS_PER_CU * TB / 256) void k_gmm_step_rfoot(pocs_gmm_launch a) {
+  gmm_step_block<K, STORE, TB, false, false, false, false, false, false, false, false, false, false, false, true>(a);
+}
+template <int K, bool STORE, int TB>
+__global__ __launch_bounds__(TB, POCS_GMM_BLOCKS_PER_CU * TB / 256) void k_gmm_step_risk_rfoot(pocs_gmm_launch a) {
+  gmm_step_block<K, STORE, TB, false, true, false, false, false, false, false, false, false, false, false, true>(a);
+}
+template <int K, bool STORE, int TB>
+__global__ __launch_bounds__(TB, POCS_GMM_BLOCKS_PER_CU * TB / 256) void k_gmm_step_rfoot_noise(pocs_gmm_launch a) {
+  gmm_step_block<K, STORE, TB, false, false, false, false, false, false, false, false, false, false, true, true>(a);
+}
+template <int K, bool STORE, int TB>
+__global__ __launch_bounds__(TB, POCS_GMM_BLOCKS_PER_CU * TB / 256) void k_gmm_step_risk_rfoot_noise(pocs_gmm_launch a) {
+  gmm_step_block<K, STORE, TB, false, true, false, false, false, false, false, false, false, false, true, true>(a);
 }
 
 // The forms under a large collision world (WORLD above): kernels of their own names again.

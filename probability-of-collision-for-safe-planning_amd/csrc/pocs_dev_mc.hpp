@@ -159,7 +159,12 @@ __device__ __forceinline__ mc_run_start mc_start(const pocs_mc_launch& a) {
 // index first + i, disc, waypoint word), the word 0 at every waypoint under POCS_DISC_NOISE_PERSISTENT and the launch's waypoint
 // otherwise.  The rows are read where they lie (wave-uniform addresses).  The head stages the sector table alone and the Box-Muller
 // radius needs the log tables: these forms stage them behind the head (stage_mc_log_tables).  Nothing else differs.
-enum { MC_PLAIN = 0, MC_COUNTS = 1, MC_STOP = 2, MC_BOXES = 4, MC_CLEAR = 8, MC_PARTS = 16, MC_REGIONS = 32, MC_SEG = 64, MC_ROUND = 128, MC_NOISE = 256 };
+//
+// MC_RFOOT (pocs_set_footprint_disc), a flag on top of MC_ROUND and of MC_ROUND | MC_NOISE, for worlds with and without discs: the
+// footprint is the disc of radius fp.hx centred on the particle, the collision test pocs_round_pose_collides (MC_NOISE:
+// pocs_round_pose_collides_noisy, the same index, seed and waypoint word).  The heading is not looked at.  Nothing else differs.
+enum { MC_PLAIN = 0, MC_COUNTS = 1, MC_STOP = 2, MC_BOXES = 4, MC_CLEAR = 8, MC_PARTS = 16, MC_REGIONS = 32, MC_SEG = 64, MC_ROUND = 128, MC_NOISE = 256,
+       MC_RFOOT = 512 };
 static_assert(POCS_MAX_OBSTACLES <= 64, "a particle's touched boxes are a 64-bit mask");
 
 // pocs_pose_collides with the touched boxes as a mask (the flag: mask != 0, as the plain form's).
@@ -470,6 +475,12 @@ __global__ __launch_bounds__(POCS_BLOCK) void k_mc_init(pocs_mc_launch a) {
       mc_wave_box_hits(h != 0u, mask, wd.M, box.c);
     } else if constexpr ((MODE & MC_PARTS) != 0) {
       h = pocs_pose_collides_parts(x, y, t, pt.p, pt.F, wd.obs, wd.M, wd.tab) ? 1u : 0u;
+    } else if constexpr ((MODE & MC_RFOOT) != 0) {
+      static_assert((MODE & MC_RFOOT) == 0 || ((MODE & MC_ROUND) != 0 && (MODE & (MC_BOXES | MC_CLEAR | MC_PARTS | MC_REGIONS | MC_SEG)) == 0), "a round footprint: on top of MC_ROUND, with or without MC_NOISE");
+      if constexpr ((MODE & MC_NOISE) != 0)
+        h = pocs_round_pose_collides_noisy(x, y, wd.fp.hx, wd.obs, a.noise, wd.M, v.seed, (uint64_t)(a.first + i), 0u, wd.tab) ? 1u : 0u;      // waypoint 0
+      else
+        h = pocs_round_pose_collides(x, y, wd.fp.hx, wd.obs, wd.M) ? 1u : 0u;
     } else if constexpr ((MODE & MC_NOISE) != 0) {
       static_assert((MODE & MC_NOISE) == 0 || ((MODE & MC_ROUND) != 0 && (MODE & (MC_BOXES | MC_CLEAR | MC_PARTS | MC_REGIONS | MC_SEG)) == 0), "uncertain discs: on top of MC_ROUND alone");
       h = pocs_pose_collides_noisy(x, y, t, &wd.fp, wd.obs, a.noise, wd.M, v.seed, (uint64_t)(a.first + i), 0u, wd.tab) ? 1u : 0u;      // waypoint 0
@@ -609,6 +620,20 @@ __device__ __forceinline__ void mc_step_body(const pocs_mc_launch& a) {
         if (in != 0u && v.hits[i] != 0u) in = 0u;      // (in a region, but collided at an earlier waypoint)
       }
       mc_wave_region_hits(in, rg.G, a.reg_counts + ((size_t)blockIdx.y * (size_t)a.W + (size_t)a.step + 1) * POCS_MAX_REGIONS);
+    } else if constexpr ((MODE & MC_RFOOT) != 0) {
+      static_assert((MODE & MC_RFOOT) == 0 || ((MODE & MC_ROUND) != 0 && (MODE & (MC_BOXES | MC_CLEAR | MC_PARTS | MC_REGIONS | MC_SEG)) == 0), "a round footprint: on top of MC_ROUND, with or without MC_NOISE");
+      bool touch;
+      if constexpr ((MODE & MC_NOISE) != 0) {
+        const uint32_t vw = a.noise_persistent ? 0u : (uint32_t)(a.step + 1);      // control s produces waypoint s + 1
+        touch = pocs_round_pose_collides_noisy(nx, ny, wd.fp.hx, wd.obs, a.noise, wd.M, v.seed, (uint64_t)(a.first + i), vw, wd.tab);
+      } else {
+        touch = pocs_round_pose_collides(nx, ny, wd.fp.hx, wd.obs, wd.M);
+      }
+      if (touch) {
+        const uint32_t old = v.hits[i];
+        v.hits[i] = old + 1u;
+        first += old == 0u ? 1u : 0u;
+      }
     } else if constexpr ((MODE & MC_NOISE) != 0) {
       static_assert((MODE & MC_NOISE) == 0 || ((MODE & MC_ROUND) != 0 && (MODE & (MC_BOXES | MC_CLEAR | MC_PARTS | MC_REGIONS | MC_SEG)) == 0), "uncertain discs: on top of MC_ROUND alone");
       const uint32_t vw = a.noise_persistent ? 0u : (uint32_t)(a.step + 1);      // control s produces waypoint s + 1

@@ -106,7 +106,7 @@ void prepare_parts(const pocs_footprint* parts, int F, const double* boxes, int 
 // the exchange and a bound moments buffer) are the calls they are with L = 0; the step API never asks.
 bool clearance_applied(const pocs_ctx* c) {
   using namespace pocs_modes;
-  return c->clr_L > 0 && !parts_applied(c) && !seg_applied(c) && !discs_applied(c) && !in_mode(c, kTree | kLargeWorld | kObsCounts | kShard | kMoments);
+  return c->clr_L > 0 && !parts_applied(c) && !seg_applied(c) && !discs_applied(c) && !rfoot_applied(c) && !in_mode(c, kTree | kLargeWorld | kObsCounts | kShard | kMoments);
 }
 
 // Watched regions: the record the kernels read (pocs_regions_dev) -- region g prepared as upload_world prepares an obstacle, for
@@ -130,7 +130,7 @@ void prepare_regions(const pocs_footprint& fp, const double* boxes, const int* k
 // L > 0 are the calls they are with G = 0; the step API never asks.
 bool regions_applied(const pocs_ctx* c) {
   using namespace pocs_modes;
-  return c->reg_G > 0 && c->clr_L == 0 && !parts_applied(c) && !seg_applied(c) && !discs_applied(c) && !in_mode(c, kTree | kLargeWorld | kObsCounts | kShard | kMoments);
+  return c->reg_G > 0 && c->clr_L == 0 && !parts_applied(c) && !seg_applied(c) && !discs_applied(c) && !rfoot_applied(c) && !in_mode(c, kTree | kLargeWorld | kObsCounts | kShard | kMoments);
 }
 
 // Segment checks (J > 1) as the kernels read them (pocs_seg_dev): J and the fractions f_j = j / J.  (pocs_probe_device_segment
@@ -152,16 +152,21 @@ int upload_world(pocs_ctx* c) {                // tables + the collision world: 
     std::vector<double> noise(noise_applied(c) ? S * POCS_MAX_OBSTACLES * POCS_NOISE_STRIDE : 0, 0.0);      // uncertain discs: a row per record
     pocs_parts_dev parts;
     for (size_t s = 0; s < S; ++s) {
-      if (discs_applied(c)) {                        // round obstacles: record s is box step min(s, Sb - 1), then disc step min(s, Sd - 1)
+      if (discs_applied(c) || rfoot_applied(c)) {    // round obstacles: record s is box step min(s, Sb - 1), then disc step min(s, Sd - 1)
+        const bool rf = rfoot_applied(c);              // (a round footprint, with or without discs: the same records with rho as the bounding radius)
         const size_t sb = s < Sb ? s : Sb - 1, sd = s < (size_t)c->disc_S ? s : (size_t)c->disc_S - 1;
         const int D = c->disc_D;
         env[s].fp = c->fp;
         env[s].M = M + D;
-        for (int m = 0; m < M; ++m)
-          pocs_prepare_box_beside_discs(&c->boxes[(sb * (size_t)M + (size_t)m) * 5], &c->fp, &env[s].obs[(size_t)m * POCS_OBS_STRIDE]);
+        for (int m = 0; m < M; ++m) {
+          const double* const box = &c->boxes[(sb * (size_t)M + (size_t)m) * 5];
+          if (rf) pocs_prepare_obstacle_round(box, c->fp_rho, &env[s].obs[(size_t)m * POCS_OBS_STRIDE]);
+          else pocs_prepare_box_beside_discs(box, &c->fp, &env[s].obs[(size_t)m * POCS_OBS_STRIDE]);
+        }
         for (int d = 0; d < D; ++d) {
           double* const rec = &env[s].obs[(size_t)(M + d) * POCS_OBS_STRIDE];
-          pocs_prepare_disc(&c->discs[(sd * (size_t)D + (size_t)d) * 3], &c->fp, rec);
+          if (rf) pocs_prepare_disc_round(&c->discs[(sd * (size_t)D + (size_t)d) * 3], c->fp_rho, rec);
+          else pocs_prepare_disc(&c->discs[(sd * (size_t)D + (size_t)d) * 3], &c->fp, rec);
           if (noise_applied(c)) {                      // the record's row (zeros: a certain disc) and the growth of its fields 6 and 7
             double* const row = &noise[(s * POCS_MAX_OBSTACLES + (size_t)(M + d)) * POCS_NOISE_STRIDE];
             pocs_disc_noise_factor(&c->disc_cov[(sd * (size_t)D + (size_t)d) * 3], row);      // (the setter has checked every row)
@@ -549,6 +554,7 @@ void fill_gmm_world(const pocs_ctx* c, pocs_gmm_launch* a, int w) {
   a->M = env_records(c);                             // (the boxes, and behind them the discs in force)
   a->round = discs_applied(c) ? 1 : 0;               // (nonzero: the sampling launch is the _round form)
   a->noise = noise_applied(c) ? noise_at(c, w) : nullptr;      // (non-null: the _noise form on top of it)
+  a->rfoot = rfoot_applied(c) ? 1 : 0;               // (nonzero: the _rfoot family, with or without discs and covariances)
   if (!parts_applied(c)) {                           // (a compound footprint's values live in device memory: the launch carries none)
     a->fp = c->fp;
     a->fp_rr = sqrt(c->fp.hx * c->fp.hx + c->fp.hy * c->fp.hy); a->fp_phi = atan2(c->fp.hy, c->fp.hx);
@@ -621,7 +627,7 @@ int enqueue_advance(Issuer is, int w) {
 // heads, so a call of one run takes the ticket form there: the same bits.)
 // (Under clearance levels and watched regions too: the counting forms exist as the ticket form only.)
 // (And under a compound footprint: the parts form exists as the ticket form only.  And under segment checks and discs: the same.)
-bool lone_call(const pocs_ctx* c) { return c->opt_lone && !large_world(c) && !clearance_applied(c) && !regions_applied(c) && !parts_applied(c) && !seg_applied(c) && !discs_applied(c) && c->batch == 1 && !c->tree.n && !c->ext_moments && !(c->xchg_connected && c->shard_first >= 0) && !risk_active(c); }
+bool lone_call(const pocs_ctx* c) { return c->opt_lone && !large_world(c) && !clearance_applied(c) && !regions_applied(c) && !parts_applied(c) && !seg_applied(c) && !discs_applied(c) && !rfoot_applied(c) && c->batch == 1 && !c->tree.n && !c->ext_moments && !(c->xchg_connected && c->shard_first >= 0) && !risk_active(c); }
 void set_risk(pocs_ctx* c, pocs_gmm_launch* a) {      // under a risk bound the launch is k_gmm_step_risk (whole calls of plans or on a tree only)
   a->risk = 1;
   a->stop = a->sync + c->sync.stop;
@@ -1020,7 +1026,7 @@ bool mc_counts_active(const pocs_ctx* c) { return c->opt_mc_wp || c->opt_obs_cou
 // And a call under a compound footprint: the parts live in the per-step kernels too (MC_PARTS).
 // And a call that counts watched regions: they live in the per-step kernels as well (MC_REGIONS).
 // And a call under segment checks: the sub-poses live in the per-step kernels (MC_SEG).
-bool mc_fused_form(const pocs_ctx* c) { return c->opt_fused && !mc_stop_active(c) && !clearance_applied(c) && !parts_applied(c) && !regions_applied(c) && !seg_applied(c) && !discs_applied(c); }      // (and under discs: MC_ROUND lives in the per-step kernels)
+bool mc_fused_form(const pocs_ctx* c) { return c->opt_fused && !mc_stop_active(c) && !clearance_applied(c) && !parts_applied(c) && !regions_applied(c) && !seg_applied(c) && !discs_applied(c) && !rfoot_applied(c); }      // (and under discs and a round footprint: MC_ROUND and MC_RFOOT live in the per-step kernels)
 // d_total, u64 words: [R] collided particles per run | counts active: [R][W] first collisions | [R] u32 stop words
 size_t mc_total_words(const pocs_ctx* c) {
   const size_t R = (size_t)c->batch, W = (size_t)c->W;
@@ -1081,6 +1087,7 @@ int enqueue_mc_all(Issuer is, long long first, long long count, bool prof) {
     if (int r = is.launch(pocs_launch_zero_counts, 0, a.seg_counts, seg_count_words(c))) return r;
   }
   if (discs_applied(c)) a.round = 1;                 // (round obstacles: the MC_ROUND forms of k_mc_init and the per-step kernel)
+  if (rfoot_applied(c)) { a.round = 1; a.rfoot = 1; }      // (a round footprint: MC_RFOOT on top, with or without discs)
   if (noise_applied(c)) { a.noise = noise_at(c, 0); a.noise_persistent = c->disc_noise_persistent ? 1 : 0; }      // (uncertain discs: MC_NOISE on top)
   if (c->plans.n) {
     a.run_plan = (const double*)c->d_runplan.p;      // every run its own start mean and steps

@@ -216,6 +216,11 @@ struct pocs_gmm_launch {
   // record (POCS_NOISE_STRIDE doubles each, zeros for a box), for the launch's waypoint -- aimed with `env`.  The waypoint word of the
   // deviations is the launch's waypoint
   const double* noise;
+  // a round footprint (pocs_set_footprint_disc; behind everything else again): nonzero = the launch is the _rfoot form (ticket form,
+  // with or without the risk bound, `noise` non-null: its noise twin; never LONE, TREE, OC, WORLD, CL, parts, regions or segment
+  // checks), whatever `round` says -- a world without discs takes the same family.  fp is {0, 0, rho, rho}: the radius is fp.hx
+  int rfoot;
+  int rfoot_pad;
 };
 #define POCS_MAX_WORLD_RECORDS 4096   // = POCS_MAX_WORLD_BOXES (include/pocs.h; pocs_ctx.hpp checks)
 #define POCS_CULL_BLOCK 256           // k_world_cull
@@ -306,6 +311,10 @@ struct pocs_mc_launch {               // blockIdx.y = run of the batch, like poc
   const double* noise;
   int noise_persistent;
   int noise_pad;
+  // a round footprint (pocs_set_footprint_disc; behind everything else again): nonzero = the MC_RFOOT forms on top of the MC_ROUND
+  // forms (`round` is nonzero too, with or without discs; `noise` non-null: on top of MC_NOISE as well).  The radius is env->fp.hx
+  int rfoot;
+  int rfoot_pad;
 };
 
 
@@ -354,6 +363,13 @@ hipError_t pocs_launch_probe_discs(const pocs_env_dev* env, const pocs_tables* t
 hipError_t pocs_launch_probe_disc_noise(const pocs_env_dev* env, const double* rows, const pocs_tables* tables, unsigned long long seed,
                                         unsigned v, unsigned long long first, int n, const double* x, const double* y, const double* th,
                                         double* centres, unsigned* flags, hipStream_t s);
+// one block; poses n x (x, y, th) by component, pose i has index first + i (first even); env: the composed records (boxes, then discs)
+// prepared for the round footprint of radius env->fp.hx; rows: null, or the records' noise rows.  out[i]: bit 0 = pose i touches some
+// box, bit 1 = some disc, displaced where its row says so (the single-pose form on the full table), bit 8 should the pair form ever
+// disagree with it
+hipError_t pocs_launch_probe_footprint_disc(const pocs_env_dev* env, const double* rows, const pocs_tables* tables, unsigned long long seed,
+                                            unsigned v, unsigned long long first, int n, const double* x, const double* y, int* out,
+                                            hipStream_t s);
 // one thread per case; K / seeds / wp / n_total: n; w / alive / out: n rows of POCS_MAX_GAUSSIANS (case i uses the first K[i]): raw weights
 // and alive flags in, cumulative component counts out (pocs_normalise_weights + pocs_component_counts, as advance_finish and
 // speculate_counts call them)

@@ -54,6 +54,26 @@ hipError_t with_K(const int K, F f) {
 hipError_t pocs_launch_gmm_step(int K, const pocs_gmm_launch& a, hipStream_t s) {
   return with_K(K, [&](auto k) {
     constexpr int KK = decltype(k)::value, TB = POCS_GMM_BLOCK_OF(KK);
+    if (a.rfoot) {                                     // a round footprint: a family of its own, with and without discs and covariances
+      if (a.lone || a.obs_counts || a.world || a.tree_parent || a.exchange_in_tail || a.clr || a.parts || a.regions || a.seg ||
+          a.M > POCS_MAX_OBSTACLES || (a.risk && (!a.stop || !a.surv)) || !(a.fp.dx == 0.0 && a.fp.dy == 0.0 && a.fp.hx == a.fp.hy && a.fp.hx >= 0.0))
+        return hipErrorInvalidValue;
+      if (a.noise) {
+        if (a.risk) {
+          if (a.store) hipLaunchKernelGGL((k_gmm_step_risk_rfoot_noise<KK, true, TB>), dim3(a.blocks), dim3(TB), 0, s, a);
+          else         hipLaunchKernelGGL((k_gmm_step_risk_rfoot_noise<KK, false, TB>), dim3(a.blocks), dim3(TB), 0, s, a);
+        } else {
+          if (a.store) hipLaunchKernelGGL((k_gmm_step_rfoot_noise<KK, true, TB>), dim3(a.blocks), dim3(TB), 0, s, a);
+          else         hipLaunchKernelGGL((k_gmm_step_rfoot_noise<KK, false, TB>), dim3(a.blocks), dim3(TB), 0, s, a);
+        }
+      } else if (a.risk) {
+        if (a.store) hipLaunchKernelGGL((k_gmm_step_risk_rfoot<KK, true, TB>), dim3(a.blocks), dim3(TB), 0, s, a);
+        else         hipLaunchKernelGGL((k_gmm_step_risk_rfoot<KK, false, TB>), dim3(a.blocks), dim3(TB), 0, s, a);
+      } else {
+        if (a.store) hipLaunchKernelGGL((k_gmm_step_rfoot<KK, true, TB>), dim3(a.blocks), dim3(TB), 0, s, a);
+        else         hipLaunchKernelGGL((k_gmm_step_rfoot<KK, false, TB>), dim3(a.blocks), dim3(TB), 0, s, a);
+      }
+    } else
     if (a.noise) {                                     // uncertain discs: the _noise forms on top of the _round forms
       if (!a.round || a.lone || a.obs_counts || a.world || a.tree_parent || a.exchange_in_tail || a.clr || a.parts || a.regions || a.seg ||
           a.M > POCS_MAX_OBSTACLES || (a.risk && (!a.stop || !a.surv)))
@@ -235,6 +255,16 @@ hipError_t pocs_launch_mc_tree_step(int nblk, const pocs_mc_launch& a, hipStream
 
 hipError_t pocs_launch_mc_init(int nblk, const pocs_mc_launch& a, hipStream_t s) {
   if ((a.wp_mode != 0 && !a.wp_counts) || (a.obs_counts && !a.wp_mode)) return hipErrorInvalidValue;
+  if (a.rfoot) {                                      // a round footprint: MC_RFOOT on top of MC_ROUND, with or without MC_NOISE
+    if (!a.round || a.world || a.obs_counts || a.clr || a.parts || a.regions || a.seg) return hipErrorInvalidValue;
+    if (a.noise) {
+      if (a.wp_mode) hipLaunchKernelGGL(k_mc_init<MC_COUNTS | MC_ROUND | MC_NOISE | MC_RFOOT>, dim3(nblk, a.nruns), dim3(POCS_BLOCK), 0, s, a);
+      else           hipLaunchKernelGGL(k_mc_init<MC_PLAIN | MC_ROUND | MC_NOISE | MC_RFOOT>, dim3(nblk, a.nruns), dim3(POCS_BLOCK), 0, s, a);
+    } else {
+      if (a.wp_mode) hipLaunchKernelGGL(k_mc_init<MC_COUNTS | MC_ROUND | MC_RFOOT>, dim3(nblk, a.nruns), dim3(POCS_BLOCK), 0, s, a);
+      else           hipLaunchKernelGGL(k_mc_init<MC_PLAIN | MC_ROUND | MC_RFOOT>, dim3(nblk, a.nruns), dim3(POCS_BLOCK), 0, s, a);
+    }
+  } else
   if (a.noise) {                                      // uncertain discs: the MC_NOISE forms on top of the MC_ROUND forms
     if (!a.round || a.world || a.obs_counts || a.clr || a.parts || a.regions || a.seg) return hipErrorInvalidValue;
     if (a.wp_mode) hipLaunchKernelGGL(k_mc_init<MC_COUNTS | MC_ROUND | MC_NOISE>, dim3(nblk, a.nruns), dim3(POCS_BLOCK), 0, s, a);
@@ -273,6 +303,33 @@ hipError_t pocs_launch_mc_init(int nblk, const pocs_mc_launch& a, hipStream_t s)
 hipError_t pocs_launch_mc_step(int nblk, const pocs_mc_launch& a, hipStream_t s) {
   const dim3 grid(nblk, a.nruns), block(POCS_BLOCK);
   if ((a.wp_mode != 0 && !a.wp_counts) || (a.obs_counts && !a.wp_mode)) return hipErrorInvalidValue;
+  if (a.rfoot) {                                      // a round footprint: the MC_RFOOT forms of the three modes, with or without MC_NOISE
+    if (!a.round || a.world || a.obs_counts || a.clr || a.parts || a.regions || a.seg || a.step < 0 || a.step + 1 >= a.W ||
+        (a.wp_mode == 2 && (!a.wp_stop || a.wp_n < 1)))
+      return hipErrorInvalidValue;
+    constexpr int RF = MC_ROUND | MC_RFOOT, RFN = MC_ROUND | MC_NOISE | MC_RFOOT;
+    if (a.noise) {
+      if (a.wp_mode == 2) {
+        if (a.nontemporal) hipLaunchKernelGGL((k_mc_step_counts<true, MC_STOP | RFN>), grid, block, 0, s, a);
+        else               hipLaunchKernelGGL((k_mc_step_counts<false, MC_STOP | RFN>), grid, block, 0, s, a);
+      } else if (a.wp_mode == 1) {
+        if (a.nontemporal) hipLaunchKernelGGL((k_mc_step_counts<true, MC_COUNTS | RFN>), grid, block, 0, s, a);
+        else               hipLaunchKernelGGL((k_mc_step_counts<false, MC_COUNTS | RFN>), grid, block, 0, s, a);
+      } else {
+        if (a.nontemporal) hipLaunchKernelGGL((k_mc_step_counts<true, MC_PLAIN | RFN>), grid, block, 0, s, a);
+        else               hipLaunchKernelGGL((k_mc_step_counts<false, MC_PLAIN | RFN>), grid, block, 0, s, a);
+      }
+    } else if (a.wp_mode == 2) {
+      if (a.nontemporal) hipLaunchKernelGGL((k_mc_step_counts<true, MC_STOP | RF>), grid, block, 0, s, a);
+      else               hipLaunchKernelGGL((k_mc_step_counts<false, MC_STOP | RF>), grid, block, 0, s, a);
+    } else if (a.wp_mode == 1) {
+      if (a.nontemporal) hipLaunchKernelGGL((k_mc_step_counts<true, MC_COUNTS | RF>), grid, block, 0, s, a);
+      else               hipLaunchKernelGGL((k_mc_step_counts<false, MC_COUNTS | RF>), grid, block, 0, s, a);
+    } else {
+      if (a.nontemporal) hipLaunchKernelGGL((k_mc_step_counts<true, MC_PLAIN | RF>), grid, block, 0, s, a);
+      else               hipLaunchKernelGGL((k_mc_step_counts<false, MC_PLAIN | RF>), grid, block, 0, s, a);
+    }
+  } else
   if (a.noise) {                                      // uncertain discs: the MC_NOISE forms of the three modes
     if (!a.round || a.world || a.obs_counts || a.clr || a.parts || a.regions || a.seg || a.step < 0 || a.step + 1 >= a.W ||
         (a.wp_mode == 2 && (!a.wp_stop || a.wp_n < 1)))
@@ -918,6 +975,75 @@ hipError_t pocs_launch_probe_disc_noise(const pocs_env_dev* env, const double* r
                                         double* centres, unsigned* flags, hipStream_t s) {
   if (!env || !rows || !tables || n < 1 || (first & 1ull) || !x || !y || !th || !centres || !flags) return hipErrorInvalidValue;
   hipLaunchKernelGGL(k_probe_disc_noise, dim3(1), dim3(POCS_BLOCK), 0, s, env, rows, tables, seed, v, first, n, x, y, th, centres, flags);
+  return hipGetLastError();
+}
+// The round footprint's test on poses, a radius, boxes, discs and factor rows the caller picks (pocs_probe_device_footprint_disc: a test
+// hook beside k_probe_discs): ONE block stages the tables, the composed records and -- where given -- their rows and asks, per pose of
+// index first + i, the functions the kernels ask.  Bit 0: the pose touches some box, bit 1: some disc, displaced where its row says so
+// -- pocs_round_pose_kinds, the single-pose form on the full table, and the MC kernels' pocs_round_pose_collides[_noisy] must say
+// (bits != 0).  Then pocs_pair_round_masks as the _rfoot kernels call it on poses 2 p, 2 p + 1 of pair (first >> 1) + p (an odd last
+// pose beside its own twin's index, which is then not read), its disc masks handed out: bit 8 should the two forms ever disagree.
+__global__ __launch_bounds__(POCS_BLOCK) void k_probe_footprint_disc(const pocs_env_dev* __restrict__ env, const double* __restrict__ rows,
+                                                                     const pocs_tables* __restrict__ tables, unsigned long long seed, unsigned v,
+                                                                     unsigned long long first, int n, const double* __restrict__ x,
+                                                                     const double* __restrict__ y, int* __restrict__ out) {
+  __shared__ pocs_tables s_tab;
+  __shared__ __attribute__((aligned(16))) double s_obs[POCS_MAX_OBSTACLES * POCS_OBS_STRIDE];
+  __shared__ __attribute__((aligned(16))) double s_rows[POCS_MAX_OBSTACLES * POCS_NOISE_STRIDE];
+  stage_tables(tables, &s_tab);
+  for (int j = threadIdx.x; j < POCS_MAX_OBSTACLES * POCS_OBS_STRIDE; j += POCS_BLOCK) s_obs[j] = env->obs[j];
+  for (int j = threadIdx.x; j < POCS_MAX_OBSTACLES * POCS_NOISE_STRIDE; j += POCS_BLOCK) s_rows[j] = rows ? rows[j] : 0.0;
+  __syncthreads();
+  const int M = env->M < POCS_MAX_OBSTACLES ? env->M : POCS_MAX_OBSTACLES;
+  const double rho = env->fp.hx;
+  const bool noisy = rows != nullptr;                                  // (the same in every thread)
+  POCS_VCONST(vc_);
+  const int npairs = (n + 1) / 2;
+  // (every lane of a wave makes every trip: the pair form ballots)
+  for (int p0 = (int)threadIdx.x - (int)(threadIdx.x & 63); p0 < npairs; p0 += POCS_BLOCK) {
+    const int p = p0 + (int)(threadIdx.x & 63);
+    const bool live = p < npairs;
+    const int i0 = live ? 2 * p : 0;
+    const bool two = live && i0 + 1 < n;
+    const int i1 = two ? i0 + 1 : i0;
+    const double xs[2] = {x[i0], x[i1]}, ys[2] = {y[i0], y[i1]};
+    const unsigned long long idx[2] = {first + (unsigned long long)i0, first + (unsigned long long)i0 + 1ull};
+    unsigned single[2];
+    bool bad[2];
+    unsigned long long all[2], disc[2];
+    if (noisy) {
+#pragma unroll
+      for (int h = 0; h < 2; ++h) {
+        single[h] = pocs_round_pose_kinds(xs[h], ys[h], rho, s_obs, M, s_rows, seed, idx[h], v, &s_tab);
+        bad[h] = pocs_round_pose_collides_noisy(xs[h], ys[h], rho, s_obs, s_rows, M, seed, idx[h], v, &s_tab) != (single[h] != 0u);
+      }
+      const pocs_noise_pair np = {s_rows, seed, idx[0] >> 1, v};
+      pocs_pair_round_masks<pocs_noise_pair>(xs, ys, rho, s_obs, M, &s_tab, &vc_, all, disc, np);
+    } else {
+#pragma unroll
+      for (int h = 0; h < 2; ++h) {
+        single[h] = pocs_round_pose_kinds(xs[h], ys[h], rho, s_obs, M);
+        bad[h] = pocs_round_pose_collides(xs[h], ys[h], rho, s_obs, M) != (single[h] != 0u);
+      }
+      pocs_pair_round_masks(xs, ys, rho, s_obs, M, &s_tab, &vc_, all, disc);
+    }
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+      const bool any = __builtin_amdgcn_inverse_ballot_w64(all[h]), round = __builtin_amdgcn_inverse_ballot_w64(disc[h]);
+      // (a pose that touches a box AND a disc: the pair form says "any" and "disc"; the box bit is not handed out apart)
+      if (any != (single[h] != 0u) || round != ((single[h] & 2u) != 0u)) bad[h] = true;
+    }
+    if (live) {
+      out[i0] = (int)(single[0] | (bad[0] ? 256u : 0u));
+      if (two) out[i1] = (int)(single[1] | (bad[1] ? 256u : 0u));
+    }
+  }
+}
+hipError_t pocs_launch_probe_footprint_disc(const pocs_env_dev* env, const double* rows, const pocs_tables* tables, unsigned long long seed,
+                                            unsigned v, unsigned long long first, int n, const double* x, const double* y, int* out,
+                                            hipStream_t s) {
+  if (!env || !tables || n < 1 || (first & 1ull) || !x || !y || !out) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(k_probe_footprint_disc, dim3(1), dim3(POCS_BLOCK), 0, s, env, rows, tables, seed, v, first, n, x, y, out);
   return hipGetLastError();
 }
 hipError_t pocs_launch_fill(void* dst, long long bytes, hipStream_t s) {

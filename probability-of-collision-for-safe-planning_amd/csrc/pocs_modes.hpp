@@ -93,6 +93,12 @@ static const char* const kSegClause = "segment checks are served by whole calls 
 constexpr unsigned kDiscExcluded = kTree | kShard | kXchgCreated | kXchgConnected | kMoments | kLargeWorld | kObsCounts | kSequence;
 static const char* const kDiscClause = "discs are served by whole calls on one GPU over worlds of at most 64 records, with a single footprint box, without per-box counts and segment checks";
 
+// A round footprint (pocs_set_footprint_disc) is no mode of the table either, for the same reason: it changes results, so what it is
+// not built for is refused in both directions -- and segment checks, which are no bit of a mode word, are asked about beside this mask
+// (rfoot_refuse, pocs_ctx.hpp; the two setters).  A compound footprint needs no ask: a footprint setter replaces the footprint.
+constexpr unsigned kRoundFpExcluded = kTree | kShard | kXchgCreated | kXchgConnected | kMoments | kLargeWorld | kObsCounts | kSequence | kProbe;
+static const char* const kRoundFpClause = "a round footprint is served by whole calls on one GPU over worlds of at most 64 records, without per-box counts and segment checks";
+
 // May a context whose active modes are `active` enter `enter`?  `among`: the modes asked about now -- a setter whose argument
 // checks stand between two of its combination checks asks in stages, so that a call with two faults keeps its code.
 struct Refusal { int code; Mode by; const char* clause; };
