@@ -204,6 +204,16 @@ def _arr(a):
     return np.ascontiguousarray(a, dtype=np.float64)
 
 
+def _rows(a, width):
+    """Records for a probe (None: none of them) -> a contiguous float64 array of rows `width` wide."""
+    return np.ascontiguousarray(_arr(a if a is not None else []).reshape(-1, width))
+
+
+def _dp_or_null(a):
+    """The array's data as a double*, NULL for an empty array."""
+    return a.ctypes.data_as(_dp) if a.size else None
+
+
 def pack_plans(plans):
     """Candidate plans ({"traj": W x 3, "odom": (W-1) x 3} each, as set_plan takes one) -> (W, trajs, odoms) as
     pocs_set_plans takes them: W int32[P]; trajs = plan p's trajectory by component (x_0..x_{W-1}, y.., theta..),
@@ -355,9 +365,7 @@ class Context:
         flags uint32[n]): the displaced centres, bit d = pose i touches displaced disc d, bit 31 = the kernels' two forms disagree
         (never)."""
         fp = _arr(footprint).ravel()
-        d = np.ascontiguousarray(_arr(discs).reshape(-1, 3))
-        v = np.ascontiguousarray(_arr(cov).reshape(-1, 3))
-        xyt = np.ascontiguousarray(_arr(poses).reshape(-1, 3))
+        d, v, xyt = _rows(discs, 3), _rows(cov, 3), _rows(poses, 3)
         assert fp.size == 4 and v.shape == d.shape
         centres = np.full((xyt.shape[0], d.shape[0], 2), np.nan)
         flags = np.full(xyt.shape[0], 0xFFFFFFFF, dtype=np.uint32)
@@ -383,15 +391,12 @@ class Context:
         touches on the device, for the caller's own boxes (M x 5), discs (D x 3) and -- where given -- covariances (D x 3): pose i has
         index first + i (first even).  int32[n]: bit 0 = touches some box, bit 1 = touches some disc (displaced where cov says so),
         bit 8 = the kernels' two forms disagree (never)."""
-        b = np.ascontiguousarray(_arr(boxes if boxes is not None else []).reshape(-1, 5))
-        d = np.ascontiguousarray(_arr(discs if discs is not None else []).reshape(-1, 3))
-        v = None if cov is None else np.ascontiguousarray(_arr(cov).reshape(-1, 3))
+        b, d, xyt = _rows(boxes, 5), _rows(discs, 3), _rows(poses, 3)
+        v = None if cov is None else _rows(cov, 3)
         assert v is None or v.shape == d.shape
-        xyt = np.ascontiguousarray(_arr(poses).reshape(-1, 3))
         out = np.full(xyt.shape[0], -1, dtype=np.int32)
-        self._chk(self.lib.pocs_probe_device_footprint_disc(self.h, float(radius), b.ctypes.data_as(_dp) if b.size else None, b.shape[0],
-                                                            d.ctypes.data_as(_dp) if d.size else None, d.shape[0],
-                                                            v.ctypes.data_as(_dp) if v is not None and v.size else None,
+        self._chk(self.lib.pocs_probe_device_footprint_disc(self.h, float(radius), _dp_or_null(b), b.shape[0], _dp_or_null(d), d.shape[0],
+                                                            None if v is None else _dp_or_null(v),
                                                             C.c_uint64(int(seed)), C.c_uint32(int(waypoint_word)), C.c_ulonglong(int(first)),
                                                             xyt.shape[0], xyt.ctypes.data_as(_dp), out.ctypes.data_as(C.POINTER(C.c_int))))
         return out
@@ -401,14 +406,11 @@ class Context:
         boxes (M x 5) and discs (D x 3).  int32[n]: bit 0 = touches some box, bit 1 = touches some disc, bit 8 = the kernels' two forms
         disagree (never)."""
         fp = _arr(footprint).ravel()
-        b = _arr(boxes if boxes is not None else []).reshape(-1, 5)
-        d = _arr(discs if discs is not None else []).reshape(-1, 3)
-        xyt = _arr(poses).reshape(-1, 3)
+        b, d, xyt = _rows(boxes, 5), _rows(discs, 3), _rows(poses, 3)
         assert fp.size == 4
         out = np.full(xyt.shape[0], -1, dtype=np.int32)
-        self._chk(self.lib.pocs_probe_device_discs(self.h, fp.ctypes.data_as(_dp), b.ctypes.data_as(_dp) if b.size else None, b.shape[0],
-                                                   d.ctypes.data_as(_dp) if d.size else None, d.shape[0], xyt.shape[0],
-                                                   xyt.ctypes.data_as(_dp), out.ctypes.data_as(C.POINTER(C.c_int))))
+        self._chk(self.lib.pocs_probe_device_discs(self.h, fp.ctypes.data_as(_dp), _dp_or_null(b), b.shape[0], _dp_or_null(d), d.shape[0],
+                                                   xyt.shape[0], xyt.ctypes.data_as(_dp), out.ctypes.data_as(C.POINTER(C.c_int))))
         return out
 
     def set_world(self, boxes):
@@ -657,13 +659,11 @@ class Context:
         the caller's own: int32[n], -1 the footprint itself touches, else the smallest level whose grown footprint does, len(d) for none."""
         fp = _arr(footprint).ravel()
         d = _arr(d).ravel()
-        b = _arr(boxes).reshape(-1, 5)
-        xyt = _arr(poses).reshape(-1, 3)
+        b, xyt = _rows(boxes, 5), _rows(poses, 3)
         assert fp.size == 4
         out = np.full(xyt.shape[0], -99, dtype=np.int32)
-        self._chk(self.lib.pocs_probe_device_clearance(self.h, fp.ctypes.data_as(_dp), d.ctypes.data_as(_dp) if d.size else None, d.size,
-                                                       b.ctypes.data_as(_dp) if b.size else None, b.shape[0], xyt.shape[0],
-                                                       xyt.ctypes.data_as(_dp), out.ctypes.data_as(C.POINTER(C.c_int))))
+        self._chk(self.lib.pocs_probe_device_clearance(self.h, fp.ctypes.data_as(_dp), _dp_or_null(d), d.size, _dp_or_null(b), b.shape[0],
+                                                       xyt.shape[0], xyt.ctypes.data_as(_dp), out.ctypes.data_as(C.POINTER(C.c_int))))
         return out
 
     def set_footprint_parts(self, parts):
@@ -681,12 +681,9 @@ class Context:
     def probe_footprint_parts(self, parts, boxes, poses):
         """Test hook: per pose (n x 3) the parts (F x 4) of the caller's own compound footprint that touch the caller's own boxes
         (M x 5) on the device: int32[n], bit f = part f touches, bit 8 = the kernels' two forms disagree (never)."""
-        q = _arr(parts).reshape(-1, 4)
-        b = _arr(boxes).reshape(-1, 5)
-        xyt = _arr(poses).reshape(-1, 3)
+        q, b, xyt = _rows(parts, 4), _rows(boxes, 5), _rows(poses, 3)
         out = np.full(xyt.shape[0], -1, dtype=np.int32)
-        self._chk(self.lib.pocs_probe_device_footprint_parts(self.h, q.ctypes.data_as(_dp) if q.size else None, q.shape[0],
-                                                             b.ctypes.data_as(_dp) if b.size else None, b.shape[0], xyt.shape[0],
+        self._chk(self.lib.pocs_probe_device_footprint_parts(self.h, _dp_or_null(q), q.shape[0], _dp_or_null(b), b.shape[0], xyt.shape[0],
                                                              xyt.ctypes.data_as(_dp), out.ctypes.data_as(C.POINTER(C.c_int))))
         return out
 
@@ -728,13 +725,12 @@ class Context:
         """Test hook: per pose (n x 3) the regions (G x 5, kinds[G]) of the caller's own that the device finds it in, for a footprint
         (dx, dy, hx, hy): int32[n], bit g = in region g, bit 8 + g = the kernels' two forms disagree on region g (never)."""
         fp = _arr(footprint).ravel()
-        b = _arr(boxes).reshape(-1, 5)
+        b, xyt = _rows(boxes, 5), _rows(poses, 3)
         k = np.ascontiguousarray(kinds, dtype=np.int32).ravel()
-        xyt = _arr(poses).reshape(-1, 3)
         assert fp.size == 4 and k.size == b.shape[0]
         ip = C.POINTER(C.c_int)
         out = np.full(xyt.shape[0], -1, dtype=np.int32)
-        self._chk(self.lib.pocs_probe_device_regions(self.h, fp.ctypes.data_as(_dp), b.ctypes.data_as(_dp) if b.size else None,
+        self._chk(self.lib.pocs_probe_device_regions(self.h, fp.ctypes.data_as(_dp), _dp_or_null(b),
                                                      k.ctypes.data_as(ip) if k.size else None, b.shape[0], xyt.shape[0],
                                                      xyt.ctypes.data_as(_dp), out.ctypes.data_as(ip)))
         return out
@@ -762,12 +758,11 @@ class Context:
         sample.  int32[n]: bit j (1 <= j < J) = sub-pose j touches, bit J = the end pose touches, bit 16 = the kernels' two forms
         disagree (never)."""
         fp = _arr(footprint).ravel()
-        b = _arr(boxes).reshape(-1, 5)
+        b, xyt = _rows(boxes, 5), _rows(poses, 3)
         u3 = _arr(u).ravel()
-        xyt = _arr(poses).reshape(-1, 3)
         assert fp.size == 4 and u3.size == 3
         out = np.full(xyt.shape[0], -1, dtype=np.int32)
-        self._chk(self.lib.pocs_probe_device_segment(self.h, fp.ctypes.data_as(_dp), b.ctypes.data_as(_dp) if b.size else None, b.shape[0],
+        self._chk(self.lib.pocs_probe_device_segment(self.h, fp.ctypes.data_as(_dp), _dp_or_null(b), b.shape[0],
                                                      u3.ctypes.data_as(_dp), int(J), int(backward), xyt.shape[0],
                                                      xyt.ctypes.data_as(_dp), out.ctypes.data_as(C.POINTER(C.c_int))))
         return out

@@ -4,7 +4,8 @@
 //   pocs_stage.hip   host chain, staging layout, run / tree images, look-ahead cache, upload of a call's runs
 //   pocs_host.hip    the run paths: GMM and MC whole calls, their tree forms, the step and exchange API
 //   pocs_api.hip     context life cycle, setters, getters, run-ahead front, text dispatcher
-//   pocs_audit.hip   read-backs of device state for tests and audits, bandwidth and device-math probes, timing getters
+//   pocs_audit.hip   read-backs of device state for tests and audits, bandwidth measurements, timing getters
+//   pocs_probe.hip   the test hooks pocs_probe_device_*
 //   pocs_modes.hpp   the modes a context can be in and the table of the pairs that exclude each other (no HIP type)
 //
 // Host only: none of these units holds a kernel (pocs_kernels.hip does, with its parts pocs_dev_*.hpp).

@@ -1,6 +1,6 @@
 // pocs_kernels.h -- launch interface between the host runtime (pocs_host.hip, pocs_ctx.hpp) and the gfx950
 // kernels (pocs_kernels.hip: the pocs_launch_* functions; the kernels themselves in its parts pocs_dev_prims.hpp,
-// pocs_dev_advance.hpp, pocs_dev_gmm.hpp, pocs_dev_mc.hpp).  Internal; the public boundary is include/pocs.h.
+// pocs_dev_advance.hpp, pocs_dev_gmm.hpp, pocs_dev_mc.hpp, pocs_dev_probe.hpp).  Internal; the public boundary is include/pocs.h.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
