@@ -657,6 +657,43 @@ int pocs_get_discs(const pocs_ctx* ctx, int* D, int* S);
 int pocs_set_disc_covariances(pocs_ctx* ctx, const double* cov /* S x D x {sxx, sxy, syy} */, int D, int S, int persistent);
 int pocs_get_disc_covariances(const pocs_ctx* ctx, double* out, int cap, int* persistent);   /* returns S*D*3, 0 when none */
 
+/* ---- prediction hypotheses: weighted alternative tracks per round obstacle, for both estimators (ours) ----------
+ * A trajectory predictor hands over a few alternatives with probabilities: "crosses in front of the robot, 0.3; waits at the kerb,
+ * 0.7".  Every disc in force may be one ALTERNATIVE of a group; the disc schedule gives each alternative its track, the covariances
+ * its spread, and this table its weight.  Hypotheses are per disc, not per disc step: an alternative is a whole track.
+ *   groups      group[d] = -1: disc d is always there, and its weight is not read.  group[d] = g, 0 <= g < D: disc d is one alternative
+ *               of group g.  The alternatives of a group exclude each other: for one pose at most one of them exists.  A group whose
+ *               weights sum to less than 1 leaves room for "none of them"; a group of one alternative with weight p is an obstacle
+ *               that exists with probability p (a door that may be open, a detection of low confidence).
+ *   thresholds  exact integers, formed on the host in this order: n_d = floor(weight[d] * 4294967296.0) (the product is exact); within
+ *               a group, in ascending d, lo_d = the sum of n_e over the earlier discs e < d of the same group, hi_d = lo_d + n_d.  The
+ *               getter returns lo and hi: the probability of an alternative is exactly n_d / 2^32.  (group -1: lo = 0, hi = 2^32.)
+ *   draw        a pose is one possible world.  For pose index i (the global sample index of a GMM call, the global particle index
+ *               first + i of an MC call), the run's effective seed, group g and waypoint word v:
+ *               words = Philox4x32-7(ctr = (lo32(i >> 1), hi32(i >> 1), v, 6 << 16 | g), key = seed) -- stream 6 --, h = i & 1,
+ *               u = words[2 h].  Disc d exists for the pose iff lo_d <= u < hi_d: an integer compare, nothing is floating point.
+ *   word        GMM calls: v = w, a fresh choice per waypoint.  The GMM estimator carries only the robot's mixture across waypoints,
+ *               so it treats the choices as INDEPENDENT IN TIME, the approximation the covariances make; against a persistent truth it
+ *               errs to the high side in the same way.  MC calls: v = 0 always -- a particle's world keeps its alternative for the
+ *               whole roll-out, which is what a hypothesis means; there is no per-waypoint setting.  Plans run on their own clocks.
+ *   flag        a gated disc record touches a pose iff the disc exists for the pose AND the record's test as it is without this says
+ *               so (the broad phase on the nominal centre with the grown fields, the narrow phase, on the displaced centre for an
+ *               uncertain disc).  Everything both estimators report is formed from the flag.  The deviation draw (stream 5) and the
+ *               existence draw (stream 6) are independent.
+ * pocs_set_disc_hypotheses: POCS_E_ARG, what was in force kept: D other than the D of the discs in force, a group outside [-1, D), a
+ * weight that is not finite or outside (0, 1], n_d = 0, a group whose last hi exceeds 2^32, a null pointer with D > 0.  POCS_E_STATE
+ * without discs; POCS_E_ORDER inside a begin/end sequence.  A null pointer with D = 0 clears, and so does a table whose groups are all
+ * -1: every call is then, launch for launch, the call it is without this.  pocs_set_discs with the same D keeps the hypotheses,
+ * whatever S is; another D, or clearing the discs, drops them.  They survive pocs_set_footprint, pocs_set_obstacles,
+ * pocs_set_obstacle_schedule, pocs_set_plans and pocs_set_disc_covariances.  Hypotheses of the same D with other numbers are
+ * overwritten in place and the cached graph is replayed (pocs_get_graph_captures does not move): the planning cycle, where new weights
+ * arrive with every prediction.  pocs_get_disc_hypotheses writes up to cap entries of each array that is not null and returns D (0
+ * when none, POCS_E_BUFFER for cap < D).
+ * SERVED, REFUSED and NOT applied: exactly what discs serve, refuse and do not apply; hypotheses need discs.  One refusal of their
+ * own, in both directions with POCS_E_STATE: a round footprint (pocs_set_footprint_disc). */
+int pocs_set_disc_hypotheses(pocs_ctx* ctx, const int* group /* D */, const double* weight /* D */, int D);
+int pocs_get_disc_hypotheses(const pocs_ctx* ctx, int* group, double* weight, unsigned long long* lo, unsigned long long* hi, int cap);   /* returns D, 0 when none */
+
 /* ---- a round footprint: a disc of radius rho centred on the pose, for both estimators (ours) -----------
  * Most mobile bases are round.  Handed over as its bounding square such a robot is 27 % too large in area, and collisions are decided
  * at corners it does not have.  pocs_set_footprint_disc makes the footprint the disc of radius rho (finite, >= 0; 0 is a point robot,
@@ -808,6 +845,17 @@ int pocs_probe_device_disc_noise(pocs_ctx* ctx, const double* fp4, const double*
    pose i touches displaced disc d -- through the MC kernels' single-pose form --, bit 31 should the sampling kernel's two-pose lane-mask
    form (poses 2 j, 2 j + 1) ever disagree.  Never refused.  POCS_E_ARG for a null pointer, D outside 1 .. 16, n outside 2 .. 2^20 or odd,
    an odd first, a bad footprint, disc or covariance and ANY input that is not finite. */
+int pocs_probe_device_disc_hypotheses(pocs_ctx* ctx, const double* fp4, const double* discs /* D x 3 */, const double* cov /* D x 3, may be null */,
+                                      const int* group /* D */, const double* weight /* D */, int D, uint64_t seed, uint32_t waypoint_word,
+                                      unsigned long long first /* even */, int n /* even */, const double* poses_xyt,
+                                      unsigned* exists_out /* n */, unsigned* flags_out /* n */);
+/* TEST HOOK beside pocs_probe_device_disc_noise, equally self-contained: prediction hypotheses on the DEVICE for the caller's own
+   footprint, D <= 32 discs, covariances (null: none) and hypotheses, prepared as the library prepares the context's.  Pose i has index
+   first + i; the seed is the caller's and the waypoint word serves deviations and existence draws alike.  Bit d of exists_out[i]: disc d
+   exists for pose i; bit d of flags_out[i]: pose i touches disc d -- through the MC kernels' single-pose form.  Should the sampling
+   kernel's two-pose lane-mask form (poses 2 j, 2 j + 1) ever disagree, the pose's exists is 0 and its flags are all ones.  Never
+   refused.  POCS_E_ARG for a null pointer but cov, D outside 1 .. 32, n outside 2 .. 2^20 or odd, an odd first, a bad footprint, disc,
+   covariance or hypothesis table and ANY input that is not finite. */
 int pocs_probe_device_footprint_disc(pocs_ctx* ctx, double radius, const double* boxes /* M x 5 */, int M, const double* discs /* D x 3 */, int D,
                                      const double* cov /* NULL or D x 3 */, uint64_t seed, uint32_t waypoint_word, unsigned long long first /* even */,
                                      int n, const double* poses_xyt, int* out /* n */);

@@ -107,6 +107,10 @@ SIGNATURES = {
     "pocs_set_disc_covariances": (C.c_int, [_vp, _dp, C.c_int, C.c_int, C.c_int]),
     "pocs_get_disc_covariances": (C.c_int, [_vp, _dp, C.c_int, C.POINTER(C.c_int)]),
     "pocs_probe_device_disc_noise": (C.c_int, [_vp, _dp, _dp, _dp, C.c_int, C.c_uint64, C.c_uint32, C.c_ulonglong, C.c_int, _dp, _dp, C.POINTER(C.c_uint)]),
+    "pocs_set_disc_hypotheses": (C.c_int, [_vp, C.POINTER(C.c_int), _dp, C.c_int]),
+    "pocs_get_disc_hypotheses": (C.c_int, [_vp, C.POINTER(C.c_int), _dp, C.POINTER(C.c_ulonglong), C.POINTER(C.c_ulonglong), C.c_int]),
+    "pocs_probe_device_disc_hypotheses": (C.c_int, [_vp, _dp, _dp, _dp, C.POINTER(C.c_int), _dp, C.c_int, C.c_uint64, C.c_uint32, C.c_ulonglong, C.c_int, _dp,
+                                                    C.POINTER(C.c_uint), C.POINTER(C.c_uint)]),
     "pocs_set_segment_checks": (C.c_int, [_vp, C.c_int]),
     "pocs_get_segment_checks": (C.c_int, [_vp]),
     "pocs_get_segment_counts": (C.c_int, [_vp, C.POINTER(C.c_ulonglong), C.c_int]),
@@ -359,6 +363,53 @@ class Context:
             return None, False
         return out[:n].reshape(S, D, 3), bool(per.value)
 
+    def set_disc_hypotheses(self, group, weight=None):
+        """Prediction hypotheses: per disc in force (set_discs) a group and a weight.  group[d] = -1: disc d is always there;
+        group[d] = g in [0, D): disc d is one alternative of group g, existing for a pose with probability floor(weight[d] 2^32) / 2^32,
+        and the alternatives of a group exclude each other (include/pocs.h).  None, an empty table or all groups -1 clears.
+        planio.prediction_modes builds discs, groups and weights from a predictor's weighted tracks."""
+        if group is None or np.asarray(group).size == 0:
+            self._chk(self.lib.pocs_set_disc_hypotheses(self.h, None, None, 0))
+            return
+        g = np.ascontiguousarray(group, dtype=np.int32).ravel()
+        w = np.ones(g.size) if weight is None else _arr(weight).ravel()
+        if w.size != g.size:
+            raise ValueError("%d groups and %d weights" % (g.size, w.size))
+        self._chk(self.lib.pocs_set_disc_hypotheses(self.h, g.ctypes.data_as(C.POINTER(C.c_int)), w.ctypes.data_as(_dp), g.size))
+
+    def disc_hypotheses(self):
+        """(group int32[D], weight float64[D], lo uint64[D], hi uint64[D]) as in force -- disc d exists for a pose iff lo[d] <= u < hi[d]
+        for the pose's 32-bit existence word u --; None when none are set."""
+        D = max(self.discs()[0], 1)
+        g, w = np.zeros(D, dtype=np.int32), np.zeros(D)
+        lo, hi = np.zeros(D, dtype=np.uint64), np.zeros(D, dtype=np.uint64)
+        n = self.lib.pocs_get_disc_hypotheses(self.h, g.ctypes.data_as(C.POINTER(C.c_int)), w.ctypes.data_as(_dp), lo.ctypes.data_as(C.POINTER(C.c_ulonglong)),
+                                              hi.ctypes.data_as(C.POINTER(C.c_ulonglong)), D)
+        if n < 0:
+            self._chk(n)
+        if n == 0:
+            return None
+        return g[:n], w[:n], lo[:n], hi[:n]
+
+    def probe_device_disc_hypotheses(self, footprint, discs, cov, group, weight, seed, waypoint_word, first, poses):
+        """Test hook: prediction hypotheses on the device for the caller's own footprint (dx, dy, hx, hy), discs (D x 3, D <= 32),
+        covariances (D x 3, or None) and hypotheses (group, weight: D each).  Pose i of `poses` (n x 3, n even) has index first + i
+        (first even).  Returns (exists uint32[n], flags uint32[n]): bit d = disc d exists for pose i, bit d = pose i touches disc d;
+        exists 0 with flags all ones = the kernels' two forms disagree (never)."""
+        fp = _arr(footprint).ravel()
+        d, xyt = _rows(discs, 3), _rows(poses, 3)
+        v = None if cov is None else _rows(cov, 3)
+        g = np.ascontiguousarray(group, dtype=np.int32).ravel()
+        w = _arr(weight).ravel()
+        assert fp.size == 4 and (v is None or v.shape == d.shape) and g.size == w.size == d.shape[0]
+        exists = np.full(xyt.shape[0], 0xFFFFFFFF, dtype=np.uint32)
+        flags = np.full(xyt.shape[0], 0xFFFFFFFF, dtype=np.uint32)
+        self._chk(self.lib.pocs_probe_device_disc_hypotheses(self.h, fp.ctypes.data_as(_dp), d.ctypes.data_as(_dp), None if v is None else v.ctypes.data_as(_dp),
+                                                             g.ctypes.data_as(C.POINTER(C.c_int)), w.ctypes.data_as(_dp), d.shape[0], C.c_uint64(int(seed)),
+                                                             C.c_uint32(int(waypoint_word)), C.c_ulonglong(int(first)), xyt.shape[0], xyt.ctypes.data_as(_dp),
+                                                             exists.ctypes.data_as(C.POINTER(C.c_uint)), flags.ctypes.data_as(C.POINTER(C.c_uint))))
+        return exists, flags
+
     def probe_device_disc_noise(self, footprint, discs, cov, seed, waypoint_word, first, poses):
         """Test hook: uncertain discs on the device for the caller's own footprint (dx, dy, hx, hy), discs (D x 3, D <= 16) and
         covariances (D x 3).  Pose i of `poses` (n x 3, n even) has index first + i (first even).  Returns (centres float64[n, D, 2],
@@ -573,6 +624,8 @@ class Context:
             self.set_discs(env["discs"])
         if env.get("disc_covariances") is not None:   # uncertain discs (set_disc_covariances)
             self.set_disc_covariances(env["disc_covariances"], bool(env.get("disc_noise_persistent", False)))
+        if env.get("disc_hypotheses") is not None:    # prediction hypotheses: (group, weight) (set_disc_hypotheses)
+            self.set_disc_hypotheses(*env["disc_hypotheses"])
         self.set_alphas(p["alphas"])
         self.set_q(p["Q"])
         self.set_landmarks(p["landmarks"])

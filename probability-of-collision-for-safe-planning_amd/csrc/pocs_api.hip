@@ -224,6 +224,8 @@ int pocs_set_footprint_disc(pocs_ctx* c, double radius) {
   }
   if (seg_applied(c))
     return fail(c, POCS_E_STATE, "pocs_set_footprint_disc: segment checks are set (pocs_set_segment_checks); %s", pocs_modes::kRoundFpClause);
+  if (hyp_applied(c))
+    return fail(c, POCS_E_STATE, "pocs_set_footprint_disc: prediction hypotheses are set (pocs_set_disc_hypotheses); hypotheses are served under a footprint box");
   const double rho = radius == 0.0 ? 0.0 : radius;   // (a point robot: +0.0)
   c->fp = pocs_footprint{0.0, 0.0, rho, rho};        // the bounding square: what pocs_get_footprint_parts reports
   c->fp_F = 1; c->fp_parts[0] = c->fp;               // (a compound footprint is replaced)
@@ -315,6 +317,7 @@ int pocs_set_discs(pocs_ctx* c, const double* discs, int D, int S) {
     if (c->disc_D > 0) c->env_dirty = true;
     c->discs.clear(); c->disc_D = 0; c->disc_S = 1;
     c->disc_cov.clear(); c->disc_noise_persistent = 0;      // (covariances need discs)
+    c->hyp_group.clear(); c->hyp_weight.clear();            // (and so do hypotheses)
     return POCS_OK;
   }
   if (S < 1 || S > POCS_MAX_WORLD_STEPS) return fail(c, POCS_E_ARG, "pocs_set_discs: %d steps outside 1..%d", S, POCS_MAX_WORLD_STEPS);
@@ -343,9 +346,61 @@ int pocs_set_discs(pocs_ctx* c, const double* discs, int D, int S) {
     return fail(c, POCS_E_STATE, "pocs_set_discs: segment checks are set (pocs_set_segment_checks); %s", pocs_modes::kDiscClause);
   c->discs.assign(discs, discs + (size_t)S * (size_t)D * 3);
   if (D != c->disc_D || S != c->disc_S) { c->disc_cov.clear(); c->disc_noise_persistent = 0; }      // (the same D and S keep the covariances: new predictions, the same fan)
+  if (D != c->disc_D) { c->hyp_group.clear(); c->hyp_weight.clear(); }      // (the same D keeps the hypotheses, whatever S is: an alternative is a whole track)
   c->disc_D = D; c->disc_S = S;
   c->env_dirty = true;                               // (same D and S: the records are overwritten in place and the cached graph replays)
   return POCS_OK;
+}
+
+// ---- prediction hypotheses (include/pocs.h) ----
+// A group and a weight per disc in force; upload_world turns them into the records' gates.
+int pocs_set_disc_hypotheses(pocs_ctx* c, const int* group, const double* weight, int D) {
+  if (!setter(c)) return POCS_E_ARG;
+  if (modes_of(c) & pocs_modes::kSequence)
+    return fail(c, POCS_E_ORDER, "pocs_set_disc_hypotheses: %s; %s", pocs_modes::name(pocs_modes::kSequence), pocs_modes::kDiscClause);
+  if ((!group || !weight) && D == 0) {               // clears: every call is again the call it is without hypotheses
+    if (!c->hyp_group.empty()) c->env_dirty = true;
+    c->hyp_group.clear(); c->hyp_weight.clear();
+    return POCS_OK;
+  }
+  if (!discs_applied(c)) return fail(c, POCS_E_STATE, "pocs_set_disc_hypotheses: no discs are set (pocs_set_discs): hypotheses belong to discs");
+  if (rfoot_applied(c))
+    return fail(c, POCS_E_STATE, "pocs_set_disc_hypotheses: a round footprint is set (pocs_set_footprint_disc); hypotheses are served under a footprint box");
+  if (D != c->disc_D) return fail(c, POCS_E_ARG, "pocs_set_disc_hypotheses: %d discs, the discs in force are %d", D, c->disc_D);
+  if (!group || !weight) return fail(c, POCS_E_ARG, "pocs_set_disc_hypotheses: null %s", !group ? "groups" : "weights");
+  std::vector<unsigned long long> lo((size_t)D), hi((size_t)D);
+  int bad = 0;
+  if (const int k = pocs_hyp_thresholds(group, weight, D, lo.data(), hi.data(), &bad))
+    return fail(c, POCS_E_ARG, "pocs_set_disc_hypotheses: disc %d (group %d, weight %g): %s", bad, group[bad], weight[bad], hyp_refusal(k));
+  bool any = false;
+  for (int d = 0; d < D; ++d) any = any || group[d] >= 0;
+  if (any) {
+    c->hyp_group.assign(group, group + D);
+    c->hyp_weight.assign(weight, weight + D);
+    for (int d = 0; d < D; ++d)
+      if (group[d] < 0) c->hyp_weight[(size_t)d] = 1.0;      // (not read: what the getter hands back for a disc that is always there)
+  } else {                                           // (all groups -1 is the same as cleared)
+    c->hyp_group.clear(); c->hyp_weight.clear();
+  }
+  c->env_dirty = true;                               // (the same D: the gates are overwritten in place and the cached graph replays)
+  return POCS_OK;
+}
+
+int pocs_get_disc_hypotheses(const pocs_ctx* c, int* group, double* weight, unsigned long long* lo, unsigned long long* hi, int cap) {
+  if (!c) return POCS_E_ARG;
+  if (!hyp_applied(c)) return 0;
+  const int D = c->disc_D;
+  if (D > cap) return POCS_E_BUFFER;
+  std::vector<unsigned long long> l((size_t)D), h((size_t)D);
+  int bad = 0;
+  pocs_hyp_thresholds(c->hyp_group.data(), c->hyp_weight.data(), D, l.data(), h.data(), &bad);
+  for (int d = 0; d < D; ++d) {
+    if (group) group[d] = c->hyp_group[(size_t)d];
+    if (weight) weight[d] = c->hyp_weight[(size_t)d];
+    if (lo) lo[d] = l[(size_t)d];
+    if (hi) hi[d] = h[(size_t)d];
+  }
+  return D;
 }
 
 // ---- uncertain discs (include/pocs.h) ----

@@ -258,6 +258,104 @@ POCS_HD bool pocs_pose_collides_noisy(double x, double y, double th, const pocs_
   return hit;
 }
 
+// ---- prediction hypotheses (pocs_set_disc_hypotheses) ------------------------------------------------------------------
+// A disc may be one ALTERNATIVE of a group: the alternatives of a group exclude each other, for one pose at most one of them
+// exists.  The host forms exact integer thresholds (pocs_hyp_thresholds): n_d = floor(weight_d 2^32) -- the product is exact --,
+// and within a group in ascending d, lo_d = the sum of n_e over the earlier discs e < d of the group, hi_d = lo_d + n_d <= 2^32.
+// A pose is one possible world: for pose index i, the run's seed, group g and waypoint word v
+//   words = Philox4x32-7((lo32(i >> 1), hi32(i >> 1), v, 6 << 16 | g), seed)        (pocs_draw, POCS_STREAM_HYP)
+//   u = words[2 h],  h = i & 1                                                      (one draw serves poses 2 j and 2 j + 1)
+// and disc d exists for the pose iff lo_d <= u < hi_d: integers, nothing is floating point.  The record's GATE is four 32-bit
+// words {lo, hi - 1, g, on} (hi - 1 fits: n_d >= 1); on = 0 is a box or a disc that is always there, and draws nothing.
+// The flag of a gated record is "exists" AND the record's test as it is without this (the broad phase on the nominal centre with
+// the grown fields, the narrow phase, on the displaced centre for an uncertain disc); streams 5 and 6 are independent.
+// Why the culls stay exact: removing a disc for a pose can only remove hits.  Every cull keeps a record when SOME pose in reach
+// could touch it; a record that is dropped touches no pose whether it exists or not, and a record that is kept is tested pose
+// by pose with its gate.  So the table's fields 6 and 7, gmm_cull's keep test and its tightened box stand with no change to any
+// record, as they stood under the growth (the block above pocs_disc_noise_factor).
+#define POCS_GATE_STRIDE 4
+// The thresholds of a table of D alternatives; lo, hi: D entries each.  0: formed; otherwise what the setter refuses, 1: a group
+// outside [-1, D), 2: a weight that is not finite or outside (0, 1], 3: n_d = 0, 4: a group whose last hi exceeds 2^32 -- and
+// *bad is the disc.  A disc of group -1 has lo = 0, hi = 2^32 and its weight is not read.
+POCS_HD int pocs_hyp_thresholds(const int* group, const double* weight, int D, unsigned long long* lo, unsigned long long* hi, int* bad) {
+  for (int d = 0; d < D; ++d) {
+    *bad = d;
+    if (group[d] < -1 || group[d] >= D) return 1;
+    if (group[d] < 0) { lo[d] = 0ull; hi[d] = 1ull << 32; continue; }
+    if (!__builtin_isfinite(weight[d]) || !(weight[d] > 0.0) || !(weight[d] <= 1.0)) return 2;
+    const unsigned long long n = (unsigned long long)floor(weight[d] * 4294967296.0);
+    if (n == 0ull) return 3;
+    unsigned long long l = 0ull;
+    for (int e = 0; e < d; ++e)
+      if (group[e] == group[d]) l = hi[e];                           // (ascending e: the last earlier one's hi is the sum so far)
+    lo[d] = l; hi[d] = l + n;
+    if (hi[d] > (1ull << 32)) return 4;
+  }
+  return 0;
+}
+POCS_HD void pocs_hyp_gate(int group, unsigned long long lo, unsigned long long hi, uint32_t* gate) {
+  gate[0] = group < 0 ? 0u : (uint32_t)lo;
+  gate[1] = group < 0 ? 0xFFFFFFFFu : (uint32_t)(hi - 1ull);
+  gate[2] = group < 0 ? 0u : (uint32_t)group;
+  gate[3] = group < 0 ? 0u : 1u;
+}
+// the existence word of group g for pose index `index`
+POCS_HD uint32_t pocs_hyp_word(uint64_t seed, uint64_t index, uint32_t v, uint32_t g) {
+  const pocs_u32x4 w = pocs_draw(seed, index >> 1, v, POCS_STREAM_HYP, g);
+  return (index & 1ull) ? w.z : w.x;
+}
+// does the record of gate `gate` exist for the pose?  (on = 0: always)
+POCS_HD bool pocs_hyp_exists(const uint32_t* gate, uint64_t seed, uint64_t index, uint32_t v) {
+  if (gate[3] == 0u) return true;
+  const uint32_t u = pocs_hyp_word(seed, index, v, gate[2]);
+  return gate[0] <= u && u <= gate[1];
+}
+// pocs_world_hit_noisy for a table whose disc records may be gated: `gate` is the record's gate, `row` its row of the noise table
+// (rows may be null: no covariances), v the deviations' waypoint word and vh the hypotheses'
+POCS_HD bool pocs_world_hit_gated(double px, double py, double sn, double cs, double rx, double ry, const double* o, const double* row,
+                                  const uint32_t* gate, uint64_t seed, uint64_t index, uint32_t v, uint32_t vh, const pocs_tables* T) {
+  if (fabs(o[0] - px) > o[6] || fabs(o[1] - py) > o[7]) return false;
+  if (pocs_record_is_disc(o[3])) {
+    if (!pocs_hyp_exists(gate, seed, index, vh)) return false;       // (the gate is wave-uniform, the answer is the lane's)
+    if (row && row[0] != 0.0) {
+      double d[5];
+      pocs_disc_displaced(o[0], o[1], row, seed, index, v, T, &d[0], &d[1]);
+      d[4] = o[4];
+      return pocs_disc_narrow(px, py, sn, cs, rx, ry, d);
+    }
+    return pocs_disc_narrow(px, py, sn, cs, rx, ry, o);
+  }
+  return pocs_box_narrow(px, py, sn, cs, rx, ry, o);
+}
+// pocs_pose_collides_noisy under hypotheses, beside it: `gates` holds POCS_GATE_STRIDE words per record of `obs`, `rows` (null: no
+// covariances) POCS_NOISE_STRIDE doubles.  `exists` / `touched`, where given, receive bit m per DISC record m that exists for the
+// pose / that the pose touches (the probe's and the harness' way in; M <= 32 there).
+POCS_HD bool pocs_pose_collides_gated(double x, double y, double th, const pocs_footprint* fp, const double* obs, const double* rows,
+                                      const uint32_t* gates, int M, uint64_t seed, uint64_t index, uint32_t v, uint32_t vh,
+                                      const pocs_tables* T, unsigned* exists = nullptr, unsigned* touched = nullptr) {
+  if (exists) *exists = 0u;
+  if (touched) *touched = 0u;
+  if (M <= 0) return false;
+  double sn, cs;
+  pocs_sincos_tab(th, T, &sn, &cs);
+  double px = x, py = y;
+  if (!(fp->dx == 0.0 && fp->dy == 0.0)) {
+    px = x + fma(cs, fp->dx, -(sn * fp->dy));
+    py = y + fma(sn, fp->dx, cs * fp->dy);
+  }
+  bool hit = false;
+  for (int m = 0; m < M; ++m) {
+    const double* o = obs + m * POCS_OBS_STRIDE;
+    const uint32_t* gate = gates + m * POCS_GATE_STRIDE;
+    if (exists && pocs_record_is_disc(o[3]) && pocs_hyp_exists(gate, seed, index, vh)) *exists |= 1u << ((unsigned)m & 31u);
+    if (pocs_world_hit_gated(px, py, sn, cs, fp->hx, fp->hy, o, rows ? rows + m * POCS_NOISE_STRIDE : nullptr, gate, seed, index, v, vh, T)) {
+      hit = true;
+      if (touched && pocs_record_is_disc(o[3])) *touched |= 1u << ((unsigned)m & 31u);
+    }
+  }
+  return hit;
+}
+
 // ---- a round footprint (pocs_set_footprint_disc) ------------------------------------------------------------------------
 // The robot is a disc of radius rho >= 0 centred on the pose's reference point (rho = 0: a point).  It has no heading: theta is never
 // read, and no sine or cosine appears anywhere below.  The records are the table's as it is under discs -- boxes by
@@ -407,6 +505,18 @@ struct pocs_noise_pair {
   uint64_t seed, pair;
   uint32_t v;
 };
+// Hypotheses (pocs_set_disc_hypotheses; the block above pocs_hyp_thresholds) on top of that: the GATES of the list the loop runs over
+// as well (LDS, POCS_GATE_STRIDE words per record, in the list's order) and the hypotheses' waypoint word.  The rows may all be zeros.
+struct pocs_noise_gate_pair {
+  static constexpr bool on = true;
+  const double* rows;
+  uint64_t seed, pair;
+  uint32_t v;
+  const uint32_t* gates;
+  uint32_t vh;
+};
+template <class NZ> struct pocs_nz_gated { static constexpr bool value = false; };
+template <> struct pocs_nz_gated<pocs_noise_gate_pair> { static constexpr bool value = true; };
 
 // ROUND: the table may hold disc records; a record's kind is decided by a scalar branch on a ballot of its marker (every lane
 // reads the same record), and `kinds`, where given, receives the two poses' masks for the disc records apart: kinds[h] is the part
@@ -414,6 +524,11 @@ struct pocs_noise_pair {
 // NZ = pocs_noise_pair (ROUND only): behind the disc branch a second scalar branch on the record's row -- every lane reads the same
 // one -- and for an uncertain disc ONE Philox call per pair, a Box-Muller pair per pose whose broad phase some lane passed, and
 // pocs_disc_narrow's operations on the displaced centre.
+// NZ = pocs_noise_gate_pair: in front of that a scalar branch on the record's gate -- every lane reads the same one -- and for a gated
+// disc that some lane's broad phase passed ONE Philox call per pair and an integer range compare per pose, balloted and and-ed into
+// the pose's broad-phase mask by a scalar instruction: a lane for whose pose the disc does not exist takes no part in the record's
+// narrow phase; a record that exists for no lane inside its box still draws its deviation's Philox words (one call per pair) and
+// skips the Box-Muller pairs and the narrow phase of both poses.
 template <bool EAGER, bool CENTRED, class Each, bool ROUND = false, class NZ = pocs_noise_none>
 __device__ __forceinline__ void pocs_pair_loop(const double x[2], const double y[2], const double th[2], const pocs_footprint* fp,
                                                const double* obs, int M, const pocs_tables* T, const pocs_vconst* V,
@@ -472,6 +587,16 @@ __device__ __forceinline__ void pocs_pair_loop(const double x[2], const double y
         disc = __builtin_amdgcn_ballot_w64(__builtin_bit_cast(unsigned long long, ay) == 0x8000000000000000ull) != 0ull;
       }
       if (ROUND && disc) {
+        if constexpr (pocs_nz_gated<NZ>::value) {
+          const uint32_t* const gt = nz.gates + m * POCS_GATE_STRIDE;
+          const uint32_t g_on = gt[3];
+          if (__builtin_amdgcn_ballot_w64(g_on != 0u) != 0ull) {     // (scalar) the disc is an alternative of a group
+            const pocs_u32x4 wh = pocs_draw(nz.seed, nz.pair, nz.vh, POCS_STREAM_HYP, gt[2]);
+            const uint32_t g_lo = gt[0], g_him = gt[1];
+            pm[0] &= __builtin_amdgcn_ballot_w64(g_lo <= wh.x && wh.x <= g_him);
+            pm[1] &= __builtin_amdgcn_ballot_w64(g_lo <= wh.z && wh.z <= g_him);
+          }
+        }
         bool noisy = false;                                          // (scalar) the disc is uncertain: its row's l00 is not zero
         if constexpr (NZ::on) {
           const double* const row = nz.rows + m * POCS_NOISE_STRIDE;

@@ -233,6 +233,12 @@ struct pocs_ctx {
   // disc index}, record by record beside d_env) and grows the disc records, and every call is served by the _noise / MC_NOISE forms
   std::vector<double> disc_cov;
   int disc_noise_persistent = 0;         // the MC path's waypoint word: 1 = 0 at every waypoint, 0 = the waypoint
+  // prediction hypotheses (pocs_set_disc_hypotheses): empty is off -- every call is, launch for launch, the call it is without this (a
+  // table whose groups are all -1 is stored as empty).  Otherwise disc_D groups and weights as the caller gave them, which the setter
+  // has turned into thresholds once already; upload_world forms them again into d_gates ([POCS_MAX_OBSTACLES] gates {lo, hi - 1, g, on},
+  // record by record, the same at every env step) and every call is served by the _hyp / MC_HYP forms
+  std::vector<int> hyp_group;
+  std::vector<double> hyp_weight;
   // a round footprint (pocs_set_footprint_disc): fp_round = false is off -- every call is, launch for launch, what it is without this.
   // On: the robot is the disc of radius fp_rho centred on the pose; `fp` is its bounding square {0, 0, rho, rho} and fp_F = 1 (what
   // pocs_get_footprint_parts reports), upload_world prepares every record with rho as the bounding radius, every call is served by
@@ -272,6 +278,7 @@ struct pocs_ctx {
   // the cached graph) and the segment counts [slots][W] u64, zeroed by a kernel at the head of every call's launches
   pocs_rt::DevBuf d_seg, d_segct;
   pocs_rt::DevBuf d_noise;               // uncertain discs: the noise rows, an allocation of its own (pocs_env_dev keeps its layout)
+  pocs_rt::DevBuf d_gates;               // prediction hypotheses: the records' gates, POCS_MAX_OBSTACLES x POCS_GATE_STRIDE words (a fixed size: new weights replay the graph)
   pocs_rt::DevBuf d_obsct;               // POCS_OPT_OBSTACLE_COUNTS: [slots][W][POCS_MAX_OBSTACLES] u64, zeroed by a kernel at the head of every call's launches
   // one-hop exchange (pocs_xchg_*): this rank's buffer, the peers' buffers as mapped here
   void* xchg_own = nullptr;
@@ -379,6 +386,15 @@ inline int env_steps(const pocs_ctx* c) { return discs_applied(c) && c->disc_S >
 inline int env_records(const pocs_ctx* c) { return world_boxes(c) + c->disc_D; }
 // Disc covariances are set and some row is not zero (pocs_set_disc_covariances): the launches carry the rows of their waypoint.
 inline bool noise_applied(const pocs_ctx* c) { return discs_applied(c) && !c->disc_cov.empty(); }
+// Hypotheses are set and some disc is gated (pocs_set_disc_hypotheses): the launches carry the gate table, and rows of zeros where the
+// context has no covariances (upload_world then fills d_noise with zeros).
+inline bool hyp_applied(const pocs_ctx* c) { return discs_applied(c) && !c->hyp_group.empty(); }
+inline bool noise_rows_held(const pocs_ctx* c) { return noise_applied(c) || hyp_applied(c); }
+// what pocs_hyp_thresholds refuses, in words
+inline const char* hyp_refusal(int k) {
+  return k == 1 ? "a group is -1 (always there) or an index in [0, D)" : k == 2 ? "a weight is finite and in (0, 1]"
+       : k == 3 ? "floor(weight * 2^32) is 0: the alternative would never exist" : "the weights of its group sum to more than 1";
+}
 inline const double* noise_at(const pocs_ctx* c, int w) {
   const int S = env_steps(c);
   return (const double*)c->d_noise.p + (size_t)(w < 0 ? 0 : w < S ? w : S - 1) * (POCS_MAX_OBSTACLES * POCS_NOISE_STRIDE);

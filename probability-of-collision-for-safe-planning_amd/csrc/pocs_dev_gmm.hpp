@@ -87,13 +87,24 @@ template <> struct gmm_sg_smem<true> {
 };
 //   (the noise form only, pocs_set_disc_covariances: LDS of its own beside gmm_smem, whose type and layout stay) per run buffer and KEPT
 //          record its row {l00, l10, l11, disc index} of the noise table, in the kept list's order: 4 KB
-template <bool RN> struct gmm_noise_rows { static __device__ __forceinline__ double* get() { return nullptr; } };
-template <> struct gmm_noise_rows<true> {
+//   (the hypotheses form, pocs_set_disc_hypotheses, on top of it: behind the two buffers' rows, per run buffer and KEPT record its gate
+//          {lo, hi - 1, g, on}, four 32-bit words, in the kept list's order: 2 KB more -- gmm_gates finds them)
+template <bool RN, bool RH = false> struct gmm_noise_rows { static __device__ __forceinline__ double* get() { return nullptr; } };
+template <> struct gmm_noise_rows<true, false> {
   static __device__ __forceinline__ double* get() {
     __shared__ alignas(16) double rows[2 * POCS_MAX_OBSTACLES * POCS_NOISE_STRIDE];
     return rows;
   }
 };
+template <> struct gmm_noise_rows<true, true> {
+  static __device__ __forceinline__ double* get() {
+    __shared__ alignas(16) double rows[2 * POCS_MAX_OBSTACLES * POCS_NOISE_STRIDE + 2 * POCS_MAX_OBSTACLES * POCS_GATE_STRIDE / 2];
+    return rows;
+  }
+};
+__device__ __forceinline__ uint32_t* gmm_gates(double* nz, const int rb) {
+  return reinterpret_cast<uint32_t*>(nz + 2 * POCS_MAX_OBSTACLES * POCS_NOISE_STRIDE) + rb * (POCS_MAX_OBSTACLES * POCS_GATE_STRIDE);
+}
 template <int K, int TB, bool OC = false, bool CL = false, bool FPN = false, bool RG = false, bool SG = false>
 struct gmm_smem : gmm_oc_smem<OC>, gmm_cl_smem<CL>, gmm_fp_smem<FPN>, gmm_rg_smem<RG>, gmm_sg_smem<SG> {
   static constexpr int NC = K * POCS_NMOM;
@@ -221,7 +232,10 @@ __device__ __forceinline__ void gmm_reach(const pocs_footprint& fp, const double
 // record m's row of the launch's noise table; the tightened box gains the record's growth gx = 6.67 |l00|, gy = 6.67 (|l10| + |l11|)
 // -- the host's own operations, so that the table's grown fields 6 and 7 and the tightened ones bound the same displaced disc
 // (pocs_collide.h, the block above pocs_disc_noise_factor) -- and a kept record's row is written to the kept list's position.
-template <bool RN = false, int K, int TB, bool OC, bool CL, bool FPN, bool RG, bool SG>
+// RH (pocs_set_disc_hypotheses, on top of RN; the rows may all be zeros): lane m also fetches record m's gate of the launch's gate table
+// and a kept record's gate is written to the kept list's position behind the rows (gmm_gates).  No box changes: removing a disc for
+// a pose can only remove hits (pocs_collide.h, the block above pocs_hyp_thresholds).
+template <bool RN = false, bool RH = false, int K, int TB, bool OC, bool CL, bool FPN, bool RG, bool SG>
 __device__ __forceinline__ void gmm_cull(const pocs_gmm_launch& a, gmm_smem<K, TB, OC, CL, FPN, RG, SG>& sm, const int rb, const int lane, const double* par,
                                          [[maybe_unused]] double* nz = nullptr) {
   const pocs_footprint fp = a.fp;
@@ -278,6 +292,12 @@ __device__ __forceinline__ void gmm_cull(const pocs_gmm_launch& a, gmm_smem<K, T
     if constexpr (RN) {
 #pragma unroll
       for (int j = 0; j < POCS_NOISE_STRIDE; ++j) nz[(rb * POCS_MAX_OBSTACLES + pos) * POCS_NOISE_STRIDE + j] = row[j];
+    }
+    if constexpr (RH) {
+      static_assert(!RH || RN, "hypotheses: on top of the noise form");
+      uint32_t* const gz = gmm_gates(nz, rb) + pos * POCS_GATE_STRIDE;
+#pragma unroll
+      for (int j = 0; j < POCS_GATE_STRIDE; ++j) gz[j] = a.gates[lane * POCS_GATE_STRIDE + j];
     }
   }
   if constexpr (OC) sm.occ[rb][lane] = 0u;           // (one wave, POCS_MAX_OBSTACLES = 64 lanes: every counter of the buffer)
@@ -535,13 +555,16 @@ __device__ __forceinline__ void gmm_cull_seg(const pocs_gmm_launch& a, gmm_smem<
 //   rows, the run's seed, the lane's pair index pair0 + lp and the waypoint, and tests an uncertain disc on its displaced centre.
 //   RF (pocs_set_footprint_disc, with or without RN, never with RD: the form serves worlds with and without discs): the collision test
 //   is pocs_pair_round_masks on the kept list gmm_cull_rfoot left -- the radius is fp.hx, the headings are not looked at.
+//   RH (pocs_set_disc_hypotheses, on top of RD and RN, never with RF): the ROUND form is handed the run buffer's gates as well
+//   (gmm_gates) and the waypoint as the hypotheses' word too, and a gated disc counts for the poses for which it exists.
 template <int K, bool STORE, int TB, bool LONE_PRE = false, bool OC = false, bool CL = false, bool FPN = false, bool RG = false, bool SG = false,
-          bool RD = false, bool RN = false, bool RF = false>
+          bool RD = false, bool RN = false, bool RF = false, bool RH = false>
 __device__ __forceinline__ void gmm_units(const pocs_gmm_launch& a, gmm_smem<K, TB, OC, CL, FPN, RG, SG>& sm, const int w, const int r0,
                                           const int ta, const int tb, const double* zpre = nullptr, const int npre = 0,
                                           [[maybe_unused]] const double* nz = nullptr) {
   static_assert(!RN || RD || RF, "uncertain discs: on top of the round form");
   static_assert(!(RF && (RD || LONE_PRE || OC || CL || FPN || RG || SG)), "a round footprint: a family of its own");
+  static_assert(!RH || (RD && RN && !RF), "hypotheses: on top of the noise form, a footprint box");
   const pocs_tables* const s_tab = &sm.tab;
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -668,6 +691,11 @@ __device__ __forceinline__ void gmm_units(const pocs_gmm_launch& a, gmm_smem<K, 
         pocs_pair_round_masks(xs, ys, fp.hx, s_keep, nkeep, s_tab, vc, hits);
       }
     } else
+    if constexpr (RH) {
+      const pocs_noise_gate_pair np = {nz + rb * (POCS_MAX_OBSTACLES * POCS_NOISE_STRIDE), seed_it, pair0 + (uint64_t)(unsigned)lp, (uint32_t)w,
+                                       gmm_gates(const_cast<double*>(nz), rb), (uint32_t)w};
+      pocs_pair_collides_masks<false, pocs_each_none, true, pocs_noise_gate_pair>(xs, ys, ts, &fp, s_keep, nkeep, s_tab, vc, hits, pocs_each_none(), nullptr, np);
+    } else
     if constexpr (RN) {
       const pocs_noise_pair np = {nz + rb * (POCS_MAX_OBSTACLES * POCS_NOISE_STRIDE), seed_it, pair0 + (uint64_t)(unsigned)lp, (uint32_t)w};
       pocs_pair_collides_masks<false, pocs_each_none, true, pocs_noise_pair>(xs, ys, ts, &fp, s_keep, nkeep, s_tab, vc, hits, pocs_each_none(), nullptr, np);
@@ -748,7 +776,9 @@ __device__ __forceinline__ void gmm_units(const pocs_gmm_launch& a, gmm_smem<K, 
       }
     }
     }
-    if (STORE && live) {
+    // (RH: the hypotheses forms read the launch's own word -- a scalar branch per iteration -- so that the family is instantiated
+    // once per K and not twice: the build's time, not the call's, is what that saves.  Every other form folds STORE as it did.)
+    if ((RH ? a.store != 0 : STORE) && live) {
       // Both poses of the pair leave together.  For the last sample of an odd shard the second slot is
       // the pair's unused twin: it lands in the padding element of the run's slice (sample_stride >=
       // count + 1 then) and is never read back.  Written once, never re-read by the kernels: non-temporal,
@@ -1042,7 +1072,7 @@ __device__ __forceinline__ void gmm_close_sums(const pocs_gmm_launch& a, const i
 // the or-ed flags), the tickets and the closers are what they are.  LDS: + 8 KB for the second kept table, + 0.3 KB, and 24 instead of
 // 32 held units, as the clearance form: two blocks per CU in every instantiation.
 template <int K, bool STORE, int TB, bool LONE, bool RISK, bool TREE = false, bool OC = false, bool WORLD = false, bool CL = false, bool FPN = false,
-          bool RG = false, bool SG = false, bool RD = false, bool RN = false, bool RF = false>
+          bool RG = false, bool SG = false, bool RD = false, bool RN = false, bool RF = false, bool RH = false>
 __device__ __forceinline__ void gmm_step_block(const pocs_gmm_launch a) {      // (by value, as a kernel holds its argument)
   typedef gmm_smem<K, TB, OC, CL, FPN, RG, SG> smem_t;
   static_assert(!RN || RD || RF, "uncertain discs: on top of the round form");
@@ -1066,7 +1096,9 @@ __device__ __forceinline__ void gmm_step_block(const pocs_gmm_launch a) {      /
   __shared__ double s_zpre[LONE ? POCS_LONE_PRE * 6 * TB : 2];
   // (RN: the kept records' noise rows per run buffer, 4 KB next to the kept lists: with the _round form's 75 424 B, 79 520 B of the
   // 81 920 B that let two blocks share a CU, for every K.  No other form holds a byte of it.)
-  double* const s_nz = gmm_noise_rows<RN>::get();
+  // (RH: their gates behind them, 2 KB more: 81 568 B at K = 8, still under the 81 920 B)
+  static_assert(!RH || (RD && RN && !RF), "hypotheses: on top of the noise form, a footprint box");
+  double* const s_nz = gmm_noise_rows<RN, RH>::get();
   int npre = 0;
   const int tid = threadIdx.x;
   const int w = a.waypoint;
@@ -1236,8 +1268,8 @@ __device__ __forceinline__ void gmm_step_block(const pocs_gmm_launch a) {      /
       if (tid < 64) gmm_cull_rfoot<RN>(a, sm, 0, tid, sm.par[0], s_nz);
       else if (tid < 128 && r1 > r0) gmm_cull_rfoot<RN>(a, sm, 1, tid - 64, sm.par[1], s_nz);
     } else if constexpr (RN) {
-      if (tid < 64) gmm_cull<true>(a, sm, 0, tid, sm.par[0], s_nz);
-      else if (tid < 128 && r1 > r0) gmm_cull<true>(a, sm, 1, tid - 64, sm.par[1], s_nz);
+      if (tid < 64) gmm_cull<true, RH>(a, sm, 0, tid, sm.par[0], s_nz);
+      else if (tid < 128 && r1 > r0) gmm_cull<true, RH>(a, sm, 1, tid - 64, sm.par[1], s_nz);
     } else {
     if (tid < 64) gmm_cull(a, sm, 0, tid, sm.par[0]);
     else if (tid < 128 && r1 > r0) gmm_cull(a, sm, 1, tid - 64, sm.par[1]);
@@ -1250,7 +1282,7 @@ __device__ __forceinline__ void gmm_step_block(const pocs_gmm_launch a) {      /
     const int tb = (ta + SUB < t1) ? ta + SUB : t1;
     if constexpr (RF) gmm_units<K, STORE, TB, LONE, OC, CL, FPN, RG, SG, false, RN, true>(a, sm, w, r0, ta, tb, s_zpre, ta == t0 ? npre : 0, s_nz);
     else
-    if constexpr (RN) gmm_units<K, STORE, TB, LONE, OC, CL, FPN, RG, SG, RD, true>(a, sm, w, r0, ta, tb, s_zpre, ta == t0 ? npre : 0, s_nz);
+    if constexpr (RN) gmm_units<K, STORE, TB, LONE, OC, CL, FPN, RG, SG, RD, true, false, RH>(a, sm, w, r0, ta, tb, s_zpre, ta == t0 ? npre : 0, s_nz);
     else
     gmm_units<K, STORE, TB, LONE, OC, CL, FPN, RG, SG, RD>(a, sm, w, r0, ta, tb, s_zpre, ta == t0 ? npre : 0);
     POCS_STAMP(1);
@@ -1474,6 +1506,19 @@ __global__ __launch_bounds__(TB, POCS_GMM_BLOCKS_PER_CU * TB / 256) void k_gmm_s
 template <int K, bool STORE, int TB>
 __global__ __launch_bounds__(TB, POCS_GMM_BLOCKS_PER_CU * TB / 256) void k_gmm_step_risk_noise(pocs_gmm_launch a) {
   gmm_step_block<K, STORE, TB, false, true, false, false, false, false, false, false, false, true, true>(a);
+}
+
+// The forms under prediction hypotheses (RH above; pocs_set_disc_hypotheses), on top of the _noise forms: kernels of their own names
+// again.  The head culls with gmm_cull<true, true>, which leaves each kept record's gate beside its row; the sampling loop draws a
+// gated disc's existence word per pair and and-s the poses for which it exists into the record's broad-phase masks.
+// Whether samples are stored is the launch's word `store` here, read at run time (gmm_units): one kernel per K and risk setting.
+template <int K, int TB>
+__global__ __launch_bounds__(TB, POCS_GMM_BLOCKS_PER_CU * TB / 256) void k_gmm_step_hyp(pocs_gmm_launch a) {
+  gmm_step_block<K, true, TB, false, false, false, false, false, false, false, false, false, true, true, false, true>(a);
+}
+template <int K, int TB>
+__global__ __launch_bounds__(TB, POCS_GMM_BLOCKS_PER_CU * TB / 256) void k_gmm_step_risk_hyp(pocs_gmm_launch a) {
+  gmm_step_block<K, true, TB, false, true, false, false, false, false, false, false, false, true, true, false, true>(a);
 }
 
 // The forms under a round footprint (RF above; pocs_set_footprint_disc): a family of its own names, for worlds with and without discs,

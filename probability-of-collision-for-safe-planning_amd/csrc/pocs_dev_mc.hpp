@@ -163,8 +163,13 @@ __device__ __forceinline__ mc_run_start mc_start(const pocs_mc_launch& a) {
 // MC_RFOOT (pocs_set_footprint_disc), a flag on top of MC_ROUND and of MC_ROUND | MC_NOISE, for worlds with and without discs: the
 // footprint is the disc of radius fp.hx centred on the particle, the collision test pocs_round_pose_collides (MC_NOISE:
 // pocs_round_pose_collides_noisy, the same index, seed and waypoint word).  The heading is not looked at.  Nothing else differs.
+//
+// MC_HYP (pocs_set_disc_hypotheses), a flag on top of MC_ROUND and of MC_ROUND | MC_NOISE, never with MC_RFOOT: a disc record whose
+// gate of the launch's gate table is on counts for the particles for which it exists (pocs_pose_collides_gated) -- the existence word
+// drawn for (seed, global particle index first + i, group, word 0): a particle's world keeps its alternative for the whole
+// roll-out.  The gates are read where they lie (wave-uniform addresses); without MC_NOISE no row is read and no log table staged.
 enum { MC_PLAIN = 0, MC_COUNTS = 1, MC_STOP = 2, MC_BOXES = 4, MC_CLEAR = 8, MC_PARTS = 16, MC_REGIONS = 32, MC_SEG = 64, MC_ROUND = 128, MC_NOISE = 256,
-       MC_RFOOT = 512 };
+       MC_RFOOT = 512, MC_HYP = 1024 };
 static_assert(POCS_MAX_OBSTACLES <= 64, "a particle's touched boxes are a 64-bit mask");
 
 // pocs_pose_collides with the touched boxes as a mask (the flag: mask != 0, as the plain form's).
@@ -475,6 +480,9 @@ __global__ __launch_bounds__(POCS_BLOCK) void k_mc_init(pocs_mc_launch a) {
       mc_wave_box_hits(h != 0u, mask, wd.M, box.c);
     } else if constexpr ((MODE & MC_PARTS) != 0) {
       h = pocs_pose_collides_parts(x, y, t, pt.p, pt.F, wd.obs, wd.M, wd.tab) ? 1u : 0u;
+    } else if constexpr ((MODE & MC_HYP) != 0) {
+      static_assert((MODE & MC_HYP) == 0 || ((MODE & MC_ROUND) != 0 && (MODE & (MC_BOXES | MC_CLEAR | MC_PARTS | MC_REGIONS | MC_SEG | MC_RFOOT)) == 0), "hypotheses: on top of MC_ROUND, with or without MC_NOISE");
+      h = pocs_pose_collides_gated(x, y, t, &wd.fp, wd.obs, (MODE & MC_NOISE) != 0 ? a.noise : nullptr, a.gates, wd.M, v.seed, (uint64_t)(a.first + i), 0u, 0u, wd.tab) ? 1u : 0u;      // waypoint 0
     } else if constexpr ((MODE & MC_RFOOT) != 0) {
       static_assert((MODE & MC_RFOOT) == 0 || ((MODE & MC_ROUND) != 0 && (MODE & (MC_BOXES | MC_CLEAR | MC_PARTS | MC_REGIONS | MC_SEG)) == 0), "a round footprint: on top of MC_ROUND, with or without MC_NOISE");
       if constexpr ((MODE & MC_NOISE) != 0)
@@ -620,6 +628,14 @@ __device__ __forceinline__ void mc_step_body(const pocs_mc_launch& a) {
         if (in != 0u && v.hits[i] != 0u) in = 0u;      // (in a region, but collided at an earlier waypoint)
       }
       mc_wave_region_hits(in, rg.G, a.reg_counts + ((size_t)blockIdx.y * (size_t)a.W + (size_t)a.step + 1) * POCS_MAX_REGIONS);
+    } else if constexpr ((MODE & MC_HYP) != 0) {
+      static_assert((MODE & MC_HYP) == 0 || ((MODE & MC_ROUND) != 0 && (MODE & (MC_BOXES | MC_CLEAR | MC_PARTS | MC_REGIONS | MC_SEG | MC_RFOOT)) == 0), "hypotheses: on top of MC_ROUND, with or without MC_NOISE");
+      const uint32_t vw = a.noise_persistent ? 0u : (uint32_t)(a.step + 1);      // (the deviations' word; the existence draws' is 0)
+      if (pocs_pose_collides_gated(nx, ny, nt, &wd.fp, wd.obs, (MODE & MC_NOISE) != 0 ? a.noise : nullptr, a.gates, wd.M, v.seed, (uint64_t)(a.first + i), vw, 0u, wd.tab)) {
+        const uint32_t old = v.hits[i];
+        v.hits[i] = old + 1u;
+        first += old == 0u ? 1u : 0u;
+      }
     } else if constexpr ((MODE & MC_RFOOT) != 0) {
       static_assert((MODE & MC_RFOOT) == 0 || ((MODE & MC_ROUND) != 0 && (MODE & (MC_BOXES | MC_CLEAR | MC_PARTS | MC_REGIONS | MC_SEG)) == 0), "a round footprint: on top of MC_ROUND, with or without MC_NOISE");
       bool touch;

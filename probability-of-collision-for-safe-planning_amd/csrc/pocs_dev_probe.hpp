@@ -5,7 +5,8 @@
 //
 //   k_probe_math, k_probe_radius_roots   the sampler's table-driven functions and its two square roots
 //   k_probe_collide, k_probe_counts      the collision test with k_gmm_step's cull; the component counts of a waypoint
-//   k_probe_clearance, k_probe_parts, k_probe_regions, k_probe_segment, k_probe_discs, k_probe_disc_noise, k_probe_footprint_disc
+//   k_probe_clearance, k_probe_parts, k_probe_regions, k_probe_segment, k_probe_discs, k_probe_disc_noise, k_probe_disc_hypotheses,
+//   k_probe_footprint_disc
 //                                        a mode's single-pose form beside its pair form, pose by pose: ONE block each, which stages
 //                                        its tables with probe_stage and walks the poses with probe_pair_walk
 //
@@ -396,6 +397,61 @@ __global__ __launch_bounds__(POCS_BLOCK) void k_probe_disc_noise(const pocs_env_
     if (live) {
       flags[i0] = single[0] | ((bad[0] || pair[0] != single[0]) ? 0x80000000u : 0u);
       if (two) flags[i1] = single[1] | ((bad[1] || pair[1] != single[1]) ? 0x80000000u : 0u);
+    }
+  });
+}
+// Prediction hypotheses on poses, a footprint, discs, factor rows and gates the caller picks (pocs_probe_device_disc_hypotheses: a test
+// hook beside k_probe_disc_noise): ONE block stages the tables, the D <= 32 grown disc records, their rows (zeros: no covariances) and
+// their gates and asks, per pose of index first + i, the functions the kernels ask.  pocs_pose_collides_gated, the MC kernels'
+// single-pose form, hands out bit d of `exists` per disc that exists for the pose and bit d of `flags` per disc the pose touches;
+// its own answer must be (flags != 0).  Then pocs_pair_collides_masks' gated ROUND form as k_gmm_step_hyp calls it, disc by disc on
+// poses 2 p, 2 p + 1 of pair (first + i0) >> 1: should the two forms ever disagree, the pose's exists is 0 and its flags are all ones.  v is the waypoint word of the
+// deviations and of the existence draws alike.
+__global__ __launch_bounds__(POCS_BLOCK) void k_probe_disc_hypotheses(const pocs_env_dev* __restrict__ env, const double* __restrict__ rows,
+                                                                      const uint32_t* __restrict__ gates, const pocs_tables* __restrict__ tables,
+                                                                      unsigned long long seed, unsigned v, unsigned long long first, int n,
+                                                                      const double* __restrict__ x, const double* __restrict__ y,
+                                                                      const double* __restrict__ th, unsigned* __restrict__ exists,
+                                                                      unsigned* __restrict__ flags) {
+  __shared__ pocs_tables s_tab;
+  __shared__ __attribute__((aligned(16))) double s_obs[POCS_MAX_OBSTACLES * POCS_OBS_STRIDE];
+  __shared__ __attribute__((aligned(16))) double s_rows[POCS_MAX_OBSTACLES * POCS_NOISE_STRIDE];
+  __shared__ __attribute__((aligned(16))) uint32_t s_gates[POCS_MAX_OBSTACLES * POCS_GATE_STRIDE];
+  stage_tables(tables, &s_tab);
+  probe_stage(env->obs, s_obs);
+  probe_stage(rows, s_rows, POCS_MAX_OBSTACLES * POCS_NOISE_STRIDE);
+  for (int j = threadIdx.x; j < POCS_MAX_OBSTACLES * POCS_GATE_STRIDE; j += POCS_BLOCK) s_gates[j] = gates[j];
+  __syncthreads();
+  const int D = env->M < 32 ? env->M : 32;
+  const pocs_footprint fp = env->fp;
+  POCS_VCONST(vc_);
+  probe_pair_walk(n, x, y, th, [&](const double* xs, const double* ys, const double* ts, const int i0, const int i1, const bool live) {
+    const bool two = i1 != i0;
+    const unsigned long long idx[2] = {first + (unsigned long long)i0, first + (unsigned long long)i0 + 1ull};
+    unsigned ex[2] = {0u, 0u}, single[2] = {0u, 0u}, pair[2] = {0u, 0u};
+    bool bad[2] = {false, false};
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+      const bool any = pocs_pose_collides_gated(xs[h], ys[h], ts[h], &fp, s_obs, s_rows, s_gates, D, seed, idx[h], v, v, &s_tab, &ex[h], &single[h]);
+      if (any != (single[h] != 0u) || (single[h] & ~ex[h]) != 0u) bad[h] = true;
+    }
+    for (int d = 0; d < D; ++d) {                                      // (scalar) the pair form, one record at a time: a bit per disc
+      unsigned long long all[2];
+      const pocs_noise_gate_pair np = {&s_rows[d * POCS_NOISE_STRIDE], seed, idx[0] >> 1, v, &s_gates[d * POCS_GATE_STRIDE], v};
+      pocs_pair_collides_masks<false, pocs_each_none, true, pocs_noise_gate_pair>(xs, ys, ts, &fp, &s_obs[d * POCS_OBS_STRIDE], 1, &s_tab, &vc_, all,
+                                                                                  pocs_each_none(), nullptr, np);
+#pragma unroll
+      for (int h = 0; h < 2; ++h)
+        if (__builtin_amdgcn_inverse_ballot_w64(all[h])) pair[h] |= 1u << d;
+    }
+    if (live) {                                                        // (a disagreement: touched discs that do not exist, all of them)
+      const bool b0 = bad[0] || pair[0] != single[0], b1 = bad[1] || pair[1] != single[1];
+      exists[i0] = b0 ? 0u : ex[0];
+      flags[i0] = b0 ? 0xFFFFFFFFu : single[0];
+      if (two) {
+        exists[i1] = b1 ? 0u : ex[1];
+        flags[i1] = b1 ? 0xFFFFFFFFu : single[1];
+      }
     }
   });
 }

@@ -149,7 +149,14 @@ int upload_world(pocs_ctx* c) {                // tables + the collision world: 
     const int M = world_boxes(c);
     std::vector<pocs_env_dev> env(S);
     memset(env.data(), 0, S * sizeof(pocs_env_dev));
-    std::vector<double> noise(noise_applied(c) ? S * POCS_MAX_OBSTACLES * POCS_NOISE_STRIDE : 0, 0.0);      // uncertain discs: a row per record
+    std::vector<double> noise(noise_rows_held(c) ? S * POCS_MAX_OBSTACLES * POCS_NOISE_STRIDE : 0, 0.0);      // uncertain discs: a row per record (hypotheses without covariances: rows of zeros)
+    std::vector<uint32_t> gates(hyp_applied(c) ? POCS_MAX_OBSTACLES * POCS_GATE_STRIDE : 0, 0u);      // prediction hypotheses: a gate per record, the same at every step
+    if (hyp_applied(c)) {
+      std::vector<unsigned long long> lo((size_t)c->disc_D), hi((size_t)c->disc_D);
+      int bad = 0;
+      pocs_hyp_thresholds(c->hyp_group.data(), c->hyp_weight.data(), c->disc_D, lo.data(), hi.data(), &bad);      // (the setter has checked the table)
+      for (int d = 0; d < c->disc_D; ++d) pocs_hyp_gate(c->hyp_group[(size_t)d], lo[(size_t)d], hi[(size_t)d], &gates[(size_t)(M + d) * POCS_GATE_STRIDE]);
+    }
     pocs_parts_dev parts;
     for (size_t s = 0; s < S; ++s) {
       if (discs_applied(c) || rfoot_applied(c)) {    // round obstacles: record s is box step min(s, Sb - 1), then disc step min(s, Sd - 1)
@@ -191,6 +198,10 @@ int upload_world(pocs_ctx* c) {                // tables + the collision world: 
     if (!noise.empty()) {                            // (the same shape: overwritten in place, the cached graph replays)
       if (int r = ensure(c, c->d_noise, noise.size() * sizeof(double))) return r;
       HIPCHK(c, hipMemcpy(c->d_noise.p, noise.data(), noise.size() * sizeof(double), hipMemcpyHostToDevice));
+    }
+    if (!gates.empty()) {                            // (a fixed size: other weights are overwritten in place, the cached graph replays)
+      if (int r = ensure(c, c->d_gates, gates.size() * sizeof(uint32_t))) return r;
+      HIPCHK(c, hipMemcpy(c->d_gates.p, gates.data(), gates.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
     }
     if (parts_applied(c)) {
       if (int r = ensure(c, c->d_parts, sizeof(pocs_parts_dev))) return r;
@@ -553,7 +564,8 @@ void fill_gmm_world(const pocs_ctx* c, pocs_gmm_launch* a, int w) {
   a->tables = (const pocs_tables*)c->d_tables.p;
   a->M = env_records(c);                             // (the boxes, and behind them the discs in force)
   a->round = discs_applied(c) ? 1 : 0;               // (nonzero: the sampling launch is the _round form)
-  a->noise = noise_applied(c) ? noise_at(c, w) : nullptr;      // (non-null: the _noise form on top of it)
+  a->noise = noise_rows_held(c) ? noise_at(c, w) : nullptr;      // (non-null: the _noise form on top of it)
+  a->gates = hyp_applied(c) ? (const uint32_t*)c->d_gates.p : nullptr;      // (non-null: the _hyp form on top of that, rows of zeros where there are no covariances)
   a->rfoot = rfoot_applied(c) ? 1 : 0;               // (nonzero: the _rfoot family, with or without discs and covariances)
   if (!parts_applied(c)) {                           // (a compound footprint's values live in device memory: the launch carries none)
     a->fp = c->fp;
@@ -1088,6 +1100,7 @@ int enqueue_mc_all(Issuer is, long long first, long long count, bool prof) {
   }
   if (discs_applied(c)) a.round = 1;                 // (round obstacles: the MC_ROUND forms of k_mc_init and the per-step kernel)
   if (rfoot_applied(c)) { a.round = 1; a.rfoot = 1; }      // (a round footprint: MC_RFOOT on top, with or without discs)
+  if (hyp_applied(c)) a.gates = (const uint32_t*)c->d_gates.p;      // (prediction hypotheses: MC_HYP on top of MC_ROUND, with or without MC_NOISE)
   if (noise_applied(c)) { a.noise = noise_at(c, 0); a.noise_persistent = c->disc_noise_persistent ? 1 : 0; }      // (uncertain discs: MC_NOISE on top)
   if (c->plans.n) {
     a.run_plan = (const double*)c->d_runplan.p;      // every run its own start mean and steps

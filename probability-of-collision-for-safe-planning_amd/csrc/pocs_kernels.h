@@ -221,6 +221,11 @@ struct pocs_gmm_launch {
   // checks), whatever `round` says -- a world without discs takes the same family.  fp is {0, 0, rho, rho}: the radius is fp.hx
   int rfoot;
   int rfoot_pad;
+  // prediction hypotheses (pocs_set_disc_hypotheses; behind everything else again): non-null = the launch is the _hyp form on top of the
+  // _noise form (`round` is nonzero and `noise` non-null too -- rows of zeros where the context has no covariances --, never `rfoot`):
+  // the gates {lo, hi - 1, g, on} of the records of `env`, record by record (POCS_GATE_STRIDE 32-bit words each, zeros for a box and
+  // for a disc that is always there), the same at every waypoint.  The waypoint word of the existence draws is the launch's waypoint
+  const uint32_t* gates;
 };
 #define POCS_MAX_WORLD_RECORDS 4096   // = POCS_MAX_WORLD_BOXES (include/pocs.h; pocs_ctx.hpp checks)
 #define POCS_CULL_BLOCK 256           // k_world_cull
@@ -315,6 +320,11 @@ struct pocs_mc_launch {               // blockIdx.y = run of the batch, like poc
   // forms (`round` is nonzero too, with or without discs; `noise` non-null: on top of MC_NOISE as well).  The radius is env->fp.hx
   int rfoot;
   int rfoot_pad;
+  // prediction hypotheses (pocs_set_disc_hypotheses; behind everything else again): non-null = the MC_HYP forms on top of the MC_ROUND
+  // forms (`round` is nonzero too; `noise` non-null: on top of MC_NOISE as well; never `rfoot`): the gates of the records of `env`,
+  // the same at every waypoint.  The waypoint word of the existence draws is 0 at every waypoint: a particle's world keeps its
+  // alternative for the whole roll-out
+  const uint32_t* gates;
 };
 
 
@@ -363,6 +373,13 @@ hipError_t pocs_launch_probe_discs(const pocs_env_dev* env, const pocs_tables* t
 hipError_t pocs_launch_probe_disc_noise(const pocs_env_dev* env, const double* rows, const pocs_tables* tables, unsigned long long seed,
                                         unsigned v, unsigned long long first, int n, const double* x, const double* y, const double* th,
                                         double* centres, unsigned* flags, hipStream_t s);
+// one block; poses n x (x, y, th) by component, pose i has index first + i (first even); env: the D <= 32 disc records alone, grown;
+// rows: their noise rows (zeros: no covariances); gates: their gates; v: the waypoint word of deviations and existence draws alike.
+// exists[i]: bit d = disc d exists for pose i; flags[i]: bit d = pose i touches disc d (the single-pose form; both); exists 0 and
+// flags all ones should the pair form ever disagree with it
+hipError_t pocs_launch_probe_disc_hypotheses(const pocs_env_dev* env, const double* rows, const uint32_t* gates, const pocs_tables* tables,
+                                             unsigned long long seed, unsigned v, unsigned long long first, int n, const double* x,
+                                             const double* y, const double* th, unsigned* exists, unsigned* flags, hipStream_t s);
 // one block; poses n x (x, y, th) by component, pose i has index first + i (first even); env: the composed records (boxes, then discs)
 // prepared for the round footprint of radius env->fp.hx; rows: null, or the records' noise rows.  out[i]: bit 0 = pose i touches some
 // box, bit 1 = some disc, displaced where its row says so (the single-pose form on the full table), bit 8 should the pair form ever

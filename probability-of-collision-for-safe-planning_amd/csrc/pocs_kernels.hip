@@ -58,6 +58,13 @@ hipError_t with_K(const int K, F f) {
 hipError_t pocs_launch_gmm_step(int K, const pocs_gmm_launch& a, hipStream_t s) {
   return with_K(K, [&](auto k) {
     constexpr int KK = decltype(k)::value, TB = POCS_GMM_BLOCK_OF(KK);
+    if (a.gates) {                                     // prediction hypotheses: the _hyp forms on top of the _noise forms
+      if (!a.round || !a.noise || a.rfoot || a.lone || a.obs_counts || a.world || a.tree_parent || a.exchange_in_tail || a.clr || a.parts ||
+          a.regions || a.seg || a.M > POCS_MAX_OBSTACLES || (a.risk && (!a.stop || !a.surv)))
+        return hipErrorInvalidValue;
+      if (a.risk) hipLaunchKernelGGL((k_gmm_step_risk_hyp<KK, TB>), dim3(a.blocks), dim3(TB), 0, s, a);      // (stored or not: the launch's word, read by the kernel)
+      else        hipLaunchKernelGGL((k_gmm_step_hyp<KK, TB>), dim3(a.blocks), dim3(TB), 0, s, a);
+    } else
     if (a.rfoot) {                                     // a round footprint: a family of its own, with and without discs and covariances
       if (a.lone || a.obs_counts || a.world || a.tree_parent || a.exchange_in_tail || a.clr || a.parts || a.regions || a.seg ||
           a.M > POCS_MAX_OBSTACLES || (a.risk && (!a.stop || !a.surv)) || !(a.fp.dx == 0.0 && a.fp.dy == 0.0 && a.fp.hx == a.fp.hy && a.fp.hx >= 0.0))
@@ -259,6 +266,16 @@ hipError_t pocs_launch_mc_tree_step(int nblk, const pocs_mc_launch& a, hipStream
 
 hipError_t pocs_launch_mc_init(int nblk, const pocs_mc_launch& a, hipStream_t s) {
   if ((a.wp_mode != 0 && !a.wp_counts) || (a.obs_counts && !a.wp_mode)) return hipErrorInvalidValue;
+  if (a.gates) {                                      // prediction hypotheses: MC_HYP on top of MC_ROUND, with or without MC_NOISE
+    if (!a.round || a.rfoot || a.world || a.obs_counts || a.clr || a.parts || a.regions || a.seg) return hipErrorInvalidValue;
+    if (a.noise) {
+      if (a.wp_mode) hipLaunchKernelGGL(k_mc_init<MC_COUNTS | MC_ROUND | MC_NOISE | MC_HYP>, dim3(nblk, a.nruns), dim3(POCS_BLOCK), 0, s, a);
+      else           hipLaunchKernelGGL(k_mc_init<MC_PLAIN | MC_ROUND | MC_NOISE | MC_HYP>, dim3(nblk, a.nruns), dim3(POCS_BLOCK), 0, s, a);
+    } else {
+      if (a.wp_mode) hipLaunchKernelGGL(k_mc_init<MC_COUNTS | MC_ROUND | MC_HYP>, dim3(nblk, a.nruns), dim3(POCS_BLOCK), 0, s, a);
+      else           hipLaunchKernelGGL(k_mc_init<MC_PLAIN | MC_ROUND | MC_HYP>, dim3(nblk, a.nruns), dim3(POCS_BLOCK), 0, s, a);
+    }
+  } else
   if (a.rfoot) {                                      // a round footprint: MC_RFOOT on top of MC_ROUND, with or without MC_NOISE
     if (!a.round || a.world || a.obs_counts || a.clr || a.parts || a.regions || a.seg) return hipErrorInvalidValue;
     if (a.noise) {
@@ -307,6 +324,33 @@ hipError_t pocs_launch_mc_init(int nblk, const pocs_mc_launch& a, hipStream_t s)
 hipError_t pocs_launch_mc_step(int nblk, const pocs_mc_launch& a, hipStream_t s) {
   const dim3 grid(nblk, a.nruns), block(POCS_BLOCK);
   if ((a.wp_mode != 0 && !a.wp_counts) || (a.obs_counts && !a.wp_mode)) return hipErrorInvalidValue;
+  if (a.gates) {                                      // prediction hypotheses: the MC_HYP forms of the three modes, with or without MC_NOISE
+    if (!a.round || a.rfoot || a.world || a.obs_counts || a.clr || a.parts || a.regions || a.seg || a.step < 0 || a.step + 1 >= a.W ||
+        (a.wp_mode == 2 && (!a.wp_stop || a.wp_n < 1)))
+      return hipErrorInvalidValue;
+    constexpr int HY = MC_ROUND | MC_HYP, HYN = MC_ROUND | MC_NOISE | MC_HYP;
+    if (a.noise) {
+      if (a.wp_mode == 2) {
+        if (a.nontemporal) hipLaunchKernelGGL((k_mc_step_counts<true, MC_STOP | HYN>), grid, block, 0, s, a);
+        else               hipLaunchKernelGGL((k_mc_step_counts<false, MC_STOP | HYN>), grid, block, 0, s, a);
+      } else if (a.wp_mode == 1) {
+        if (a.nontemporal) hipLaunchKernelGGL((k_mc_step_counts<true, MC_COUNTS | HYN>), grid, block, 0, s, a);
+        else               hipLaunchKernelGGL((k_mc_step_counts<false, MC_COUNTS | HYN>), grid, block, 0, s, a);
+      } else {
+        if (a.nontemporal) hipLaunchKernelGGL((k_mc_step_counts<true, MC_PLAIN | HYN>), grid, block, 0, s, a);
+        else               hipLaunchKernelGGL((k_mc_step_counts<false, MC_PLAIN | HYN>), grid, block, 0, s, a);
+      }
+    } else if (a.wp_mode == 2) {
+      if (a.nontemporal) hipLaunchKernelGGL((k_mc_step_counts<true, MC_STOP | HY>), grid, block, 0, s, a);
+      else               hipLaunchKernelGGL((k_mc_step_counts<false, MC_STOP | HY>), grid, block, 0, s, a);
+    } else if (a.wp_mode == 1) {
+      if (a.nontemporal) hipLaunchKernelGGL((k_mc_step_counts<true, MC_COUNTS | HY>), grid, block, 0, s, a);
+      else               hipLaunchKernelGGL((k_mc_step_counts<false, MC_COUNTS | HY>), grid, block, 0, s, a);
+    } else {
+      if (a.nontemporal) hipLaunchKernelGGL((k_mc_step_counts<true, MC_PLAIN | HY>), grid, block, 0, s, a);
+      else               hipLaunchKernelGGL((k_mc_step_counts<false, MC_PLAIN | HY>), grid, block, 0, s, a);
+    }
+  } else
   if (a.rfoot) {                                      // a round footprint: the MC_RFOOT forms of the three modes, with or without MC_NOISE
     if (!a.round || a.world || a.obs_counts || a.clr || a.parts || a.regions || a.seg || a.step < 0 || a.step + 1 >= a.W ||
         (a.wp_mode == 2 && (!a.wp_stop || a.wp_n < 1)))
@@ -585,6 +629,13 @@ hipError_t pocs_launch_probe_disc_noise(const pocs_env_dev* env, const double* r
                                         double* centres, unsigned* flags, hipStream_t s) {
   if (!env || !rows || !tables || n < 1 || (first & 1ull) || !x || !y || !th || !centres || !flags) return hipErrorInvalidValue;
   hipLaunchKernelGGL(k_probe_disc_noise, dim3(1), dim3(POCS_BLOCK), 0, s, env, rows, tables, seed, v, first, n, x, y, th, centres, flags);
+  return hipGetLastError();
+}
+hipError_t pocs_launch_probe_disc_hypotheses(const pocs_env_dev* env, const double* rows, const uint32_t* gates, const pocs_tables* tables,
+                                             unsigned long long seed, unsigned v, unsigned long long first, int n, const double* x,
+                                             const double* y, const double* th, unsigned* exists, unsigned* flags, hipStream_t s) {
+  if (!env || !rows || !gates || !tables || n < 1 || (first & 1ull) || !x || !y || !th || !exists || !flags) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(k_probe_disc_hypotheses, dim3(1), dim3(POCS_BLOCK), 0, s, env, rows, gates, tables, seed, v, first, n, x, y, th, exists, flags);
   return hipGetLastError();
 }
 hipError_t pocs_launch_probe_footprint_disc(const pocs_env_dev* env, const double* rows, const pocs_tables* tables, unsigned long long seed,

@@ -70,6 +70,7 @@ POCS_HD pocs_u32x4 pocs_philox4x32(uint32_t c0, uint32_t c1, uint32_t c2, uint32
 #define POCS_STREAM_MCINIT 2u  // initial particle cloud                   (MCSimulator.h:287-297)
 #define POCS_STREAM_GMM 3u     // mixture samples                          (GM_Model.h:83-116)
 #define POCS_STREAM_DISC 5u    // an uncertain disc's deviation per pose (pocs_set_disc_covariances; 4 is POCS_STREAM_COUNTS, pocs_model.h)
+#define POCS_STREAM_HYP 6u     // which alternative of a group of discs exists for a pose (pocs_set_disc_hypotheses)
 
 POCS_HD pocs_u32x4 pocs_philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1) {
   return pocs_philox4x32<10>(c0, c1, c2, c3, k0, k1);
@@ -78,7 +79,7 @@ POCS_HD pocs_u32x4 pocs_philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uin
 
 POCS_HD pocs_u32x4 pocs_draw(uint64_t seed, uint64_t index, uint32_t waypoint, uint32_t stream,
                              uint32_t slot) {
-  if (stream == POCS_STREAM_GMM || stream == POCS_STREAM_DISC)      // (a literal at every call site: one of the two is compiled)
+  if (stream == POCS_STREAM_GMM || stream == POCS_STREAM_DISC || stream == POCS_STREAM_HYP)      // (a literal at every call site: one of the two is compiled)
     return pocs_philox4x32<POCS_GMM_PHILOX_ROUNDS>((uint32_t)index, (uint32_t)(index >> 32), waypoint,
                                                    (stream << 16) | slot, (uint32_t)seed, (uint32_t)(seed >> 32));
   return pocs_philox4x32<10>((uint32_t)index, (uint32_t)(index >> 32), waypoint,

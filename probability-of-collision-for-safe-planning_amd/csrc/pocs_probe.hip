@@ -433,4 +433,45 @@ int pocs_probe_device_disc_noise(pocs_ctx* c, const double* fp4, const double* d
   return s.download(flags, flags_out, (size_t)n * sizeof(unsigned));
 }
 
+// Test hook: which discs exist for a pose and which it touches, on the device, for chosen poses, pose indices, footprint, discs,
+// covariances (may be null: none) and hypotheses (include/pocs.h): records, rows and gates as upload_world prepares the context's.
+int pocs_probe_device_disc_hypotheses(pocs_ctx* c, const double* fp4, const double* discs, const double* cov, const int* group,
+                                      const double* weight, int D, uint64_t seed, uint32_t waypoint_word, unsigned long long first, int n,
+                                      const double* poses, unsigned* exists_out, unsigned* flags_out) {
+  static const char E[] = "pocs_probe_device_disc_hypotheses";
+  if (!c) return POCS_E_ARG;
+  if (!fp4 || !discs || !group || !weight || !poses || !exists_out || !flags_out || D < 1 || D > 32 || n < 2 || n > (1 << 20) || (n & 1) ||
+      (first & 1ull) || first > (1ull << 62))
+    return fail(c, POCS_E_ARG, "pocs_probe_device_disc_hypotheses: 1 <= D <= 32, 2 <= n <= 2^20 and even, first even and at most 2^62, no null pointers but the covariances");
+  if (int r = footprint_ok(c, E, fp4)) return r;
+  if (int r = discs_ok(c, E, discs, D)) return r;
+  if (int r = poses_ok(c, E, poses, n)) return r;
+  unsigned long long lo[32], hi[32];
+  int bad = 0;
+  if (const int k = pocs_hyp_thresholds(group, weight, D, lo, hi, &bad))
+    return fail(c, POCS_E_ARG, "pocs_probe_device_disc_hypotheses: disc %d: %s", bad, hyp_refusal(k));
+  pocs_env_dev env;
+  bare_env(&env, pocs_footprint{fp4[0], fp4[1], fp4[2], fp4[3]}, nullptr, 0, nullptr, discs, D, pocs_prepare_disc);
+  std::vector<double> rows(POCS_MAX_OBSTACLES * POCS_NOISE_STRIDE, 0.0);
+  std::vector<uint32_t> gates(POCS_MAX_OBSTACLES * POCS_GATE_STRIDE, 0u);
+  for (int d = 0; d < D; ++d) {
+    if (cov)
+      if (int r = noise_row(c, E, cov + (size_t)d * 3, d, &rows[(size_t)d * POCS_NOISE_STRIDE], &env.obs[(size_t)d * POCS_OBS_STRIDE])) return r;
+    pocs_hyp_gate(group[d], lo[d], hi[d], &gates[(size_t)d * POCS_GATE_STRIDE]);
+  }
+  if (int r = device_with_tables(c)) return r;
+  const std::vector<double> h = pose_columns(poses, n);
+  Scratch s(c);
+  const int p_env = s.add(&env, sizeof env), p_rows = s.add(rows.data(), rows.size() * sizeof(double)),
+            p_gates = s.add(gates.data(), gates.size() * sizeof(uint32_t)), x = s.add(h.data(), h.size() * sizeof(double)),
+            exists = s.zeros((size_t)n * sizeof(unsigned)), flags = s.zeros((size_t)n * sizeof(unsigned));
+  if (int r = s.upload()) return r;
+  const double* d_x = s.at<double>(x);
+  if (int r = s.ran(pocs_launch_probe_disc_hypotheses(s.at<pocs_env_dev>(p_env), s.at<double>(p_rows), s.at<uint32_t>(p_gates), (const pocs_tables*)c->d_tables.p,
+                                                      seed, waypoint_word, first, n, d_x, d_x + n, d_x + 2 * (size_t)n, s.at<unsigned>(exists),
+                                                      s.at<unsigned>(flags), c->stream))) return r;
+  if (int r = s.download(exists, exists_out, (size_t)n * sizeof(unsigned))) return r;
+  return s.download(flags, flags_out, (size_t)n * sizeof(unsigned));
+}
+
 }  // extern "C"

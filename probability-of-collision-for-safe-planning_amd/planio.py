@@ -222,6 +222,41 @@ def prediction_covariances(sigma0, rate, S, D):
     return out
 
 
+def prediction_modes(agents, radius):
+    """A multi-modal prediction as discs with hypotheses (Context.set_discs, Context.set_disc_hypotheses).  `agents`: a list of agents,
+    each a list of (weight, track) alternatives with track of shape S x 2 (the same S everywhere); `radius`: one radius, or one per
+    agent.  Returns (discs S x D x 3, group int32[D], weight float64[D]) with D the number of alternatives of all agents: agent a's
+    alternatives are the discs of one group, named by the index of its first disc.  ValueError for no agent, an agent without
+    alternatives, ragged S, a weight outside (0, 1], a group sum above 1 and any value that is not finite."""
+    agents = [list(a) for a in agents]
+    if not agents or any(not a for a in agents):
+        raise ValueError("at least one agent, each with at least one (weight, track) alternative")
+    radii = np.broadcast_to(np.asarray(radius, dtype=np.float64), (len(agents),)) if np.ndim(radius) <= 1 else None
+    if radii is None or not (np.all(np.isfinite(radii)) and np.all(radii > 0.0)):
+        raise ValueError("a radius is finite and positive, one for all agents or one per agent")
+    cols, group, weight, S = [], [], [], None
+    for a, alts in enumerate(agents):
+        g, total = len(cols), 0.0
+        for w, track in alts:
+            w, t = float(w), np.asarray(track, dtype=np.float64)
+            if t.ndim != 2 or t.shape[1] != 2 or t.shape[0] < 1:
+                raise ValueError("a track is S x 2")
+            S = t.shape[0] if S is None else S
+            if t.shape[0] != S:
+                raise ValueError("ragged tracks: %d steps beside %d" % (t.shape[0], S))
+            if not (np.isfinite(w) and 0.0 < w <= 1.0):
+                raise ValueError("a weight lies in (0, 1]")
+            if not np.all(np.isfinite(t)):
+                raise ValueError("a track is finite")
+            total += w
+            cols.append(np.column_stack([t, np.full(S, radii[a])]))
+            group.append(g)
+            weight.append(w)
+        if total > 1.0:
+            raise ValueError("the weights of agent %d sum to %r, more than 1" % (a, total))
+    return np.stack(cols, axis=1), np.array(group, dtype=np.int32), np.array(weight, dtype=np.float64)
+
+
 def goal_region(plan, half_x, half_y):
     """The goal tolerance of a plan as a watched region (Context.set_regions): the box (cx, cy, half_x, half_y, yaw) centred at
     the plan's last waypoint and turned to its heading.  `plan` is a dict with `traj` (W x 3) or the W x 3 array itself.
