@@ -168,8 +168,8 @@ __device__ __forceinline__ mc_run_start mc_start(const pocs_mc_launch& a) {
 // gate of the launch's gate table is on counts for the particles for which it exists (pocs_pose_collides_gated) -- the existence word
 // drawn for (seed, global particle index first + i, group, word 0): a particle's world keeps its alternative for the whole
 // roll-out.  The gates are read where they lie (wave-uniform addresses); without MC_NOISE no row is read and no log table staged.
-enum { MC_PLAIN = 0, MC_COUNTS = 1, MC_STOP = 2, MC_BOXES = 4, MC_CLEAR = 8, MC_PARTS = 16, MC_REGIONS = 32, MC_SEG = 64, MC_ROUND = 128, MC_NOISE = 256,
-       MC_RFOOT = 512, MC_HYP = 1024 };
+//
+// The bits themselves (enum MC_*): pocs_launch_forms.hpp, where the host chooses a launch's word.
 static_assert(POCS_MAX_OBSTACLES <= 64, "a particle's touched boxes are a 64-bit mask");
 
 // pocs_pose_collides with the touched boxes as a mask (the flag: mask != 0, as the plain form's).

@@ -5,6 +5,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "pocs_collide.h"
+#include "pocs_launch_forms.hpp"   // the MC_* bits of the MC kernels' form word; which kernel a launch record asks for
 #include "pocs_model.h"
 #include "pocs_world.h"
 
@@ -113,6 +114,9 @@ struct pocs_xchg_dev {
 
 // Arrays carry a leading "run" dimension: a launch advances `nruns` independent estimations (the
 // reference's driver performs 200 of them one after the other, MCSimulation.py:238-256) in lockstep.
+// Where a field below says "non-null (nonzero) = the launch is the kernel's _x form", that is its part in a choice made in ONE place,
+// pocs_forms::gmm_step_form / gmm_tree_step_form (pocs_launch_forms.hpp): which of several such words wins, what a form needs and
+// refuses beside it ("never LONE, TREE, ...") and which of its values are checked is that header's rule for the feature, not this text.
 struct pocs_gmm_launch {
   const pocs_run_header* hdr;    // [nruns] per-run seeds
   const pocs_env_dev* env;       // obstacle table (records only; M and the footprint travel below)
@@ -233,6 +237,8 @@ struct pocs_gmm_launch {
 #define POCS_TREE_STOP_INHERITED 0x80000000u
 #define POCS_SYNC_ABORT 1
 
+// "non-null (nonzero) = the MC_X forms" below: the word's part in the choice of pocs_forms::mc_init_form / mc_step_form / mc_fused_form /
+// mc_tree_step_form (pocs_launch_forms.hpp), which hold the precedence, the refusals and the checks as for pocs_gmm_launch.
 struct pocs_mc_launch {               // blockIdx.y = run of the batch, like pocs_gmm_launch
   const pocs_run_header* hdr;          // [nruns]
   const pocs_env_dev* env;
@@ -327,7 +333,8 @@ struct pocs_mc_launch {               // blockIdx.y = run of the batch, like poc
   const uint32_t* gates;
 };
 
-
+// The launches.  hipErrorInvalidValue: the record is refused -- for the launches that choose among kernels (gmm_step, gmm_tree_step,
+// mc_init, mc_step, mc_fused, mc_tree_step) by their chooser in pocs_launch_forms.hpp -- and nothing was launched.
 hipError_t pocs_launch_gmm_step(int K, const pocs_gmm_launch& a, hipStream_t s);              // grid = a.blocks
 hipError_t pocs_launch_world_cull(int K, const pocs_gmm_launch& a, hipStream_t s);            // grid = a.run_cnt: one block per run of the launch
 hipError_t pocs_launch_gmm_advance(int K, const pocs_gmm_launch& a, hipStream_t s);

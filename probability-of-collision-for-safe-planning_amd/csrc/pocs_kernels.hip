@@ -1,7 +1,10 @@
 // pocs_kernels.hip -- hand-written gfx950 (CDNA4, wave64) kernels of the hot path: the ONE unit of the library that holds
 // device code (one gfx950 code object).  The kernels live in its parts, by family, included below in this order; this
 // file keeps what the host runtime calls (pocs_launch_*, pocs_kernels.h, the test hooks' pocs_launch_probe_* among them), k_zero_counts
-// and the bandwidth kernels k_copy and k_fill.
+// and the bandwidth kernels k_copy and k_fill.  A pocs_launch_* that has a choice of kernels -- the GMM sampling launch, the MC path's
+// init, step and fused roll-out, the two tree steps -- does not make it here: it asks its chooser in pocs_launch_forms.hpp (host only;
+// precedence of the features, what each needs, refuses and checks), looks the answer's kernel up in the tables below (gmm_kernel_of,
+// mc_kernel_of: the list of the hot path's instantiations) and launches that.
 //
 //   pocs_dev_prims.hpp    wave sums, table staging, write-through / L1-bypassing / non-temporal accessors, the hand-off
 //                         fences, the diagnostic hooks                                           (relies on nothing)
@@ -48,6 +51,84 @@ hipError_t with_K(const int K, F f) {
     default: return hipErrorInvalidValue;
   }
 }
+
+// From a form (pocs_launch_forms.hpp: the chooser's answer) to its kernel.  The tables below ARE the list of the hot path's
+// instantiations -- an address taken here is what emits one --, and a form that has no entry has no kernel: null, a refusal.
+using gmm_kernel = void (*)(pocs_gmm_launch);
+using mc_kernel = void (*)(pocs_mc_launch);
+namespace pf = pocs_forms;
+static_assert(pf::kMaxGaussians == POCS_MAX_GAUSSIANS && pf::kMaxObstacles == POCS_MAX_OBSTACLES && pf::kMaxClearanceLevels == POCS_MAX_CLEARANCE_LEVELS &&
+              pf::kMaxFootprintParts == POCS_MAX_FOOTPRINT_PARTS && pf::kMaxRegions == POCS_MAX_REGIONS && pf::kMaxWorldRecords == POCS_MAX_WORLD_RECORDS,
+              "the choosers check the library's limits");
+template <int K>
+gmm_kernel gmm_kernel_of(const pf::Form f) {
+  constexpr int TB = POCS_GMM_BLOCK_OF(K);
+  switch (f.fam) {
+#define STORE_LONE(k) case pf::k: { static constexpr gmm_kernel t[] = {k<K, false, TB, false>, k<K, true, TB, false>, k<K, false, TB, true>, k<K, true, TB, true>}; return t[f.store + 2 * f.lone]; }
+#define STORE(k) case pf::k: { static constexpr gmm_kernel t[] = {k<K, false, TB>, k<K, true, TB>}; return t[f.store]; }
+#define RISK(k) case pf::k: { static constexpr gmm_kernel t[] = {k<K, TB, false>, k<K, TB, true>}; return t[f.risk]; }
+    STORE_LONE(k_gmm_step) STORE(k_gmm_step_risk) STORE_LONE(k_gmm_step_boxes) STORE(k_gmm_step_risk_boxes)
+    STORE(k_gmm_step_world) STORE(k_gmm_step_risk_world) STORE(k_gmm_step_clear) STORE(k_gmm_step_risk_clear)
+    STORE(k_gmm_step_regions) STORE(k_gmm_step_risk_regions) STORE(k_gmm_step_parts) STORE(k_gmm_step_risk_parts)
+    STORE(k_gmm_step_seg) STORE(k_gmm_step_risk_seg) STORE(k_gmm_step_round) STORE(k_gmm_step_risk_round)
+    STORE(k_gmm_step_noise) STORE(k_gmm_step_risk_noise) STORE(k_gmm_step_rfoot) STORE(k_gmm_step_risk_rfoot)
+    STORE(k_gmm_step_rfoot_noise) STORE(k_gmm_step_risk_rfoot_noise)
+    RISK(k_gmm_step_tree) RISK(k_gmm_step_tree_boxes)
+    case pf::k_gmm_step_hyp: return k_gmm_step_hyp<K, TB>;                 // (stored or not: the launch's word, read by the kernel)
+    case pf::k_gmm_step_risk_hyp: return k_gmm_step_risk_hyp<K, TB>;
+    default: return nullptr;
+#undef STORE_LONE
+#undef STORE
+#undef RISK
+  }
+}
+// The MC form words that have a kernel: every mode (k_mc_init: the two it has) under each word of FEATURE_WORDS; the counting modes
+// alone, with and without MC_BOXES and (the per-step kernel) MC_SEG; the bare modes under a large world and an obstacle schedule.
+#define FEATURE_WORDS(MODES, X, k)                                                                                                        \
+  MODES(X, k, MC_CLEAR) MODES(X, k, MC_PARTS) MODES(X, k, MC_REGIONS) MODES(X, k, MC_ROUND) MODES(X, k, MC_ROUND | MC_NOISE)                \
+  MODES(X, k, MC_ROUND | MC_RFOOT) MODES(X, k, MC_ROUND | MC_NOISE | MC_RFOOT) MODES(X, k, MC_ROUND | MC_HYP) MODES(X, k, MC_ROUND | MC_NOISE | MC_HYP)
+#define MODES_2(X, k, w) X(k, MC_PLAIN | (w)) X(k, MC_COUNTS | (w))
+#define MODES_3(X, k, w) MODES_2(X, k, w) X(k, MC_STOP | (w))
+#define WORD(k, w) case (w): return k<(w)>;
+#define NT_WORD(k, w) case (w): { static constexpr mc_kernel t[] = {k<false, (w)>, k<true, (w)>}; return t[f.nt]; }
+#define NT(k) case pf::k: { static constexpr mc_kernel t[] = {k<false>, k<true>}; return t[f.nt]; }
+mc_kernel mc_kernel_of(const pf::Form f) {
+  switch (f.fam) {
+    case pf::k_mc_init:
+      switch (f.word) { MODES_2(WORD, k_mc_init, 0) WORD(k_mc_init, MC_COUNTS | MC_BOXES) FEATURE_WORDS(MODES_2, WORD, k_mc_init) default: return nullptr; }
+    case pf::k_mc_init_world:
+      switch (f.word) { MODES_2(WORD, k_mc_init_world, 0) default: return nullptr; }
+    NT(k_mc_step)
+    case pf::k_mc_step_counts:
+      switch (f.word) {
+        NT_WORD(k_mc_step_counts, MC_COUNTS) NT_WORD(k_mc_step_counts, MC_STOP) NT_WORD(k_mc_step_counts, MC_COUNTS | MC_BOXES) NT_WORD(k_mc_step_counts, MC_STOP | MC_BOXES)
+        NT_WORD(k_mc_step_counts, MC_COUNTS | MC_SEG) NT_WORD(k_mc_step_counts, MC_STOP | MC_SEG) FEATURE_WORDS(MODES_3, NT_WORD, k_mc_step_counts)
+        default: return nullptr;
+      }
+    case pf::k_mc_step_world:
+      switch (f.word) { MODES_3(NT_WORD, k_mc_step_world, 0) default: return nullptr; }
+    case pf::k_mc_fused: return k_mc_fused;
+    case pf::k_mc_fused_counts: return k_mc_fused_counts;
+    case pf::k_mc_fused_boxes: return k_mc_fused_boxes;
+    case pf::k_mc_fused_sched:
+      switch (f.word) { MODES_2(WORD, k_mc_fused_sched, 0) WORD(k_mc_fused_sched, MC_COUNTS | MC_BOXES) default: return nullptr; }
+    NT(k_mc_tree_step) NT(k_mc_tree_step_boxes)
+    default: return nullptr;
+  }
+}
+#undef FEATURE_WORDS
+#undef MODES_2
+#undef MODES_3
+#undef WORD
+#undef NT_WORD
+#undef NT
+// The one launch of a chosen kernel.
+template <typename L>
+hipError_t launch_form(void (*const kernel)(L), const dim3 grid, const dim3 block, hipStream_t s, const L& a) {
+  if (!kernel) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(kernel, grid, block, 0, s, a);
+  return hipGetLastError();
+}
 }  // namespace
 
 #ifdef POCS_TUNING
@@ -55,145 +136,13 @@ hipError_t with_K(const int K, F f) {
 #include "pocs_tuning.h"
 #endif
 
+// One waypoint's sampling launch.  Which kernel, and which records are refused: pocs_forms::gmm_step_form.
 hipError_t pocs_launch_gmm_step(int K, const pocs_gmm_launch& a, hipStream_t s) {
+  const pf::Form f = pf::gmm_step_form(K, a);
+  if (!f) return hipErrorInvalidValue;
   return with_K(K, [&](auto k) {
     constexpr int KK = decltype(k)::value, TB = POCS_GMM_BLOCK_OF(KK);
-    if (a.gates) {                                     // prediction hypotheses: the _hyp forms on top of the _noise forms
-      if (!a.round || !a.noise || a.rfoot || a.lone || a.obs_counts || a.world || a.tree_parent || a.exchange_in_tail || a.clr || a.parts ||
-          a.regions || a.seg || a.M > POCS_MAX_OBSTACLES || (a.risk && (!a.stop || !a.surv)))
-        return hipErrorInvalidValue;
-      if (a.risk) hipLaunchKernelGGL((k_gmm_step_risk_hyp<KK, TB>), dim3(a.blocks), dim3(TB), 0, s, a);      // (stored or not: the launch's word, read by the kernel)
-      else        hipLaunchKernelGGL((k_gmm_step_hyp<KK, TB>), dim3(a.blocks), dim3(TB), 0, s, a);
-    } else
-    if (a.rfoot) {                                     // a round footprint: a family of its own, with and without discs and covariances
-      if (a.lone || a.obs_counts || a.world || a.tree_parent || a.exchange_in_tail || a.clr || a.parts || a.regions || a.seg ||
-          a.M > POCS_MAX_OBSTACLES || (a.risk && (!a.stop || !a.surv)) || !(a.fp.dx == 0.0 && a.fp.dy == 0.0 && a.fp.hx == a.fp.hy && a.fp.hx >= 0.0))
-        return hipErrorInvalidValue;
-      if (a.noise) {
-        if (a.risk) {
-          if (a.store) hipLaunchKernelGGL((k_gmm_step_risk_rfoot_noise<KK, true, TB>), dim3(a.blocks), dim3(TB), 0, s, a);
-          else         hipLaunchKernelGGL((k_gmm_step_risk_rfoot_noise<KK, false, TB>), dim3(a.blocks), dim3(TB), 0, s, a);
-        } else {
-          if (a.store) hipLaunchKernelGGL((k_gmm_step_rfoot_noise<KK, true, TB>), dim3(a.blocks), dim3(TB), 0, s, a);
-          else         hipLaunchKernelGGL((k_gmm_step_rfoot_noise<KK, false, TB>), dim3(a.blocks), dim3(TB), 0, s, a);
-        }
-      } else if (a.risk) {
-        if (a.store) hipLaunchKernelGGL((k_gmm_step_risk_rfoot<KK, true, TB>), dim3(a.blocks), dim3(TB), 0, s, a);
-        else         hipLaunchKernelGGL((k_gmm_step_risk_rfoot<KK, false, TB>), dim3(a.blocks), dim3(TB), 0, s, a);
-      } else {
-        if (a.store) hipLaunchKernelGGL((k_gmm_step_rfoot<KK, true, TB>), dim3(a.blocks), dim3(TB), 0, s, a);
-        else         hipLaunchKernelGGL((k_gmm_step_rfoot<KK, false, TB>), dim3(a.blocks), dim3(TB), 0, s, a);
-      }
-    } else
-    if (a.noise) {                                     // uncertain discs: the _noise forms on top of the _round forms
-      if (!a.round || a.lone || a.obs_counts || a.world || a.tree_parent || a.exchange_in_tail || a.clr || a.parts || a.regions || a.seg ||
-          a.M > POCS_MAX_OBSTACLES || (a.risk && (!a.stop || !a.surv)))
-        return hipErrorInvalidValue;
-      if (a.risk) {
-        if (a.store) hipLaunchKernelGGL((k_gmm_step_risk_noise<KK, true, TB>), dim3(a.blocks), dim3(TB), 0, s, a);
-        else         hipLaunchKernelGGL((k_gmm_step_risk_noise<KK, false, TB>), dim3(a.blocks), dim3(TB), 0, s, a);
-      } else {
-        if (a.store) hipLaunchKernelGGL((k_gmm_step_noise<KK, true, TB>), dim3(a.blocks), dim3(TB), 0, s, a);
-        else         hipLaunchKernelGGL((k_gmm_step_noise<KK, false, TB>), dim3(a.blocks), dim3(TB), 0, s, a);
-      }
-    } else
-    if (a.round) {                                     // round obstacles: the ticket forms whose table may hold disc records
-      if (a.lone || a.obs_counts || a.world || a.tree_parent || a.exchange_in_tail || a.clr || a.parts || a.regions || a.seg ||
-          a.M > POCS_MAX_OBSTACLES || (a.risk && (!a.stop || !a.surv)))
-        return hipErrorInvalidValue;
-      if (a.risk) {
-        if (a.store) hipLaunchKernelGGL((k_gmm_step_risk_round<KK, true, TB>), dim3(a.blocks), dim3(TB), 0, s, a);
-        else         hipLaunchKernelGGL((k_gmm_step_risk_round<KK, false, TB>), dim3(a.blocks), dim3(TB), 0, s, a);
-      } else {
-        if (a.store) hipLaunchKernelGGL((k_gmm_step_round<KK, true, TB>), dim3(a.blocks), dim3(TB), 0, s, a);
-        else         hipLaunchKernelGGL((k_gmm_step_round<KK, false, TB>), dim3(a.blocks), dim3(TB), 0, s, a);
-      }
-    } else
-    if (a.seg) {                                       // segment checks: the ticket forms that also test the sub-poses on the way in
-      if (a.lone || a.obs_counts || a.world || a.tree_parent || a.exchange_in_tail || a.clr || a.parts || a.regions || !a.seg_counts || !a.chain ||
-          a.M > POCS_MAX_OBSTACLES || (a.risk && (!a.stop || !a.surv)))
-        return hipErrorInvalidValue;
-      if (a.risk) {
-        if (a.store) hipLaunchKernelGGL((k_gmm_step_risk_seg<KK, true, TB>), dim3(a.blocks), dim3(TB), 0, s, a);
-        else         hipLaunchKernelGGL((k_gmm_step_risk_seg<KK, false, TB>), dim3(a.blocks), dim3(TB), 0, s, a);
-      } else {
-        if (a.store) hipLaunchKernelGGL((k_gmm_step_seg<KK, true, TB>), dim3(a.blocks), dim3(TB), 0, s, a);
-        else         hipLaunchKernelGGL((k_gmm_step_seg<KK, false, TB>), dim3(a.blocks), dim3(TB), 0, s, a);
-      }
-    } else
-    if (a.parts) {                                     // a compound footprint: the ticket forms that test every part
-      if (a.lone || a.obs_counts || a.world || a.tree_parent || a.exchange_in_tail || a.clr || a.parts_F < 2 || a.parts_F > POCS_MAX_FOOTPRINT_PARTS ||
-          a.M > POCS_MAX_OBSTACLES || (a.risk && (!a.stop || !a.surv)))
-        return hipErrorInvalidValue;
-      if (a.risk) {
-        if (a.store) hipLaunchKernelGGL((k_gmm_step_risk_parts<KK, true, TB>), dim3(a.blocks), dim3(TB), 0, s, a);
-        else         hipLaunchKernelGGL((k_gmm_step_risk_parts<KK, false, TB>), dim3(a.blocks), dim3(TB), 0, s, a);
-      } else {
-        if (a.store) hipLaunchKernelGGL((k_gmm_step_parts<KK, true, TB>), dim3(a.blocks), dim3(TB), 0, s, a);
-        else         hipLaunchKernelGGL((k_gmm_step_parts<KK, false, TB>), dim3(a.blocks), dim3(TB), 0, s, a);
-      }
-    } else
-    if (a.regions) {                                   // watched regions: the ticket forms that also count per region
-      if (a.lone || a.obs_counts || a.world || a.tree_parent || a.exchange_in_tail || a.clr || !a.reg_counts || a.reg_G < 1 || a.reg_G > POCS_MAX_REGIONS ||
-          a.M > POCS_MAX_OBSTACLES || (a.risk && (!a.stop || !a.surv)))
-        return hipErrorInvalidValue;
-      if (a.risk) {
-        if (a.store) hipLaunchKernelGGL((k_gmm_step_risk_regions<KK, true, TB>), dim3(a.blocks), dim3(TB), 0, s, a);
-        else         hipLaunchKernelGGL((k_gmm_step_risk_regions<KK, false, TB>), dim3(a.blocks), dim3(TB), 0, s, a);
-      } else {
-        if (a.store) hipLaunchKernelGGL((k_gmm_step_regions<KK, true, TB>), dim3(a.blocks), dim3(TB), 0, s, a);
-        else         hipLaunchKernelGGL((k_gmm_step_regions<KK, false, TB>), dim3(a.blocks), dim3(TB), 0, s, a);
-      }
-    } else
-    if (a.clr) {                                       // clearance levels: the ticket forms that also count per level
-      if (a.lone || a.obs_counts || a.world || a.tree_parent || a.exchange_in_tail || !a.clr_counts || a.clr_L < 1 || a.clr_L > POCS_MAX_CLEARANCE_LEVELS ||
-          a.M > POCS_MAX_OBSTACLES || (a.risk && (!a.stop || !a.surv)))
-        return hipErrorInvalidValue;
-      if (a.risk) {
-        if (a.store) hipLaunchKernelGGL((k_gmm_step_risk_clear<KK, true, TB>), dim3(a.blocks), dim3(TB), 0, s, a);
-        else         hipLaunchKernelGGL((k_gmm_step_risk_clear<KK, false, TB>), dim3(a.blocks), dim3(TB), 0, s, a);
-      } else {
-        if (a.store) hipLaunchKernelGGL((k_gmm_step_clear<KK, true, TB>), dim3(a.blocks), dim3(TB), 0, s, a);
-        else         hipLaunchKernelGGL((k_gmm_step_clear<KK, false, TB>), dim3(a.blocks), dim3(TB), 0, s, a);
-      }
-    } else
-    if (a.world) {                                     // a large world: the ticket forms that fetch what k_world_cull has left
-      if (a.lone || a.obs_counts || a.exchange_in_tail || a.tree_parent || !a.kept || !a.reach || a.M != 0 ||
-          (a.risk && (!a.stop || !a.surv)))
-        return hipErrorInvalidValue;
-      if (a.risk) {
-        if (a.store) hipLaunchKernelGGL((k_gmm_step_risk_world<KK, true, TB>), dim3(a.blocks), dim3(TB), 0, s, a);
-        else         hipLaunchKernelGGL((k_gmm_step_risk_world<KK, false, TB>), dim3(a.blocks), dim3(TB), 0, s, a);
-      } else {
-        if (a.store) hipLaunchKernelGGL((k_gmm_step_world<KK, true, TB>), dim3(a.blocks), dim3(TB), 0, s, a);
-        else         hipLaunchKernelGGL((k_gmm_step_world<KK, false, TB>), dim3(a.blocks), dim3(TB), 0, s, a);
-      }
-    } else
-    if (a.obs_counts) {                                // POCS_OPT_OBSTACLE_COUNTS: the same choice among the counting forms
-      if (a.M > POCS_MAX_OBSTACLES) return hipErrorInvalidValue;
-      if (a.risk) {
-        if (a.lone || a.exchange_in_tail || !a.stop || !a.surv) return hipErrorInvalidValue;
-        if (a.store) hipLaunchKernelGGL((k_gmm_step_risk_boxes<KK, true, TB>), dim3(a.blocks), dim3(TB), 0, s, a);
-        else         hipLaunchKernelGGL((k_gmm_step_risk_boxes<KK, false, TB>), dim3(a.blocks), dim3(TB), 0, s, a);
-      } else if (a.lone) {
-        if (a.store) hipLaunchKernelGGL((k_gmm_step_boxes<KK, true, TB, true>), dim3(a.blocks), dim3(TB), 0, s, a);
-        else         hipLaunchKernelGGL((k_gmm_step_boxes<KK, false, TB, true>), dim3(a.blocks), dim3(TB), 0, s, a);
-      } else {
-        if (a.store) hipLaunchKernelGGL((k_gmm_step_boxes<KK, true, TB, false>), dim3(a.blocks), dim3(TB), 0, s, a);
-        else         hipLaunchKernelGGL((k_gmm_step_boxes<KK, false, TB, false>), dim3(a.blocks), dim3(TB), 0, s, a);
-      }
-    } else if (a.risk) {
-      if (a.lone || a.exchange_in_tail || !a.stop || !a.surv) return hipErrorInvalidValue;
-      if (a.store) hipLaunchKernelGGL((k_gmm_step_risk<KK, true, TB>), dim3(a.blocks), dim3(TB), 0, s, a);
-      else         hipLaunchKernelGGL((k_gmm_step_risk<KK, false, TB>), dim3(a.blocks), dim3(TB), 0, s, a);
-    } else if (a.lone) {
-      if (a.store) hipLaunchKernelGGL((k_gmm_step<KK, true, TB, true>), dim3(a.blocks), dim3(TB), 0, s, a);
-      else         hipLaunchKernelGGL((k_gmm_step<KK, false, TB, true>), dim3(a.blocks), dim3(TB), 0, s, a);
-    } else {
-      if (a.store) hipLaunchKernelGGL((k_gmm_step<KK, true, TB, false>), dim3(a.blocks), dim3(TB), 0, s, a);
-      else         hipLaunchKernelGGL((k_gmm_step<KK, false, TB, false>), dim3(a.blocks), dim3(TB), 0, s, a);
-    }
-    return hipGetLastError();
+    return launch_form(gmm_kernel_of<KK>(f), dim3(a.blocks), dim3(TB), s, a);
   });
 }
 // The cull of a large world in front of a waypoint's sampling launch: one block per run of the launch's run range.
@@ -227,17 +176,11 @@ hipError_t pocs_launch_gmm_advance(int K, const pocs_gmm_launch& a, hipStream_t 
 // one per node: the launch must address them with W = 1 (TREE, gmm_step_block), and nothing may ask its closers for more than
 // the node's sums (no advance, no exchange, no stored samples).
 hipError_t pocs_launch_gmm_tree_step(int K, const pocs_gmm_launch& a, hipStream_t s) {
-  if (a.W != 1 || !a.tree_parent || a.lone || a.store || a.advance_in_tail || a.exchange_in_tail || a.run_cnt < 1 || a.run_cnt > 256 ||
-      a.run_lo < 0 || a.run_lo + a.run_cnt > a.nruns || (a.risk && (!a.stop || !a.surv)))
-    return hipErrorInvalidValue;
+  const pf::Form f = pf::gmm_tree_step_form(K, a);
+  if (!f) return hipErrorInvalidValue;
   return with_K(K, [&](auto k) {
     constexpr int KK = decltype(k)::value, TB = POCS_GMM_BLOCK_OF(KK);
-    if (a.obs_counts) {
-      if (a.risk) hipLaunchKernelGGL((k_gmm_step_tree_boxes<KK, TB, true>), dim3(a.blocks), dim3(TB), 0, s, a);
-      else        hipLaunchKernelGGL((k_gmm_step_tree_boxes<KK, TB, false>), dim3(a.blocks), dim3(TB), 0, s, a);
-    } else if (a.risk) hipLaunchKernelGGL((k_gmm_step_tree<KK, TB, true>), dim3(a.blocks), dim3(TB), 0, s, a);
-    else               hipLaunchKernelGGL((k_gmm_step_tree<KK, TB, false>), dim3(a.blocks), dim3(TB), 0, s, a);
-    return hipGetLastError();
+    return launch_form(gmm_kernel_of<KK>(f), dim3(a.blocks), dim3(TB), s, a);
   });
 }
 // ... and the launch that builds the level's mixtures ahead of it: one block per node, grid = a.run_cnt.
@@ -251,272 +194,22 @@ hipError_t pocs_launch_gmm_tree_advance(int K, const pocs_gmm_launch& a, hipStre
 }
 // One level of a tree of plans on the MC path: grid (nblk, a.nruns), a.nruns = the launch's nodes, slots tree_lo ...
 hipError_t pocs_launch_mc_tree_step(int nblk, const pocs_mc_launch& a, hipStream_t s) {
-  if (a.world) return hipErrorInvalidValue;
-  if (!a.tree_parent || !a.tree_sx || !a.tree_sy || !a.tree_sth || !a.tree_shits || !a.wp_counts || !a.total || a.nruns < 1 || a.nruns > 256 ||
-      a.tree_dst_lo < 1 || a.tree_lo < a.tree_dst_lo || a.tree_src_lo < 0 || a.tree_src_lo >= a.tree_dst_lo || a.tree_sx == a.x)
-    return hipErrorInvalidValue;
-  const dim3 grid(nblk, a.nruns), block(POCS_BLOCK);
-  if (a.obs_counts) {
-    if (a.nontemporal) hipLaunchKernelGGL(k_mc_tree_step_boxes<true>, grid, block, 0, s, a);
-    else               hipLaunchKernelGGL(k_mc_tree_step_boxes<false>, grid, block, 0, s, a);
-  } else if (a.nontemporal) hipLaunchKernelGGL(k_mc_tree_step<true>, grid, block, 0, s, a);
-  else                      hipLaunchKernelGGL(k_mc_tree_step<false>, grid, block, 0, s, a);
-  return hipGetLastError();
+  const pf::Form f = pf::mc_tree_step_form(a);
+  return f ? launch_form(mc_kernel_of(f), dim3(nblk, a.nruns), dim3(POCS_BLOCK), s, a) : hipErrorInvalidValue;
 }
 
+// The MC path's launches, all on grid (nblk, a.nruns): the initial cloud, one control, the fused roll-out (pocs_forms::mc_*_form).
 hipError_t pocs_launch_mc_init(int nblk, const pocs_mc_launch& a, hipStream_t s) {
-  if ((a.wp_mode != 0 && !a.wp_counts) || (a.obs_counts && !a.wp_mode)) return hipErrorInvalidValue;
-  if (a.gates) {                                      // prediction hypotheses: MC_HYP on top of MC_ROUND, with or without MC_NOISE
-    if (!a.round || a.rfoot || a.world || a.obs_counts || a.clr || a.parts || a.regions || a.seg) return hipErrorInvalidValue;
-    if (a.noise) {
-      if (a.wp_mode) hipLaunchKernelGGL(k_mc_init<MC_COUNTS | MC_ROUND | MC_NOISE | MC_HYP>, dim3(nblk, a.nruns), dim3(POCS_BLOCK), 0, s, a);
-      else           hipLaunchKernelGGL(k_mc_init<MC_PLAIN | MC_ROUND | MC_NOISE | MC_HYP>, dim3(nblk, a.nruns), dim3(POCS_BLOCK), 0, s, a);
-    } else {
-      if (a.wp_mode) hipLaunchKernelGGL(k_mc_init<MC_COUNTS | MC_ROUND | MC_HYP>, dim3(nblk, a.nruns), dim3(POCS_BLOCK), 0, s, a);
-      else           hipLaunchKernelGGL(k_mc_init<MC_PLAIN | MC_ROUND | MC_HYP>, dim3(nblk, a.nruns), dim3(POCS_BLOCK), 0, s, a);
-    }
-  } else
-  if (a.rfoot) {                                      // a round footprint: MC_RFOOT on top of MC_ROUND, with or without MC_NOISE
-    if (!a.round || a.world || a.obs_counts || a.clr || a.parts || a.regions || a.seg) return hipErrorInvalidValue;
-    if (a.noise) {
-      if (a.wp_mode) hipLaunchKernelGGL(k_mc_init<MC_COUNTS | MC_ROUND | MC_NOISE | MC_RFOOT>, dim3(nblk, a.nruns), dim3(POCS_BLOCK), 0, s, a);
-      else           hipLaunchKernelGGL(k_mc_init<MC_PLAIN | MC_ROUND | MC_NOISE | MC_RFOOT>, dim3(nblk, a.nruns), dim3(POCS_BLOCK), 0, s, a);
-    } else {
-      if (a.wp_mode) hipLaunchKernelGGL(k_mc_init<MC_COUNTS | MC_ROUND | MC_RFOOT>, dim3(nblk, a.nruns), dim3(POCS_BLOCK), 0, s, a);
-      else           hipLaunchKernelGGL(k_mc_init<MC_PLAIN | MC_ROUND | MC_RFOOT>, dim3(nblk, a.nruns), dim3(POCS_BLOCK), 0, s, a);
-    }
-  } else
-  if (a.noise) {                                      // uncertain discs: the MC_NOISE forms on top of the MC_ROUND forms
-    if (!a.round || a.world || a.obs_counts || a.clr || a.parts || a.regions || a.seg) return hipErrorInvalidValue;
-    if (a.wp_mode) hipLaunchKernelGGL(k_mc_init<MC_COUNTS | MC_ROUND | MC_NOISE>, dim3(nblk, a.nruns), dim3(POCS_BLOCK), 0, s, a);
-    else           hipLaunchKernelGGL(k_mc_init<MC_PLAIN | MC_ROUND | MC_NOISE>, dim3(nblk, a.nruns), dim3(POCS_BLOCK), 0, s, a);
-  } else
-  if (a.round) {                                      // round obstacles: the MC_ROUND forms (a small world, no counts per box, level or region, one footprint box)
-    if (a.world || a.obs_counts || a.clr || a.parts || a.regions || a.seg) return hipErrorInvalidValue;
-    if (a.wp_mode) hipLaunchKernelGGL(k_mc_init<MC_COUNTS | MC_ROUND>, dim3(nblk, a.nruns), dim3(POCS_BLOCK), 0, s, a);
-    else           hipLaunchKernelGGL(k_mc_init<MC_PLAIN | MC_ROUND>, dim3(nblk, a.nruns), dim3(POCS_BLOCK), 0, s, a);
-  } else
-  if (a.parts) {                                      // a compound footprint: the MC_PARTS forms (a small world, no per-box counts, no levels)
-    if (a.world || a.obs_counts || a.clr || a.parts_F < 2 || a.parts_F > POCS_MAX_FOOTPRINT_PARTS) return hipErrorInvalidValue;
-    if (a.wp_mode) hipLaunchKernelGGL(k_mc_init<MC_COUNTS | MC_PARTS>, dim3(nblk, a.nruns), dim3(POCS_BLOCK), 0, s, a);
-    else           hipLaunchKernelGGL(k_mc_init<MC_PLAIN | MC_PARTS>, dim3(nblk, a.nruns), dim3(POCS_BLOCK), 0, s, a);
-  } else
-  if (a.regions) {                                    // watched regions: the MC_REGIONS forms (a small world, no per-box counts, levels or parts)
-    if (a.world || a.obs_counts || a.clr || !a.reg_counts || a.reg_G < 1 || a.reg_G > POCS_MAX_REGIONS) return hipErrorInvalidValue;
-    if (a.wp_mode) hipLaunchKernelGGL(k_mc_init<MC_COUNTS | MC_REGIONS>, dim3(nblk, a.nruns), dim3(POCS_BLOCK), 0, s, a);
-    else           hipLaunchKernelGGL(k_mc_init<MC_PLAIN | MC_REGIONS>, dim3(nblk, a.nruns), dim3(POCS_BLOCK), 0, s, a);
-  } else
-  if (a.clr) {                                        // clearance levels: the MC_CLEAR forms (a small world, no per-box counts)
-    if (a.world || a.obs_counts || !a.clr_counts || !a.clr_level || a.clr_L < 1 || a.clr_L > POCS_MAX_CLEARANCE_LEVELS) return hipErrorInvalidValue;
-    if (a.wp_mode) hipLaunchKernelGGL(k_mc_init<MC_COUNTS | MC_CLEAR>, dim3(nblk, a.nruns), dim3(POCS_BLOCK), 0, s, a);
-    else           hipLaunchKernelGGL(k_mc_init<MC_PLAIN | MC_CLEAR>, dim3(nblk, a.nruns), dim3(POCS_BLOCK), 0, s, a);
-  } else
-  if (a.world) {                                      // a large world (no per-box counts there)
-    if (a.obs_counts || a.world_M < 1 || a.world_M > POCS_MAX_WORLD_RECORDS) return hipErrorInvalidValue;
-    if (a.wp_mode) hipLaunchKernelGGL(k_mc_init_world<MC_COUNTS>, dim3(nblk, a.nruns), dim3(POCS_BLOCK), 0, s, a);
-    else           hipLaunchKernelGGL(k_mc_init_world<MC_PLAIN>, dim3(nblk, a.nruns), dim3(POCS_BLOCK), 0, s, a);
-  } else
-  if (a.obs_counts) hipLaunchKernelGGL(k_mc_init<MC_COUNTS | MC_BOXES>, dim3(nblk, a.nruns), dim3(POCS_BLOCK), 0, s, a);
-  else if (a.wp_mode) hipLaunchKernelGGL(k_mc_init<MC_COUNTS>, dim3(nblk, a.nruns), dim3(POCS_BLOCK), 0, s, a);
-  else           hipLaunchKernelGGL(k_mc_init<MC_PLAIN>, dim3(nblk, a.nruns), dim3(POCS_BLOCK), 0, s, a);
-  return hipGetLastError();
+  const pf::Form f = pf::mc_init_form(a);
+  return f ? launch_form(mc_kernel_of(f), dim3(nblk, a.nruns), dim3(POCS_BLOCK), s, a) : hipErrorInvalidValue;
 }
 hipError_t pocs_launch_mc_step(int nblk, const pocs_mc_launch& a, hipStream_t s) {
-  const dim3 grid(nblk, a.nruns), block(POCS_BLOCK);
-  if ((a.wp_mode != 0 && !a.wp_counts) || (a.obs_counts && !a.wp_mode)) return hipErrorInvalidValue;
-  if (a.gates) {                                      // prediction hypotheses: the MC_HYP forms of the three modes, with or without MC_NOISE
-    if (!a.round || a.rfoot || a.world || a.obs_counts || a.clr || a.parts || a.regions || a.seg || a.step < 0 || a.step + 1 >= a.W ||
-        (a.wp_mode == 2 && (!a.wp_stop || a.wp_n < 1)))
-      return hipErrorInvalidValue;
-    constexpr int HY = MC_ROUND | MC_HYP, HYN = MC_ROUND | MC_NOISE | MC_HYP;
-    if (a.noise) {
-      if (a.wp_mode == 2) {
-        if (a.nontemporal) hipLaunchKernelGGL((k_mc_step_counts<true, MC_STOP | HYN>), grid, block, 0, s, a);
-        else               hipLaunchKernelGGL((k_mc_step_counts<false, MC_STOP | HYN>), grid, block, 0, s, a);
-      } else if (a.wp_mode == 1) {
-        if (a.nontemporal) hipLaunchKernelGGL((k_mc_step_counts<true, MC_COUNTS | HYN>), grid, block, 0, s, a);
-        else               hipLaunchKernelGGL((k_mc_step_counts<false, MC_COUNTS | HYN>), grid, block, 0, s, a);
-      } else {
-        if (a.nontemporal) hipLaunchKernelGGL((k_mc_step_counts<true, MC_PLAIN | HYN>), grid, block, 0, s, a);
-        else               hipLaunchKernelGGL((k_mc_step_counts<false, MC_PLAIN | HYN>), grid, block, 0, s, a);
-      }
-    } else if (a.wp_mode == 2) {
-      if (a.nontemporal) hipLaunchKernelGGL((k_mc_step_counts<true, MC_STOP | HY>), grid, block, 0, s, a);
-      else               hipLaunchKernelGGL((k_mc_step_counts<false, MC_STOP | HY>), grid, block, 0, s, a);
-    } else if (a.wp_mode == 1) {
-      if (a.nontemporal) hipLaunchKernelGGL((k_mc_step_counts<true, MC_COUNTS | HY>), grid, block, 0, s, a);
-      else               hipLaunchKernelGGL((k_mc_step_counts<false, MC_COUNTS | HY>), grid, block, 0, s, a);
-    } else {
-      if (a.nontemporal) hipLaunchKernelGGL((k_mc_step_counts<true, MC_PLAIN | HY>), grid, block, 0, s, a);
-      else               hipLaunchKernelGGL((k_mc_step_counts<false, MC_PLAIN | HY>), grid, block, 0, s, a);
-    }
-  } else
-  if (a.rfoot) {                                      // a round footprint: the MC_RFOOT forms of the three modes, with or without MC_NOISE
-    if (!a.round || a.world || a.obs_counts || a.clr || a.parts || a.regions || a.seg || a.step < 0 || a.step + 1 >= a.W ||
-        (a.wp_mode == 2 && (!a.wp_stop || a.wp_n < 1)))
-      return hipErrorInvalidValue;
-    constexpr int RF = MC_ROUND | MC_RFOOT, RFN = MC_ROUND | MC_NOISE | MC_RFOOT;
-    if (a.noise) {
-      if (a.wp_mode == 2) {
-        if (a.nontemporal) hipLaunchKernelGGL((k_mc_step_counts<true, MC_STOP | RFN>), grid, block, 0, s, a);
-        else               hipLaunchKernelGGL((k_mc_step_counts<false, MC_STOP | RFN>), grid, block, 0, s, a);
-      } else if (a.wp_mode == 1) {
-        if (a.nontemporal) hipLaunchKernelGGL((k_mc_step_counts<true, MC_COUNTS | RFN>), grid, block, 0, s, a);
-        else               hipLaunchKernelGGL((k_mc_step_counts<false, MC_COUNTS | RFN>), grid, block, 0, s, a);
-      } else {
-        if (a.nontemporal) hipLaunchKernelGGL((k_mc_step_counts<true, MC_PLAIN | RFN>), grid, block, 0, s, a);
-        else               hipLaunchKernelGGL((k_mc_step_counts<false, MC_PLAIN | RFN>), grid, block, 0, s, a);
-      }
-    } else if (a.wp_mode == 2) {
-      if (a.nontemporal) hipLaunchKernelGGL((k_mc_step_counts<true, MC_STOP | RF>), grid, block, 0, s, a);
-      else               hipLaunchKernelGGL((k_mc_step_counts<false, MC_STOP | RF>), grid, block, 0, s, a);
-    } else if (a.wp_mode == 1) {
-      if (a.nontemporal) hipLaunchKernelGGL((k_mc_step_counts<true, MC_COUNTS | RF>), grid, block, 0, s, a);
-      else               hipLaunchKernelGGL((k_mc_step_counts<false, MC_COUNTS | RF>), grid, block, 0, s, a);
-    } else {
-      if (a.nontemporal) hipLaunchKernelGGL((k_mc_step_counts<true, MC_PLAIN | RF>), grid, block, 0, s, a);
-      else               hipLaunchKernelGGL((k_mc_step_counts<false, MC_PLAIN | RF>), grid, block, 0, s, a);
-    }
-  } else
-  if (a.noise) {                                      // uncertain discs: the MC_NOISE forms of the three modes
-    if (!a.round || a.world || a.obs_counts || a.clr || a.parts || a.regions || a.seg || a.step < 0 || a.step + 1 >= a.W ||
-        (a.wp_mode == 2 && (!a.wp_stop || a.wp_n < 1)))
-      return hipErrorInvalidValue;
-    if (a.wp_mode == 2) {
-      if (a.nontemporal) hipLaunchKernelGGL((k_mc_step_counts<true, MC_STOP | MC_ROUND | MC_NOISE>), grid, block, 0, s, a);
-      else               hipLaunchKernelGGL((k_mc_step_counts<false, MC_STOP | MC_ROUND | MC_NOISE>), grid, block, 0, s, a);
-    } else if (a.wp_mode == 1) {
-      if (a.nontemporal) hipLaunchKernelGGL((k_mc_step_counts<true, MC_COUNTS | MC_ROUND | MC_NOISE>), grid, block, 0, s, a);
-      else               hipLaunchKernelGGL((k_mc_step_counts<false, MC_COUNTS | MC_ROUND | MC_NOISE>), grid, block, 0, s, a);
-    } else {
-      if (a.nontemporal) hipLaunchKernelGGL((k_mc_step_counts<true, MC_PLAIN | MC_ROUND | MC_NOISE>), grid, block, 0, s, a);
-      else               hipLaunchKernelGGL((k_mc_step_counts<false, MC_PLAIN | MC_ROUND | MC_NOISE>), grid, block, 0, s, a);
-    }
-  } else
-  if (a.round) {                                      // round obstacles: the MC_ROUND forms of the three modes
-    if (a.world || a.obs_counts || a.clr || a.parts || a.regions || a.seg || a.step < 0 || a.step + 1 >= a.W ||
-        (a.wp_mode == 2 && (!a.wp_stop || a.wp_n < 1)))
-      return hipErrorInvalidValue;
-    if (a.wp_mode == 2) {
-      if (a.nontemporal) hipLaunchKernelGGL((k_mc_step_counts<true, MC_STOP | MC_ROUND>), grid, block, 0, s, a);
-      else               hipLaunchKernelGGL((k_mc_step_counts<false, MC_STOP | MC_ROUND>), grid, block, 0, s, a);
-    } else if (a.wp_mode == 1) {
-      if (a.nontemporal) hipLaunchKernelGGL((k_mc_step_counts<true, MC_COUNTS | MC_ROUND>), grid, block, 0, s, a);
-      else               hipLaunchKernelGGL((k_mc_step_counts<false, MC_COUNTS | MC_ROUND>), grid, block, 0, s, a);
-    } else {
-      if (a.nontemporal) hipLaunchKernelGGL((k_mc_step_counts<true, MC_PLAIN | MC_ROUND>), grid, block, 0, s, a);
-      else               hipLaunchKernelGGL((k_mc_step_counts<false, MC_PLAIN | MC_ROUND>), grid, block, 0, s, a);
-    }
-  } else
-  if (a.seg) {                                        // segment checks: the MC_SEG forms of the two counting modes
-    if (a.world || a.obs_counts || a.clr || a.parts || a.regions || !a.seg_counts || a.wp_mode == 0 || a.step < 0 || a.step + 1 >= a.W ||
-        (a.wp_mode == 2 && (!a.wp_stop || a.wp_n < 1)))
-      return hipErrorInvalidValue;
-    if (a.wp_mode == 2) {
-      if (a.nontemporal) hipLaunchKernelGGL((k_mc_step_counts<true, MC_STOP | MC_SEG>), grid, block, 0, s, a);
-      else               hipLaunchKernelGGL((k_mc_step_counts<false, MC_STOP | MC_SEG>), grid, block, 0, s, a);
-    } else {
-      if (a.nontemporal) hipLaunchKernelGGL((k_mc_step_counts<true, MC_COUNTS | MC_SEG>), grid, block, 0, s, a);
-      else               hipLaunchKernelGGL((k_mc_step_counts<false, MC_COUNTS | MC_SEG>), grid, block, 0, s, a);
-    }
-  } else
-  if (a.parts) {                                      // a compound footprint: the MC_PARTS forms of the three modes
-    if (a.world || a.obs_counts || a.clr || a.parts_F < 2 || a.parts_F > POCS_MAX_FOOTPRINT_PARTS || a.step < 0 || a.step + 1 >= a.W ||
-        (a.wp_mode == 2 && (!a.wp_stop || a.wp_n < 1)))
-      return hipErrorInvalidValue;
-    if (a.wp_mode == 2) {
-      if (a.nontemporal) hipLaunchKernelGGL((k_mc_step_counts<true, MC_STOP | MC_PARTS>), grid, block, 0, s, a);
-      else               hipLaunchKernelGGL((k_mc_step_counts<false, MC_STOP | MC_PARTS>), grid, block, 0, s, a);
-    } else if (a.wp_mode == 1) {
-      if (a.nontemporal) hipLaunchKernelGGL((k_mc_step_counts<true, MC_COUNTS | MC_PARTS>), grid, block, 0, s, a);
-      else               hipLaunchKernelGGL((k_mc_step_counts<false, MC_COUNTS | MC_PARTS>), grid, block, 0, s, a);
-    } else {
-      if (a.nontemporal) hipLaunchKernelGGL((k_mc_step_counts<true, MC_PLAIN | MC_PARTS>), grid, block, 0, s, a);
-      else               hipLaunchKernelGGL((k_mc_step_counts<false, MC_PLAIN | MC_PARTS>), grid, block, 0, s, a);
-    }
-  } else
-  if (a.regions) {                                    // watched regions: the MC_REGIONS forms of the three modes
-    if (a.world || a.obs_counts || a.clr || !a.reg_counts || a.reg_G < 1 || a.reg_G > POCS_MAX_REGIONS || a.step < 0 || a.step + 1 >= a.W ||
-        (a.wp_mode == 2 && (!a.wp_stop || a.wp_n < 1)))
-      return hipErrorInvalidValue;
-    if (a.wp_mode == 2) {
-      if (a.nontemporal) hipLaunchKernelGGL((k_mc_step_counts<true, MC_STOP | MC_REGIONS>), grid, block, 0, s, a);
-      else               hipLaunchKernelGGL((k_mc_step_counts<false, MC_STOP | MC_REGIONS>), grid, block, 0, s, a);
-    } else if (a.wp_mode == 1) {
-      if (a.nontemporal) hipLaunchKernelGGL((k_mc_step_counts<true, MC_COUNTS | MC_REGIONS>), grid, block, 0, s, a);
-      else               hipLaunchKernelGGL((k_mc_step_counts<false, MC_COUNTS | MC_REGIONS>), grid, block, 0, s, a);
-    } else {
-      if (a.nontemporal) hipLaunchKernelGGL((k_mc_step_counts<true, MC_PLAIN | MC_REGIONS>), grid, block, 0, s, a);
-      else               hipLaunchKernelGGL((k_mc_step_counts<false, MC_PLAIN | MC_REGIONS>), grid, block, 0, s, a);
-    }
-  } else
-  if (a.clr) {                                        // clearance levels: the MC_CLEAR forms of the three modes
-    if (a.world || a.obs_counts || !a.clr_counts || !a.clr_level || a.clr_L < 1 || a.clr_L > POCS_MAX_CLEARANCE_LEVELS || a.step < 0 || a.step + 1 >= a.W ||
-        (a.wp_mode == 2 && (!a.wp_stop || a.wp_n < 1)))
-      return hipErrorInvalidValue;
-    if (a.wp_mode == 2) {
-      if (a.nontemporal) hipLaunchKernelGGL((k_mc_step_counts<true, MC_STOP | MC_CLEAR>), grid, block, 0, s, a);
-      else               hipLaunchKernelGGL((k_mc_step_counts<false, MC_STOP | MC_CLEAR>), grid, block, 0, s, a);
-    } else if (a.wp_mode == 1) {
-      if (a.nontemporal) hipLaunchKernelGGL((k_mc_step_counts<true, MC_COUNTS | MC_CLEAR>), grid, block, 0, s, a);
-      else               hipLaunchKernelGGL((k_mc_step_counts<false, MC_COUNTS | MC_CLEAR>), grid, block, 0, s, a);
-    } else {
-      if (a.nontemporal) hipLaunchKernelGGL((k_mc_step_counts<true, MC_PLAIN | MC_CLEAR>), grid, block, 0, s, a);
-      else               hipLaunchKernelGGL((k_mc_step_counts<false, MC_PLAIN | MC_CLEAR>), grid, block, 0, s, a);
-    }
-  } else
-  if (a.world) {                                      // a large world: the same three modes, no per-box counts
-    if (a.obs_counts || a.world_M < 1 || a.world_M > POCS_MAX_WORLD_RECORDS) return hipErrorInvalidValue;
-    if (a.wp_mode != 0 && (a.step < 0 || a.step + 1 >= a.W || (a.wp_mode == 2 && (!a.wp_stop || a.wp_n < 1)))) return hipErrorInvalidValue;
-    if (a.wp_mode == 2) {
-      if (a.nontemporal) hipLaunchKernelGGL((k_mc_step_world<true, MC_STOP>), grid, block, 0, s, a);
-      else               hipLaunchKernelGGL((k_mc_step_world<false, MC_STOP>), grid, block, 0, s, a);
-    } else if (a.wp_mode == 1) {
-      if (a.nontemporal) hipLaunchKernelGGL((k_mc_step_world<true, MC_COUNTS>), grid, block, 0, s, a);
-      else               hipLaunchKernelGGL((k_mc_step_world<false, MC_COUNTS>), grid, block, 0, s, a);
-    } else {
-      if (a.nontemporal) hipLaunchKernelGGL((k_mc_step_world<true, MC_PLAIN>), grid, block, 0, s, a);
-      else               hipLaunchKernelGGL((k_mc_step_world<false, MC_PLAIN>), grid, block, 0, s, a);
-    }
-  } else
-  if (a.obs_counts) {                                 // ... and per obstacle box: the MC_BOXES forms of the two below
-    if (a.step < 0 || a.step + 1 >= a.W || (a.wp_mode == 2 && (!a.wp_stop || a.wp_n < 1))) return hipErrorInvalidValue;
-    if (a.wp_mode == 2) {
-      if (a.nontemporal) hipLaunchKernelGGL((k_mc_step_counts<true, MC_STOP | MC_BOXES>), grid, block, 0, s, a);
-      else               hipLaunchKernelGGL((k_mc_step_counts<false, MC_STOP | MC_BOXES>), grid, block, 0, s, a);
-    } else {
-      if (a.nontemporal) hipLaunchKernelGGL((k_mc_step_counts<true, MC_COUNTS | MC_BOXES>), grid, block, 0, s, a);
-      else               hipLaunchKernelGGL((k_mc_step_counts<false, MC_COUNTS | MC_BOXES>), grid, block, 0, s, a);
-    }
-  } else if (a.wp_mode == 2) {                               // first collisions per waypoint, and the risk bound obeyed
-    if (!a.wp_stop || a.wp_n < 1 || a.step < 0 || a.step + 1 >= a.W) return hipErrorInvalidValue;
-    if (a.nontemporal) hipLaunchKernelGGL((k_mc_step_counts<true, MC_STOP>), grid, block, 0, s, a);
-    else               hipLaunchKernelGGL((k_mc_step_counts<false, MC_STOP>), grid, block, 0, s, a);
-  } else if (a.wp_mode == 1) {                        // first collisions per waypoint
-    if (a.step < 0 || a.step + 1 >= a.W) return hipErrorInvalidValue;
-    if (a.nontemporal) hipLaunchKernelGGL((k_mc_step_counts<true, MC_COUNTS>), grid, block, 0, s, a);
-    else               hipLaunchKernelGGL((k_mc_step_counts<false, MC_COUNTS>), grid, block, 0, s, a);
-  } else if (a.nontemporal) hipLaunchKernelGGL(k_mc_step<true>, grid, block, 0, s, a);
-  else                      hipLaunchKernelGGL(k_mc_step<false>, grid, block, 0, s, a);
-  return hipGetLastError();
+  const pf::Form f = pf::mc_step_form(a);
+  return f ? launch_form(mc_kernel_of(f), dim3(nblk, a.nruns), dim3(POCS_BLOCK), s, a) : hipErrorInvalidValue;
 }
 hipError_t pocs_launch_mc_fused(int nblk, const pocs_mc_launch& a, hipStream_t s) {
-  if (a.wp_mode == 2 || (a.wp_mode != 0 && !a.wp_counts) || (a.obs_counts && !a.wp_mode)) return hipErrorInvalidValue;      // (no stop without a launch boundary per step)
-  if (a.clr) return hipErrorInvalidValue;             // (clearance levels: the per-step form)
-  if (a.parts) return hipErrorInvalidValue;           // (a compound footprint: the per-step form)
-  if (a.regions) return hipErrorInvalidValue;         // (watched regions: the per-step form)
-  if (a.seg) return hipErrorInvalidValue;             // (segment checks: the per-step form)
-  if (a.round) return hipErrorInvalidValue;           // (round obstacles: the per-step form)
-  if (a.world) return hipErrorInvalidValue;           // (a large world is not staged: no fused form)
-  if (a.obs_counts) {
-    if (a.env_steps > 1) hipLaunchKernelGGL(k_mc_fused_sched<MC_COUNTS | MC_BOXES>, dim3(nblk, a.nruns), dim3(POCS_BLOCK), 0, s, a);
-    else                 hipLaunchKernelGGL(k_mc_fused_boxes, dim3(nblk, a.nruns), dim3(POCS_BLOCK), 0, s, a);
-  } else if (a.env_steps > 1) {                              // an obstacle schedule: the world is restaged per step
-    if (a.wp_mode) hipLaunchKernelGGL(k_mc_fused_sched<MC_COUNTS>, dim3(nblk, a.nruns), dim3(POCS_BLOCK), 0, s, a);
-    else           hipLaunchKernelGGL(k_mc_fused_sched<MC_PLAIN>, dim3(nblk, a.nruns), dim3(POCS_BLOCK), 0, s, a);
-  } else if (a.wp_mode) hipLaunchKernelGGL(k_mc_fused_counts, dim3(nblk, a.nruns), dim3(POCS_BLOCK), 0, s, a);
-  else                  hipLaunchKernelGGL(k_mc_fused, dim3(nblk, a.nruns), dim3(POCS_BLOCK), 0, s, a);
-  return hipGetLastError();
+  const pf::Form f = pf::mc_fused_form(a);
+  return f ? launch_form(mc_kernel_of(f), dim3(nblk, a.nruns), dim3(POCS_BLOCK), s, a) : hipErrorInvalidValue;
 }
 hipError_t pocs_launch_mc_count(int nblk, const pocs_mc_launch& a, hipStream_t s) {
   hipLaunchKernelGGL(k_mc_count, dim3(nblk, a.nruns), dim3(POCS_BLOCK), 0, s, a);
